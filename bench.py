@@ -11,9 +11,14 @@ One "step" = one hrt_render_launch of the whole frame at the configured spp (BAS
 the frame is split into interleaved 8-row stripes (one tile per GPU, BVH replicated) and each step
 ends with the RCCL reduce of the per-tile radiance into rank 0's frame.
 
-Prints ONE JSON line on rank 0 with the metric, a `roofline` object for the dominant kernel
-(closest-hit traversal; algorithmic bytes per ray x rays / HIP-event time) and a `cpu_baseline`
-object (the CPU oracle, OpenMP, on a bounded sample of the same workload).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the metric
+(`value` Mrays/s, `ms_per_step`, the workload and the per-kernel HIP-event times of the timed steps).
+`--full` adds what takes runs of its own: a `roofline` object for the dominant kernel (closest-hit
+traversal; algorithmic bytes per ray x rays / HIP-event time, from an extra counting pass), the rates
+on the other builders' trees, the primary-ray reuse figures, and a `cpu_baseline` object (the CPU
+oracle, OpenMP, on a bounded sample of the same workload) with the GPU's `parity` on that sample.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's colour buffer) as
+DIR/color.npy, float32, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -37,14 +42,21 @@ RAY_BYTES, HIT_BYTES, NODE_BYTES, PRIM_BYTES = 32, 20, 80, 48      # DESIGN.md "
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C4", choices=["C1", "C2", "C3", "C4", "C5"])
     ap.add_argument("--spp", type=int, default=0, help="override the config's samples per pixel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-builder", action="store_true", help="skip the short run on the other builder's tree (config.alt_builder)")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="target CPU time of the baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the other builders' trees, the primary-ray reuse and the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and its parity check")
+    ap.add_argument("--no-alt-builder", action="store_true", help="(--full) skip the short runs on the other builders' trees and the primary-ray reuse")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="(--full) target CPU time of the baseline sample")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launcher_argv(gpus, env, argv, port=None):
@@ -212,6 +224,80 @@ def cpu_baseline(hrt, scene, target_seconds, renderer=None):
     return base, parity
 
 
+def roofline(hrt, st, sc, args, world):
+    """The `roofline` object (--full): the dominant kernel's algorithmic bytes over its HIP-event time in the timed steps (`st`), with the
+    per-ray node / primitive counts of the extra counting pass (`sc`)."""
+    nodes_per_ray = sc.node_visits_closest / max(sc.rays_closest, 1)
+    prims_per_ray = sc.prim_tests_closest / max(sc.rays_closest, 1)
+    bytes_per_ray = RAY_BYTES + NODE_BYTES * nodes_per_ray + PRIM_BYTES * prims_per_ray + HIT_BYTES
+    any_nodes = (sc.node_visits - sc.node_visits_closest) / max(sc.rays_any, 1)
+    any_prims = (sc.prim_tests - sc.prim_tests_closest) / max(sc.rays_any, 1)
+    bytes_per_any_ray = RAY_BYTES + NODE_BYTES * any_nodes + PRIM_BYTES * any_prims + HIT_BYTES
+    fused = st.kernel_launches[hrt.K_PATHS] > 0
+    if fused:
+        # fused path mode: ONE launch per step renders every sample of every pixel; rays live in registers, so
+        # the algorithmic traffic is the BVH bytes a ray has to read (no ray / hit records)
+        trav_ms = st.kernel_ms[hrt.K_PATHS]
+        trav_launches = max(int(st.kernel_launches[hrt.K_PATHS]), 1)
+        b_closest = NODE_BYTES * nodes_per_ray + PRIM_BYTES * prims_per_ray
+        b_any = NODE_BYTES * any_nodes + PRIM_BYTES * any_prims
+        which = os.environ.get("HRT_FUSED", "1")
+        kernel_name = {"2": "k_traverse<FUSED> (round 1's persistent path kernel)"}.get(
+            which, "k_fused (persistent path kernel: generate + traverse + shade + accumulate)")
+    else:
+        # wavefront mode: every traverse launch of the timed region (closest-hit rays and the depth-5 any-hit rays)
+        trav_ms = st.kernel_ms[hrt.K_TRAVERSE] + st.kernel_ms[hrt.K_TRAVERSE_ANY]
+        trav_launches = max(int(st.kernel_launches[hrt.K_TRAVERSE] + st.kernel_launches[hrt.K_TRAVERSE_ANY]), 1)
+        b_closest, b_any = bytes_per_ray, bytes_per_any_ray
+        kernel_name = "k_traverse"
+    avg_launch_ms = trav_ms / trav_launches
+    rays_per_launch = st.rays / trav_launches
+    bytes_per_launch = (b_closest * st.rays_closest + b_any * st.rays_any) / trav_launches
+    achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+    # memory-side traffic and the instruction-issue view come from the PMC passes committed for THIS workload (tools/profile_final.sh:
+    # separate --pmc runs, which cannot share a process with the timed region).  They are only quoted when the file was taken on
+    # the build that is running (lib/BUILD_ID = hash of the kernel sources); otherwise they are null and marked stale.
+    traffic = traffic_source = issue = None
+    if args.config == "C4" and world == 1 and fused and args.spp == 0:
+        traffic, traffic_source, issue = profile_fields(ROOT / "profiles", build_id())
+    # What bounds the kernel is INSTRUCTION ISSUE (`bound`, `issue_frac`, `useful_lane_frac`: DESIGN.md section 4.1), not memory:
+    # the tree of this scene is resident in L2 / Infinity Cache.  `achieved` / `peak` / `frac` stay the contract's figure
+    # (SURVEY 8d: ALGORITHMIC bytes -- 80 B per node visit + 48 B per primitive test -- over the launch time over the HBM
+    # peak; repeated as `algorithmic_frac`), `traffic` / `measured_frac` are what reached the fabric.
+    return {"bound": "instruction-issue", "kernel": kernel_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "algorithmic_frac": round(achieved / HBM_PEAK_GBS, 4),
+            "issue_frac": issue.get("issue_frac") if issue else None,
+            "useful_lane_frac": issue.get("useful_lane_frac") if issue else None,
+            "issue": issue,
+            "traffic": traffic, "traffic_source": traffic_source,
+            "measured_frac": round(traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_launch_ms > 0 else None,
+            "note": "frac is algorithmic bytes over the HBM peak, served mostly by L2 / Infinity Cache (tree resident); the kernel is issue-bound",
+            "bytes_per_ray": round(b_closest, 1), "nodes_per_ray": round(nodes_per_ray, 3),
+            "prims_per_ray": round(prims_per_ray, 3), "bytes_per_any_hit_ray": round(b_any, 1),
+            "bytes_per_launch": round(bytes_per_launch, 0), "avg_launch_ms": round(avg_launch_ms, 4),
+            "rays_per_launch": round(rays_per_launch, 1), "launches": trav_launches}
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes each float32 / float64 array as out_dir/<name>.npy.  Outputs that would together exceed `budget` bytes keep a fixed
+    subset of their rows (every k-th, from row 0), the same in every run of the same arguments.  Returns {name: {shape, rows_kept_every}}."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    stride = max(1, -(-total // budget))
+    written = {}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"bench.py: output {name} is {a.dtype}, not float32 / float64")
+        kept = np.ascontiguousarray(a[::stride])
+        np.save(out_dir / f"{name}.npy", kept)
+        written[name] = {"shape": list(a.shape), "rows_kept_every": stride}
+    return written
+
+
 def main():
     args = parse()
     child = launcher_argv(args.gpus, os.environ, sys.argv[1:])
@@ -322,46 +408,20 @@ def main():
     if ranks_seen != args.gpus:
         raise SystemExit(f"bench.py: {ranks_seen} ranks took part in the all_reduce, --gpus says {args.gpus}")
 
-    # ---- per-ray node / primitive counts (canonical walk order): one extra untimed pass ----
-    r.set_flags(hrt.CTX_COUNT)
-    r.reset_stats()
-    r.render(2, tile=tile, sync=True)
-    sc = r.stats()
-    nodes_per_ray = sc.node_visits_closest / max(sc.rays_closest, 1)
-    prims_per_ray = sc.prim_tests_closest / max(sc.rays_closest, 1)
-    bytes_per_ray = RAY_BYTES + NODE_BYTES * nodes_per_ray + PRIM_BYTES * prims_per_ray + HIT_BYTES
-    any_nodes = (sc.node_visits - sc.node_visits_closest) / max(sc.rays_any, 1)
-    any_prims = (sc.prim_tests - sc.prim_tests_closest) / max(sc.rays_any, 1)
-    bytes_per_any_ray = RAY_BYTES + NODE_BYTES * any_nodes + PRIM_BYTES * any_prims + HIT_BYTES
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the colour buffer as the last timed step left it (N > 1: the reduced frame)
+        dumped = dump_outputs(args.dump_outputs, {"color": r.color.cpu().numpy()})
+        print(f"bench.py: wrote {dumped} under {args.dump_outputs}", file=sys.stderr, flush=True)
+
+    sc = None
+    if args.full:
+        # ---- per-ray node / primitive counts (canonical walk order): one extra untimed pass ----
+        r.set_flags(hrt.CTX_COUNT)
+        r.reset_stats()
+        r.render(2, tile=tile, sync=True)
+        sc = r.stats()
 
     if rank == 0:
-        fused = st.kernel_launches[hrt.K_PATHS] > 0
-        if fused:
-            # fused path mode: ONE launch per step renders every sample of every pixel; rays live in registers, so
-            # the algorithmic traffic is the BVH bytes a ray has to read (no ray / hit records)
-            trav_ms = st.kernel_ms[hrt.K_PATHS]
-            trav_launches = max(int(st.kernel_launches[hrt.K_PATHS]), 1)
-            b_closest = NODE_BYTES * nodes_per_ray + PRIM_BYTES * prims_per_ray
-            b_any = NODE_BYTES * any_nodes + PRIM_BYTES * any_prims
-            which = os.environ.get("HRT_FUSED", "1")
-            kernel_name = {"2": "k_traverse<FUSED> (round 1's persistent path kernel)"}.get(
-                which, "k_fused (persistent path kernel: generate + traverse + shade + accumulate)")
-        else:
-            # wavefront mode: every traverse launch of the timed region (closest-hit rays and the depth-5 any-hit rays)
-            trav_ms = st.kernel_ms[hrt.K_TRAVERSE] + st.kernel_ms[hrt.K_TRAVERSE_ANY]
-            trav_launches = max(int(st.kernel_launches[hrt.K_TRAVERSE] + st.kernel_launches[hrt.K_TRAVERSE_ANY]), 1)
-            b_closest, b_any = bytes_per_ray, bytes_per_any_ray
-            kernel_name = "k_traverse"
-        avg_launch_ms = trav_ms / trav_launches
-        rays_per_launch = st.rays / trav_launches
-        bytes_per_launch = (b_closest * st.rays_closest + b_any * st.rays_any) / trav_launches
-        achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
-        # memory-side traffic and the instruction-issue view come from the PMC passes committed for THIS workload (tools/profile_final.sh:
-        # separate --pmc runs, which cannot share a process with the timed region).  They are only quoted when the file was taken on
-        # the build that is running (lib/BUILD_ID = hash of the kernel sources); otherwise they are null and marked stale.
-        traffic = traffic_source = issue = None
-        if args.config == "C4" and world == 1 and fused and args.spp == 0:
-            traffic, traffic_source, issue = profile_fields(ROOT / "profiles", build_id())
         out = {
             "metric": "Mrays/s at 1920x1080, 1M-tri scene",
             "value": round(total_rays / elapsed / 1e6, 3),
@@ -380,25 +440,11 @@ def main():
                        "rays_per_step": int(total_rays / max(args.steps, 1)), "rays_per_path": round(st.rays / max(st.paths, 1), 4),
                        "bvh_nodes": int(st.bvh_nodes), "bvh_bytes": int(st.bvh_bytes), "bvh_build_s": round(build_s, 3),
                        "bvh_builder": LABEL_PLOC if device_build else LABEL_SPLIT[split_on_device]},
-            # What bounds the kernel is INSTRUCTION ISSUE (`bound`, `issue_frac`, `useful_lane_frac`: DESIGN.md section 4.1), not memory:
-            # the tree of this scene is resident in L2 / Infinity Cache.  `achieved` / `peak` / `frac` stay the contract's figure
-            # (ALGORITHMIC bytes -- 80 B per node visit + 48 B per primitive test -- over the launch time over the HBM
-            # peak; repeated as `algorithmic_frac`), `traffic` / `measured_frac` are what reached the fabric.
-            "roofline": {"bound": "instruction-issue", "kernel": kernel_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "algorithmic_frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "issue_frac": issue.get("issue_frac") if issue else None,
-                         "useful_lane_frac": issue.get("useful_lane_frac") if issue else None,
-                         "issue": issue,
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "measured_frac": round(traffic / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_launch_ms > 0 else None,
-                         "note": "frac is algorithmic bytes over the HBM peak, served mostly by L2 / Infinity Cache (tree resident); the kernel is issue-bound",
-                         "bytes_per_ray": round(b_closest, 1), "nodes_per_ray": round(nodes_per_ray, 3),
-                         "prims_per_ray": round(prims_per_ray, 3), "bytes_per_any_hit_ray": round(b_any, 1),
-                         "bytes_per_launch": round(bytes_per_launch, 0), "avg_launch_ms": round(avg_launch_ms, 4),
-                         "rays_per_launch": round(rays_per_launch, 1), "launches": trav_launches},
-            "kernel_ms": {hrt.KERNEL_NAMES[k]: round(st.kernel_ms[k], 3) for k in range(hrt.K_COUNT)},
         }
-        if world == 1 and not args.no_alt_builder:
+        if args.full:
+            out["roofline"] = roofline(hrt, st, sc, args, world)
+        out["kernel_ms"] = {hrt.KERNEL_NAMES[k]: round(st.kernel_ms[k], 3) for k in range(hrt.K_COUNT)}
+        if args.full and world == 1 and not args.no_alt_builder:
             # the same frame on the trees of the OTHER builders (a context each; a few steps are enough for a rate)
             # (label, context flag, environment for the context's creation)
             alts = [(LABEL_PLOC, 0, {})] if not device_build else [(LABEL_SPLIT[split_on_device], hrt.CTX_FAST_TRACE, {})]
@@ -432,7 +478,7 @@ def main():
                 out["config"]["alt_builders"].append({"bvh_builder": label, "value": round(sa.rays / alt_dt / 1e6, 3), "unit": "Mrays/s", "steps": alt_steps,
                                                       "bvh_nodes": int(sa.bvh_nodes), "bvh_build_s": round(alt_build_s, 3)})
                 alt.close()
-        if world == 1 and not args.no_alt_builder:
+        if args.full and world == 1 and not args.no_alt_builder:
             # the same frame with HRT_CTX_REUSE_PRIMARY (include/hrt.h): a pixel's primary ray is traversed once per launch instead of
             # once per sample -- the same image bit for bit in less time.  Its rays are the TRAVERSED ones only (a third fewer), so
             # its Mrays/s is not this line's `value` and is not printed: the gain is the step time.
@@ -456,7 +502,7 @@ def main():
             out["config"]["primary_reuse"] = {"flag": "HRT_CTX_REUSE_PRIMARY (off for `value`)", "steps": reuse_steps, "ms_per_step": round(reuse_dt / reuse_steps * 1e3, 3),
                                               "ms_per_step_without": out["ms_per_step"], "traversed_rays_per_step": int(sr.rays // reuse_steps),
                                               "paths_per_step": int(sr.paths // reuse_steps), "image_bit_identical_at_8spp": same}
-        if not args.no_cpu_baseline and world == 1:             # the CPU leg is timed at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:             # the CPU leg is timed at N = 1 only
             r.set_flags(0)                                      # production kernels for the parity render
             out["cpu_baseline"], out["parity"] = cpu_baseline(hrt, scene, args.cpu_seconds, r)
         print(json.dumps(out), flush=True)

@@ -82,3 +82,32 @@ def test_profile_figures_are_quoted_only_for_the_running_build(bench, tmp_path):
     root = ROOT / "profiles"
     newest = sorted(root.glob("r*_pmc_fused_kernel.json"))[-1]
     assert json.loads(newest.read_text())["provenance"]["build"]
+
+
+def test_plain_run_options(bench, monkeypatch):
+    """A plain run is the headline only: --full (roofline, other builders, CPU baseline) and --dump-outputs are off unless asked for,
+    and --steps is the number of timed steps, at least one."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and args.full is False and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(bench, tmp_path):
+    import numpy as np
+    color = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    info = bench.dump_outputs(tmp_path / "all", {"color": color})
+    got = np.load(tmp_path / "all" / "color.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, color)
+    assert info == {"color": {"shape": [6, 5, 4], "rows_kept_every": 1}}
+    # over the budget: a fixed subset of the rows (every k-th from row 0), the same in every run
+    info = bench.dump_outputs(tmp_path / "part", {"color": color}, budget=color.nbytes // 2)
+    got = np.load(tmp_path / "part" / "color.npy")
+    assert got.nbytes <= color.nbytes // 2 and np.array_equal(got, color[::2]) and info["color"]["rows_kept_every"] == 2
+    with pytest.raises(TypeError):
+        bench.dump_outputs(tmp_path / "ints", {"ids": np.zeros(3, np.int32)})

@@ -275,21 +275,23 @@ def test_tiles_partition_the_frame(hrt):
     assert max(sizes) - min(sizes) <= 8
 
 
-def test_hand_issued_loads_are_not_touched_before_their_wait():
+def test_hand_issued_loads_are_not_touched_before_their_wait(tmp_path):
     """The traversal kernels issue their node / primitive loads from inline asm and retire them with hand-counted
     s_waitcnt: between the two the compiler must not read, copy or spill the destination registers (it does not know they
     are in flight).  tools/audit_asm_loads.py compiles kernels.hip, fused.hip and fused_queue.hip to assembly with the Makefile's own flags
     and checks every instantiation; any compiler or flag change that breaks the invariant fails here."""
+    import os
     import subprocess
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "tools" / "audit_asm_loads.py")], capture_output=True, text=True)
+    env = dict(os.environ, TMPDIR=str(tmp_path))                   # (the assembly is written to the test's own directory)
+    r = subprocess.run([sys.executable, str(root / "tools" / "audit_asm_loads.py")], capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 hazardous instructions" in r.stdout and "hazardous instructions" in r.stdout
 
 
-def test_path_kernel_hot_loop_keeps_its_instruction_budget():
+def test_path_kernel_hot_loop_keeps_its_instruction_budget(tmp_path):
     """k_fused is bound by instruction issue: its traversal loop is 470 instructions for triangles-only
     scenes -- 171 of the single-pipe kind -- with no scratch access, at 4 waves per SIMD (<= 128 VGPRs).  tools/loop_stats.py
     compiles fused.hip with the Makefile's flags and counts; a compiler, flag or source change that fattens the loop, spills inside
@@ -300,14 +302,14 @@ def test_path_kernel_hot_loop_keeps_its_instruction_budget():
     root = Path(__file__).resolve().parent.parent
     sys.path.insert(0, str(root / "tools"))
     import loop_stats
-    found = {name: (cs, ops) for name, cs, ops in loop_stats.loops("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused")}
+    found = {name: (cs, ops) for name, cs, ops in loop_stats.loops("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused", asm=tmp_path / "fused.s")}
     tri = [v for k, v in found.items() if "ILb0ELb0ELb0E" in k]          # <HAS_SPHERES = false, INSTANCED = false, REUSE = false>: C4's kernel
     assert len(found) == 8 and len(tri) == 1, sorted(found)
     cs, ops = tri[0]
     assert sum(cs.values()) <= 480, dict(cs)
     assert cs["valu_complex"] <= 175 and cs["salu"] <= 110, dict(cs)
     assert not any(op.startswith("scratch_") or op.startswith("buffer_") for op in ops), sorted(ops)
-    text = Path("/tmp/hrt_loops_fused.s").read_text()
+    text = (tmp_path / "fused.s").read_text()
     # 4 waves per SIMD (<= 128 VGPRs) for the one-level kernels; the INSTANCED instantiations are compiled for 3 (<= 168)
     counts = sorted(int(v) for v in re.findall(r"\.vgpr_count:\s+(\d+)", text))
     assert len(counts) == 8 and counts[3] <= 128 and counts[7] <= 168, counts
@@ -337,9 +339,9 @@ def test_context_flags_of_the_binding_are_the_headers(hrt):
         assert value & (value - 1) == 0, name
 
 
-def test_tools_compile():
+def test_tools_compile(tmp_path):
     """The measurement and stress scripts under tools/ are run by hand on the GPU box: at least they parse."""
     import py_compile
     from pathlib import Path
     for path in sorted((Path(__file__).resolve().parent.parent / "tools").glob("*.py")):
-        py_compile.compile(str(path), doraise=True, cfile=f"/tmp/hrt_pyc_{path.stem}.pyc")
+        py_compile.compile(str(path), doraise=True, cfile=str(tmp_path / f"{path.stem}.pyc"))

@@ -7,7 +7,7 @@ destinations of a group of loads before the wait that covers it (expected: none)
 assembly, which for these loops (issue at the top of the body, waits further down the same body) is the order of execution.
 Run by tests/test_host_cpu.py; exit status 1 when anything is found.
 Usage: tools/audit_asm_loads.py [-v]"""
-import re, subprocess, sys
+import re, subprocess, sys, tempfile
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -22,7 +22,7 @@ def makefile_hipflags():
 
 
 def audit(source, kernel_prefix, verbose=False):
-    asm = f"/tmp/hrt_audit_{Path(source).stem}.s"
+    asm = str(Path(tempfile.gettempdir()) / f"hrt_audit_{Path(source).stem}.s")
     flags = [f for f in makefile_hipflags() if f != "-fPIC"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", asm, source], cwd=ROOT, stderr=subprocess.DEVNULL)
     text = open(asm).read()

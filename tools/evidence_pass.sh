@@ -16,5 +16,5 @@ echo tiles done
 echo refit done
 timeout -k 10 600 tools/bench_other_configs.sh > $O/r04_bench_other_configs.txt 2>&1 || exit 1
 echo configs done
-timeout -k 10 400 python3 bench.py > $O/r04_bench_c4_256spp.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/r04_bench_c4_256spp.json 2> $O/bench.err || exit 1
 echo bench done

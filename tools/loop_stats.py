@@ -4,7 +4,7 @@ instantiation, from the assembly the Makefile's flags produce: VALU split into t
 kinds of profiles/r02_valu_pipes_microbench.txt, SALU, memory.  The SIMD issues about one instruction of ANY kind per 2.4 cycles
 (profiles/r02_valu_issue_patterns_microbench.txt), so the total is what a loop iteration costs.
 Usage: tools/loop_stats.py [substring of the mangled kernel name ...]"""
-import re, subprocess, sys
+import re, subprocess, sys, tempfile
 from collections import Counter
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -14,8 +14,9 @@ SIMPLE = {"v_fma_f32", "v_add_f32", "v_mul_f32", "v_sub_f32", "v_subrev_f32", "v
           "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_mov_b32", "v_mov_b64", "v_cndmask_b32", "v_not_b32"}
 
 
-def loops(source, prefix):
-    asm = f"/tmp/hrt_loops_{Path(source).stem}.s"
+def loops(source, prefix, asm=None):
+    """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields its loops."""
+    asm = str(asm or Path(tempfile.gettempdir()) / f"hrt_loops_{Path(source).stem}.s")
     flags = [f for f in makefile_hipflags() if f != "-fPIC"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", asm, source], cwd=ROOT, stderr=subprocess.DEVNULL)
     text = open(asm).read()

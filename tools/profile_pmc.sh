@@ -4,7 +4,7 @@
 # Usage: tools/profile_pmc.sh <outdir> [bench args...]
 set -u
 OUT=${1:-gpurun_out/pmc}; shift || true
-ARGS=${*:-"--steps 1 --warmup 0 --spp 2 --no-cpu-baseline"}
+ARGS=${*:-"--full --steps 1 --warmup 0 --spp 2 --no-cpu-baseline"}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {

@@ -2,7 +2,7 @@
 # Second PMC battery: L2 / fabric / busy counters for the traverse kernel.
 set -u
 OUT=${1:-gpurun_out/pmc3}; shift || true
-ARGS=${*:-"--steps 1 --warmup 0 --spp 2 --no-cpu-baseline"}
+ARGS=${*:-"--full --steps 1 --warmup 0 --spp 2 --no-cpu-baseline"}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {

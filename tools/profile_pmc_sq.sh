@@ -3,7 +3,7 @@
 # Usage: tools/profile_pmc_sq.sh <outdir> [bench args...]     (environment knobs such as HRT_FUSED are inherited)
 set -u
 OUT=${1:-gpurun_out/pmc_sq}; shift || true
-ARGS=${*:-"--steps 1 --warmup 0 --spp 8 --no-cpu-baseline"}
+ARGS=${*:-"--full --steps 1 --warmup 0 --spp 8 --no-cpu-baseline"}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {

@@ -7,7 +7,7 @@ OUT=$1; shift
 ARGS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done
 shift
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 1 --warmup 0 --spp 16 --no-cpu-baseline)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 1 --warmup 0 --spp 16 --no-cpu-baseline)
 export TMPDIR=/tmp
 : > "$OUT"
 combos=("")

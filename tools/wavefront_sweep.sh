@@ -3,7 +3,7 @@
 # Usage: tools/wavefront_sweep.sh <outdir>
 OUT=${1:-gpurun_out/wavefront}; mkdir -p $OUT
 for cfg in "1 0" "1 1" "0 0" "0 1"; do set -- $cfg
-  HRT_FUSED=0 HRT_WAVEFRONT_LEAN=$1 HRT_WAVEFRONT_GRAPH=$2 HRT_BENCH_NO_TIMING=1 python3 bench.py --steps 3 --warmup 1 --spp 16 --no-alt-builder --cpu-seconds 6 > $OUT/wf_$1_$2.json 2> $OUT/wf_$1_$2.err
+  HRT_FUSED=0 HRT_WAVEFRONT_LEAN=$1 HRT_WAVEFRONT_GRAPH=$2 HRT_BENCH_NO_TIMING=1 python3 bench.py --full --steps 3 --warmup 1 --spp 16 --no-alt-builder --cpu-seconds 6 > $OUT/wf_$1_$2.json 2> $OUT/wf_$1_$2.err
   python3 -c "
 import json
 try:
