@@ -76,6 +76,8 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
     const char *__restrict__ prim_bytes = reinterpret_cast<const char *>(a.prims);
     const float tmin = a.tmin, tmax_ray = a.tmax;
     const uint32_t leaf_hold = a.leaf_hold >= 1 && a.leaf_hold <= 4 ? (uint32_t)a.leaf_hold : 4u;      // (a lane that could never take a node would never finish)
+    // the traversal loop ends once at least refill_threshold lanes are idle -- or all of them: at most max_alive lanes alive
+    const uint32_t max_alive = (uint32_t)a.refill_threshold >= 64u ? 0u : 64u - (uint32_t)a.refill_threshold;
     const uint32_t tx = threadIdx.x;
     const uint32_t ldsn = (uint32_t)reinterpret_cast<uintptr_t>(&s_nodes[0][tx]), ldsl = (uint32_t)reinterpret_cast<uintptr_t>(&s_leaves[0][tx]);
 
@@ -328,16 +330,20 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
     #ifdef HRT_LANE_STATS
                 { ++ls_iter; ls_alive += __popcll(__ballot(alive)); ls_node += __popcll(mask_n0); ls_prim += __popcll(mask_p); ls_ppass += mask_p != 0ull; }
     #endif
-                // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight) ----
+                // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight).  Triangles:
+                //      every lane tests (straight-line arithmetic, no loads) and a lane without a primitive rejects whatever its
+                //      registers hold -- some lane nearly always has one, so a per-lane branch would save nothing but cost a mask
+                //      save, a branch and a restore.  Spheres read the instance table: only lanes with a primitive test. ----
                 bool hit_any = false, improved = false;
                 if (mask_p != 0ull) {
                     wait_prim_loads(rpa, rpb, rpc);
-                    if (L.pidx != kNoWork) {
-                        const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
-                                     pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
-                        improved = test_prim<HAS_SPHERES, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
-                        hit_any = any && improved;
-                    }
+                    const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
+                                 pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
+                    if constexpr (!HAS_SPHERES)
+                        improved = test_prim<false, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, L.pidx != kNoWork);
+                    else if (L.pidx != kNoWork)
+                        improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
+                    hit_any = any & improved;
                 }
                 if (kTail && !INSTANCED && a.tail_split) {
                     // pieces of split rays publish their improvements one lane at a time (rare: a few per ray) ...
@@ -365,13 +371,14 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
                         }
                     }
                 }
-                // ---- A. node step ----
+                // ---- A. node step: one-level trees, for the whole wave (arithmetic only; what lanes without a node made of their
+                //      registers is not filed: mask_n0 below) ----
                 uint2 child = make_uint2(0u, 0u), tri = make_uint2(0u, 0u);
                 __builtin_amdgcn_s_setprio(HRT_PRIO_NODE);
                 wait_node_loads(rn0, rn1, rn2, rn3, rn4);
                 [[maybe_unused]] bool enter = false;
                 if constexpr (!INSTANCED) {
-                    if (L.nidx != kNoWork && !hit_any) lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+                    lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
                 } else {
                     enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
                     if (L.nidx != kNoWork && !hit_any && !enter) lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
@@ -421,21 +428,25 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
                 //      primitive per lane, skipped while few lanes have leaf work and none depends on it); the primitive and the node of
                 //      the next iteration; finished? ----
                 __builtin_amdgcn_s_setprio(HRT_PRIO_BOOK);
-                bool done = false;
                 // an any-hit ray is done with its first accepted intersection: nothing more to fetch (what is left on its stacks is
                 // dropped when the lane's next ray starts, lean_start)
-                if (hit_any) { L.nidx = kNoWork; L.pidx = kNoWork; done = true; }
+                if (hit_any) { L.nidx = kNoWork; L.pidx = kNoWork; }
+                // the sequence runs for the lanes that are alive and not finished by an any-hit, and files the groups of those that
+                // made a node step (nidx is still what it was at the loads for them)
+                const uint64_t book = __ballot(alive) & ~__ballot(hit_any);
+                uint64_t fin;
                 [[maybe_unused]] uint32_t lane = 0u;
                 if constexpr (!INSTANCED) {
-                    if (alive && !done) done = lean_bookkeeping_asm(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold) != 0u;
+                    fin = lean_bookkeeping_masked(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0);
                 } else {
                     // (this instantiation is two registers over its budget and the compiler's choice of what to keep in scratch is the two
                     // stack addresses, reloaded here in every iteration: they are a constant plus eight times the lane number -- two
                     // instructions to make again)
                     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
                     const uint32_t ldsn_i = (uint32_t)reinterpret_cast<uintptr_t>(&s_nodes[0][0]) + 8u * lane, ldsl_i = (uint32_t)reinterpret_cast<uintptr_t>(&s_leaves[0][0]) + 8u * lane;
-                    if (alive && !done) done = lean_bookkeeping_asm(L, child, tri, ldsn_i, ldsl_i, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold) != 0u;
+                    fin = lean_bookkeeping_masked(L, child, tri, ldsn_i, ldsl_i, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, ~0ull);
                 }
+                bool done = hit_any || __builtin_amdgcn_inverse_ballot_w64(fin);
                 if constexpr (INSTANCED) {
                     // in: the frame starts above what the lane holds (siblings still in hand have just been pushed, step 2 of the sequence)
                     if (enter) { I.frame = (uint32_t)L.base | ((uint32_t)L.nsp << 8); L.base = L.nsp; }
@@ -471,8 +482,9 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
                     }
                 }
                 const uint64_t act = __ballot(alive);
-                if (act == 0ull) break;
-                if (kTail ? (uint32_t)__popcll(__ballot(waiting)) >= (uint32_t)a.tail_regen : (64u - (uint32_t)__popcll(act)) >= (uint32_t)a.refill_threshold) break;
+                if constexpr (kTail) {
+                    if (act == 0ull || (uint32_t)__popcll(__ballot(waiting)) >= (uint32_t)a.tail_regen) break;
+                } else if ((uint32_t)__popcll(act) <= max_alive) break;      // (every lane finished included)
             }
         };
         if (exhausted) traverse(std::true_type{}); else traverse(std::false_type{});

@@ -234,10 +234,13 @@ __device__ __forceinline__ float safe_rcp_dir(float d) {
 // node did that for triangles and spheres alike); the record does not know who instances it: `inst_cur` does.
 // (test_prim_ray: the ray given explicitly -- a lane of the instanced kernel that has left an instance with leaf tests still to make keeps that
 // instance's object-space ray in LDS while its registers hold the world ray again)
+// (live, triangles only: false rejects the record -- the caller's lane has none and A / B / C are whatever its registers held; the
+// test still runs, so that the caller needs no per-lane branch round it)
 template <bool HAS_SPHERES, bool INSTANCED = false>
 __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
-                                              const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u) {
+                                              const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
+                                              bool live = true) {
     float t, u = 0.0f, v = 0.0f;
     uint32_t prim = __float_as_uint(A.w), inst;
     if (HAS_SPHERES && __float_as_uint(C.w) == 1u) {
@@ -271,7 +274,7 @@ __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, co
         // branch / restore each; the SIMD issues ~1 instruction of ANY kind per 2.4 cycles, scalar ones included
         // (profiles/r02_valu_issue_patterns_microbench.txt).  Same decisions, same values: a rejected lane's later
         // quantities are never used, det == 0 gives inv = inf and u = NaN or +-inf, which fails the u test like the
-        // explicit one does.
+        // explicit one does.  (u <= 1 is not tested: v >= 0 and u + v <= 1 imply it, the rounded sum included.)
         inst = INSTANCED ? inst_cur : __float_as_uint(B.w);
         const V3 e1 = mk3(B.x, B.y, B.z), e2 = mk3(C.x, C.y, C.z);
         const V3 pvec = cross3(d, e2);
@@ -282,7 +285,7 @@ __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, co
         const V3 qvec = cross3(tvec, e1);
         v = dot3(d, qvec) * inv;
         t = dot3(e2, qvec) * inv;
-        const bool ok = (det != 0.0f) & (u >= 0.0f) & (u <= 1.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (t > tmin) & (t < tmax_ray);
+        const bool ok = live & (det != 0.0f) & (u >= 0.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (t > tmin) & (t < tmax_ray);
         if (!HAS_SPHERES) {
             // closest hit: min t, ties -> lowest (instance, primitive); predicated update
             const bool better = ok & ((t < s.bt) | ((t == s.bt) & ((inst < s.binst) | ((inst == s.binst) & (prim < s.bprim)))));
@@ -305,8 +308,9 @@ __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, co
 template <bool HAS_SPHERES, bool INSTANCED = false>
 __device__ __forceinline__ bool test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
-                                          const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u) {
-    return test_prim_ray<HAS_SPHERES, INSTANCED>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur);
+                                          const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
+                                          bool live = true) {
+    return test_prim_ray<HAS_SPHERES, INSTANCED>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))

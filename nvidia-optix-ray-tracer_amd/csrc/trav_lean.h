@@ -139,23 +139,31 @@ __device__ __forceinline__ void issue_node_loads_off(uint64_t mask, const void *
 //   (7) the next node: the nearest child of the group in hand -- unless the leaf stack could not take another group: such a
 //       lane waits with its node work until primitives have been consumed, which is why the leaf stack needs no overflow path
 //   (8) nothing left to do?
-// Runs for the lanes that are active at the call (alive, not finished by an any-hit); inactive lanes keep their registers.  The
-// node stack has NO overflow path either: the caller guarantees a tree of at most kNodeStackLds levels below the root.
+// Runs for the lanes of `act` that are active at the call (alive, not finished by an any-hit) and files the groups of the lanes of
+// `nm` only (those that made a node step: the others' child / tri are whatever the wave-wide node step made of stale registers);
+// other lanes keep their registers.  The masks are operands so that the caller needs no `if` around the call -- each would be a
+// mask save, a branch and a restore.  The node stack has NO overflow path either: the caller guarantees a tree of at most
+// kNodeStackLds levels below the root.
 //   ldsn / ldsl: byte address in LDS of this lane's column of the node / leaf stack (entries are 512 bytes apart)
 //   pct, quorum: leaf passes are skipped while fewer than pct % of the active lanes have leaf work and fewer than `quorum`
 //   lanes have nothing else to do (those wait)
-// Returns 1 in the lanes whose ray has nothing left to do.
-__device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 child, uint2 tri, uint32_t ldsn, uint32_t ldsl, uint32_t pct, uint32_t quorum, uint32_t hold = 4u) {
+// Returns the mask of the lanes of `act` whose ray has nothing left to do.
+__device__ __forceinline__ uint64_t lean_bookkeeping_masked(LeanLane &L, uint2 child, uint2 tri, uint32_t ldsn, uint32_t ldsl, uint32_t pct, uint32_t quorum,
+                                                            uint32_t hold, uint64_t act, uint64_t nm) {
     static_assert(kLeafStackLds == 4 && kTraverseBlock == 64 && sizeof(uint2) == 8,
                   "the sequence below has the leaf stack's depth (4, 'about to fill' = 3) and the stacks' row pitch (64 lanes x 8 bytes = 1 << 9) as literals");
-    uint32_t fin, t0, t1, t2, c0, c1;
-    uint64_t sv0, sv1, sv2, c2;
+    uint32_t t0, t1, t2, c0, c1;
+    uint64_t fin, svi, sv0, sv1, sv2, c2, c6;
     const uint32_t k24 = 0x00ffffffu;
     asm volatile(
-        "s_mov_b64 %[sv0], exec\n\t"
+        "s_mov_b64 %[svi], exec\n\t"
+        "s_and_b64 %[sv0], exec, %[act]\n\t"
+        "s_and_b64 %[c2], %[sv0], %[nm]\n\t"            // lanes that file the groups of a node step
+        "v_cmp_lt_u32_e64 %[sv2], %[k24], %[chy]\n\t"   // ... whose children's group has hits
+        "v_cmp_lt_u32_e64 %[c6], %[k24], %[cy]\n\t"     // ... and whose group in hand has siblings left
         // (1) the leaf group of this node: into the hand if it is free, else onto the leaf stack
         "v_cmp_ne_u32_e32 vcc, 0, %[ty]\n\t"
-        "s_and_b64 exec, exec, vcc\n\t"
+        "s_and_b64 exec, %[c2], vcc\n\t"
         "v_cmp_eq_u32_e32 vcc, 0, %[py]\n\t"
         "v_cndmask_b32_e32 %[px], %[px], %[tx], vcc\n\t"
         "v_cndmask_b32_e32 %[py], %[py], %[ty], vcc\n\t"
@@ -163,49 +171,39 @@ __device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 chil
         "v_lshl_add_u32 %[t0], %[lsp], 9, %[ldsl]\n\t"
         "ds_write2_b32 %[t0], %[tx], %[ty] offset1:1\n\t"
         "v_add_u32_e32 %[lsp], 1, %[lsp]\n\t"
-        "s_mov_b64 exec, %[sv0]\n\t"
         // (2) the sibling group of this node's children becomes the group in hand; siblings still in hand go to the stack first
-        "v_cmp_lt_u32_e32 vcc, %[k24], %[chy]\n\t"
-        "s_and_b64 exec, exec, vcc\n\t"
-        "v_cmp_lt_u32_e32 vcc, %[k24], %[cy]\n\t"
-        "s_mov_b64 %[sv1], exec\n\t"
-        "s_and_b64 exec, exec, vcc\n\t"
+        "s_and_b64 %[sv1], %[c2], %[sv2]\n\t"
+        "s_and_b64 exec, %[sv1], %[c6]\n\t"
         "v_lshl_add_u32 %[t0], %[nsp], 9, %[ldsn]\n\t"
         "ds_write2_b32 %[t0], %[cx], %[cy] offset1:1\n\t"
         "v_add_u32_e32 %[nsp], 1, %[nsp]\n\t"
-        "s_mov_b64 exec, %[sv1]\n\t"
-        "v_mov_b32_e32 %[cx], %[chx]\n\t"
-        "v_mov_b32_e32 %[cy], %[chy]\n\t"
         "s_mov_b64 exec, %[sv0]\n\t"
+        "v_cndmask_b32_e64 %[cx], %[cx], %[chx], %[sv1]\n\t"
+        "v_cndmask_b32_e64 %[cy], %[cy], %[chy], %[sv1]\n\t"
         // (3) leaf pass?  sv1: lanes with leaf work; sv2: lanes WITHOUT node work.  Yes when pct % of the lanes have leaf work, or
-        //     `quorum` lanes have nothing else to do, or a leaf stack is about to fill, or no lane has node work
-        "v_cmp_ne_u32_e32 vcc, 0, %[py]\n\t"
-        "s_mov_b64 %[sv1], vcc\n\t"
+        //     no lane has node work, or `quorum` lanes have nothing else to do, or a leaf stack is about to fill: each condition
+        //     leaves SCC, and c2 collects them (-1: yes)
+        "v_cmp_ne_u32_e64 %[sv1], 0, %[py]\n\t"
         "v_cmp_ge_u32_e32 vcc, %[k24], %[cy]\n\t"
         "v_cmp_eq_u32_e64 %[sv2], %[base], %[nsp]\n\t"
+        "s_andn2_b64 %[c6], vcc, %[sv2]\n\t"             // (6) below: no hits left in hand, something on the node stack
         "s_and_b64 %[sv2], %[sv2], vcc\n\t"
         "s_bcnt1_i32_b64 %[c0], %[sv1]\n\t"
         "s_bcnt1_i32_b64 %[c1], exec\n\t"
         "s_mulk_i32 %[c0], 0x64\n\t"
         "s_mul_i32 %[c1], %[c1], %[pct]\n\t"
         "s_cmp_ge_u32 %[c0], %[c1]\n\t"
-        "s_cselect_b64 vcc, -1, 0\n\t"
-        "s_xor_b64 %[c2], %[sv2], exec\n\t"                // lanes with node work
-        "s_cmp_eq_u64 %[c2], 0\n\t"
         "s_cselect_b64 %[c2], -1, 0\n\t"
-        "s_or_b64 vcc, vcc, %[c2]\n\t"
-        "s_and_b64 %[sv2], %[sv2], %[sv1]\n\t"             // lanes with nothing but leaf work
+        "s_andn2_b64 vcc, exec, %[sv2]\n\t"              // lanes with node work (SCC: any)
+        "s_cselect_b64 %[c2], %[c2], -1\n\t"
+        "s_and_b64 %[sv2], %[sv2], %[sv1]\n\t"           // lanes with nothing but leaf work
         "s_bcnt1_i32_b64 %[c0], %[sv2]\n\t"
         "s_cmp_ge_u32 %[c0], %[quorum]\n\t"
-        "s_cselect_b64 %[sv2], -1, 0\n\t"
-        "s_or_b64 %[sv2], %[sv2], vcc\n\t"
-        "s_lshr_b32 %[c0], %[hold], 1\n\t"                 // "about to fill": one group below the hold (4 -> more than 2 queued, as ever; 1 -> any)
-        "v_cmp_lt_u32_e32 vcc, %[c0], %[lsp]\n\t"
-        "s_and_b64 vcc, vcc, %[sv1]\n\t"                   // a leaf stack about to fill
-        "s_cmp_lg_u64 vcc, 0\n\t"
-        "s_cselect_b64 vcc, -1, 0\n\t"
-        "s_or_b64 vcc, vcc, %[sv2]\n\t"
-        "s_and_b64 vcc, vcc, %[sv1]\n\t"
+        "s_cselect_b64 %[c2], -1, %[c2]\n\t"
+        "v_cmp_lt_u32_e32 vcc, %[hold2], %[lsp]\n\t"     // "about to fill": one group below the hold (4 -> more than 2 queued, as ever; 1 -> any)
+        "s_and_b64 vcc, vcc, %[sv1]\n\t"                 // a leaf stack about to fill (SCC)
+        "s_cselect_b64 %[c2], -1, %[c2]\n\t"
+        "s_and_b64 vcc, %[c2], %[sv1]\n\t"
         // (4) one primitive of the leaf group in hand
         "v_mov_b32_e32 %[pidx], -1\n\t"
         "s_mov_b64 exec, vcc\n\t"
@@ -222,11 +220,9 @@ __device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 chil
         "v_lshl_add_u32 %[t0], %[lsp], 9, %[ldsl]\n\t"
         "ds_read_b32 %[px], %[t0]\n\t"
         "ds_read_b32 %[py], %[t0] offset:4\n\t"
-        "s_mov_b64 exec, %[sv0]\n\t"
-        // (6) a group in hand without hits left is replaced by the top of the node stack
-        "v_cmp_ge_u32_e32 vcc, %[k24], %[cy]\n\t"
-        "v_cmp_ne_u32_e64 %[sv1], %[base], %[nsp]\n\t"
-        "s_and_b64 exec, vcc, %[sv1]\n\t"
+        // (6) a group in hand without hits left is replaced by the top of the node stack (the lanes were chosen in (3): cy and nsp
+        //     have not changed since)
+        "s_mov_b64 exec, %[c6]\n\t"
         "v_add_u32_e32 %[nsp], -1, %[nsp]\n\t"
         "v_lshl_add_u32 %[t0], %[nsp], 9, %[ldsn]\n\t"
         "ds_read_b32 %[cx], %[t0]\n\t"
@@ -257,15 +253,19 @@ __device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 chil
         "v_cmp_eq_u32_e64 %[sv1], 0, %[t1]\n\t"
         "s_and_b64 %[sv1], %[sv1], vcc\n\t"
         "v_cmp_ge_u32_e32 vcc, %[k24], %[cy]\n\t"
-        "s_and_b64 vcc, vcc, %[sv1]\n\t"
-        "v_cndmask_b32_e64 %[fin], 0, 1, vcc"
+        "s_and_b64 %[fin], vcc, %[sv1]\n\t"              // (compares under exec = sv0: no bits outside it)
+        "s_mov_b64 exec, %[svi]"
         : [cx] "+v"(L.s.cur.x), [cy] "+v"(L.s.cur.y), [px] "+v"(L.s.ptri.x), [py] "+v"(L.s.ptri.y), [nsp] "+v"(L.nsp), [lsp] "+v"(L.lsp),
-          [nidx] "+v"(L.nidx), [pidx] "+v"(L.pidx), [fin] "=&v"(fin), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
-          [sv0] "=&s"(sv0), [sv1] "=&s"(sv1), [sv2] "=&s"(sv2), [c2] "=&s"(c2), [c0] "=&s"(c0), [c1] "=&s"(c1)
+          [nidx] "+v"(L.nidx), [pidx] "+v"(L.pidx), [fin] "=&s"(fin), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
+          [svi] "=&s"(svi), [sv0] "=&s"(sv0), [sv1] "=&s"(sv1), [sv2] "=&s"(sv2), [c2] "=&s"(c2), [c6] "=&s"(c6), [c0] "=&s"(c0), [c1] "=&s"(c1)
         : [chx] "v"(child.x), [chy] "v"(child.y), [tx] "v"(tri.x), [ty] "v"(tri.y), [oct] "v"(L.s.oct_inv4), [base] "v"(L.base), [ldsn] "v"(ldsn), [ldsl] "v"(ldsl),
-          [k24] "s"(k24), [pct] "s"(pct), [quorum] "s"(quorum), [hold] "s"(hold)
+          [k24] "s"(k24), [pct] "s"(pct), [quorum] "s"(quorum), [hold] "s"(hold), [hold2] "s"(hold >> 1), [act] "s"(act), [nm] "s"(nm)
         : "vcc", "scc", "memory");
     return fin;
+}
+// The same for all lanes active at the call, whose groups are all filed.  Returns 1 in the lanes whose ray has nothing left to do.
+__device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 child, uint2 tri, uint32_t ldsn, uint32_t ldsl, uint32_t pct, uint32_t quorum, uint32_t hold = 4u) {
+    return __builtin_amdgcn_inverse_ballot_w64(lean_bookkeeping_masked(L, child, tri, ldsn, ldsl, pct, quorum, hold, ~0ull, ~0ull)) ? 1u : 0u;
 }
 
 }  // namespace hrt

@@ -14,8 +14,25 @@ SIMPLE = {"v_fma_f32", "v_add_f32", "v_mul_f32", "v_sub_f32", "v_subrev_f32", "v
           "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_mov_b32", "v_mov_b64", "v_cndmask_b32", "v_not_b32"}
 
 
-def loops(source, prefix, asm=None):
-    """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields its loops."""
+def kind(op):
+    """valu_simple / valu_complex / salu / mem of an opcode (encoding suffix stripped)"""
+    if op.startswith("v_"):
+        return "valu_simple" if op in SIMPLE else "valu_complex"
+    return "salu" if op.startswith("s_") else "mem"
+
+
+def instructions(lines):
+    """(opcode without its encoding suffix, line) of the instructions among `lines` (labels, comments, asm markers skipped)"""
+    for l in lines:
+        t = l.strip().split()
+        if not t or t[0].startswith(";") or t[0].endswith(":"):
+            continue
+        yield re.sub(r"_(e32|e64|sdwa|dpp)$", "", t[0]), l
+
+
+def loop_bodies(source, prefix, asm=None):
+    """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields (kernel, lines of
+    its traversal loop in layout order)."""
     asm = str(asm or Path(tempfile.gettempdir()) / f"hrt_loops_{Path(source).stem}.s")
     flags = [f for f in makefile_hipflags() if f != "-fPIC"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", asm, source], cwd=ROOT, stderr=subprocess.DEVNULL)
@@ -38,20 +55,22 @@ def loops(source, prefix, asm=None):
         if not back:
             continue
         end, start = back[-1]
+        yield name, body[start:end + 1]
+
+
+def loops(source, prefix, asm=None):
+    """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields its loops."""
+    for name, lines in loop_bodies(source, prefix, asm):
         cs, ops = Counter(), Counter()
-        for l in body[start:end + 1]:
-            t = l.strip().split()
-            if not t or t[0].startswith(";") or t[0].endswith(":"):
-                continue
-            op = re.sub(r"_(e32|e64|sdwa|dpp)$", "", t[0])
+        for op, _ in instructions(lines):
             ops[op] += 1
-            if op.startswith("v_"):
-                cs["valu_simple" if op in SIMPLE else "valu_complex"] += 1
-            elif op.startswith("s_"):
-                cs["salu"] += 1
-            else:
-                cs["mem"] += 1
+            cs[kind(op)] += 1
         yield name, cs, ops
+
+
+def model_cycles(cs):
+    """issue cycles of a loop iteration under the cost model of DESIGN.md section 4.1"""
+    return 4.1 * cs["valu_complex"] + 2.37 * cs["valu_simple"] + 2.4 * cs["salu"]
 
 
 if __name__ == "__main__":
@@ -61,6 +80,7 @@ if __name__ == "__main__":
             if want and not any(w in name for w in want):
                 continue
             total = sum(cs.values())
-            print(f"{name}: {total} instructions in the traversal loop: VALU {cs['valu_simple']} dual-pipe + {cs['valu_complex']} single-pipe, SALU {cs['salu']}, memory {cs['mem']}")
+            print(f"{name}: {total} instructions in the traversal loop: VALU {cs['valu_simple']} dual-pipe + {cs['valu_complex']} single-pipe, SALU {cs['salu']}, memory {cs['mem']}"
+                  f" -- {model_cycles(cs):.0f} modelled cycles")
             if "-v" in want or len(want) == 1:
                 print("   ", ", ".join(f"{k} {v}" for k, v in ops.most_common(24)))
