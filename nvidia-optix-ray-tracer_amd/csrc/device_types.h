@@ -197,8 +197,8 @@ void launch_debug_trig(int which, const float *a, const float *b, uint32_t first
 // host-callable launchers (defined in kernels.hip)
 void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t *d_jump, hipStream_t s);
 void launch_generate(const GenerateArgs &a, hipStream_t s);
-void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, bool dma, uint32_t grid_blocks, hipStream_t s);
-void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // round 1's fused kernel k_traverse<.., FUSED> (HRT_FUSED=2)
+void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
+void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // round 1's fused kernel k_traverse<.., FUSED>: trees k_fused cannot take
 constexpr int kFusedBlocksPerCu = 16;  // k_fused is compiled for 4 waves per SIMD (125 VGPRs, nothing spilled): more workgroups per CU would only queue
 constexpr int kFusedInstancedBlocksPerCu = 12;   // k_fused<.., INSTANCED> is compiled for 3 waves per SIMD (fused.hip)
 constexpr uint32_t kFetchShards = 8;         // slice counters (one per XCD-group of blocks)
@@ -206,7 +206,7 @@ constexpr uint32_t kFetchShardStride = 32;   // u32s between counters: one 128-b
 constexpr int kFusedMaxDepth = 12;     // deepest tree (levels below the root) k_fused takes: its per-lane node stack in LDS (trav_lean.h: kNodeStackLds)
 void launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
 void launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // two-level trees (transform nodes, bvh8.h)
-void launch_trace_queue(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // k_trace_queue (fused_queue.hip): wavefront mode's traverse kernel, the loop of k_fused over ray queues      // k_fused (fused.hip): the default
+void launch_trace_queue(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // k_trace_queue (fused_queue.hip): wavefront mode's traverse kernel, k_fused's traversal over ray queues
 void launch_sum(float4 *accum, const float4 *result, uint32_t n, uint32_t first_sample, hipStream_t s);
 void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s);
 void launch_shade(const ShadeArgs &a, int program, uint32_t grid_blocks, hipStream_t s);

@@ -2,7 +2,7 @@
 //
 // Replaces the OptiX launch of the reference (raygen -> optixTrace -> closest-hit / miss, recursively, shader/Shader.cu:46-287;
 // launched at src/Global/RendererMesh.cu:416-419).  Same execution model as round 1's fused mode of k_traverse (kernels.hip,
-// still there as HRT_FUSED=2): every lane OWNS a pixel and carries its path state in registers -- RNG state, sample and depth
+// still there for trees beyond k_fused's limits): every lane OWNS a pixel and carries its path state in registers -- RNG state, sample and depth
 // counters, the albedo chain, the running sum; waves take 16-pixel slices of the tile from sharded counters; a lane whose ray
 // has finished waits, and once enough lanes of the wave wait a regeneration phase (wave-uniform branch) shades them in place
 // with the shared device functions of trav_common.h and starts the next ray in the same lane: the bounce, the next sample's

@@ -1,11 +1,12 @@
 // fused_queue.hip -- k_trace_queue: the traverse kernel of the WAVEFRONT pipeline (generate / traverse / bin / shade / accumulate as
 // separate launches, hrt_api.cpp) with the traversal step of the production path kernel: trav_lean.h -- two small LDS stacks, the
-// hand-written bookkeeping, hand-counted vmcnt, issue priorities per phase, tail splitting with a shared best hit -- exactly the loop
-// of k_fused (fused.hip), fed from ray queues instead of pixels: a lane takes a RayRec from one of up to two queue segments
+// hand-written bookkeeping, hand-counted vmcnt, issue priorities per phase, tail splitting with a shared best hit -- the building
+// blocks of k_fused's loop (fused.hip; that loop has since dropped the per-lane guards round them, this one keeps them), fed from ray
+// queues instead of pixels: a lane takes a RayRec from one of up to two queue segments
 // (their lengths are read from device memory, so a render is a fixed sequence of launches), traverses it, and writes the hit
 // record; no path state, no RNG.  Replaces optixTrace = RT-core traversal + built-in intersection (shader/Shader.cu:70,
 // src/Global/RendererImpl.cu:295-314) for the rays of one wavefront stage.  Round 1's k_traverse (kernels.hip) stays for the
-// counting build, the LDS-DMA gather mode and trees deeper than k_fused's node stack.
+// counting build and for trees outside k_fused's limits (deeper than its node stack, or beyond 32-bit offsets).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>

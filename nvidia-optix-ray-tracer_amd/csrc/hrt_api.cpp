@@ -242,6 +242,44 @@ static bool fits_fused_kernel(const HrtContext *ctx, const Tlas &t) {
     return t.max_depth <= (uint32_t)ctx->fused_max_depth && (uint64_t)t.n_nodes * t.node_stride < ctx->fused_max_bytes &&
            (uint64_t)std::max(t.n_prims, 1u) * t.prim_stride < ctx->fused_max_bytes;
 }
+// A two-level tree is traced by k_fused's instanced form only: not by the counting build, not outside HRT_FUSED=1, not when it does not fit.
+static bool two_level_admitted(const HrtContext *ctx, const Tlas &t, bool count) {
+    return !t.two_level || (!count && ctx->fused == 1 && fits_fused_kernel(ctx, t));
+}
+// How many leaf groups a lane may queue before its node work waits for primitive tests.  A queued group is tested whatever has been hit
+// meanwhile, so the more primitive tests a ray makes per node visit the sooner they should follow their node: soups (7 tests per 21 visits)
+// run the stack full, scenes of many bodies (19 per 22 in a dense cloud) want 2, two-level trees (30 per 28, all of them inside instances) 1 --
+// profiles/r04_leaf_hold.txt: +2 % / +7 %, C4 unchanged; the shipped sample's 25 particles (1.4 tests per 5.4 visits) are a soup in this respect.
+static int leaf_hold_for(const HrtContext *ctx, const Tlas &t) {
+    return ctx->leaf_hold > 0 ? ctx->leaf_hold : t.two_level ? 1 : (t.scene_of_bodies && t.n_instances >= 256u) ? 2 : 4;
+}
+// The fields of a traversal launch that do not depend on the kernel or the call site.
+static TraverseArgs traverse_args(const HrtContext *ctx, const Tlas &t, float tmin, float tmax) {
+    TraverseArgs ta{};
+    ta.nodes = t.d_nodes; ta.prims = t.d_prims; ta.node_stride = t.node_stride; ta.prim_stride = t.prim_stride;
+    ta.inst_inv = t.d_inst_inv; ta.inst_identity = t.d_inst_identity;
+    ta.tmin = tmin; ta.tmax = tmax;
+    ta.leaf_quorum = ctx->leaf_quorum; ta.tail_regen = ctx->fused_tail_regen;
+    ta.tail_split = t.two_level ? 0 : ctx->tail_split;      // (the pieces of a split ray would have to carry the instance they are in)
+    return ta;
+}
+// The path kernel of a tree: k_fused, its instanced form for two-level trees, or -- for a tree outside k_fused's limits -- round 1's
+// fused kernel, counted in fused_fallback_launches.  blocks_per_cu: one-wave workgroups per CU at most.
+enum class PathKernel { Fused, FusedInstanced, Round1 };
+struct PathKernelChoice { PathKernel kernel; uint32_t blocks_per_cu; };
+static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
+    const uint32_t knob = (uint32_t)ctx->fused_blocks_per_cu;
+    if (!fits_fused_kernel(ctx, t)) { ctx->fused_fallback_launches++; return {PathKernel::Round1, knob}; }
+    if (t.two_level) return {PathKernel::FusedInstanced, std::min<uint32_t>(knob, (uint32_t)kFusedInstancedBlocksPerCu)};
+    return {PathKernel::Fused, std::min<uint32_t>(knob, (uint32_t)kFusedBlocksPerCu)};
+}
+static void launch_path_kernel(PathKernel k, const TraverseArgs &ta, bool has_spheres, uint32_t grid, hipStream_t s) {
+    switch (k) {
+        case PathKernel::Fused: launch_fused(ta, has_spheres, grid, s); break;
+        case PathKernel::FusedInstanced: launch_fused_instanced(ta, has_spheres, grid, s); break;
+        case PathKernel::Round1: launch_paths_v1(ta, has_spheres, grid, s); break;
+    }
+}
 static int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s) {
     if (ctx->table_tlas == handle && ctx->table_tlas_gen == t->generation && ctx->table_mat_gen == ctx->materials_generation) return HRT_OK;
     const uint32_t n = std::max(t->n_instances, 1u);
@@ -282,23 +320,16 @@ struct LaunchFrame {
 };
 
 // ---- fused path mode: ONE launch, every lane owns a pixel and runs all its samples (generate, traverse, shade, accumulate in place).
-//      No stage barriers.  The default (HRT_FUSED=1); HRT_FUSED=2 and trees outside k_fused's limits: round 1's path kernel. ----
+//      No stage barriers.  The default (HRT_FUSED=1); trees outside k_fused's limits take round 1's path kernel. ----
 static int render_fused(const LaunchFrame &f) {
     HrtContext *ctx = f.ctx; Tlas *t = f.t; const HrtGlobalParams *h_params = f.h_params; const HrtRayGenParams *rg = f.rg;
     const uint32_t spp = f.spp, n = f.n; hipStream_t s = f.s;
     Workspace &w = ctx->ws;
     StageCounters *stg = w.set[0].stages;
-    TraverseArgs ta{};
-    ta.nodes = t->d_nodes; ta.prims = t->d_prims; ta.node_stride = t->node_stride; ta.prim_stride = t->prim_stride;
+    TraverseArgs ta = traverse_args(ctx, *t, kFloatZero, kFloatInfinity);
     ta.fetch_counter = stg[0].fetch;
-    ta.inst_inv = t->d_inst_inv; ta.inst_identity = t->d_inst_identity;
-    ta.tmin = kFloatZero; ta.tmax = kFloatInfinity;
-    ta.refill_threshold = ctx->fused_refill_threshold; ta.postpone_pct = ctx->postpone_pct; ta.leaf_quorum = ctx->leaf_quorum; ta.tail_regen = ctx->fused_tail_regen; ta.tail_split = ctx->tail_split; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
-    // How many leaf groups a lane may queue before its node work waits for primitive tests.  A queued group is tested whatever has been hit
-    // meanwhile, so the more primitive tests a ray makes per node visit the sooner they should follow their node: soups (7 tests per 21 visits)
-    // run the stack full, scenes of many bodies (19 per 22 in a dense cloud) want 2, two-level trees (30 per 28, all of them inside instances) 1 --
-    // profiles/r04_leaf_hold.txt: +2 % / +7 %, C4 unchanged; the shipped sample's 25 particles (1.4 tests per 5.4 visits) are a soup in this respect.
-    ta.leaf_hold = ctx->leaf_hold > 0 ? ctx->leaf_hold : t->two_level ? 1 : (t->scene_of_bodies && t->n_instances >= 256u) ? 2 : 4;
+    ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
+    ta.leaf_hold = leaf_hold_for(ctx, *t);
     if (ctx->refill_auto && t->two_level) ta.refill_threshold = 12;      // (a two-level ray is long and its lanes finish far apart: 12 against 20 is +1.4-2.3 %, flattened trees lose 4 %)
     PathArgs &pa = ta.path;
     pa.rows = w.rows; pa.first_pixel = 0; pa.n_tile_pixels = n; pa.width = rg->width; pa.height = rg->height; pa.spp = spp;
@@ -314,18 +345,15 @@ static int render_fused(const LaunchFrame &f) {
     // 172 ms on 12 waves per CU, 210 ms on 16).  A full frame has many pixels per lane and keeps the maximum: 16 waves
     // per CU = 4 per SIMD for k_fused (122 VGPRs, nothing spilled: 3120 Mrays/s on C4; compiled for 5 waves it spills 95
     // registers around the shading: 2560), 20 = 5 per SIMD for round 1's kernel (96 VGPRs, a few spills: 2905).
-    // k_fused (fused.hip) keeps one sibling group per tree level in LDS and has no overflow path: deeper trees, and HRT_FUSED=2, take round 1's kernel
-    const bool lean = ctx->fused != 2 && fits_fused_kernel(ctx, *t);
-    if (t->two_level && !lean) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS needs the default path kernel (HRT_FUSED=1)");
-    if (lean) ta.postpone_pct = ctx->fused_postpone_pct;
-    else if (ctx->fused != 2) ctx->fused_fallback_launches++;        // the tree does not fit k_fused
-    uint32_t blocks_per_cu = lean ? std::min<uint32_t>((uint32_t)ctx->fused_blocks_per_cu, (uint32_t)(t->two_level ? kFusedInstancedBlocksPerCu : kFusedBlocksPerCu)) : (uint32_t)ctx->fused_blocks_per_cu;
+    const PathKernelChoice pk = choose_path_kernel(ctx, *t);
+    const bool lean = pk.kernel != PathKernel::Round1;
+    ta.postpone_pct = lean ? ctx->fused_postpone_pct : ctx->postpone_pct;
+    uint32_t blocks_per_cu = pk.blocks_per_cu;
     if (ctx->traverse_blocks_auto) {
         const uint32_t fit = (uint32_t)((10ull * n + 14ull * 64ull * (uint64_t)ctx->n_cu - 1ull) / (14ull * 64ull * (uint64_t)ctx->n_cu));
         blocks_per_cu = std::min(blocks_per_cu, std::max(fit, 4u));
     }
     const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * blocks_per_cu, (n + 63u) / 64u);
-    if (t->two_level) ta.tail_split = 0;        // (the pieces of a split ray would have to carry the instance they are in)
     // HRT_CTX_REUSE_PRIMARY: the lanes' slots for their pixels' primary hits (k_fused<.., REUSE>, fused.hip)
     if (lean && spp > 1u && ((ctx->flags & HRT_CTX_REUSE_PRIMARY) != 0u || ctx->reuse_primary)) {
         if (grid * 64u > w.primary_cache_lanes) {
@@ -336,11 +364,7 @@ static int render_fused(const LaunchFrame &f) {
         }
         pa.primary_cache = w.primary_cache;
     }
-    auto launch = [&]() {
-        if (lean && t->two_level) launch_fused_instanced(ta, t->has_spheres, grid, s);
-        else if (lean) launch_fused(ta, t->has_spheres, grid, s);
-        else launch_paths_v1(ta, t->has_spheres, grid, s);
-    };
+    auto launch = [&]() { launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s); };
     // Longest-processing-time-first: a pixel's samples run one after the other in one lane, so a render ends with
     // whatever pixels were started last.  For renders of many samples the first sample is a probe launch of its own
     // that records how long each slice's pixels took over their sample; the slices are then handed out slowest first,
@@ -391,8 +415,8 @@ static int render_fused(const LaunchFrame &f) {
     constexpr uint32_t kCounterWords = (uint32_t)(sizeof(StageCounters) / sizeof(uint32_t));
     if (n >= kCounterWords) { fa.reset_counters = reinterpret_cast<uint32_t *>(stg); fa.n_reset = kCounterWords; }
     { Timer tm(ctx, s, HRT_K_FINALIZE); launch_finalize(fa, s); }
-    ctx->fused_counters_clean = fa.reset_counters != nullptr;
     HIP_TRY(ctx, hipGetLastError());
+    ctx->fused_counters_clean = fa.reset_counters != nullptr;
     ctx->paths += (uint64_t)n * spp;
     ctx->last_tlas = h_params->handle;
     return HRT_OK;
@@ -480,22 +504,22 @@ static int render_wavefront(const LaunchFrame &f, bool count) {
     };
     // one traverse launch over class (sa, da) and, optionally, class (sb_, db)
     auto do_traverse = [&](const Sub &sb, uint32_t sa, uint32_t da, bool second, uint32_t sb_, uint32_t db) {
-        TraverseArgs ta{};
-        ta.nodes = t->d_nodes; ta.prims = t->d_prims; ta.node_stride = t->node_stride; ta.prim_stride = t->prim_stride;
+        TraverseArgs ta = traverse_args(ctx, *t, kFloatZero, kFloatInfinity);      // Shader.cu:232, :266
         ta.seg[0] = seg_of(sa, da, sb);
         if (second) ta.seg[1] = seg_of(sb_, db, sb);
         ta.fetch_counter = stages_of(sa, sb)[da].fetch;
-        ta.inst_inv = t->d_inst_inv; ta.inst_identity = t->d_inst_identity;
-        ta.tmin = kFloatZero; ta.tmax = kFloatInfinity;      // Shader.cu:232, :266
-        ta.refill_threshold = ctx->refill_threshold; ta.postpone_pct = ctx->postpone_pct; ta.leaf_quorum = ctx->leaf_quorum; ta.leaf_hold = 4; ta.tail_regen = ctx->fused_tail_regen; ta.tail_split = ctx->tail_split; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
+        ta.leaf_hold = 4; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
         Timer tm(ctx, sb.st, (da >= kRayTraceDepth && !second) ? HRT_K_TRAVERSE_ANY : HRT_K_TRAVERSE);
-        // production traversal: the loop of the path kernel over the ray queues (k_trace_queue); the counting build, the LDS-DMA gather
-        // mode and trees that do not fit k_fused's stacks / offsets keep round 1's k_traverse
-        if (!count && ctx->lds_gather == 0 && ctx->wavefront_lean && fits_fused_kernel(ctx, *t)) {
+        // production traversal: k_fused's traversal over the ray queues (k_trace_queue); the counting build and trees that do not fit
+        // k_fused's stacks / offsets keep round 1's k_traverse
+        if (!count && fits_fused_kernel(ctx, *t)) {
             ta.postpone_pct = ctx->fused_postpone_pct; ta.refill_threshold = ctx->fused_refill_threshold;
             const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * (uint32_t)std::min(ctx->traverse_blocks_per_cu, kFusedBlocksPerCu), (2u * sb.n + 63u) / 64u);
             launch_trace_queue(ta, t->has_spheres, grid, sb.st);
-        } else launch_traverse(ta, count, t->has_spheres, ctx->lds_gather != 0, sb.grid_trav, sb.st);
+        } else {
+            ta.postpone_pct = ctx->postpone_pct; ta.refill_threshold = ctx->refill_threshold;
+            launch_traverse(ta, count, t->has_spheres, sb.grid_trav, sb.st);
+        }
     };
     // everything that follows the traversal of class (sample, depth): binning, shading, path ends
     auto do_after = [&](const Sub &sb, uint32_t sample, uint32_t depth) {
@@ -642,7 +666,7 @@ int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const Hr
     }
 
     const bool count = (ctx->flags & HRT_CTX_COUNT) != 0;
-    if (t->two_level && (count || ctx->fused != 1)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only (not under HRT_CTX_COUNT / HRT_FUSED != 1)");
+    if (!two_level_admitted(ctx, *t, count)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only (not under HRT_CTX_COUNT / HRT_FUSED != 1, and not beyond its limits)");
     const LaunchFrame frame{ctx, t, h_params, rg, spp, n, s};
     const bool use_fused = !count && (ctx->fused > 0 || (ctx->fused < 0 && n <= (uint32_t)ctx->fused_max_pixels));
     return use_fused ? render_fused(frame) : render_wavefront(frame, count);
@@ -730,37 +754,32 @@ int hrt_trace_rays(HrtContext *ctx, HrtTraversable tlas, const HrtFloat3 *d_orig
     HIP_TRY(ctx, hipMalloc((void **)&fetch, sizeof(uint32_t) * 8 * 32));
     HIP_TRY(ctx, hipMemsetAsync(fetch, 0, sizeof(uint32_t) * 8 * 32, s));
     launch_pack_rays(reinterpret_cast<const float *>(d_origins), reinterpret_cast<const float *>(d_directions), n_rays, rays, s);
-    TraverseArgs ta{};
-    ta.nodes = t->d_nodes; ta.prims = t->d_prims; ta.node_stride = t->node_stride; ta.prim_stride = t->prim_stride;
-    ta.fetch_counter = fetch; ta.inst_inv = t->d_inst_inv; ta.inst_identity = t->d_inst_identity;
-    ta.tmin = tmin; ta.tmax = tmax; ta.postpone_pct = ctx->postpone_pct; ta.leaf_quorum = ctx->leaf_quorum; ta.leaf_hold = ctx->leaf_hold > 0 ? ctx->leaf_hold : t->two_level ? 1 : (t->scene_of_bodies && t->n_instances >= 256u) ? 2 : 4; ta.tail_regen = ctx->fused_tail_regen;
+    TraverseArgs ta = traverse_args(ctx, *t, tmin, tmax);
+    ta.fetch_counter = fetch; ta.leaf_hold = leaf_hold_for(ctx, *t);
     const bool count = (ctx->flags & HRT_CTX_COUNT) != 0;
-    if (t->two_level && (count || ctx->fused != 1 || !fits_fused_kernel(ctx, *t))) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only");
+    if (!two_level_admitted(ctx, *t, count)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only");
     if (!count && ctx->fused > 0) {
         // the production configuration: the rays go through the very kernel hrt_render_launch runs (fused path kernel, v_rcp_f32
         // slab test, regeneration thresholds), each ray standing in for a pixel that is traced once and not shaded
-        ta.refill_threshold = ctx->fused_refill_threshold; ta.tail_split = ctx->tail_split; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
+        ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
         PathArgs &pa = ta.path;
         pa.n_tile_pixels = n_rays; pa.first_pixel = 0; pa.width = n_rays; pa.height = 1; pa.spp = 1;
         pa.trace_rays = rays; pa.trace_tuvp = tuvp; pa.trace_inst = inst; pa.trace_any = any_hit ? 1u : 0u;
         pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
-        const bool lean = ctx->fused != 2 && fits_fused_kernel(ctx, *t);
-        if (lean) ta.postpone_pct = ctx->fused_postpone_pct;
-        else if (ctx->fused != 2) ctx->fused_fallback_launches++;
-        const uint32_t blocks_per_cu = lean ? std::min<uint32_t>((uint32_t)ctx->fused_blocks_per_cu, (uint32_t)(t->two_level ? kFusedInstancedBlocksPerCu : kFusedBlocksPerCu)) : (uint32_t)ctx->fused_blocks_per_cu;
-        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * blocks_per_cu, (n_rays + 63u) / 64u);
+        const PathKernelChoice pk = choose_path_kernel(ctx, *t);
+        ta.postpone_pct = pk.kernel != PathKernel::Round1 ? ctx->fused_postpone_pct : ctx->postpone_pct;
+        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * pk.blocks_per_cu, (n_rays + 63u) / 64u);
         Timer tm(ctx, s, HRT_K_PATHS);
-        if (t->two_level) { ta.tail_split = 0; launch_fused_instanced(ta, t->has_spheres, grid, s); }
-        else if (lean) launch_fused(ta, t->has_spheres, grid, s); else launch_paths_v1(ta, t->has_spheres, grid, s);
+        launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s);
     } else {
         ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
         ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;
         ta.seg[0].count_nodes = any_hit ? &ctx->d_stats->nodes_any : &ctx->d_stats->nodes_closest;
         ta.seg[0].count_prims = any_hit ? &ctx->d_stats->prims_any : &ctx->d_stats->prims_closest;
-        ta.refill_threshold = ctx->refill_threshold; ta.tail_split = ctx->tail_split; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
+        ta.refill_threshold = ctx->refill_threshold; ta.postpone_pct = ctx->postpone_pct; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
         const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * (uint32_t)ctx->traverse_blocks_per_cu, (n_rays + 63u) / 64u);
         Timer tm(ctx, s, any_hit ? HRT_K_TRAVERSE_ANY : HRT_K_TRAVERSE);
-        launch_traverse(ta, count, t->has_spheres, ctx->lds_gather != 0, grid, s);
+        launch_traverse(ta, count, t->has_spheres, grid, s);
     }
     launch_unpack_hits(tuvp, inst, n_rays, d_t, d_u, d_v, d_prim, d_inst, s);
     hipError_t e = hipStreamSynchronize(s);

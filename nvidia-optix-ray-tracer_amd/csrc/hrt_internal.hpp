@@ -158,18 +158,17 @@ struct HrtContext {
     std::vector<TimedSpan> spans; std::vector<hipEvent_t> event_pool; size_t events_used = 0;
     double kernel_ms[HRT_K_COUNT] = {0}; uint64_t kernel_launches[HRT_K_COUNT] = {0};
     float4 *d_linear = nullptr;
-    int refill_threshold = 16;                  // wavefront mode; fused mode: fused_refill_threshold
+    int refill_threshold = 16;                  // round 1's kernels (k_traverse); k_fused and k_trace_queue: fused_refill_threshold
     int fused_refill_threshold = 20, fused_fetch_chunk = 16;   // measured optimum of the fused path mode (profiles/r01_sweep_fused_*.txt, r02_sweep_fused_knobs.txt, r03_sweep_fused_knobs.txt: 20 is 1 % ahead of 16)
     int traverse_blocks_per_cu = 16;            // one-wave workgroups of the wavefront traverse kernel per CU
     int fused_blocks_per_cu = 20;               // ... of the fused path kernels: round 1's takes 5 waves per SIMD (96 VGPRs), k_fused is capped at kFusedBlocksPerCu
     bool traverse_blocks_auto = true;           // fused mode: fewer of them for small tiles (not when the env knob is set)
-    int postpone_pct = 25;                      // wavefront kernels and round 1 path kernel; k_fused: fused_postpone_pct
+    int postpone_pct = 25;                      // round 1's kernels (k_traverse); k_fused and k_trace_queue: fused_postpone_pct
     int fused_postpone_pct = 40;                // (r02_sweep_lanes_active.txt: same speed as 25, 65 % of the lanes active instead of 63.4 %)
     int fused_max_depth = kFusedMaxDepth;       // deeper trees take round 1's fused kernel (HRT_FUSED_MAX_DEPTH lowers it: tests)
     uint64_t fused_max_bytes = 1ull << 32;      // k_fused addresses nodes and records by 32-bit byte offsets: larger arrays take round 1's kernel (HRT_FUSED_MAX_BYTES lowers it: tests)
     bool fused_counters_clean = false;          // the path kernel's slice counters are zero (the previous launch's finalize kernel left them so)
     uint64_t fused_fallback_launches = 0;       // launches that took round 1's path kernel because the tree did not fit k_fused
-    int wavefront_lean = 1;                     // wavefront mode traverses with k_trace_queue (the loop of k_fused); 0: round 1's k_traverse (HRT_WAVEFRONT_LEAN)
     int wavefront_graph = 0;                    // wavefront mode: 1 = replay a captured pair of samples as a hipGraph; 0 (default) = enqueue every launch: the launches
                                                 // are not what limits the mode (traversal is 85 % of its GPU time), profiles/r03_wavefront.txt
     uint64_t graph_replays = 0;
@@ -182,12 +181,11 @@ struct HrtContext {
     bool node_stride_auto = true;               // no HRT_NODE_STRIDE given: trees beyond the Infinity Cache (> 3.5 M primitives) get 128-byte nodes -- a packed
                                                 // 80-byte node straddles two 128-byte lines two times in five, which only costs once the lines come from HBM
                                                 // (32 M triangles: +3.4 %, 8 M: +1 %, C4: -3 %; profiles/r03_large_scenes_node_stride.txt)
-    int fused = 1;                              // 1: fused persistent path kernel k_fused (default), 2: round 1's fused kernel, 0: wavefront kernels, -1: fused only for small tiles
+    int fused = 1;                              // 1: fused persistent path kernel k_fused (default), 0: wavefront kernels, -1: fused only for small tiles
     int fused_max_pixels = 700000;
     bool reuse_primary = false;                 // HRT_REUSE_PRIMARY: every launch as under HRT_CTX_REUSE_PRIMARY
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int fused_max_spp = 512;                    // samples per fused launch
-    int lds_gather = 0;                         // 1: cooperative LDS-DMA gathers, 0: per-lane register loads
     int fetch_chunk = 64;
     int substream_min_pixels = 32768;
     int two_level = 0;                          // hrt_tlas_build: 1 = two-level trees (transform nodes over shared BLASes) whenever the path kernel can take them,

@@ -6,7 +6,9 @@
 //
 //   k_rng_init      XORWOW curand_init restated (HostFunctions.cu:122-127)
 //   k_generate      primary rays                 (Shader.cu:246-267)
-//   k_traverse      persistent-wave BVH8 closest-hit / any-hit traversal (optixTrace, Shader.cu:70)
+//   k_traverse      persistent-wave BVH8 closest-hit / any-hit traversal (optixTrace, Shader.cu:70): round 1's kernel, now
+//                   the counting walk (COUNT) and the traversal -- over ray queues, or as a path kernel (FUSED) -- of the
+//                   trees that k_trace_queue / k_fused cannot take
 //   k_bin_hits      sort hits by program with wave ballot + prefix count (SBT dispatch)
 //   k_shade<P>      one kernel per closest-hit program (Shader.cu:108-233)
 //   k_accumulate    path termination: miss colour / depth cut-off, innermost-first albedo fold
@@ -79,14 +81,12 @@ __global__ __launch_bounds__(256) void k_generate(GenerateArgs a) {
     a.rays[q] = r;
 }
 
-template <bool COUNT, bool HAS_SPHERES, bool DMA, bool FUSED>
+template <bool COUNT, bool HAS_SPHERES, bool FUSED>
 // 5 waves per SIMD: the register allocator is held to 96 VGPRs (the fused instantiations spill 27 / 71 dwords to scratch,
 // which costs less than the fifth wave gives: profiles/r01_sweep_occupancy.txt)
 __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) {
-    static_assert(kTraverseBlock == 64, "one wave per workgroup: staging images and mailboxes are per wave");
+    static_assert(kTraverseBlock == 64, "one wave per workgroup: the LDS stack and the mailboxes are per wave");
     __shared__ uint2 s_stack[kLdsStack][kTraverseBlock];
-    __shared__ uint4 s_node_stage[DMA ? 5 * 64 : 1];          // 64 node slots x 80 B, filled by LDS-DMA
-    __shared__ uint4 s_prim_stage[DMA ? 3 * 64 : 1];          // 64 primitive slots x 48 B
     // tail splitting: one mailbox per lane that owns a split ray (indexed by its home lane)
     __shared__ float s_mb_t[kTraverseBlock], s_mb_u[kTraverseBlock], s_mb_v[kTraverseBlock];
     __shared__ uint32_t s_mb_prim[kTraverseBlock], s_mb_inst[kTraverseBlock], s_mb_pending[kTraverseBlock];
@@ -103,15 +103,6 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
     const float tmin = a.tmin, tmax_ray = a.tmax;
     const uint32_t tx = threadIdx.x;                // = lane
 
-    // gather geometry: in DMA instruction i this lane fetches piece g_off[i] of the slot owned by lane g_own[i]
-    uint32_t gn_own[5], gn_off[5], gp_own[3], gp_off[3];
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) { const uint32_t x = 64u * i + tx; gn_own[i] = x / 5u; gn_off[i] = (x % 5u) * 16u; }
-#pragma unroll
-    for (uint32_t i = 0; i < 3; ++i) { const uint32_t x = 64u * i + tx; gp_own[i] = x / 3u; gp_off[i] = (x % 3u) * 16u; }
-    const uint32_t node_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)reinterpret_cast<uintptr_t>(&s_node_stage[0]));
-    const uint32_t prim_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)reinterpret_cast<uintptr_t>(&s_prim_stage[0]));
-
     TravState s;
     bool alive = false;
     bool exhausted = false;                 // wave-uniform
@@ -123,7 +114,8 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
 
     // FUSED (path mode): the lane owns a pixel and carries its path state; a finished ray is shaded in
     // place and the next ray (bounce, next sample, next pixel) starts in the same lane -- no queues, no
-    // per-stage launches, no stage barriers.  The default mode of the production build.
+    // per-stage launches, no stage barriers.  Path mode runs it only for trees k_fused cannot take
+    // (fits_fused_kernel, hrt_api.cpp).
     bool have_pixel = false, waiting = false, px_first = true;
     uint32_t px_local = 0u, px_tid = 0u, px_sample = 0u, px_depth = 1u;
     uint32_t px_chain[4] = {0u, 0u, 0u, 0u};
@@ -390,22 +382,10 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             }
 
             // ---- G. fetch what every lane needs next: primitives first, nodes second ----
-            f32x4 rpa, rpb, rpc;                      // !DMA: the lane's own primitive / node in registers
+            f32x4 rpa, rpb, rpc;                      // the lane's own primitive / node in registers
             u32x4 rn0, rn1, rn2, rn3, rn4;
-            if (DMA) {
-                const void *pp[3], *np[5];
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    pp[i] = prim_bytes + (size_t)(uint32_t)__shfl((int)pidx, (int)gp_own[i]) * a.prim_stride + gp_off[i];
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    np[i] = node_bytes + (size_t)(uint32_t)__shfl((int)nidx, (int)gn_own[i]) * a.node_stride + gn_off[i];
-                gather_prim_pieces(prim_lds, pp[0], pp[1], pp[2]);
-                gather_node_pieces(node_lds, np[0], np[1], np[2], np[3], np[4]);
-            } else {
-                issue_prim_loads(prim_bytes + (size_t)pidx * a.prim_stride, rpa, rpb, rpc);
-                issue_node_loads(node_bytes + (size_t)nidx * a.node_stride, rn0, rn1, rn2, rn3, rn4);
-            }
+            issue_prim_loads(prim_bytes + (size_t)pidx * a.prim_stride, rpa, rpb, rpc);
+            issue_node_loads(node_bytes + (size_t)nidx * a.node_stride, rn0, rn1, rn2, rn3, rn4);
 
             bool done = false;
             if (any && alive && shared && s_mb_prim[home] != kMissPrim) done = true;   // another piece already found a hit
@@ -414,17 +394,10 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             { const uint64_t mp = __ballot(alive && has_prim), mn = __ballot(alive && has_node); ++ls_iter; ls_alive += __popcll(__ballot(alive)); ls_node += __popcll(mn); ls_prim += __popcll(mp); ls_ppass += mp != 0ull; }
 #endif
             // ---- C. leaf test: waits for the primitive pieces only ----
-            if (DMA) wait_prim_gather(); else wait_prim_loads(rpa, rpb, rpc);
+            wait_prim_loads(rpa, rpb, rpc);
             if (!COUNT && alive && !done && has_prim) {
-                float4 pa, pb, pc;
-                if (DMA) {
-                    pa = reinterpret_cast<const float4 *>(s_prim_stage)[3 * tx + 0];
-                    pb = reinterpret_cast<const float4 *>(s_prim_stage)[3 * tx + 1];
-                    pc = reinterpret_cast<const float4 *>(s_prim_stage)[3 * tx + 2];
-                } else {
-                    pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w); pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w);
-                    pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
-                }
+                const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w);
+                const float4 pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
                 const bool better = test_prim<HAS_SPHERES>(pa, pb, pc, s, tmin, tmax_ray, a.inst_inv, a.inst_identity);
                 if (any && better) done = true;
             }
@@ -432,17 +405,11 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
 
             // ---- A. node phase ----
             uint2 tri = make_uint2(0u, 0u);
-            if (DMA) wait_node_gather(); else wait_node_loads(rn0, rn1, rn2, rn3, rn4);
+            wait_node_loads(rn0, rn1, rn2, rn3, rn4);
             if (alive && !done && has_node) {
-                uint4 n0, n1, n2, n3, n4;
-                if (DMA) {
-                    n0 = s_node_stage[5 * tx + 0]; n1 = s_node_stage[5 * tx + 1]; n2 = s_node_stage[5 * tx + 2];
-                    n3 = s_node_stage[5 * tx + 3]; n4 = s_node_stage[5 * tx + 4];
-                } else {
-                    n0 = make_uint4(rn0.x, rn0.y, rn0.z, rn0.w); n1 = make_uint4(rn1.x, rn1.y, rn1.z, rn1.w);
-                    n2 = make_uint4(rn2.x, rn2.y, rn2.z, rn2.w); n3 = make_uint4(rn3.x, rn3.y, rn3.z, rn3.w);
-                    n4 = make_uint4(rn4.x, rn4.y, rn4.z, rn4.w);
-                }
+                const uint4 n0 = make_uint4(rn0.x, rn0.y, rn0.z, rn0.w), n1 = make_uint4(rn1.x, rn1.y, rn1.z, rn1.w);
+                const uint4 n2 = make_uint4(rn2.x, rn2.y, rn2.z, rn2.w), n3 = make_uint4(rn3.x, rn3.y, rn3.z, rn3.w);
+                const uint4 n4 = make_uint4(rn4.x, rn4.y, rn4.z, rn4.w);
                 if (COUNT) { if (in_b) ++cnt_nodes_b; else ++cnt_nodes; }
                 const float px = __uint_as_float(n0.x), py = __uint_as_float(n0.y), pz = __uint_as_float(n0.z);
                 const uint32_t e_imask = n0.w;
@@ -818,25 +785,21 @@ void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t
 void launch_generate(const GenerateArgs &a, hipStream_t s) {
     if (a.n_tile_pixels) hipLaunchKernelGGL(k_generate, dim3(ceil_div(a.n_tile_pixels, 256)), dim3(256), 0, s, a);
 }
-void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, bool dma, uint32_t grid_blocks, hipStream_t s) {
+void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    const int sel = (dma ? 4 : 0) | (count ? 2 : 0) | (has_spheres ? 1 : 0);
+    const int sel = (count ? 2 : 0) | (has_spheres ? 1 : 0);
     switch (sel) {
-        case 0: hipLaunchKernelGGL((k_traverse<false, false, false, false>), g, b, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((k_traverse<false, true, false, false>), g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_traverse<true, false, false, false>), g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((k_traverse<true, true, false, false>), g, b, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((k_traverse<false, false, true, false>), g, b, 0, s, a); break;
-        case 5: hipLaunchKernelGGL((k_traverse<false, true, true, false>), g, b, 0, s, a); break;
-        case 6: hipLaunchKernelGGL((k_traverse<true, false, true, false>), g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_traverse<true, true, true, false>), g, b, 0, s, a); break;
+        case 0: hipLaunchKernelGGL((k_traverse<false, false, false>), g, b, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((k_traverse<false, true, false>), g, b, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((k_traverse<true, false, false>), g, b, 0, s, a); break;
+        default: hipLaunchKernelGGL((k_traverse<true, true, false>), g, b, 0, s, a); break;
     }
 }
 // fused path mode: one launch renders every sample of every pixel of the tile
 void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    if (has_spheres) hipLaunchKernelGGL((k_traverse<false, true, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_traverse<false, false, false, true>), g, b, 0, s, a);
+    if (has_spheres) hipLaunchKernelGGL((k_traverse<false, true, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_traverse<false, false, true>), g, b, 0, s, a);
 }
 void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s) {
     hipLaunchKernelGGL(k_bin_hits, dim3(grid_blocks), dim3(256), 0, s, a);

@@ -315,44 +315,10 @@ __device__ __forceinline__ bool test_prim(const float4 A, const float4 B, const 
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))
 
-// ---- cooperative gathers of the traversal pipeline ------------------------------------------------
-// One ray per lane means 64 unrelated 80-byte nodes (and 48-byte primitives) per wave and step.
-// Loaded lane by lane (5 + 3 dwordx4 per lane) that is 8 wave-instructions x 64 separate L1
-// look-ups; measured, this address divergence -- not HBM, not L2 -- bounded the kernel (83 G
-// steps/s on a 20 KB tree against 232 G with identical rays).  Instead the wave gathers the 64
-// nodes with 5 LDS-DMA instructions (global_load_lds_dwordx4): LDS byte x of the 5120-byte
-// staging image belongs to node slot x / 80, so lanes 5k..5k+4 of an instruction read the five
-// consecutive 16-byte pieces of ONE node -- coalesced into one or two line look-ups -- and the
-// data lands in LDS at wave base + 16 * lane, i.e. already as [slot][piece].  Each lane then
-// reads its own slot back with ds_read_b128 (stride 80 B / 48 B is bank-conflict-free).
-// The asm has no VGPR destination, so nothing can be read before it has landed except through
-// LDS, and the two waits below carry a "memory" clobber: register-safe.  vmcnt is counted by
-// hand: primitive pieces (3) are issued first, node pieces (5) second, so the primitive needs
-// vmcnt(5) and the node vmcnt(0); VMEM operations the compiler adds can only lengthen the waits.
-__device__ __forceinline__ void gather_node_pieces(uint32_t lds_base, const void *p0, const void *p1, const void *p2,
-                                                   const void *p3, const void *p4) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "s"(lds_base) : "memory", "scc");
-}
-__device__ __forceinline__ void gather_prim_pieces(uint32_t lds_base, const void *p0, const void *p1, const void *p2) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\t"
-                 "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(p0), "v"(p1), "v"(p2), "s"(lds_base) : "memory", "scc");
-}
-// Per-lane variant (template parameter DMA = false): every lane loads its own node / primitive into
-// registers.  More L1 look-ups per step, but no staging image, so more waves fit per CU.  The
-// destinations are named "+v" in the wait statements so that no use is scheduled above the wait.
+// ---- the loads of the traversal step ------------------------------------------------------------
+// Every lane loads its own node (5 dwordx4) and primitive (3 dwordx4) into registers: primitive first, node second, so that
+// the primitive needs vmcnt(5) and the node vmcnt(0).  The destinations are named "+v" in the wait statements so that no use
+// is scheduled above the wait.  (A cooperative LDS-DMA gather of the wave's 64 nodes was measured and not adopted: DESIGN.md 4.)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void issue_prim_loads(const void *p, f32x4 &a, f32x4 &b, f32x4 &c) {
@@ -405,7 +371,5 @@ __device__ __forceinline__ void wait_prim_loads(f32x4 &a, f32x4 &b, f32x4 &c) {
 __device__ __forceinline__ void wait_node_loads(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, u32x4 &e) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) :: "memory");
 }
-__device__ __forceinline__ void wait_prim_gather() { asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); }
-__device__ __forceinline__ void wait_node_gather() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 }  // namespace hrt

@@ -10,7 +10,7 @@ hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
 import oracle_py as oracle
 w, h, spp, salt = 64, 94, 3, 525075280
 scene = hrt.scenes.cornell_box(w, h, spp)
-for mode in ("1", "2", "0"):
+for mode in ("1", "0"):
     os.environ["HRT_FUSED"] = mode
     r = hrt.Renderer(0, 0)
     r.load_scene(scene); r.set_frame(w, h, salt, linear=True)

@@ -37,11 +37,12 @@ for k in range(n_scenes):
     refs = {}
     combos = list(itertools.product((0, 1), (0, 1), ("", "1", "3")))
     if os.environ.get("STRESS_OTHER_MODES"):      # the other execution modes (flattened trees): wavefront pipeline, round 1's path kernel, the counting build
-        combos = [(0, 0, "fused0"), (0, 0, "fused2"), (0, 0, "count"), (0, 0, "fused-1")]
+        combos = [(0, 0, "fused0"), (0, 0, "deep"), (0, 0, "count"), (0, 0, "fused-1")]
     for two, reuse, hold in combos:
         ctx_flags = 0
-        os.environ.pop("HRT_FUSED", None)
+        os.environ.pop("HRT_FUSED", None); os.environ.pop("HRT_FUSED_MAX_DEPTH", None)
         if hold.startswith("fused"): os.environ["HRT_FUSED"] = hold[5:]; hold = ""
+        elif hold == "deep": os.environ["HRT_FUSED_MAX_DEPTH"] = "1"; hold = ""      # trees deeper than one level take round 1's path kernel
         elif hold == "count": ctx_flags = hrt.CTX_COUNT; hold = ""
         if hold: os.environ["HRT_LEAF_HOLD"] = hold
         else: os.environ.pop("HRT_LEAF_HOLD", None)

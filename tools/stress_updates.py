@@ -37,9 +37,11 @@ for k in range(n_scenes):
     elif kind == 1: scene = hrt.scenes.particle_cloud(int(rng.integers(4, 500)), w, h, spp, subdiv=int(rng.integers(0, 3)), seed=int(rng.integers(1, 100)))
     else: scene = hrt.scenes.particle_scene(int(rng.integers(1, 200)), w, h, spp, frame=int(rng.integers(0, 5)))
     flags = (hrt.CTX_TWO_LEVEL if rng.random() < 0.4 else 0) | (hrt.CTX_ASYNC_UPDATE if rng.random() < 0.5 else 0)
-    mode = str(rng.choice(["1", "1", "1", "2", "0"]))
+    mode = str(rng.choice(["1", "1", "1", "deep", "0"]))      # deep: k_fused's depth limit lowered to 1, round 1's path kernel takes the tree
     if flags & hrt.CTX_TWO_LEVEL: mode = "1"
-    os.environ["HRT_FUSED"] = mode
+    os.environ["HRT_FUSED"] = "1" if mode == "deep" else mode
+    if mode == "deep": os.environ["HRT_FUSED_MAX_DEPTH"] = "1"
+    else: os.environ.pop("HRT_FUSED_MAX_DEPTH", None)
     salt = int(rng.integers(1, 1 << 30))
     scene = copy.deepcopy(scene)
     r = hrt.Renderer(0, flags)
