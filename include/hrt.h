@@ -163,6 +163,46 @@ int  hrt_to_rgba8(HrtContext *ctx, const HrtFloat4 *d_src, HrtUchar4 *d_dst,
  * bit-exact against the oracle. */
 int  hrt_color_to_float4(HrtContext *ctx, const HrtFloat4 *d_src, HrtFloat4 *d_dst, uint32_t n, void *stream);
 
+/* ---- denoiser: what stands in for denoiseOutput (src/Global/RendererImpl.cu:680-710) --------------------------------------
+ * The reference hands its sRGB-encoded colour buffer to the OptiX denoiser, whose network cannot be reproduced.  In its slot:
+ * an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the buffers the reference MEANT to give OptiX --
+ * the depth-1 albedo and normal AOV of Shader.cu:216-227, which quirk Q3 blanks in the reference -- recomputed from one
+ * primary ray per pixel into a buffer of the denoiser's own (albedoBuffer / normalBuffer stay zero).  Deterministic, defined
+ * with + - * / only (DESIGN.md "Denoiser" has the definition and tests/denoise_ref.py restates it), no CPU path. */
+
+/* one pixel's guide: the primary hit of the ray the path kernel traces first for the pixel (same origin, direction, tmin, tmax) */
+typedef struct HrtDenoiseGuide {
+    uint16_t normal[3];            /* IEEE half, round to nearest even: normalize(normalVector) as Shader.cu:224-226 (front-face flipped) */
+    uint16_t albedo[3];            /* IEEE half, round to nearest even: the hit material's albedo                                          */
+    float    depth;                /* hit distance t; +inf on a miss (normal and albedo then 0).  The filter takes a pixel of depth
+                                      0 < depth < +inf as a hit, every other one as background                                          */
+} HrtDenoiseGuide;                 /* 16 B */
+
+typedef struct HrtDenoiseParams {
+    uint32_t iterations;           /* filter passes, 1..16; pass i takes taps 2^i pixels apart                              (default 5)    */
+    float    sigma_color;          /* colour edge stop of pass 0, halved every pass: wc = 1/(1 + |c_p - c_q|^2 / sigma_i^2)  (default 0.5)  */
+    float    sigma_albedo;         /* wa = 1/(1 + |a_p - a_q|^2 / sigma_albedo^2)                                            (default 0.1)  */
+    float    sigma_depth;          /* wz = 1/(1 + ((z_p - z_q) / (sigma_depth * z_p * 2^i))^2)                              (default 0.02) */
+    uint32_t normal_power_log2;    /* wn = max(0, n_p . n_q)^(2^k), k squarings, 0..8                                      (default 3)    */
+    uint32_t reserved;             /* must be 0 */
+} HrtDenoiseParams;
+
+int  hrt_denoise_default_params(HrtDenoiseParams *out);
+/* the primary-hit guides of the full frame h_raygen describes (width x height, camera; its buffers are not read or written) through
+ * the TLAS h_params->handle, into d_guides (width * height records).  Needs hrt_materials_set; a two-level tree is refused under
+ * HRT_CTX_COUNT (HRT_ERR_STATE), as by hrt_trace_rays.  Enqueued only. */
+int  hrt_denoise_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                        HrtDenoiseGuide *d_guides, void *stream);
+/* the filter alone over caller-given guides: d_color (width * height float4) -> d_out, which may be d_color itself.
+ * h_dparams == NULL: the defaults.  Enqueued only. */
+int  hrt_denoise_filter(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDenoiseGuide *d_guides, HrtFloat4 *d_out,
+                        uint32_t width, uint32_t height, const HrtDenoiseParams *h_dparams, void *stream);
+/* replaces denoiseOutput, src/Global/RendererImpl.cu:680-710: the guides of the frame (in memory the context owns) and the filter
+ * of h_raygen->colorBuffer into d_out (may be the colour buffer).  Follow with hrt_to_rgba8 as the reference follows with
+ * convertFloat4ToUchar4Kernel; its skipDenoise path is hrt_to_rgba8 of the colour buffer alone.  Enqueued only. */
+int  hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                        const HrtDenoiseParams *h_dparams, HrtFloat4 *d_out, void *stream);
+
 /* ---- measurement (no reference counterpart: the reference has no timers) ------------- */
 enum { HRT_K_GENERATE = 0, HRT_K_TRAVERSE, HRT_K_TRAVERSE_ANY, HRT_K_BIN, HRT_K_SHADE,
        HRT_K_ACCUMULATE, HRT_K_FINALIZE, HRT_K_PATHS /* fused path mode */, HRT_K_REFIT /* hrt_tlas_update */, HRT_K_COUNT };
@@ -229,5 +269,7 @@ void hrt_host_free(HrtBvhBlob *blob);
 
 #ifdef __cplusplus
 }
+static_assert(sizeof(HrtDenoiseGuide) == 16, "HrtDenoiseGuide is 16 B");
+static_assert(sizeof(HrtDenoiseParams) == 24, "HrtDenoiseParams is 24 B");
 #endif
 #endif /* HRT_H */

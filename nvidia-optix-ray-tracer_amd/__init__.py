@@ -88,6 +88,15 @@ class BvhBlob(C.Structure):
                 ("n_triangles", C.c_uint64), ("bounds", C.c_float * 6)]
 
 
+class DenoiseParams(C.Structure):
+    """HrtDenoiseParams (include/hrt.h): the a-trous filter's passes and edge stops."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DENOISE_GUIDE_BYTES = 16        # HrtDenoiseGuide: normal[3], albedo[3] as IEEE halves, depth (float)
+
+assert C.sizeof(DenoiseParams) == 24
 assert C.sizeof(GlobalParams) == 16 and C.sizeof(RayGenParams) == 80 and C.sizeof(MissParams) == 12
 assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof(Instance) == 80
 
@@ -103,6 +112,7 @@ EXPORTS = [
     "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_to_rgba8", "hrt_color_to_float4",
     "hrt_stats_reset", "hrt_stats_get", "hrt_trace_rays", "hrt_debug_set_linear_output",
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
+    "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
 ]
 
 
@@ -164,6 +174,12 @@ def load_library():
     lib.hrt_debug_trig.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     lib.hrt_host_build_bvh8.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BvhBlob)]
     lib.hrt_tlas_download.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BvhBlob)]
+    lib.hrt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    lib.hrt_denoise_guides.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_void_p, C.c_void_p]
+    lib.hrt_denoise_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                       C.POINTER(DenoiseParams), C.c_void_p]
+    lib.hrt_denoise_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
+                                       C.c_void_p, C.c_void_p]
     lib.hrt_host_free.argtypes = [C.POINTER(BvhBlob)]
     lib.hrt_host_free.restype = None
     _lib = lib
@@ -174,4 +190,4 @@ from .host import Renderer, configure_camera, tile_for_rank, reduce_tiles  # noq
 from . import scenes  # noqa: E402
 
 __all__ = ["load_library", "Renderer", "configure_camera", "tile_for_rank", "reduce_tiles", "scenes", "HrtError",
-           "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats"]
+           "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats", "DenoiseParams"]

@@ -1,0 +1,137 @@
+// denoise.hip -- the denoiser that takes the OptiX denoiser's slot (denoiseOutput, src/Global/RendererImpl.cu:680-710; include/hrt.h):
+//   k_denoise_rays    the primary ray of every pixel of a full frame, as k_generate makes it (Shader.cu:246-267)
+//   k_denoise_guides  hit record -> HrtDenoiseGuide: normalised shading normal and albedo of the primary hit as IEEE halves, hit distance
+//                     (the depth-1 AOV of Shader.cu:216-227 that quirk Q3 blanks in the reference); the traversal between the two is
+//                     hrt_trace_rays' (hrt_api.cpp trace_records): the path kernel in the context's configuration
+//   k_denoise_pass    one pass of the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010): 5x5 B3-spline taps `step` pixels
+//                     apart, weighted by colour, normal, albedo and depth distance to the centre pixel
+// The filter is defined with + - * / and max only, taps in row-major order, sums in float32, and compiled with -ffp-contract=off: its
+// result is reproduced bit for bit by tests/denoise_ref.py (DESIGN.md "Denoiser").
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "device_types.h"
+#include "trav_common.h"
+
+#pragma clang fp contract(off)
+
+namespace hrt {
+
+namespace {
+constexpr int kDenoiseTile = 16;          // 16 x 16 pixels per workgroup: a tap's 16 rows of 16 pixels are 4 cache lines of colour + 4 of guides
+
+__device__ __forceinline__ uint32_t half_bits(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }     // RNE
+__device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
+__device__ __forceinline__ bool guide_hit(float z) { return z > 0.0f && z < INFINITY; }
+
+// one HrtDenoiseGuide as 4 words: normal[0..2], albedo[0..2] (halves, little-endian), depth
+struct Guide { V3 n, a; float z; };
+__device__ __forceinline__ Guide guide_decode(const uint4 g) {
+    Guide r;
+    r.n = mk3(half_value(g.x & 0xffffu), half_value(g.x >> 16), half_value(g.y & 0xffffu));
+    r.a = mk3(half_value(g.y >> 16), half_value(g.z & 0xffffu), half_value(g.z >> 16));
+    r.z = __uint_as_float(g.w);
+    return r;
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_denoise_rays(DenoiseRayArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.width * a.height) return;
+    const uint32_t iy = i / a.width, ix = i - iy * a.width;
+    const V3 dir = primary_direction(ix, iy, a.width, a.height, a.U, a.V, a.W);
+    RayRec r;
+    r.o = make_float4(a.center[0], a.center[1], a.center[2], __uint_as_float(i));
+    r.d = make_float4(dir.x, dir.y, dir.z, __uint_as_float(i));
+    a.rays[i] = r;
+}
+
+__global__ __launch_bounds__(256) void k_denoise_guides(DenoiseGuideArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t inst = a.inst[i];
+    uint4 g = make_uint4(0u, 0u, 0u, __float_as_uint(INFINITY));
+    if (inst != kMissPrim) {
+        const float4 h = a.tuvp[i];
+        const RayRec r = a.rays[i];
+        const V3 o = mk3(r.o.x, r.o.y, r.o.z), d = mk3(r.d.x, r.d.y, r.d.z);
+        const HitGroup hg = a.hitgroups[inst];
+        const bool sphere = a.inst_program[inst] < (uint32_t)kProgramTriangleRough;
+        const V3 n = normalize3(hit_normal<true>(sphere, hg, hit_point(o, d, h.x), d, h.y, h.z, __float_as_uint(h.w)));   // Shader.cu:114, :224
+        g.x = half_bits(n.x) | (half_bits(n.y) << 16);
+        g.y = half_bits(n.z) | (half_bits(hg.albedo[0]) << 16);
+        g.z = half_bits(hg.albedo[1]) | (half_bits(hg.albedo[2]) << 16);
+        g.w = __float_as_uint(h.x);
+    }
+    a.guides[i] = g;
+}
+
+// out(p) = sum_q w(p,q) c(q) / sum_q w(p,q) over the 25 taps q = p + step * (dx, dy), dx, dy in -2..2, row-major (dy outer), where
+//   w = ((h[dx] * h[dy]) * wn) / (((1 + |c_p - c_q|^2 k_color) * (1 + |a_p - a_q|^2 k_albedo)) * (1 + ((z_p - z_q) / (sigma_depth step z_p))^2)),
+//   wn = max(0, n_p . n_q) squared normal_squarings times; taps outside the frame or on background are left out; background pixels and
+//   pixels without weight keep their colour; alpha is the centre's.  (The three edge stops share one division; the depth term's
+//   reciprocal is taken once per pixel.)
+// A row's five taps are loaded together -- addresses clamped into the frame, the taps that do not count left out of the sums by a
+// select -- so that ten loads are in flight instead of a dependent guide-then-colour pair per tap.
+// kSquarings >= 0: normal_squarings fixed at compile time (the default's instantiation), -1: read from the arguments.
+template <int kSquarings>
+__global__ __launch_bounds__(kDenoiseTile * kDenoiseTile) void k_denoise_pass(DenoisePassArgs a) {
+    const int x = (int)(blockIdx.x * kDenoiseTile + threadIdx.x), y = (int)(blockIdx.y * kDenoiseTile + threadIdx.y);
+    const int W = (int)a.width, H = (int)a.height, s = (int)a.step;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * a.width + (size_t)x;
+    const float4 cp = a.src[p];
+    const Guide gp = guide_decode(a.guides[p]);
+    if (!guide_hit(gp.z)) { a.dst[p] = cp; return; }
+    const uint32_t squarings = kSquarings >= 0 ? (uint32_t)kSquarings : a.normal_squarings;
+    const float inv_z = 1.0f / (a.sigma_depth_step * gp.z);
+    const float kH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int qy = y + (j - 2) * s;
+        if (qy < 0 || qy >= H) continue;
+        const size_t row = (size_t)qy * a.width;
+        uint4 graw[5]; float4 cq[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int qx = min(max(x + (i - 2) * s, 0), W - 1);
+            graw[i] = a.guides[row + (size_t)qx];
+            cq[i] = a.src[row + (size_t)qx];
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int qx = x + (i - 2) * s;
+            const Guide gq = guide_decode(graw[i]);
+            const bool take = qx >= 0 && qx < W && guide_hit(gq.z);
+            const float dr = cq[i].x - cp.x, dg = cq[i].y - cp.y, db = cq[i].z - cp.z;
+            const float dc2 = dr * dr + dg * dg + db * db;
+            float wn = fmaxf(dot3(gp.n, gq.n), 0.0f);
+            for (uint32_t k = 0; k < squarings; ++k) wn = wn * wn;
+            const V3 da = sub3(gp.a, gq.a);
+            const float da2 = len2_3(da);
+            const float rz = (gp.z - gq.z) * inv_z;
+            const float w = ((kH[i] * kH[j]) * wn) / (((1.0f + dc2 * a.k_color) * (1.0f + da2 * a.k_albedo)) * (1.0f + rz * rz));
+            sw = take ? sw + w : sw;
+            sr = take ? sr + w * cq[i].x : sr; sg = take ? sg + w * cq[i].y : sg; sb = take ? sb + w * cq[i].z : sb;
+        }
+    }
+    a.dst[p] = sw > 0.0f ? make_float4(sr / sw, sg / sw, sb / sw, cp.w) : cp;
+}
+
+static inline uint32_t ceil_div_u(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
+
+void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s) {
+    const uint32_t n = a.width * a.height;
+    if (n) hipLaunchKernelGGL(k_denoise_rays, dim3(ceil_div_u(n, 256)), dim3(256), 0, s, a);
+}
+void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s) {
+    if (a.n) hipLaunchKernelGGL(k_denoise_guides, dim3(ceil_div_u(a.n, 256)), dim3(256), 0, s, a);
+}
+void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s) {
+    if (!a.width || !a.height) return;
+    const dim3 grid(ceil_div_u(a.width, kDenoiseTile), ceil_div_u(a.height, kDenoiseTile)), block(kDenoiseTile, kDenoiseTile);
+    if (a.normal_squarings == 3u) hipLaunchKernelGGL(k_denoise_pass<3>, grid, block, 0, s, a);      // the default (HrtDenoiseParams)
+    else hipLaunchKernelGGL(k_denoise_pass<-1>, grid, block, 0, s, a);
+}
+
+}  // namespace hrt

@@ -194,6 +194,28 @@ struct PoseArgs {
 void launch_pose_instances(const PoseArgs &a, hipStream_t s);
 void launch_debug_trig(int which, const float *a, const float *b, uint32_t first, uint32_t stride, uint64_t n, int force_slow, float *out, hipStream_t s);
 
+// denoiser (denoise.hip): the guide pass -- primary rays of a full frame, then their hits turned into HrtDenoiseGuide records (16 B,
+// uint4 here) -- and one a-trous pass of the filter
+struct DenoiseRayArgs {
+    RayRec *rays; uint32_t width, height;
+    float center[3], U[3], V[3], W[3];
+};
+struct DenoiseGuideArgs {
+    const RayRec *rays; const float4 *tuvp; const uint32_t *inst; uint32_t n;
+    const HitGroup *hitgroups; const uint32_t *inst_program;
+    uint4 *guides;
+};
+struct DenoisePassArgs {
+    const float4 *src; const uint4 *guides; float4 *dst;
+    uint32_t width, height, step;  // taps step pixels apart
+    float k_color, k_albedo;       // 1 / sigma_color_i^2, 1 / sigma_albedo^2
+    float sigma_depth_step;        // sigma_depth * step
+    uint32_t normal_squarings;
+};
+void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
+void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);
+void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s);
+
 // host-callable launchers (defined in kernels.hip)
 void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t *d_jump, hipStream_t s);
 void launch_generate(const GenerateArgs &a, hipStream_t s);

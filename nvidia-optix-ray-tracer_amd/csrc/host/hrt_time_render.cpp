@@ -1,9 +1,10 @@
 // hrt_time_render.cpp -- the reference's Time-mode program flow, headless, in the reference's own language:
 // main() (src/Global/Main.cu:12-50) -> RendererTime::commitRendererData (src/Global/RendererTime.cu:160-290)
-// -> RendererTime::startRender's frame loop (:373-520) with the window, camera input and denoiser left out.
-//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height]
+// -> RendererTime::startRender's frame loop (:373-520) with the window and camera input left out; the denoiser (denoiseOutput, :501-510)
+// runs with --denoise.
+//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
-// Per frame: hrt_pose_instances -> updateIAS -> launch + sync -> convert to 8 bit; the last frame is written as PPM.
+// Per frame: hrt_pose_instances -> updateIAS -> launch + sync -> (denoiseOutput) -> convert to 8 bit; the last frame is written as PPM.
 #include "renderer_host.hpp"
 #include "hrt_io.h"
 
@@ -28,7 +29,11 @@ template <typename T> static T *toDevice(const T *host, size_t count) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height]\n", argv[0]); return 2; }
+    // --denoise (anywhere): every frame goes through denoiseOutput before the conversion, as the reference's default display does
+    // (RendererTime.cu / RendererMesh.cu: launch -> denoiseOutput -> convertFloat4ToUchar4Kernel); without it the raw frame is shown, skipDenoise
+    bool denoise = false;
+    { int k = 1; for (int i = 1; i < argc; ++i) { if (std::strcmp(argv[i], "--denoise") == 0) denoise = true; else argv[k++] = argv[i]; } argc = k; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise]\n", argv[0]); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -142,6 +147,7 @@ int main(int argc, char **argv) {
         hrtCheckError(ctx, hrt_materials_set(ctx, perFile[0].records.data(), (uint32_t)perFile[0].records.size()));
         const HrtGlobalParams params{std::get<0>(perFile[0].ias), dev_stateArray};
         launch(ctx, params, raygen, 1);
+        if (denoise) denoiseOutput(ctx, params, raygen, color);
         hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr));
     }
     long frames = 0;
@@ -150,8 +156,8 @@ int main(int argc, char **argv) {
     // than in a normal run, where the steps are only enqueued), summed separately for the first frame of a file (materials, the update
     // that turns the identity-built IAS into the posed scene) and the others
     const bool breakdown = std::getenv("HRT_TIME_RENDER_BREAKDOWN") != nullptr;
-    enum { kMaterials, kPose, kUpdate, kLaunch, kRgba, kSteps };
-    const char *stepName[kSteps] = {"hrt_materials_set", "hrt_pose_instances", "hrt_tlas_update", "hrt_render_launch", "hrt_to_rgba8 + sync"};
+    enum { kMaterials, kPose, kUpdate, kLaunch, kDenoise, kRgba, kSteps };
+    const char *stepName[kSteps] = {"hrt_materials_set", "hrt_pose_instances", "hrt_tlas_update", "hrt_render_launch", "hrt_denoise_launch", "hrt_to_rgba8 + sync"};
     double stepMs[2][kSteps] = {{0}}; long stepFrames[2] = {0, 0};
     auto timed = [&](int first, int step, auto &&fn) {
         if (!breakdown) { fn(); return; }
@@ -181,6 +187,7 @@ int main(int argc, char **argv) {
             // (launch, conversion, then the frame's one synchronisation -- the reference synchronises between the two, RendererTime.cu:497-515,
             // because its denoiser runs on the host's schedule; nothing here needs the frame before the bytes exist)
             timed(first, kLaunch, [&] { hrtCheckError(ctx, hrt_render_launch(ctx, &params, &raygen, 1, nullptr, nullptr)); });
+            if (denoise) timed(first, kDenoise, [&] { denoiseOutput(ctx, params, raygen, color); });     // (in place: the colour buffer is not read again)
             timed(first, kRgba, [&] { hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr)); hrtCheckError(ctx, hrt_sync(ctx, nullptr)); });
         }
     }

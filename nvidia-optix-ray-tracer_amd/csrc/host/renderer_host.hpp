@@ -163,4 +163,12 @@ inline void launch(HrtContext *ctx, const HrtGlobalParams &params, const HrtRayG
     hrtCheckError(ctx, hrt_sync(ctx, stream));
 }
 
+// denoiseOutput, src/Global/RendererImpl.cu:680-710: the OptiX denoiser's slot, filled by the library's guided a-trous filter (include/hrt.h);
+// like the reference it reads the frame's colour buffer and leaves the result for convertFloat4ToUchar4Kernel (hrt_to_rgba8).  The
+// skipDenoise branch (Tab held) converts the colour buffer directly.
+inline void denoiseOutput(HrtContext *ctx, const HrtGlobalParams &params, const HrtRayGenParams &raygen, HrtFloat4 *output,
+                          const HrtDenoiseParams *denoiseParams = nullptr, hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_denoise_launch(ctx, &params, &raygen, denoiseParams, output, stream));
+}
+
 }  // namespace project

@@ -168,6 +168,7 @@ int hrt_ctx_destroy(HrtContext *ctx) {
         void *sp[] = {st.rays[0], st.rays[1], st.hit_tuvp, st.hit_inst, st.bin_items, st.chain, st.result, st.stages};
         for (void *p : sp) if (p) (void)hipFree(p);
     }
+    free_denoise_work(ctx);
     if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
     void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -280,7 +281,9 @@ static void launch_path_kernel(PathKernel k, const TraverseArgs &ta, bool has_sp
         case PathKernel::Round1: launch_paths_v1(ta, has_spheres, grid, s); break;
     }
 }
-static int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s) {
+extern "C++" {      // (helpers of hrt_internal.hpp, shared with hrt_denoise.cpp)
+namespace hrt {
+int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s) {
     if (ctx->table_tlas == handle && ctx->table_tlas_gen == t->generation && ctx->table_mat_gen == ctx->materials_generation) return HRT_OK;
     const uint32_t n = std::max(t->n_instances, 1u);
     std::vector<HitGroup> hg(n); std::vector<uint32_t> prog(n, 0);
@@ -310,6 +313,46 @@ static int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t
     ctx->table_tlas = handle; ctx->table_tlas_gen = t->generation; ctx->table_mat_gen = ctx->materials_generation;
     return HRT_OK;
 }
+
+// The traversal of hrt_trace_rays (and of the denoiser's guide pass, hrt_denoise.cpp): n_rays rays already in RayRec form through the
+// kernel hrt_render_launch runs in the context's configuration, hit records into tuvp / inst (t = tmax, inst = kMissPrim on a miss).
+// fetch: 8 x 32 slice counters, zeroed here.  Enqueued only.
+int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n_rays, float tmin, float tmax, bool any_hit,
+                  float4 *tuvp, uint32_t *inst, uint32_t *fetch, hipStream_t s) {
+    HIP_TRY(ctx, hipMemsetAsync(fetch, 0, sizeof(uint32_t) * 8 * 32, s));
+    TraverseArgs ta = traverse_args(ctx, t, tmin, tmax);
+    ta.fetch_counter = fetch; ta.leaf_hold = leaf_hold_for(ctx, t);
+    const bool count = (ctx->flags & HRT_CTX_COUNT) != 0;
+    if (!two_level_admitted(ctx, t, count)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only");
+    if (!count && ctx->fused > 0) {
+        // the production configuration: the rays go through the very kernel hrt_render_launch runs (fused path kernel, v_rcp_f32
+        // slab test, regeneration thresholds), each ray standing in for a pixel that is traced once and not shaded
+        ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
+        PathArgs &pa = ta.path;
+        pa.n_tile_pixels = n_rays; pa.first_pixel = 0; pa.width = n_rays; pa.height = 1; pa.spp = 1;
+        pa.trace_rays = rays; pa.trace_tuvp = tuvp; pa.trace_inst = inst; pa.trace_any = any_hit ? 1u : 0u;
+        pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
+        const PathKernelChoice pk = choose_path_kernel(ctx, t);
+        ta.postpone_pct = pk.kernel != PathKernel::Round1 ? ctx->fused_postpone_pct : ctx->postpone_pct;
+        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * pk.blocks_per_cu, (n_rays + 63u) / 64u);
+        Timer tm(ctx, s, HRT_K_PATHS);
+        launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s);
+    } else {
+        ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
+        ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;
+        ta.seg[0].count_nodes = any_hit ? &ctx->d_stats->nodes_any : &ctx->d_stats->nodes_closest;
+        ta.seg[0].count_prims = any_hit ? &ctx->d_stats->prims_any : &ctx->d_stats->prims_closest;
+        ta.refill_threshold = ctx->refill_threshold; ta.postpone_pct = ctx->postpone_pct; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
+        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * (uint32_t)ctx->traverse_blocks_per_cu, (n_rays + 63u) / 64u);
+        Timer tm(ctx, s, any_hit ? HRT_K_TRAVERSE_ANY : HRT_K_TRAVERSE);
+        launch_traverse(ta, count, t.has_spheres, grid, s);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
+}
+
+}  // namespace hrt
+}  // extern "C++"
 
 // What both execution modes of a launch work from (hrt_render_launch has checked the arguments, found the tree, refreshed the material
 // tables and uploaded the tile's row list).
@@ -752,35 +795,9 @@ int hrt_trace_rays(HrtContext *ctx, HrtTraversable tlas, const HrtFloat3 *d_orig
     HIP_TRY(ctx, hipMalloc((void **)&tuvp, sizeof(float4) * (size_t)n_rays));
     HIP_TRY(ctx, hipMalloc((void **)&inst, sizeof(uint32_t) * (size_t)n_rays));
     HIP_TRY(ctx, hipMalloc((void **)&fetch, sizeof(uint32_t) * 8 * 32));
-    HIP_TRY(ctx, hipMemsetAsync(fetch, 0, sizeof(uint32_t) * 8 * 32, s));
     launch_pack_rays(reinterpret_cast<const float *>(d_origins), reinterpret_cast<const float *>(d_directions), n_rays, rays, s);
-    TraverseArgs ta = traverse_args(ctx, *t, tmin, tmax);
-    ta.fetch_counter = fetch; ta.leaf_hold = leaf_hold_for(ctx, *t);
-    const bool count = (ctx->flags & HRT_CTX_COUNT) != 0;
-    if (!two_level_admitted(ctx, *t, count)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only");
-    if (!count && ctx->fused > 0) {
-        // the production configuration: the rays go through the very kernel hrt_render_launch runs (fused path kernel, v_rcp_f32
-        // slab test, regeneration thresholds), each ray standing in for a pixel that is traced once and not shaded
-        ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
-        PathArgs &pa = ta.path;
-        pa.n_tile_pixels = n_rays; pa.first_pixel = 0; pa.width = n_rays; pa.height = 1; pa.spp = 1;
-        pa.trace_rays = rays; pa.trace_tuvp = tuvp; pa.trace_inst = inst; pa.trace_any = any_hit ? 1u : 0u;
-        pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
-        const PathKernelChoice pk = choose_path_kernel(ctx, *t);
-        ta.postpone_pct = pk.kernel != PathKernel::Round1 ? ctx->fused_postpone_pct : ctx->postpone_pct;
-        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * pk.blocks_per_cu, (n_rays + 63u) / 64u);
-        Timer tm(ctx, s, HRT_K_PATHS);
-        launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s);
-    } else {
-        ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
-        ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;
-        ta.seg[0].count_nodes = any_hit ? &ctx->d_stats->nodes_any : &ctx->d_stats->nodes_closest;
-        ta.seg[0].count_prims = any_hit ? &ctx->d_stats->prims_any : &ctx->d_stats->prims_closest;
-        ta.refill_threshold = ctx->refill_threshold; ta.postpone_pct = ctx->postpone_pct; ta.fetch_chunk = (uint32_t)ctx->fetch_chunk;
-        const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * (uint32_t)ctx->traverse_blocks_per_cu, (n_rays + 63u) / 64u);
-        Timer tm(ctx, s, any_hit ? HRT_K_TRAVERSE_ANY : HRT_K_TRAVERSE);
-        launch_traverse(ta, count, t->has_spheres, grid, s);
-    }
+    const int rc = trace_records(ctx, *t, rays, n_rays, tmin, tmax, any_hit != 0, tuvp, inst, fetch, s);
+    if (rc != HRT_OK) return rc;
     launch_unpack_hits(tuvp, inst, n_rays, d_t, d_u, d_v, d_prim, d_inst, s);
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ctx, HRT_ERR_HIP, "hrt_trace_rays: %s", hipGetErrorString(e));

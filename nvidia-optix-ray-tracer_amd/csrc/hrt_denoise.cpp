@@ -1,0 +1,167 @@
+// hrt_denoise.cpp -- C ABI of the denoiser (include/hrt.h "denoiser"): what stands in for denoiseOutput, src/Global/RendererImpl.cu:680-710.
+// Guide pass: the primary rays of the frame (denoise.hip k_denoise_rays) through hrt_trace_rays' traversal (hrt_api.cpp trace_records: the
+// path kernel in the context's configuration, flattened and two-level trees alike), their hits turned into HrtDenoiseGuide records with
+// the material tables of the launch.  Filter: `iterations` a-trous passes, one launch each, ping-ponging between two frames the context
+// owns.  Every call only enqueues work (the material tables' upload after hrt_materials_set synchronises once, as in hrt_render_launch).
+#include "hrt_internal.hpp"
+
+namespace hrt {
+
+void free_denoise_work(HrtContext *ctx) {
+    DenoiseWork &d = ctx->denoise;
+    void *ptrs[] = {d.rays, d.tuvp, d.inst, d.guides, d.frame[0], d.frame[1], d.fetch};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    d = DenoiseWork{};
+}
+
+namespace {
+
+constexpr uint32_t kMaxDenoiseSide = 1u << 16;       // (the filter's pixel arithmetic is in int: sides plus 2 * 2^15 stay far from overflow)
+
+int check_frame(HrtContext *ctx, uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || width > kMaxDenoiseSide || height > kMaxDenoiseSide || (uint64_t)width * height > 0xffffffffull)
+        return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", width, height);
+    return HRT_OK;
+}
+
+// the per-pixel arrays for n pixels: the guide pass's (trace) or the filter's two frames
+int ensure_work(HrtContext *ctx, uint32_t n, bool trace) {
+    DenoiseWork &d = ctx->denoise;
+    if (n > d.capacity) {
+        free_denoise_work(ctx);
+        HIP_TRY(ctx, hipMalloc((void **)&d.fetch, sizeof(uint32_t) * 8 * 32));
+        d.capacity = n;
+    }
+    if (trace && !d.rays) {
+        HIP_TRY(ctx, hipMalloc((void **)&d.rays, sizeof(RayRec) * (size_t)d.capacity));
+        HIP_TRY(ctx, hipMalloc((void **)&d.tuvp, sizeof(float4) * (size_t)d.capacity));
+        HIP_TRY(ctx, hipMalloc((void **)&d.inst, sizeof(uint32_t) * (size_t)d.capacity));
+        HIP_TRY(ctx, hipMalloc((void **)&d.guides, sizeof(uint4) * (size_t)d.capacity));
+    }
+    if (!trace && !d.frame[0]) {
+        HIP_TRY(ctx, hipMalloc((void **)&d.frame[0], sizeof(float4) * (size_t)d.capacity));
+        HIP_TRY(ctx, hipMalloc((void **)&d.frame[1], sizeof(float4) * (size_t)d.capacity));
+    }
+    return HRT_OK;
+}
+
+bool positive_finite(float x) { return std::isfinite(x) && x > 0.0f; }
+
+// the parameters (NULL: the defaults) and the constants of every pass; HRT_ERR_INVALID when one is out of range
+int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, std::vector<DenoisePassArgs> &passes) {
+    HrtDenoiseParams p;
+    hrt_denoise_default_params(&p);
+    if (h_dparams) p = *h_dparams;
+    if (p.iterations < 1 || p.iterations > 16 || p.normal_power_log2 > 8 || p.reserved != 0 ||
+        !positive_finite(p.sigma_color) || !positive_finite(p.sigma_albedo) || !positive_finite(p.sigma_depth))
+        return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range (iterations 1..16, sigmas > 0 and finite, normal_power_log2 <= 8, reserved 0)");
+    passes.assign(p.iterations, DenoisePassArgs{});
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        DenoisePassArgs &a = passes[i];
+        a.step = 1u << i;
+        const float sc = std::ldexp(p.sigma_color, -(int)i);                          // sigma_color * 2^-i, exact above the subnormals
+        a.k_color = 1.0f / (sc * sc);
+        a.k_albedo = 1.0f / (p.sigma_albedo * p.sigma_albedo);
+        a.sigma_depth_step = p.sigma_depth * (float)a.step;
+        a.normal_squarings = p.normal_power_log2;
+        if (!positive_finite(a.k_color) || !positive_finite(a.k_albedo) || !positive_finite(a.sigma_depth_step))
+            return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
+    }
+    return HRT_OK;
+}
+
+int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, float4 *out, uint32_t width, uint32_t height,
+               std::vector<DenoisePassArgs> &passes, hipStream_t s) {
+    int rc = ensure_work(ctx, width * height, false);
+    if (rc != HRT_OK) return rc;
+    const float4 *src = color;
+    const size_t n = passes.size();
+    for (size_t i = 0; i < n; ++i) {
+        DenoisePassArgs &a = passes[i];
+        // the last pass writes d_out -- unless d_out is its source (one pass in place), which goes through a frame of the context's
+        float4 *dst = i + 1 < n || out == src ? ctx->denoise.frame[i & 1] : out;
+        a.src = src; a.guides = guides; a.dst = dst; a.width = width; a.height = height;
+        launch_denoise_pass(a, s);
+        src = dst;
+    }
+    if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
+}
+
+// guides == NULL: into the context's own (hrt_denoise_launch)
+int run_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg, uint4 *guides, hipStream_t s) {
+    if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
+    Tlas *t;
+    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
+      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
+      t = it->second.get(); }
+    const uint32_t n = rg->width * rg->height;
+    int rc = refresh_tables(ctx, h_params->handle, t, s);
+    if (rc == HRT_OK) rc = ensure_work(ctx, n, true);
+    if (rc != HRT_OK) return rc;
+    DenoiseWork &d = ctx->denoise;
+    DenoiseRayArgs ra{};
+    ra.rays = d.rays; ra.width = rg->width; ra.height = rg->height;
+    std::memcpy(ra.center, &rg->cameraCenter, 12); std::memcpy(ra.U, &rg->cameraU, 12); std::memcpy(ra.V, &rg->cameraV, 12); std::memcpy(ra.W, &rg->cameraW, 12);
+    launch_denoise_rays(ra, s);
+    rc = trace_records(ctx, *t, d.rays, n, kFloatZero, kFloatInfinity, false, d.tuvp, d.inst, d.fetch, s);      // Shader.cu:266
+    if (rc != HRT_OK) return rc;
+    DenoiseGuideArgs ga{};
+    ga.rays = d.rays; ga.tuvp = d.tuvp; ga.inst = d.inst; ga.n = n;
+    ga.hitgroups = ctx->d_hitgroups; ga.inst_program = ctx->d_inst_program; ga.guides = guides ? guides : d.guides;
+    launch_denoise_guides(ga, s);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_tlas = h_params->handle;
+    return HRT_OK;
+}
+
+}  // namespace
+}  // namespace hrt
+
+
+extern "C" {
+
+int hrt_denoise_default_params(HrtDenoiseParams *out) {
+    if (!out) return HRT_ERR_INVALID;
+    // (profiles/r05_denoise.txt: the sweep these come from)
+    *out = HrtDenoiseParams{5u, 0.5f, 0.1f, 0.02f, 3u, 0u};
+    return HRT_OK;
+}
+
+int hrt_denoise_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, HrtDenoiseGuide *d_guides, void *stream) {
+    if (!ctx || !h_params || !h_raygen || !d_guides) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    int rc = check_frame(ctx, h_raygen->width, h_raygen->height);
+    if (rc != HRT_OK) return rc;
+    return run_guides(ctx, h_params, h_raygen, reinterpret_cast<uint4 *>(d_guides), (hipStream_t)stream);
+}
+
+int hrt_denoise_filter(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDenoiseGuide *d_guides, HrtFloat4 *d_out,
+                       uint32_t width, uint32_t height, const HrtDenoiseParams *h_dparams, void *stream) {
+    if (!ctx || !d_color || !d_guides || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    int rc = check_frame(ctx, width, height);
+    std::vector<DenoisePassArgs> passes;
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
+    if (rc != HRT_OK) return rc;
+    return run_filter(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), reinterpret_cast<float4 *>(d_out),
+                      width, height, passes, (hipStream_t)stream);
+}
+
+int hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
+                       HrtFloat4 *d_out, void *stream) {
+    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    int rc = check_frame(ctx, h_raygen->width, h_raygen->height);
+    std::vector<DenoisePassArgs> passes;
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
+    const hipStream_t s = (hipStream_t)stream;
+    if (rc == HRT_OK) rc = run_guides(ctx, h_params, h_raygen, nullptr, s);
+    if (rc != HRT_OK) return rc;
+    return run_filter(ctx, reinterpret_cast<const float4 *>(h_raygen->colorBuffer), ctx->denoise.guides, reinterpret_cast<float4 *>(d_out),
+                      h_raygen->width, h_raygen->height, passes, s);
+}
+
+}  // extern "C"

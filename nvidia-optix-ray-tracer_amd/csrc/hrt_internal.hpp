@@ -115,6 +115,16 @@ struct Workspace {
     float4 *primary_cache = nullptr; uint32_t primary_cache_lanes = 0;                     // HRT_CTX_REUSE_PRIMARY: two float4 per lane of the path kernel's grid
 };
 
+// the denoiser's working memory (hrt_denoise.cpp), grown on demand: the guide pass's rays and hit records, the guides of hrt_denoise_launch,
+// the filter's two ping-pong frames
+struct DenoiseWork {
+    uint32_t capacity = 0;                  // pixels each of the per-pixel arrays below holds
+    RayRec *rays = nullptr; float4 *tuvp = nullptr; uint32_t *inst = nullptr;
+    uint4 *guides = nullptr;
+    float4 *frame[2] = {nullptr, nullptr};
+    uint32_t *fetch = nullptr;              // 8 x 32 slice counters of the traversal
+};
+
 struct TimedSpan { int kind; hipEvent_t a, b; };
 
 // working memory of the device builds, kept by the context between builds (a few arenas: builds may run on several loader threads)
@@ -215,6 +225,7 @@ struct HrtContext {
     int substreams = 0;                         // sub-tiles rendered on their own HIP streams so that one's tail overlaps another's bulk
     std::vector<hipStream_t> sub_streams; std::vector<hipEvent_t> sub_done; hipEvent_t ev_begin = nullptr;
     hipStream_t graph_stream = nullptr; hipEvent_t ev_graph_done = nullptr;     // wavefront mode's graph capture when the caller's stream is the null stream
+    hrt::DenoiseWork denoise;                   // hrt_denoise_* (hrt_denoise.cpp)
 };
 
 namespace hrt {
@@ -249,6 +260,13 @@ struct Timer {
 };
 
 void drain_spans(HrtContext *ctx);
+
+// hrt_api.cpp: the launch's material tables for a TLAS, and hrt_trace_rays' traversal of rays in RayRec form (enqueued only)
+int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s);
+int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n_rays, float tmin, float tmax, bool any_hit,
+                  float4 *tuvp, uint32_t *inst, uint32_t *fetch, hipStream_t s);
+// hrt_denoise.cpp
+void free_denoise_work(HrtContext *ctx);
 
 // hrt_accel.cpp
 hrt::ScratchArena scratch_acquire(HrtContext *ctx, size_t bytes);      // {nullptr, 0} when the device is out of memory

@@ -100,25 +100,31 @@ __device__ __forceinline__ V3 random_space_vector(Xorwow &rng) {
 // hit point of a ray, shader/Shader.cu:111-114
 __device__ __forceinline__ V3 hit_point(V3 rayOrigin, V3 rayDirection, float t) { return add3(rayOrigin, muls3(rayDirection, t)); }
 
-template <bool kSphere, bool kRough>
-__device__ __forceinline__ void scatter_at(const HitGroup &hg, V3 hitPoint, V3 rayDirection, float u, float v,
-                                           uint32_t primitiveIndex, Xorwow &rng, V3 &reflectDirection) {
-    V3 normalVector;
-    if (kSphere) {                                                        // :122-136
+// the normal a closest-hit program scatters about, shader/Shader.cu:122-155: the sphere's (hitPoint - centre) / radius with the
+// object-space centre (quirk Q1) or the interpolated vertex normal, neither transformed nor normalised (Q2), turned against the ray.
+// One definition for the programs below and the denoiser's guide pass (denoise.hip), which normalises it as the depth-1 AOV does (:216-227).
+template <bool HAS_SPHERES>
+__device__ __forceinline__ V3 hit_normal(bool sphere, const HitGroup &hg, V3 hitPoint, V3 rayDirection, float u, float v, uint32_t primitiveIndex) {
+    V3 _normal;
+    if (HAS_SPHERES && sphere) {                                          // :122-136
         const float *cp = reinterpret_cast<const float *>(hg.ptr0) + 3 * (size_t)primitiveIndex;
         const V3 sphereCenter = mk3(cp[0], cp[1], cp[2]);
         const float sphereRadius = reinterpret_cast<const float *>(hg.ptr1)[primitiveIndex];
-        const V3 outwardNormal = divs3(sub3(hitPoint, sphereCenter), sphereRadius);
-        const bool hitFrontFace = dot3(rayDirection, outwardNormal) < 0.0f;
-        normalVector = hitFrontFace ? outwardNormal : neg3(outwardNormal);
+        _normal = divs3(sub3(hitPoint, sphereCenter), sphereRadius);
     } else {                                                              // :137-155
         const float *np = reinterpret_cast<const float *>(hg.ptr0) + 9 * (size_t)primitiveIndex;
         const V3 n1 = mk3(np[0], np[1], np[2]), n2 = mk3(np[3], np[4], np[5]), n3 = mk3(np[6], np[7], np[8]);
         const float w = 1.0f - u - v;
-        const V3 _normal = add3(add3(muls3(n1, w), muls3(n2, u)), muls3(n3, v));
-        const bool hitFrontFace = dot3(rayDirection, _normal) < 0.0f;
-        normalVector = hitFrontFace ? _normal : neg3(_normal);
+        _normal = add3(add3(muls3(n1, w), muls3(n2, u)), muls3(n3, v));
     }
+    const bool hitFrontFace = dot3(rayDirection, _normal) < 0.0f;
+    return hitFrontFace ? _normal : neg3(_normal);
+}
+
+template <bool kSphere, bool kRough>
+__device__ __forceinline__ void scatter_at(const HitGroup &hg, V3 hitPoint, V3 rayDirection, float u, float v,
+                                           uint32_t primitiveIndex, Xorwow &rng, V3 &reflectDirection) {
+    const V3 normalVector = hit_normal<kSphere>(kSphere, hg, hitPoint, rayDirection, u, v, primitiveIndex);
     if (kRough) {                                                         // :169-179
         reflectDirection = add3(normalVector, random_space_vector(rng));
         if (fabsf(len2_3(reflectDirection) - kFloatZero * kFloatZero) < kFloatZero) reflectDirection = normalVector;
@@ -150,20 +156,7 @@ __device__ __forceinline__ void scatter_programs(uint32_t program, const HitGrou
                                                  uint32_t primitiveIndex, Xorwow &rng, V3 &hitPoint, V3 &reflectDirection) {
     hitPoint = hit_point(rayOrigin, rayDirection, t);                     // :114
     const bool rough = (program & 1u) == 0u;                              // kProgramSphereRough = 0, kProgramTriangleRough = 2
-    V3 _normal;
-    if (HAS_SPHERES && program < (uint32_t)kProgramTriangleRough) {       // :122-136
-        const float *cp = reinterpret_cast<const float *>(hg.ptr0) + 3 * (size_t)primitiveIndex;
-        const V3 sphereCenter = mk3(cp[0], cp[1], cp[2]);
-        const float sphereRadius = reinterpret_cast<const float *>(hg.ptr1)[primitiveIndex];
-        _normal = divs3(sub3(hitPoint, sphereCenter), sphereRadius);
-    } else {                                                              // :137-155
-        const float *np = reinterpret_cast<const float *>(hg.ptr0) + 9 * (size_t)primitiveIndex;
-        const V3 n1 = mk3(np[0], np[1], np[2]), n2 = mk3(np[3], np[4], np[5]), n3 = mk3(np[6], np[7], np[8]);
-        const float w = 1.0f - u - v;
-        _normal = add3(add3(muls3(n1, w), muls3(n2, u)), muls3(n3, v));
-    }
-    const bool hitFrontFace = dot3(rayDirection, _normal) < 0.0f;
-    const V3 normalVector = hitFrontFace ? _normal : neg3(_normal);
+    const V3 normalVector = hit_normal<HAS_SPHERES>(program < (uint32_t)kProgramTriangleRough, hg, hitPoint, rayDirection, u, v, primitiveIndex);
     V3 rsv = mk3(0.0f, 0.0f, 0.0f);
     if (rough || hg.fuzz > 0.0f) rsv = random_space_vector(rng);
     if (rough) {                                                          // :169-179

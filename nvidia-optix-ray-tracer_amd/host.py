@@ -243,7 +243,7 @@ class Renderer:
         return out
 
     # ---- the launch ----
-    def render(self, spp=1, tile=None, sync=True):
+    def _launch_blocks(self):
         from . import GlobalParams, RayGenParams, Float3
         center, u, v, w = self.cam
         params = GlobalParams(self.tlas, self.states)
@@ -256,6 +256,10 @@ class Renderer:
         rg.cameraU = Float3(*[float(x) for x in u])
         rg.cameraV = Float3(*[float(x) for x in v])
         rg.cameraW = Float3(*[float(x) for x in w])
+        return params, rg
+
+    def render(self, spp=1, tile=None, sync=True):
+        params, rg = self._launch_blocks()
         st = self._stream()
         self._check(self.lib.hrt_render_launch(self.ctx, C.byref(params), C.byref(rg), spp,
                                                C.byref(tile) if tile is not None else None, st), "hrt_render_launch")
@@ -267,6 +271,66 @@ class Renderer:
         out = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=self.device)
         self._check(self.lib.hrt_to_rgba8(self.ctx, self.color.data_ptr(), out.data_ptr(), self.width, self.height,
                                           self._stream()), "hrt_to_rgba8")
+        self._torch.cuda.synchronize(self.device)
+        return out
+
+    # ---- the denoiser (denoiseOutput, src/Global/RendererImpl.cu:680-710) ----
+    def _denoise_params(self, params):
+        from . import DenoiseParams
+        if params is None:
+            return None
+        if isinstance(params, DenoiseParams):
+            return params
+        p = DenoiseParams()
+        self._check(self.lib.hrt_denoise_default_params(C.byref(p)), "hrt_denoise_default_params")
+        for k, v in dict(params).items():
+            setattr(p, k, v)
+        return p
+
+    def denoise_guides(self):
+        """The primary-hit guides of the current frame and camera: (H, W, 8) uint16 tensor -- per pixel the HrtDenoiseGuide record,
+        normal[3] and albedo[3] as IEEE halves, then the hit distance as two halves of a float (``.view(torch.float32)`` of
+        ``[..., 6:8]``; +inf on a miss)."""
+        torch = self._torch
+        params, rg = self._launch_blocks()
+        guides = torch.empty((self.height, self.width, 8), dtype=torch.int16, device=self.device)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_guides(self.ctx, C.byref(params), C.byref(rg), guides.data_ptr(), st), "hrt_denoise_guides")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return guides
+
+    def denoise_filter(self, color, guides, params=None, out=None):
+        """The filter alone: ``color`` (H, W, 4) float32 and ``guides`` (H, W, 8) 16-bit (denoise_guides) device tensors -> a new
+        (H, W, 4) tensor, or ``out`` (which may be ``color``).  params: None (the defaults), a DenoiseParams or a dict of its fields."""
+        torch = self._torch
+        h, w = int(color.shape[0]), int(color.shape[1])
+        assert color.is_contiguous() and guides.is_contiguous() and tuple(guides.shape) == (h, w, 8) and guides.element_size() == 2
+        out = torch.empty_like(color) if out is None else out
+        p = self._denoise_params(params)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_filter(self.ctx, color.data_ptr(), guides.data_ptr(), out.data_ptr(), w, h,
+                                                C.byref(p) if p is not None else None, st), "hrt_denoise_filter")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return out
+
+    def denoise(self, params=None, out=None):
+        """denoiseOutput: the guides of the current frame + the filter of the colour buffer (``self.color``, what the last render
+        wrote) -> a new (H, W, 4) float32 tensor, or ``out`` (which may be ``self.color``).  The AOV buffers are not touched."""
+        params_blk, rg = self._launch_blocks()
+        out = self._torch.empty_like(self.color) if out is None else out
+        p = self._denoise_params(params)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
+                                                out.data_ptr(), st), "hrt_denoise_launch")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return out
+
+    def to_rgba8_of(self, frame):
+        """convertFloat4ToUchar4Kernel of any (H, W, 4) float32 device tensor (to_rgba8: of the colour buffer)."""
+        torch = self._torch
+        out = torch.empty((frame.shape[0], frame.shape[1], 4), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.hrt_to_rgba8(self.ctx, frame.data_ptr(), out.data_ptr(), frame.shape[1], frame.shape[0], self._stream()),
+                    "hrt_to_rgba8")
         self._torch.cuda.synchronize(self.device)
         return out
 

@@ -1,0 +1,72 @@
+"""What the denoiser costs at 1080p next to the 1-spp frame it cleans: C4 (bench.py's scene) and the shipped sample (tests/golden/files,
+first frame of Time mode).  Per scene: a 1-spp render, hrt_denoise_guides, hrt_denoise_filter and hrt_denoise_launch, each the median
+of --reps timed repetitions (HIP events around the call, after a warm-up).  Under `rocprofv3 --kernel-trace --stats` the per-kernel
+split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_denoise_pass (one launch per filter pass).
+
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample]
+"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def median_ms(torch, fn, reps):
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    times.sort()
+    return times[len(times) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--scenes", default="c4,sample")
+    args = ap.parse_args()
+    import torch
+    hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
+    io = importlib.import_module("nvidia-optix-ray-tracer_amd.io")
+    w, h = args.width, args.height
+    for name in args.scenes.split(","):
+        r = hrt.Renderer(0, 0)
+        if name == "c4":
+            r.load_scene(hrt.scenes.BASELINE_CONFIGS["C4"]())
+            r.set_frame(w, h, hrt.scenes.SEED_SALT, aov=False)
+        else:
+            tm = io.time_mode_scene(ROOT / "tests" / "golden" / "files" / "config.json", width=w, height=h)
+            cfg = tm["config"]
+            r.load_scene(tm["scene"])
+            r.set_frame(w, h, hrt.scenes.SEED_SALT, aov=False)
+            r.pose_instances(tm["states"][0], tm["states"][min(1, len(tm["states"]) - 1)], float(tm["durations"][0]), 0,
+                             tm["frame_counts"][0], first_instance=tm["n_extra"], offset=cfg["particle-shift"], scale=cfg["particle-scale"])
+        out = torch.empty_like(r.color)
+        r.render(1)
+        guides = r.denoise_guides()
+        r.denoise_filter(r.color, guides, out=out)
+        r.denoise(out=out)
+        res = {"scene": name, "width": w, "height": h,
+               "render_1spp_ms": median_ms(torch, lambda: r.render(1, sync=False), args.reps),
+               "guides_ms": median_ms(torch, r.denoise_guides, args.reps),
+               "filter_ms": median_ms(torch, lambda: r.denoise_filter(r.color, guides, out=out), args.reps),
+               "denoise_launch_ms": median_ms(torch, lambda: r.denoise(out=out), args.reps)}
+        res["filter_per_pass_ms"] = res["filter_ms"] / 5
+        print(json.dumps(res), flush=True)
+        r.close()
+
+
+if __name__ == "__main__":
+    main()
