@@ -229,20 +229,10 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                 const uint64_t need = __ballot(!alive && !have_pixel && !want_primary);
                 if (need != 0ull && !exhausted) {
                     if (wbeg >= wend) {
-                        for (uint32_t k = kstart; k < kFetchShards && wbeg >= wend; ++k) {
-                            const uint32_t shard = (home_shard + k) & (kFetchShards - 1);
-                            uint32_t c = 0;
-                            if (tx == 0u) c = atomicAdd(a.fetch_counter + shard * kFetchShardStride, 1u);
-                            c = (uint32_t)__shfl((int)c, 0);
-                            const uint64_t q = (uint64_t)c * kFetchShards + shard;          // the q-th slice handed out ...
-                            if (q * (uint64_t)a.fetch_chunk < (uint64_t)n_rays) {
-                                // ... is slice slice_order[q] of the tile: the expensive slices first, so that the render
-                                // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
-                                const uint64_t beg = (a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q) * (uint64_t)a.fetch_chunk;
-                                wbeg = (uint32_t)beg;
-                                wend = (uint32_t)(beg + a.fetch_chunk < (uint64_t)n_rays ? beg + a.fetch_chunk : (uint64_t)n_rays);
-                            } else kstart = k + 1;
-                        }
+                        // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
+                        // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
+                        wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_rays, tx,
+                                        [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
                         if (wbeg >= wend) exhausted = true;
                     }
                     if (!exhausted) {
@@ -288,17 +278,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
         // ---- refill idle lanes from the wave's slice ----
         if (!exhausted && (n_idle >= (uint32_t)a.refill_threshold || idle == ~0ull)) {
             if (wbeg >= wend) {
-                for (uint32_t k = kstart; k < kFetchShards && wbeg >= wend; ++k) {
-                    const uint32_t shard = (home_shard + k) & (kFetchShards - 1);
-                    uint32_t c = 0;
-                    if (tx == 0u) c = atomicAdd(a.fetch_counter + shard * kFetchShardStride, 1u);
-                    c = (uint32_t)__shfl((int)c, 0);
-                    const uint64_t beg = ((uint64_t)c * kFetchShards + shard) * (uint64_t)a.fetch_chunk;
-                    if (beg < (uint64_t)n_rays) {
-                        wbeg = (uint32_t)beg;
-                        wend = (uint32_t)(beg + a.fetch_chunk < (uint64_t)n_rays ? beg + a.fetch_chunk : (uint64_t)n_rays);
-                    } else kstart = k + 1;             // this shard is drained for good
-                }
+                wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_rays, tx, [](uint64_t q) { return q; });
                 if (wbeg >= wend) exhausted = true;
             }
             if (!exhausted) {

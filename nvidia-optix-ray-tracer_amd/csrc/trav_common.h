@@ -20,6 +20,27 @@ __device__ __forceinline__ uint32_t lane_prefix(uint64_t mask) {
 }
 __device__ __forceinline__ uint32_t wave_first_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
+// The wave's next slice [wbeg, wend) of `n` items (pixels, rays): slices of `fetch_chunk` items are handed out by kFetchShards
+// counters on a line of their own each (chunk c of shard s is the (c * kFetchShards + s)-th slice handed out), and slice_of maps that
+// number to the slice it stands for.  A wave starts at its home shard and goes round the others once that is drained; shards found
+// drained are skipped for good (kstart).  Leaves wbeg >= wend when nothing is left.  Wave-uniform; lane 0 asks.
+template <class SliceOf>
+__device__ __forceinline__ void wave_next_slice(uint32_t &wbeg, uint32_t &wend, uint32_t &kstart, uint32_t home_shard, uint32_t *counters, uint32_t fetch_chunk,
+                                                uint32_t n, uint32_t tx, SliceOf slice_of) {
+    for (uint32_t k = kstart; k < kFetchShards && wbeg >= wend; ++k) {
+        const uint32_t shard = (home_shard + k) & (kFetchShards - 1);
+        uint32_t c = 0;
+        if (tx == 0u) c = atomicAdd(counters + shard * kFetchShardStride, 1u);
+        c = (uint32_t)__shfl((int)c, 0);
+        const uint64_t q = (uint64_t)c * kFetchShards + shard;
+        if (q * (uint64_t)fetch_chunk < (uint64_t)n) {
+            const uint64_t beg = slice_of(q) * (uint64_t)fetch_chunk;
+            wbeg = (uint32_t)beg;
+            wend = (uint32_t)(beg + fetch_chunk < (uint64_t)n ? beg + fetch_chunk : (uint64_t)n);
+        } else kstart = k + 1;
+    }
+}
+
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 mk3(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ V3 add3(V3 a, V3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
@@ -327,36 +348,6 @@ __device__ __forceinline__ void issue_node_loads(const void *p, u32x4 &a, u32x4 
                  "global_load_dwordx4 %3, %5, off offset:48\n\t"
                  "global_load_dwordx4 %4, %5, off offset:64"
                  : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d), "=&v"(e) : "v"(p) : "memory");
-}
-// The same loads for a subset of the lanes (mask != 0, a subset of the lanes that are active here; wave-uniform): the vector
-// memory pipeline returns 16 bytes per ACTIVE lane and instruction whatever the address -- 64 B per clock and CU in all, the
-// resource that bounds the path kernel (profiles/r02_exp_bounds.txt) -- so lanes that have no primitive / node to fetch
-// are switched off for the loads instead of fetching record 0.  Registers of the lanes left out keep their old contents
-// (the operands are in/out: declare the registers once, outside the loop).
-__device__ __forceinline__ void issue_prim_loads_masked(uint64_t mask, const void *p, f32x4 &a, f32x4 &b, f32x4 &c) {
-    uint64_t save;
-    asm volatile("s_mov_b64 %3, exec\n\t"
-                 "s_mov_b64 exec, %5\n\t"
-                 "global_load_dwordx4 %0, %4, off\n\t"
-                 "global_load_dwordx4 %1, %4, off offset:16\n\t"
-                 "global_load_dwordx4 %2, %4, off offset:32\n\t"
-                 "s_mov_b64 exec, %3"
-                 : "+v"(a), "+v"(b), "+v"(c), "=&s"(save) : "v"(p), "s"(mask) : "memory");
-}
-__device__ __forceinline__ void issue_node_loads_masked(uint64_t mask, const void *p, u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, u32x4 &e) {
-    uint64_t save;
-    asm volatile("s_mov_b64 %5, exec\n\t"
-                 "s_mov_b64 exec, %7\n\t"
-                 "global_load_dwordx4 %0, %6, off\n\t"
-                 "global_load_dwordx4 %1, %6, off offset:16\n\t"
-                 "global_load_dwordx4 %2, %6, off offset:32\n\t"
-                 "global_load_dwordx4 %3, %6, off offset:48\n\t"
-                 "global_load_dwordx4 %4, %6, off offset:64\n\t"
-                 "s_mov_b64 exec, %5"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "=&s"(save) : "v"(p), "s"(mask) : "memory");
-}
-__device__ __forceinline__ void wait_all_prim_loads(f32x4 &a, f32x4 &b, f32x4 &c) {       // no node loads behind them
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c) :: "memory");
 }
 __device__ __forceinline__ void wait_prim_loads(f32x4 &a, f32x4 &b, f32x4 &c) {
     asm volatile("s_waitcnt vmcnt(5)" : "+v"(a), "+v"(b), "+v"(c) :: "memory");

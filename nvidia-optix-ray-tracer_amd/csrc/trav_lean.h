@@ -1,4 +1,4 @@
-// trav_lean.h -- the traversal step of the production path kernel (fused.hip), written for INSTRUCTION COUNT.
+// trav_lean.h -- the building blocks of the path kernels' traversal step (the loop itself: trav_loop.h), written for INSTRUCTION COUNT.
 //
 // What round 2 measured (profiles/r02_valu_issue_patterns_microbench.txt, r02_exp_bounds.txt): a gfx950 SIMD issues about one
 // instruction of ANY kind per 2.4 cycles -- scalar instructions, mask saves / restores and branches count like vector ones --
@@ -27,13 +27,20 @@ constexpr int kLeafStackLds = 4;       // leaf groups per lane in LDS (never mor
 struct LeanLane {
     TravState s;                 // ray, reciprocal direction, octant, best hit; s.cur = sibling group in hand, s.ptri = leaf group in hand
     int nsp, lsp;                // top of the node stack / entries on the leaf stack
-    int base;                    // bottom of the node stack: entries below have been given away (tail splitting, fused.hip)
+    int base;                    // bottom of the node stack: entries below have been given away (tail splitting, trav_loop.h)
     uint32_t nidx, pidx;         // node / primitive to fetch next (kNoWork: none)
 };
 
 __device__ __forceinline__ void lean_reset(LeanLane &L) {
     L.s.cur = make_uint2(0u, 0u); L.s.ptri = make_uint2(0u, 0u);
     L.nsp = 0; L.base = 0; L.lsp = 0; L.nidx = kNoWork; L.pidx = kNoWork;
+}
+
+// a lane without a ray: nothing to fetch, a ray and a best hit that are harmless to compute with (the wave-wide steps run for every lane)
+__device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray) {
+    lean_reset(L);
+    L.s.bt = tmax_ray; L.s.bu = 0.0f; L.s.bv = 0.0f; L.s.bprim = kMissPrim; L.s.binst = kMissPrim;
+    L.s.ox = L.s.oy = L.s.oz = 0.0f; L.s.dx = L.s.dy = 0.0f; L.s.dz = 1.0f; L.s.idx = L.s.idy = L.s.idz = 1.0f; L.s.oct_inv4 = 0u;
 }
 
 // a new ray: the root is its first node
@@ -90,7 +97,7 @@ __device__ __forceinline__ void lean_node(const TravState &s, float tmin, const 
 }
 
 // the next node of a lane that has just been handed a sibling group (tail splitting): its nearest child -- step (7) of
-// lean_bookkeeping_asm in C++
+// lean_bookkeeping_masked in C++
 __device__ __forceinline__ void lean_pick_node(LeanLane &L) {
     TravState &s = L.s;
     const uint32_t hits_imask = s.cur.y;
@@ -100,9 +107,13 @@ __device__ __forceinline__ void lean_pick_node(LeanLane &L) {
     L.nidx = s.cur.x + (uint32_t)__popc(hits_imask & ~(0xffffffffu << slot_index));
 }
 
-// Hand-issued loads like issue_*_loads_masked (trav_common.h), addressed as uniform base + 32-bit byte offset per lane (one
-// v_mul_lo_u32 per record instead of a 64-bit multiply-add and its operand moves).  Lanes outside `mask` load nothing and keep
-// their registers; an empty mask is fine: the loads still count in vmcnt, in order.
+// Hand-issued loads like issue_*_loads (trav_common.h) for a subset of the lanes (`mask`: a subset of the lanes that are active
+// here; wave-uniform): the vector memory pipeline returns 16 bytes per ACTIVE lane and instruction whatever the address -- 64 B per
+// clock and CU in all, the resource that bounds the path kernel (profiles/r02_exp_bounds.txt) -- so lanes that have no primitive /
+// node to fetch are switched off for the loads instead of fetching record 0.  Lanes outside `mask` keep their registers (the
+// operands are in/out: declare the registers once, outside the loop); an empty mask is fine: the loads still count in vmcnt, in
+// order.  Addressed as uniform base + 32-bit byte offset per lane (one v_mul_lo_u32 per record instead of a 64-bit multiply-add and
+// its operand moves).
 __device__ __forceinline__ void issue_prim_loads_off(uint64_t mask, const void *base, uint32_t off, f32x4 &a, f32x4 &b, f32x4 &c) {
     uint64_t save;
     asm volatile("s_mov_b64 %3, exec\n\t"
@@ -262,10 +273,6 @@ __device__ __forceinline__ uint64_t lean_bookkeeping_masked(LeanLane &L, uint2 c
           [k24] "s"(k24), [pct] "s"(pct), [quorum] "s"(quorum), [hold] "s"(hold), [hold2] "s"(hold >> 1), [act] "s"(act), [nm] "s"(nm)
         : "vcc", "scc", "memory");
     return fin;
-}
-// The same for all lanes active at the call, whose groups are all filed.  Returns 1 in the lanes whose ray has nothing left to do.
-__device__ __forceinline__ uint32_t lean_bookkeeping_asm(LeanLane &L, uint2 child, uint2 tri, uint32_t ldsn, uint32_t ldsl, uint32_t pct, uint32_t quorum, uint32_t hold = 4u) {
-    return __builtin_amdgcn_inverse_ballot_w64(lean_bookkeeping_masked(L, child, tri, ldsn, ldsl, pct, quorum, hold, ~0ull, ~0ull)) ? 1u : 0u;
 }
 
 }  // namespace hrt

@@ -1,0 +1,267 @@
+// trav_loop.h -- the traversal loop of the path kernels: everything a wave does between two regenerations, ONCE, for k_fused
+// (fused.hip: pixels, path state in registers) and k_trace_queue (fused_queue.hip: ray queues).  Built from the blocks of
+// trav_lean.h -- hand-issued loads, the wave-wide node step, the hand-written bookkeeping sequence with its masks as operands --
+// plus what only the loop knows: the issue priority of each phase, the any-hit shortcut, the exit rules, and the tail-splitting
+// protocol (tail_donate / tail_publish / tail_adopt / tail_retire below), which can be read on its own.
+// Everything here is inlined into the two kernels; their LDS arrays stay declared there and are named through Mailboxes.
+#pragma once
+#include "trav_lean.h"
+
+namespace hrt {
+
+// Issue priority of a wave per phase of its loop (s_setprio: among the waves of a SIMD that are ready, the highest goes first).
+// A wave that is about to fetch -- the bookkeeping that chooses its next node and primitive, the loads themselves -- and a wave
+// in a regeneration go before a wave in its node step, and that before a wave in its primitive test: the fetches go out as
+// early as possible and the waves drift apart instead of queueing for memory together.  C4: 3180 -> 3390 Mrays/s
+// (profiles/r02_sweep_wave_priority.txt; every other assignment of the levels tried is within 3 % of this one, no priorities at
+// all 6 % below).
+#ifndef HRT_PRIO_BOOK
+#define HRT_PRIO_BOOK 2      // bookkeeping + address arithmetic + load issue
+#define HRT_PRIO_PRIM 0      // primitive wait + test
+#define HRT_PRIO_NODE 1      // node wait + slab tests
+#define HRT_PRIO_REGEN 2     // the kernels' own phase: shading or hit stores, next pixel or queue entry, new ray
+#endif
+
+// what a lane is doing with its ray
+struct LaneFlags {
+    bool alive = false;         // a ray is being traversed in this lane
+    bool waiting = false;       // ... has finished and waits for the next regeneration
+    bool any = false;           // this lane's ray only needs to know whether anything is hit
+    bool shared = false;        // this lane works on a piece of a ray that has been split across lanes (tail splitting)
+    uint32_t home;              // ... whose owner is this lane (the lane itself while nothing is shared)
+};
+
+// The wave's tail-splitting mailboxes: __shared__ arrays of kTraverseBlock entries each, declared in the kernels.  One mailbox
+// per lane that owns a split ray (indexed by its home lane) collects the pieces' hits; `pending` counts the pieces still under
+// way, `pair` matches donors with free lanes for one hand-over.  (k_fused's INSTANCED instantiation, where tail splitting is
+// off, parks a lane's world ray in the same memory while the lane is inside an instance: fused.hip, InstLane.)
+struct Mailboxes {
+    float *t, *u, *v;
+    uint32_t *prim, *inst, *pending, *pair;
+};
+
+// Lane-utilisation counters of the instrumented build (`make stats`, tools/lane_stats.py); empty otherwise.
+struct LaneStats {
+#ifdef HRT_LANE_STATS
+    unsigned long long iter = 0, alive = 0, node = 0, prim = 0, ppass = 0, regen = 0, enter = 0;
+#endif
+    __device__ __forceinline__ void regeneration() {
+#ifdef HRT_LANE_STATS
+        ++regen;
+#endif
+    }
+    __device__ __forceinline__ void iteration([[maybe_unused]] bool lane_alive, [[maybe_unused]] uint64_t mask_n, [[maybe_unused]] uint64_t mask_p) {
+#ifdef HRT_LANE_STATS
+        ++iter; alive += __popcll(__ballot(lane_alive)); node += __popcll(mask_n); prim += __popcll(mask_p); ppass += mask_p != 0ull;
+#endif
+    }
+    __device__ __forceinline__ void entered([[maybe_unused]] bool lane_enters) {
+#ifdef HRT_LANE_STATS
+        enter += __popcll(__ballot(lane_enters));
+#endif
+    }
+};
+
+// One-level trees: the lane is never inside an instance.  (The two-level kernel's counterpart, with the transform-node steps, is
+// fused.hip's InstLane.)
+struct NoInstLane { static constexpr uint32_t inst_cur = 0u; };
+
+// ---- tail splitting: the work is used up (no pixels, no queue entries left) and a few rays remain, one after the other in k_fused's
+//      sample chains.  A busy lane gives the BOTTOM entry of its node stack (the largest pending subtree) to a free lane of
+//      the wave, which continues with a copy of the ray.  The pieces of a split ray share ONE best hit, the mailbox of
+//      the lane that owns the ray: a piece publishes every improvement there (canonical order: the result does not
+//      depend on who found what, or when) and adopts what the others found closer, so every piece culls with the
+//      ray's best hit so far.  A piece that finishes signs off at the mailbox, and the owner takes the merged hit once the last
+//      one has.  Four blocks, in the order a loop iteration runs them; all lanes of the wave call each (they hold wave barriers).
+//      `is_free`: this lane has nothing of its own to do and may take a piece. ----
+
+// (one donation per busy lane and iteration: more rounds of this change nothing, r02_sweep_tile_tail.txt)
+__device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmax_ray) {
+    const uint64_t free_m = __ballot(is_free);
+    const uint64_t donors = __ballot(F.alive && L.nsp > L.base);
+    const uint32_t n_free = (uint32_t)__popcll(free_m), n_don = (uint32_t)__popcll(donors);
+    const uint32_t n_pairs = n_free < n_don ? n_free : n_don;
+    if (n_pairs) {
+        const uint32_t drank = lane_prefix(donors), irank = lane_prefix(free_m);
+        const bool is_donor = F.alive && L.nsp > L.base && drank < n_pairs;
+        const bool is_recv = is_free && irank < n_pairs;
+        uint2 give = make_uint2(0u, 0u);
+        if (is_donor) {
+            give = nodes[L.base][tx];
+            ++L.base;
+            if (!F.shared) {
+                F.shared = true; F.home = tx;
+                mb.t[tx] = L.s.bt; mb.u[tx] = L.s.bu; mb.v[tx] = L.s.bv; mb.prim[tx] = L.s.bprim; mb.inst[tx] = L.s.binst;
+                mb.pending[tx] = 2u;
+            } else atomicAdd(&mb.pending[F.home], 1u);
+            mb.pair[drank] = tx;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int src = is_recv ? (int)mb.pair[irank] : (int)tx;
+        // every lane shuffles; only receivers keep what they read
+        TravState &s = L.s;
+        const float r_ox = __shfl(s.ox, src), r_oy = __shfl(s.oy, src), r_oz = __shfl(s.oz, src);
+        const float r_dx = __shfl(s.dx, src), r_dy = __shfl(s.dy, src), r_dz = __shfl(s.dz, src);
+        const uint32_t r_home = (uint32_t)__shfl((int)(F.home | (F.any ? 0x100u : 0u)), src);
+        const uint32_t r_gx = (uint32_t)__shfl((int)give.x, src), r_gy = (uint32_t)__shfl((int)give.y, src);
+        if (is_recv) {
+            lean_start(L, mk3(r_ox, r_oy, r_oz), mk3(r_dx, r_dy, r_dz), tmax_ray);     // the same reciprocals and octant as the owner's
+            F.home = r_home & 0xffu; F.any = (r_home & 0x100u) != 0u; F.shared = true; F.alive = true;
+            s.bt = mb.t[F.home]; s.bu = mb.u[F.home]; s.bv = mb.v[F.home]; s.bprim = mb.prim[F.home]; s.binst = mb.inst[F.home];
+            s.cur = make_uint2(r_gx, r_gy);           // a sibling group with hits: only those are pushed
+            lean_pick_node(L);                        // (replaces the root lean_start chose)
+        }
+    }
+}
+
+// pieces of split rays publish their improvements one lane at a time (rare: a few per ray) ...
+__device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool improved, uint32_t tx) {
+    uint64_t pub = __ballot(improved && F.shared);
+    while (pub) {
+        const uint32_t l = (uint32_t)__ffsll((long long)pub) - 1u;
+        pub &= pub - 1ull;
+        if (tx == l) {
+            const TravState &s = L.s;
+            const float mt = mb.t[F.home];
+            const uint64_t mid = ((uint64_t)mb.inst[F.home] << 32) | mb.prim[F.home];
+            const uint64_t id = ((uint64_t)s.binst << 32) | s.bprim;
+            if (F.any ? mb.prim[F.home] == kMissPrim : (s.bt < mt || (s.bt == mt && id < mid))) {
+                mb.t[F.home] = s.bt; mb.u[F.home] = s.bu; mb.v[F.home] = s.bv; mb.prim[F.home] = s.bprim; mb.inst[F.home] = s.binst;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// ... and take over what another piece has found closer; an any-hit ray is done once any piece has hit.  Returns the lane's hit_any
+// (by value on purpose: as a `bool &` it cost each one-level k_fused three more spilled registers)
+__device__ __forceinline__ bool tail_adopt(LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool hit_any) {
+    if (F.alive && F.shared) {
+        if (F.any) hit_any = hit_any || mb.prim[F.home] != kMissPrim;
+        else if (mb.t[F.home] < L.s.bt) {
+            L.s.bt = mb.t[F.home]; L.s.bu = mb.u[F.home]; L.s.bv = mb.v[F.home]; L.s.bprim = mb.prim[F.home]; L.s.binst = mb.inst[F.home];
+        }
+    }
+    return hit_any;
+}
+
+// a piece whose lane reports `done` retires; the owner of the ray takes the merged hit once the last piece has
+__device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mailboxes &mb, bool done, uint32_t tx) {
+    // a piece that has finished has nothing left to merge: the mailbox holds the ray's best hit
+    if (F.alive && done && F.shared) {
+        atomicSub(&mb.pending[F.home], 1u);
+        F.alive = false;
+        if (F.home != tx) { F.shared = false; F.home = tx; }        // a helper is free again; the owner waits for the last piece
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // the owner of a split ray picks the merged hit up once its last piece has finished
+    if (F.shared && !F.alive && F.home == tx && mb.pending[tx] == 0u) {
+        L.s.bt = mb.t[tx]; L.s.bu = mb.u[tx]; L.s.bv = mb.v[tx]; L.s.bprim = mb.prim[tx]; L.s.binst = mb.inst[tx];
+        F.shared = false; F.waiting = true;
+    }
+}
+
+// ---- traverse until enough lanes have finished to make a regeneration worthwhile ----
+// The kernels instantiate the loop twice: kTail = true, with tail splitting and the drained phase's exit rule (at least
+// a.tail_regen rays wait, or none is alive), runs once the work is used up -- the other copy pays nothing for either and ends
+// once at most `max_alive` lanes are alive.
+//   I: the lane's instance state (NoInstLane, or fused.hip's InstLane with the transform-node steps of a two-level tree)
+//   nodes / leaves: the wave's LDS stacks; ldsn / ldsl: byte address in LDS of this lane's column of each
+//   leaf_hold: lean_bookkeeping_masked's `hold`;  may_help: the lane has no work of its own outside the loop either (tail splitting)
+// `a` is the kernel's argument block, by reference: only scalars are read from it, where they are used.
+template <bool HAS_SPHERES, bool INSTANCED, bool kTail, class Inst>
+__device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Inst &I, LaneStats &stats, const Mailboxes &mb,
+                                                  uint2 (*nodes)[kTraverseBlock], uint2 (*leaves)[kTraverseBlock], uint32_t ldsn, uint32_t ldsl,
+                                                  const TraverseArgs &a, const char *node_bytes, const char *prim_bytes,
+                                                  float tmin, float tmax_ray, uint32_t leaf_hold, uint32_t max_alive, bool may_help, uint32_t tx) {
+    constexpr bool kSplit = kTail && !INSTANCED;        // (tail splitting is off for two-level trees)
+    // the registers the loads land in: "defined" without an instruction (lanes that load nothing never look at theirs)
+    f32x4 rpa, rpb, rpc;
+    u32x4 rn0, rn1, rn2, rn3, rn4;
+    asm volatile("" : "=v"(rpa), "=v"(rpb), "=v"(rpc), "=v"(rn0), "=v"(rn1), "=v"(rn2), "=v"(rn3), "=v"(rn4));
+    for (;;) {
+        if (kSplit && a.tail_split) tail_donate(L, F, mb, nodes, !F.alive && !F.waiting && may_help && !F.shared, tx, tmax_ray);
+
+        // ---- G. fetch what the lanes need next: primitives first, nodes second -- for the lanes that need one only (the
+        //      instruction slots of the loads are not saved, but their L1 / TA cycles are).  The node loads are issued even when
+        //      no lane wants one: they are then ALWAYS the five youngest vector-memory operations at the primitives' wait,
+        //      whose vmcnt(5) is counted by hand. ----
+        const uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
+        {
+            uint32_t po = L.pidx * a.prim_stride, no = L.nidx * a.node_stride;      // (garbage for kNoWork: masked out)
+            asm volatile("" : "+v"(po), "+v"(no));          // both offsets before the first load
+            if (mask_p != 0ull) issue_prim_loads_off(mask_p, prim_bytes, po, rpa, rpb, rpc);
+            issue_node_loads_off(mask_n0, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
+            __builtin_amdgcn_s_setprio(HRT_PRIO_PRIM);
+        }
+        stats.iteration(F.alive, mask_n0, mask_p);
+        // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight).  Triangles:
+        //      every lane tests (straight-line arithmetic, no loads) and a lane without a primitive rejects whatever its
+        //      registers hold -- some lane nearly always has one, so a per-lane branch would save nothing but cost a mask
+        //      save, a branch and a restore.  Spheres read the instance table: only lanes with a primitive test. ----
+        bool hit_any = false, improved = false;
+        if (mask_p != 0ull) {
+            wait_prim_loads(rpa, rpb, rpc);
+            const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
+                         pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
+            if constexpr (!HAS_SPHERES)
+                improved = test_prim<false, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, L.pidx != kNoWork);
+            else if (L.pidx != kNoWork)
+                improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
+            hit_any = F.any & improved;
+        }
+        if (kSplit && a.tail_split) {
+            tail_publish(L, F, mb, improved, tx);
+            hit_any = tail_adopt(L, F, mb, hit_any);
+        }
+        // ---- A. node step: one-level trees, for the whole wave (arithmetic only; what lanes without a node made of their
+        //      registers is not filed: mask_n0 below) ----
+        uint2 child = make_uint2(0u, 0u), tri = make_uint2(0u, 0u);
+        __builtin_amdgcn_s_setprio(HRT_PRIO_NODE);
+        wait_node_loads(rn0, rn1, rn2, rn3, rn4);
+        [[maybe_unused]] bool enter = false;
+        if constexpr (!INSTANCED) {
+            lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+        } else {
+            enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
+            if (L.nidx != kNoWork && !hit_any && !enter) lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            enter = I.enter_instance(enter, L.s, child, rn0, rn1, rn2, rn3, rn4, mb, tx);
+            stats.entered(enter);
+        }
+        // ---- B. bookkeeping (trav_lean.h: one hand-written sequence): file the new groups; the leaf pass (ONE per iteration, one
+        //      primitive per lane, skipped while few lanes have leaf work and none depends on it); the primitive and the node of
+        //      the next iteration; finished? ----
+        __builtin_amdgcn_s_setprio(HRT_PRIO_BOOK);
+        // an any-hit ray is done with its first accepted intersection: nothing more to fetch (what is left on its stacks is
+        // dropped when the lane's next ray starts, lean_start)
+        if (hit_any) { L.nidx = kNoWork; L.pidx = kNoWork; }
+        // the sequence runs for the lanes that are alive and not finished by an any-hit, and files the groups of those that
+        // made a node step (nidx is still what it was at the loads for them)
+        const uint64_t book = __ballot(F.alive) & ~__ballot(hit_any);
+        uint64_t fin;
+        [[maybe_unused]] uint32_t lane = 0u;
+        if constexpr (!INSTANCED) {
+            fin = lean_bookkeeping_masked(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0);
+        } else {
+            // (this instantiation is two registers over its budget and the compiler's choice of what to keep in scratch is the two
+            // stack addresses, reloaded here in every iteration: they are a constant plus eight times the lane number -- two
+            // instructions to make again)
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+            const uint32_t ldsn_i = (uint32_t)reinterpret_cast<uintptr_t>(&nodes[0][0]) + 8u * lane, ldsl_i = (uint32_t)reinterpret_cast<uintptr_t>(&leaves[0][0]) + 8u * lane;
+            fin = lean_bookkeeping_masked(L, child, tri, ldsn_i, ldsl_i, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, ~0ull);
+        }
+        bool done = hit_any || __builtin_amdgcn_inverse_ballot_w64(fin);
+        if constexpr (INSTANCED) done = I.switch_frames(enter, done, hit_any, L, mb, nodes, tx, lane);
+        if (done && (!kTail || !F.shared)) { F.alive = false; F.waiting = true; }
+        if (kSplit && a.tail_split) tail_retire(L, F, mb, done, tx);
+        const uint64_t act = __ballot(F.alive);
+        if constexpr (kTail) {
+            if (act == 0ull || (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen) break;
+        } else if ((uint32_t)__popcll(act) <= max_alive) break;      // (every lane finished included)
+    }
+}
+
+}  // namespace hrt

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The traversal loop of k_fused (tools/loop_stats.py: the same loop, the same counts) split into its phases, so that a change to one
+"""The traversal loop of k_fused (csrc/trav_loop.h, shared with k_trace_queue; tools/loop_stats.py: the same loop, the same counts) split into its phases, so that a change to one
 phase can be checked against the others.  The phases are found by the markers the loop already has, in layout order:
     exit  the loop test (the compiler lays the latch out before the header) and whatever follows the bookkeeping sequence
     G     from the loop header to the first s_setprio: tail hand-over (kTail copy only), work masks, load issue
