@@ -41,7 +41,7 @@ $(LIBDIR)/refit.o: $(CSRC)/refit.hip $(CSRC)/device_types.h $(CSRC)/bvh8_geom.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/denoise.o: $(CSRC)/denoise.hip $(CSRC)/device_types.h $(CSRC)/trav_common.h
+$(LIBDIR)/denoise.o: $(CSRC)/denoise.hip $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/bvh8_geom.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -203,6 +203,34 @@ int  hrt_denoise_filter(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDeno
 int  hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
                         const HrtDenoiseParams *h_dparams, HrtFloat4 *d_out, void *stream);
 
+/* Temporal mode: the frames of an animation reuse the samples of the frames before them (DESIGN.md 3e "Temporal mode";
+ * tests/denoise_temporal_ref.py restates it).  Each call traces the guides as hrt_denoise_launch does, reprojects every hit pixel into
+ * the previous frame (through the instance's object space: this frame's world->object table, the last call's object->world table, the
+ * last call's camera), blends the colour buffer into the bilinearly fetched history of the same instance and primitive at the expected
+ * depth -- A = H + alpha (C - H), alpha = max(1 / L, alpha_min), L the history length, at most max_history -- and filters A as
+ * hrt_denoise_launch filters the colour buffer.  A call without history (the first, after hrt_denoise_temporal_reset, or after a
+ * change of TLAS handle, frame size or instance count) starts it afresh and returns hrt_denoise_launch's result bit for bit.
+ * The history (about 100 B per pixel) lives in the context. */
+typedef struct HrtDenoiseTemporalParams {
+    float    alpha_min;            /* smallest blend weight of the current frame, 0 < alpha_min <= 1                      (default 0.8)  */
+    uint32_t max_history;          /* cap of the history length L, 1..65536                                                 (default 32)   */
+    float    depth_tolerance;      /* a history tap counts if |z_prev - z'| <= depth_tolerance * z', > 0                   (default 0.02) */
+    uint32_t reserved;             /* must be 0 */
+} HrtDenoiseTemporalParams;
+
+int  hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out);
+/* one frame of the temporal mode into d_out (may be h_raygen->colorBuffer).  NULL parameters: the defaults.  Two-level trees and
+ * counting contexts as in hrt_denoise_guides.  Enqueued only. */
+int  hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                                 const HrtDenoiseParams *h_dparams, const HrtDenoiseTemporalParams *h_tparams,
+                                 HrtFloat4 *d_out, void *stream);
+/* forget the history: the next hrt_denoise_temporal_launch starts afresh */
+int  hrt_denoise_temporal_reset(HrtContext *ctx);
+/* the last hrt_denoise_temporal_launch's intermediates, width * height each (a NULL pointer skips its buffer): the accumulated colour
+ * A (float4, what the filter took), the history length L (float; 0 on background), and the reprojected position (x', y') in the
+ * previous frame's pixel coordinates (float2; NaN where no projection was made).  HRT_ERR_STATE before the first call.  Enqueued only. */
+int  hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float *d_length, float *d_motion, void *stream);
+
 /* ---- measurement (no reference counterpart: the reference has no timers) ------------- */
 enum { HRT_K_GENERATE = 0, HRT_K_TRAVERSE, HRT_K_TRAVERSE_ANY, HRT_K_BIN, HRT_K_SHADE,
        HRT_K_ACCUMULATE, HRT_K_FINALIZE, HRT_K_PATHS /* fused path mode */, HRT_K_REFIT /* hrt_tlas_update */, HRT_K_COUNT };
@@ -270,6 +298,7 @@ void hrt_host_free(HrtBvhBlob *blob);
 #ifdef __cplusplus
 }
 static_assert(sizeof(HrtDenoiseGuide) == 16, "HrtDenoiseGuide is 16 B");
+static_assert(sizeof(HrtDenoiseTemporalParams) == 16, "HrtDenoiseTemporalParams is 16 B");
 static_assert(sizeof(HrtDenoiseParams) == 24, "HrtDenoiseParams is 24 B");
 #endif
 #endif /* HRT_H */

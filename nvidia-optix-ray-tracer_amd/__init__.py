@@ -94,9 +94,14 @@ class DenoiseParams(C.Structure):
                 ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DenoiseTemporalParams(C.Structure):
+    """HrtDenoiseTemporalParams (include/hrt.h): the temporal mode's blend floor, history cap and depth test."""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("reserved", C.c_uint32)]
+
+
 DENOISE_GUIDE_BYTES = 16        # HrtDenoiseGuide: normal[3], albedo[3] as IEEE halves, depth (float)
 
-assert C.sizeof(DenoiseParams) == 24
+assert C.sizeof(DenoiseParams) == 24 and C.sizeof(DenoiseTemporalParams) == 16
 assert C.sizeof(GlobalParams) == 16 and C.sizeof(RayGenParams) == 80 and C.sizeof(MissParams) == 12
 assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof(Instance) == 80
 
@@ -113,6 +118,7 @@ EXPORTS = [
     "hrt_stats_reset", "hrt_stats_get", "hrt_trace_rays", "hrt_debug_set_linear_output",
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
+    "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
 ]
 
 
@@ -180,6 +186,11 @@ def load_library():
                                        C.POINTER(DenoiseParams), C.c_void_p]
     lib.hrt_denoise_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
                                        C.c_void_p, C.c_void_p]
+    lib.hrt_denoise_temporal_default_params.argtypes = [C.POINTER(DenoiseTemporalParams)]
+    lib.hrt_denoise_temporal_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
+                                                C.POINTER(DenoiseTemporalParams), C.c_void_p, C.c_void_p]
+    lib.hrt_denoise_temporal_reset.argtypes = [C.c_void_p]
+    lib.hrt_debug_denoise_temporal_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_host_free.argtypes = [C.POINTER(BvhBlob)]
     lib.hrt_host_free.restype = None
     _lib = lib
@@ -190,4 +201,5 @@ from .host import Renderer, configure_camera, tile_for_rank, reduce_tiles  # noq
 from . import scenes  # noqa: E402
 
 __all__ = ["load_library", "Renderer", "configure_camera", "tile_for_rank", "reduce_tiles", "scenes", "HrtError",
-           "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats", "DenoiseParams"]
+           "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats", "DenoiseParams",
+           "DenoiseTemporalParams"]

@@ -212,6 +212,19 @@ struct DenoisePassArgs {
     float sigma_depth_step;        // sigma_depth * step
     uint32_t normal_squarings;
 };
+// the temporal mode's reprojection and blend: one thread per pixel of the frame; prev_* are the last call's history (has_history == 0:
+// none), cur_* this call's
+struct DenoiseTemporalArgs {
+    const RayRec *rays; const float4 *tuvp; const uint32_t *inst; const float4 *color;
+    const float *inst_inv;                                   // this frame's world -> object table (Tlas::d_inst_inv)
+    const float *prev_xf;                                    // the last call's object -> world table
+    const float4 *prev_accum; const float *prev_length; const uint4 *prev_guides; const uint2 *prev_id;
+    float4 *accum; float *length; uint2 *id; float2 *motion;
+    uint32_t width, height, has_history;
+    float prev_center[3], prev_U[3], prev_V[3], prev_W[3];
+    float alpha_min, max_history, depth_tolerance;
+};
+void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
 void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);
 void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s);

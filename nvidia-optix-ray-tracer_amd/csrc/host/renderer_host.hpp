@@ -171,4 +171,12 @@ inline void denoiseOutput(HrtContext *ctx, const HrtGlobalParams &params, const 
     hrtCheckError(ctx, hrt_denoise_launch(ctx, &params, &raygen, denoiseParams, output, stream));
 }
 
+// denoiseOutput's temporal mode (include/hrt.h): the same slot, for a frame loop at a few samples per pixel -- each frame is blended into
+// the reprojected history of the frames before it, then filtered.  The history lives in the context; the first frame is denoiseOutput's.
+inline void denoiseOutputTemporal(HrtContext *ctx, const HrtGlobalParams &params, const HrtRayGenParams &raygen, HrtFloat4 *output,
+                                  const HrtDenoiseParams *denoiseParams = nullptr, const HrtDenoiseTemporalParams *temporalParams = nullptr,
+                                  hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_denoise_temporal_launch(ctx, &params, &raygen, denoiseParams, temporalParams, output, stream));
+}
+
 }  // namespace project

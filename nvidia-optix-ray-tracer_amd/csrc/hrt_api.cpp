@@ -169,6 +169,7 @@ int hrt_ctx_destroy(HrtContext *ctx) {
         for (void *p : sp) if (p) (void)hipFree(p);
     }
     free_denoise_work(ctx);
+    free_denoise_history(ctx);
     if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
     void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program};
     for (void *p : ptrs) if (p) (void)hipFree(p);

@@ -14,6 +14,16 @@ void free_denoise_work(HrtContext *ctx) {
     d = DenoiseWork{};
 }
 
+void free_denoise_history(HrtContext *ctx) {
+    DenoiseHistory &h = ctx->denoise_history;
+    for (DenoiseHistorySet &s : h.set) {
+        void *ptrs[] = {s.accum, s.length, s.guides, s.id, s.xf};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+    }
+    if (h.motion) (void)hipFree(h.motion);
+    h = DenoiseHistory{};
+}
+
 namespace {
 
 constexpr uint32_t kMaxDenoiseSide = 1u << 16;       // (the filter's pixel arithmetic is in int: sides plus 2 * 2^15 stay far from overflow)
@@ -116,6 +126,43 @@ int run_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGen
     return HRT_OK;
 }
 
+// the temporal parameters (NULL: the defaults); HRT_ERR_INVALID when one is out of range
+int temporal_constants(HrtContext *ctx, const HrtDenoiseTemporalParams *h_tparams, HrtDenoiseTemporalParams &p) {
+    hrt_denoise_temporal_default_params(&p);
+    if (h_tparams) p = *h_tparams;
+    if (!positive_finite(p.alpha_min) || p.alpha_min > 1.0f || p.max_history < 1 || p.max_history > 65536 ||
+        !positive_finite(p.depth_tolerance) || p.reserved != 0)
+        return fail(ctx, HRT_ERR_INVALID, "temporal denoise parameters out of range (0 < alpha_min <= 1, max_history 1..65536, depth_tolerance > 0 and finite, reserved 0)");
+    return HRT_OK;
+}
+
+// the history's arrays for n pixels and n_inst instances; a new size forgets the history
+int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst) {
+    DenoiseHistory &h = ctx->denoise_history;
+    if (h.pixels != n) {
+        free_denoise_history(ctx);
+        for (DenoiseHistorySet &s : h.set) {
+            HIP_TRY(ctx, hipMalloc((void **)&s.accum, sizeof(float4) * (size_t)n));
+            HIP_TRY(ctx, hipMalloc((void **)&s.length, sizeof(float) * (size_t)n));
+            HIP_TRY(ctx, hipMalloc((void **)&s.guides, sizeof(uint4) * (size_t)n));
+            HIP_TRY(ctx, hipMalloc((void **)&s.id, sizeof(uint2) * (size_t)n));
+        }
+        HIP_TRY(ctx, hipMalloc((void **)&h.motion, sizeof(float2) * (size_t)n));
+        h.pixels = n;
+    }
+    const uint32_t need = std::max(n_inst, 1u);
+    if (need > h.xf_capacity) {
+        h.valid = false;
+        for (DenoiseHistorySet &s : h.set) {
+            if (s.xf) (void)hipFree(s.xf);
+            s.xf = nullptr;
+            HIP_TRY(ctx, hipMalloc((void **)&s.xf, sizeof(float) * 12 * (size_t)need));
+        }
+        h.xf_capacity = need;
+    }
+    return HRT_OK;
+}
+
 }  // namespace
 }  // namespace hrt
 
@@ -162,6 +209,81 @@ int hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const H
     if (rc != HRT_OK) return rc;
     return run_filter(ctx, reinterpret_cast<const float4 *>(h_raygen->colorBuffer), ctx->denoise.guides, reinterpret_cast<float4 *>(d_out),
                       h_raygen->width, h_raygen->height, passes, s);
+}
+
+int hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out) {
+    if (!out) return HRT_ERR_INVALID;
+    // (profiles/r07_denoise_temporal.txt: the sweep these come from)
+    *out = HrtDenoiseTemporalParams{0.8f, 32u, 0.02f, 0u};
+    return HRT_OK;
+}
+
+int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
+                                const HrtDenoiseTemporalParams *h_tparams, HrtFloat4 *d_out, void *stream) {
+    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    const uint32_t width = h_raygen->width, height = h_raygen->height, n = width * height;
+    int rc = check_frame(ctx, width, height);
+    std::vector<DenoisePassArgs> passes;
+    HrtDenoiseTemporalParams tp;
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
+    if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
+    if (rc != HRT_OK) return rc;
+    Tlas *t;
+    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
+      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
+      t = it->second.get(); }
+    rc = ensure_history(ctx, n, t->n_instances);
+    if (rc != HRT_OK) return rc;
+    DenoiseHistory &h = ctx->denoise_history;
+    const bool has_history = h.valid && h.tlas == h_params->handle && h.width == width && h.height == height && h.n_instances == t->n_instances;
+    const DenoiseHistorySet &prev = h.set[h.cur];
+    DenoiseHistorySet &next = h.set[h.cur ^ 1u];
+    const hipStream_t s = (hipStream_t)stream;
+    rc = run_guides(ctx, h_params, h_raygen, next.guides, s);
+    if (rc != HRT_OK) return rc;
+    const DenoiseWork &d = ctx->denoise;
+    DenoiseTemporalArgs ta{};
+    ta.rays = d.rays; ta.tuvp = d.tuvp; ta.inst = d.inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
+    ta.inst_inv = t->d_inst_inv; ta.prev_xf = prev.xf;
+    ta.prev_accum = prev.accum; ta.prev_length = prev.length; ta.prev_guides = prev.guides; ta.prev_id = prev.id;
+    ta.accum = next.accum; ta.length = next.length; ta.id = next.id; ta.motion = h.motion;
+    ta.width = width; ta.height = height; ta.has_history = has_history ? 1u : 0u;
+    std::memcpy(ta.prev_center, prev.center, 12); std::memcpy(ta.prev_U, prev.U, 12); std::memcpy(ta.prev_V, prev.V, 12); std::memcpy(ta.prev_W, prev.W, 12);
+    ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
+    launch_denoise_temporal(ta, s);
+    HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
+    std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
+    std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
+    h.cur ^= 1u;
+    h.valid = false;                  // (until the filter is enqueued as well)
+    h.called = true;
+    h.tlas = h_params->handle; h.width = width; h.height = height; h.n_instances = t->n_instances;
+    rc = run_filter(ctx, next.accum, next.guides, reinterpret_cast<float4 *>(d_out), width, height, passes, s);
+    if (rc != HRT_OK) return rc;
+    h.valid = true;
+    return HRT_OK;
+}
+
+int hrt_denoise_temporal_reset(HrtContext *ctx) {
+    if (!ctx) return HRT_ERR_INVALID;
+    ctx->denoise_history.valid = false;
+    return HRT_OK;
+}
+
+int hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float *d_length, float *d_motion, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    const DenoiseHistory &h = ctx->denoise_history;
+    if (!h.called) return fail(ctx, HRT_ERR_STATE, "hrt_denoise_temporal_launch has not been called");
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)h.width * h.height;
+    const DenoiseHistorySet &last = h.set[h.cur];
+    if (d_accum) HIP_TRY(ctx, hipMemcpyAsync(d_accum, last.accum, sizeof(float4) * n, hipMemcpyDeviceToDevice, s));
+    if (d_length) HIP_TRY(ctx, hipMemcpyAsync(d_length, last.length, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    if (d_motion) HIP_TRY(ctx, hipMemcpyAsync(d_motion, h.motion, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+    return HRT_OK;
 }
 
 }  // extern "C"

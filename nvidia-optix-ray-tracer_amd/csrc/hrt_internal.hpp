@@ -125,6 +125,23 @@ struct DenoiseWork {
     uint32_t *fetch = nullptr;              // 8 x 32 slice counters of the traversal
 };
 
+// the temporal mode's history (hrt_denoise.cpp): two sets, the last call's and the one this call writes, swapped per call; each holds the
+// accumulated colour, the history length, the guides and (instance, primitive) of every pixel, the object -> world table and the camera
+struct DenoiseHistorySet {
+    float4 *accum = nullptr; float *length = nullptr; uint4 *guides = nullptr; uint2 *id = nullptr;
+    float *xf = nullptr;
+    float center[3], U[3], V[3], W[3];
+};
+struct DenoiseHistory {
+    uint32_t pixels = 0, xf_capacity = 0;   // pixels of every per-pixel array, instances the xf tables hold
+    DenoiseHistorySet set[2];
+    float2 *motion = nullptr;               // the last call's (x', y')
+    uint32_t cur = 0;                       // set[cur] is the last call's; a call writes set[cur ^ 1], then flips cur
+    bool valid = false;                     // a history to blend with exists
+    bool called = false;                    // the intermediates of a call exist (hrt_debug_denoise_temporal_state)
+    uint64_t tlas = 0; uint32_t width = 0, height = 0, n_instances = 0;     // what it was made for
+};
+
 struct TimedSpan { int kind; hipEvent_t a, b; };
 
 // working memory of the device builds, kept by the context between builds (a few arenas: builds may run on several loader threads)
@@ -226,6 +243,7 @@ struct HrtContext {
     std::vector<hipStream_t> sub_streams; std::vector<hipEvent_t> sub_done; hipEvent_t ev_begin = nullptr;
     hipStream_t graph_stream = nullptr; hipEvent_t ev_graph_done = nullptr;     // wavefront mode's graph capture when the caller's stream is the null stream
     hrt::DenoiseWork denoise;                   // hrt_denoise_* (hrt_denoise.cpp)
+    hrt::DenoiseHistory denoise_history;        // hrt_denoise_temporal_* (hrt_denoise.cpp)
 };
 
 namespace hrt {
@@ -267,6 +285,7 @@ int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n
                   float4 *tuvp, uint32_t *inst, uint32_t *fetch, hipStream_t s);
 // hrt_denoise.cpp
 void free_denoise_work(HrtContext *ctx);
+void free_denoise_history(HrtContext *ctx);
 
 // hrt_accel.cpp
 hrt::ScratchArena scratch_acquire(HrtContext *ctx, size_t bytes);      // {nullptr, 0} when the device is out of memory

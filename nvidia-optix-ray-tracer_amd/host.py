@@ -325,6 +325,51 @@ class Renderer:
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return out
 
+    def _denoise_temporal_params(self, tparams):
+        from . import DenoiseTemporalParams
+        if tparams is None:
+            return None
+        if isinstance(tparams, DenoiseTemporalParams):
+            return tparams
+        p = DenoiseTemporalParams()
+        self._check(self.lib.hrt_denoise_temporal_default_params(C.byref(p)), "hrt_denoise_temporal_default_params")
+        for k, v in dict(tparams).items():
+            setattr(p, k, v)
+        return p
+
+    def denoise_temporal(self, params=None, tparams=None, out=None):
+        """The temporal mode of denoiseOutput: the colour buffer blended into the reprojected history of the frames before it, then
+        filtered -> a new (H, W, 4) float32 tensor, or ``out`` (which may be ``self.color``).  params as for denoise; tparams: None (the
+        defaults), a DenoiseTemporalParams or a dict of its fields.  The first call, and the first after denoise_temporal_reset or a
+        change of scene or frame size, equals denoise()."""
+        params_blk, rg = self._launch_blocks()
+        out = self._torch.empty_like(self.color) if out is None else out
+        p, tp = self._denoise_params(params), self._denoise_temporal_params(tparams)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_temporal_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
+                                                         C.byref(tp) if tp is not None else None, out.data_ptr(), st),
+                    "hrt_denoise_temporal_launch")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        self._temporal_shape = (self.height, self.width)
+        return out
+
+    def denoise_temporal_reset(self):
+        self._check(self.lib.hrt_denoise_temporal_reset(self.ctx), "hrt_denoise_temporal_reset")
+
+    def denoise_temporal_state(self):
+        """The last denoise_temporal's intermediates: (accumulated colour (H, W, 4), history length (H, W), reprojected position
+        (H, W, 2) in the previous frame's pixels, NaN where none was made), float32 device tensors."""
+        torch = self._torch
+        h, w = getattr(self, "_temporal_shape", (self.height, self.width))       # (the size of the call the state is of)
+        acc = torch.empty((h, w, 4), dtype=torch.float32, device=self.device)
+        length = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        motion = torch.empty((h, w, 2), dtype=torch.float32, device=self.device)
+        st = self._stream()
+        self._check(self.lib.hrt_debug_denoise_temporal_state(self.ctx, acc.data_ptr(), length.data_ptr(), motion.data_ptr(), st),
+                    "hrt_debug_denoise_temporal_state")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return acc, length, motion
+
     def to_rgba8_of(self, frame):
         """convertFloat4ToUchar4Kernel of any (H, W, 4) float32 device tensor (to_rgba8: of the colour buffer)."""
         torch = self._torch

@@ -2,8 +2,10 @@
 first frame of Time mode).  Per scene: a 1-spp render, hrt_denoise_guides, hrt_denoise_filter and hrt_denoise_launch, each the median
 of --reps timed repetitions (HIP events around the call, after a warm-up).  Under `rocprofv3 --kernel-trace --stats` the per-kernel
 split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_denoise_pass (one launch per filter pass).
+--temporal adds hrt_denoise_temporal_launch (the frame repeated, so that every call after the first blends with a history): its own
+kernel is k_denoise_temporal.
 
-    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample]
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal]
 """
 from __future__ import annotations
 
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scenes", default="c4,sample")
+    ap.add_argument("--temporal", action="store_true")
     args = ap.parse_args()
     import torch
     hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
@@ -64,6 +67,9 @@ def main():
                "filter_ms": median_ms(torch, lambda: r.denoise_filter(r.color, guides, out=out), args.reps),
                "denoise_launch_ms": median_ms(torch, lambda: r.denoise(out=out), args.reps)}
         res["filter_per_pass_ms"] = res["filter_ms"] / 5
+        if args.temporal:
+            r.denoise_temporal(out=out)
+            res["denoise_temporal_ms"] = median_ms(torch, lambda: r.denoise_temporal(out=out), args.reps)
         print(json.dumps(res), flush=True)
         r.close()
 
