@@ -168,7 +168,10 @@ int  hrt_color_to_float4(HrtContext *ctx, const HrtFloat4 *d_src, HrtFloat4 *d_d
  * an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the buffers the reference MEANT to give OptiX --
  * the depth-1 albedo and normal AOV of Shader.cu:216-227, which quirk Q3 blanks in the reference -- recomputed from one
  * primary ray per pixel into a buffer of the denoiser's own (albedoBuffer / normalBuffer stay zero).  Deterministic, defined
- * with + - * / only (DESIGN.md "Denoiser" has the definition and tests/denoise_ref.py restates it), no CPU path. */
+ * with + - * / only (DESIGN.md "Denoiser" has the definition and tests/denoise_ref.py restates it), no CPU path.
+ * Non-finite colour is not removed: in a pass, a pixel with a NaN among its taps' colours (its own included, and an infinite pixel's
+ * own inf - inf) has a NaN weight sum and keeps its colour unfiltered; otherwise an infinite tap turns the channels it is infinite in
+ * to NaN; later passes carry this at most 2 (2^iterations - 1) pixels far.  The alpha channel is always the centre pixel's bits. */
 
 /* one pixel's guide: the primary hit of the ray the path kernel traces first for the pixel (same origin, direction, tmin, tmax) */
 typedef struct HrtDenoiseGuide {

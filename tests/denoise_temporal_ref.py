@@ -39,11 +39,14 @@ def _xf_point(m, p):
     return np.stack([((m[:, 4 * r] * x + m[:, 4 * r + 1] * y) + m[:, 4 * r + 2] * z) + m[:, 4 * r + 3] for r in range(3)], axis=1)
 
 
-def temporal_step(hist, color, hits, cam, inv, xf, width, height, tparams=None):
+def temporal_step(hist, color, hits, cam, inv, xf, width, height, tparams=None, diag=None):
     """One call's reprojection and blend.
     hist: the previous call's history (the dict this returns) or None (no history).  color: (H, W, 4) float32 colour buffer.
     hits: (t, u, v, prim, inst) of the frame's primary rays (oracle_py.OracleScene.trace, row-major pixels).  cam: (center, U, V, W).
     inv / xf: (n, 12) world -> object tables of this frame and object -> world tables (the instance transforms) of this frame.
+    diag: a dict that receives, for a call with history, the terms the outputs are decided by (tests/test_denoise_edges_cpu.py asserts
+    that its cases reach them): "sel" the hit pixels' indices and per hit pixel "s", "inside" / "same_id" / "depth_ok" / "taken"
+    ((n, 4) bool, per tap), "sw" and "unclamped" (sl / sw + 1 before the max_history clamp).
     Returns (A (H, W, 4), L (H, W), motion (H, W, 2), history)."""
     p = dict(DEFAULTS)
     p.update(tparams or {})
@@ -90,11 +93,15 @@ def temporal_step(hist, color, hits, cam, inv, xf, width, height, tparams=None):
             h_z = np.asarray(hist["depth"], np.float32).reshape(-1)
             h_inst = np.asarray(hist["inst"], np.uint32).reshape(-1)
             h_prim = np.asarray(hist["prim"], np.uint32).reshape(-1)
+            taps = []
             for k in range(4):
                 qx, qy = x0 + f32(k & 1), y0 + f32(k >> 1)
                 inside = proj & (qx >= 0) & (qx <= fw - one) & (qy >= 0) & (qy <= fh - one)
                 q = np.where(inside, np.where(inside, qy, 0).astype(np.int64) * width + np.where(inside, qx, 0).astype(np.int64), 0)
-                take = inside & (h_inst[q] == inst[sel]) & (h_prim[q] == prim[sel]) & (np.abs(h_z[q] - zp) <= tol * zp)
+                same_id = (h_inst[q] == inst[sel]) & (h_prim[q] == prim[sel])
+                depth_ok = np.abs(h_z[q] - zp) <= tol * zp
+                take = inside & same_id & depth_ok
+                taps.append((inside, same_id, depth_ok, take))
                 sw = np.where(take, sw + w[k], sw)
                 sa = np.where(take[:, None], sa + w[k][:, None] * h_acc[q, :3], sa)
                 sl = np.where(take, sl + w[k] * h_len[q], sl)
@@ -103,6 +110,9 @@ def temporal_step(hist, color, hits, cam, inv, xf, width, height, tparams=None):
             L = np.minimum(sl / sw + one, max_history)
             alpha = np.maximum(one / L, alpha_min)
             A = H + alpha[:, None] * (c[sel, :3] - H)
+            if diag is not None:
+                diag.update(sel=sel, s=s, sw=sw, unclamped=sl / sw + one, xp=xp, yp=yp,
+                            **{name: np.stack([t[i] for t in taps], axis=1) for i, name in enumerate(("inside", "same_id", "depth_ok", "taken"))})
         b = sel[blend]
         acc[b, :3] = A[blend]
         length[b] = L[blend]
@@ -116,7 +126,7 @@ def temporal_step(hist, color, hits, cam, inv, xf, width, height, tparams=None):
     return history["accum"], history["length"], motion.reshape(height, width, 2), history
 
 
-def temporal_frame(hist, color, oscene, scene, cam, width, height, params=None, tparams=None):
+def temporal_frame(hist, color, oscene, scene, cam, width, height, params=None, tparams=None, diag=None):
     """One whole hrt_denoise_temporal_launch over the oracle's primary hits of `scene` (whose instance transforms are this frame's):
     returns (output, A, L, motion, history)."""
     center, U, V, W = cam
@@ -124,6 +134,6 @@ def temporal_frame(hist, color, oscene, scene, cam, width, height, params=None, 
     origins = np.broadcast_to(np.asarray(center, np.float32), dirs.shape).copy()
     hits = oscene.trace(origins, dirs)
     xf = np.array([np.asarray(it["transform"], np.float32).reshape(12) for it in scene["instances"]], np.float32).reshape(-1, 12)
-    A, L, motion, hist2 = temporal_step(hist, color, hits, cam, world_to_object(oscene), xf, width, height, tparams)
+    A, L, motion, hist2 = temporal_step(hist, color, hits, cam, world_to_object(oscene), xf, width, height, tparams, diag)
     guides = ref.guides_from_hits(scene, center, dirs, *hits, width, height)
     return ref.atrous(A, guides, params), A, L, motion, hist2
