@@ -26,133 +26,13 @@ void invert_affine(const float *m, float *o) {
     o[8] = (float)n20; o[9] = (float)n21; o[10] = (float)n22; o[11] = (float)(-(n20 * tx + n21 * ty + n22 * tz));
 }
 
-// Working memory of the device builds.  A build takes the smallest free arena that is large enough (or allocates one, a quarter
-// larger than asked for) and gives it back when it is done; the context keeps up to eight of them, so loader threads building
-// side by side each find one.  Without this a 1500-triangle rebuild spent most of its 2 ms in hipMalloc / hipFree.
-ScratchArena scratch_acquire(HrtContext *ctx, size_t bytes) {
-    {
-        std::lock_guard<std::mutex> lk(ctx->scratch_mu);
-        int best = -1;
-        for (int i = 0; i < (int)ctx->scratch_free.size(); ++i)
-            if (ctx->scratch_free[i].bytes >= bytes && (best < 0 || ctx->scratch_free[i].bytes < ctx->scratch_free[best].bytes)) best = i;
-        if (best >= 0) { const ScratchArena a = ctx->scratch_free[best]; ctx->scratch_free.erase(ctx->scratch_free.begin() + best); return a; }
-    }
-    ScratchArena a;
-    a.bytes = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&a.p, a.bytes) != hipSuccess) {
-        // out of memory: what the context keeps for later -- the trees' cached blocks AND the other arenas (up to eight, each too small
-        // for this request or it would have been taken above) -- goes back to the runtime first, then exactly what was asked for
-        (void)hipGetLastError();
-        pool_drain(ctx);
-        std::vector<ScratchArena> arenas;
-        { std::lock_guard<std::mutex> lk(ctx->scratch_mu); arenas.swap(ctx->scratch_free); }
-        for (const ScratchArena &x : arenas) (void)hipFree(x.p);
-        a.bytes = bytes;
-        if (hipMalloc(&a.p, a.bytes) != hipSuccess) { (void)hipGetLastError(); a = ScratchArena(); }
-    }
-    return a;
-}
-void scratch_release(HrtContext *ctx, ScratchArena a) {
-    if (!a.p) return;
-    if (a.bytes > ((size_t)2 << 30)) { (void)hipFree(a.p); return; }      // the working memory of a very large build is not kept
-    ScratchArena drop;
-    {
-        std::lock_guard<std::mutex> lk(ctx->scratch_mu);
-        ctx->scratch_free.push_back(a);
-        if (ctx->scratch_free.size() > 8) {                // keep the large ones
-            size_t smallest = 0;
-            for (size_t i = 1; i < ctx->scratch_free.size(); ++i) if (ctx->scratch_free[i].bytes < ctx->scratch_free[smallest].bytes) smallest = i;
-            drop = ctx->scratch_free[smallest];
-            ctx->scratch_free.erase(ctx->scratch_free.begin() + (long)smallest);
-        }
-    }
-    if (drop.p) (void)hipFree(drop.p);
-}
-
-// Device memory of the trees (nodes, records, a dozen small per-instance tables), kept by the context when a tree is freed and handed
-// out again to the next build: an update that rebuilds (every file's first frame in the reference's Time mode) otherwise spends more
-// time in ~20 hipMalloc / hipFree pairs -- each hipFree waits for the device -- than in its kernels.  Eight size classes per octave;
-// blocks above 64 MiB and anything beyond 1 GiB in all go back to the runtime.
-void pool_drain(HrtContext *ctx);
-static size_t pool_class(size_t bytes) {
-    bytes = std::max<size_t>(bytes, 256);
-    size_t p2 = 256;
-    while (p2 * 2 <= bytes) p2 *= 2;
-    const size_t step = p2 / 8;
-    return (bytes + step - 1) / step * step;
-}
-hipError_t pool_alloc(HrtContext *ctx, void **p, size_t bytes) {
-    const size_t cls = pool_class(bytes);
-    {
-        std::lock_guard<std::mutex> lk(ctx->pool_mu);
-        for (size_t i = 0; i < ctx->pool_free.size(); ++i)
-            if (ctx->pool_free[i].bytes == cls) {
-                *p = ctx->pool_free[i].p;
-                ctx->pool_free.erase(ctx->pool_free.begin() + (long)i);
-                ctx->pool_bytes -= cls; ctx->pool_live[*p] = cls;
-                return hipSuccess;
-            }
-    }
-    hipError_t e = hipMalloc(p, cls);
-    if (e != hipSuccess) {          // out of memory: what the pool and the builds' arenas keep goes back to the runtime first
-        (void)hipGetLastError();
-        pool_drain(ctx);
-        std::vector<ScratchArena> arenas;
-        { std::lock_guard<std::mutex> lk(ctx->scratch_mu); arenas.swap(ctx->scratch_free); }
-        for (const ScratchArena &a : arenas) (void)hipFree(a.p);
-        e = hipMalloc(p, cls);
-    }
-    if (e == hipSuccess) { std::lock_guard<std::mutex> lk(ctx->pool_mu); ctx->pool_live[*p] = cls; }
-    return e;
-}
-// (the caller has made sure the device is done with the block)
-void pool_release(HrtContext *ctx, void *p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(ctx->pool_mu);
-        const auto it = ctx->pool_live.find(p);
-        if (it != ctx->pool_live.end()) {
-            const size_t bytes = it->second;
-            ctx->pool_live.erase(it);
-            if (bytes <= ((size_t)64 << 20) && ctx->pool_bytes + bytes <= ((size_t)1 << 30) && ctx->pool_free.size() < 512) {
-                ctx->pool_free.push_back({p, bytes}); ctx->pool_bytes += bytes;
-                return;
-            }
-        }
-    }
-    (void)hipFree(p);
-}
-void pool_drain(HrtContext *ctx) {
-    std::vector<ScratchArena> blocks;
-    { std::lock_guard<std::mutex> lk(ctx->pool_mu); blocks.swap(ctx->pool_free); ctx->pool_bytes = 0; }
-    for (const ScratchArena &b : blocks) (void)hipFree(b.p);
-}
-
 void free_tlas_device(HrtContext *ctx, Tlas &t) {
-    if (t.d_nodes || t.d_prims || t.d_inst_inv || t.d_inst_xf) (void)hipDeviceSynchronize();      // (what each hipFree used to do; the blocks go to the context's pool)
-    pool_release(ctx, (void *)t.d_nodes);
-    pool_release(ctx, (void *)t.d_prims);
-    pool_release(ctx, (void *)t.d_inst_inv);
-    pool_release(ctx, (void *)t.d_inst_identity);
-    pool_release(ctx, (void *)t.d_node_box);
-    pool_release(ctx, (void *)t.d_node_ref);
-    pool_release(ctx, (void *)t.d_order);
-    pool_release(ctx, (void *)t.d_inst_xf);
-    pool_release(ctx, (void *)t.d_area);
-    pool_release(ctx, (void *)t.d_inst_src);
-    pool_release(ctx, (void *)t.d_inst_first);
-    pool_release(ctx, (void *)t.d_inst_kind);
-    pool_release(ctx, (void *)t.d_inst_root); pool_release(ctx, (void *)t.d_blas_bound); t.d_blas_bound = nullptr;
-    t.d_inst_first = t.d_inst_kind = t.d_inst_root = nullptr;
-    pool_release(ctx, (void *)t.d_sig_handle);
-    pool_release(ctx, (void *)t.d_sig_visibility);
-    pool_release(ctx, (void *)t.d_sig_sbt);
-    pool_release(ctx, (void *)t.d_blas_box);
-    pool_release(ctx, (void *)t.d_update_flags);
-    pool_release(ctx, (void *)t.d_rec_box); t.d_rec_box = nullptr;
-    t.d_sig_handle = nullptr; t.d_sig_visibility = nullptr; t.d_sig_sbt = nullptr; t.d_blas_box = nullptr; t.d_update_flags = nullptr;
-    t.d_nodes = t.d_prims = nullptr; t.d_inst_inv = nullptr; t.d_inst_identity = nullptr;
-    t.d_node_box = t.d_node_ref = t.d_inst_xf = t.d_area = nullptr; t.d_inst_src = nullptr; t.d_order = nullptr;
+    TlasDevice &d = t.dev;
+    if (d.d_nodes || d.d_prims || d.d_inst_inv || d.d_inst_xf) (void)hipDeviceSynchronize();      // (what each hipFree used to do; the blocks go to the context's pool)
+    void *blocks[sizeof(TlasDevice) / sizeof(void *)];
+    std::memcpy(blocks, &d, sizeof d);
+    for (void *p : blocks) pool_release(ctx, p);
+    d = TlasDevice();
     t.area_pending = false;
 }
 void free_tlas_host(Tlas &t) {
@@ -164,6 +44,22 @@ void free_tlas_host(Tlas &t) {
 }
 
 int g_instance_table_threads = 8;      // HRT_TABLE_THREADS
+
+// Which instances a tree holds.  The reference traces with mask 1 (Shader.cu:71): an instance counts when that bit is set and its BLAS has a
+// box (a BLAS without a valid primitive keeps lo > hi).  What works on the boxes asks instance_has_box: the scene scale (instance_tables),
+// the tree over instances, the templates hrt_tlas_build makes ahead, instances_moved_far.
+static bool instance_has_box(const HrtInstance &in, const Blas &b) { return (in.visibilityMask & 1u) != 0 && b.lo[0] <= b.hi[0]; }
+// ... and its BLAS has primitives: asked where an instance becomes ONE primitive of a two-level tree's top level (whether to build such a
+// tree, and the top level's numbering).  A BLAS without primitives has no box either, so the two agree today; these callers count, and say so.
+static bool instance_has_prims(const HrtInstance &in, const Blas &b) { return instance_has_box(in, b) && b.n_prims != 0u; }
+
+// The eight corners of a BLAS's box under an instance's transform (identity: as they are).
+static void blas_box_corners(const Blas &b, const float *m, bool identity, float w[8][3]) {
+    for (int c = 0; c < 8; ++c) {
+        const float q[3] = {(c & 1) ? b.hi[0] : b.lo[0], (c & 2) ? b.hi[1] : b.lo[1], (c & 4) ? b.hi[2] : b.lo[2]};
+        if (identity) { w[c][0] = q[0]; w[c][1] = q[1]; w[c][2] = q[2]; } else xf_point(m, q, w[c]);
+    }
+}
 
 // Per-instance tables of a set of instances: object->world, world->object, identity flags, and the
 // largest |coordinate| of the transformed BLAS boxes (what the padding of the tree is derived from).
@@ -179,14 +75,11 @@ float instance_tables(const std::vector<HrtInstance> &inst, const std::vector<st
             const bool id = is_identity(m);
             ident[i] = id ? 1u : 0u;
             invert_affine(m, &inv[12 * i]);
-            const Blas &b = *blas[i];
-            if ((inst[i].visibilityMask & 1u) == 0 || !(b.lo[0] <= b.hi[0])) continue;
-            for (int c = 0; c < 8; ++c) {
-                const float q[3] = {(c & 1) ? b.hi[0] : b.lo[0], (c & 2) ? b.hi[1] : b.lo[1], (c & 4) ? b.hi[2] : b.lo[2]};
-                float w[3];
-                if (id) { w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; } else xf_point(m, q, w);
-                for (int a = 0; a < 3; ++a) if (std::isfinite(w[a])) smax = std::max(smax, std::fabs(w[a]));
-            }
+            if (!instance_has_box(inst[i], *blas[i])) continue;
+            float w[8][3];
+            blas_box_corners(*blas[i], m, id, w);
+            for (int c = 0; c < 8; ++c)
+                for (int a = 0; a < 3; ++a) if (std::isfinite(w[c][a])) smax = std::max(smax, std::fabs(w[c][a]));
         }
         return smax;
     };
@@ -203,7 +96,7 @@ float instance_tables(const std::vector<HrtInstance> &inst, const std::vector<st
 }
 
 void launch_refit_phases(RefitArgs ra, const std::vector<std::pair<uint32_t, uint32_t>> &phases, hipStream_t s);
-static void attach_rec_box(HrtContext *ctx, Tlas &t, RefitArgs &ra, uint32_t n_records);
+static RefitArgs refit_args(HrtContext *ctx, Tlas &t);
 
 // The host builder needs the geometry on the host: fetched from the BLAS's device copy the first time it is asked for
 // (HRT_BUILD=host only; the device build never brings geometry across the bus).
@@ -225,10 +118,64 @@ int ensure_host_geometry(HrtContext *ctx, Blas &b, hipStream_t s) {
     return HRT_OK;
 }
 
+// ---- what the device builds share (ensure_template, build_merged_on_device, build_two_level) ----
+static size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+// A build's arena holds its staged output and small tables in front of the build's own working memory.  take() lays them out, each
+// 256-aligned, before the arena exists (`used` is what they need in all); at() gives the pointers once it does.
+struct ArenaLayout {
+    size_t used = 0;
+    unsigned char *base = nullptr;
+    size_t take(size_t bytes) { const size_t at = used; used += align256(bytes); return at; }
+    template <class T> T *at(size_t offset) const { return reinterpret_cast<T *>(base + offset); }
+};
+
+// Gives a build's arena back to the context when the build's scope ends, however it ends.  On an error path kernels may still be writing to
+// the arena: the stream is synchronised first, so that another loader thread is not handed it before they are done.
+struct ArenaRelease {
+    HrtContext *ctx; ScratchArena arena; hipStream_t s;
+    ~ArenaRelease() { (void)hipStreamSynchronize(s); scratch_release(ctx, arena); }
+};
+
+// The part of a device build's input that comes from the context's knobs; what differs between the builds is in the arguments (`topdown`: the
+// top-down phase of build_split.hip in front of PLOC, with `split_budget` extra references per primitive for spatial splits; `pad`: the
+// padding its SAH areas are computed with).  The instance tables and the output buffers are the caller's.
+static GpuBuildInput build_input(const HrtContext *ctx, uint32_t max_leaf_prims, float c_prim, bool instance_leaves, bool topdown, float split_budget, float pad) {
+    GpuBuildInput in{};
+    in.max_leaf_prims = max_leaf_prims; in.instance_leaves = instance_leaves;
+    in.width = (uint32_t)ctx->build_width; in.c_node = ctx->build_c_node; in.c_prim = c_prim; in.ploc_radius = ctx->ploc_radius; in.quant_guard = ctx->quant_guard;
+    in.split.enabled = topdown; in.split.budget_frac = split_budget; in.split.alpha = ctx->split_alpha; in.split.bias = ctx->split_bias; in.split.cut_bias = ctx->split_cut_bias;
+    in.split.cell_refs = (uint32_t)ctx->split_cell_refs; in.split.pad = pad; in.split.verbose = ctx->build_verbose;
+    return in;
+}
+
+// Refit phases of a tree stored breadth first (nodes of level l: [level_begin[l], level_begin[l + 1])): a level each, children before parents.
+static std::vector<std::pair<uint32_t, uint32_t>> phases_from_levels(const std::vector<uint32_t> &level_begin) {
+    std::vector<std::pair<uint32_t, uint32_t>> phases;
+    for (size_t l = level_begin.size(); l-- > 1;) phases.emplace_back(level_begin[l - 1], level_begin[l] - level_begin[l - 1]);
+    return phases;
+}
+
+// A tree no kernel can walk: 2 * depth + 2 entries of the traversal stack (device_types.h)
+static bool too_deep(uint32_t max_depth) { return 2 * max_depth + 2 > kTraversalStackEntries; }
+
+// Primitive p of a BLAS under an instance's transform, as the host builder takes it (the host geometry is there: ensure_host_geometry).
+static BuildPrim build_prim_of(const Blas &b, uint32_t p, const float *m, bool identity, uint32_t inst) {
+    BuildPrim bp; std::memset(&bp, 0, sizeof bp);
+    if (b.kind == kPrimKindTriangle) {
+        triangle_world(&b.verts[9 * (size_t)p], m, identity, bp.rec.a, bp.rec.b, bp.rec.c, bp.lo, bp.hi);
+    } else {
+        const float *c = &b.centers[3 * (size_t)p];
+        bp.rec.a[0] = c[0]; bp.rec.a[1] = c[1]; bp.rec.a[2] = c[2]; bp.rec.b[0] = b.radii[p];
+        sphere_world_bounds(c, b.radii[p], m, identity, bp.lo, bp.hi);
+    }
+    bp.rec.prim = p; bp.rec.inst = inst; bp.rec.kind = b.kind;
+    return bp;
+}
+
 // Object-space BVH8 of one BLAS (built once): the subtree every instance of it gets in a tree over instances.  Built on the
 // device like everything else (one identity instance); only its topology -- nodes' child / primitive bases, masks, the
 // primitive ids -- comes back to the host, where assemble_instanced_bvh8 stitches instance subtrees under a top tree.
-// keep_device: the topology also stays on the device (Blas::d_tmpl_*), for two-level TLASes to copy from
 static int template_to_device(HrtContext *ctx, Blas &b, hipStream_t s) {
     if (b.d_tmpl_nodes || b.tmpl.nodes.empty()) return HRT_OK;
     HIP_TRY(ctx, hipMalloc((void **)&b.d_tmpl_nodes, sizeof(Bvh8Node) * b.tmpl.nodes.size()));
@@ -238,6 +185,7 @@ static int template_to_device(HrtContext *ctx, Blas &b, hipStream_t s) {
     HIP_TRY(ctx, hipStreamSynchronize(s));
     return HRT_OK;
 }
+// keep_device: the topology also stays on the device (Blas::d_tmpl_*), for two-level TLASes to copy from
 int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = false) {
     if (!ctx->build_on_device) {
         const int rc = ensure_host_geometry(ctx, b, s);
@@ -249,16 +197,7 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
         std::vector<BuildPrim> prims;
         prims.reserve(b.n_prims);
         for (uint32_t p = 0; p < b.n_prims; ++p) {
-            BuildPrim bp; std::memset(&bp, 0, sizeof bp);
-            if (b.kind == kPrimKindTriangle) {
-                triangle_world(&b.verts[9 * (size_t)p], nullptr, true, bp.rec.a, bp.rec.b, bp.rec.c, bp.lo, bp.hi);
-                bp.rec.kind = kPrimKindTriangle;
-            } else {
-                const float *c = &b.centers[3 * (size_t)p];
-                bp.rec.a[0] = c[0]; bp.rec.a[1] = c[1]; bp.rec.a[2] = c[2]; bp.rec.b[0] = b.radii[p]; bp.rec.kind = kPrimKindSphere;
-                sphere_world_bounds(c, b.radii[p], nullptr, true, bp.lo, bp.hi);
-            }
-            bp.rec.prim = p;
+            const BuildPrim bp = build_prim_of(b, p, nullptr, true, 0u);
             if (finite_box(bp.lo, bp.hi)) prims.push_back(bp);
         }
         build_bvh8(prims, b.tmpl, 0);
@@ -273,33 +212,29 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
     const uint32_t h_first[2] = {0u, n}, h_kind = b.kind, h_ident = 1u;
     const float h_xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const void *h_src = b.d_verts;
-    auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
-    const size_t o_first = 0, o_kind = o_first + 256, o_src = o_kind + 256, o_xf = o_src + 256, o_ident = o_xf + 256;
-    const size_t o_nodes = o_ident + 256, o_prims = o_nodes + up(sizeof(Bvh8Node) * (size_t)n), o_ref = o_prims + up(sizeof(PrimRecord) * (size_t)n);
-    const size_t o_scratch = o_ref + up(sizeof(float) * 2 * (size_t)n);
-    const ScratchArena arena = scratch_acquire(ctx, o_scratch + gpu_build_scratch_bytes(n));
+    ArenaLayout lay;
+    const size_t o_first = lay.take(sizeof h_first), o_kind = lay.take(sizeof h_kind), o_src = lay.take(sizeof h_src), o_xf = lay.take(sizeof h_xf), o_ident = lay.take(sizeof h_ident);
+    const size_t o_nodes = lay.take(sizeof(Bvh8Node) * (size_t)n), o_prims = lay.take(sizeof(PrimRecord) * (size_t)n), o_ref = lay.take(sizeof(float) * 2 * (size_t)n);
+    const ScratchArena arena = scratch_acquire(ctx, lay.used + gpu_build_scratch_bytes(n));
     if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build of a BLAS template: no working memory");
-    // (on an error path kernels may still be writing to the arena: another loader thread must not be handed it before they are done)
-    struct Release { HrtContext *c; ScratchArena a; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); scratch_release(c, a); } } release{ctx, arena, s};
-    unsigned char *base = static_cast<unsigned char *>(arena.p);
-    unsigned char *d_nodes = base + o_nodes, *d_prims = base + o_prims;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
-    GpuBuildInput in{};
+    ArenaRelease release{ctx, arena, s};
+    lay.base = static_cast<unsigned char *>(arena.p);
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
+    GpuBuildInput in = build_input(ctx, kMaxLeafPrims, ctx->build_c_prim_bodies, false, false, 0.0f, 0.0f);      // (no top-down phase)
     in.n_prims = n; in.n_inst = 1;
-    in.d_inst_first = reinterpret_cast<const uint32_t *>(base + o_first); in.d_inst_kind = reinterpret_cast<const uint32_t *>(base + o_kind);
-    in.d_inst_src = reinterpret_cast<const void *const *>(base + o_src); in.d_inst_xf = reinterpret_cast<const float *>(base + o_xf);
-    in.d_inst_identity = reinterpret_cast<const uint32_t *>(base + o_ident);
-    in.max_leaf_prims = kMaxLeafPrims; in.width = (uint32_t)ctx->build_width; in.c_node = ctx->build_c_node; in.c_prim = ctx->build_c_prim_bodies; in.ploc_radius = ctx->ploc_radius; in.quant_guard = ctx->quant_guard;
-    in.out_nodes = d_nodes; in.node_stride = sizeof(Bvh8Node); in.out_prims = d_prims; in.prim_stride = sizeof(PrimRecord); in.out_node_ref = reinterpret_cast<float *>(base + o_ref);
-    in.scratch = base + o_scratch; in.scratch_bytes = arena.bytes - o_scratch;
+    in.d_inst_first = lay.at<const uint32_t>(o_first); in.d_inst_kind = lay.at<const uint32_t>(o_kind);
+    in.d_inst_src = lay.at<const void *const>(o_src); in.d_inst_xf = lay.at<const float>(o_xf);
+    in.d_inst_identity = lay.at<const uint32_t>(o_ident);
+    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = sizeof(Bvh8Node); in.out_prims = lay.at<unsigned char>(o_prims); in.prim_stride = sizeof(PrimRecord); in.out_node_ref = lay.at<float>(o_ref);
+    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
     const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
     if (r.error != hipSuccess) return fail(ctx, HRT_ERR_HIP, "device build of a BLAS template failed: %s (%s)", hipGetErrorString(r.error), r.where);
     if (r.n_prims == 0) { build_bvh8({}, b.tmpl, 1); b.tmpl_built = true; return HRT_OK; }
     b.tmpl.nodes.resize(r.n_nodes); b.tmpl.prims.resize(r.n_prims);
-    HIP_TRY(ctx, hipMemcpyAsync(b.tmpl.nodes.data(), d_nodes, sizeof(Bvh8Node) * (size_t)r.n_nodes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(b.tmpl.prims.data(), d_prims, sizeof(PrimRecord) * (size_t)r.n_prims, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(b.tmpl.nodes.data(), in.out_nodes, sizeof(Bvh8Node) * (size_t)r.n_nodes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(b.tmpl.prims.data(), in.out_prims, sizeof(PrimRecord) * (size_t)r.n_prims, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     b.tmpl.max_depth = r.max_depth; b.tmpl.level_begin = r.level_begin;
     if (b.kind == kPrimKindTriangle) b.tmpl.n_triangles = r.n_prims; else b.tmpl.n_spheres = r.n_prims;
@@ -307,118 +242,353 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
     return keep_device ? template_to_device(ctx, b, s) : HRT_OK;
 }
 
-// Build a TLAS on the host and upload it together with the tables the device refit needs (hrt_tlas_update).
+// Build a TLAS and upload it together with the tables the device refit needs (hrt_tlas_update).  What is built (TreeKind):
 //  * merged (default of hrt_tlas_build): every instance is flattened into world space and ONE tree is built over all
-//    primitives -- the best tree, at the price of a full SAH build;
-//  * instanced: a top tree over the instances' boxes whose leaves are per-instance copies of object-space template
+//    primitives -- the best tree, at the price of a full SAH build; on the device (with spatial splits under HRT_CTX_FAST_TRACE),
+//    or by the host builder (HRT_BUILD=host);
+//  * over instances: a top tree over the instances' boxes whose leaves are per-instance copies of object-space template
 //    trees; only the topology comes from the host (milliseconds for thousands of instances), the device refit
 //    computes every box and world-space record.  The shape the reference's own scenes have (particles instancing a
-//    few shapes); used when a refitted tree has degraded and has to be rebuilt while frames are being rendered.
-// Either way the result is one world-space BVH8: the traversal kernels do not know the difference.
+//    few shapes); used when a refitted tree has degraded and has to be rebuilt while frames are being rendered;
+//  * two levels: transform nodes over one shared tree per BLAS.
+// But for the last, the result is one world-space BVH8: the traversal kernels do not know the difference.
+enum class TreeKind { HostFlattened, OverInstances, DeviceMerged, DeviceSplit, TwoLevel };
+struct BuildPlan {
+    TreeKind kind = TreeKind::HostFlattened;
+    // global primitive numbering of the merged builds: instance after instance, invisible instances contribute nothing
+    std::vector<uint32_t> first;
+    uint32_t n_tri_in = 0;                                           // triangles among them
+    std::vector<Blas *> uniq; std::vector<uint32_t> slot_of;        // TwoLevel: the BLASes that have instances in the tree; per instance, which of them
+};
 constexpr int kRetryFlattened = 1;      // build_tlas_fresh: the two-level tree asked for cannot be had (too deep for the path kernel's stack): build the flattened one
 
-// ---- the merged device build (the body of build_tlas_fresh for it): every visible instance's primitives in ONE world-space tree -- topology and
-//      primitive ids from build.hip (the top-down SAH phase, with spatial splits under HRT_CTX_FAST_TRACE, then PLOC in the cells, the optimal
-//      collapse, the emission); the refit computes every record, box and quantised child, exactly as after an instance update ----
-static int build_merged_on_device(HrtContext *ctx, Tlas &t, const std::vector<uint32_t> &first, bool device_split, bool scene_of_bodies, uint32_t n_tri_in,
-                                  float scene_scale, size_t pb, RefitArgs ra, hipStream_t s) {
+static float refit_pad(float scene_scale) { return 4e-6f * std::max(1.0f, scene_scale); }
+
+// ---- the tables every structure needs: per instance the transform, its inverse, the identity flag and `src`, what the refit takes as the
+//      instance's geometry (the BLAS's vertices; the top level of a two-level tree: its bounds); the word the refit's area sum goes to; and
+//      what asynchronous updates compare against and transform on the device ----
+static int upload_instance_tables(HrtContext *ctx, Tlas &t, const std::vector<const void *> &src, hipStream_t s) {
     const uint32_t n = t.n_instances;
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_first, sizeof(uint32_t) * first.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_kind, sizeof(uint32_t) * std::max(n, 1u)));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_kind, t.kind.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    GpuBuildInput in{};
-    in.n_prims = first[n]; in.n_inst = n; in.d_inst_first = t.d_inst_first; in.d_inst_kind = t.d_inst_kind; in.d_inst_src = t.d_inst_src;
-    in.d_inst_xf = t.d_inst_xf; in.d_inst_identity = t.d_inst_identity;
-    in.max_leaf_prims = kMaxLeafPrims; in.width = (uint32_t)ctx->build_width; in.c_node = ctx->build_c_node; in.c_prim = scene_of_bodies ? ctx->build_c_prim_bodies : ctx->build_c_prim; in.ploc_radius = ctx->ploc_radius; in.quant_guard = ctx->quant_guard;
+    TlasDevice &d = t.dev;
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_inv, sizeof(float) * t.h_inv.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_xf, sizeof(float) * t.h_xf.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_identity, sizeof(uint32_t) * t.h_ident.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_src, sizeof(void *) * src.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_area, sizeof(float)));
+    if (!t.h_area) HIP_TRY(ctx, hipHostMalloc((void **)&t.h_area, sizeof(float), hipHostMallocDefault));
+    if (!t.area_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&t.area_ready, hipEventDisableTiming));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_inv, t.h_inv.data(), sizeof(float) * t.h_inv.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_xf, t.h_xf.data(), sizeof(float) * t.h_xf.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_identity, t.h_ident.data(), sizeof(uint32_t) * t.h_ident.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync((void *)d.d_inst_src, src.data(), sizeof(void *) * src.size(), hipMemcpyHostToDevice, s));
+    // what asynchronous updates compare against and transform on the device
+    std::vector<float> bbox(6 * (size_t)std::max(n, 1u), 0.0f);
+    for (uint32_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { bbox[6 * (size_t)i + a] = t.blas_refs[i]->lo[a]; bbox[6 * (size_t)i + 3 + a] = t.blas_refs[i]->hi[a]; }
+    std::vector<unsigned long long> sigh(std::max(n, 1u), 0ull);
+    for (uint32_t i = 0; i < n; ++i) sigh[i] = t.sig_handle[i];
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_sig_handle, sizeof(unsigned long long) * sigh.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_sig_visibility, sizeof(uint32_t) * std::max(n, 1u)));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_sig_sbt, sizeof(uint32_t) * std::max(n, 1u)));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_blas_box, sizeof(float) * bbox.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_update_flags, sizeof(uint32_t) * 2));
+    if (!t.h_update_flags) HIP_TRY(ctx, hipHostMalloc((void **)&t.h_update_flags, sizeof(uint32_t) * 4, hipHostMallocDefault));
+    t.h_update_flags[0] = t.h_update_flags[2] = 0x3f800000u; t.h_update_flags[1] = t.h_update_flags[3] = 0u;
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_sig_handle, sigh.data(), sizeof(unsigned long long) * sigh.size(), hipMemcpyHostToDevice, s));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(d.d_sig_visibility, t.sig_visibility.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(d.d_sig_sbt, t.sbt_offset.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_blas_box, bbox.data(), sizeof(float) * bbox.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));            // (the staging vectors, and the caller's `src`, go out of scope)
+    return HRT_OK;
+}
+// ... with the BLASes' vertices as the geometry: every structure but the two-level one
+static int upload_instance_tables(HrtContext *ctx, Tlas &t, hipStream_t s) {
+    std::vector<const void *> src(std::max(t.n_instances, 1u), nullptr);
+    for (uint32_t i = 0; i < t.n_instances; ++i) src[i] = t.blas_refs[i]->d_verts;
+    return upload_instance_tables(ctx, t, src, s);
+}
+
+// ---- a host-built tree (t.bvh; `order`: the refit order of a tree over instances, empty otherwise) goes to the device ----
+static int upload_host_tree(HrtContext *ctx, Tlas &t, const std::vector<uint32_t> &order, hipStream_t s) {
+    if (too_deep(t.bvh.max_depth)) return fail(ctx, HRT_ERR_INVALID, "BVH depth %u exceeds the traversal stack", t.bvh.max_depth);
+    const int rc = upload_instance_tables(ctx, t, s);
+    if (rc != HRT_OK) return rc;
+    TlasDevice &d = t.dev;
+    const size_t n_nodes = t.bvh.nodes.size(), n_prims = t.bvh.prims.size();
+    const size_t nb = (size_t)t.node_stride * n_nodes;
+    const size_t pb = (size_t)t.prim_stride * std::max<size_t>(n_prims, 1);
+    HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, nb));
+    HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, pb));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * std::max<size_t>(6 * n_nodes, 6)));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * std::max<size_t>(2 * n_nodes, 2)));
+    if (!order.empty()) HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_order, sizeof(uint32_t) * order.size()));
+    if (t.node_stride == sizeof(Bvh8Node) && t.prim_stride == sizeof(PrimRecord)) {
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, t.bvh.nodes.data(), nb, hipMemcpyHostToDevice, s));
+        if (n_prims) HIP_TRY(ctx, hipMemcpyAsync(d.d_prims, t.bvh.prims.data(), sizeof(PrimRecord) * n_prims, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    } else {
+        std::vector<unsigned char> hn(nb, 0), hp(pb, 0);
+        for (size_t i = 0; i < n_nodes; ++i) std::memcpy(&hn[i * t.node_stride], &t.bvh.nodes[i], sizeof(Bvh8Node));
+        for (size_t i = 0; i < n_prims; ++i) std::memcpy(&hp[i * t.prim_stride], &t.bvh.prims[i], sizeof(PrimRecord));
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, hn.data(), nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_prims, hp.data(), pb, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    if (!t.bvh.node_box.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_node_box, t.bvh.node_box.data(), sizeof(float) * t.bvh.node_box.size(), hipMemcpyHostToDevice, s));
+    if (!t.bvh.node_ref.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, t.bvh.node_ref.data(), sizeof(float) * t.bvh.node_ref.size(), hipMemcpyHostToDevice, s));
+    if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync(d.d_order, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
+    t.n_nodes = (uint32_t)n_nodes; t.n_prims = (uint32_t)n_prims;
+    t.alloc_bytes = (uint64_t)nb + sizeof(float) * 8 * std::max<size_t>(n_nodes, 1) + pb;
+    t.n_triangles = t.bvh.n_triangles; t.n_spheres = t.bvh.n_spheres; t.max_depth = t.bvh.max_depth;
+    for (int a = 0; a < 3; ++a) { t.lo[a] = t.bvh.lo[a]; t.hi[a] = t.bvh.hi[a]; }
+    return HRT_OK;
+}
+
+// ---- the host's binned-SAH build over the flattened scene (HRT_BUILD=host), and the empty scene ----
+static int build_flattened_on_host(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, uint32_t n_prims_in, float scene_scale, bool fast_trace, hipStream_t s) {
+    std::vector<BuildPrim> prims;
+    prims.reserve(n_prims_in);
+    for (uint32_t i = 0; i < t.n_instances && n_prims_in; ++i) {
+        Blas &b = *t.blas_refs[i];
+        if ((inst[i].visibilityMask & 1u) == 0) continue;
+        const int rc = ensure_host_geometry(ctx, b, s);
+        if (rc != HRT_OK) return rc;
+        for (uint32_t p = 0; p < b.n_prims; ++p) {
+            const BuildPrim bp = build_prim_of(b, p, inst[i].transform, t.h_ident[i] != 0u, i);
+            // NaN / Inf geometry never hits anything; keep it out of the tree
+            if (!finite_box(bp.lo, bp.hi)) continue;
+            prims.push_back(bp);
+        }
+    }
+    // HRT_CTX_FAST_TRACE: the static-scene tree, with spatial splits (a later refit recomputes the boxes from whole primitives:
+    // valid, conservative, and without the splits' benefit -- the quality guard of hrt_tlas_update then rebuilds on the device)
+    build_bvh8(prims, t.bvh, 0, scene_scale, kMaxLeafPrims, fast_trace);
+    t.has_split_refs = t.bvh.prims.size() > prims.size();
+    t.phases = phases_from_levels(t.bvh.level_begin);
+    return upload_host_tree(ctx, t, {}, s);
+}
+
+// ---- a tree over instances: the host stitches per-instance copies of the BLASes' template trees under a top tree over the instances' boxes
+//      (topology only); the device refit computes the rest ----
+static int build_over_instances(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, float scene_scale, hipStream_t s) {
+    const uint32_t n = t.n_instances;
+    std::vector<const Bvh8 *> tmpl(n, nullptr);
+    std::vector<float> box(6 * (size_t)std::max(n, 1u), 0.0f);
+    for (uint32_t i = 0; i < n; ++i) {
+        Blas &b = *t.blas_refs[i];
+        if (!instance_has_box(inst[i], b)) continue;
+        float w[8][3], lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        blas_box_corners(b, inst[i].transform, t.h_ident[i] != 0u, w);
+        for (int c = 0; c < 8; ++c)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], w[c][a]); hi[a] = std::fmax(hi[a], w[c][a]); }
+        if (!finite_box(lo, hi)) continue;                                                 // a NaN transform: nothing to hit
+        const int rc = ensure_template(ctx, b, s);
+        if (rc != HRT_OK) return rc;
+        tmpl[i] = &b.tmpl;
+        for (int a = 0; a < 3; ++a) { box[6 * (size_t)i + a] = lo[a]; box[6 * (size_t)i + 3 + a] = hi[a]; }
+    }
+    InstancedTree it;
+    assemble_instanced_bvh8(tmpl, box, it);
+    t.bvh = Bvh8();
+    t.bvh.nodes = std::move(it.nodes); t.bvh.prims = std::move(it.prims);
+    t.bvh.n_triangles = it.n_triangles; t.bvh.n_spheres = it.n_spheres; t.bvh.max_depth = it.max_depth;
+    t.bvh.node_box.assign(6 * t.bvh.nodes.size(), 0.0f);
+    t.bvh.node_ref.assign(2 * t.bvh.nodes.size(), 0.0f);
+    for (size_t i = 0; i < it.weight.size(); ++i) t.bvh.node_ref[2 * i] = it.weight[i];
+    for (size_t h = 0; h + 1 < it.phase_begin.size(); ++h) t.phases.emplace_back(it.phase_begin[h], it.phase_begin[h + 1] - it.phase_begin[h]);
+    const int rc = upload_host_tree(ctx, t, it.order, s);
+    if (rc != HRT_OK) return rc;
+    if (t.n_prims) {
+        // the device computes what the host left blank: world-space records, boxes, origins, exponents, quantised
+        // children, and the built areas the quality guard compares later refits with
+        RefitArgs ra = refit_args(ctx, t);
+        ra.pad = refit_pad(scene_scale); ra.write_reference = 1u;
+        launch_refit_phases(ra, t.phases, s);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));            // (it.order goes out of scope)
+    return HRT_OK;
+}
+
+// ---- the merged device build: every visible instance's primitives in ONE world-space tree -- topology and primitive ids from build.hip (the
+//      top-down SAH phase, with spatial splits when device_split, then PLOC in the cells, the optimal collapse, the emission); the refit
+//      computes every record, box and quantised child, exactly as after an instance update ----
+static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &plan, bool device_split, float scene_scale, hipStream_t s) {
+    const uint32_t n = t.n_instances;
+    const std::vector<uint32_t> &first = plan.first;
+    TlasDevice &d = t.dev;
+    const int rc = upload_instance_tables(ctx, t, s);
+    if (rc != HRT_OK) return rc;
+    const size_t pb = (size_t)t.prim_stride * std::max<size_t>(first[n], 1);
+    if (!device_split) HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, pb));      // (a split build knows its record count afterwards)
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_first, sizeof(uint32_t) * first.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_kind, sizeof(uint32_t) * std::max(n, 1u)));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_kind, t.kind.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     // the top-down phase always (object splits: what gives the tree its shape above the cells PLOC builds -- on the reference's kind of
     // scene, separate bodies over a huge ground sphere, PLOC alone costs seven times the node visits); spatial splits under HRT_CTX_FAST_TRACE
-    in.split.enabled = device_split || ctx->build_topdown != 0; in.split.budget_frac = device_split ? ctx->split_budget : 0.0f; in.split.alpha = ctx->split_alpha; in.split.bias = ctx->split_bias; in.split.cut_bias = ctx->split_cut_bias;
-    in.split.cell_refs = (uint32_t)ctx->split_cell_refs; in.split.pad = ra.pad; in.split.verbose = ctx->build_verbose;
+    GpuBuildInput in = build_input(ctx, kMaxLeafPrims, t.scene_of_bodies ? ctx->build_c_prim_bodies : ctx->build_c_prim, false,
+                                   device_split || ctx->build_topdown != 0, device_split ? ctx->split_budget : 0.0f, refit_pad(scene_scale));
+    in.n_prims = first[n]; in.n_inst = n; in.d_inst_first = d.d_inst_first; in.d_inst_kind = d.d_inst_kind; in.d_inst_src = d.d_inst_src;
+    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity;
     // worst-case node output (one node and two reference floats per leaf: primitive, or reference of a spatial split) at the front of the
     // working memory; a split build's records and their clip boxes too (their number is known afterwards)
     const size_t max_leaves = gpu_build_max_refs(in.n_prims, &in.split);
-    const size_t stage_nodes = ((size_t)t.node_stride * max_leaves + 255u) & ~(size_t)255u, stage_ref = (sizeof(float) * 2 * max_leaves + 255u) & ~(size_t)255u;
-    const size_t stage_prims = device_split ? ((size_t)t.prim_stride * max_leaves + 255u) & ~(size_t)255u : 0u, stage_clip = device_split ? (sizeof(float) * 6 * max_leaves + 255u) & ~(size_t)255u : 0u;
-    const size_t stage_all = stage_nodes + stage_ref + stage_prims + stage_clip, want = gpu_build_scratch_bytes(in.n_prims, &in.split) + stage_all;
+    ArenaLayout lay;
+    const size_t o_nodes = lay.take((size_t)t.node_stride * max_leaves), o_ref = lay.take(sizeof(float) * 2 * max_leaves);
+    const size_t o_prims = lay.take(device_split ? (size_t)t.prim_stride * max_leaves : 0u), o_clip = lay.take(device_split ? sizeof(float) * 6 * max_leaves : 0u);
+    const size_t want = gpu_build_scratch_bytes(in.n_prims, &in.split) + lay.used;
     ScratchArena arena = scratch_acquire(ctx, want);
     if (!arena.p && in.split.enabled && !device_split) {      // no room for the top-down phase's buffers: PLOC alone
         in.split.enabled = false;
-        arena = scratch_acquire(ctx, gpu_build_scratch_bytes(in.n_prims, nullptr) + stage_all);
+        arena = scratch_acquire(ctx, gpu_build_scratch_bytes(in.n_prims, nullptr) + lay.used);
     }
     if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", want);
-    struct Release { HrtContext *c; ScratchArena a; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); scratch_release(c, a); } } release{ctx, arena, s};      // (see ensure_template)
-    unsigned char *stage = static_cast<unsigned char *>(arena.p);
-    in.out_nodes = stage; in.node_stride = t.node_stride; in.out_node_ref = reinterpret_cast<float *>(stage + stage_nodes);
-    in.out_prims = device_split ? stage + stage_nodes + stage_ref : ra.prims; in.prim_stride = t.prim_stride;
-    in.out_clip = device_split ? reinterpret_cast<float *>(stage + stage_nodes + stage_ref + stage_prims) : nullptr;
-    in.scratch = stage + stage_all; in.scratch_bytes = arena.bytes - stage_all;
+    ArenaRelease release{ctx, arena, s};
+    lay.base = static_cast<unsigned char *>(arena.p);
+    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = t.node_stride; in.out_node_ref = lay.at<float>(o_ref);
+    in.out_prims = device_split ? lay.at<unsigned char>(o_prims) : static_cast<unsigned char *>(d.d_prims); in.prim_stride = t.prim_stride;
+    in.out_clip = device_split ? lay.at<float>(o_clip) : nullptr;
+    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
     GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
     // A tree deeper than any kernel's stack (a chain of primitives over many orders of magnitude: nearest-neighbour clustering, like SAH, takes
     // one off the rest at every level): built again by position -- every cluster with its Morton neighbour, log2(n) levels, whatever the areas
-    if (r.error == hipSuccess && r.n_prims != 0u && 2 * r.max_depth + 2 > (uint32_t)(8 + 56) && !device_split) {
+    if (r.error == hipSuccess && r.n_prims != 0u && too_deep(r.max_depth) && !device_split) {
         if (ctx->build_verbose) std::fprintf(stderr, "[hrt] the tree is %u levels deep: built again by position\n", r.max_depth);
         in.balanced = true; in.split.enabled = false;
         r = gpu_build_bvh8(in, s);
     }
     if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build failed: %s (%s)", hipGetErrorString(r.error), r.where);
-    {   // the tree's own buffers, as large as the build turned out to need
+    {   // the tree's own buffers, as large as the build turned out to need (the build emitted its nodes into the working memory, sized for
+        // the worst case: one node per primitive; typically a seventh is used)
         const size_t nn = std::max<size_t>(r.n_prims ? r.n_nodes : 1u, 1u);
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_nodes, (size_t)t.node_stride * nn));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_box, sizeof(float) * 6 * nn));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_ref, sizeof(float) * 2 * nn));
+        HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, (size_t)t.node_stride * nn));
+        HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * 6 * nn));
+        HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * 2 * nn));
         size_t rec_bytes = pb;
         if (device_split) {
             rec_bytes = (size_t)t.prim_stride * std::max<size_t>(r.n_records, 1);
-            HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_prims, rec_bytes));
-            ra.prims = reinterpret_cast<unsigned char *>(t.d_prims);
-            if (r.n_records) HIP_TRY(ctx, hipMemcpyAsync(t.d_prims, in.out_prims, (size_t)t.prim_stride * r.n_records, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, rec_bytes));
+            if (r.n_records) HIP_TRY(ctx, hipMemcpyAsync(d.d_prims, in.out_prims, (size_t)t.prim_stride * r.n_records, hipMemcpyDeviceToDevice, s));
         }
         if (r.n_prims) {
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_nodes, stage, (size_t)t.node_stride * nn, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_node_ref, in.out_node_ref, sizeof(float) * 2 * nn, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, in.out_nodes, (size_t)t.node_stride * nn, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, in.out_node_ref, sizeof(float) * 2 * nn, hipMemcpyDeviceToDevice, s));
             HIP_TRY(ctx, hipStreamSynchronize(s));         // the working memory goes back to the context when this scope ends
         }
-        ra.nodes = reinterpret_cast<unsigned char *>(t.d_nodes); ra.node_box = t.d_node_box; ra.node_ref = t.d_node_ref;
         t.alloc_bytes = (uint64_t)t.node_stride * nn + sizeof(float) * 8 * nn + rec_bytes;
     }
     t.bvh = Bvh8();
     if (r.n_prims == 0u) {
         // every primitive had non-finite bounds: the empty root (every ray misses)
         build_bvh8({}, t.bvh, 1, scene_scale);
-        HIP_TRY(ctx, hipMemcpyAsync(t.d_nodes, t.bvh.nodes.data(), sizeof(Bvh8Node), hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, t.bvh.nodes.data(), sizeof(Bvh8Node), hipMemcpyHostToDevice, s));
         t.phases.clear();
         t.n_nodes = 1; t.n_prims = 0; t.n_triangles = t.n_spheres = 0; t.max_depth = 0;
-    } else {
-        if (2 * r.max_depth + 2 > (uint32_t)(8 + 56)) return fail(ctx, HRT_ERR_INVALID, "BVH depth %u exceeds the traversal stack", r.max_depth);
-        for (size_t l = r.level_begin.size() - 1; l-- > 0;) t.phases.emplace_back(r.level_begin[l], r.level_begin[l + 1] - r.level_begin[l]);
-        // (a split build: every record's box is the one its cell is responsible for, not the primitive's -- this once; a later
-        // update would recompute the boxes from whole primitives, so the first update rebuilds instead: has_split_refs)
-        if (device_split && r.split_levels) { ra.clip = in.out_clip; t.has_split_refs = true; }
-        attach_rec_box(ctx, t, ra, r.n_records);
-        launch_refit_phases(ra, t.phases, s);
-        HIP_TRY(ctx, hipGetLastError());
-        if (device_split && r.split_levels) HIP_TRY(ctx, hipStreamSynchronize(s));      // (the clip boxes live in the working memory)
-        ra.clip = nullptr;
-        if (ctx->build_verbose)
-            std::fprintf(stderr, "[hrt] device build: %u primitives -> %u records, %u nodes, depth %u, %u PLOC rounds (radius %d), %u split levels, %u cells\n",
-                         r.n_prims, r.n_records, r.n_nodes, r.max_depth, r.ploc_rounds, ctx->ploc_radius, r.split_levels, r.n_cells);
-        const uint32_t dropped = first[n] - r.n_prims;      // non-finite primitives (counted against the triangles unless there are none)
-        t.n_nodes = r.n_nodes; t.n_prims = r.n_records; t.max_depth = r.max_depth;
-        t.n_triangles = n_tri_in >= dropped ? n_tri_in - dropped : 0u; t.n_spheres = r.n_prims - t.n_triangles;
-        for (int a = 0; a < 3; ++a) { t.lo[a] = r.lo[a]; t.hi[a] = r.hi[a]; }
+        return HRT_OK;
     }
+    if (too_deep(r.max_depth)) return fail(ctx, HRT_ERR_INVALID, "BVH depth %u exceeds the traversal stack", r.max_depth);
+    const uint32_t dropped = first[n] - r.n_prims;      // non-finite primitives (counted against the triangles unless there are none)
+    t.n_nodes = r.n_nodes; t.n_prims = r.n_records; t.max_depth = r.max_depth;
+    t.n_triangles = plan.n_tri_in >= dropped ? plan.n_tri_in - dropped : 0u; t.n_spheres = r.n_prims - t.n_triangles;
+    for (int a = 0; a < 3; ++a) { t.lo[a] = r.lo[a]; t.hi[a] = r.hi[a]; }
+    t.phases = phases_from_levels(r.level_begin);
+    RefitArgs ra = refit_args(ctx, t);
+    ra.pad = in.split.pad; ra.write_reference = 1u;
+    // (a split build: every record's box is the one its cell is responsible for, not the primitive's -- this once; a later
+    // update would recompute the boxes from whole primitives, so the first update rebuilds instead: has_split_refs)
+    if (device_split && r.split_levels) { ra.clip = in.out_clip; t.has_split_refs = true; }
+    launch_refit_phases(ra, t.phases, s);
+    HIP_TRY(ctx, hipGetLastError());
+    if (device_split && r.split_levels) HIP_TRY(ctx, hipStreamSynchronize(s));      // (the clip boxes live in the working memory)
+    if (ctx->build_verbose)
+        std::fprintf(stderr, "[hrt] device build: %u primitives -> %u records, %u nodes, depth %u, %u PLOC rounds (radius %d), %u split levels, %u cells\n",
+                     r.n_prims, r.n_records, r.n_nodes, r.max_depth, r.ploc_rounds, ctx->ploc_radius, r.split_levels, r.n_cells);
     return HRT_OK;
 }
 
-// ---- a two-level tree (the body of build_tlas_fresh for it).  (1) every unique BLAS has its object-space tree (topology),
-//      built once per BLAS and kept on the device; (2) the device build over the instances' bounds, whose leaves come out as transform nodes;
-//      (3) the BLAS trees are copied in behind the top level and refitted in object space; (4) the top level's refit -- the only part an update
-//      repeats.  t's per-instance tables (transforms, inverses, bounds as the top level's "geometry") are in place; `ra` carries them. ----
-static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const std::vector<Blas *> &uniq, const std::vector<uint32_t> &slot_of,
-                           const std::vector<uint32_t> &first, float scene_scale, RefitArgs ra, hipStream_t s) {
-    const uint32_t n = (uint32_t)inst.size();
+// ---- a two-level tree.  (1) every unique BLAS has its object-space tree (topology), built once per BLAS and kept on
+//      the device; (2) the device build over the instances' bounds, whose leaves come out as transform nodes; (3) the BLAS trees are copied
+//      in behind the top level and refitted in object space; (4) the top level's refit -- the only part an update repeats. ----
+
+// The top level's "geometry": per instance its BLAS's box and bounding sphere, on the device; `src` points the instances at them.
+static int upload_blas_bounds(HrtContext *ctx, Tlas &t, std::vector<const void *> &src, hipStream_t s) {
+    const uint32_t n = t.n_instances;
+    std::vector<float> bound(10 * (size_t)std::max(n, 1u), 0.0f);
+    for (uint32_t i = 0; i < n; ++i) {
+        Blas &b = *t.blas_refs[i];
+        float *q = &bound[10 * (size_t)i];
+        for (int a = 0; a < 3; ++a) { q[a] = b.lo[a]; q[3 + a] = b.hi[a]; }
+        q[9] = -1.0f;
+        if (b.n_prims != 0u && b.lo[0] <= b.hi[0]) {
+            std::lock_guard<std::mutex> lk(b.tmpl_mu);
+            if (!b.bsphere_ready) {
+                for (int a = 0; a < 3; ++a) b.bsphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
+                const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
+                const hipError_t e = gpu_blas_radius(b.d_verts, b.n_prims, b.kind, b.bsphere, &b.bsphere[3], arena.p, s);
+                scratch_release(ctx, arena);
+                HIP_TRY(ctx, e);
+                b.bsphere_ready = true;
+            }
+            for (int a = 0; a < 4; ++a) q[6 + a] = b.bsphere[a];
+        }
+    }
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.dev.d_blas_bound, sizeof(float) * bound.size()));
+    HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_blas_bound, bound.data(), sizeof(float) * bound.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    src.assign(std::max(n, 1u), nullptr);
+    for (uint32_t i = 0; i < n; ++i) src[i] = t.dev.d_blas_bound + 10 * (size_t)i;
+    return HRT_OK;
+}
+
+// The refit of the packed BLAS trees, all BLASes at once: phase k = the k-th level from the bottom of every tree (a template is stored breadth
+// first, children one level below their parents), walked through an order array of node indices.
+static void pack_refit_order(const std::vector<Blas *> &uniq, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
+                             std::vector<uint32_t> &order, std::vector<std::pair<uint32_t, uint32_t>> &pack_phases) {
     const uint32_t nu = (uint32_t)uniq.size();
+    order.reserve(node_off[nu]);
+    for (uint32_t k = 0; k <= blas_depth; ++k) {
+        const uint32_t begin = (uint32_t)order.size();
+        for (uint32_t j = 0; j < nu; ++j) {
+            const std::vector<uint32_t> &lb = uniq[j]->tmpl.level_begin;
+            const uint32_t levels = lb.empty() ? 0u : (uint32_t)lb.size() - 1u;
+            if (k >= levels) continue;
+            const uint32_t l = levels - 1u - k;
+            for (uint32_t x = lb[l]; x < lb[l + 1]; ++x) order.push_back(n_top + node_off[j] + x);
+        }
+        if (order.size() > begin) pack_phases.emplace_back(begin, (uint32_t)order.size() - begin);
+    }
+}
+
+// The boxes inside a BLAS are padded for the object-space rays that will come: the slab test's error grows with the distance
+// of the ray's origin, which in object space is the world's extent seen through the instance's inverse (a rigid pose: the
+// world's own extent, as for the flattened tree).  first2: the top level's numbering (instances outside the tree take no number).
+static float object_space_reach(const Tlas &t, const std::vector<Blas *> &uniq, const std::vector<uint32_t> &first2, float scene_scale) {
+    float obj_coord = 1.0f, reach = 1.0f;
+    for (const Blas *b : uniq)
+        for (int a = 0; a < 3; ++a) obj_coord = std::max(obj_coord, std::max(std::fabs(b->lo[a]), std::fabs(b->hi[a])));
+    for (uint32_t i = 0; i < t.n_instances; ++i) {
+        if (first2[i + 1] == first2[i]) continue;
+        const float *v = &t.h_inv[12 * (size_t)i];
+        float rown = 0.0f;
+        for (int rr = 0; rr < 3; ++rr) rown = std::max(rown, std::fabs(v[4 * rr]) + std::fabs(v[4 * rr + 1]) + std::fabs(v[4 * rr + 2]));
+        if (std::isfinite(rown)) reach = std::max(reach, rown * scene_scale);
+    }
+    return std::max(reach, obj_coord);
+}
+
+static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const BuildPlan &plan, float scene_scale, hipStream_t s) {
+    const uint32_t n = t.n_instances;
+    const std::vector<Blas *> &uniq = plan.uniq;
+    const uint32_t nu = (uint32_t)uniq.size();
+    TlasDevice &d = t.dev;
+    {
+        std::vector<const void *> src;
+        int rc = upload_blas_bounds(ctx, t, src, s);
+        if (rc == HRT_OK) rc = upload_instance_tables(ctx, t, src, s);
+        if (rc != HRT_OK) return rc;
+    }
     std::vector<uint32_t> node_off(nu + 1, 0u), prim_off(nu + 1, 0u);
     uint32_t blas_depth = 0;
     for (uint32_t j = 0; j < nu; ++j) {
@@ -431,36 +601,32 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     }
     // the top level's primitives: one per visible instance of a non-empty BLAS
     std::vector<uint32_t> first2(n + 1, 0u), kind2(std::max(n, 1u), kPrimKindInstance);
-    for (uint32_t i = 0; i < n; ++i) {
-        const Blas &b = *t.blas_refs[i];
-        first2[i + 1] = first2[i] + (((inst[i].visibilityMask & 1u) != 0 && b.n_prims != 0u && b.lo[0] <= b.hi[0]) ? 1u : 0u);
-    }
+    for (uint32_t i = 0; i < n; ++i) first2[i + 1] = first2[i] + (instance_has_prims(inst[i], *t.blas_refs[i]) ? 1u : 0u);
     const uint32_t n2 = first2[n];
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_first, sizeof(uint32_t) * first2.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_kind, sizeof(uint32_t) * kind2.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_root, sizeof(uint32_t) * std::max(n, 1u)));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_first, first2.data(), sizeof(uint32_t) * first2.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_kind, kind2.data(), sizeof(uint32_t) * kind2.size(), hipMemcpyHostToDevice, s));
-    GpuBuildInput in{};
-    in.n_prims = n2; in.n_inst = n; in.d_inst_first = t.d_inst_first; in.d_inst_kind = t.d_inst_kind; in.d_inst_src = t.d_inst_src;
-    in.d_inst_xf = t.d_inst_xf; in.d_inst_identity = t.d_inst_identity;
-    in.max_leaf_prims = 1; in.instance_leaves = true; in.c_node = ctx->build_c_node; in.c_prim = ctx->build_c_prim; in.ploc_radius = ctx->ploc_radius; in.quant_guard = ctx->quant_guard;
-    in.split.enabled = ctx->build_topdown != 0; in.split.budget_frac = 0.0f; in.split.alpha = ctx->split_alpha; in.split.bias = ctx->split_bias; in.split.cut_bias = ctx->split_cut_bias;
-    in.split.cell_refs = (uint32_t)ctx->split_cell_refs; in.split.pad = ra.pad; in.split.verbose = ctx->build_verbose;
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_first, sizeof(uint32_t) * first2.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_kind, sizeof(uint32_t) * kind2.size()));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_root, sizeof(uint32_t) * std::max(n, 1u)));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_first, first2.data(), sizeof(uint32_t) * first2.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_kind, kind2.data(), sizeof(uint32_t) * kind2.size(), hipMemcpyHostToDevice, s));
+    GpuBuildInput in = build_input(ctx, 1, ctx->build_c_prim, true, ctx->build_topdown != 0, 0.0f, refit_pad(scene_scale));
+    in.width = 8;      // (HRT_BVH_WIDTH, the flattened trees' measuring knob, does not reach the top level)
+    in.n_prims = n2; in.n_inst = n; in.d_inst_first = d.d_inst_first; in.d_inst_kind = d.d_inst_kind; in.d_inst_src = d.d_inst_src;
+    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity;
     // worst case: a transform node per instance and fewer box nodes than instances
     const size_t max_nodes = 2 * (size_t)n2 + 2;
-    const size_t stage_nodes = ((size_t)t.node_stride * max_nodes + 255u) & ~(size_t)255u, stage_ref = (sizeof(float) * 2 * max_nodes + 255u) & ~(size_t)255u;
+    ArenaLayout lay;
+    const size_t o_nodes = lay.take((size_t)t.node_stride * max_nodes), o_ref = lay.take(sizeof(float) * 2 * max_nodes);
     // (the pack's refit tables and walk order share the block: nu small tables, one entry per BLAS node)
-    const size_t tab_xf = ((sizeof(float) * 12 * nu) + 255u) & ~(size_t)255u, tab_id = ((sizeof(uint32_t) * nu) + 255u) & ~(size_t)255u, tab_src = ((sizeof(void *) * nu) + 255u) & ~(size_t)255u;
-    const size_t tab_order = ((sizeof(uint32_t) * (size_t)node_off[nu]) + 255u) & ~(size_t)255u;
-    const size_t stage_all = stage_nodes + stage_ref + tab_xf + tab_id + tab_src + tab_order, want = gpu_build_scratch_bytes(n2, &in.split) + stage_all;
-    ScratchArena arena = scratch_acquire(ctx, want);
+    const size_t o_pxf = lay.take(sizeof(float) * 12 * nu), o_pid = lay.take(sizeof(uint32_t) * nu), o_psrc = lay.take(sizeof(void *) * nu);
+    const size_t o_porder = lay.take(sizeof(uint32_t) * (size_t)node_off[nu]);
+    const size_t want = gpu_build_scratch_bytes(n2, &in.split) + lay.used;
+    const ScratchArena arena = scratch_acquire(ctx, want);
     if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", want);
-    struct Release { HrtContext *c; ScratchArena a; hipStream_t st; ~Release() { (void)hipStreamSynchronize(st); scratch_release(c, a); } } release{ctx, arena, s};
-    unsigned char *stage = static_cast<unsigned char *>(arena.p);
-    in.out_nodes = stage; in.node_stride = t.node_stride; in.out_node_ref = reinterpret_cast<float *>(stage + stage_nodes);
-    in.out_prims = stage; in.prim_stride = t.prim_stride;        // (no record is written: the leaves are transform nodes)
-    in.scratch = stage + stage_all; in.scratch_bytes = arena.bytes - stage_all;
+    ArenaRelease release{ctx, arena, s};
+    lay.base = static_cast<unsigned char *>(arena.p);
+    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = t.node_stride; in.out_node_ref = lay.at<float>(o_ref);
+    in.out_prims = in.out_nodes; in.prim_stride = t.prim_stride;        // (no record is written: the leaves are transform nodes)
+    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
     const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
     if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build of the top level failed: %s (%s)", hipGetErrorString(r.error), r.where);
     if (r.n_prims == 0u) return kRetryFlattened;                                 // nothing valid to instance: the flattened path emits the empty root
@@ -468,82 +634,53 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     if (r.max_depth + 1u + blas_depth > (uint32_t)ctx->fused_max_depth) return kRetryFlattened;
     const uint32_t n_top = r.n_nodes, n_all = n_top + node_off[nu], n_rec = prim_off[nu];
     if ((uint64_t)n_all * t.node_stride >= ctx->fused_max_bytes || (uint64_t)std::max(n_rec, 1u) * t.prim_stride >= ctx->fused_max_bytes) return kRetryFlattened;
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_nodes, (size_t)t.node_stride * n_all + 16));       // (+16: the path kernel reads 80 bytes of the last node whatever its stride)
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_box, sizeof(float) * 6 * (size_t)n_all));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_ref, sizeof(float) * 2 * (size_t)n_all));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_prims, (size_t)t.prim_stride * std::max(n_rec, 1u)));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_nodes, stage, (size_t)t.node_stride * n_top, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_node_ref, in.out_node_ref, sizeof(float) * 2 * (size_t)n_top, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, (size_t)t.node_stride * n_all + 16));       // (+16: the path kernel reads 80 bytes of the last node whatever its stride)
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * 6 * (size_t)n_all));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * 2 * (size_t)n_all));
+    HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, (size_t)t.prim_stride * std::max(n_rec, 1u)));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, in.out_nodes, (size_t)t.node_stride * n_top, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, in.out_node_ref, sizeof(float) * 2 * (size_t)n_top, hipMemcpyDeviceToDevice, s));
     // (3) the BLAS trees behind the top level
     std::vector<uint32_t> roots(std::max(n, 1u), 0u);
-    for (uint32_t i = 0; i < n; ++i) roots[i] = n_top + node_off[slot_of[i]];
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_root, roots.data(), sizeof(uint32_t) * roots.size(), hipMemcpyHostToDevice, s));
+    for (uint32_t i = 0; i < n; ++i) roots[i] = n_top + node_off[plan.slot_of[i]];
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_root, roots.data(), sizeof(uint32_t) * roots.size(), hipMemcpyHostToDevice, s));
     for (uint32_t j = 0; j < nu; ++j) {
         PackBlasArgs pa{};
         pa.src_nodes = uniq[j]->d_tmpl_nodes; pa.src_prims = uniq[j]->d_tmpl_prims; pa.n_nodes = node_off[j + 1] - node_off[j]; pa.n_prims = prim_off[j + 1] - prim_off[j];
-        pa.dst_nodes = reinterpret_cast<unsigned char *>(t.d_nodes); pa.dst_prims = reinterpret_cast<unsigned char *>(t.d_prims); pa.node_stride = t.node_stride; pa.prim_stride = t.prim_stride;
+        pa.dst_nodes = reinterpret_cast<unsigned char *>(d.d_nodes); pa.dst_prims = reinterpret_cast<unsigned char *>(d.d_prims); pa.node_stride = t.node_stride; pa.prim_stride = t.prim_stride;
         pa.node_off = n_top + node_off[j]; pa.prim_off = prim_off[j]; pa.slot = j;
         launch_pack_blas(pa, s);
     }
-    // their refit, all BLASes at once: phase k = the k-th level from the bottom of every tree (a template is stored breadth first,
-    // children one level below their parents), walked through an order array; per-BLAS tables with the identity transform
+    // their refit: per-BLAS tables with the identity transform
     std::vector<float> pxf(12 * (size_t)nu, 0.0f); std::vector<uint32_t> pid(nu, 1u); std::vector<const void *> psrc(nu, nullptr);
-    std::vector<uint32_t> order; order.reserve(node_off[nu]);
+    for (uint32_t j = 0; j < nu; ++j) { pxf[12 * (size_t)j] = pxf[12 * (size_t)j + 5] = pxf[12 * (size_t)j + 10] = 1.0f; psrc[j] = uniq[j]->d_verts; }
+    std::vector<uint32_t> order;
     std::vector<std::pair<uint32_t, uint32_t>> pack_phases;
-    float obj_coord = 1.0f;
-    for (uint32_t j = 0; j < nu; ++j) {
-        pxf[12 * (size_t)j] = pxf[12 * (size_t)j + 5] = pxf[12 * (size_t)j + 10] = 1.0f; psrc[j] = uniq[j]->d_verts;
-        for (int a = 0; a < 3; ++a) obj_coord = std::max(obj_coord, std::max(std::fabs(uniq[j]->lo[a]), std::fabs(uniq[j]->hi[a])));
-    }
-    for (uint32_t k = 0; k <= blas_depth; ++k) {
-        const uint32_t begin = (uint32_t)order.size();
-        for (uint32_t j = 0; j < nu; ++j) {
-            const std::vector<uint32_t> &lb = uniq[j]->tmpl.level_begin;
-            const uint32_t levels = lb.empty() ? 0u : (uint32_t)lb.size() - 1u;
-            if (k >= levels) continue;
-            const uint32_t l = levels - 1u - k;
-            for (uint32_t x = lb[l]; x < lb[l + 1]; ++x) order.push_back(n_top + node_off[j] + x);
-        }
-        if (order.size() > begin) pack_phases.emplace_back(begin, (uint32_t)order.size() - begin);
-    }
+    pack_refit_order(uniq, node_off, n_top, blas_depth, order, pack_phases);
     if (order.size() != node_off[nu]) return fail(ctx, HRT_ERR_HIP, "two-level tree: a BLAS template's levels do not cover its nodes");
-    unsigned char *tabs = stage + stage_nodes + stage_ref;
-    float *d_pxf = reinterpret_cast<float *>(tabs); uint32_t *d_pid = reinterpret_cast<uint32_t *>(tabs + tab_xf);
-    const void **d_psrc = reinterpret_cast<const void **>(tabs + tab_xf + tab_id); uint32_t *d_porder = reinterpret_cast<uint32_t *>(tabs + tab_xf + tab_id + tab_src);
-    HIP_TRY(ctx, hipMemcpyAsync(d_pxf, pxf.data(), sizeof(float) * pxf.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pid, pid.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync((void *)d_psrc, psrc.data(), sizeof(void *) * nu, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_porder, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
-    // The boxes inside a BLAS are padded for the object-space rays that will come: the slab test's error grows with the distance
-    // of the ray's origin, which in object space is the world's extent seen through the instance's inverse (a rigid pose: the
-    // world's own extent, as for the flattened tree).
-    float reach = 1.0f;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (first2[i + 1] == first2[i]) continue;
-        const float *v = &t.h_inv[12 * (size_t)i];
-        float rown = 0.0f;
-        for (int rr = 0; rr < 3; ++rr) rown = std::max(rown, std::fabs(v[4 * rr]) + std::fabs(v[4 * rr + 1]) + std::fabs(v[4 * rr + 2]));
-        if (std::isfinite(rown)) reach = std::max(reach, rown * scene_scale);
-    }
-    t.built_reach = std::max(reach, obj_coord);
-    RefitArgs rp{};
-    rp.nodes = reinterpret_cast<unsigned char *>(t.d_nodes); rp.node_stride = t.node_stride; rp.prims = reinterpret_cast<unsigned char *>(t.d_prims); rp.prim_stride = t.prim_stride;
-    rp.node_box = t.d_node_box; rp.node_ref = t.d_node_ref; rp.inst_xf = d_pxf; rp.inst_identity = d_pid; rp.inst_src = d_psrc; rp.order = d_porder;
+    HIP_TRY(ctx, hipMemcpyAsync(lay.at<float>(o_pxf), pxf.data(), sizeof(float) * pxf.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.at<uint32_t>(o_pid), pid.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.at<const void *>(o_psrc), psrc.data(), sizeof(void *) * nu, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.at<uint32_t>(o_porder), order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
+    t.built_reach = object_space_reach(t, uniq, first2, scene_scale);
+    RefitArgs rp{};      // (the pack's own tables: not refit_args)
+    rp.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); rp.node_stride = t.node_stride; rp.prims = reinterpret_cast<unsigned char *>(d.d_prims); rp.prim_stride = t.prim_stride;
+    rp.node_box = d.d_node_box; rp.node_ref = d.d_node_ref; rp.inst_xf = lay.at<float>(o_pxf); rp.inst_identity = lay.at<uint32_t>(o_pid); rp.inst_src = lay.at<const void *>(o_psrc); rp.order = lay.at<uint32_t>(o_porder);
     rp.pad = 4e-6f * t.built_reach; rp.write_reference = 1u;
     launch_refit_phases(rp, pack_phases, s);
     HIP_TRY(ctx, hipGetLastError());
     // (4) the top level
-    ra.nodes = reinterpret_cast<unsigned char *>(t.d_nodes); ra.prims = reinterpret_cast<unsigned char *>(t.d_prims); ra.node_box = t.d_node_box; ra.node_ref = t.d_node_ref;
-    ra.inst_inv = t.d_inst_inv; ra.inst_root = t.d_inst_root;
-    for (size_t l = r.level_begin.size() - 1; l-- > 0;) t.phases.emplace_back(r.level_begin[l], r.level_begin[l + 1] - r.level_begin[l]);
+    t.two_level = true; t.n_top_nodes = n_top; t.n_unique_blas = nu;
+    t.phases = phases_from_levels(r.level_begin);
+    RefitArgs ra = refit_args(ctx, t);
+    ra.pad = in.split.pad; ra.write_reference = 1u;
     launch_refit_phases(ra, t.phases, s);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(s));
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] two-level build: %u instances over %u BLASes -> %u top nodes (depth %u, %u split levels), %u BLAS nodes (depth <= %u), %u records (flattened: %u)\n",
-                     n2, nu, n_top, r.max_depth, r.split_levels, node_off[nu], blas_depth, n_rec, first[n]);
+                     n2, nu, n_top, r.max_depth, r.split_levels, node_off[nu], blas_depth, n_rec, plan.first[n]);
     t.bvh = Bvh8();
-    t.two_level = true; t.n_top_nodes = n_top; t.n_unique_blas = nu;
     t.n_nodes = n_all; t.n_prims = n_rec; t.max_depth = r.max_depth + 1u + blas_depth;
     t.n_triangles = t.n_spheres = 0;
     for (uint32_t j = 0; j < nu; ++j) { t.n_triangles += uniq[j]->tmpl.n_triangles; t.n_spheres += uniq[j]->tmpl.n_spheres; }
@@ -552,6 +689,65 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     return HRT_OK;
 }
 
+// ---- what to build, decided once ----
+
+// the split build's working memory (~1.2 KB per primitive with the staged output) has to be there: otherwise the default build
+static bool split_build_fits(HrtContext *ctx, uint32_t n_prims) {
+    SplitParams probe; probe.enabled = true; probe.budget_frac = ctx->split_budget; probe.cell_refs = (uint32_t)ctx->split_cell_refs;
+    const size_t leaves = gpu_build_max_refs(n_prims, &probe);
+    const size_t want = gpu_build_scratch_bytes(n_prims, &probe) + leaves * (size_t)(128 + 8 + ctx->prim_stride + 24);
+    size_t free_b = 0, total_b = 0, kept = 0;      // (what the context keeps for later counts as free: an allocation that fails gives it back first)
+    { std::lock_guard<std::mutex> lk(ctx->scratch_mu); for (const ScratchArena &x : ctx->scratch_free) kept += x.bytes; }
+    { std::lock_guard<std::mutex> lk(ctx->pool_mu); kept += ctx->pool_bytes; }
+    return leaves <= (1u << 30) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want <= (free_b + kept) / 10 * 9;
+}
+
+// Two levels or one?  Flattening costs memory, build and refit time in proportion to instances x primitives; a two-level tree
+// (transform nodes over one shared tree per BLAS) in proportion to instances + unique primitives, at the price of a ray
+// transform per instance entered.  Asked for (two_level_mode > 0), or chosen when the flattened tree would leave the caches
+// while the shared one stays in them.  Only k_fused walks such trees: not under HRT_CTX_COUNT / HRT_FUSED != 1.  Fills plan.uniq / slot_of.
+static bool wants_two_level(const HrtContext *ctx, const std::vector<HrtInstance> &inst, const std::vector<std::shared_ptr<Blas>> &refs, int two_level_mode, BuildPlan &plan) {
+    const uint32_t n = (uint32_t)inst.size();
+    plan.slot_of.assign(n, 0u);
+    if (two_level_mode < 0 || (ctx->flags & HRT_CTX_COUNT) != 0 || ctx->fused != 1) return false;
+    std::unordered_map<Blas *, uint32_t> seen;
+    uint64_t unique_prims = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        Blas *b = refs[i].get();
+        if (!instance_has_prims(inst[i], *b)) continue;
+        auto it = seen.find(b);
+        if (it == seen.end()) { it = seen.emplace(b, (uint32_t)plan.uniq.size()).first; plan.uniq.push_back(b); unique_prims += b->n_prims; }
+        plan.slot_of[i] = it->second;
+    }
+    const uint32_t total = plan.first[n];
+    return !plan.uniq.empty() && (two_level_mode > 0 || ((uint64_t)total >= ctx->two_level_min_prims && (double)total >= (double)ctx->two_level_min_share * (double)unique_prims));
+}
+
+static int plan_build(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const std::vector<std::shared_ptr<Blas>> &refs, bool instanced, bool fast_trace, int two_level_mode, BuildPlan &plan) {
+    const uint32_t n = (uint32_t)inst.size();
+    plan.first.assign(n + 1, 0u);
+    uint32_t n_vis = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool vis = (inst[i].visibilityMask & 1u) != 0;       // the reference traces with mask 1 (Shader.cu:71)
+        const uint32_t cnt = vis ? refs[i]->n_prims : 0u;
+        if ((uint64_t)plan.first[i] + cnt > 0xfffffff0ull) return fail(ctx, HRT_ERR_INVALID, "more than 2^32 primitives in one TLAS");
+        plan.first[i + 1] = plan.first[i] + cnt;
+        if (refs[i]->kind == kPrimKindTriangle) plan.n_tri_in += cnt;
+        n_vis += cnt ? 1u : 0u;
+    }
+    const uint32_t total = plan.first[n];
+    // a scene of bodies (the reference's kind: particles instancing a few shapes) or a soup?  (the collapse's primitive cost: hrt_internal.hpp)
+    t.scene_of_bodies = n_vis >= 4u && (uint64_t)total < 20000ull * n_vis;      // (the launch picks the path kernel's leaf-hold by it, hrt_api.cpp)
+    t.node_stride = (uint32_t)ctx->node_stride; t.prim_stride = (uint32_t)ctx->prim_stride;
+    if (ctx->node_stride_auto && total > 3500000u) t.node_stride = 128u;      // a tree that will not fit the Infinity Cache: one 128-byte line per node
+    // HRT_CTX_FAST_TRACE: the static-scene tree with spatial splits -- from the device's builder, or (HRT_FAST_TRACE_BUILD=host) from the host's;
+    // it gets the flattened tree whatever two_level_mode says
+    if (instanced) plan.kind = TreeKind::OverInstances;
+    else if (!ctx->build_on_device || (fast_trace && !ctx->fast_trace_on_device) || total == 0u) plan.kind = TreeKind::HostFlattened;
+    else if (fast_trace) plan.kind = split_build_fits(ctx, total) ? TreeKind::DeviceSplit : TreeKind::DeviceMerged;
+    else plan.kind = wants_two_level(ctx, inst, refs, two_level_mode, plan) ? TreeKind::TwoLevel : TreeKind::DeviceMerged;
+    return HRT_OK;
+}
 
 static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, hipStream_t s, bool instanced, bool fast_trace, int two_level_mode) {
     const uint32_t n = (uint32_t)inst.size();
@@ -564,6 +760,7 @@ static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInsta
             refs[i] = it->second;
         }
     }
+    // the per-instance host tables
     const float scene_scale = instance_tables(inst, refs, t.h_xf, t.h_inv, t.h_ident);
     t.sbt_offset.assign(n, 0); t.kind.assign(n, 0); t.has_spheres = false;
     t.sig_handle.assign(n, 0); t.sig_visibility.assign(n, 0);
@@ -573,240 +770,24 @@ static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInsta
         t.sig_handle[i] = inst[i].traversableHandle; t.sig_visibility[i] = inst[i].visibilityMask & 1u;
         if ((inst[i].visibilityMask & 1u) != 0 && refs[i]->kind == kPrimKindSphere && refs[i]->n_prims) t.has_spheres = true;
     }
-    std::vector<uint32_t> order;
     t.phases.clear();
-    // HRT_CTX_FAST_TRACE: the static-scene tree with spatial splits -- from the host builder, or (HRT_FAST_TRACE_BUILD=device) from the device's
-    bool device_split = fast_trace && ctx->fast_trace_on_device != 0 && !instanced && ctx->build_on_device != 0;
-    const bool device_merged = !instanced && ctx->build_on_device != 0 && (!fast_trace || device_split);
-    // global primitive numbering of the merged builds: instance after instance, invisible instances contribute nothing
-    std::vector<uint32_t> first(n + 1, 0u);
-    uint32_t n_tri_in = 0, n_sph_in = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool vis = (inst[i].visibilityMask & 1u) != 0;       // the reference traces with mask 1 (Shader.cu:71)
-        const uint32_t cnt = vis ? refs[i]->n_prims : 0u;
-        if ((uint64_t)first[i] + cnt > 0xfffffff0ull) return fail(ctx, HRT_ERR_INVALID, "more than 2^32 primitives in one TLAS");
-        first[i + 1] = first[i] + cnt;
-        if (refs[i]->kind == kPrimKindTriangle) n_tri_in += cnt; else n_sph_in += cnt;
-        (void)n_sph_in;
-    }
-    // a scene of bodies (the reference's kind: particles instancing a few shapes) or a soup?  (the collapse's primitive cost: hrt_internal.hpp)
-    uint32_t n_vis = 0;
-    for (uint32_t i = 0; i < n; ++i) n_vis += first[i + 1] > first[i] ? 1u : 0u;
-    const bool scene_of_bodies = n_vis >= 4u && (uint64_t)first[n] < 20000ull * n_vis;
-    t.scene_of_bodies = scene_of_bodies;      // (the launch picks the path kernel's leaf-hold by it, hrt_api.cpp)
-    // ---- two levels or one?  Flattening costs memory, build and refit time in proportion to instances x primitives; a two-level tree
-    //      (transform nodes over one shared tree per BLAS) in proportion to instances + unique primitives, at the price of a ray
-    //      transform per instance entered.  Asked for (two_level_mode > 0), or chosen when the flattened tree would leave the caches
-    //      while the shared one stays in them.  Only k_fused walks such trees: not under HRT_CTX_COUNT / HRT_FUSED != 1. ----
-    bool two_level = false;
-    std::vector<Blas *> uniq; std::vector<uint32_t> slot_of(n, 0u);
-    if (two_level_mode >= 0 && !instanced && device_merged && !device_split && first[n] != 0u && (ctx->flags & HRT_CTX_COUNT) == 0 && ctx->fused == 1) {
-        std::unordered_map<Blas *, uint32_t> seen;
-        uint64_t unique_prims = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            Blas *b = refs[i].get();
-            if ((inst[i].visibilityMask & 1u) == 0 || b->n_prims == 0u || !(b->lo[0] <= b->hi[0])) continue;
-            auto it = seen.find(b);
-            if (it == seen.end()) { it = seen.emplace(b, (uint32_t)uniq.size()).first; uniq.push_back(b); unique_prims += b->n_prims; }
-            slot_of[i] = it->second;
-        }
-        two_level = !uniq.empty() && (two_level_mode > 0 || ((uint64_t)first[n] >= ctx->two_level_min_prims &&
-                                                             (double)first[n] >= (double)ctx->two_level_min_share * (double)unique_prims));
-        if (two_level && fast_trace && two_level_mode <= 0) two_level = false;      // (a static scene that asks for the best tree gets the flattened one with spatial splits)
-    }
-    if (device_split) {
-        // the split build's working memory (~1.2 KB per primitive with the staged output) has to be there: otherwise the default build
-        SplitParams probe; probe.enabled = true; probe.budget_frac = ctx->split_budget; probe.cell_refs = (uint32_t)ctx->split_cell_refs;
-        const size_t leaves = gpu_build_max_refs(first[n], &probe);
-        const size_t want = gpu_build_scratch_bytes(first[n], &probe) + leaves * (size_t)(128 + 8 + ctx->prim_stride + 24);
-        size_t free_b = 0, total_b = 0, kept = 0;      // (what the context keeps for later counts as free: an allocation that fails gives it back first)
-        { std::lock_guard<std::mutex> lk(ctx->scratch_mu); for (const ScratchArena &x : ctx->scratch_free) kept += x.bytes; }
-        { std::lock_guard<std::mutex> lk(ctx->pool_mu); kept += ctx->pool_bytes; }
-        if (leaves > (1u << 30) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || want > (free_b + kept) / 10 * 9) device_split = false;
-    }
-    if (instanced) {
-        std::vector<const Bvh8 *> tmpl(n, nullptr);
-        std::vector<float> box(6 * (size_t)std::max(n, 1u), 0.0f);
-        for (uint32_t i = 0; i < n; ++i) {
-            Blas &b = *refs[i];
-            if ((inst[i].visibilityMask & 1u) == 0 || !(b.lo[0] <= b.hi[0])) continue;
-            float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int c = 0; c < 8; ++c) {
-                const float q[3] = {(c & 1) ? b.hi[0] : b.lo[0], (c & 2) ? b.hi[1] : b.lo[1], (c & 4) ? b.hi[2] : b.lo[2]};
-                float w[3];
-                if (t.h_ident[i]) { w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; } else xf_point(inst[i].transform, q, w);
-                for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], w[a]); hi[a] = std::fmax(hi[a], w[a]); }
-            }
-            if (!finite_box(lo, hi)) continue;                                                 // a NaN transform: nothing to hit
-            const int rc = ensure_template(ctx, b, s);
-            if (rc != HRT_OK) return rc;
-            tmpl[i] = &b.tmpl;
-            for (int a = 0; a < 3; ++a) { box[6 * (size_t)i + a] = lo[a]; box[6 * (size_t)i + 3 + a] = hi[a]; }
-        }
-        InstancedTree it;
-        assemble_instanced_bvh8(tmpl, box, it);
-        t.bvh = Bvh8();
-        t.bvh.nodes = std::move(it.nodes); t.bvh.prims = std::move(it.prims);
-        t.bvh.n_triangles = it.n_triangles; t.bvh.n_spheres = it.n_spheres; t.bvh.max_depth = it.max_depth;
-        t.bvh.node_box.assign(6 * t.bvh.nodes.size(), 0.0f);
-        t.bvh.node_ref.assign(2 * t.bvh.nodes.size(), 0.0f);
-        for (size_t i = 0; i < it.weight.size(); ++i) t.bvh.node_ref[2 * i] = it.weight[i];
-        order = std::move(it.order);
-        for (size_t h = 0; h + 1 < it.phase_begin.size(); ++h) t.phases.emplace_back(it.phase_begin[h], it.phase_begin[h + 1] - it.phase_begin[h]);
-    } else if (!device_merged || first[n] == 0u) {
-        // the host's binned-SAH build over the flattened scene (HRT_BUILD=host), and the empty scene
-        std::vector<BuildPrim> prims;
-        prims.reserve(first[n]);
-        for (uint32_t i = 0; i < n && first[n]; ++i) {
-            Blas *b = refs[i].get();
-            const float *m = inst[i].transform;
-            const bool id = t.h_ident[i] != 0u;
-            if ((inst[i].visibilityMask & 1u) == 0) continue;
-            const int rc = ensure_host_geometry(ctx, *b, s);
-            if (rc != HRT_OK) return rc;
-            for (uint32_t p = 0; p < b->n_prims; ++p) {
-                BuildPrim bp; std::memset(&bp, 0, sizeof bp);
-                if (b->kind == kPrimKindTriangle) {
-                    triangle_world(&b->verts[9 * (size_t)p], m, id, bp.rec.a, bp.rec.b, bp.rec.c, bp.lo, bp.hi);
-                    bp.rec.prim = p; bp.rec.inst = i; bp.rec.kind = kPrimKindTriangle;
-                } else {
-                    const float *c = &b->centers[3 * (size_t)p];
-                    bp.rec.a[0] = c[0]; bp.rec.a[1] = c[1]; bp.rec.a[2] = c[2]; bp.rec.prim = p;
-                    bp.rec.b[0] = b->radii[p]; bp.rec.inst = i; bp.rec.kind = kPrimKindSphere;
-                    sphere_world_bounds(c, b->radii[p], m, id, bp.lo, bp.hi);
-                }
-                // NaN / Inf geometry never hits anything; keep it out of the tree
-                if (!finite_box(bp.lo, bp.hi)) continue;
-                prims.push_back(bp);
-            }
-        }
-        // HRT_CTX_FAST_TRACE: the static-scene tree, with spatial splits (a later refit recomputes the boxes from whole primitives:
-        // valid, conservative, and without the splits' benefit -- the quality guard of hrt_tlas_update then rebuilds on the device)
-        build_bvh8(prims, t.bvh, 0, scene_scale, kMaxLeafPrims, fast_trace);
-        t.has_split_refs = t.bvh.prims.size() > prims.size();
-        for (size_t l = t.bvh.level_begin.size() - 1; l-- > 0;) t.phases.emplace_back(t.bvh.level_begin[l], t.bvh.level_begin[l + 1] - t.bvh.level_begin[l]);
-    }
-    const bool on_device = device_merged && first[n] != 0u;
-    if (!on_device && 2 * t.bvh.max_depth + 2 > (uint32_t)(8 + 56))
-        return fail(ctx, HRT_ERR_INVALID, "BVH depth %u exceeds the traversal stack", t.bvh.max_depth);
-
+    BuildPlan plan;
+    int rc = plan_build(ctx, t, inst, refs, instanced, fast_trace, two_level_mode, plan);
+    if (rc != HRT_OK) return rc;
     free_tlas_device(ctx, t);
     t.n_instances = n;
     t.blas_refs = std::move(refs);
-    t.node_stride = (uint32_t)ctx->node_stride; t.prim_stride = (uint32_t)ctx->prim_stride;
-    if (ctx->node_stride_auto && first[n] > 3500000u) t.node_stride = 128u;      // a tree that will not fit the Infinity Cache: one 128-byte line per node
-    // A device build emits its nodes into the build's working memory, sized for the worst case (one node per primitive;
-    // typically a seventh is used); the TLAS gets buffers of the size the build turned out to need (below).
-    const size_t n_nodes = on_device ? 0 : t.bvh.nodes.size(), n_prims = on_device ? (size_t)first[n] : t.bvh.prims.size();
-    const size_t nb = (size_t)t.node_stride * n_nodes;
-    const size_t pb = (size_t)t.prim_stride * std::max<size_t>(n_prims, 1);
-    std::vector<const void *> src(std::max(n, 1u), nullptr);
-    for (uint32_t i = 0; i < n; ++i) src[i] = t.blas_refs[i]->d_verts;
-    if (two_level) {      // the top level's "geometry": the instances' BLAS boxes and bounding spheres
-        std::vector<float> bound(10 * (size_t)std::max(n, 1u), 0.0f);
-        for (uint32_t i = 0; i < n; ++i) {
-            Blas &b = *t.blas_refs[i];
-            float *q = &bound[10 * (size_t)i];
-            for (int a = 0; a < 3; ++a) { q[a] = b.lo[a]; q[3 + a] = b.hi[a]; }
-            q[9] = -1.0f;
-            if (b.n_prims != 0u && b.lo[0] <= b.hi[0]) {
-                std::lock_guard<std::mutex> lk(b.tmpl_mu);
-                if (!b.bsphere_ready) {
-                    for (int a = 0; a < 3; ++a) b.bsphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
-                    const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
-                    const hipError_t e = gpu_blas_radius(b.d_verts, b.n_prims, b.kind, b.bsphere, &b.bsphere[3], arena.p, s);
-                    scratch_release(ctx, arena);
-                    HIP_TRY(ctx, e);
-                    b.bsphere_ready = true;
-                }
-                for (int a = 0; a < 4; ++a) q[6 + a] = b.bsphere[a];
-            }
-        }
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_blas_bound, sizeof(float) * bound.size()));
-        HIP_TRY(ctx, hipMemcpyAsync(t.d_blas_bound, bound.data(), sizeof(float) * bound.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < n; ++i) src[i] = t.d_blas_bound + 10 * (size_t)i;
+    // every path below uploads the tables all structures need (upload_instance_tables), makes the allocations of its own, and leaves the tree's counts in t
+    switch (plan.kind) {
+    case TreeKind::HostFlattened: rc = build_flattened_on_host(ctx, t, inst, plan.first[n], scene_scale, fast_trace, s); break;
+    case TreeKind::OverInstances: rc = build_over_instances(ctx, t, inst, scene_scale, s); break;
+    case TreeKind::DeviceMerged:  rc = build_merged_on_device(ctx, t, plan, false, scene_scale, s); break;
+    case TreeKind::DeviceSplit:   rc = build_merged_on_device(ctx, t, plan, true, scene_scale, s); break;
+    case TreeKind::TwoLevel:      rc = build_two_level(ctx, t, inst, plan, scene_scale, s); break;
     }
-    if (!on_device) HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_nodes, nb));
-    if (!(on_device && (device_split || two_level))) HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_prims, pb));      // (a split build knows its record count afterwards; a two-level tree holds the unique primitives' records only)
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_inv, sizeof(float) * t.h_inv.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_xf, sizeof(float) * t.h_xf.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_identity, sizeof(uint32_t) * t.h_ident.size()));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_inst_src, sizeof(void *) * src.size()));
-    if (!on_device) {
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_box, sizeof(float) * std::max<size_t>(6 * n_nodes, 6)));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_node_ref, sizeof(float) * std::max<size_t>(2 * n_nodes, 2)));
-    }
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_area, sizeof(float)));
-    if (!order.empty()) HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_order, sizeof(uint32_t) * order.size()));
-    if (!t.h_area) HIP_TRY(ctx, hipHostMalloc((void **)&t.h_area, sizeof(float), hipHostMallocDefault));
-    if (!t.area_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&t.area_ready, hipEventDisableTiming));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_inv, t.h_inv.data(), sizeof(float) * t.h_inv.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_xf, t.h_xf.data(), sizeof(float) * t.h_xf.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_identity, t.h_ident.data(), sizeof(uint32_t) * t.h_ident.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync((void *)t.d_inst_src, src.data(), sizeof(void *) * src.size(), hipMemcpyHostToDevice, s));
-    {   // what asynchronous updates compare against and transform on the device
-        std::vector<float> bbox(6 * (size_t)std::max(n, 1u), 0.0f);
-        for (uint32_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { bbox[6 * (size_t)i + a] = t.blas_refs[i]->lo[a]; bbox[6 * (size_t)i + 3 + a] = t.blas_refs[i]->hi[a]; }
-        std::vector<unsigned long long> sigh(std::max(n, 1u), 0ull);
-        for (uint32_t i = 0; i < n; ++i) sigh[i] = t.sig_handle[i];
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_sig_handle, sizeof(unsigned long long) * sigh.size()));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_sig_visibility, sizeof(uint32_t) * std::max(n, 1u)));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_sig_sbt, sizeof(uint32_t) * std::max(n, 1u)));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_blas_box, sizeof(float) * bbox.size()));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.d_update_flags, sizeof(uint32_t) * 2));
-        if (!t.h_update_flags) HIP_TRY(ctx, hipHostMalloc((void **)&t.h_update_flags, sizeof(uint32_t) * 4, hipHostMallocDefault));
-        t.h_update_flags[0] = t.h_update_flags[2] = 0x3f800000u; t.h_update_flags[1] = t.h_update_flags[3] = 0u;
-        HIP_TRY(ctx, hipMemcpyAsync(t.d_sig_handle, sigh.data(), sizeof(unsigned long long) * sigh.size(), hipMemcpyHostToDevice, s));
-        if (n) HIP_TRY(ctx, hipMemcpyAsync(t.d_sig_visibility, t.sig_visibility.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        if (n) HIP_TRY(ctx, hipMemcpyAsync(t.d_sig_sbt, t.sbt_offset.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipMemcpyAsync(t.d_blas_box, bbox.data(), sizeof(float) * bbox.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));            // (the staging vectors go out of scope)
-    }
-    RefitArgs ra{};
-    ra.nodes = reinterpret_cast<unsigned char *>(t.d_nodes); ra.node_stride = t.node_stride;
-    ra.prims = reinterpret_cast<unsigned char *>(t.d_prims); ra.prim_stride = t.prim_stride;
-    ra.node_box = t.d_node_box; ra.node_ref = t.d_node_ref; ra.inst_xf = t.d_inst_xf; ra.inst_identity = t.d_inst_identity;
-    ra.inst_src = t.d_inst_src; ra.pad = 4e-6f * std::max(1.0f, scene_scale); ra.write_reference = 1u;
-    if (on_device && two_level) {
-        const int rc2 = build_two_level(ctx, t, inst, uniq, slot_of, first, scene_scale, ra, s);
-        if (rc2 != HRT_OK) return rc2;
-    } else if (on_device) {
-        const int rc2 = build_merged_on_device(ctx, t, first, device_split, scene_of_bodies, n_tri_in, scene_scale, pb, ra, s);
-        if (rc2 != HRT_OK) return rc2;
-    } else {
-        if (t.node_stride == sizeof(Bvh8Node) && t.prim_stride == sizeof(PrimRecord)) {
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_nodes, t.bvh.nodes.data(), nb, hipMemcpyHostToDevice, s));
-            if (n_prims) HIP_TRY(ctx, hipMemcpyAsync(t.d_prims, t.bvh.prims.data(), sizeof(PrimRecord) * n_prims, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-        } else {
-            std::vector<unsigned char> hn(nb, 0), hp(pb, 0);
-            for (size_t i = 0; i < n_nodes; ++i) std::memcpy(&hn[i * t.node_stride], &t.bvh.nodes[i], sizeof(Bvh8Node));
-            for (size_t i = 0; i < n_prims; ++i) std::memcpy(&hp[i * t.prim_stride], &t.bvh.prims[i], sizeof(PrimRecord));
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_nodes, hn.data(), nb, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_prims, hp.data(), pb, hipMemcpyHostToDevice, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-        }
-        if (!t.bvh.node_box.empty())
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_node_box, t.bvh.node_box.data(), sizeof(float) * t.bvh.node_box.size(), hipMemcpyHostToDevice, s));
-        if (!t.bvh.node_ref.empty())
-            HIP_TRY(ctx, hipMemcpyAsync(t.d_node_ref, t.bvh.node_ref.data(), sizeof(float) * t.bvh.node_ref.size(), hipMemcpyHostToDevice, s));
-        if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync(t.d_order, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
-        if (instanced && n_prims) {
-            // the device computes what the host left blank: world-space records, boxes, origins, exponents, quantised
-            // children, and the built areas the quality guard compares later refits with
-            ra.order = t.d_order;
-            attach_rec_box(ctx, t, ra, (uint32_t)n_prims);
-            launch_refit_phases(ra, t.phases, s);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        t.n_nodes = (uint32_t)t.bvh.nodes.size(); t.n_prims = (uint32_t)t.bvh.prims.size();
-        t.alloc_bytes = (uint64_t)nb + sizeof(float) * 8 * std::max<size_t>(n_nodes, 1) + pb;
-        t.n_triangles = t.bvh.n_triangles; t.n_spheres = t.bvh.n_spheres; t.max_depth = t.bvh.max_depth;
-        for (int a = 0; a < 3; ++a) { t.lo[a] = t.bvh.lo[a]; t.hi[a] = t.bvh.hi[a]; }
-    }
+    if (rc != HRT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    t.instanced = instanced;
+    t.instanced = plan.kind == TreeKind::OverInstances;
     t.refits_since_build = 0;
     return HRT_OK;
 }
@@ -883,31 +864,39 @@ void launch_refit_phases(RefitArgs ra, const std::vector<std::pair<uint32_t, uin
 constexpr uint32_t kRecBoxMaxRecords = 65536;
 static void attach_rec_box(HrtContext *ctx, Tlas &t, RefitArgs &ra, uint32_t n_records) {
     if (n_records == 0u || n_records > kRecBoxMaxRecords) return;
-    if (!t.d_rec_box && pool_alloc(ctx, (void **)&t.d_rec_box, sizeof(float) * 6 * (size_t)n_records) != hipSuccess) { (void)hipGetLastError(); t.d_rec_box = nullptr; return; }
-    ra.rec_box = t.d_rec_box; ra.n_records = n_records;
+    if (!t.dev.d_rec_box && pool_alloc(ctx, (void **)&t.dev.d_rec_box, sizeof(float) * 6 * (size_t)n_records) != hipSuccess) { (void)hipGetLastError(); t.dev.d_rec_box = nullptr; return; }
+    ra.rec_box = t.dev.d_rec_box; ra.n_records = n_records;
+}
+
+// What every refit of a tree takes from it (its counts and two_level are set).  The caller adds what differs: the padding (`pad`, or `scale_bits`
+// when the scene scale is on the device), `area_sum` or `write_reference`, `clip`.
+static RefitArgs refit_args(HrtContext *ctx, Tlas &t) {
+    const TlasDevice &d = t.dev;
+    RefitArgs ra{};
+    ra.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); ra.node_stride = t.node_stride;
+    ra.prims = reinterpret_cast<unsigned char *>(d.d_prims); ra.prim_stride = t.prim_stride;
+    ra.node_box = d.d_node_box; ra.node_ref = d.d_node_ref; ra.inst_xf = d.d_inst_xf; ra.inst_identity = d.d_inst_identity; ra.inst_src = d.d_inst_src;
+    ra.order = d.d_order;
+    if (t.two_level) { ra.inst_inv = d.d_inst_inv; ra.inst_root = d.d_inst_root; }      // (the top level only: transform nodes and the boxes above them)
+    else attach_rec_box(ctx, t, ra, t.n_prims);
+    return ra;
 }
 
 // Device refit of a built tree under new instance transforms: upload the per-instance tables, then one
 // k_refit_level launch per tree level, deepest first.  Asynchronous on s.
 int refit_tlas(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, hipStream_t s) {
     const float scene_scale = instance_tables(inst, t.blas_refs, t.h_xf, t.h_inv, t.h_ident);
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_inv, t.h_inv.data(), sizeof(float) * t.h_inv.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_xf, t.h_xf.data(), sizeof(float) * t.h_xf.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(t.d_inst_identity, t.h_ident.data(), sizeof(uint32_t) * t.h_ident.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(t.d_area, 0, sizeof(float), s));
+    HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_inv, t.h_inv.data(), sizeof(float) * t.h_inv.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_xf, t.h_xf.data(), sizeof(float) * t.h_xf.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_identity, t.h_ident.data(), sizeof(uint32_t) * t.h_ident.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(t.dev.d_area, 0, sizeof(float), s));
     t.async_words_ready = false;
-    RefitArgs ra{};
-    ra.nodes = reinterpret_cast<unsigned char *>(t.d_nodes); ra.node_stride = t.node_stride;
-    ra.prims = reinterpret_cast<unsigned char *>(t.d_prims); ra.prim_stride = t.prim_stride;
-    ra.node_box = t.d_node_box; ra.node_ref = t.d_node_ref; ra.inst_xf = t.d_inst_xf; ra.inst_identity = t.d_inst_identity; ra.inst_src = t.d_inst_src;
-    ra.pad = 4e-6f * std::max(1.0f, scene_scale);
-    ra.area_sum = t.d_area;
-    ra.order = t.d_order;
-    if (t.two_level) { ra.inst_inv = t.d_inst_inv; ra.inst_root = t.d_inst_root; }      // (the top level only: transform nodes and the boxes above them)
-    else attach_rec_box(ctx, t, ra, t.n_prims);
+    RefitArgs ra = refit_args(ctx, t);
+    ra.pad = refit_pad(scene_scale);
+    ra.area_sum = t.dev.d_area;
     { Timer tm(ctx, s, HRT_K_REFIT); launch_refit_phases(ra, t.phases, s); }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(t.h_area, t.d_area, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(t.h_area, t.dev.d_area, sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipEventRecord(t.area_ready, s));
     t.area_pending = true;
     t.refits++; t.refits_since_build++; ctx->tlas_refits++;
@@ -933,7 +922,7 @@ static bool instances_moved_far(const Tlas &t, const std::vector<HrtInstance> &i
     uint32_t valid = 0, far = 0;
     for (uint32_t i = 0; i < t.n_instances; ++i) {
         const Blas *b = t.blas_refs[i].get();
-        if (!b || (inst[i].visibilityMask & 1u) == 0 || !(b->lo[0] <= b->hi[0])) continue;
+        if (!b || !instance_has_box(inst[i], *b)) continue;
         const float c[3] = {0.5f * (b->lo[0] + b->hi[0]), 0.5f * (b->lo[1] + b->hi[1]), 0.5f * (b->lo[2] + b->hi[2])};
         const float e[3] = {b->hi[0] - b->lo[0], b->hi[1] - b->lo[1], b->hi[2] - b->lo[2]};
         float was[3], now[3], ext[3];
@@ -946,6 +935,14 @@ static bool instances_moved_far(const Tlas &t, const std::vector<HrtInstance> &i
         if (d2 > w2) ++far;
     }
     return valid >= 4 && 2 * far > valid;
+}
+
+static int register_blas(HrtContext *ctx, std::shared_ptr<Blas> b, HrtTraversable *out_blas) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const uint64_t h = ctx->next_handle++;
+    ctx->blas[h] = std::move(b);
+    *out_blas = h;
+    return HRT_OK;
 }
 
 extern "C" {
@@ -969,11 +966,7 @@ int hrt_blas_build_triangles(HrtContext *ctx, const HrtFloat3 *d_vertices, uint3
         scratch_release(ctx, arena);
         HIP_TRY(ctx, e);
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const uint64_t h = ctx->next_handle++;
-    ctx->blas[h] = std::move(b);
-    *out_blas = h;
-    return HRT_OK;
+    return register_blas(ctx, std::move(b), out_blas);
 }
 
 int hrt_blas_build_spheres(HrtContext *ctx, const HrtFloat3 *d_centers, const float *d_radii, uint32_t n, void *stream, HrtTraversable *out_blas) {
@@ -991,11 +984,7 @@ int hrt_blas_build_spheres(HrtContext *ctx, const HrtFloat3 *d_centers, const fl
         scratch_release(ctx, arena);
         HIP_TRY(ctx, e);
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const uint64_t h = ctx->next_handle++;
-    ctx->blas[h] = std::move(b);
-    *out_blas = h;
-    return HRT_OK;
+    return register_blas(ctx, std::move(b), out_blas);
 }
 
 int hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas) {
@@ -1013,14 +1002,13 @@ int hrt_tlas_build(HrtContext *ctx, const HrtInstance *d_instances, uint32_t n, 
     int rc = download_instances(ctx, d_instances, n, (hipStream_t)stream, inst);
     const int two_level_mode = (ctx->flags & HRT_CTX_TWO_LEVEL) != 0 ? 1 : ctx->two_level;
     if (rc == HRT_OK) rc = build_tlas_into(ctx, *t, inst, (hipStream_t)stream, ctx->tlas_instanced > 0 && two_level_mode <= 0, (ctx->flags & HRT_CTX_FAST_TRACE) != 0, two_level_mode);
-    if (rc != HRT_OK) { free_tlas_device(ctx, *t); free_tlas_host(*t); return rc; }
     // A rebuild in the middle of an animation builds a tree over instances when the scene is small (hrt_tlas_update): the per-BLAS
     // template trees that needs are built now, while the scene is being loaded, not inside the first frame that rebuilds (the
     // reference's shipped sample: 9 templates, 8.7 ms of its first frame)
-    if (!t->two_level && rebuild_over_instances(ctx, *t))
+    if (rc == HRT_OK && !t->two_level && rebuild_over_instances(ctx, *t))
         for (uint32_t i = 0; i < n && rc == HRT_OK; ++i) {
             Blas &b = *t->blas_refs[i];
-            if ((inst[i].visibilityMask & 1u) != 0 && b.lo[0] <= b.hi[0]) rc = ensure_template(ctx, b, (hipStream_t)stream);
+            if (instance_has_box(inst[i], b)) rc = ensure_template(ctx, b, (hipStream_t)stream);
         }
     if (rc != HRT_OK) { free_tlas_device(ctx, *t); free_tlas_host(*t); return rc; }
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1057,24 +1045,19 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
             // (the device words the tables kernel and the refit accumulate into -- scene scale, verdict bits, area sum -- are left in their
             // initial state by the previous asynchronous update's epilogue; after a build or a synchronous update they are set here)
             if (!t->async_words_ready) {
-                HIP_TRY(ctx, hipMemcpyAsync(t->d_update_flags, t->h_update_flags + 2, sizeof(uint32_t) * 2, hipMemcpyHostToDevice, s));
-                HIP_TRY(ctx, hipMemsetAsync(t->d_area, 0, sizeof(float), s));
+                HIP_TRY(ctx, hipMemcpyAsync(t->dev.d_update_flags, t->h_update_flags + 2, sizeof(uint32_t) * 2, hipMemcpyHostToDevice, s));
+                HIP_TRY(ctx, hipMemsetAsync(t->dev.d_area, 0, sizeof(float), s));
                 t->async_words_ready = true;
             }
             InstanceTableArgs ia{};
-            ia.instances = d_instances; ia.n = n; ia.sig_handle = t->d_sig_handle; ia.sig_visibility = t->d_sig_visibility; ia.sig_sbt = t->d_sig_sbt; ia.blas_box = t->d_blas_box;
-            ia.inst_xf = t->d_inst_xf; ia.inst_inv = t->d_inst_inv; ia.inst_identity = t->d_inst_identity; ia.flags = t->d_update_flags;
+            ia.instances = d_instances; ia.n = n; ia.sig_handle = t->dev.d_sig_handle; ia.sig_visibility = t->dev.d_sig_visibility; ia.sig_sbt = t->dev.d_sig_sbt; ia.blas_box = t->dev.d_blas_box;
+            ia.inst_xf = t->dev.d_inst_xf; ia.inst_inv = t->dev.d_inst_inv; ia.inst_identity = t->dev.d_inst_identity; ia.flags = t->dev.d_update_flags;
             launch_instance_tables(ia, s);
-            RefitArgs ra{};
-            ra.nodes = reinterpret_cast<unsigned char *>(t->d_nodes); ra.node_stride = t->node_stride;
-            ra.prims = reinterpret_cast<unsigned char *>(t->d_prims); ra.prim_stride = t->prim_stride;
-            ra.node_box = t->d_node_box; ra.node_ref = t->d_node_ref; ra.inst_xf = t->d_inst_xf; ra.inst_identity = t->d_inst_identity; ra.inst_src = t->d_inst_src;
-            ra.scale_bits = t->d_update_flags; ra.area_sum = t->d_area; ra.order = t->d_order;
-            if (t->two_level) { ra.inst_inv = t->d_inst_inv; ra.inst_root = t->d_inst_root; }
-            else attach_rec_box(ctx, *t, ra, t->n_prims);
+            RefitArgs ra = refit_args(ctx, *t);
+            ra.scale_bits = t->dev.d_update_flags; ra.area_sum = t->dev.d_area;
             { Timer tm(ctx, s, HRT_K_REFIT); launch_refit_phases(ra, t->phases, s); }
             // one launch where there were two copies to the host, one from it and a fill: results to pinned memory, device words reset
-            UpdateEpilogueArgs ue{t->d_area, t->d_update_flags, t->h_area, t->h_update_flags, t->h_update_flags[2], t->h_update_flags[3]};
+            UpdateEpilogueArgs ue{t->dev.d_area, t->dev.d_update_flags, t->h_area, t->h_update_flags, t->h_update_flags[2], t->h_update_flags[3]};
             launch_update_epilogue(ue, s);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipEventRecord(t->area_ready, s));
@@ -1105,7 +1088,7 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
         for (uint32_t i = 0; i < n; ++i) if (inst[i].sbtOffset != t->sbt_offset[i]) { t->sbt_offset[i] = inst[i].sbtOffset; sbt_changed = true; }
         if (sbt_changed) {
             t->generation++;                              // the material tables are re-derived at the next launch
-            HIP_TRY(ctx, hipMemcpyAsync(t->d_sig_sbt, t->sbt_offset.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, hipMemcpyAsync(t->dev.d_sig_sbt, t->sbt_offset.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
             HIP_TRY(ctx, hipStreamSynchronize(s));
         }
         const bool first_after_build = t->refits_since_build == 0;
@@ -1186,8 +1169,8 @@ int hrt_tlas_download(HrtContext *ctx, HrtTraversable tlas, HrtBvhBlob *out) {
     // the device copy is the truth: device builds exist nowhere else, and a refit rewrites the tree in place
     HIP_TRY(ctx, hipDeviceSynchronize());
     const size_t n_nodes = t->n_nodes, n_prims = t->n_prims;
-    HIP_TRY(ctx, hipMemcpy2D(out->nodes, sizeof(Bvh8Node), t->d_nodes, t->node_stride, sizeof(Bvh8Node), n_nodes, hipMemcpyDeviceToHost));
-    if (n_prims) HIP_TRY(ctx, hipMemcpy2D(out->triangles, sizeof(PrimRecord), t->d_prims, t->prim_stride, sizeof(PrimRecord), n_prims, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy2D(out->nodes, sizeof(Bvh8Node), t->dev.d_nodes, t->node_stride, sizeof(Bvh8Node), n_nodes, hipMemcpyDeviceToHost));
+    if (n_prims) HIP_TRY(ctx, hipMemcpy2D(out->triangles, sizeof(PrimRecord), t->dev.d_prims, t->prim_stride, sizeof(PrimRecord), n_prims, hipMemcpyDeviceToHost));
     return HRT_OK;
 }
 

@@ -246,14 +246,14 @@ int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params
     const DenoiseWork &d = ctx->denoise;
     DenoiseTemporalArgs ta{};
     ta.rays = d.rays; ta.tuvp = d.tuvp; ta.inst = d.inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
-    ta.inst_inv = t->d_inst_inv; ta.prev_xf = prev.xf;
+    ta.inst_inv = t->dev.d_inst_inv; ta.prev_xf = prev.xf;
     ta.prev_accum = prev.accum; ta.prev_length = prev.length; ta.prev_guides = prev.guides; ta.prev_id = prev.id;
     ta.accum = next.accum; ta.length = next.length; ta.id = next.id; ta.motion = h.motion;
     ta.width = width; ta.height = height; ta.has_history = has_history ? 1u : 0u;
     std::memcpy(ta.prev_center, prev.center, 12); std::memcpy(ta.prev_U, prev.U, 12); std::memcpy(ta.prev_V, prev.V, 12); std::memcpy(ta.prev_W, prev.W, 12);
     ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
     launch_denoise_temporal(ta, s);
-    HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->dev.d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
     std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
     std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
     h.cur ^= 1u;

@@ -1,7 +1,7 @@
 // hrt_internal.hpp -- what the translation units of libhrt.so share: the objects behind the opaque handles of
 // include/hrt.h (context, BLAS, TLAS, workspace), error plumbing and the helpers that cross file boundaries.
 // hrt_api.cpp: context, materials, RNG, the launch, measurement.  hrt_accel.cpp: acceleration structures
-// (build, per-frame refit, trees over instances, poses, download).
+// (build, per-frame refit, trees over instances, poses, download).  hrt_mem.cpp: the device memory a context keeps between builds.
 #pragma once
 #include "../../include/hrt.h"
 #include "bvh8.h"
@@ -19,6 +19,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -45,6 +46,28 @@ struct Blas {
     ~Blas() { if (d_verts) (void)hipFree(d_verts); if (d_tmpl_nodes) (void)hipFree(d_tmpl_nodes); if (d_tmpl_prims) (void)hipFree(d_tmpl_prims); }
 };
 
+// The device memory of a TLAS: every member is a block from the context's pool (pool_alloc) and nothing else, so that free_tlas_device
+// can hand them all back by walking the struct and reset them by value.  A new table is declared here and nowhere else.
+struct TlasDevice {
+    void *d_nodes = nullptr, *d_prims = nullptr;
+    float *d_inst_inv = nullptr;
+    uint32_t *d_inst_identity = nullptr;
+    // refit (hrt_tlas_update): the device tables the refit kernel reads
+    float *d_node_box = nullptr, *d_node_ref = nullptr;
+    uint32_t *d_order = nullptr;                         // trees over instances: refit order (NULL: breadth-first index ranges)
+    float *d_inst_xf = nullptr, *d_area = nullptr;
+    const void **d_inst_src = nullptr;
+    uint32_t *d_inst_first = nullptr, *d_inst_kind = nullptr;   // device build: global number of each instance's first primitive; geometry kind
+    uint32_t *d_inst_root = nullptr;                     // two-level trees, per instance: node index of its BLAS's root
+    float *d_blas_bound = nullptr;                       // two-level trees, per instance, 10 floats: its BLAS's object-space box and bounding sphere (the top level's "geometry")
+    // asynchronous updates (HRT_CTX_ASYNC_UPDATE): what the tree was built with, for the device-side tables kernel, and its verdict
+    unsigned long long *d_sig_handle = nullptr; uint32_t *d_sig_visibility = nullptr, *d_sig_sbt = nullptr; float *d_blas_box = nullptr;
+    uint32_t *d_update_flags = nullptr;                  // [0] scene scale (float bits), [1] bit 0: handle / visibility changed, bit 1: an sbtOffset changed
+    float *d_rec_box = nullptr;                          // small trees: 6 floats per record, the refit's per-record pass (refit.hip k_refit_records)
+};
+static_assert(std::is_standard_layout<TlasDevice>::value && std::is_trivially_copyable<TlasDevice>::value && sizeof(TlasDevice) % sizeof(void *) == 0,
+              "TlasDevice holds pool blocks only: free_tlas_device walks it as an array of pointers");
+
 struct Tlas {
     uint32_t n_instances = 0;
     std::vector<uint32_t> sbt_offset;      // per instance
@@ -52,24 +75,17 @@ struct Tlas {
     Bvh8 bvh;                               // host copy of a HOST-built tree (empty for device builds)
     uint32_t n_nodes = 0, n_prims = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    void *d_nodes = nullptr, *d_prims = nullptr;
-    float *d_inst_inv = nullptr;
-    uint32_t *d_inst_identity = nullptr;
+    TlasDevice dev;                         // nodes, records and every per-instance table on the device
     bool has_spheres = false;
     uint32_t node_stride = 80, prim_stride = 48;
     uint64_t alloc_bytes = 0;               // device memory of nodes + node boxes / reference areas + records, as allocated
     uint64_t generation = 0;
-    // refit (hrt_tlas_update): what must stay the same, and the device tables the refit kernel reads
+    // refit (hrt_tlas_update): what must stay the same (the device tables the refit kernel reads: TlasDevice)
     std::vector<std::shared_ptr<Blas>> blas_refs;       // keeps the source geometry alive
     std::vector<uint64_t> sig_handle; std::vector<uint32_t> sig_visibility;
     std::vector<float> h_xf, h_inv; std::vector<uint32_t> h_ident;   // staging of the per-instance uploads
-    float *d_node_box = nullptr, *d_node_ref = nullptr, *d_inst_xf = nullptr, *d_area = nullptr;
-    uint32_t *d_order = nullptr;                         // trees over instances: refit order (NULL: breadth-first index ranges)
-    uint32_t *d_inst_first = nullptr, *d_inst_kind = nullptr;   // device build: global number of each instance's first primitive; geometry kind
-    // asynchronous updates (HRT_CTX_ASYNC_UPDATE): what the tree was built with, for the device-side tables kernel, and its verdict
-    unsigned long long *d_sig_handle = nullptr; uint32_t *d_sig_visibility = nullptr, *d_sig_sbt = nullptr; float *d_blas_box = nullptr;
-    uint32_t *d_update_flags = nullptr;                  // [0] scene scale (float bits), [1] bit 0: handle / visibility changed, bit 1: an sbtOffset changed
-    bool built_posed = false;                            // built by an update, for the poses of that frame (not the reference's identity-posed load-time build): asynchronous updates may follow at once
+    // asynchronous updates (HRT_CTX_ASYNC_UPDATE)
+    bool built_posed = false;                           // built by an update, for the poses of that frame (not the reference's identity-posed load-time build): asynchronous updates may follow at once
     bool async_words_ready = false;                      // d_update_flags / d_area are in their initial state (the asynchronous update's epilogue leaves them so)
     uint32_t *h_update_flags = nullptr;                  // pinned: [0..1] copy of the above after the last update, [2..3] their initial values
     std::vector<std::pair<uint32_t, uint32_t>> phases;   // (first, count) in processing order, children before parents
@@ -79,14 +95,10 @@ struct Tlas {
     // trees' records only.  Memory and update cost: instances + unique primitives.
     bool two_level = false; uint32_t n_top_nodes = 0, n_unique_blas = 0;
     bool scene_of_bodies = false;        // at least 4 visible instances of fewer than 20 000 primitives each on average (the reference's kind of scene)
-    uint32_t *d_inst_root = nullptr;                     // per instance: node index of its BLAS's root
-    float *d_blas_bound = nullptr;                       // per instance, 10 floats: its BLAS's object-space box and bounding sphere (the top level's "geometry")
     float built_reach = 1.0f;                            // the largest object-space |coordinate| a ray origin was assumed to have when the BLAS trees were padded
     bool has_split_refs = false;                         // built with spatial splits (HRT_CTX_FAST_TRACE): a refit would recompute the leaf boxes from whole primitives, so the first update rebuilds instead
-    const void **d_inst_src = nullptr;
     float *h_area = nullptr;                             // pinned: area sum of the last refit
     hipEvent_t area_ready = nullptr; bool area_pending = false;
-    float *d_rec_box = nullptr;                          // small trees: 6 floats per record, the refit's per-record pass (refit.hip k_refit_records)
     uint64_t refits = 0, rebuilds = 0, refits_since_build = 0;
 };
 
@@ -162,7 +174,7 @@ struct HrtContext {
     std::unordered_map<uint64_t, std::unique_ptr<hrt::Tlas>> tlas;
     uint64_t next_handle = 0x1000;
     std::mutex pin_mu; void *pin_stage = nullptr; size_t pin_bytes = 0;      // pinned staging for the instance array of large synchronous updates (hrt_accel.cpp download_instances)
-    std::mutex scratch_mu; std::vector<hrt::ScratchArena> scratch_free;      // scratch_acquire / scratch_release (hrt_accel.cpp)
+    std::mutex scratch_mu; std::vector<hrt::ScratchArena> scratch_free;      // scratch_acquire / scratch_release (hrt_mem.cpp)
     std::mutex pool_mu; std::vector<hrt::ScratchArena> pool_free; std::unordered_map<void *, size_t> pool_live; size_t pool_bytes = 0;   // pool_alloc / pool_release: the trees' device memory
     // materials
     std::vector<HrtSbtRecord> records;
@@ -287,13 +299,14 @@ int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n
 void free_denoise_work(HrtContext *ctx);
 void free_denoise_history(HrtContext *ctx);
 
-// hrt_accel.cpp
+// hrt_mem.cpp
 hrt::ScratchArena scratch_acquire(HrtContext *ctx, size_t bytes);      // {nullptr, 0} when the device is out of memory
 void scratch_release(HrtContext *ctx, hrt::ScratchArena a);
-void free_tlas_device(HrtContext *ctx, Tlas &t);
 hipError_t pool_alloc(HrtContext *ctx, void **p, size_t bytes);
 void pool_release(HrtContext *ctx, void *p);
 void pool_drain(HrtContext *ctx);
+// hrt_accel.cpp
+void free_tlas_device(HrtContext *ctx, Tlas &t);
 void free_tlas_host(Tlas &t);
 
 }  // namespace hrt

@@ -215,6 +215,7 @@ __device__ __forceinline__ V3 fold_chain(bool miss, const float *bg, const uint3
 // ---------------------------------------------------------------------------------------
 constexpr int kLdsStack = 8;          // entries per lane staged in LDS
 constexpr int kSpillStack = 56;       // overflow entries per lane in scratch
+static_assert(kLdsStack + kSpillStack == (int)kTraversalStackEntries, "the builds' depth limit (device_types.h) is this stack's capacity");
 constexpr int kTraverseBlock = 64;         // one wave per workgroup
 
 struct TravState {
