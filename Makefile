@@ -17,11 +17,11 @@ all: lib oracle tools
 
 lib: $(LIBDIR)/libhrt.so $(LIBDIR)/libhrt_io.so
 
-$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h
+$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/path_lane.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/fused.o: $(CSRC)/fused.hip $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h
+$(LIBDIR)/fused.o: $(CSRC)/fused.hip $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -116,7 +116,7 @@ clean:
 
 # instrumented build for tools/lane_stats.py: lane-utilisation counters compiled into the path kernels
 stats: $(LIBDIR)/libhrt_stats.so
-$(LIBDIR)/libhrt_stats.so: $(LIBDIR)/fused_queue.o $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(LIBDIR)/libhrt.so
+$(LIBDIR)/libhrt_stats.so: $(LIBDIR)/fused_queue.o $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h $(LIBDIR)/libhrt.so
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/kernels.hip -o $(LIBDIR)/kernels_stats.o
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused.hip -o $(LIBDIR)/fused_stats.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/kernels_stats.o $(LIBDIR)/fused_stats.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o -pthread

@@ -11,14 +11,16 @@
 // count: the SIMD issues one instruction of any kind per ~2.4 cycles and this kernel is bound by exactly that --, one scatter body
 // for all programs, an issue priority per loop phase, and tail splitting once the tile is used up (lanes without a pixel take
 // subtrees off the busy lanes' stacks; the pieces of a ray share one best hit in LDS).  The loop between two regenerations is
-// trav_loop.h's, shared with k_trace_queue (fused_queue.hip); what is here is the regeneration phase and the two-level tree's
-// transform-node steps.
+// trav_loop.h's, shared with k_trace_queue (fused_queue.hip); the steps of the regeneration phase are path_lane.h's, shared with
+// k_traverse<.., FUSED>.  What is here is when a regeneration happens, the primary-hit cache (REUSE) round those steps, and the
+// two-level tree's transform-node steps.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 #include "device_types.h"
 #include "trav_common.h"
 #include "trav_loop.h"
+#include "path_lane.h"
 
 #pragma clang fp contract(off)
 
@@ -152,15 +154,8 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
     F.home = tx;
     bool exhausted = false;                 // wave-uniform: no pixels left to start
 
-    // the lane's pixel
-    bool have_pixel = false, px_first = true;
-    uint32_t px_local = 0u, px_tid = 0u, px_sample = 0u, px_depth = 1u;
-    uint32_t px_chain[4] = {0u, 0u, 0u, 0u};
-    float px_ax = 0.0f, px_ay = 0.0f, px_az = 0.0f;
-    uint32_t px_t0 = 0u;                                    // probe launch: clock at the pixel's start
-    float px_pdx = 0.0f, px_pdy = 0.0f, px_pdz = 1.0f;      // the pixel's primary direction: the same for every sample (no jitter, Shader.cu:249-261)
-    Xorwow px_rng{};
-    uint32_t px_rays_closest = 0u, px_rays_any = 0u;
+    PathLane P;                             // the lane's pixel: path_lane.h
+    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path
     LaneStats stats;
 
     // the wave's slice of the tile: [wbeg, wend); slices of fetch_chunk pixels are handed out by kFetchShards counters
@@ -179,11 +174,10 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
         if (force_regen || idle == ~0ull || (exhausted ? (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
             stats.regeneration();
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
-            bool launch = false, want_primary = false;      // launch: this lane starts the ray (ro, rd) below
+            PathStep st;                            // st.launch: this lane starts the ray (st.ro, st.rd) below
             [[maybe_unused]] bool reshade = false;
             [[maybe_unused]] const bool was_forced = force_regen;
             force_regen = false;
-            V3 ro = mk3(0.0f, 0.0f, 0.0f), rd = mk3(0.0f, 0.0f, 1.0f);
             if (!F.alive && F.waiting) {
                 F.waiting = false;
                 const TravState &s = L.s;
@@ -194,102 +188,30 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
                     float4 *slot = a.path.primary_cache + 2u * (blockIdx.x * kTraverseBlock + tx);
                     if (cached) {                   // ... or, for a primary ray that was not traversed again, what the pixel's first sample found
                         const float4 c0 = slot[0]; const float4 c1 = slot[1];
-                        o = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); d = mk3(px_pdx, px_pdy, px_pdz);
+                        o = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); d = mk3(P.px_pdx, P.px_pdy, P.px_pdz);
                         bt = c0.x; bu = c0.y; bv = c0.z; bprim = __float_as_uint(c0.w); binst = __float_as_uint(c1.x);
                         cached = false;
-                    } else if (!a.path.trace_rays && px_depth == 1u && px_sample == 0u) {      // the primary hit of the pixel's first sample in this launch
+                    } else if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // the primary hit of the pixel's first sample in this launch
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                const bool miss = bprim == kMissPrim;
-                if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
-                    a.path.trace_tuvp[px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
-                    a.path.trace_inst[px_local] = binst;
-                    have_pixel = false;
-                } else if (miss || px_depth >= kRayTraceDepth) {
-                    // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
-                    const V3 r = fold_chain(miss, a.path.bg, px_chain, px_depth, a.path.hitgroups);
-                    if (px_first) { px_ax = r.x; px_ay = r.y; px_az = r.z; px_first = false; }
-                    else { px_ax += r.x; px_ay += r.y; px_az += r.z; }
-                    ++px_sample;
-                    if constexpr (REUSE) {
-                        // a primary ray that leaves the scene: every sample of the pixel is the background colour, added one by one
-                        if (miss && px_depth == 1u && !a.path.slice_cost)
-                            for (; px_sample < a.path.spp; ++px_sample) { px_ax += r.x; px_ay += r.y; px_az += r.z; }
-                    }
-                    if (a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
-                        atomicAdd(a.path.slice_cost + px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - px_t0) >> 4);
-                    if (px_sample >= a.path.spp) {
-                        a.path.accum[px_local] = make_float4(px_ax, px_ay, px_az, 0.0f);
-                        rng_store(a.path.states + px_tid, px_rng);
-                        have_pixel = false;
-                    } else want_primary = true;
+                st = path_finish<HAS_SPHERES, REUSE>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
+            }
+            exhausted = path_take(P, st, a, n_pixels, !F.alive && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx);
+            if (st.want_primary) {
+                bool from_cache = false;
+                if constexpr (REUSE) from_cache = !a.path.trace_rays && P.px_sample > 0u;
+                if (from_cache) {
+                    // a pixel's later primary rays are not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
+                    P.px_depth = 1u; F.waiting = true; cached = true; reshade = true;
                 } else {
-                    const uint32_t inst = binst;
-                    const HitGroup hg = a.path.hitgroups[inst];
-                    const uint32_t program = a.path.inst_program[inst];
-                    V3 hp, nd;
-                    scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, px_rng, hp, nd);
-                    px_chain[px_depth - 1u] = inst;
-                    ++px_depth;
-                    ro = hp; rd = nd; launch = true;
+                    const PathRay r = path_primary<false>(P, a);
+                    st.ro = r.o; st.rd = r.d; st.launch = true;
                 }
             }
-            // lanes without a pixel take the next ones of the wave's slice of the tile
-            const uint64_t need = __ballot(!F.alive && !have_pixel && !want_primary && !launch);
-            if (need != 0ull && !exhausted) {
-                if (wbeg >= wend) {
-                    // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
-                    // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
-                    wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_pixels, tx,
-                                    [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
-                    if (wbeg >= wend) exhausted = true;
-                }
-                if (!exhausted) {
-                    const uint32_t n_need = (uint32_t)__popcll(need);
-                    const uint32_t take = n_need < wend - wbeg ? n_need : wend - wbeg;
-                    const uint32_t rank = lane_prefix(need);
-                    const uint32_t mine = wbeg + rank;
-                    wbeg += take;
-                    if (!F.alive && !have_pixel && !want_primary && !launch && rank < take) {
-                        const uint32_t j = a.path.first_pixel + mine;
-                        px_local = j;
-                        have_pixel = true; want_primary = true;
-                        if (!a.path.trace_rays) {
-                            const uint32_t row = j / a.path.width;
-                            const uint32_t ix = j - row * a.path.width;
-                            const uint32_t iy = a.path.rows[row];
-                            px_tid = iy * a.path.width + ix;
-                            px_sample = 0u; px_rng = rng_load(a.path.states + px_tid);
-                            px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
-                            if (!px_first) { const float4 acc = a.path.accum[px_local]; px_ax = acc.x; px_ay = acc.y; px_az = acc.z; }
-                            if (a.path.slice_cost) px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-                            const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
-                            px_pdx = pd.x; px_pdy = pd.y; px_pdz = pd.z;
-                        }
-                    }
-                }
-            }
-            if (want_primary) {
-                if (a.path.trace_rays) {
-                    const RayRec r = a.path.trace_rays[px_local];
-                    px_depth = a.path.trace_any ? kRayTraceDepth : 1u;      // any-hit queries take the depth-limit ray's early exit
-                    ro = mk3(r.o.x, r.o.y, r.o.z); rd = mk3(r.d.x, r.d.y, r.d.z);
-                    launch = true;
-                } else {
-                    px_depth = 1u;
-                    ro = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); rd = mk3(px_pdx, px_pdy, px_pdz);
-                    launch = true;
-                    if constexpr (REUSE) {
-                        // not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
-                        if (px_sample > 0u) { launch = false; F.waiting = true; cached = true; reshade = true; }
-                    }
-                }
-            }
-            if (launch) {
-                F.any = px_depth >= kRayTraceDepth;      // a hit at the depth limit is black whatever it is (Shader.cu:102-107)
-                if (F.any) ++px_rays_any; else ++px_rays_closest;
-                lean_start(L, ro, rd, tmax_ray);
+            if (st.launch) {
+                F.any = path_count_ray(P);
+                lean_start(L, st.ro, st.rd, tmax_ray);
                 if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
                 F.alive = true;
             }
@@ -303,42 +225,27 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
 
         // ---- traverse until enough lanes have finished to make a regeneration worthwhile: trav_loop.h; the copy with tail splitting
         //      and the drained phase's exit rule runs once the tile is used up ----
-        if (exhausted) traverse_to_regen<HAS_SPHERES, INSTANCED, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !have_pixel, tx);
-        else traverse_to_regen<HAS_SPHERES, INSTANCED, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !have_pixel, tx);
+        if (exhausted) traverse_to_regen<HAS_SPHERES, INSTANCED, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+        else traverse_to_regen<HAS_SPHERES, INSTANCED, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
-#ifdef HRT_LANE_STATS
-    if (tx == 0u) {
-        unsigned long long *d = reinterpret_cast<unsigned long long *>(a.path.rays_closest);
-        atomicAdd(d + 6, stats.iter); atomicAdd(d + 7, stats.alive); atomicAdd(d + 8, stats.node); atomicAdd(d + 9, stats.prim); atomicAdd(d + 2, stats.ppass); atomicAdd(d + 3, stats.regen); atomicAdd(d + 4, stats.enter);
-    }
-#endif
-    for (int off = 32; off > 0; off >>= 1) {
-        px_rays_closest += (uint32_t)__shfl_down((int)px_rays_closest, off);
-        px_rays_any += (uint32_t)__shfl_down((int)px_rays_any, off);
-    }
-    if (tx == 0u) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_closest), (unsigned long long)px_rays_closest);
-        atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_any), (unsigned long long)px_rays_any);
-    }
+    stats.report(a.path.rays_closest, tx);
+    path_report_rays(P, a, tx);
 }
 
-// one launch renders every sample of every pixel of the tile
-void launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
+// one launch renders every sample of every pixel of the tile: the instantiation for the scene's primitives and, where the caller has set
+// a primary-hit cache up, primary reuse
+template <bool INSTANCED>
+static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    const bool reuse = a.path.primary_cache != nullptr;
-    if (has_spheres && reuse) hipLaunchKernelGGL((k_fused<true, false, true>), g, b, 0, s, a);
-    else if (has_spheres) hipLaunchKernelGGL((k_fused<true, false, false>), g, b, 0, s, a);
-    else if (reuse) hipLaunchKernelGGL((k_fused<false, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_fused<false, false, false>), g, b, 0, s, a);
+    switch ((has_spheres ? 2 : 0) | (a.path.primary_cache != nullptr ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL((k_fused<false, INSTANCED, false>), g, b, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((k_fused<false, INSTANCED, true>), g, b, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((k_fused<true, INSTANCED, false>), g, b, 0, s, a); break;
+        default: hipLaunchKernelGGL((k_fused<true, INSTANCED, true>), g, b, 0, s, a); break;
+    }
 }
+void launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { launch_fused_as<false>(a, has_spheres, grid_blocks, s); }
 // ... through a two-level tree (transform nodes over shared BLASes)
-void launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
-    const dim3 g(grid_blocks), b(kTraverseBlock);
-    const bool reuse = a.path.primary_cache != nullptr;
-    if (has_spheres && reuse) hipLaunchKernelGGL((k_fused<true, true, true>), g, b, 0, s, a);
-    else if (has_spheres) hipLaunchKernelGGL((k_fused<true, true, false>), g, b, 0, s, a);
-    else if (reuse) hipLaunchKernelGGL((k_fused<false, true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_fused<false, true, false>), g, b, 0, s, a);
-}
+void launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { launch_fused_as<true>(a, has_spheres, grid_blocks, s); }
 
 }  // namespace hrt

@@ -2,8 +2,8 @@
 // separate launches, hrt_api.cpp).  Its traversal loop is the production path kernel's, the very same code (trav_loop.h: two small LDS
 // stacks, the hand-written bookkeeping, hand-counted vmcnt, issue priorities per phase, tail splitting with a shared best hit); what is
 // here is what feeds it from ray queues instead of pixels: a lane takes a RayRec from one of up to two queue segments
-// (their lengths are read from device memory, so a render is a fixed sequence of launches), traverses it, and writes the hit
-// record; no path state, no RNG.  Replaces optixTrace = RT-core traversal + built-in intersection (shader/Shader.cu:70,
+// (their lengths are read from device memory, so a render is a fixed sequence of launches; trav_common.h's queue_* helpers, shared
+// with k_traverse), traverses it, and writes the hit record; no path state, no RNG.  Replaces optixTrace = RT-core traversal + built-in intersection (shader/Shader.cu:70,
 // src/Global/RendererImpl.cu:295-314) for the rays of one wavefront stage.  Round 1's k_traverse (kernels.hip) stays for the
 // counting build and for trees outside k_fused's limits (deeper than its node stack, or beyond 32-bit offsets).
 #include <hip/hip_runtime.h>
@@ -25,10 +25,8 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
     __shared__ uint32_t s_mb_prim[kTraverseBlock], s_mb_inst[kTraverseBlock], s_mb_pending[kTraverseBlock];
     __shared__ uint32_t s_pair[kTraverseBlock];
 
-    // up to two queue segments per launch (e.g. the depth-4 rays of sample s and the primary rays of sample s + 1): ray i < n_a
-    // comes from segment 0, the others from segment 1
-    const uint32_t n_a = a.seg[0].n_ptr ? (a.seg[0].n_ptr[0] + a.seg[0].n_ptr[1] + a.seg[0].n_ptr[2] + a.seg[0].n_ptr[3]) : a.seg[0].n;
-    const uint32_t n_b = a.seg[1].rays ? (a.seg[1].n_ptr ? (a.seg[1].n_ptr[0] + a.seg[1].n_ptr[1] + a.seg[1].n_ptr[2] + a.seg[1].n_ptr[3]) : a.seg[1].n) : 0u;
+    // up to two queue segments per launch (trav_common.h: queue_*)
+    const uint32_t n_a = queue_length(a.seg[0]), n_b = a.seg[1].rays ? queue_length(a.seg[1]) : 0u;
     const uint32_t n_rays = n_a + n_b;
     const char *__restrict__ node_bytes = reinterpret_cast<const char *>(a.nodes);
     const char *__restrict__ prim_bytes = reinterpret_cast<const char *>(a.prims);
@@ -60,12 +58,7 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
             if (!F.alive && F.waiting) {
                 F.waiting = false;
                 const TravState &s = L.s;
-                const bool in_b = q_index >= n_a;
-                const uint32_t k = in_b ? q_index - n_a : q_index;
-                float4 *tuvp = in_b ? a.seg[1].hit_tuvp : a.seg[0].hit_tuvp;
-                uint32_t *hinst = in_b ? a.seg[1].hit_inst : a.seg[0].hit_inst;
-                tuvp[k] = make_float4(s.bt, s.bu, s.bv, __uint_as_float(s.bprim));
-                hinst[k] = s.binst;
+                queue_write_hit(a, queue_pos(q_index, n_a), s.bt, s.bu, s.bv, s.bprim, s.binst);
             }
             const uint64_t need = __ballot(!F.alive);
             bool launch = false;
@@ -84,9 +77,9 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
                 }
             }
             if (launch) {
-                const bool in_b = q_index >= n_a;
-                const RayRec r = in_b ? a.seg[1].rays[q_index - n_a] : a.seg[0].rays[q_index];
-                F.any = (in_b ? a.seg[1].any_hit : a.seg[0].any_hit) != 0u;
+                const QueuePos qp = queue_pos(q_index, n_a);
+                const RayRec r = queue_ray(a, qp);
+                F.any = queue_any_hit(a, qp);
                 lean_start(L, mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z), tmax_ray);
                 F.alive = true;
             }

@@ -8,7 +8,9 @@
 //   k_generate      primary rays                 (Shader.cu:246-267)
 //   k_traverse      persistent-wave BVH8 closest-hit / any-hit traversal (optixTrace, Shader.cu:70): round 1's kernel, now
 //                   the counting walk (COUNT) and the traversal -- over ray queues, or as a path kernel (FUSED) -- of the
-//                   trees that k_trace_queue / k_fused cannot take
+//                   trees that k_trace_queue / k_fused cannot take.  Its own: the loop, one mixed LDS + scratch stack
+//                   without a depth limit, merge-at-finish tail splitting.  Shared with the newer kernels: the regeneration
+//                   phase (path_lane.h), the queue feed, the ray start and the node step (trav_common.h)
 //   k_bin_hits      sort hits by program with wave ballot + prefix count (SBT dispatch)
 //   k_shade<P>      one kernel per closest-hit program (Shader.cu:108-233)
 //   k_accumulate    path termination: miss colour / depth cut-off, innermost-first albedo fold
@@ -24,6 +26,7 @@
 #include "device_types.h"
 #include "srgb_pow.h"
 #include "trav_common.h"
+#include "path_lane.h"
 
 #pragma clang fp contract(off)
 
@@ -93,10 +96,8 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
     __shared__ uint32_t s_pair[kTraverseBlock];
     uint2 spill[kSpillStack];
 
-    // up to two queue segments per launch (e.g. the depth-4 rays of sample s and the primary rays of
-    // sample s+1): ray i < n_a comes from segment 0, the others from segment 1
-    const uint32_t n_a = a.seg[0].n_ptr ? (a.seg[0].n_ptr[0] + a.seg[0].n_ptr[1] + a.seg[0].n_ptr[2] + a.seg[0].n_ptr[3]) : a.seg[0].n;
-    const uint32_t n_b = a.seg[1].rays ? (a.seg[1].n_ptr ? (a.seg[1].n_ptr[0] + a.seg[1].n_ptr[1] + a.seg[1].n_ptr[2] + a.seg[1].n_ptr[3]) : a.seg[1].n) : 0u;
+    // up to two queue segments per launch (trav_common.h: queue_*)
+    const uint32_t n_a = queue_length(a.seg[0]), n_b = a.seg[1].rays ? queue_length(a.seg[1]) : 0u;
     const uint32_t n_rays = FUSED ? a.path.n_tile_pixels : n_a + n_b;     // fused: the queue is the tile's pixel list
     const char *__restrict__ node_bytes = reinterpret_cast<const char *>(a.nodes);
     const char *__restrict__ prim_bytes = reinterpret_cast<const char *>(a.prims);
@@ -114,19 +115,12 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
 
     // FUSED (path mode): the lane owns a pixel and carries its path state; a finished ray is shaded in
     // place and the next ray (bounce, next sample, next pixel) starts in the same lane -- no queues, no
-    // per-stage launches, no stage barriers.  Path mode runs it only for trees k_fused cannot take
-    // (fits_fused_kernel, hrt_api.cpp).
-    bool have_pixel = false, waiting = false, px_first = true;
-    uint32_t px_local = 0u, px_tid = 0u, px_sample = 0u, px_depth = 1u;
-    uint32_t px_chain[4] = {0u, 0u, 0u, 0u};
-    float px_ax = 0.0f, px_ay = 0.0f, px_az = 0.0f;
-    uint32_t px_t0 = 0u;                                    // probe launch: clock at the pixel's start
-    float px_pdx = 0.0f, px_pdy = 0.0f, px_pdz = 1.0f;      // the pixel's primary direction: the same for every sample (no jitter, Shader.cu:249-261)
-    Xorwow px_rng{};
-    uint32_t px_rays_closest = 0u, px_rays_any = 0u;
-#ifdef HRT_LANE_STATS
-    unsigned long long ls_iter = 0, ls_alive = 0, ls_node = 0, ls_prim = 0, ls_ppass = 0, ls_regen = 0;
-#endif
+    // per-stage launches, no stage barriers: the regeneration phase of path_lane.h, shared with k_fused.
+    // Path mode runs this kernel only for trees k_fused cannot take (fits_fused_kernel, hrt_api.cpp).
+    bool waiting = false;
+    PathLane P;                             // the lane's pixel
+    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path
+    LaneStats stats;
 
     // what the next iteration gathers for this lane
     bool has_node = false, has_prim = false;
@@ -158,6 +152,15 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             has_node = true;
         } else { has_node = false; nidx = 0u; }
     };
+    // a new ray in this lane (the caller has set `any`): the root becomes the lane's next node
+    auto start_ray = [&](V3 o, V3 d) {
+        trav_start<COUNT>(s, o, d, tmax_ray);
+        s.cur = make_uint2(0u, 0x80000000u);
+        s.ptri = make_uint2(0u, 0u);
+        s.sp = 0; s.base = 0;
+        alive = true; has_prim = false; pidx = 0u;
+        advance_select();
+    };
 
     // wave-local slice of the queue: [wbeg, wend).  Slices of fetch_chunk rays are handed out by
     // kFetchShards counters (chunk c of shard s covers rays (c * kFetchShards + s) * fetch_chunk ...),
@@ -173,105 +176,20 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
         if (FUSED) {
             // ---- regenerate: shade finished rays in place, start the next sample / pixel ----
             if (n_idle >= (uint32_t)a.refill_threshold || idle == ~0ull) {
-#ifdef HRT_LANE_STATS
-                ++ls_regen;
-#endif
-                auto start_ray = [&](V3 o, V3 d) {
-                    s.ox = o.x; s.oy = o.y; s.oz = o.z; s.dx = d.x; s.dy = d.y; s.dz = d.z;
-                    s.idx = safe_rcp_dir<COUNT>(s.dx); s.idy = safe_rcp_dir<COUNT>(s.dy); s.idz = safe_rcp_dir<COUNT>(s.dz);
-                    const uint32_t oct = (s.dx < 0.0f ? 4u : 0u) | (s.dy < 0.0f ? 2u : 0u) | (s.dz < 0.0f ? 1u : 0u);
-                    s.oct_inv4 = (7u - oct) * 0x01010101u;
-                    s.bt = tmax_ray; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
-                    s.cur = make_uint2(0u, 0x80000000u);
-                    s.ptri = make_uint2(0u, 0u);
-                    s.sp = 0; s.base = 0;
-                    any = px_depth >= kRayTraceDepth;      // a hit at the depth limit is black whatever it is
-                    if (any) ++px_rays_any; else ++px_rays_closest;
-                    alive = true; has_prim = false; pidx = 0u;
-                    advance_select();
-                };
-                bool want_primary = false;
+                stats.regeneration();
+                // (a bounce starts at once, before the next pixels are taken: its origin and direction need not live through that)
+                auto launch = [&](V3 o, V3 d) { any = path_count_ray(P); start_ray(o, d); };
+                PathStep st;
                 if (!alive && waiting) {
                     waiting = false;
-                    const bool miss = s.bprim == kMissPrim;
-                    if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
-                        a.path.trace_tuvp[px_local] = make_float4(s.bt, s.bu, s.bv, __uint_as_float(s.bprim));
-                        a.path.trace_inst[px_local] = s.binst;
-                        have_pixel = false;
-                    } else if (miss || px_depth >= kRayTraceDepth) {
-                        const V3 r = fold_chain(miss, a.path.bg, px_chain, px_depth, a.path.hitgroups);
-                        if (px_first) { px_ax = r.x; px_ay = r.y; px_az = r.z; px_first = false; }
-                        else { px_ax += r.x; px_ay += r.y; px_az += r.z; }
-                        ++px_sample;
-                        if (a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
-                            atomicAdd(a.path.slice_cost + px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - px_t0) >> 4);
-                        if (px_sample >= a.path.spp) {
-                            a.path.accum[px_local] = make_float4(px_ax, px_ay, px_az, 0.0f);
-                            rng_store(a.path.states + px_tid, px_rng);
-                            have_pixel = false;
-                        } else want_primary = true;
-                    } else {
-                        const uint32_t inst = s.binst;
-                        const HitGroup hg = a.path.hitgroups[inst];
-                        const uint32_t program = a.path.inst_program[inst];
-                        const V3 ro = mk3(s.ox, s.oy, s.oz), rd = mk3(s.dx, s.dy, s.dz);
-                        V3 hp, nd;
-                        if (program == (uint32_t)kProgramTriangleRough) scatter<false, true>(hg, ro, rd, s.bt, s.bu, s.bv, s.bprim, px_rng, hp, nd);
-                        else if (program == (uint32_t)kProgramTriangleMetal) scatter<false, false>(hg, ro, rd, s.bt, s.bu, s.bv, s.bprim, px_rng, hp, nd);
-                        else if (program == (uint32_t)kProgramSphereRough) scatter<true, true>(hg, ro, rd, s.bt, s.bu, s.bv, s.bprim, px_rng, hp, nd);
-                        else scatter<true, false>(hg, ro, rd, s.bt, s.bu, s.bv, s.bprim, px_rng, hp, nd);
-                        px_chain[px_depth - 1u] = inst;
-                        ++px_depth;
-                        start_ray(hp, nd);
-                    }
+                    st = path_finish<HAS_SPHERES, false>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), s.bt, s.bu, s.bv, s.bprim, s.binst);
+                    if (st.launch) launch(st.ro, st.rd);
                 }
-                // lanes without a pixel take the next ones of the wave's slice of the tile
-                const uint64_t need = __ballot(!alive && !have_pixel && !want_primary);
-                if (need != 0ull && !exhausted) {
-                    if (wbeg >= wend) {
-                        // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
-                        // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
-                        wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_rays, tx,
-                                        [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
-                        if (wbeg >= wend) exhausted = true;
-                    }
-                    if (!exhausted) {
-                        const uint32_t n_need = (uint32_t)__popcll(need);
-                        const uint32_t take = n_need < wend - wbeg ? n_need : wend - wbeg;
-                        const uint32_t rank = lane_prefix(need);
-                        const uint32_t mine = wbeg + rank;
-                        wbeg += take;
-                        if (!alive && !have_pixel && !want_primary && rank < take) {
-                            const uint32_t j = a.path.first_pixel + mine;
-                            px_local = j;
-                            have_pixel = true; want_primary = true;
-                            if (!a.path.trace_rays) {
-                                const uint32_t row = j / a.path.width;
-                                const uint32_t ix = j - row * a.path.width;
-                                const uint32_t iy = a.path.rows[row];
-                                px_tid = iy * a.path.width + ix;
-                                px_sample = 0u; px_rng = rng_load(a.path.states + px_tid);
-                                px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
-                                if (!px_first) { const float4 acc = a.path.accum[px_local]; px_ax = acc.x; px_ay = acc.y; px_az = acc.z; }
-                                if (a.path.slice_cost) px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-                                const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
-                                px_pdx = pd.x; px_pdy = pd.y; px_pdz = pd.z;
-                            }
-                        }
-                    }
-                }
-                if (!alive && want_primary && a.path.trace_rays) {
-                    const RayRec r = a.path.trace_rays[px_local];
-                    px_depth = a.path.trace_any ? kRayTraceDepth : 1u;      // any-hit queries take the depth-limit ray's early exit
-                    start_ray(mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z));
-                } else if (!alive && want_primary) {
-                    px_depth = 1u;
-                    V3 pd = mk3(px_pdx, px_pdy, px_pdz);
-                    if (HAS_SPHERES) {      // the sphere build is at its register limit (4 waves per SIMD): recompute instead of keeping
-                        const uint32_t iy = px_tid / a.path.width, ix = px_tid - iy * a.path.width;
-                        pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
-                    }
-                    start_ray(mk3(a.path.center[0], a.path.center[1], a.path.center[2]), pd);
+                exhausted = path_take(P, st, a, n_rays, !alive && !P.have_pixel && !st.want_primary, wbeg, wend, kstart, exhausted, home_shard, tx);
+                if (st.want_primary) {
+                    // (the sphere build is at its register limit: it makes the pixel's primary direction again instead of keeping it)
+                    const PathRay r = path_primary<HAS_SPHERES>(P, a);
+                    launch(r.o, r.d);
                 }
             }
         } else
@@ -287,21 +205,11 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                 const uint32_t mine = wbeg + rank;
                 wbeg += take;
                 if (!alive && rank < take) {
-                    in_b = mine >= n_a;
-                    any = (in_b ? a.seg[1].any_hit : a.seg[0].any_hit) != 0u;
-                    const RayRec r = in_b ? a.seg[1].rays[mine - n_a] : a.seg[0].rays[mine];
-                    s.ox = r.o.x; s.oy = r.o.y; s.oz = r.o.z;
-                    s.dx = r.d.x; s.dy = r.d.y; s.dz = r.d.z;
-                    s.idx = safe_rcp_dir<COUNT>(s.dx); s.idy = safe_rcp_dir<COUNT>(s.dy); s.idz = safe_rcp_dir<COUNT>(s.dz);
-                    const uint32_t oct = (s.dx < 0.0f ? 4u : 0u) | (s.dy < 0.0f ? 2u : 0u) | (s.dz < 0.0f ? 1u : 0u);
-                    s.oct_inv4 = (7u - oct) * 0x01010101u;
-                    s.bt = tmax_ray; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
-                    s.cur = make_uint2(0u, 0x80000000u);
-                    s.ptri = make_uint2(0u, 0u);
-                    s.sp = 0; s.base = 0;
-                    s.slot = in_b ? mine - n_a : mine;
-                    alive = true; has_prim = false; pidx = 0u;
-                    advance_select();                   // the root becomes this lane's next node
+                    const QueuePos qp = queue_pos(mine, n_a);
+                    const RayRec r = queue_ray(a, qp);
+                    in_b = qp.in_b; s.slot = qp.k;
+                    any = queue_any_hit(a, qp);
+                    start_ray(mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z));
                 }
             }
         }
@@ -370,9 +278,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             bool done = false;
             if (any && alive && shared && s_mb_prim[home] != kMissPrim) done = true;   // another piece already found a hit
 
-#ifdef HRT_LANE_STATS
-            { const uint64_t mp = __ballot(alive && has_prim), mn = __ballot(alive && has_node); ++ls_iter; ls_alive += __popcll(__ballot(alive)); ls_node += __popcll(mn); ls_prim += __popcll(mp); ls_ppass += mp != 0ull; }
-#endif
+            stats.iteration(alive, __ballot(alive && has_node), __ballot(alive && has_prim));
             // ---- C. leaf test: waits for the primitive pieces only ----
             wait_prim_loads(rpa, rpb, rpc);
             if (!COUNT && alive && !done && has_prim) {
@@ -387,45 +293,10 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             uint2 tri = make_uint2(0u, 0u);
             wait_node_loads(rn0, rn1, rn2, rn3, rn4);
             if (alive && !done && has_node) {
-                const uint4 n0 = make_uint4(rn0.x, rn0.y, rn0.z, rn0.w), n1 = make_uint4(rn1.x, rn1.y, rn1.z, rn1.w);
-                const uint4 n2 = make_uint4(rn2.x, rn2.y, rn2.z, rn2.w), n3 = make_uint4(rn3.x, rn3.y, rn3.z, rn3.w);
-                const uint4 n4 = make_uint4(rn4.x, rn4.y, rn4.z, rn4.w);
                 if (COUNT) { if (in_b) ++cnt_nodes_b; else ++cnt_nodes; }
-                const float px = __uint_as_float(n0.x), py = __uint_as_float(n0.y), pz = __uint_as_float(n0.z);
-                const uint32_t e_imask = n0.w;
-                const float aix = __uint_as_float((e_imask & 0xffu) << 23) * s.idx;
-                const float aiy = __uint_as_float(((e_imask >> 8) & 0xffu) << 23) * s.idy;
-                const float aiz = __uint_as_float(((e_imask >> 16) & 0xffu) << 23) * s.idz;
-                const float aox = (px - s.ox) * s.idx, aoy = (py - s.oy) * s.idy, aoz = (pz - s.oz) * s.idz;
-                const bool nx = s.dx < 0.0f, ny = s.dy < 0.0f, nz = s.dz < 0.0f;
-                uint32_t hitmask = 0u;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const uint32_t meta4 = h ? n1.w : n1.z;
-                    const uint32_t is_inner4 = (meta4 & (meta4 << 1)) & 0x10101010u;
-                    const uint32_t inner_mask4 = (is_inner4 >> 4) * 0xffu;
-                    const uint32_t bit_index4 = (meta4 ^ (s.oct_inv4 & inner_mask4)) & 0x1f1f1f1fu;
-                    const uint32_t child_bits4 = (meta4 >> 5) & 0x07070707u;
-                    const uint32_t qlox = h ? n2.y : n2.x, qloy = h ? n2.w : n2.z, qloz = h ? n3.y : n3.x;
-                    const uint32_t qhix = h ? n3.w : n3.z, qhiy = h ? n4.y : n4.x, qhiz = h ? n4.w : n4.z;
-                    const uint32_t xn = nx ? qhix : qlox, xf = nx ? qlox : qhix;
-                    const uint32_t yn = ny ? qhiy : qloy, yf = ny ? qloy : qhiy;
-                    const uint32_t zn = nz ? qhiz : qloz, zf = nz ? qloz : qhiz;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float tnx = fmaf(HRT_BYTE_F(xn, j), aix, aox), tfx = fmaf(HRT_BYTE_F(xf, j), aix, aox);
-                        const float tny = fmaf(HRT_BYTE_F(yn, j), aiy, aoy), tfy = fmaf(HRT_BYTE_F(yf, j), aiy, aoy);
-                        const float tnz = fmaf(HRT_BYTE_F(zn, j), aiz, aoz), tfz = fmaf(HRT_BYTE_F(zf, j), aiz, aoz);
-                        const float tlo = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-                        const float thi = fminf(fminf(tfx, tfy), fminf(tfz, s.bt));
-                        const uint32_t cb = (child_bits4 >> (8 * j)) & 0xffu;
-                        const uint32_t bi = (bit_index4 >> (8 * j)) & 0xffu;
-                        // conservative: the builder pads and rounds the child boxes outwards
-                        if (tlo <= thi) hitmask |= cb << bi;
-                    }
-                }
-                s.cur = make_uint2(n1.x, (hitmask & 0xff000000u) | (e_imask >> 24));
-                tri = make_uint2(n1.y, hitmask & 0x00ffffffu);
+                uint2 child;
+                node_slab_test(s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+                s.cur = child;
             }
             has_node = false; nidx = 0u;
 
@@ -475,8 +346,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                 if (FUSED && done) {
                     alive = false; waiting = true; has_node = false; has_prim = false; nidx = 0u; pidx = 0u;   // shaded at the next regeneration
                 } else if (done && !shared) {
-                    (in_b ? a.seg[1].hit_tuvp : a.seg[0].hit_tuvp)[s.slot] = make_float4(s.bt, s.bu, s.bv, __uint_as_float(s.bprim));
-                    (in_b ? a.seg[1].hit_inst : a.seg[0].hit_inst)[s.slot] = s.binst;
+                    queue_write_hit(a, QueuePos{in_b, s.slot}, s.bt, s.bu, s.bv, s.bprim, s.binst);
                     alive = false; has_node = false; has_prim = false; nidx = 0u; pidx = 0u;
                 }
             }
@@ -494,10 +364,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                     if (better) { s_mb_t[home] = s.bt; s_mb_u[home] = s.bu; s_mb_v[home] = s.bv; s_mb_prim[home] = s.bprim; s_mb_inst[home] = s.binst; }
                     const uint32_t pend = s_mb_pending[home] - 1u;
                     s_mb_pending[home] = pend;
-                    if (pend == 0u) {
-                        (in_b ? a.seg[1].hit_tuvp : a.seg[0].hit_tuvp)[s.slot] = make_float4(s_mb_t[home], s_mb_u[home], s_mb_v[home], __uint_as_float(s_mb_prim[home]));
-                        (in_b ? a.seg[1].hit_inst : a.seg[0].hit_inst)[s.slot] = s_mb_inst[home];
-                    }
+                    if (pend == 0u) queue_write_hit(a, QueuePos{in_b, s.slot}, s_mb_t[home], s_mb_u[home], s_mb_v[home], s_mb_prim[home], s_mb_inst[home]);
                     alive = false; shared = false; home = tx; has_node = false; has_prim = false; nidx = 0u; pidx = 0u;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -508,21 +375,9 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             if ((FUSED || !exhausted) && (64u - (uint32_t)__popcll(act)) >= (uint32_t)a.refill_threshold) break;
         }
     }
-#ifdef HRT_LANE_STATS
-    if (FUSED && tx == 0u) {
-        unsigned long long *d = reinterpret_cast<unsigned long long *>(a.path.rays_closest);
-        atomicAdd(d + 6, ls_iter); atomicAdd(d + 7, ls_alive); atomicAdd(d + 8, ls_node); atomicAdd(d + 9, ls_prim); atomicAdd(d + 2, ls_ppass); atomicAdd(d + 3, ls_regen);
-    }
-#endif
     if (FUSED) {
-        for (int off = 32; off > 0; off >>= 1) {
-            px_rays_closest += (uint32_t)__shfl_down((int)px_rays_closest, off);
-            px_rays_any += (uint32_t)__shfl_down((int)px_rays_any, off);
-        }
-        if (tx == 0u) {
-            atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_closest), (unsigned long long)px_rays_closest);
-            atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_any), (unsigned long long)px_rays_any);
-        }
+        stats.report(a.path.rays_closest, tx);
+        path_report_rays(P, a, tx);
     }
     if (COUNT) {
         // wave-level reduction, one atomic pair per wave
@@ -767,8 +622,7 @@ void launch_generate(const GenerateArgs &a, hipStream_t s) {
 }
 void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    const int sel = (count ? 2 : 0) | (has_spheres ? 1 : 0);
-    switch (sel) {
+    switch ((count ? 2 : 0) | (has_spheres ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((k_traverse<false, false, false>), g, b, 0, s, a); break;
         case 1: hipLaunchKernelGGL((k_traverse<false, true, false>), g, b, 0, s, a); break;
         case 2: hipLaunchKernelGGL((k_traverse<true, false, false>), g, b, 0, s, a); break;

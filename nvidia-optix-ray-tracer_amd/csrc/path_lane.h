@@ -1,0 +1,161 @@
+// path_lane.h -- the regeneration phase of a path kernel, ONCE, for k_fused (fused.hip) and k_traverse<.., FUSED> (kernels.hip): a lane
+// OWNS a pixel and carries its path state in registers (PathLane); when its ray has finished it is shaded in place and the next
+// ray -- the bounce, the next sample's primary ray, the next pixel's -- starts in the same lane.  Three steps, in the order a
+// regeneration runs them:
+//   path_finish    what becomes of a finished ray: the hrt_trace_rays record, the end of a path, or a bounce
+//   path_take      lanes without a pixel take the next ones of the wave's slice of the tile
+//   path_primary   the ray a lane that wants a primary ray starts
+// and path_count_ray / path_report_rays for the ray counters.  The kernels keep what is theirs: WHEN a regeneration happens, how a
+// ray is started in their traversal state, k_fused's primary-hit cache (REUSE) and its instance state.
+// Everything is inlined; PathLane is a plain struct of scalars, passed by reference, results come back by value, so that the state
+// stays in registers exactly as when the kernels spelled it out (k_fused has none to spare: check the ISA after any change here).
+#pragma once
+#include "trav_common.h"
+
+namespace hrt {
+
+// the lane's pixel (hrt_trace_rays on a path kernel: a caller's ray, px_local its index).  Scalars only: the albedo chain of the path, an
+// array indexed by the depth, is a variable of its own in the kernels (`uint32_t chain[4]`, path_finish's px_chain) -- as a member it
+// would keep the whole struct in scratch memory.
+struct PathLane {
+    bool have_pixel = false, px_first = true;
+    uint32_t px_local = 0u, px_tid = 0u, px_sample = 0u, px_depth = 1u;
+    float px_ax = 0.0f, px_ay = 0.0f, px_az = 0.0f;
+    uint32_t px_t0 = 0u;                                    // probe launch: clock at the pixel's start
+    float px_pdx = 0.0f, px_pdy = 0.0f, px_pdz = 1.0f;      // the pixel's primary direction: the same for every sample (no jitter, Shader.cu:249-261)
+    Xorwow px_rng{};
+    uint32_t px_rays_closest = 0u, px_rays_any = 0u;
+};
+
+// what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
+struct PathStep {
+    bool launch = false, want_primary = false;
+    V3 ro = {0.0f, 0.0f, 0.0f}, rd = {0.0f, 0.0f, 1.0f};
+};
+
+// A ray (o, d) has finished with the hit record (bt, bu, bv, bprim, binst).  The lane gives its pixel up (have_pixel = false: record or
+// sum written), wants the next sample's primary ray, or launches the bounce.
+// REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
+template <bool HAS_SPHERES, bool REUSE>
+__device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst) {
+    PathStep st;
+    const bool miss = bprim == kMissPrim;
+    if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
+        a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
+        a.path.trace_inst[P.px_local] = binst;
+        P.have_pixel = false;
+    } else if (miss || P.px_depth >= kRayTraceDepth) {
+        // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
+        const V3 r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        if (P.px_first) { P.px_ax = r.x; P.px_ay = r.y; P.px_az = r.z; P.px_first = false; }
+        else { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
+        ++P.px_sample;
+        if constexpr (REUSE) {
+            // a primary ray that leaves the scene: every sample of the pixel is the background colour, added one by one
+            if (miss && P.px_depth == 1u && !a.path.slice_cost)
+                for (; P.px_sample < a.path.spp; ++P.px_sample) { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
+        }
+        if (a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
+            atomicAdd(a.path.slice_cost + P.px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - P.px_t0) >> 4);
+        if (P.px_sample >= a.path.spp) {
+            a.path.accum[P.px_local] = make_float4(P.px_ax, P.px_ay, P.px_az, 0.0f);
+            rng_store(a.path.states + P.px_tid, P.px_rng);
+            P.have_pixel = false;
+        } else st.want_primary = true;
+    } else {
+        const uint32_t inst = binst;
+        const HitGroup hg = a.path.hitgroups[inst];
+        const uint32_t program = a.path.inst_program[inst];
+        V3 hp, nd;
+        scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
+        px_chain[P.px_depth - 1u] = inst;
+        ++P.px_depth;
+        st.ro = hp; st.rd = nd; st.launch = true;
+    }
+    return st;
+}
+
+// Lanes without a pixel (`free_lane`) take the next ones of the wave's slice [wbeg, wend) of the tile's n_pixels, in lane order, and
+// initialise them; a lane that took one wants a primary ray (st.want_primary).  Returns `exhausted` (wave-uniform): the tile is used up
+// (in and out by value on purpose: as a `bool &` it moved k_fused's sphere instantiations' loops by an instruction).
+__device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
+                                          bool exhausted, uint32_t home_shard, uint32_t tx) {
+    const uint64_t need = __ballot(free_lane);
+    if (need != 0ull && !exhausted) {
+        if (wbeg >= wend) {
+            // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
+            // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
+            wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_pixels, tx,
+                            [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
+            if (wbeg >= wend) exhausted = true;
+        }
+        if (!exhausted) {
+            const uint32_t n_need = (uint32_t)__popcll(need);
+            const uint32_t take = n_need < wend - wbeg ? n_need : wend - wbeg;
+            const uint32_t rank = lane_prefix(need);
+            const uint32_t mine = wbeg + rank;
+            wbeg += take;
+            if (free_lane && rank < take) {
+                const uint32_t j = a.path.first_pixel + mine;
+                P.px_local = j;
+                P.have_pixel = true; st.want_primary = true;
+                if (!a.path.trace_rays) {
+                    const uint32_t row = j / a.path.width;
+                    const uint32_t ix = j - row * a.path.width;
+                    const uint32_t iy = a.path.rows[row];
+                    P.px_tid = iy * a.path.width + ix;
+                    P.px_sample = 0u; P.px_rng = rng_load(a.path.states + P.px_tid);
+                    P.px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
+                    if (!P.px_first) { const float4 acc = a.path.accum[P.px_local]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; }
+                    if (a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
+                    const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
+                    P.px_pdx = pd.x; P.px_pdy = pd.y; P.px_pdz = pd.z;
+                }
+            }
+        }
+    }
+    return exhausted;
+}
+
+// The primary ray of a lane that wants one: the caller's ray (hrt_trace_rays) or the camera ray of the lane's pixel; sets the depth.
+// RECOMPUTE_DIRECTION: make the pixel's direction again instead of keeping px_pd* alive across the traversal (a kernel at its
+// register limit: k_traverse<.., HAS_SPHERES, FUSED>).
+struct PathRay { V3 o, d; };
+template <bool RECOMPUTE_DIRECTION>
+__device__ __forceinline__ PathRay path_primary(PathLane &P, const TraverseArgs &a) {
+    PathRay r;
+    if (a.path.trace_rays) {
+        const RayRec q = a.path.trace_rays[P.px_local];
+        P.px_depth = a.path.trace_any ? kRayTraceDepth : 1u;      // any-hit queries take the depth-limit ray's early exit
+        r.o = mk3(q.o.x, q.o.y, q.o.z); r.d = mk3(q.d.x, q.d.y, q.d.z);
+    } else {
+        P.px_depth = 1u;
+        r.o = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); r.d = mk3(P.px_pdx, P.px_pdy, P.px_pdz);
+        if (RECOMPUTE_DIRECTION) {
+            const uint32_t iy = P.px_tid / a.path.width, ix = P.px_tid - iy * a.path.width;
+            r.d = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
+        }
+    }
+    return r;
+}
+
+// the lane launches a ray: counted; returns whether any hit will do -- a hit at the depth limit is black whatever it is (Shader.cu:102-107)
+__device__ __forceinline__ bool path_count_ray(PathLane &P) {
+    const bool any = P.px_depth >= kRayTraceDepth;
+    if (any) ++P.px_rays_any; else ++P.px_rays_closest;
+    return any;
+}
+
+// end of the kernel: the wave's ray counts, one atomic pair per wave
+__device__ __forceinline__ void path_report_rays(PathLane &P, const TraverseArgs &a, uint32_t tx) {
+    for (int off = 32; off > 0; off >>= 1) {
+        P.px_rays_closest += (uint32_t)__shfl_down((int)P.px_rays_closest, off);
+        P.px_rays_any += (uint32_t)__shfl_down((int)P.px_rays_any, off);
+    }
+    if (tx == 0u) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_closest), (unsigned long long)P.px_rays_closest);
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.path.rays_any), (unsigned long long)P.px_rays_any);
+    }
+}
+
+}  // namespace hrt

@@ -1,7 +1,9 @@
 // trav_common.h -- device code shared by the kernels of kernels.hip (wavefront pipeline, counting build, round-1 fused
 // kernel), fused.hip and fused_queue.hip (the production path kernel and its queue form): vector helpers, XORWOW, the shading arithmetic of shader/Shader.cu,
-// the canonical primitive test and the load / wait primitives of the traversal step.  One definition each, hence one
-// rounding behaviour everywhere.  Device-only: include from .hip files compiled with -ffp-contract=off.
+// the wave's slice fetch, the ray queues' feed (queue_*), the start of a ray in a TravState (trav_start), the canonical primitive
+// test, the node step (node_slab_test), the load / wait primitives of the traversal step and the instrumented build's LaneStats.
+// One definition each, hence one rounding behaviour everywhere.  Device-only: include from .hip files compiled with -ffp-contract=off.
+// (The regeneration phase of the two path kernels: path_lane.h; the loop of k_fused / k_trace_queue: trav_loop.h over trav_lean.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +41,20 @@ __device__ __forceinline__ void wave_next_slice(uint32_t &wbeg, uint32_t &wend, 
             wend = (uint32_t)(beg + fetch_chunk < (uint64_t)n ? beg + fetch_chunk : (uint64_t)n);
         } else kstart = k + 1;
     }
+}
+
+// Ray queues (k_trace_queue, k_traverse's queue form): up to two segments per launch (e.g. the depth-4 rays of sample s and the primary
+// rays of sample s + 1), their lengths read from device memory so that a render is a fixed sequence of launches.  Position q of the
+// concatenated queue is ray q of segment 0 while q < n_a, else ray q - n_a of segment 1.
+//   n_a = queue_length(a.seg[0]), n_b = a.seg[1].rays ? queue_length(a.seg[1]) : 0
+__device__ __forceinline__ uint32_t queue_length(const TraverseSeg &g) { return g.n_ptr ? (g.n_ptr[0] + g.n_ptr[1] + g.n_ptr[2] + g.n_ptr[3]) : g.n; }
+struct QueuePos { bool in_b; uint32_t k; };        // segment 1? / index within the segment
+__device__ __forceinline__ QueuePos queue_pos(uint32_t q, uint32_t n_a) { QueuePos p; p.in_b = q >= n_a; p.k = p.in_b ? q - n_a : q; return p; }
+__device__ __forceinline__ RayRec queue_ray(const TraverseArgs &a, QueuePos p) { return p.in_b ? a.seg[1].rays[p.k] : a.seg[0].rays[p.k]; }
+__device__ __forceinline__ bool queue_any_hit(const TraverseArgs &a, QueuePos p) { return (p.in_b ? a.seg[1].any_hit : a.seg[0].any_hit) != 0u; }
+__device__ __forceinline__ void queue_write_hit(const TraverseArgs &a, QueuePos p, float t, float u, float v, uint32_t prim, uint32_t inst) {
+    (p.in_b ? a.seg[1].hit_tuvp : a.seg[0].hit_tuvp)[p.k] = make_float4(t, u, v, __uint_as_float(prim));
+    (p.in_b ? a.seg[1].hit_inst : a.seg[0].hit_inst)[p.k] = inst;
 }
 
 struct V3 { float x, y, z; };
@@ -244,6 +260,17 @@ __device__ __forceinline__ float safe_rcp_dir(float d) {
     return EXACT ? 1.0f / dd : __builtin_amdgcn_rcpf(dd);
 }
 
+// a new ray in `s`: origin, direction, guarded reciprocals, octant word, empty best hit.  (What the ray's first node is and how the
+// stacks are emptied is the kernels': lean_start, k_traverse's start_ray.)
+template <bool EXACT>
+__device__ __forceinline__ void trav_start(TravState &s, V3 o, V3 d, float tmax_ray) {
+    s.ox = o.x; s.oy = o.y; s.oz = o.z; s.dx = d.x; s.dy = d.y; s.dz = d.z;
+    s.idx = safe_rcp_dir<EXACT>(s.dx); s.idy = safe_rcp_dir<EXACT>(s.dy); s.idz = safe_rcp_dir<EXACT>(s.dz);
+    const uint32_t oct = (s.dx < 0.0f ? 4u : 0u) | (s.dy < 0.0f ? 2u : 0u) | (s.dz < 0.0f ? 1u : 0u);
+    s.oct_inv4 = (7u - oct) * 0x01010101u;
+    s.bt = tmax_ray; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
+}
+
 // canonical primitive test (DESIGN.md "canonical intersector"); updates the best hit.
 // INSTANCED (two-level trees, fused.hip): the record is a shared BLAS's, in object space, and so is the ray in `s` by now (the transform
 // node did that for triangles and spheres alike); the record does not know who instances it: `inst_cur` does.
@@ -356,5 +383,78 @@ __device__ __forceinline__ void wait_prim_loads(f32x4 &a, f32x4 &b, f32x4 &c) {
 __device__ __forceinline__ void wait_node_loads(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, u32x4 &e) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) :: "memory");
 }
+
+// the node step: slab test of the eight quantised children of the node in rn0..rn4 against the ray in `s`; returns the children's
+// sibling group (first child, hit bits 31..24 | inner mask; y <= 0xffffff: none) and leaf group (first primitive, bit per primitive that
+// may be hit; y == 0: none)
+__device__ __forceinline__ void node_slab_test(const TravState &s, float tmin, const u32x4 rn0, const u32x4 rn1, const u32x4 rn2, const u32x4 rn3,
+                                          const u32x4 rn4, uint2 &child, uint2 &tri) {
+    const float px = __uint_as_float(rn0.x), py = __uint_as_float(rn0.y), pz = __uint_as_float(rn0.z);
+    const uint32_t e_imask = rn0.w;
+    const float aix = __uint_as_float((e_imask & 0xffu) << 23) * s.idx;
+    const float aiy = __uint_as_float(((e_imask >> 8) & 0xffu) << 23) * s.idy;
+    const float aiz = __uint_as_float(((e_imask >> 16) & 0xffu) << 23) * s.idz;
+    const float aox = (px - s.ox) * s.idx, aoy = (py - s.oy) * s.idy, aoz = (pz - s.oz) * s.idz;
+    const bool nx = s.dx < 0.0f, ny = s.dy < 0.0f, nz = s.dz < 0.0f;
+    uint32_t hitmask = 0u;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t meta4 = h ? rn1.w : rn1.z;
+        const uint32_t is_inner4 = (meta4 & (meta4 << 1)) & 0x10101010u;
+        const uint32_t inner_mask4 = (is_inner4 >> 4) * 0xffu;
+        const uint32_t bit_index4 = (meta4 ^ (s.oct_inv4 & inner_mask4)) & 0x1f1f1f1fu;
+        const uint32_t child_bits4 = (meta4 >> 5) & 0x07070707u;
+        const uint32_t qlox = h ? rn2.y : rn2.x, qloy = h ? rn2.w : rn2.z, qloz = h ? rn3.y : rn3.x;
+        const uint32_t qhix = h ? rn3.w : rn3.z, qhiy = h ? rn4.y : rn4.x, qhiz = h ? rn4.w : rn4.z;
+        const uint32_t xn = nx ? qhix : qlox, xf = nx ? qlox : qhix;
+        const uint32_t yn = ny ? qhiy : qloy, yf = ny ? qloy : qhiy;
+        const uint32_t zn = nz ? qhiz : qloz, zf = nz ? qloz : qhiz;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float tnx = fmaf(HRT_BYTE_F(xn, j), aix, aox), tfx = fmaf(HRT_BYTE_F(xf, j), aix, aox);
+            const float tny = fmaf(HRT_BYTE_F(yn, j), aiy, aoy), tfy = fmaf(HRT_BYTE_F(yf, j), aiy, aoy);
+            const float tnz = fmaf(HRT_BYTE_F(zn, j), aiz, aoz), tfz = fmaf(HRT_BYTE_F(zf, j), aiz, aoz);
+            const float tlo = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+            const float thi = fminf(fminf(tfx, tfy), fminf(tfz, s.bt));
+            const uint32_t cb = (child_bits4 >> (8 * j)) & 0xffu;
+            const uint32_t bi = (bit_index4 >> (8 * j)) & 0xffu;
+            // conservative: the builder pads and rounds the child boxes outwards
+            if (tlo <= thi) hitmask |= cb << bi;
+        }
+    }
+    child = make_uint2(rn1.x, (hitmask & 0xff000000u) | (e_imask >> 24));
+    tri = make_uint2(rn1.y, hitmask & 0x00ffffffu);
+}
+
+// Lane-utilisation counters of the instrumented build (`make stats`, tools/lane_stats.py); empty otherwise.
+struct LaneStats {
+#ifdef HRT_LANE_STATS
+    unsigned long long iter = 0, alive = 0, node = 0, prim = 0, ppass = 0, regen = 0, enter = 0;
+#endif
+    __device__ __forceinline__ void regeneration() {
+#ifdef HRT_LANE_STATS
+        ++regen;
+#endif
+    }
+    __device__ __forceinline__ void iteration([[maybe_unused]] bool lane_alive, [[maybe_unused]] uint64_t mask_n, [[maybe_unused]] uint64_t mask_p) {
+#ifdef HRT_LANE_STATS
+        ++iter; alive += __popcll(__ballot(lane_alive)); node += __popcll(mask_n); prim += __popcll(mask_p); ppass += mask_p != 0ull;
+#endif
+    }
+    __device__ __forceinline__ void entered([[maybe_unused]] bool lane_enters) {
+#ifdef HRT_LANE_STATS
+        enter += __popcll(__ballot(lane_enters));
+#endif
+    }
+    // end of a path kernel: lane 0 adds the wave's counters to the slots tools/lane_stats.py reads, behind the ray counters
+    __device__ __forceinline__ void report([[maybe_unused]] uint64_t *rays_closest, [[maybe_unused]] uint32_t tx) {
+#ifdef HRT_LANE_STATS
+        if (tx == 0u) {
+            unsigned long long *d = reinterpret_cast<unsigned long long *>(rays_closest);
+            atomicAdd(d + 6, iter); atomicAdd(d + 7, alive); atomicAdd(d + 8, node); atomicAdd(d + 9, prim); atomicAdd(d + 2, ppass); atomicAdd(d + 3, regen); atomicAdd(d + 4, enter);
+        }
+#endif
+    }
+};
 
 }  // namespace hrt

@@ -12,7 +12,7 @@
 //     node stack holds one group per tree level and trees deeper than that take round 1's kernel (hrt_api.cpp);
 //   * the bookkeeping after the node step as one hand-written instruction sequence;
 //   * "no work" encoded in the work index itself (nidx / pidx = kNoWork) instead of separate bools;
-//   * the straight-line primitive test of trav_common.h;
+//   * the straight-line primitive test and the node step (node_slab_test) of trav_common.h, the same as k_traverse's;
 //   * lazy pushes: the sibling group in hand goes to the stack only when a child group arrives while siblings remain.
 #pragma once
 #include "trav_common.h"
@@ -45,55 +45,9 @@ __device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray) {
 
 // a new ray: the root is its first node
 __device__ __forceinline__ void lean_start(LeanLane &L, V3 o, V3 d, float tmax_ray) {
-    TravState &s = L.s;
-    s.ox = o.x; s.oy = o.y; s.oz = o.z; s.dx = d.x; s.dy = d.y; s.dz = d.z;
-    s.idx = safe_rcp_dir<false>(s.dx); s.idy = safe_rcp_dir<false>(s.dy); s.idz = safe_rcp_dir<false>(s.dz);
-    const uint32_t oct = (s.dx < 0.0f ? 4u : 0u) | (s.dy < 0.0f ? 2u : 0u) | (s.dz < 0.0f ? 1u : 0u);
-    s.oct_inv4 = (7u - oct) * 0x01010101u;
-    s.bt = tmax_ray; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
+    trav_start<false>(L.s, o, d, tmax_ray);
     lean_reset(L);
     L.nidx = 0u;
-}
-
-// the node step: slab test of the eight children (identical arithmetic to k_traverse); returns the children's sibling group and
-// leaf group (y == 0 / <= 0xffffff: none)
-__device__ __forceinline__ void lean_node(const TravState &s, float tmin, const u32x4 rn0, const u32x4 rn1, const u32x4 rn2, const u32x4 rn3,
-                                          const u32x4 rn4, uint2 &child, uint2 &tri) {
-    const float px = __uint_as_float(rn0.x), py = __uint_as_float(rn0.y), pz = __uint_as_float(rn0.z);
-    const uint32_t e_imask = rn0.w;
-    const float aix = __uint_as_float((e_imask & 0xffu) << 23) * s.idx;
-    const float aiy = __uint_as_float(((e_imask >> 8) & 0xffu) << 23) * s.idy;
-    const float aiz = __uint_as_float(((e_imask >> 16) & 0xffu) << 23) * s.idz;
-    const float aox = (px - s.ox) * s.idx, aoy = (py - s.oy) * s.idy, aoz = (pz - s.oz) * s.idz;
-    const bool nx = s.dx < 0.0f, ny = s.dy < 0.0f, nz = s.dz < 0.0f;
-    uint32_t hitmask = 0u;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const uint32_t meta4 = h ? rn1.w : rn1.z;
-        const uint32_t is_inner4 = (meta4 & (meta4 << 1)) & 0x10101010u;
-        const uint32_t inner_mask4 = (is_inner4 >> 4) * 0xffu;
-        const uint32_t bit_index4 = (meta4 ^ (s.oct_inv4 & inner_mask4)) & 0x1f1f1f1fu;
-        const uint32_t child_bits4 = (meta4 >> 5) & 0x07070707u;
-        const uint32_t qlox = h ? rn2.y : rn2.x, qloy = h ? rn2.w : rn2.z, qloz = h ? rn3.y : rn3.x;
-        const uint32_t qhix = h ? rn3.w : rn3.z, qhiy = h ? rn4.y : rn4.x, qhiz = h ? rn4.w : rn4.z;
-        const uint32_t xn = nx ? qhix : qlox, xf = nx ? qlox : qhix;
-        const uint32_t yn = ny ? qhiy : qloy, yf = ny ? qloy : qhiy;
-        const uint32_t zn = nz ? qhiz : qloz, zf = nz ? qloz : qhiz;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float tnx = fmaf(HRT_BYTE_F(xn, j), aix, aox), tfx = fmaf(HRT_BYTE_F(xf, j), aix, aox);
-            const float tny = fmaf(HRT_BYTE_F(yn, j), aiy, aoy), tfy = fmaf(HRT_BYTE_F(yf, j), aiy, aoy);
-            const float tnz = fmaf(HRT_BYTE_F(zn, j), aiz, aoz), tfz = fmaf(HRT_BYTE_F(zf, j), aiz, aoz);
-            const float tlo = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-            const float thi = fminf(fminf(tfx, tfy), fminf(tfz, s.bt));
-            const uint32_t cb = (child_bits4 >> (8 * j)) & 0xffu;
-            const uint32_t bi = (bit_index4 >> (8 * j)) & 0xffu;
-            // conservative: the builder pads and rounds the child boxes outwards
-            if (tlo <= thi) hitmask |= cb << bi;
-        }
-    }
-    child = make_uint2(rn1.x, (hitmask & 0xff000000u) | (e_imask >> 24));
-    tri = make_uint2(rn1.y, hitmask & 0x00ffffffu);
 }
 
 // the next node of a lane that has just been handed a sibling group (tail splitting): its nearest child -- step (7) of

@@ -4,6 +4,7 @@
 // plus what only the loop knows: the issue priority of each phase, the any-hit shortcut, the exit rules, and the tail-splitting
 // protocol (tail_donate / tail_publish / tail_adopt / tail_retire below), which can be read on its own.
 // Everything here is inlined into the two kernels; their LDS arrays stay declared there and are named through Mailboxes.
+// (LaneStats, the instrumented build's counters, is trav_common.h's: k_traverse counts with it too.)
 #pragma once
 #include "trav_lean.h"
 
@@ -38,28 +39,6 @@ struct LaneFlags {
 struct Mailboxes {
     float *t, *u, *v;
     uint32_t *prim, *inst, *pending, *pair;
-};
-
-// Lane-utilisation counters of the instrumented build (`make stats`, tools/lane_stats.py); empty otherwise.
-struct LaneStats {
-#ifdef HRT_LANE_STATS
-    unsigned long long iter = 0, alive = 0, node = 0, prim = 0, ppass = 0, regen = 0, enter = 0;
-#endif
-    __device__ __forceinline__ void regeneration() {
-#ifdef HRT_LANE_STATS
-        ++regen;
-#endif
-    }
-    __device__ __forceinline__ void iteration([[maybe_unused]] bool lane_alive, [[maybe_unused]] uint64_t mask_n, [[maybe_unused]] uint64_t mask_p) {
-#ifdef HRT_LANE_STATS
-        ++iter; alive += __popcll(__ballot(lane_alive)); node += __popcll(mask_n); prim += __popcll(mask_p); ppass += mask_p != 0ull;
-#endif
-    }
-    __device__ __forceinline__ void entered([[maybe_unused]] bool lane_enters) {
-#ifdef HRT_LANE_STATS
-        enter += __popcll(__ballot(lane_enters));
-#endif
-    }
 };
 
 // One-level trees: the lane is never inside an instance.  (The two-level kernel's counterpart, with the transform-node steps, is
@@ -224,10 +203,10 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         wait_node_loads(rn0, rn1, rn2, rn3, rn4);
         [[maybe_unused]] bool enter = false;
         if constexpr (!INSTANCED) {
-            lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            node_slab_test(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
         } else {
             enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
-            if (L.nidx != kNoWork && !hit_any && !enter) lean_node(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
             enter = I.enter_instance(enter, L.s, child, rn0, rn1, rn2, rn3, rn4, mb, tx);
             stats.entered(enter);
         }
