@@ -62,7 +62,9 @@ typedef struct HrtContext HrtContext;
                                     primitives, at least 4 per unique one; HRT_TWO_LEVEL=1 / -1: always / never).  Hits of such a tree are pinned to the
                                     oracle's INSTANCED mode (object-space triangle test), those of a flattened tree to its FLATTENED mode: the two
                                     differ in rounding, not in geometry.  Trees too deep for the path kernel's stack, and contexts that count
-                                    (HRT_CTX_COUNT) or run another execution mode (HRT_FUSED != 1), flatten. */
+                                    (HRT_CTX_COUNT) or run another execution mode (HRT_FUSED != 1), flatten.  Together with HRT_CTX_FAST_TRACE the
+                                    shared BLAS trees are built with spatial splits (see there).  The flag asks for two levels whatever the
+                                    environment says: it wins over HRT_TWO_LEVEL=-1. */
 #define HRT_CTX_REUSE_PRIMARY 0x20u /* hrt_render_launch with spp > 1: the reference's raygen has no pixel jitter (shader/Shader.cu:249-261), so a pixel's
                                     primary ray hits the same thing in every sample.  With this flag (or HRT_REUSE_PRIMARY=1) the path kernel traverses it for
                                     the first sample a launch takes of the pixel and shades the later samples from that hit record: the same image bit
@@ -78,7 +80,21 @@ typedef struct HrtContext HrtContext;
                                     HRT_FAST_TRACE_BUILD=host -- by the host's binned-SAH builder from a host copy of the geometry (the same
                                     rules, ~1.3 s).  Such a tree is for static scenes: the first hrt_tlas_update replaces it by a
                                     default-built one (a refit cannot keep the split references' boxes), and rebuilds inside hrt_tlas_update
-                                    are always default builds (the reference's IAS flags: ALLOW_UPDATE | PREFER_FAST_BUILD, RendererImpl.cu:180). */
+                                    are always default builds (the reference's IAS flags: ALLOW_UPDATE | PREFER_FAST_BUILD, RendererImpl.cu:180).
+                                    A split build whose tree comes out deeper than any kernel's stack (a geometric chain of primitives) is built
+                                    again by position, without splits, like the default build; it used to fail with HRT_ERR_INVALID.
+                                    TOGETHER WITH HRT_CTX_TWO_LEVEL (or HRT_TWO_LEVEL=1: two levels asked for, not chosen by size) -- the
+                                    reference's own pairing, fast-trace GASes under an IAS it updates every frame -- hrt_tlas_build makes a
+                                    two-level tree whose BLAS trees carry the splits: every BLAS of more than 4096 primitives gets a second
+                                    object-space tree with spatial splits, built once on the device and shared by every TLAS that instances
+                                    it (records and a 24-byte clip box each on top of the unsplit template's memory).  Geometry does not move
+                                    relative to the boxes of its own object space, so such a tree is REFITTED by hrt_tlas_update like any
+                                    two-level tree (the top level only) and keeps its splits for ever; a rebuild inside an update copies the
+                                    cached split trees in again.  Smaller BLASes, a split phase that gives up and a split build that does not
+                                    fit in memory leave that BLAS the unsplit tree, byte for byte as under HRT_CTX_TWO_LEVEL alone.  Where no
+                                    two-level tree can be had -- HRT_CTX_COUNT, HRT_FUSED != 1, HRT_FAST_TRACE_BUILD=host, top + 1 + deepest
+                                    BLAS levels beyond the path kernel's stack (split trees are deeper) -- the flattened split tree above is
+                                    built, as with HRT_CTX_FAST_TRACE alone. */
 
 /* replaces createContext / destroyContext, src/Global/RendererImpl.cu:6-27 */
 int  hrt_ctx_create(int device_id, uint32_t flags, HrtContext **out_ctx);

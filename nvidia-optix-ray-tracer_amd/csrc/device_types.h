@@ -150,8 +150,8 @@ struct RefitArgs {
     float *area_sum;               // weighted mean of area now / area as built (quality after the refit), may be NULL
     float *rec_box; uint32_t n_records;   // when set (small trees): 6 floats per record, the record's padded box, written by k_refit_records before the levels
                                    // are walked -- the records' arithmetic then runs one thread per record instead of inside the walk up the tree
-    const float *clip;             // when set (the refit that completes a device build with spatial splits): 6 floats per record, the box of the part
-                                   // of the primitive this record stands for, taken instead of the primitive's own
+    const float *clip;             // when set (the refit that completes a device build with spatial splits, flattened or of a two-level tree's BLASes): 6 floats per
+                                   // record, the box of the part of the primitive this record stands for, taken instead of the primitive's own
 };
 constexpr uint32_t kRefitTopLevels = 16, kRefitTopLevelNodes = 128;      // (one pass of the 1024-thread workgroup per level; wider levels are quicker as launches of their own: 95 -> ~45 us for the reference's sample)
 struct RefitLevels { uint32_t n_levels; uint32_t first[kRefitTopLevels], count[kRefitTopLevels]; };   // phases in processing order, each at most kRefitTopLevelNodes wide
@@ -161,6 +161,10 @@ struct PackBlasArgs {
     unsigned char *dst_nodes, *dst_prims; uint32_t node_stride, prim_stride;
     uint32_t node_off, prim_off;   // where the tree lands: index of its root in the TLAS's node array, of its first record
     uint32_t slot;                 // the BLAS's number in the tables of the pack's refit (written to the records' instance field)
+    // a TLAS that holds a BLAS tree with spatial splits: the pack's refit takes every record's box from ONE array over all records (RefitArgs::clip)
+    float *dst_clip;               // 6 floats per record of the TLAS (NULL: no BLAS of this TLAS has split references)
+    const float *src_clip;         // this BLAS's own clip boxes; NULL: it has none, its records get their primitives' own boxes ...
+    const float *src_geom;         // ... from its object-space geometry (9 floats per triangle; spheres are in their records)
 };
 void launch_pack_blas(const PackBlasArgs &a, hipStream_t s);
 void launch_refit_level(const RefitArgs &a, hipStream_t s);

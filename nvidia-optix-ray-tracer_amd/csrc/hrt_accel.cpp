@@ -173,16 +173,25 @@ static BuildPrim build_prim_of(const Blas &b, uint32_t p, const float *m, bool i
     return bp;
 }
 
+// Device memory a BLAS will own, while it is being filled: freed again unless everything arrived and the pointers were handed over -- a BLAS
+// never shows a tree of which only a part is there (several loader threads share the BLASes).
+struct PendingBlocks {
+    void *p[3] = {nullptr, nullptr, nullptr};
+    ~PendingBlocks() { for (void *q : p) if (q) (void)hipFree(q); }
+    template <class T> T *hand_over(int k) { T *q = static_cast<T *>(p[k]); p[k] = nullptr; return q; }
+};
 // Object-space BVH8 of one BLAS (built once): the subtree every instance of it gets in a tree over instances.  Built on the
 // device like everything else (one identity instance); only its topology -- nodes' child / primitive bases, masks, the
 // primitive ids -- comes back to the host, where assemble_instanced_bvh8 stitches instance subtrees under a top tree.
 static int template_to_device(HrtContext *ctx, Blas &b, hipStream_t s) {
     if (b.d_tmpl_nodes || b.tmpl.nodes.empty()) return HRT_OK;
-    HIP_TRY(ctx, hipMalloc((void **)&b.d_tmpl_nodes, sizeof(Bvh8Node) * b.tmpl.nodes.size()));
-    HIP_TRY(ctx, hipMalloc((void **)&b.d_tmpl_prims, sizeof(PrimRecord) * std::max<size_t>(b.tmpl.prims.size(), 1)));
-    HIP_TRY(ctx, hipMemcpyAsync(b.d_tmpl_nodes, b.tmpl.nodes.data(), sizeof(Bvh8Node) * b.tmpl.nodes.size(), hipMemcpyHostToDevice, s));
-    if (!b.tmpl.prims.empty()) HIP_TRY(ctx, hipMemcpyAsync(b.d_tmpl_prims, b.tmpl.prims.data(), sizeof(PrimRecord) * b.tmpl.prims.size(), hipMemcpyHostToDevice, s));
+    PendingBlocks blk;
+    HIP_TRY(ctx, hipMalloc(&blk.p[0], sizeof(Bvh8Node) * b.tmpl.nodes.size()));
+    HIP_TRY(ctx, hipMalloc(&blk.p[1], sizeof(PrimRecord) * std::max<size_t>(b.tmpl.prims.size(), 1)));
+    HIP_TRY(ctx, hipMemcpyAsync(blk.p[0], b.tmpl.nodes.data(), sizeof(Bvh8Node) * b.tmpl.nodes.size(), hipMemcpyHostToDevice, s));
+    if (!b.tmpl.prims.empty()) HIP_TRY(ctx, hipMemcpyAsync(blk.p[1], b.tmpl.prims.data(), sizeof(PrimRecord) * b.tmpl.prims.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
+    b.d_tmpl_prims = blk.hand_over<unsigned char>(1); b.d_tmpl_nodes = blk.hand_over<unsigned char>(0);
     return HRT_OK;
 }
 // keep_device: the topology also stays on the device (Blas::d_tmpl_*), for two-level TLASes to copy from
@@ -240,6 +249,73 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
     if (b.kind == kPrimKindTriangle) b.tmpl.n_triangles = r.n_prims; else b.tmpl.n_spheres = r.n_prims;
     b.tmpl_built = true;
     return keep_device ? template_to_device(ctx, b, s) : HRT_OK;
+}
+
+static bool split_build_fits(HrtContext *ctx, uint32_t n_prims);
+static float refit_pad(float scene_scale);
+
+// The split tree of a BLAS (Blas::split): the same build over one identity instance, with the top-down phase and the context's budget of
+// extra references -- as build_merged_on_device(.., device_split = true) builds the flattened scene.  Its record count is known afterwards:
+// nodes, records and clip boxes are staged in the arena and copied into blocks of their own, which the BLAS gets once all of it is there.
+// Leaves b.split empty (and the unsplit template in charge, byte for byte as without HRT_CTX_FAST_TRACE) where the split phase does not run:
+// 4096 primitives or fewer (build.hip), a phase that gave up, a tree no kernel could walk; and where its working memory is not to be had.
+static int ensure_split_template(HrtContext *ctx, Blas &b, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(b.tmpl_mu);
+    if (b.split_decided) return HRT_OK;
+    const uint32_t n = b.n_prims;
+    if (n <= 4096u) { b.split_decided = true; return HRT_OK; }
+    if (!split_build_fits(ctx, n)) return HRT_OK;      // (not for ever: a later TLAS may find the memory)
+    float scale = 1.0f;
+    for (int a = 0; a < 3; ++a) { if (std::isfinite(b.lo[a])) scale = std::max(scale, std::fabs(b.lo[a])); if (std::isfinite(b.hi[a])) scale = std::max(scale, std::fabs(b.hi[a])); }
+    const uint32_t h_first[2] = {0u, n}, h_kind = b.kind, h_ident = 1u;
+    const float h_xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const void *h_src = b.d_verts;
+    GpuBuildInput in = build_input(ctx, kMaxLeafPrims, ctx->build_c_prim_bodies, false, true, ctx->split_budget, refit_pad(scale));
+    in.n_prims = n; in.n_inst = 1;
+    const size_t max_leaves = gpu_build_max_refs(n, &in.split);
+    ArenaLayout lay;
+    const size_t o_first = lay.take(sizeof h_first), o_kind = lay.take(sizeof h_kind), o_src = lay.take(sizeof h_src), o_xf = lay.take(sizeof h_xf), o_ident = lay.take(sizeof h_ident);
+    const size_t o_nodes = lay.take(sizeof(Bvh8Node) * max_leaves), o_ref = lay.take(sizeof(float) * 2 * max_leaves);
+    const size_t o_prims = lay.take(sizeof(PrimRecord) * max_leaves), o_clip = lay.take(sizeof(float) * 6 * max_leaves);
+    const ScratchArena arena = scratch_acquire(ctx, lay.used + gpu_build_scratch_bytes(n, &in.split));
+    if (!arena.p) return HRT_OK;                        // (as above)
+    ArenaRelease release{ctx, arena, s};
+    lay.base = static_cast<unsigned char *>(arena.p);
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
+    in.d_inst_first = lay.at<const uint32_t>(o_first); in.d_inst_kind = lay.at<const uint32_t>(o_kind);
+    in.d_inst_src = lay.at<const void *const>(o_src); in.d_inst_xf = lay.at<const float>(o_xf);
+    in.d_inst_identity = lay.at<const uint32_t>(o_ident);
+    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = sizeof(Bvh8Node); in.out_prims = lay.at<unsigned char>(o_prims); in.prim_stride = sizeof(PrimRecord);
+    in.out_node_ref = lay.at<float>(o_ref); in.out_clip = lay.at<float>(o_clip);
+    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
+    const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
+    if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build of a BLAS's split tree failed: %s (%s)", hipGetErrorString(r.error), r.where);
+    if (ctx->build_verbose)
+        std::fprintf(stderr, "[hrt] split tree of a BLAS: %u primitives -> %u records, %u nodes, depth %u, %u split levels, %u cells%s\n",
+                     r.n_prims, r.n_records, r.n_nodes, r.max_depth, r.split_levels, r.n_cells, r.split_levels ? "" : " (not used: the unsplit template serves)");
+    if (r.n_prims == 0u || r.split_levels == 0u || too_deep(r.max_depth)) { b.split_decided = true; return HRT_OK; }
+    PendingBlocks blk;
+    const size_t nb = sizeof(Bvh8Node) * (size_t)r.n_nodes, pb = sizeof(PrimRecord) * (size_t)r.n_records, cb = sizeof(float) * 6 * (size_t)r.n_records;
+    {   // no room for the tree to stay: like working memory that is not to be had -- the unsplit template serves, and a later TLAS may try again
+        const size_t bytes[3] = {nb, pb, cb};
+        for (int k = 0; k < 3; ++k) {
+            const hipError_t e = hipMalloc(&blk.p[k], bytes[k]);
+            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); blk.p[k] = nullptr; return HRT_OK; }
+            HIP_TRY(ctx, e);
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(blk.p[0], in.out_nodes, nb, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(blk.p[1], in.out_prims, pb, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(blk.p[2], in.out_clip, cb, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    Blas::SplitTree &t = b.split;
+    t.n_nodes = r.n_nodes; t.n_records = r.n_records; t.max_depth = r.max_depth; t.level_begin = r.level_begin;
+    t.n_triangles = b.kind == kPrimKindTriangle ? r.n_prims : 0u; t.n_spheres = b.kind == kPrimKindTriangle ? 0u : r.n_prims;
+    t.d_clip = blk.hand_over<float>(2); t.d_prims = blk.hand_over<unsigned char>(1); t.d_nodes = blk.hand_over<unsigned char>(0);
+    b.split_decided = true;
+    return HRT_OK;
 }
 
 // Build a TLAS and upload it together with the tables the device refit needs (hrt_tlas_update).  What is built (TreeKind):
@@ -454,7 +530,8 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
     // A tree deeper than any kernel's stack (a chain of primitives over many orders of magnitude: nearest-neighbour clustering, like SAH, takes
     // one off the rest at every level): built again by position -- every cluster with its Morton neighbour, log2(n) levels, whatever the areas
-    if (r.error == hipSuccess && r.n_prims != 0u && too_deep(r.max_depth) && !device_split) {
+    // (a split build too: the tree by position has no splits, its records are the primitives -- the staged buffers hold them all the same)
+    if (r.error == hipSuccess && r.n_prims != 0u && too_deep(r.max_depth)) {
         if (ctx->build_verbose) std::fprintf(stderr, "[hrt] the tree is %u levels deep: built again by position\n", r.max_depth);
         in.balanced = true; in.split.enabled = false;
         r = gpu_build_bvh8(in, s);
@@ -542,16 +619,44 @@ static int upload_blas_bounds(HrtContext *ctx, Tlas &t, std::vector<const void *
     return HRT_OK;
 }
 
+// The object-space tree a two-level TLAS copies in for one of its BLASes: the template (Blas::tmpl / d_tmpl_*), or under HRT_CTX_FAST_TRACE
+// the tree with spatial splits (Blas::split) where the BLAS has one.  (Both are written once, under Blas::tmpl_mu, and never change.)
+struct PackedTree {
+    const unsigned char *d_nodes = nullptr, *d_prims = nullptr; const float *d_clip = nullptr;
+    uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
+    const std::vector<uint32_t> *level_begin = nullptr;
+};
+static int packed_tree_of(HrtContext *ctx, Blas &b, bool fast_trace, hipStream_t s, PackedTree &out) {
+    if (fast_trace) {
+        const int rc = ensure_split_template(ctx, b, s);
+        if (rc != HRT_OK) return rc;
+        bool have;
+        { std::lock_guard<std::mutex> lk(b.tmpl_mu); have = b.split.d_nodes != nullptr; }
+        if (have) {
+            const Blas::SplitTree &t = b.split;
+            out.d_nodes = t.d_nodes; out.d_prims = t.d_prims; out.d_clip = t.d_clip; out.n_nodes = t.n_nodes; out.n_records = t.n_records;
+            out.n_triangles = t.n_triangles; out.n_spheres = t.n_spheres; out.max_depth = t.max_depth; out.level_begin = &t.level_begin;
+            return HRT_OK;
+        }
+    }
+    const int rc = ensure_template(ctx, b, s, true);
+    if (rc != HRT_OK) return rc;
+    const Bvh8 &tp = b.tmpl;
+    out.d_nodes = b.d_tmpl_nodes; out.d_prims = b.d_tmpl_prims; out.n_nodes = (uint32_t)tp.nodes.size(); out.n_records = (uint32_t)tp.prims.size();
+    out.n_triangles = tp.n_triangles; out.n_spheres = tp.n_spheres; out.max_depth = tp.max_depth; out.level_begin = &tp.level_begin;
+    return HRT_OK;
+}
+
 // The refit of the packed BLAS trees, all BLASes at once: phase k = the k-th level from the bottom of every tree (a template is stored breadth
 // first, children one level below their parents), walked through an order array of node indices.
-static void pack_refit_order(const std::vector<Blas *> &uniq, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
+static void pack_refit_order(const std::vector<PackedTree> &trees, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
                              std::vector<uint32_t> &order, std::vector<std::pair<uint32_t, uint32_t>> &pack_phases) {
-    const uint32_t nu = (uint32_t)uniq.size();
+    const uint32_t nu = (uint32_t)trees.size();
     order.reserve(node_off[nu]);
     for (uint32_t k = 0; k <= blas_depth; ++k) {
         const uint32_t begin = (uint32_t)order.size();
         for (uint32_t j = 0; j < nu; ++j) {
-            const std::vector<uint32_t> &lb = uniq[j]->tmpl.level_begin;
+            const std::vector<uint32_t> &lb = *trees[j].level_begin;
             const uint32_t levels = lb.empty() ? 0u : (uint32_t)lb.size() - 1u;
             if (k >= levels) continue;
             const uint32_t l = levels - 1u - k;
@@ -578,7 +683,7 @@ static float object_space_reach(const Tlas &t, const std::vector<Blas *> &uniq, 
     return std::max(reach, obj_coord);
 }
 
-static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const BuildPlan &plan, float scene_scale, hipStream_t s) {
+static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const BuildPlan &plan, bool fast_trace, float scene_scale, hipStream_t s) {
     const uint32_t n = t.n_instances;
     const std::vector<Blas *> &uniq = plan.uniq;
     const uint32_t nu = (uint32_t)uniq.size();
@@ -590,14 +695,16 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
         if (rc != HRT_OK) return rc;
     }
     std::vector<uint32_t> node_off(nu + 1, 0u), prim_off(nu + 1, 0u);
-    uint32_t blas_depth = 0;
+    std::vector<PackedTree> trees(nu);
+    uint32_t blas_depth = 0, n_split = 0;
     for (uint32_t j = 0; j < nu; ++j) {
-        const int rc = ensure_template(ctx, *uniq[j], s, true);
+        const int rc = packed_tree_of(ctx, *uniq[j], fast_trace, s, trees[j]);
         if (rc != HRT_OK) return rc;
-        const Bvh8 &tp = uniq[j]->tmpl;
-        if ((uint64_t)node_off[j] + tp.nodes.size() > 0x7fffffffull || (uint64_t)prim_off[j] + tp.prims.size() > 0x7fffffffull) return fail(ctx, HRT_ERR_INVALID, "two-level tree: more than 2^31 nodes or records");
-        node_off[j + 1] = node_off[j] + (uint32_t)tp.nodes.size(); prim_off[j + 1] = prim_off[j] + (uint32_t)tp.prims.size();
+        const PackedTree &tp = trees[j];
+        if ((uint64_t)node_off[j] + tp.n_nodes > 0x7fffffffull || (uint64_t)prim_off[j] + tp.n_records > 0x7fffffffull) return fail(ctx, HRT_ERR_INVALID, "two-level tree: more than 2^31 nodes or records");
+        node_off[j + 1] = node_off[j] + tp.n_nodes; prim_off[j + 1] = prim_off[j] + tp.n_records;
         blas_depth = std::max(blas_depth, tp.max_depth);
+        n_split += tp.d_clip ? 1u : 0u;
     }
     // the top level's primitives: one per visible instance of a non-empty BLAS
     std::vector<uint32_t> first2(n + 1, 0u), kind2(std::max(n, 1u), kPrimKindInstance);
@@ -619,6 +726,8 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     // (the pack's refit tables and walk order share the block: nu small tables, one entry per BLAS node)
     const size_t o_pxf = lay.take(sizeof(float) * 12 * nu), o_pid = lay.take(sizeof(uint32_t) * nu), o_psrc = lay.take(sizeof(void *) * nu);
     const size_t o_porder = lay.take(sizeof(uint32_t) * (size_t)node_off[nu]);
+    // (... and, where a BLAS tree has spatial splits, the box the pack's refit takes for every record of the TLAS: the BLASes keep their own copies)
+    const size_t o_pclip = lay.take(n_split ? sizeof(float) * 6 * (size_t)prim_off[nu] : 0u);
     const size_t want = gpu_build_scratch_bytes(n2, &in.split) + lay.used;
     const ScratchArena arena = scratch_acquire(ctx, want);
     if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", want);
@@ -646,9 +755,10 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_root, roots.data(), sizeof(uint32_t) * roots.size(), hipMemcpyHostToDevice, s));
     for (uint32_t j = 0; j < nu; ++j) {
         PackBlasArgs pa{};
-        pa.src_nodes = uniq[j]->d_tmpl_nodes; pa.src_prims = uniq[j]->d_tmpl_prims; pa.n_nodes = node_off[j + 1] - node_off[j]; pa.n_prims = prim_off[j + 1] - prim_off[j];
+        pa.src_nodes = trees[j].d_nodes; pa.src_prims = trees[j].d_prims; pa.n_nodes = node_off[j + 1] - node_off[j]; pa.n_prims = prim_off[j + 1] - prim_off[j];
         pa.dst_nodes = reinterpret_cast<unsigned char *>(d.d_nodes); pa.dst_prims = reinterpret_cast<unsigned char *>(d.d_prims); pa.node_stride = t.node_stride; pa.prim_stride = t.prim_stride;
         pa.node_off = n_top + node_off[j]; pa.prim_off = prim_off[j]; pa.slot = j;
+        if (n_split) { pa.dst_clip = lay.at<float>(o_pclip); pa.src_clip = trees[j].d_clip; pa.src_geom = uniq[j]->d_verts; }
         launch_pack_blas(pa, s);
     }
     // their refit: per-BLAS tables with the identity transform
@@ -656,7 +766,7 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     for (uint32_t j = 0; j < nu; ++j) { pxf[12 * (size_t)j] = pxf[12 * (size_t)j + 5] = pxf[12 * (size_t)j + 10] = 1.0f; psrc[j] = uniq[j]->d_verts; }
     std::vector<uint32_t> order;
     std::vector<std::pair<uint32_t, uint32_t>> pack_phases;
-    pack_refit_order(uniq, node_off, n_top, blas_depth, order, pack_phases);
+    pack_refit_order(trees, node_off, n_top, blas_depth, order, pack_phases);
     if (order.size() != node_off[nu]) return fail(ctx, HRT_ERR_HIP, "two-level tree: a BLAS template's levels do not cover its nodes");
     HIP_TRY(ctx, hipMemcpyAsync(lay.at<float>(o_pxf), pxf.data(), sizeof(float) * pxf.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(lay.at<uint32_t>(o_pid), pid.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, s));
@@ -667,6 +777,8 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     rp.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); rp.node_stride = t.node_stride; rp.prims = reinterpret_cast<unsigned char *>(d.d_prims); rp.prim_stride = t.prim_stride;
     rp.node_box = d.d_node_box; rp.node_ref = d.d_node_ref; rp.inst_xf = lay.at<float>(o_pxf); rp.inst_identity = lay.at<uint32_t>(o_pid); rp.inst_src = lay.at<const void *>(o_psrc); rp.order = lay.at<uint32_t>(o_porder);
     rp.pad = 4e-6f * t.built_reach; rp.write_reference = 1u;
+    // (a record of a tree with spatial splits: the box of its part of the primitive, padded alike -- and for ever: an update refits the top level only)
+    if (n_split) rp.clip = lay.at<float>(o_pclip);
     launch_refit_phases(rp, pack_phases, s);
     HIP_TRY(ctx, hipGetLastError());
     // (4) the top level
@@ -678,12 +790,12 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(s));
     if (ctx->build_verbose)
-        std::fprintf(stderr, "[hrt] two-level build: %u instances over %u BLASes -> %u top nodes (depth %u, %u split levels), %u BLAS nodes (depth <= %u), %u records (flattened: %u)\n",
-                     n2, nu, n_top, r.max_depth, r.split_levels, node_off[nu], blas_depth, n_rec, plan.first[n]);
+        std::fprintf(stderr, "[hrt] two-level build: %u instances over %u BLASes (%u with spatial splits) -> %u top nodes (depth %u, %u split levels), %u BLAS nodes (depth <= %u), %u records (flattened: %u)\n",
+                     n2, nu, n_split, n_top, r.max_depth, r.split_levels, node_off[nu], blas_depth, n_rec, plan.first[n]);
     t.bvh = Bvh8();
     t.n_nodes = n_all; t.n_prims = n_rec; t.max_depth = r.max_depth + 1u + blas_depth;
     t.n_triangles = t.n_spheres = 0;
-    for (uint32_t j = 0; j < nu; ++j) { t.n_triangles += uniq[j]->tmpl.n_triangles; t.n_spheres += uniq[j]->tmpl.n_spheres; }
+    for (uint32_t j = 0; j < nu; ++j) { t.n_triangles += trees[j].n_triangles; t.n_spheres += trees[j].n_spheres; }
     t.alloc_bytes = (uint64_t)t.node_stride * n_all + sizeof(float) * 8 * (uint64_t)n_all + (uint64_t)t.prim_stride * std::max(n_rec, 1u);
     for (int a = 0; a < 3; ++a) { t.lo[a] = r.lo[a]; t.hi[a] = r.hi[a]; }
     return HRT_OK;
@@ -740,10 +852,12 @@ static int plan_build(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &
     t.scene_of_bodies = n_vis >= 4u && (uint64_t)total < 20000ull * n_vis;      // (the launch picks the path kernel's leaf-hold by it, hrt_api.cpp)
     t.node_stride = (uint32_t)ctx->node_stride; t.prim_stride = (uint32_t)ctx->prim_stride;
     if (ctx->node_stride_auto && total > 3500000u) t.node_stride = 128u;      // a tree that will not fit the Infinity Cache: one 128-byte line per node
-    // HRT_CTX_FAST_TRACE: the static-scene tree with spatial splits -- from the device's builder, or (HRT_FAST_TRACE_BUILD=host) from the host's;
-    // it gets the flattened tree whatever two_level_mode says
+    // HRT_CTX_FAST_TRACE: the static-scene tree with spatial splits -- from the device's builder, or (HRT_FAST_TRACE_BUILD=host) from the host's.
+    // It gets the flattened tree unless two levels were ASKED for (two_level_mode > 0, not chosen by size) and the device builds: then the
+    // splits go into the shared BLAS trees, where they last through every update (build_two_level)
     if (instanced) plan.kind = TreeKind::OverInstances;
     else if (!ctx->build_on_device || (fast_trace && !ctx->fast_trace_on_device) || total == 0u) plan.kind = TreeKind::HostFlattened;
+    else if (fast_trace && two_level_mode > 0 && wants_two_level(ctx, inst, refs, two_level_mode, plan)) plan.kind = TreeKind::TwoLevel;
     else if (fast_trace) plan.kind = split_build_fits(ctx, total) ? TreeKind::DeviceSplit : TreeKind::DeviceMerged;
     else plan.kind = wants_two_level(ctx, inst, refs, two_level_mode, plan) ? TreeKind::TwoLevel : TreeKind::DeviceMerged;
     return HRT_OK;
@@ -783,11 +897,12 @@ static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInsta
     case TreeKind::OverInstances: rc = build_over_instances(ctx, t, inst, scene_scale, s); break;
     case TreeKind::DeviceMerged:  rc = build_merged_on_device(ctx, t, plan, false, scene_scale, s); break;
     case TreeKind::DeviceSplit:   rc = build_merged_on_device(ctx, t, plan, true, scene_scale, s); break;
-    case TreeKind::TwoLevel:      rc = build_two_level(ctx, t, inst, plan, scene_scale, s); break;
+    case TreeKind::TwoLevel:      rc = build_two_level(ctx, t, inst, plan, fast_trace, scene_scale, s); break;
     }
     if (rc != HRT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s));
     t.instanced = plan.kind == TreeKind::OverInstances;
+    t.fast_trace = fast_trace;
     t.refits_since_build = 0;
     return HRT_OK;
 }
@@ -1108,8 +1223,8 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
                      force_rebuild ? "verdict of the previous asynchronous refit" : moved_far ? "most instances are further from where the tree was built than they are wide" : "handles / visibility changed or the refit just done degraded the tree", ctx->tlas_refit_ratio.load(),
                      (unsigned long long)t->refits_since_build);
     HIP_TRY(ctx, hipDeviceSynchronize());                 // launches on other streams may still read the old tree
-    // a two-level tree stays one: its top level is rebuilt, the BLAS trees are copied in again
-    const int rb = t->two_level ? build_tlas_into(ctx, *t, inst, s, false, false, 1) : build_tlas_into(ctx, *t, inst, s, rebuild_over_instances(ctx, *t));
+    // a two-level tree stays one: its top level is rebuilt, the BLAS trees -- with their spatial splits, where it was built for trace speed -- are copied in again
+    const int rb = t->two_level ? build_tlas_into(ctx, *t, inst, s, false, t->fast_trace, 1) : build_tlas_into(ctx, *t, inst, s, rebuild_over_instances(ctx, *t));
     if (rb == HRT_OK) t->built_posed = true;      // (built for the instances as they are now: the next update need not be checked on the spot)
     return rb;
 }

@@ -43,7 +43,17 @@ struct Blas {
     // ... and its device copy (topology, packed 80 / 48 byte records): what a two-level TLAS copies in behind its top level
     unsigned char *d_tmpl_nodes = nullptr, *d_tmpl_prims = nullptr;
     float bsphere[4] = {0, 0, 0, -1.0f}; bool bsphere_ready = false;      // bounding sphere (centre of the box, largest vertex distance): the instances' tight bound
-    ~Blas() { if (d_verts) (void)hipFree(d_verts); if (d_tmpl_nodes) (void)hipFree(d_tmpl_nodes); if (d_tmpl_prims) (void)hipFree(d_tmpl_prims); }
+    // A SECOND object-space tree, with spatial splits: what the two-level trees of a HRT_CTX_FAST_TRACE context copy in instead of `tmpl` (the
+    // geometry never moves relative to these boxes, so the splits never expire).  Device only, packed like d_tmpl_*, plus the box of every
+    // record's part of its primitive (6 floats per record: what the pack's refit takes instead of the primitive's own box).  Built once
+    // (tmpl_mu) and shared by every TLAS that instances the BLAS; `tmpl` stays what it is.
+    struct SplitTree {
+        unsigned char *d_nodes = nullptr, *d_prims = nullptr; float *d_clip = nullptr;
+        uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
+        std::vector<uint32_t> level_begin;
+    } split;
+    bool split_decided = false;      // `split` is there, or this BLAS is known to go without (4096 primitives or fewer; the top-down phase gave up)
+    ~Blas() { for (void *p : {(void *)d_verts, (void *)d_tmpl_nodes, (void *)d_tmpl_prims, (void *)split.d_nodes, (void *)split.d_prims, (void *)split.d_clip}) if (p) (void)hipFree(p); }
 };
 
 // The device memory of a TLAS: every member is a block from the context's pool (pool_alloc) and nothing else, so that free_tlas_device
@@ -96,7 +106,9 @@ struct Tlas {
     bool two_level = false; uint32_t n_top_nodes = 0, n_unique_blas = 0;
     bool scene_of_bodies = false;        // at least 4 visible instances of fewer than 20 000 primitives each on average (the reference's kind of scene)
     float built_reach = 1.0f;                            // the largest object-space |coordinate| a ray origin was assumed to have when the BLAS trees were padded
-    bool has_split_refs = false;                         // built with spatial splits (HRT_CTX_FAST_TRACE): a refit would recompute the leaf boxes from whole primitives, so the first update rebuilds instead
+    bool has_split_refs = false;                         // a FLATTENED tree built with spatial splits (HRT_CTX_FAST_TRACE): a refit would recompute the leaf boxes from whole primitives, so the first update rebuilds instead
+                                                         // (never a two-level tree: its updates do not touch the BLAS trees, split or not)
+    bool fast_trace = false;                             // what hrt_tlas_build was asked for: a rebuild inside hrt_tlas_update of a two-level tree asks for the same (the BLASes' split trees are reused)
     float *h_area = nullptr;                             // pinned: area sum of the last refit
     hipEvent_t area_ready = nullptr; bool area_pending = false;
     uint64_t refits = 0, rebuilds = 0, refits_since_build = 0;

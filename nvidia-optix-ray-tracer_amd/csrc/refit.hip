@@ -267,7 +267,8 @@ void launch_instance_tables(const InstanceTableArgs &a, hipStream_t s) {
 
 // ---- two-level trees: a BLAS's object-space tree (topology: the template, built once per BLAS) goes into the TLAS's arrays behind the
 // top level -- its node and record numbers move by where it lands, its records name its slot in the table of BLASes the pack's refit
-// reads (geometry source, identity transform); everything else is the refit's to compute, as after any build. ----
+// reads (geometry source, identity transform); everything else is the refit's to compute, as after any build.  Where a BLAS of the TLAS
+// carries spatial splits, the records' boxes for that refit are laid out here too (PackBlasArgs::dst_clip). ----
 __global__ __launch_bounds__(256) void k_pack_blas(PackBlasArgs a) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < a.n_nodes) {
@@ -281,6 +282,24 @@ __global__ __launch_bounds__(256) void k_pack_blas(PackBlasArgs a) {
         uint32_t *dst = reinterpret_cast<uint32_t *>(a.dst_prims + (size_t)(a.prim_off + i) * a.prim_stride);
         for (int q = 0; q < 12; ++q) dst[q] = src[q];
         dst[7] = a.slot;
+        if (a.dst_clip) {
+            // the box the pack's refit takes for this record: of its part of the primitive (a tree with spatial splits), else what refit_record
+            // itself computes from the whole primitive under the pack's identity transform -- the same functions, the same bits
+            float *cb = a.dst_clip + 6 * (size_t)(a.prim_off + i);
+            float lo[3], hi[3];
+            if (a.src_clip) {
+                for (int q = 0; q < 3; ++q) { lo[q] = a.src_clip[6 * (size_t)i + q]; hi[q] = a.src_clip[6 * (size_t)i + 3 + q]; }
+            } else if (src[11] == 0u) {
+                const float *g = a.src_geom + 9 * (size_t)src[3];
+                float s9[9], v0[3], e1[3], e2[3];
+                for (int q = 0; q < 9; ++q) s9[q] = g[q];
+                triangle_world(s9, nullptr, true, v0, e1, e2, lo, hi);
+            } else {
+                const float c3[3] = {__uint_as_float(src[0]), __uint_as_float(src[1]), __uint_as_float(src[2])};
+                sphere_world_bounds(c3, __uint_as_float(src[4]), nullptr, true, lo, hi);
+            }
+            for (int q = 0; q < 3; ++q) { cb[q] = lo[q]; cb[3 + q] = hi[q]; }
+        }
     }
 }
 void launch_pack_blas(const PackBlasArgs &a, hipStream_t s) {
