@@ -243,12 +243,46 @@ int  hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out);
 int  hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
                                  const HrtDenoiseParams *h_dparams, const HrtDenoiseTemporalParams *h_tparams,
                                  HrtFloat4 *d_out, void *stream);
-/* forget the history: the next hrt_denoise_temporal_launch starts afresh */
+/* forget the history: the next hrt_denoise_temporal_launch (or hrt_denoise_variance_launch) starts afresh */
 int  hrt_denoise_temporal_reset(HrtContext *ctx);
 /* the last hrt_denoise_temporal_launch's intermediates, width * height each (a NULL pointer skips its buffer): the accumulated colour
  * A (float4, what the filter took), the history length L (float; 0 on background), and the reprojected position (x', y') in the
  * previous frame's pixel coordinates (float2; NaN where no projection was made).  HRT_ERR_STATE before the first call.  Enqueued only. */
 int  hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float *d_length, float *d_motion, void *stream);
+
+/* Variance-guided mode: the temporal mode with the filter's colour edge stop following the accumulated frame's variance (SVGF,
+ * Schied et al. 2017; DESIGN.md 3e "Variance-guided mode"; tests/denoise_variance_ref.py restates it).  Next to the colour, the history
+ * carries the first two moments M = (m1, m2) of the luminance l(c) = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z through the same
+ * reprojection and blend (8 B per pixel and set more).  The per-pixel variance is max(0, m2 - m1^2) where the history length L has
+ * reached history_min, and the variance of the moments over the 5x5 block's pixels of the same instance where it has not.  Every
+ * filter pass weighs a tap's luminance difference against the 3x3-smoothed variance, 1 / (1 + dl^2 / (sigma_luminance^2 var +
+ * variance_floor)), in place of the colour stop, and filters the variance as that of the weighted mean.  sigma_color is not used,
+ * but is still refused (HRT_ERR_INVALID) unless it is > 0 and finite, like every other field of HrtDenoiseParams.
+ * The history is the temporal mode's: a call whose predecessor was hrt_denoise_temporal_launch (or the reverse) starts afresh, as
+ * after hrt_denoise_temporal_reset or a change of TLAS handle, frame size or instance count.  A call that starts afresh is NOT
+ * hrt_denoise_launch's result: it is the definition with L = 1 on every hit pixel, so the 5x5 variance applies everywhere. */
+typedef struct HrtDenoiseVarianceParams {
+    float    sigma_luminance;      /* luminance edge stop in standard deviations, > 0                                       (default 4.0)  */
+    uint32_t history_min;          /* 1..65536: a hit pixel with L below it takes the 5x5 variance                          (default 4)    */
+    float    variance_floor;       /* added to sigma_luminance^2 var, > 0                                                   (default 1e-6) */
+    uint32_t reserved;             /* must be 0 */
+} HrtDenoiseVarianceParams;
+
+int  hrt_denoise_variance_default_params(HrtDenoiseVarianceParams *out);
+/* the variance-guided filter alone over caller-given colour, guides and variance (width * height floats): -> d_out (may be d_color)
+ * and the filtered variance -> d_var_out (may be d_variance, or NULL).  NULL parameters: the defaults.  Enqueued only. */
+int  hrt_denoise_filter_variance(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDenoiseGuide *d_guides, const float *d_variance,
+                                 HrtFloat4 *d_out, float *d_var_out, uint32_t width, uint32_t height,
+                                 const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams, void *stream);
+/* one frame of the variance-guided mode into d_out (may be h_raygen->colorBuffer): guides, reprojection and blend with the moments,
+ * variance, variance-guided filter.  NULL parameters: the defaults.  Enqueued only. */
+int  hrt_denoise_variance_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                                 const HrtDenoiseParams *h_dparams, const HrtDenoiseTemporalParams *h_tparams,
+                                 const HrtDenoiseVarianceParams *h_vparams, HrtFloat4 *d_out, void *stream);
+/* the last hrt_denoise_variance_launch's moments (width * height float2) and the variance its filter took (width * height float); a
+ * NULL pointer skips its buffer.  hrt_debug_denoise_temporal_state gives its A, L and motion.  HRT_ERR_STATE before the first call.
+ * Enqueued only. */
+int  hrt_debug_denoise_variance_state(HrtContext *ctx, float *d_moments, float *d_variance, void *stream);
 
 /* ---- measurement (no reference counterpart: the reference has no timers) ------------- */
 enum { HRT_K_GENERATE = 0, HRT_K_TRAVERSE, HRT_K_TRAVERSE_ANY, HRT_K_BIN, HRT_K_SHADE,
@@ -319,5 +353,6 @@ void hrt_host_free(HrtBvhBlob *blob);
 static_assert(sizeof(HrtDenoiseGuide) == 16, "HrtDenoiseGuide is 16 B");
 static_assert(sizeof(HrtDenoiseTemporalParams) == 16, "HrtDenoiseTemporalParams is 16 B");
 static_assert(sizeof(HrtDenoiseParams) == 24, "HrtDenoiseParams is 24 B");
+static_assert(sizeof(HrtDenoiseVarianceParams) == 16, "HrtDenoiseVarianceParams is 16 B");
 #endif
 #endif /* HRT_H */

@@ -99,9 +99,14 @@ class DenoiseTemporalParams(C.Structure):
     _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("reserved", C.c_uint32)]
 
 
+class DenoiseVarianceParams(C.Structure):
+    """HrtDenoiseVarianceParams (include/hrt.h): the variance-guided mode's luminance stop, young-history threshold and variance floor."""
+    _fields_ = [("sigma_luminance", C.c_float), ("history_min", C.c_uint32), ("variance_floor", C.c_float), ("reserved", C.c_uint32)]
+
+
 DENOISE_GUIDE_BYTES = 16        # HrtDenoiseGuide: normal[3], albedo[3] as IEEE halves, depth (float)
 
-assert C.sizeof(DenoiseParams) == 24 and C.sizeof(DenoiseTemporalParams) == 16
+assert C.sizeof(DenoiseParams) == 24 and C.sizeof(DenoiseTemporalParams) == 16 and C.sizeof(DenoiseVarianceParams) == 16
 assert C.sizeof(GlobalParams) == 16 and C.sizeof(RayGenParams) == 80 and C.sizeof(MissParams) == 12
 assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof(Instance) == 80
 
@@ -119,6 +124,7 @@ EXPORTS = [
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
+    "hrt_denoise_variance_default_params", "hrt_denoise_filter_variance", "hrt_denoise_variance_launch", "hrt_debug_denoise_variance_state",
 ]
 
 
@@ -191,6 +197,12 @@ def load_library():
                                                 C.POINTER(DenoiseTemporalParams), C.c_void_p, C.c_void_p]
     lib.hrt_denoise_temporal_reset.argtypes = [C.c_void_p]
     lib.hrt_debug_denoise_temporal_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hrt_denoise_variance_default_params.argtypes = [C.POINTER(DenoiseVarianceParams)]
+    lib.hrt_denoise_filter_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceParams), C.c_void_p]
+    lib.hrt_denoise_variance_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
+                                                C.POINTER(DenoiseTemporalParams), C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p]
+    lib.hrt_debug_denoise_variance_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_host_free.argtypes = [C.POINTER(BvhBlob)]
     lib.hrt_host_free.restype = None
     _lib = lib
@@ -202,4 +214,4 @@ from . import scenes  # noqa: E402
 
 __all__ = ["load_library", "Renderer", "configure_camera", "tile_for_rank", "reduce_tiles", "scenes", "HrtError",
            "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats", "DenoiseParams",
-           "DenoiseTemporalParams"]
+           "DenoiseTemporalParams", "DenoiseVarianceParams"]

@@ -6,6 +6,9 @@
 //   k_denoise_pass    one pass of the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010): 5x5 B3-spline taps `step` pixels
 //                     apart, weighted by colour, normal, albedo and depth distance to the centre pixel
 //   k_denoise_temporal the temporal mode's reprojection of every hit pixel into the previous frame and its blend with the history there
+//                     (<true>: the variance-guided mode's, which carries the first two moments of the luminance through the same blend)
+//   k_denoise_variance the variance-guided mode's per-pixel luminance variance, from the moments or, under a young history, from the 5x5 block
+//   k_denoise_pass_var k_denoise_pass with the colour edge stop scaled by the local variance, which it filters along with the colour
 // The filter is defined with + - * / and max only, taps in row-major order, sums in float32, and compiled with -ffp-contract=off: its
 // result is reproduced bit for bit by tests/denoise_ref.py (DESIGN.md "Denoiser").
 #include <hip/hip_runtime.h>
@@ -24,6 +27,8 @@ constexpr int kDenoiseTile = 16;          // 16 x 16 pixels per workgroup: a tap
 __device__ __forceinline__ uint32_t half_bits(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }     // RNE
 __device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
 __device__ __forceinline__ bool guide_hit(float z) { return z > 0.0f && z < INFINITY; }
+// luminance of an sRGB-encoded colour (the variance-guided mode's edge stop and moments)
+__device__ __forceinline__ float luminance(const float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
 // one HrtDenoiseGuide as 4 words: normal[0..2], albedo[0..2] (halves, little-endian), depth
 struct Guide { V3 n, a; float z; };
@@ -130,8 +135,11 @@ __global__ __launch_bounds__(kDenoiseTile * kDenoiseTile) void k_denoise_pass(De
 // (1-fx)fy, fx fy, each taken if it lies in the frame and holds the same (instance, primitive) at |z_prev - z'| <= tol z'.  With the sum
 // of the taken weights sw > 0: H = (sum w A_prev) / sw, Lh = (sum w L_prev) / sw (sums in tap order), L = min(Lh + 1, max_history),
 // alpha = max(1 / L, alpha_min), A = H + alpha (C - H) per colour channel, alpha the current pixel's; else A = C, L = 1.  Background:
-// A = C, L = 0.  (x', y') goes to `motion` (NaN without a projection).  The four taps' records are loaded together from clamped
-// addresses and the ones that do not count are left out by a select, as in k_denoise_pass.
+// A = C, L = 0.  (x', y') goes to `motion` (NaN without a projection).  The four taps' ids and depths, which decide whether a tap counts,
+// are loaded together from clamped addresses; A_prev, L_prev (and M_prev) are then read for the taps that count only.
+// kMoments (the variance-guided mode): M = (m1, m2), the moments of the luminance l(C), go through the same taps, weights and alpha:
+// with mc = (l(C), l(C) l(C)), M = Hm + alpha (mc - Hm), Hm = (sum w M_prev) / sw; without history M = mc; background M = (0, 0).
+template <bool kMoments>
 __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.width * a.height) return;
@@ -140,6 +148,7 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
     const float nan = __builtin_nanf("");
     float4 acc = c;
     float len = 0.0f;
+    float2 mom = make_float2(0.0f, 0.0f);
     float2 mo = make_float2(nan, nan);
     uint2 id = make_uint2(kMissPrim, 0u);
     if (inst != kMissPrim) {
@@ -147,6 +156,8 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
         const uint32_t prim = __float_as_uint(h.w);
         id = make_uint2(inst, prim);
         len = 1.0f;
+        float lc = 0.0f;
+        if (kMoments) { lc = luminance(c); mom = make_float2(lc, lc * lc); }
         if (a.has_history) {
             const RayRec ray = a.rays[p];
             const float hp[3] = {ray.o.x + ray.d.x * h.x, ray.o.y + ray.d.y * h.x, ray.o.z + ray.d.z * h.x};      // hit_point
@@ -179,7 +190,7 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
                 uint2 qid[4]; float qz[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { qid[k] = a.prev_id[q[k]]; qz[k] = __uint_as_float(a.prev_guides[q[k]].w); }
-                float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
+                float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const bool take = in[k] && qid[k].x == inst && qid[k].y == prim && fabsf(qz[k] - zp) <= a.depth_tolerance * zp;
@@ -189,6 +200,7 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
                         sw = sw + w[k];
                         sr = sr + w[k] * ha.x; sg = sg + w[k] * ha.y; sb = sb + w[k] * ha.z;
                         sl = sl + w[k] * hl;
+                        if (kMoments) { const float2 hm = a.prev_moments[q[k]]; sm1 = sm1 + w[k] * hm.x; sm2 = sm2 + w[k] * hm.y; }
                     }
                 }
                 if (sw > 0.0f) {
@@ -196,6 +208,7 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
                     len = fminf(sl / sw + 1.0f, a.max_history);
                     const float alpha = fmaxf(1.0f / len, a.alpha_min);
                     acc = make_float4(hr + alpha * (c.x - hr), hg + alpha * (c.y - hg), hb + alpha * (c.z - hb), c.w);
+                    if (kMoments) { const float h1 = sm1 / sw, h2 = sm2 / sw; mom = make_float2(h1 + alpha * (mom.x - h1), h2 + alpha * (mom.y - h2)); }
                 }
             }
         }
@@ -204,13 +217,147 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a)
     a.length[p] = len;
     a.id[p] = id;
     a.motion[p] = mo;
+    if (kMoments) a.moments[p] = mom;
+}
+
+// The variance-guided mode's variance of the luminance, one thread per pixel (DESIGN.md 3e "Variance-guided mode";
+// tests/denoise_variance_ref.py).  Background: 0.  A hit pixel with L >= history_min: max(0, m2 - m1 m1).  Any other hit pixel (a young
+// history): over the 5x5 block around it, row-major, the taps inside the frame that hold the centre's instance (the centre among
+// them): n their count, s1 = sum m1_q, s2 = sum m2_q, mu = s1 / n, var = max(0, s2 / n - mu mu).  max(0, x) is fmaxf: NaN -> 0.
+__global__ __launch_bounds__(256) void k_denoise_variance(DenoiseVarianceArgs a) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.width * a.height) return;
+    const uint32_t inst = a.id[p].x;
+    float var = 0.0f;
+    if (inst != kMissPrim) {
+        if (a.length[p] >= a.history_min) {                  // (a NaN length: the spatial estimate)
+            const float2 m = a.moments[p];
+            var = fmaxf(0.0f, m.y - m.x * m.x);
+        } else {
+            const int W = (int)a.width, H = (int)a.height;
+            const int y = (int)(p / a.width), x = (int)(p - (uint32_t)y * a.width);
+            float n = 0.0f, s1 = 0.0f, s2 = 0.0f;
+            for (int j = -2; j <= 2; ++j) {
+                const int qy = y + j;
+                if (qy < 0 || qy >= H) continue;
+#pragma unroll
+                for (int i = -2; i <= 2; ++i) {
+                    const int qx = x + i;
+                    const size_t q = (size_t)qy * a.width + (size_t)min(max(qx, 0), W - 1);
+                    const uint32_t qi = a.id[q].x;
+                    const float2 m = a.moments[q];
+                    const bool take = qx >= 0 && qx < W && qi == inst;
+                    n = take ? n + 1.0f : n;
+                    s1 = take ? s1 + m.x : s1;
+                    s2 = take ? s2 + m.y : s2;
+                }
+            }
+            const float mu = s1 / n;
+            var = fmaxf(0.0f, s2 / n - mu * mu);
+        }
+    }
+    a.variance[p] = var;
+}
+
+// k_denoise_pass of the variance-guided mode: the same geometry, taps, normal, albedo and depth stops, exclusions and `sw > 0` rule; the
+// colour stop is the luminance difference over the local variance,
+//   w = ((h[dx] * h[dy]) * wn) / (((1 + (dl dl) inv_v) * (1 + |a_p - a_q|^2 k_albedo)) * (1 + rz rz)),  dl = l(c_q) - l(c_p),
+//   inv_v = 1 / (k_luminance gv + variance_floor),  gv = (sum g var_q) / (sum g) over the 3x3 block of step 1 around p, the taps inside
+//   the frame that are hits, g = {1/4, 1/2, 1/4} x {1/4, 1/2, 1/4}, row-major,
+// and the variance goes through the filter as the variance of the weighted mean: var_out = (sum (w w) var_q) / (sw sw).  A pixel that
+// keeps its colour keeps its variance.  The stop does not shrink with the pass: the variance does.
+template <int kSquarings>
+__global__ __launch_bounds__(kDenoiseTile * kDenoiseTile) void k_denoise_pass_var(DenoisePassVarArgs a) {
+    const int x = (int)(blockIdx.x * kDenoiseTile + threadIdx.x), y = (int)(blockIdx.y * kDenoiseTile + threadIdx.y);
+    const int W = (int)a.width, H = (int)a.height, s = (int)a.step;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * a.width + (size_t)x;
+    const float4 cp = a.src[p];
+    const float vp = a.var_src[p];
+    const Guide gp = guide_decode(a.guides[p]);
+    if (!guide_hit(gp.z)) { a.dst[p] = cp; a.var_dst[p] = vp; return; }
+    const uint32_t squarings = kSquarings >= 0 ? (uint32_t)kSquarings : a.normal_squarings;
+    const float inv_z = 1.0f / (a.sigma_depth_step * gp.z);
+    const float kG[3] = {0.25f, 0.5f, 0.25f};
+    float sgv = 0.0f, sgw = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int qy = y + (j - 1);
+        if (qy < 0 || qy >= H) continue;
+        const size_t row = (size_t)qy * a.width;
+        float vq[3], zq[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int qx = min(max(x + (i - 1), 0), W - 1);
+            vq[i] = a.var_src[row + (size_t)qx];
+            zq[i] = __uint_as_float(a.guides[row + (size_t)qx].w);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int qx = x + (i - 1);
+            const bool take = qx >= 0 && qx < W && guide_hit(zq[i]);
+            const float g = kG[i] * kG[j];
+            sgw = take ? sgw + g : sgw;
+            sgv = take ? sgv + g * vq[i] : sgv;
+        }
+    }
+    const float gv = sgv / sgw;
+    const float inv_v = 1.0f / (a.k_luminance * gv + a.variance_floor);
+    const float lp = luminance(cp);
+    const float kH[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int qy = y + (j - 2) * s;
+        if (qy < 0 || qy >= H) continue;
+        const size_t row = (size_t)qy * a.width;
+        uint4 graw[5]; float4 cq[5]; float vq[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int qx = min(max(x + (i - 2) * s, 0), W - 1);
+            graw[i] = a.guides[row + (size_t)qx];
+            cq[i] = a.src[row + (size_t)qx];
+            vq[i] = a.var_src[row + (size_t)qx];
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int qx = x + (i - 2) * s;
+            const Guide gq = guide_decode(graw[i]);
+            const bool take = qx >= 0 && qx < W && guide_hit(gq.z);
+            const float dl = luminance(cq[i]) - lp;
+            float wn = fmaxf(dot3(gp.n, gq.n), 0.0f);
+            for (uint32_t k = 0; k < squarings; ++k) wn = wn * wn;
+            const V3 da = sub3(gp.a, gq.a);
+            const float da2 = len2_3(da);
+            const float rz = (gp.z - gq.z) * inv_z;
+            const float w = ((kH[i] * kH[j]) * wn) / (((1.0f + (dl * dl) * inv_v) * (1.0f + da2 * a.k_albedo)) * (1.0f + rz * rz));
+            sw = take ? sw + w : sw;
+            sr = take ? sr + w * cq[i].x : sr; sg = take ? sg + w * cq[i].y : sg; sb = take ? sb + w * cq[i].z : sb;
+            sv = take ? sv + (w * w) * vq[i] : sv;
+        }
+    }
+    const bool filtered = sw > 0.0f;
+    a.dst[p] = filtered ? make_float4(sr / sw, sg / sw, sb / sw, cp.w) : cp;
+    a.var_dst[p] = filtered ? sv / (sw * sw) : vp;
 }
 
 static inline uint32_t ceil_div_u(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s) {
     const uint32_t n = a.width * a.height;
-    if (n) hipLaunchKernelGGL(k_denoise_temporal, dim3(ceil_div_u(n, 256)), dim3(256), 0, s, a);
+    if (!n) return;
+    if (a.moments) hipLaunchKernelGGL(k_denoise_temporal<true>, dim3(ceil_div_u(n, 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_denoise_temporal<false>, dim3(ceil_div_u(n, 256)), dim3(256), 0, s, a);
+}
+void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s) {
+    const uint32_t n = a.width * a.height;
+    if (n) hipLaunchKernelGGL(k_denoise_variance, dim3(ceil_div_u(n, 256)), dim3(256), 0, s, a);
+}
+void launch_denoise_pass_var(const DenoisePassVarArgs &a, hipStream_t s) {
+    if (!a.width || !a.height) return;
+    const dim3 grid(ceil_div_u(a.width, kDenoiseTile), ceil_div_u(a.height, kDenoiseTile)), block(kDenoiseTile, kDenoiseTile);
+    if (a.normal_squarings == 3u) hipLaunchKernelGGL(k_denoise_pass_var<3>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_denoise_pass_var<-1>, grid, block, 0, s, a);
 }
 
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s) {

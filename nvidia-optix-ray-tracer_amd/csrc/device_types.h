@@ -227,7 +227,25 @@ struct DenoiseTemporalArgs {
     uint32_t width, height, has_history;
     float prev_center[3], prev_U[3], prev_V[3], prev_W[3];
     float alpha_min, max_history, depth_tolerance;
+    const float2 *prev_moments; float2 *moments;             // the variance-guided mode's luminance moments (moments == NULL: not carried)
 };
+// the variance-guided mode (DESIGN.md 3e "Variance-guided mode"): the per-pixel variance from the moments, and one filter pass that
+// carries a variance frame along with the colour
+struct DenoiseVarianceArgs {
+    const float2 *moments; const float *length; const uint2 *id; float *variance;
+    uint32_t width, height;
+    float history_min;                                       // L below it: the spatial estimate
+};
+struct DenoisePassVarArgs {
+    const float4 *src; const float *var_src; const uint4 *guides; float4 *dst; float *var_dst;
+    uint32_t width, height, step;
+    float k_luminance;             // sigma_luminance^2
+    float variance_floor;
+    float k_albedo, sigma_depth_step;
+    uint32_t normal_squarings;
+};
+void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s);
+void launch_denoise_pass_var(const DenoisePassVarArgs &a, hipStream_t s);
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
 void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);

@@ -2,7 +2,7 @@
 // main() (src/Global/Main.cu:21-36) -> RendererMesh::writeCacheFilesAndExit (src/Util/VTKMeshReader.cu:146-215) when the
 // config says "cache", else RendererMesh::commitRendererData (src/Global/RendererMesh.cu:160-310) -> RendererMesh::startRender's
 // frame loop (:312-440) with the window and camera input left out; the denoiser (denoiseOutput, :420-426) runs with --denoise.
-//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal]
+//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
 // Loading: up to cache-process-thread-count loader threads, each with its own stream, read particleN.cache and build one GAS per
 // particle plus the file's IAS ON THE DEVICE (readVTKFileCache, :93-157).  Per frame: every particle drifts by its velocity
@@ -60,11 +60,13 @@ int main(int argc, char **argv) {
     // --denoise (anywhere): every frame goes through denoiseOutput before the conversion, as the reference's default display does
     // (RendererTime.cu / RendererMesh.cu: launch -> denoiseOutput -> convertFloat4ToUchar4Kernel); without it the raw frame is shown, skipDenoise
     // --denoise-temporal (anywhere): the same slot in the library's temporal mode, each frame blended into the history of the ones before
-    bool denoise = false, denoiseTemporal = false;
+    // --denoise-variance (anywhere): the temporal mode with variance-guided edge stops (denoiseOutputVariance)
+    bool denoise = false, denoiseTemporal = false, denoiseVariance = false;
     { int k = 1; for (int i = 1; i < argc; ++i) { if (std::strcmp(argv[i], "--denoise") == 0) denoise = true;
-                                                  else if (std::strcmp(argv[i], "--denoise-temporal") == 0) denoiseTemporal = true; else argv[k++] = argv[i]; } argc = k; }
-    if (denoise && denoiseTemporal) { std::fprintf(stderr, "--denoise and --denoise-temporal exclude each other\n"); return 2; }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise | --denoise-temporal]\n", argv[0]); return 2; }
+                                                  else if (std::strcmp(argv[i], "--denoise-temporal") == 0) denoiseTemporal = true;
+                                                  else if (std::strcmp(argv[i], "--denoise-variance") == 0) denoiseVariance = true; else argv[k++] = argv[i]; } argc = k; }
+    if ((int)denoise + (int)denoiseTemporal + (int)denoiseVariance > 1) { std::fprintf(stderr, "--denoise, --denoise-temporal and --denoise-variance exclude each other\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]\n", argv[0]); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -220,6 +222,7 @@ int main(int argc, char **argv) {
             hrtCheckError(ctx, hrt_render_launch(ctx, &params, &raygen, 1, nullptr, nullptr));      // (launch, conversion, then the frame's one synchronisation)
             if (denoise) denoiseOutput(ctx, params, raygen, color);                                   // (in place: the colour buffer is not read again)
             if (denoiseTemporal) denoiseOutputTemporal(ctx, params, raygen, color);
+            if (denoiseVariance) denoiseOutputVariance(ctx, params, raygen, color);
             hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr));
             hrtCheckError(ctx, hrt_sync(ctx, nullptr));
         }

@@ -2,7 +2,7 @@
 // main() (src/Global/Main.cu:12-50) -> RendererTime::commitRendererData (src/Global/RendererTime.cu:160-290)
 // -> RendererTime::startRender's frame loop (:373-520) with the window and camera input left out; the denoiser (denoiseOutput, :501-510)
 // runs with --denoise.
-//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal]
+//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
 // Per frame: hrt_pose_instances -> updateIAS -> launch + sync -> (denoiseOutput) -> convert to 8 bit; the last frame is written as PPM.
 #include "renderer_host.hpp"
@@ -32,11 +32,13 @@ int main(int argc, char **argv) {
     // --denoise (anywhere): every frame goes through denoiseOutput before the conversion, as the reference's default display does
     // (RendererTime.cu / RendererMesh.cu: launch -> denoiseOutput -> convertFloat4ToUchar4Kernel); without it the raw frame is shown, skipDenoise
     // --denoise-temporal (anywhere): the same slot in the library's temporal mode, each frame blended into the history of the ones before
-    bool denoise = false, denoiseTemporal = false;
+    // --denoise-variance (anywhere): the temporal mode with variance-guided edge stops (denoiseOutputVariance)
+    bool denoise = false, denoiseTemporal = false, denoiseVariance = false;
     { int k = 1; for (int i = 1; i < argc; ++i) { if (std::strcmp(argv[i], "--denoise") == 0) denoise = true;
-                                                  else if (std::strcmp(argv[i], "--denoise-temporal") == 0) denoiseTemporal = true; else argv[k++] = argv[i]; } argc = k; }
-    if (denoise && denoiseTemporal) { std::fprintf(stderr, "--denoise and --denoise-temporal exclude each other\n"); return 2; }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise | --denoise-temporal]\n", argv[0]); return 2; }
+                                                  else if (std::strcmp(argv[i], "--denoise-temporal") == 0) denoiseTemporal = true;
+                                                  else if (std::strcmp(argv[i], "--denoise-variance") == 0) denoiseVariance = true; else argv[k++] = argv[i]; } argc = k; }
+    if ((int)denoise + (int)denoiseTemporal + (int)denoiseVariance > 1) { std::fprintf(stderr, "--denoise, --denoise-temporal and --denoise-variance exclude each other\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]\n", argv[0]); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -152,6 +154,7 @@ int main(int argc, char **argv) {
         launch(ctx, params, raygen, 1);
         if (denoise) denoiseOutput(ctx, params, raygen, color);
         if (denoiseTemporal) denoiseOutputTemporal(ctx, params, raygen, color);
+        if (denoiseVariance) denoiseOutputVariance(ctx, params, raygen, color);
         hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr));
     }
     long frames = 0;
@@ -193,6 +196,7 @@ int main(int argc, char **argv) {
             timed(first, kLaunch, [&] { hrtCheckError(ctx, hrt_render_launch(ctx, &params, &raygen, 1, nullptr, nullptr)); });
             if (denoise) timed(first, kDenoise, [&] { denoiseOutput(ctx, params, raygen, color); });     // (in place: the colour buffer is not read again)
             if (denoiseTemporal) timed(first, kDenoise, [&] { denoiseOutputTemporal(ctx, params, raygen, color); });
+            if (denoiseVariance) timed(first, kDenoise, [&] { denoiseOutputVariance(ctx, params, raygen, color); });
             timed(first, kRgba, [&] { hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr)); hrtCheckError(ctx, hrt_sync(ctx, nullptr)); });
         }
     }

@@ -179,4 +179,12 @@ inline void denoiseOutputTemporal(HrtContext *ctx, const HrtGlobalParams &params
     hrtCheckError(ctx, hrt_denoise_temporal_launch(ctx, &params, &raygen, denoiseParams, temporalParams, output, stream));
 }
 
+// denoiseOutput's variance-guided mode (include/hrt.h): the temporal mode with the luminance moments carried through the history and the
+// filter's colour edge stop following the accumulated frame's variance.  It shares the context's history with the temporal mode.
+inline void denoiseOutputVariance(HrtContext *ctx, const HrtGlobalParams &params, const HrtRayGenParams &raygen, HrtFloat4 *output,
+                                  const HrtDenoiseParams *denoiseParams = nullptr, const HrtDenoiseTemporalParams *temporalParams = nullptr,
+                                  const HrtDenoiseVarianceParams *varianceParams = nullptr, hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_denoise_variance_launch(ctx, &params, &raygen, denoiseParams, temporalParams, varianceParams, output, stream));
+}
+
 }  // namespace project

@@ -2,14 +2,16 @@
 // Guide pass: the primary rays of the frame (denoise.hip k_denoise_rays) through hrt_trace_rays' traversal (hrt_api.cpp trace_records: the
 // path kernel in the context's configuration, flattened and two-level trees alike), their hits turned into HrtDenoiseGuide records with
 // the material tables of the launch.  Filter: `iterations` a-trous passes, one launch each, ping-ponging between two frames the context
-// owns.  Every call only enqueues work (the material tables' upload after hrt_materials_set synchronises once, as in hrt_render_launch).
+// owns.  The temporal and the variance-guided mode share the reprojection step (run_temporal) and the history; the variance-guided filter
+// (run_filter_variance) ping-pongs a variance frame next to the colour.  Every call only enqueues work (the material tables' upload
+// after hrt_materials_set synchronises once, as in hrt_render_launch).
 #include "hrt_internal.hpp"
 
 namespace hrt {
 
 void free_denoise_work(HrtContext *ctx) {
     DenoiseWork &d = ctx->denoise;
-    void *ptrs[] = {d.rays, d.tuvp, d.inst, d.guides, d.frame[0], d.frame[1], d.fetch};
+    void *ptrs[] = {d.rays, d.tuvp, d.inst, d.guides, d.frame[0], d.frame[1], d.var[0], d.var[1], d.fetch};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     d = DenoiseWork{};
 }
@@ -17,10 +19,11 @@ void free_denoise_work(HrtContext *ctx) {
 void free_denoise_history(HrtContext *ctx) {
     DenoiseHistory &h = ctx->denoise_history;
     for (DenoiseHistorySet &s : h.set) {
-        void *ptrs[] = {s.accum, s.length, s.guides, s.id, s.xf};
+        void *ptrs[] = {s.accum, s.length, s.guides, s.id, s.moments, s.xf};
         for (void *p : ptrs) if (p) (void)hipFree(p);
     }
     if (h.motion) (void)hipFree(h.motion);
+    if (h.variance) (void)hipFree(h.variance);
     h = DenoiseHistory{};
 }
 
@@ -55,26 +58,50 @@ int ensure_work(HrtContext *ctx, uint32_t n, bool trace) {
     return HRT_OK;
 }
 
+// ... and the variance-guided filter's two variance frames next to its colour frames.  They are sized by d.capacity like every other
+// array here: free_denoise_work, which ensure_work calls before the capacity grows, frees them too, so a non-NULL one is large enough.
+int ensure_variance_work(HrtContext *ctx, uint32_t n) {
+    int rc = ensure_work(ctx, n, false);
+    if (rc != HRT_OK) return rc;
+    DenoiseWork &d = ctx->denoise;
+    for (float *&v : d.var)
+        if (!v) HIP_TRY(ctx, hipMalloc((void **)&v, sizeof(float) * (size_t)d.capacity));
+    return HRT_OK;
+}
+
 bool positive_finite(float x) { return std::isfinite(x) && x > 0.0f; }
 
-// the parameters (NULL: the defaults) and the constants of every pass; HRT_ERR_INVALID when one is out of range
-int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, std::vector<DenoisePassArgs> &passes) {
-    HrtDenoiseParams p;
+// the filter's parameters (NULL: the defaults), validated; HRT_ERR_INVALID when one is out of range
+int filter_params(HrtContext *ctx, const HrtDenoiseParams *h_dparams, HrtDenoiseParams &p) {
     hrt_denoise_default_params(&p);
     if (h_dparams) p = *h_dparams;
     if (p.iterations < 1 || p.iterations > 16 || p.normal_power_log2 > 8 || p.reserved != 0 ||
         !positive_finite(p.sigma_color) || !positive_finite(p.sigma_albedo) || !positive_finite(p.sigma_depth))
         return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range (iterations 1..16, sigmas > 0 and finite, normal_power_log2 <= 8, reserved 0)");
+    return HRT_OK;
+}
+
+// pass i's step and the constants of the stops that both filters have (DenoisePassArgs, DenoisePassVarArgs); false: one is not finite
+template <class PassArgs>
+bool shared_pass_constants(PassArgs &a, const HrtDenoiseParams &p, uint32_t i) {
+    a.step = 1u << i;
+    a.k_albedo = 1.0f / (p.sigma_albedo * p.sigma_albedo);
+    a.sigma_depth_step = p.sigma_depth * (float)a.step;
+    a.normal_squarings = p.normal_power_log2;
+    return positive_finite(a.k_albedo) && positive_finite(a.sigma_depth_step);
+}
+
+// ... and the constants of every pass
+int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, std::vector<DenoisePassArgs> &passes) {
+    HrtDenoiseParams p;
+    int rc = filter_params(ctx, h_dparams, p);
+    if (rc != HRT_OK) return rc;
     passes.assign(p.iterations, DenoisePassArgs{});
     for (uint32_t i = 0; i < p.iterations; ++i) {
         DenoisePassArgs &a = passes[i];
-        a.step = 1u << i;
         const float sc = std::ldexp(p.sigma_color, -(int)i);                          // sigma_color * 2^-i, exact above the subnormals
         a.k_color = 1.0f / (sc * sc);
-        a.k_albedo = 1.0f / (p.sigma_albedo * p.sigma_albedo);
-        a.sigma_depth_step = p.sigma_depth * (float)a.step;
-        a.normal_squarings = p.normal_power_log2;
-        if (!positive_finite(a.k_color) || !positive_finite(a.k_albedo) || !positive_finite(a.sigma_depth_step))
+        if (!shared_pass_constants(a, p, i) || !positive_finite(a.k_color))
             return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
     }
     return HRT_OK;
@@ -95,6 +122,51 @@ int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, float4
         src = dst;
     }
     if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
+}
+
+// the variance-guided mode's parameters (NULL: the defaults) and every pass's constants; sigma_color is not used by this mode beyond
+// filter_params' range check, the other fields of HrtDenoiseParams are
+int variance_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams,
+                       HrtDenoiseVarianceParams &vp, std::vector<DenoisePassVarArgs> &passes) {
+    HrtDenoiseParams p;
+    int rc = filter_params(ctx, h_dparams, p);
+    if (rc != HRT_OK) return rc;
+    hrt_denoise_variance_default_params(&vp);
+    if (h_vparams) vp = *h_vparams;
+    const float k_luminance = vp.sigma_luminance * vp.sigma_luminance;
+    if (!positive_finite(vp.sigma_luminance) || !positive_finite(k_luminance) || vp.history_min < 1 || vp.history_min > 65536 ||
+        !positive_finite(vp.variance_floor) || vp.reserved != 0)
+        return fail(ctx, HRT_ERR_INVALID, "variance denoise parameters out of range (sigma_luminance > 0 with a finite, non-zero square, history_min 1..65536, variance_floor > 0 and finite, reserved 0)");
+    passes.assign(p.iterations, DenoisePassVarArgs{});
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        DenoisePassVarArgs &a = passes[i];
+        a.k_luminance = k_luminance; a.variance_floor = vp.variance_floor;
+        if (!shared_pass_constants(a, p, i))
+            return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
+    }
+    return HRT_OK;
+}
+
+// run_filter with a variance frame alongside: the last pass writes `out` and, if given, `var_out`, by run_filter's rule each
+int run_filter_variance(HrtContext *ctx, const float4 *color, const uint4 *guides, const float *variance, float4 *out, float *var_out,
+                        uint32_t width, uint32_t height, std::vector<DenoisePassVarArgs> &passes, hipStream_t s) {
+    int rc = ensure_variance_work(ctx, width * height);
+    if (rc != HRT_OK) return rc;
+    const float4 *src = color;
+    const float *vsrc = variance;
+    const size_t n = passes.size();
+    for (size_t i = 0; i < n; ++i) {
+        DenoisePassVarArgs &a = passes[i];
+        float4 *dst = i + 1 < n || out == src ? ctx->denoise.frame[i & 1] : out;
+        float *vdst = i + 1 < n || !var_out || var_out == vsrc ? ctx->denoise.var[i & 1] : var_out;
+        a.src = src; a.var_src = vsrc; a.guides = guides; a.dst = dst; a.var_dst = vdst; a.width = width; a.height = height;
+        launch_denoise_pass_var(a, s);
+        src = dst; vsrc = vdst;
+    }
+    if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
+    if (var_out && vsrc != var_out) HIP_TRY(ctx, hipMemcpyAsync(var_out, vsrc, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
     HIP_TRY(ctx, hipGetLastError());
     return HRT_OK;
 }
@@ -136,8 +208,8 @@ int temporal_constants(HrtContext *ctx, const HrtDenoiseTemporalParams *h_tparam
     return HRT_OK;
 }
 
-// the history's arrays for n pixels and n_inst instances; a new size forgets the history
-int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst) {
+// the history's arrays for n pixels and n_inst instances; a new size forgets the history.  moments: the variance-guided mode's arrays too
+int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst, bool moments) {
     DenoiseHistory &h = ctx->denoise_history;
     if (h.pixels != n) {
         free_denoise_history(ctx);
@@ -150,6 +222,11 @@ int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst) {
         HIP_TRY(ctx, hipMalloc((void **)&h.motion, sizeof(float2) * (size_t)n));
         h.pixels = n;
     }
+    if (moments && !h.variance) {
+        for (DenoiseHistorySet &s : h.set)
+            if (!s.moments) HIP_TRY(ctx, hipMalloc((void **)&s.moments, sizeof(float2) * (size_t)n));
+        HIP_TRY(ctx, hipMalloc((void **)&h.variance, sizeof(float) * (size_t)n));
+    }
     const uint32_t need = std::max(n_inst, 1u);
     if (need > h.xf_capacity) {
         h.valid = false;
@@ -160,6 +237,47 @@ int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst) {
         }
         h.xf_capacity = need;
     }
+    return HRT_OK;
+}
+
+// what the temporal and the variance-guided mode share: the guides of the frame into the history set this call writes, the reprojection
+// and blend (with the luminance moments in the variance-guided mode), the object -> world table and camera kept for the next call.
+// Leaves the history invalid and h.set[h.cur] the set just written: the caller enqueues its filter, then sets h.valid.
+int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseTemporalParams &tp,
+                 DenoiseHistory::Mode mode, hipStream_t s) {
+    const uint32_t width = h_raygen->width, height = h_raygen->height, n = width * height;
+    const bool moments = mode == DenoiseHistory::kVariance;
+    Tlas *t;
+    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
+      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
+      t = it->second.get(); }
+    int rc = ensure_history(ctx, n, t->n_instances, moments);
+    if (rc != HRT_OK) return rc;
+    DenoiseHistory &h = ctx->denoise_history;
+    const bool has_history = h.valid && h.mode == mode && h.tlas == h_params->handle && h.width == width && h.height == height && h.n_instances == t->n_instances;
+    const DenoiseHistorySet &prev = h.set[h.cur];
+    DenoiseHistorySet &next = h.set[h.cur ^ 1u];
+    rc = run_guides(ctx, h_params, h_raygen, next.guides, s);
+    if (rc != HRT_OK) return rc;
+    const DenoiseWork &d = ctx->denoise;
+    DenoiseTemporalArgs ta{};
+    ta.rays = d.rays; ta.tuvp = d.tuvp; ta.inst = d.inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
+    ta.inst_inv = t->dev.d_inst_inv; ta.prev_xf = prev.xf;
+    ta.prev_accum = prev.accum; ta.prev_length = prev.length; ta.prev_guides = prev.guides; ta.prev_id = prev.id;
+    ta.accum = next.accum; ta.length = next.length; ta.id = next.id; ta.motion = h.motion;
+    ta.width = width; ta.height = height; ta.has_history = has_history ? 1u : 0u;
+    std::memcpy(ta.prev_center, prev.center, 12); std::memcpy(ta.prev_U, prev.U, 12); std::memcpy(ta.prev_V, prev.V, 12); std::memcpy(ta.prev_W, prev.W, 12);
+    ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
+    if (moments) { ta.prev_moments = prev.moments; ta.moments = next.moments; }
+    launch_denoise_temporal(ta, s);
+    HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->dev.d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
+    std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
+    std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
+    h.cur ^= 1u;
+    h.valid = false;                  // (until the caller has enqueued the filter as well)
+    h.mode = mode;
+    h.called = true;
+    h.tlas = h_params->handle; h.width = width; h.height = height; h.n_instances = t->n_instances;
     return HRT_OK;
 }
 
@@ -223,43 +341,18 @@ int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params
     if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
     if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
-    const uint32_t width = h_raygen->width, height = h_raygen->height, n = width * height;
+    const uint32_t width = h_raygen->width, height = h_raygen->height;
     int rc = check_frame(ctx, width, height);
     std::vector<DenoisePassArgs> passes;
     HrtDenoiseTemporalParams tp;
     if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
     if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
     if (rc != HRT_OK) return rc;
-    Tlas *t;
-    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
-      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
-      t = it->second.get(); }
-    rc = ensure_history(ctx, n, t->n_instances);
-    if (rc != HRT_OK) return rc;
-    DenoiseHistory &h = ctx->denoise_history;
-    const bool has_history = h.valid && h.tlas == h_params->handle && h.width == width && h.height == height && h.n_instances == t->n_instances;
-    const DenoiseHistorySet &prev = h.set[h.cur];
-    DenoiseHistorySet &next = h.set[h.cur ^ 1u];
     const hipStream_t s = (hipStream_t)stream;
-    rc = run_guides(ctx, h_params, h_raygen, next.guides, s);
+    DenoiseHistory &h = ctx->denoise_history;
+    rc = run_temporal(ctx, h_params, h_raygen, tp, DenoiseHistory::kTemporal, s);
     if (rc != HRT_OK) return rc;
-    const DenoiseWork &d = ctx->denoise;
-    DenoiseTemporalArgs ta{};
-    ta.rays = d.rays; ta.tuvp = d.tuvp; ta.inst = d.inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
-    ta.inst_inv = t->dev.d_inst_inv; ta.prev_xf = prev.xf;
-    ta.prev_accum = prev.accum; ta.prev_length = prev.length; ta.prev_guides = prev.guides; ta.prev_id = prev.id;
-    ta.accum = next.accum; ta.length = next.length; ta.id = next.id; ta.motion = h.motion;
-    ta.width = width; ta.height = height; ta.has_history = has_history ? 1u : 0u;
-    std::memcpy(ta.prev_center, prev.center, 12); std::memcpy(ta.prev_U, prev.U, 12); std::memcpy(ta.prev_V, prev.V, 12); std::memcpy(ta.prev_W, prev.W, 12);
-    ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
-    launch_denoise_temporal(ta, s);
-    HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->dev.d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
-    std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
-    std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
-    h.cur ^= 1u;
-    h.valid = false;                  // (until the filter is enqueued as well)
-    h.called = true;
-    h.tlas = h_params->handle; h.width = width; h.height = height; h.n_instances = t->n_instances;
+    const DenoiseHistorySet &next = h.set[h.cur];
     rc = run_filter(ctx, next.accum, next.guides, reinterpret_cast<float4 *>(d_out), width, height, passes, s);
     if (rc != HRT_OK) return rc;
     h.valid = true;
@@ -283,6 +376,70 @@ int hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float 
     if (d_accum) HIP_TRY(ctx, hipMemcpyAsync(d_accum, last.accum, sizeof(float4) * n, hipMemcpyDeviceToDevice, s));
     if (d_length) HIP_TRY(ctx, hipMemcpyAsync(d_length, last.length, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     if (d_motion) HIP_TRY(ctx, hipMemcpyAsync(d_motion, h.motion, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+    return HRT_OK;
+}
+
+int hrt_denoise_variance_default_params(HrtDenoiseVarianceParams *out) {
+    if (!out) return HRT_ERR_INVALID;
+    // (profiles/r12_denoise_variance.txt: the four-case sweep that picks sigma_luminance 4.0 and history_min 4)
+    *out = HrtDenoiseVarianceParams{4.0f, 4u, 1e-6f, 0u};
+    return HRT_OK;
+}
+
+int hrt_denoise_filter_variance(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDenoiseGuide *d_guides, const float *d_variance,
+                                HrtFloat4 *d_out, float *d_var_out, uint32_t width, uint32_t height, const HrtDenoiseParams *h_dparams,
+                                const HrtDenoiseVarianceParams *h_vparams, void *stream) {
+    if (!ctx || !d_color || !d_guides || !d_variance || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    int rc = check_frame(ctx, width, height);
+    std::vector<DenoisePassVarArgs> passes;
+    HrtDenoiseVarianceParams vp;
+    if (rc == HRT_OK) rc = variance_constants(ctx, h_dparams, h_vparams, vp, passes);
+    if (rc != HRT_OK) return rc;
+    return run_filter_variance(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), d_variance,
+                               reinterpret_cast<float4 *>(d_out), d_var_out, width, height, passes, (hipStream_t)stream);
+}
+
+int hrt_denoise_variance_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
+                                const HrtDenoiseTemporalParams *h_tparams, const HrtDenoiseVarianceParams *h_vparams, HrtFloat4 *d_out,
+                                void *stream) {
+    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    const uint32_t width = h_raygen->width, height = h_raygen->height;
+    int rc = check_frame(ctx, width, height);
+    std::vector<DenoisePassVarArgs> passes;
+    HrtDenoiseTemporalParams tp;
+    HrtDenoiseVarianceParams vp;
+    if (rc == HRT_OK) rc = variance_constants(ctx, h_dparams, h_vparams, vp, passes);
+    if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
+    if (rc != HRT_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    DenoiseHistory &h = ctx->denoise_history;
+    rc = run_temporal(ctx, h_params, h_raygen, tp, DenoiseHistory::kVariance, s);
+    if (rc != HRT_OK) return rc;
+    const DenoiseHistorySet &next = h.set[h.cur];
+    DenoiseVarianceArgs va{};
+    va.moments = next.moments; va.length = next.length; va.id = next.id; va.variance = h.variance;
+    va.width = width; va.height = height; va.history_min = (float)vp.history_min;
+    launch_denoise_variance(va, s);
+    h.variance_called = true;
+    h.variance_set = h.cur;
+    rc = run_filter_variance(ctx, next.accum, next.guides, h.variance, reinterpret_cast<float4 *>(d_out), nullptr, width, height, passes, s);
+    if (rc != HRT_OK) return rc;
+    h.valid = true;
+    return HRT_OK;
+}
+
+int hrt_debug_denoise_variance_state(HrtContext *ctx, float *d_moments, float *d_variance, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    const DenoiseHistory &h = ctx->denoise_history;
+    if (!h.variance_called) return fail(ctx, HRT_ERR_STATE, "hrt_denoise_variance_launch has not been called");
+    const hipStream_t s = (hipStream_t)stream;
+    const size_t n = h.pixels;
+    if (d_moments) HIP_TRY(ctx, hipMemcpyAsync(d_moments, h.set[h.variance_set].moments, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+    if (d_variance) HIP_TRY(ctx, hipMemcpyAsync(d_variance, h.variance, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
     return HRT_OK;
 }
 

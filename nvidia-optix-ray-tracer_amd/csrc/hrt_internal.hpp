@@ -140,12 +140,13 @@ struct Workspace {
 };
 
 // the denoiser's working memory (hrt_denoise.cpp), grown on demand: the guide pass's rays and hit records, the guides of hrt_denoise_launch,
-// the filter's two ping-pong frames
+// the filter's two ping-pong frames, the variance-guided filter's two variance frames
 struct DenoiseWork {
     uint32_t capacity = 0;                  // pixels each of the per-pixel arrays below holds
     RayRec *rays = nullptr; float4 *tuvp = nullptr; uint32_t *inst = nullptr;
     uint4 *guides = nullptr;
     float4 *frame[2] = {nullptr, nullptr};
+    float *var[2] = {nullptr, nullptr};
     uint32_t *fetch = nullptr;              // 8 x 32 slice counters of the traversal
 };
 
@@ -153,6 +154,7 @@ struct DenoiseWork {
 // accumulated colour, the history length, the guides and (instance, primitive) of every pixel, the object -> world table and the camera
 struct DenoiseHistorySet {
     float4 *accum = nullptr; float *length = nullptr; uint4 *guides = nullptr; uint2 *id = nullptr;
+    float2 *moments = nullptr;              // the variance-guided mode's (m1, m2), allocated by its first call
     float *xf = nullptr;
     float center[3], U[3], V[3], W[3];
 };
@@ -163,6 +165,11 @@ struct DenoiseHistory {
     uint32_t cur = 0;                       // set[cur] is the last call's; a call writes set[cur ^ 1], then flips cur
     bool valid = false;                     // a history to blend with exists
     bool called = false;                    // the intermediates of a call exist (hrt_debug_denoise_temporal_state)
+    enum Mode : uint32_t { kNone = 0, kTemporal, kVariance };
+    Mode mode = kNone;                      // whose history it is: a call of the other mode starts afresh
+    float *variance = nullptr;              // the variance-guided mode: what k_denoise_variance wrote and the filter took
+    bool variance_called = false;           // hrt_debug_denoise_variance_state: set[variance_set].moments and `variance` are a call's
+    uint32_t variance_set = 0;
     uint64_t tlas = 0; uint32_t width = 0, height = 0, n_instances = 0;     // what it was made for
 };
 

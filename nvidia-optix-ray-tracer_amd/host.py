@@ -370,6 +370,65 @@ class Renderer:
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return acc, length, motion
 
+    def _denoise_variance_params(self, vparams):
+        from . import DenoiseVarianceParams
+        if vparams is None:
+            return None
+        if isinstance(vparams, DenoiseVarianceParams):
+            return vparams
+        p = DenoiseVarianceParams()
+        self._check(self.lib.hrt_denoise_variance_default_params(C.byref(p)), "hrt_denoise_variance_default_params")
+        for k, v in dict(vparams).items():
+            setattr(p, k, v)
+        return p
+
+    def denoise_filter_variance(self, color, guides, variance, params=None, vparams=None, out=None, var_out=None):
+        """The variance-guided filter alone: ``color`` (H, W, 4) float32, ``guides`` (H, W, 8) 16-bit and ``variance`` (H, W) float32
+        device tensors -> (colour, variance): new tensors, or ``out`` (may be ``color``) and ``var_out`` (may be ``variance``;
+        False: the filtered variance is not returned).  vparams: None, a DenoiseVarianceParams or a dict of its fields."""
+        torch = self._torch
+        h, w = int(color.shape[0]), int(color.shape[1])
+        assert color.is_contiguous() and guides.is_contiguous() and tuple(guides.shape) == (h, w, 8) and guides.element_size() == 2
+        assert variance.is_contiguous() and tuple(variance.shape) == (h, w) and variance.dtype == torch.float32
+        out = torch.empty_like(color) if out is None else out
+        if var_out is None:
+            var_out = torch.empty_like(variance)
+        p, vp = self._denoise_params(params), self._denoise_variance_params(vparams)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_filter_variance(self.ctx, color.data_ptr(), guides.data_ptr(), variance.data_ptr(), out.data_ptr(),
+                                                         var_out.data_ptr() if var_out is not False else None, w, h,
+                                                         C.byref(p) if p is not None else None, C.byref(vp) if vp is not None else None, st),
+                    "hrt_denoise_filter_variance")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return out, (var_out if var_out is not False else None)
+
+    def denoise_variance(self, params=None, tparams=None, vparams=None, out=None):
+        """The variance-guided mode of denoiseOutput: denoise_temporal's reprojection and blend, with the luminance moments carried
+        along, and a filter whose colour edge stop follows the accumulated frame's variance -> a new (H, W, 4) float32 tensor, or
+        ``out`` (which may be ``self.color``).  Shares its history with denoise_temporal: a call after the other mode starts afresh."""
+        params_blk, rg = self._launch_blocks()
+        out = self._torch.empty_like(self.color) if out is None else out
+        p, tp, vp = self._denoise_params(params), self._denoise_temporal_params(tparams), self._denoise_variance_params(vparams)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_variance_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
+                                                         C.byref(tp) if tp is not None else None, C.byref(vp) if vp is not None else None,
+                                                         out.data_ptr(), st), "hrt_denoise_variance_launch")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        self._temporal_shape = (self.height, self.width)
+        return out
+
+    def denoise_variance_state(self):
+        """The last denoise_variance's luminance moments (H, W, 2) and the variance its filter took (H, W), float32 device tensors."""
+        torch = self._torch
+        h, w = getattr(self, "_temporal_shape", (self.height, self.width))
+        moments = torch.empty((h, w, 2), dtype=torch.float32, device=self.device)
+        variance = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        st = self._stream()
+        self._check(self.lib.hrt_debug_denoise_variance_state(self.ctx, moments.data_ptr(), variance.data_ptr(), st),
+                    "hrt_debug_denoise_variance_state")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return moments, variance
+
     def to_rgba8_of(self, frame):
         """convertFloat4ToUchar4Kernel of any (H, W, 4) float32 device tensor (to_rgba8: of the colour buffer)."""
         torch = self._torch

@@ -1,11 +1,13 @@
 """What the denoiser costs at 1080p next to the 1-spp frame it cleans: C4 (bench.py's scene) and the shipped sample (tests/golden/files,
 first frame of Time mode).  Per scene: a 1-spp render, hrt_denoise_guides, hrt_denoise_filter and hrt_denoise_launch, each the median
-of --reps timed repetitions (HIP events around the call, after a warm-up).  Under `rocprofv3 --kernel-trace --stats` the per-kernel
+of --reps timed repetitions (HIP events around the Renderer method, after a warm-up: the figure includes the method's argument checks
+and its hrt_sync, so it is a whole-call time, not a sum of kernel times).  Under `rocprofv3 --kernel-trace --stats` the per-kernel
 split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_denoise_pass (one launch per filter pass).
 --temporal adds hrt_denoise_temporal_launch (the frame repeated, so that every call after the first blends with a history): its own
-kernel is k_denoise_temporal.
+kernel is k_denoise_temporal.  --variance adds hrt_denoise_variance_launch in the same way (k_denoise_temporal<true>,
+k_denoise_variance, k_denoise_pass_var) and hrt_denoise_filter_variance over the frame's guides and a constant variance.
 
-    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal]
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal] [--variance]
 """
 from __future__ import annotations
 
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scenes", default="c4,sample")
     ap.add_argument("--temporal", action="store_true")
+    ap.add_argument("--variance", action="store_true")
     args = ap.parse_args()
     import torch
     hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
@@ -57,6 +60,8 @@ def main():
             r.pose_instances(tm["states"][0], tm["states"][min(1, len(tm["states"]) - 1)], float(tm["durations"][0]), 0,
                              tm["frame_counts"][0], first_instance=tm["n_extra"], offset=cfg["particle-shift"], scale=cfg["particle-scale"])
         out = torch.empty_like(r.color)
+        dp = hrt.DenoiseParams()
+        r.lib.hrt_denoise_default_params(dp)
         r.render(1)
         guides = r.denoise_guides()
         r.denoise_filter(r.color, guides, out=out)
@@ -66,10 +71,19 @@ def main():
                "guides_ms": median_ms(torch, r.denoise_guides, args.reps),
                "filter_ms": median_ms(torch, lambda: r.denoise_filter(r.color, guides, out=out), args.reps),
                "denoise_launch_ms": median_ms(torch, lambda: r.denoise(out=out), args.reps)}
-        res["filter_per_pass_ms"] = res["filter_ms"] / 5
+        res["filter_per_pass_ms"] = res["filter_ms"] / dp.iterations
         if args.temporal:
             r.denoise_temporal(out=out)
             res["denoise_temporal_ms"] = median_ms(torch, lambda: r.denoise_temporal(out=out), args.reps)
+        if args.variance:
+            var = torch.full((h, w), 1e-3, dtype=torch.float32, device=r.device)
+            var_out = torch.empty_like(var)
+            r.denoise_temporal_reset()
+            r.denoise_variance(out=out)
+            res["denoise_variance_ms"] = median_ms(torch, lambda: r.denoise_variance(out=out), args.reps)
+            r.denoise_filter_variance(r.color, guides, var, out=out, var_out=var_out)
+            res["filter_variance_ms"] = median_ms(torch, lambda: r.denoise_filter_variance(r.color, guides, var, out=out, var_out=var_out), args.reps)
+            res["filter_variance_per_pass_ms"] = res["filter_variance_ms"] / dp.iterations
         print(json.dumps(res), flush=True)
         r.close()
 
