@@ -307,6 +307,10 @@ typedef struct HrtStats {
                                               fit k_fused (deeper than 12 levels, or node / record arrays beyond 4 GiB = 32-bit byte offsets) */
     uint64_t graph_replays;                /* wavefront mode: sample pairs replayed from a captured hipGraph since the context was created */
     uint64_t bvh_alloc_bytes;              /* device memory the TLAS last launched holds for nodes, node boxes and records (bvh_bytes: the packed payload) */
+    uint64_t sample_block_launches;        /* path-kernel launches since the context was created that handed pixels out in sample blocks (HRT_SAMPLE_BLOCK) */
+    uint64_t tail[8];                      /* instrumented build only (make stats, tools/tail_profile.py): the path kernel's drained phase --
+                                              wave iterations, alive lanes over them, clock base, ~first drained clock, last exit clock,
+                                              sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
 } HrtStats;
 
 int  hrt_stats_reset(HrtContext *ctx);

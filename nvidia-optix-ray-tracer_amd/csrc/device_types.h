@@ -70,6 +70,13 @@ struct PathArgs {
     const RayRec *trace_rays;      // fused kernel as hrt_trace_rays: the "pixels" are these rays, traced once; results below (else NULL)
     float4 *trace_tuvp; uint32_t *trace_inst; uint32_t trace_any;
     float4 *primary_cache;         // k_fused<.., REUSE>: two float4 per lane of the grid, the primary hit of the lane's pixel (else NULL)
+    // sample blocks (path_lane.h; k_fused's one-level instantiations without REUSE): 0 = a lane keeps its pixel for all samples of the launch
+    uint32_t sample_block;         // K: samples a lane takes of a pixel before it gives it back
+    uint32_t block_magic;          // min(2^32 / K, 2^32 - 1): path_finish's test for a multiple of K (0 with K = 0)
+    uint32_t block_slices;         // slices of the tile
+    uint32_t block_slices_magic, block_chunk_magic;   // min(2^32 / d, 2^32 - 1) for d = block_slices, fetch_chunk (path_lane.h: div_magic)
+    uint32_t block_items;          // passes x slices: what the slice counters hand out (x fetch_chunk below 2^32)
+    uint32_t *block_progress;      // per slice: blocks ended by its pixels, zeroed before the launch
 };
 
 struct TraverseArgs {
@@ -256,6 +263,7 @@ void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t
 void launch_generate(const GenerateArgs &a, hipStream_t s);
 void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
 void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // round 1's fused kernel k_traverse<.., FUSED>: trees k_fused cannot take
+constexpr int kSampleBlockAuto = 32;   // HRT_SAMPLE_BLOCK=auto: samples per block (profiles/r13_sample_blocks.txt)
 constexpr int kFusedBlocksPerCu = 16;  // k_fused is compiled for 4 waves per SIMD (125 VGPRs, nothing spilled): more workgroups per CU would only queue
 constexpr int kFusedInstancedBlocksPerCu = 12;   // k_fused<.., INSTANCED> is compiled for 3 waves per SIMD (fused.hip)
 constexpr uint32_t kFetchShards = 8;         // slice counters (one per XCD-group of blocks)

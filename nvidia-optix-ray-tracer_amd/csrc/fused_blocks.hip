@@ -1,0 +1,21 @@
+// fused_blocks.hip -- k_path_blocks: the persistent path kernel (fused_body.h) handing pixels out in sample blocks (path_lane.h; DESIGN.md
+// section 2.1).  A kernel and a translation unit of its own: the hand-over costs the regeneration a dozen spilled registers, which k_fused
+// (fused.hip) -- whose registers, spills and loop tests/test_host_cpu.py pins -- need not pay.  One-level trees, no primary-hit cache.
+#include "fused_body.h"
+
+#pragma clang fp contract(off)
+
+namespace hrt {
+
+template <bool HAS_SPHERES>
+__global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_path_blocks(TraverseArgs a) {
+    fused_body<HAS_SPHERES, false, false, true>(a);
+}
+
+void launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
+    const dim3 g(grid_blocks), b(kTraverseBlock);
+    if (has_spheres) hipLaunchKernelGGL((k_path_blocks<true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_path_blocks<false>), g, b, 0, s, a);
+}
+
+}  // namespace hrt

@@ -1,0 +1,251 @@
+// fused_body.h -- the body of the persistent path kernel, ONCE, for the kernels that run it: k_fused (fused.hip) and k_path_blocks
+// (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h).  What the body does is described at the top of fused.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+#include "device_types.h"
+#include "trav_common.h"
+#include "trav_loop.h"
+#include "path_lane.h"
+
+#pragma clang fp contract(off)
+
+namespace hrt {
+
+#ifndef HRT_SPHERE_CULL
+#define HRT_SPHERE_CULL 1     // INSTANCED: a ray that misses an instance's bounding sphere does not enter it (0: enters every instance whose box it crosses)
+#endif
+// INSTANCED: the tree has two levels (bvh8.h: transform nodes; the reference's IAS over shared GASes, RendererImpl.cu:174-206).  A lane
+// whose next node turns out to be a transform node leaves its world ray in LDS, goes on with the ray in the instance's object space
+// (row-major 3x4 inverse from the node; identity: copied) and the BLAS's root as the only child; its node stack continues ABOVE what it
+// held (`base` = the frame's bottom), so the bookkeeping sequence is the one-level kernel's, unchanged.  When it reports the frame
+// empty the lane takes its world ray back and pops what it had left in world space.  A separate instantiation: the one-level kernels
+// and their register budget are untouched.
+struct InstLane {
+    // the instance whose BLAS this lane is in (kNoWork: none), and what its node stack looked like when it went in (base | entries << 8)
+    uint32_t inst_cur = kNoWork, frame = 0u;
+    // the rest of a world ray that waits in LDS while its lane is inside an instance (reciprocals, octant); origin and direction wait in
+    // the mailboxes' memory: tail splitting is off for two-level trees
+    float *park_idx, *park_idy, *park_idz;
+    uint32_t *park_oct;
+
+    // after the node loads: lanes whose node is a transform node (`enter`) go on in the instance's object space, with the BLAS's root as
+    // the only child -- unless the ray misses the instance's bounding sphere (`enter` is withdrawn, the node has no children)
+    __device__ __forceinline__ bool enter_instance(bool enter, TravState &ls, uint2 &child, const u32x4 rn0, const u32x4 rn1, const u32x4 rn2, const u32x4 rn3,
+                                                   const u32x4 rn4, const Mailboxes &mb, uint32_t tx) {
+        if (__ballot(enter) != 0ull) {
+            float ox = ls.ox, oy = ls.oy, oz = ls.oz, dx = ls.dx, dy = ls.dy, dz = ls.dz;      // the ray in the instance's object space
+            if (enter) {
+                const TravState &s = ls;
+                if (rn1.z == 0u) {          // not the identity: xf_point / xf_vector of the oracle, operation for operation
+                    const float m0 = __uint_as_float(rn2.x), m1 = __uint_as_float(rn2.y), m2 = __uint_as_float(rn2.z), m3 = __uint_as_float(rn2.w);
+                    const float m4 = __uint_as_float(rn3.x), m5 = __uint_as_float(rn3.y), m6 = __uint_as_float(rn3.z), m7 = __uint_as_float(rn3.w);
+                    const float m8 = __uint_as_float(rn4.x), m9 = __uint_as_float(rn4.y), m10 = __uint_as_float(rn4.z), m11 = __uint_as_float(rn4.w);
+                    ox = ((m0 * s.ox + m1 * s.oy) + m2 * s.oz) + m3; oy = ((m4 * s.ox + m5 * s.oy) + m6 * s.oz) + m7; oz = ((m8 * s.ox + m9 * s.oy) + m10 * s.oz) + m11;
+                    dx = (m0 * s.dx + m1 * s.dy) + m2 * s.dz; dy = (m4 * s.dx + m5 * s.dy) + m6 * s.dz; dz = (m8 * s.dx + m9 * s.dy) + m10 * s.dz;
+                }
+                // The object-space ray against the BLAS's bounding sphere (words 0-2: centre, word 7: radius, negative: none) -- the
+                // instance's box in the top level is the box of that sphere under a rotation nobody knows in advance, and half the rays
+                // that cross such a box miss the sphere.  Culling only, with slack for the rounding of every term: misses the line of
+                // the ray by more than the radius, or starts outside and points away.
+                const float R = __uint_as_float(rn1.w);
+                const float cx = ox - __uint_as_float(rn0.x), cy = oy - __uint_as_float(rn0.y), cz = oz - __uint_as_float(rn0.z);
+                const float cc = fmaf(cx, cx, fmaf(cy, cy, cz * cz)), aa = fmaf(dx, dx, fmaf(dy, dy, dz * dz)), b = fmaf(cx, dx, fmaf(cy, dy, cz * dz));
+                const float R2 = R * R * 1.0001f, ca = cc * aa;
+                // (branch-free on purpose, & and | instead of && and ||: with a branch on R >= 0 inside this block hipcc 7.2 carries child.x and
+                // inst_cur of the block below through the registers it also uses for cc and b here, and the lanes that took the branch
+                // entered node 0 instead of their BLAS, for ever -- found in the ISA, tools/debug_two_level.py)
+                const bool beside = fmaf(-b, b, ca) > fmaf(R2, aa, 4e-6f * ca), behind = (b > 0.0f) & (cc > fmaf(4e-6f, cc, R2));
+                if (HRT_SPHERE_CULL && ((R >= 0.0f) & (beside | behind))) enter = false;
+            }
+            if (enter) {
+                TravState &s = ls;
+                mb.t[tx] = s.ox; mb.u[tx] = s.oy; mb.v[tx] = s.oz;
+                mb.prim[tx] = __float_as_uint(s.dx); mb.inst[tx] = __float_as_uint(s.dy); mb.pending[tx] = __float_as_uint(s.dz);
+                park_idx[tx] = s.idx; park_idy[tx] = s.idy; park_idz[tx] = s.idz; park_oct[tx] = s.oct_inv4;
+                inst_cur = rn1.y;
+                s.ox = ox; s.oy = oy; s.oz = oz; s.dx = dx; s.dy = dy; s.dz = dz;
+                s.idx = safe_rcp_dir<false>(dx); s.idy = safe_rcp_dir<false>(dy); s.idz = safe_rcp_dir<false>(dz);
+                const uint32_t oct = (dx < 0.0f ? 4u : 0u) | (dy < 0.0f ? 2u : 0u) | (dz < 0.0f ? 1u : 0u);
+                s.oct_inv4 = (7u - oct) * 0x01010101u;
+                child = make_uint2(rn1.x, 0x01000000u);      // one child, no inner-mask bits: the pick below is child base + 0 = the BLAS's root
+            }
+        }
+        return enter;
+    }
+    // after the bookkeeping: frames begin and end
+    __device__ __forceinline__ bool switch_frames(bool enter, bool done, bool hit_any, LeanLane &L, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], uint32_t tx, uint32_t lane) {
+        // in: the frame starts above what the lane holds (siblings still in hand have just been pushed, step 2 of the sequence)
+        if (enter) { frame = (uint32_t)L.base | ((uint32_t)L.nsp << 8); L.base = L.nsp; }
+        // out: the frame is empty -- nothing in hand, on the node stack above `base`, or in the leaf stack -- but the ray is not done
+        const bool leave = done && !hit_any && inst_cur != kNoWork;
+        if (__ballot(leave) != 0ull) {
+            if (leave) {
+                TravState &s = L.s;
+                s.ox = mb.t[tx]; s.oy = mb.u[tx]; s.oz = mb.v[tx];
+                s.dx = __uint_as_float(mb.prim[tx]); s.dy = __uint_as_float(mb.inst[tx]); s.dz = __uint_as_float(mb.pending[tx]);
+                s.idx = park_idx[tx]; s.idy = park_idy[tx]; s.idz = park_idz[tx]; s.oct_inv4 = park_oct[tx];
+                inst_cur = kNoWork;
+                L.base = (int)(frame & 0xffu); L.nsp = (int)(frame >> 8);
+                if (L.nsp != L.base) { --L.nsp; s.cur = nodes[L.nsp][lane]; }      // (only groups with hits are ever pushed)
+                if (s.cur.y > 0x00ffffffu) { lean_pick_node(L); done = false; }
+            }
+        }
+        return done;
+    }
+};
+
+// REUSE (HRT_CTX_REUSE_PRIMARY): the reference's raygen has no pixel jitter (Shader.cu:249-261), so the primary ray of a pixel -- and its
+// hit -- is the same for every sample.  The first sample a launch takes of a pixel traces it and leaves the hit record in the lane's slot of
+// `primary_cache`; the later ones are shaded from there (same record, same shading, same random numbers: the same bits) and only their
+// bounces are traversed.  Rays that are not traversed are not counted.  A separate instantiation, like INSTANCED.
+#ifndef HRT_FUSED_WAVES_PER_SIMD
+#define HRT_FUSED_WAVES_PER_SIMD 4      // 128 VGPRs, a dozen kernel constants spilled; 5 waves (96 VGPRs, 95 spilled around the shading): 2560 against 3122 Mrays/s
+#endif
+#ifndef HRT_INST_WAVES_PER_SIMD
+#define HRT_INST_WAVES_PER_SIMD 3       // the INSTANCED instantiation: 160 VGPRs, nothing spilled, 12 waves per CU (at 4 waves per SIMD it spills 47 registers around
+                                        // the shading: 2 % slower on both particle clouds, profiles/r04_two_level_sweep.txt)
+#endif
+// The kernel's body: k_fused below, and -- BLOCKS -- k_path_blocks, which hands pixels out in sample blocks (path_lane.h).  A kernel of its own
+// because the hand-over costs the regeneration a dozen spilled registers more, which the launches without blocks need not pay.
+template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS>
+__device__ __forceinline__ void fused_body(const TraverseArgs &a) {
+    static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    __shared__ uint2 s_nodes[kNodeStackLds][kTraverseBlock];     // sibling groups: one per tree level (hrt_api.cpp sends deeper trees to k_traverse)
+    __shared__ uint2 s_leaves[kLeafStackLds][kTraverseBlock];    // leaf groups
+    // tail splitting: one mailbox per lane that owns a split ray (indexed by its home lane) collects the pieces' hits
+    __shared__ float s_mb_t[kTraverseBlock], s_mb_u[kTraverseBlock], s_mb_v[kTraverseBlock];
+    __shared__ uint32_t s_mb_prim[kTraverseBlock], s_mb_inst[kTraverseBlock], s_mb_pending[kTraverseBlock];
+    __shared__ uint32_t s_pair[kTraverseBlock];
+    // INSTANCED: the rest of a world ray that waits while its lane is inside an instance (reciprocals, octant)
+    __shared__ float s_park_idx[kTraverseBlock], s_park_idy[kTraverseBlock], s_park_idz[kTraverseBlock];
+    __shared__ uint32_t s_park_oct[kTraverseBlock];
+
+    const uint32_t n_pixels = a.path.n_tile_pixels;
+    const char *__restrict__ node_bytes = reinterpret_cast<const char *>(a.nodes);
+    const char *__restrict__ prim_bytes = reinterpret_cast<const char *>(a.prims);
+    const float tmin = a.tmin, tmax_ray = a.tmax;
+    const uint32_t leaf_hold = a.leaf_hold >= 1 && a.leaf_hold <= 4 ? (uint32_t)a.leaf_hold : 4u;      // (a lane that could never take a node would never finish)
+    // the traversal loop ends once at least refill_threshold lanes are idle -- or all of them: at most max_alive lanes alive
+    const uint32_t max_alive = (uint32_t)a.refill_threshold >= 64u ? 0u : 64u - (uint32_t)a.refill_threshold;
+    const uint32_t tx = threadIdx.x;
+    const uint32_t ldsn = (uint32_t)reinterpret_cast<uintptr_t>(&s_nodes[0][tx]), ldsl = (uint32_t)reinterpret_cast<uintptr_t>(&s_leaves[0][tx]);
+
+    const Mailboxes mb{s_mb_t, s_mb_u, s_mb_v, s_mb_prim, s_mb_inst, s_mb_pending, s_pair};
+
+    std::conditional_t<INSTANCED, InstLane, NoInstLane> I;
+    if constexpr (INSTANCED) { I.park_idx = s_park_idx; I.park_idy = s_park_idy; I.park_idz = s_park_idz; I.park_oct = s_park_oct; }
+
+    LeanLane L;
+    lean_idle(L, tmax_ray);
+    LaneFlags F;                            // alive / waiting / any / shared: trav_loop.h
+    F.home = tx;
+    bool exhausted = false;                 // wave-uniform: no pixels left to start
+
+    PathLane P;                             // the lane's pixel: path_lane.h
+    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path
+    LaneStats stats;
+
+    // the wave's slice of the tile: [wbeg, wend); slices of fetch_chunk pixels are handed out by kFetchShards counters
+    uint32_t wbeg = 0, wend = 0, kstart = 0;
+    const uint32_t home_shard = blockIdx.x & (kFetchShards - 1);
+    static_assert(!BLOCKS || (!INSTANCED && !REUSE), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
+    [[maybe_unused]] BlockSlice B;                  // (BLOCKS) the item the wave holds
+
+    [[maybe_unused]] bool force_regen = false;      // (REUSE, wave-uniform)
+    [[maybe_unused]] bool cached = false;           // (REUSE) this lane waits to be shaded with its pixel's cached primary hit
+    for (;;) {
+        const uint64_t idle = __ballot(!F.alive);
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        // ---- regenerate: shade finished rays in place, start the next sample / pixel ----
+        // (once the tile is used up the lanes without a pixel stay idle and the render ends with the slowest pixels' sample chains:
+        // what counts then is how soon a finished ray's successor starts, against what a regeneration costs the rays still under
+        // way -- a dozen waiting rays, or nothing else left to do: 1/8 of the C4 frame 142 ms with 1, 129 ms with 8 to 16)
+        if (force_regen || idle == ~0ull || (exhausted ? (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
+            stats.regeneration();
+            __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
+            PathStep st;                            // st.launch: this lane starts the ray (st.ro, st.rd) below
+            [[maybe_unused]] bool reshade = false;
+            [[maybe_unused]] const bool was_forced = force_regen;
+            force_regen = false;
+            if (!F.alive && F.waiting) {
+                F.waiting = false;
+                const TravState &s = L.s;
+                // the finished ray and what it hit
+                V3 o = mk3(s.ox, s.oy, s.oz), d = mk3(s.dx, s.dy, s.dz);
+                float bt = s.bt, bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = s.binst;
+                if constexpr (REUSE) {
+                    float4 *slot = a.path.primary_cache + 2u * (blockIdx.x * kTraverseBlock + tx);
+                    if (cached) {                   // ... or, for a primary ray that was not traversed again, what the pixel's first sample found
+                        const float4 c0 = slot[0]; const float4 c1 = slot[1];
+                        o = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); d = mk3(P.px_pdx, P.px_pdy, P.px_pdz);
+                        bt = c0.x; bu = c0.y; bv = c0.z; bprim = __float_as_uint(c0.w); binst = __float_as_uint(c1.x);
+                        cached = false;
+                    } else if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // the primary hit of the pixel's first sample in this launch
+                        slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
+                    }
+                }
+                st = path_finish<HAS_SPHERES, REUSE, BLOCKS>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
+            }
+            exhausted = path_take<BLOCKS>(P, st, a, n_pixels, !F.alive && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
+            stats.drained(exhausted);
+            if (st.want_primary) {
+                bool from_cache = false;
+                if constexpr (REUSE) from_cache = !a.path.trace_rays && P.px_sample > 0u;
+                if (from_cache) {
+                    // a pixel's later primary rays are not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
+                    P.px_depth = 1u; F.waiting = true; cached = true; reshade = true;
+                } else {
+                    const PathRay r = path_primary<false>(P, a);
+                    st.ro = r.o; st.rd = r.d; st.launch = true;
+                }
+            }
+            if (st.launch) {
+                F.any = path_count_ray(P);
+                lean_start(L, st.ro, st.rd, tmax_ray);
+                if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
+                F.alive = true;
+            }
+            // REUSE: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that
+            // their bounces start together with the other lanes' rays (one extra round, not more: the others are waiting)
+            if constexpr (REUSE) { if (!was_forced && __ballot(reshade) != 0ull) { force_regen = true; continue; } }
+        }
+        // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, REUSE, a lane with a cached hit to shade:
+        // an empty pass through the loop below brings it back here)
+        if (__ballot(REUSE ? F.alive || F.waiting : F.alive) == 0ull) {
+            bool leave = true;
+            if constexpr (BLOCKS) leave = B.need == 0u;
+            if (leave) break;
+            // Sample blocks: the wave holds an item whose predecessor is still under way and has nothing else to do.  It must not leave
+            // (the item's pixels would never be rendered), so it looks again after a short sleep.  This cannot hang, PROVIDED every one of
+            // the kFetchShards counters is the home of a wave (grid >= kFetchShards: render_fused hands out blocks on no smaller grid).  The
+            // counters do not hand the items out in order of their numbers -- a wave stays with its home counter until that is drained --
+            // so "the predecessor was fetched before" is NOT what the argument rests on.  Suppose all waves were stuck, and let i be the
+            // lowest-numbered item whose pixels have not all ended their block; every item below i is done, i's predecessor among them.
+            //   i has been fetched: the wave that holds it finds it ready at its next look and its free lanes take i's pixels.
+            //   i has not: it is item c of counter s = i % kFetchShards; the items of s below it are done, hence fetched, so the counter
+            //     stands at c exactly.  A wave whose home is s has never found s drained, so whatever it has fetched came from s, is
+            //     numbered below i and is done: it holds nothing, its lanes are free, and its next regeneration fetches i.
+            // Either way some wave is not stuck (the grid is sized to what is resident; were it not, workgroups 0 to kFetchShards - 1, one
+            // home wave per counter, are the first to be).  (With fewer waves than counters the second case fails: the only wave of an 8 x 6 frame
+            // takes item 0, then item 8 of its home counter -- pass 2 of a slice whose passes 0 and 1 are items of counters nobody
+            // visits.)  An empty pass through the loop below brings the wave back to its regeneration: a `continue` here costs the
+            // kernel a hundred spilled registers.
+            __builtin_amdgcn_s_sleep(32);
+        }
+
+        // ---- traverse until enough lanes have finished to make a regeneration worthwhile: trav_loop.h; the copy with tail splitting
+        //      and the drained phase's exit rule runs once the tile is used up ----
+        if (exhausted) {
+            stats.tail_begin();
+            traverse_to_regen<HAS_SPHERES, INSTANCED, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+            stats.tail_end();
+        }
+        else traverse_to_regen<HAS_SPHERES, INSTANCED, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+    }
+    stats.report(a.path.rays_closest, tx);
+    path_report_rays(P, a, tx);
+}
+
+}  // namespace hrt

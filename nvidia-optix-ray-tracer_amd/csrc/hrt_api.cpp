@@ -171,7 +171,7 @@ int hrt_ctx_destroy(HrtContext *ctx) {
     free_denoise_work(ctx);
     free_denoise_history(ctx);
     if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
-    void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program};
+    void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.block_progress, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (const ScratchArena &a : ctx->scratch_free) (void)hipFree(a.p);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -416,7 +416,10 @@ static int render_fused(const LaunchFrame &f) {
     uint32_t done_spp = 0;
     const uint32_t n_slices = (n + ta.fetch_chunk - 1u) / ta.fetch_chunk;
     // Worth it when a lane gets only a few pixels (the tiles of the multi-GPU split: 1/4 of the C4 frame 238 -> 219 ms);
-    // a full frame has ~6 pixels per lane, a tail of a few percent, and keeps its single launch.
+    // a full frame has ~8 pixels per lane and keeps its single launch.  Its tail is not small either -- from the first wave that finds
+    // the tile used up to the end of the kernel is 22 % of the kernel's time on C4, and 9 % of the kernel's lane-slots stand idle in it, at 64
+    // spp as at 256 (tools/tail_profile.py, profiles/r13_sample_blocks.txt) -- but it is sample blocks, below, that shorten it.
+    bool lpt = false;
     if (ctx->fused_lpt && spp >= 16u && n_slices >= 4096u && (uint64_t)n < 4ull * 64ull * (uint64_t)grid) {
         if (n_slices > w.slice_capacity) {
             for (uint32_t *p : {w.slice_cost, w.slice_order}) if (p) (void)hipFree(p);
@@ -440,12 +443,41 @@ static int render_fused(const LaunchFrame &f) {
         HIP_TRY(ctx, hipMemcpyAsync(w.slice_order, ctx->h_slice_order.data(), sizeof(uint32_t) * n_slices, hipMemcpyHostToDevice, s));
         pa.slice_cost = nullptr; pa.slice_order = w.slice_order;
         done_spp = probe_spp;
+        lpt = true;
+    }
+    // Sample blocks (path_lane.h): a lane gives its pixel back after K samples and the slices go round pass by pass, so only the last K
+    // samples of a frame run in a draining GPU.  k_fused's one-level kernels without the primary-hit cache (which wants a pixel's samples in
+    // one lane) and without the cost order (which keeps precedence on the small tiles where it applies).  `auto`: only where an item's
+    // predecessor was handed out at least three fills of the machine before it -- the hand-over then never has to wait.
+    // Never, forced or not, on a grid of fewer waves than slice counters: a wave keeps an item that is not ready until it is, and takes
+    // from another counter only once its own is drained, so every counter needs a wave whose home it is -- otherwise the predecessor of
+    // a held item can sit behind a counter that nobody visits and the wave waits for ever (the argument: fused_body.h).
+    uint32_t K = 0;
+    if (pk.kernel == PathKernel::Fused && !pa.primary_cache && !lpt && ctx->sample_block != 0 && grid >= kFetchShards) {
+        if (ctx->sample_block > 0) K = (uint32_t)ctx->sample_block;
+        else if ((uint64_t)n_slices * ta.fetch_chunk >= 4ull * 64ull * (uint64_t)grid) K = (uint32_t)kSampleBlockAuto;
+    }
+    if (K != 0u && n_slices > w.block_capacity) {
+        if (w.block_progress) (void)hipFree(w.block_progress);
+        w.block_progress = nullptr; w.block_capacity = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.block_progress, sizeof(uint32_t) * n_slices));
+        w.block_capacity = n_slices;
     }
     // very long renders are cut into launches of at most fused_max_spp samples (a launch should stay in the
     // range of seconds); the RNG states and the running sums carry over, so the result is the same bits
     while (done_spp < spp) {
         const uint32_t now = std::min<uint32_t>(spp - done_spp, (uint32_t)ctx->fused_max_spp);
         pa.spp = now; pa.continue_sum = done_spp > 0 ? 1u : 0u;
+        // this launch in blocks: at least two of them (`auto`: two whole ones), and the counters' numbers, in pixels, within 32 bits
+        const uint64_t passes = K ? ((uint64_t)now + K - 1u) / K : 0u;
+        const bool blocks = passes >= 2u && (ctx->sample_block > 0 || now >= 2u * K) && passes * n_slices * ta.fetch_chunk < (1ull << 32);
+        auto magic = [](uint32_t d) { return d ? (uint32_t)std::min<uint64_t>((1ull << 32) / d, 0xffffffffull) : 0u; };      // (an empty tile has no slices)
+        pa.sample_block = blocks ? K : 0u; pa.block_magic = blocks ? magic(K) : 0u;
+        pa.block_slices = n_slices; pa.block_slices_magic = magic(n_slices); pa.block_chunk_magic = magic(ta.fetch_chunk); pa.block_items = blocks ? (uint32_t)(passes * n_slices) : 0u; pa.block_progress = blocks ? w.block_progress : nullptr;
+        if (blocks) {
+            HIP_TRY(ctx, hipMemsetAsync(w.block_progress, 0, sizeof(uint32_t) * n_slices, s));
+            ctx->sample_block_launches++;
+        }
         // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         ctx->fused_counters_clean = false;
@@ -766,6 +798,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->paths = ctx->paths; out->node_visits = ds.nodes_closest + ds.nodes_any; out->prim_tests = ds.prims_closest + ds.prims_any;
     out->node_visits_closest = ds.nodes_closest; out->prim_tests_closest = ds.prims_closest;
     for (int k = 0; k < 4; ++k) out->debug[k] = ds.debug[k];
+    for (int k = 0; k < 8; ++k) out->tail[k] = ds.tail[k];
     out->tlas_refits = ctx->tlas_refits; out->tlas_rebuilds = ctx->tlas_rebuilds; out->tlas_refit_ratio = ctx->tlas_refit_ratio;
     for (int k = 0; k < HRT_K_COUNT; ++k) { out->kernel_ms[k] = ctx->kernel_ms[k]; out->kernel_launches[k] = ctx->kernel_launches[k]; }
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -777,6 +810,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
         out->bvh_alloc_bytes = tl.alloc_bytes;
     }
     out->fused_fallback_launches = ctx->fused_fallback_launches; out->graph_replays = ctx->graph_replays;
+    out->sample_block_launches = ctx->sample_block_launches;
     return HRT_OK;
 }
 

@@ -118,7 +118,7 @@ struct Tlas {
 struct StageCounters { uint32_t bin_count[32]; uint32_t fetch[8 * 32]; };
 static_assert(sizeof(StageCounters) == 128 + 8 * 128, "stage counters layout");
 
-struct DeviceStats { uint64_t rays_closest, rays_any, nodes_closest, prims_closest, nodes_any, prims_any; uint64_t debug[4]; };
+struct DeviceStats { uint64_t rays_closest, rays_any, nodes_closest, prims_closest, nodes_any, prims_any; uint64_t debug[4]; uint64_t tail[8]; };
 
 // Everything one sample needs besides the per-pixel state.  Two sets (sample parity): the stages of
 // two consecutive samples overlap in time (hrt_render_launch), never more.
@@ -136,6 +136,7 @@ struct Workspace {
     float4 *accum = nullptr;
     uint32_t *rows = nullptr;
     uint32_t *slice_cost = nullptr, *slice_order = nullptr; uint32_t slice_capacity = 0;   // fused mode: cost-ordered slices
+    uint32_t *block_progress = nullptr; uint32_t block_capacity = 0;                         // fused mode, sample blocks: per slice, the blocks its pixels have ended
     float4 *primary_cache = nullptr; uint32_t primary_cache_lanes = 0;                     // HRT_CTX_REUSE_PRIMARY: two float4 per lane of the path kernel's grid
 };
 
@@ -243,6 +244,8 @@ struct HrtContext {
     int fused_max_pixels = 700000;
     bool reuse_primary = false;                 // HRT_REUSE_PRIMARY: every launch as under HRT_CTX_REUSE_PRIMARY
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
+    int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)
+    uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks
     int fused_max_spp = 512;                    // samples per fused launch
     int fetch_chunk = 64;
     int substream_min_pixels = 32768;

@@ -33,10 +33,54 @@ struct PathStep {
     V3 ro = {0.0f, 0.0f, 0.0f}, rd = {0.0f, 0.0f, 1.0f};
 };
 
+// Sample blocks (PathArgs::sample_block = K > 0): the work item is not a slice of pixels with all their samples but
+// (pass b, slice q) = samples [b K, (b + 1) K) of the slice's pixels; the counters hand all items of pass 0 out, then pass 1's, ... so
+// that only the last pass has an end-of-frame tail, K / spp of a whole pixel's.  A lane that finishes a block leaves sum and RNG state
+// where a finished pixel's go and the lane that takes the pixel's next block continues from there: the same additions in the same
+// order from the same stream, the same bits.  What a wave knows about the item it holds (wave-uniform):
+struct BlockSlice {
+    uint32_t pass = 0u;         // b
+    uint32_t slice = 0u;        // q
+    uint32_t need = 0u;         // what block_progress[q] must have reached before the item's pixels may start (0: nothing to wait for)
+};
+
+// The hand-over between passes crosses CUs and XCDs (whose L2s are not coherent with one another) and must not cost the tree its place
+// in the caches, so no fence writes back or invalidates anything:
+//   the lane that ends a block   stores the 40 bytes write-through (relaxed agent-scope atomic stores: global_store_dwordx2 ... sc1), the wave
+//                                waits for them (s_waitcnt vmcnt(0)), then the lane adds 1 to the slice's progress word (agent-scope atomic add:
+//                                global_atomic_add_u32 ... sc1);
+//   the wave that holds (b, q)   reads the progress word past L1 (relaxed agent-scope atomic load: global_load_dword ... sc1) and, once it says that all
+//                                pixels of (b - 1, q) are stored, its lanes load their 40 bytes past L1 as well (global_load_dwordx2 ... sc1).
+// In block mode no other load or store touches those bytes inside a launch.
+// x / d for a divisor the host knows, m = min(2^32 / d, 2^32 - 1): the product's high word is short by one at most (every x, every d >= 1)
+__device__ __forceinline__ uint32_t div_magic(uint32_t x, uint32_t d, uint32_t m) { const uint32_t q = __umulhi(x, m); return x - q * d >= d ? q + 1u : q; }
+__device__ __forceinline__ unsigned long long pack_u64(uint32_t lo, uint32_t hi) { return (unsigned long long)lo | ((unsigned long long)hi << 32); }
+__device__ __forceinline__ void handover_store(const PathArgs &pa, const PathLane &P, uint32_t fetch_chunk) {
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(pa.accum + P.px_local), *st = reinterpret_cast<unsigned long long *>(pa.states + P.px_tid);
+    __hip_atomic_store(acc, pack_u64(__float_as_uint(P.px_ax), __float_as_uint(P.px_ay)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(acc + 1, pack_u64(__float_as_uint(P.px_az), 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st, pack_u64(P.px_rng.d, P.px_rng.v0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st + 1, pack_u64(P.px_rng.v1, P.px_rng.v2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(st + 2, pack_u64(P.px_rng.v3, P.px_rng.v4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every store of the wave has been written through before any lane says so
+    __hip_atomic_fetch_add(pa.block_progress + div_magic(P.px_local, fetch_chunk, pa.block_chunk_magic), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, bool with_sum) {
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(pa.accum + P.px_local), *st = reinterpret_cast<unsigned long long *>(pa.states + P.px_tid);
+    const unsigned long long r0 = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r1 = __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                             r2 = __hip_atomic_load(st + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    P.px_rng.d = (uint32_t)r0; P.px_rng.v0 = (uint32_t)(r0 >> 32); P.px_rng.v1 = (uint32_t)r1; P.px_rng.v2 = (uint32_t)(r1 >> 32); P.px_rng.v3 = (uint32_t)r2; P.px_rng.v4 = (uint32_t)(r2 >> 32);
+    if (with_sum) {
+        const unsigned long long a0 = __hip_atomic_load(acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a1 = __hip_atomic_load(acc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        P.px_ax = __uint_as_float((uint32_t)a0); P.px_ay = __uint_as_float((uint32_t)(a0 >> 32)); P.px_az = __uint_as_float((uint32_t)a1);
+    }
+}
+
 // A ray (o, d) has finished with the hit record (bt, bu, bv, bprim, binst).  The lane gives its pixel up (have_pixel = false: record or
 // sum written), wants the next sample's primary ray, or launches the bounce.
 // REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
-template <bool HAS_SPHERES, bool REUSE>
+// BLOCKS: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
+template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst) {
     PathStep st;
     const bool miss = bprim == kMissPrim;
@@ -57,9 +101,19 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
         }
         if (a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
             atomicAdd(a.path.slice_cost + P.px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - P.px_t0) >> 4);
-        if (P.px_sample >= a.path.spp) {
-            a.path.accum[P.px_local] = make_float4(P.px_ax, P.px_ay, P.px_az, 0.0f);
-            rng_store(a.path.states + P.px_tid, P.px_rng);
+        bool ends = P.px_sample >= a.path.spp;
+        if constexpr (BLOCKS) {
+            // ... or px_sample is a multiple of K: with M = min(2^32 / K, 2^32 - 1) the quotient is short by one at most, so the remainder
+            // comes out as 0 or K exactly then (every px_sample, every K >= 1; K = 0, M = 0: never, px_sample is at least 1 here)
+            const uint32_t rem = P.px_sample - __umulhi(P.px_sample, a.path.block_magic) * a.path.sample_block;
+            ends = ends || rem == 0u || rem == a.path.sample_block;
+        }
+        if (ends) {
+            if (BLOCKS && a.path.sample_block != 0u) handover_store(a.path, P, a.fetch_chunk);
+            else {
+                a.path.accum[P.px_local] = make_float4(P.px_ax, P.px_ay, P.px_az, 0.0f);
+                rng_store(a.path.states + P.px_tid, P.px_rng);
+            }
             P.have_pixel = false;
         } else st.want_primary = true;
     } else {
@@ -78,18 +132,51 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // Lanes without a pixel (`free_lane`) take the next ones of the wave's slice [wbeg, wend) of the tile's n_pixels, in lane order, and
 // initialise them; a lane that took one wants a primary ray (st.want_primary).  Returns `exhausted` (wave-uniform): the tile is used up
 // (in and out by value on purpose: as a `bool &` it moved k_fused's sphere instantiations' loops by an instruction).
+// BLOCKS (B: the wave's item): in block mode the counters hand out block_items = passes x slices numbers, number i standing for pass
+// i / slices of slice i % slices, and an item of a later pass waits for its predecessor: while the slice's progress word says that pixels of
+// (b - 1, q) are still under way the wave keeps the item, starts none of its pixels and looks again at its next regeneration.  It never
+// waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
+template <bool BLOCKS = false>
 __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
-                                          bool exhausted, uint32_t home_shard, uint32_t tx) {
+                                          bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
-        if (wbeg >= wend) {
+        bool by_blocks = false;
+        if constexpr (BLOCKS) by_blocks = a.path.sample_block != 0u;
+        if (by_blocks) {
+            if constexpr (BLOCKS) {
+                if (wbeg >= wend) {
+                    uint32_t item = 0u;
+                    wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, a.path.block_items * a.fetch_chunk, tx,
+                                    [&](uint64_t q) { item = (uint32_t)q; return q; });
+                    if (wbeg >= wend) exhausted = true;
+                    else {
+                        item = wave_first_u32(item);
+                        B->pass = div_magic(item, a.path.block_slices, a.path.block_slices_magic);
+                        B->slice = item - B->pass * a.path.block_slices;
+                        wbeg = B->slice * a.fetch_chunk;
+                        wend = wbeg + a.fetch_chunk < n_pixels ? wbeg + a.fetch_chunk : n_pixels;
+                        B->need = B->pass * (wend - wbeg);         // every pixel of the slice adds 1 per block it ends
+                    }
+                }
+                if (!exhausted && B->need != 0u) {
+                    const uint32_t done = __hip_atomic_load(a.path.block_progress + B->slice, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (wave_first_u32(done) >= B->need) {
+                        B->need = 0u;
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // (no instruction: the pixels' loads stay behind the poll)
+                    }
+                }
+            }
+        } else if (wbeg >= wend) {
             // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
             // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
             wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_pixels, tx,
                             [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
             if (wbeg >= wend) exhausted = true;
         }
-        if (!exhausted) {
+        bool ready = true;
+        if constexpr (BLOCKS) ready = B->need == 0u;
+        if (!exhausted && ready) {
             const uint32_t n_need = (uint32_t)__popcll(need);
             const uint32_t take = n_need < wend - wbeg ? n_need : wend - wbeg;
             const uint32_t rank = lane_prefix(need);
@@ -104,9 +191,17 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                     const uint32_t ix = j - row * a.path.width;
                     const uint32_t iy = a.path.rows[row];
                     P.px_tid = iy * a.path.width + ix;
-                    P.px_sample = 0u; P.px_rng = rng_load(a.path.states + P.px_tid);
                     P.px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
-                    if (!P.px_first) { const float4 acc = a.path.accum[P.px_local]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; }
+                    if (by_blocks) {
+                        if constexpr (BLOCKS) {                     // ... and so do later blocks of a launch
+                            P.px_sample = B->pass * a.path.sample_block;
+                            P.px_first = P.px_first && B->pass == 0u;
+                            handover_load(a.path, P, !P.px_first);
+                        }
+                    } else {
+                        P.px_sample = 0u; P.px_rng = rng_load(a.path.states + P.px_tid);
+                        if (!P.px_first) { const float4 acc = a.path.accum[P.px_local]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; }
+                    }
                     if (a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
                     const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
                     P.px_pdx = pd.x; P.px_pdy = pd.y; P.px_pdz = pd.z;

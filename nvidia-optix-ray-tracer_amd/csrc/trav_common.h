@@ -430,7 +430,27 @@ __device__ __forceinline__ void node_slab_test(const TravState &s, float tmin, c
 struct LaneStats {
 #ifdef HRT_LANE_STATS
     unsigned long long iter = 0, alive = 0, node = 0, prim = 0, ppass = 0, regen = 0, enter = 0;
+    // the drained phase (tools/tail_profile.py): iterations and alive lanes of the kTail copy of the loop, the wave's clock
+    // (s_memrealtime: one 100 MHz counter for the whole device) when it first found the work used up
+    unsigned long long tail_iter = 0, tail_alive = 0, t_drained = 0, mark_iter = 0, mark_alive = 0;
 #endif
+    // the wave has found the tile used up (every regeneration from then on says so: the first one counts)
+    __device__ __forceinline__ void drained([[maybe_unused]] bool exhausted) {
+#ifdef HRT_LANE_STATS
+        if (exhausted && t_drained == 0ull) t_drained = __builtin_amdgcn_s_memrealtime();
+#endif
+    }
+    // round a call of the drained copy of the loop
+    __device__ __forceinline__ void tail_begin() {
+#ifdef HRT_LANE_STATS
+        mark_iter = iter; mark_alive = alive;
+#endif
+    }
+    __device__ __forceinline__ void tail_end() {
+#ifdef HRT_LANE_STATS
+        tail_iter += iter - mark_iter; tail_alive += alive - mark_alive;
+#endif
+    }
     __device__ __forceinline__ void regeneration() {
 #ifdef HRT_LANE_STATS
         ++regen;
@@ -452,6 +472,20 @@ struct LaneStats {
         if (tx == 0u) {
             unsigned long long *d = reinterpret_cast<unsigned long long *>(rays_closest);
             atomicAdd(d + 6, iter); atomicAdd(d + 7, alive); atomicAdd(d + 8, node); atomicAdd(d + 9, prim); atomicAdd(d + 2, ppass); atomicAdd(d + 3, regen); atomicAdd(d + 4, enter);
+            // DeviceStats::tail, behind debug[4].  Clocks are kept relative to the first reporting wave's (slot 2), plus 2^40 so that a
+            // wave that drained before that one exited stays positive; the first drained clock as the maximum of its complement,
+            // so that zeroed memory is the neutral element of every slot.
+            unsigned long long *t = d + 10;
+            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+            unsigned long long base = atomicCAS(t + 2, 0ull, now);
+            if (base == 0ull) base = now;
+            if (t_drained == 0ull) t_drained = now;
+            const unsigned long long bias = 1ull << 40, exit_rel = now - base + bias, lane_iters = 64ull * tail_iter;
+            atomicAdd(t + 0, tail_iter); atomicAdd(t + 1, tail_alive);
+            atomicMax(t + 3, ~(t_drained - base + bias)); atomicMax(t + 4, exit_rel); atomicAdd(t + 5, exit_rel);
+            // lane-ticks without a ray between draining and exit: the share of idle lanes over the drained iterations, times that span
+            atomicAdd(t + 6, tail_iter ? (now - t_drained) * (lane_iters - tail_alive) / tail_iter : (now - t_drained) * 64ull);
+            atomicAdd(t + 7, 1ull);
         }
 #endif
     }

@@ -73,7 +73,8 @@ def audit(source, kernel_prefix, verbose=False):
 if __name__ == "__main__":
     v = "-v" in sys.argv
     total_groups = total_bad = 0
-    for src, prefix in (("nvidia-optix-ray-tracer_amd/csrc/kernels.hip", "_ZN3hrt10k_traverse"), ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"), ("nvidia-optix-ray-tracer_amd/csrc/fused_queue.hip", "_ZN3hrt13k_trace_queue")):
+    for src, prefix in (("nvidia-optix-ray-tracer_amd/csrc/kernels.hip", "_ZN3hrt10k_traverse"), ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"), ("nvidia-optix-ray-tracer_amd/csrc/fused_blocks.hip", "_ZN3hrt13k_path_blocks"),
+                        ("nvidia-optix-ray-tracer_amd/csrc/fused_queue.hip", "_ZN3hrt13k_trace_queue")):
         g, b = audit(src, prefix, v)
         print(f"{src}: {g} groups of in-flight loads checked, {b} hazardous instructions")
         total_groups += g; total_bad += b
