@@ -145,5 +145,5 @@ $(ASAN_DIR)/liboracle.so: oracle/oracle.c
 asan-test: asan
 	LD_PRELOAD="$$(gcc -print-file-name=libasan.so) $$(gcc -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 \
 	HRT_IO_LIB=$(CURDIR)/$(ASAN_DIR)/libhrt_io.so HRT_HOST_BVH_LIB=$(CURDIR)/$(ASAN_DIR)/libhrt_host_bvh.so HRT_ORACLE_LIB=$(CURDIR)/$(ASAN_DIR)/liboracle.so \
-	python3 -m pytest tests/test_fuzz_inputs_cpu.py tests/test_io_cpu.py tests/test_oracle_cpu.py tests/test_host_cpu.py -x -q -p no:cacheprovider -k "not pow_pin and not cpp_driver and not exports_every and not no_cpu_fallback and not sbt_header and not sanitizer_job"
+	python3 -m pytest tests/test_fuzz_inputs_cpu.py tests/test_io_cpu.py tests/test_oracle_cpu.py tests/test_host_cpu.py tests/test_adversarial_rays_cpu.py -x -q -p no:cacheprovider -k "not pow_pin and not cpp_driver and not exports_every and not no_cpu_fallback and not sbt_header and not sanitizer_job"
 .PHONY: asan asan-test
