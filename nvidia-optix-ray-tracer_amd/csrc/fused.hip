@@ -22,6 +22,8 @@ namespace hrt {
 
 void launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // fused_blocks.hip
 
+// (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
+// from the segment itself, fused_body.h: kernarg_traverse_args)
 template <bool HAS_SPHERES, bool INSTANCED, bool REUSE>
 __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD : HRT_FUSED_WAVES_PER_SIMD) void k_fused(TraverseArgs a) {
     fused_body<HAS_SPHERES, INSTANCED, REUSE, false>(a);

@@ -1,5 +1,5 @@
 // fused_blocks.hip -- k_path_blocks: the persistent path kernel (fused_body.h) handing pixels out in sample blocks (path_lane.h; DESIGN.md
-// section 2.1).  A kernel and a translation unit of its own: the hand-over costs the regeneration a dozen spilled registers, which k_fused
+// section 2.1).  A kernel and a translation unit of its own: the hand-over costs the regeneration ten spilled registers (lane state), which k_fused
 // (fused.hip) -- whose registers, spills and loop tests/test_host_cpu.py pins -- need not pay.  One-level trees, no primary-hit cache.
 #include "fused_body.h"
 
@@ -7,6 +7,8 @@
 
 namespace hrt {
 
+// (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
+// from the segment itself, fused_body.h: kernarg_traverse_args)
 template <bool HAS_SPHERES>
 __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_path_blocks(TraverseArgs a) {
     fused_body<HAS_SPHERES, false, false, true>(a);

@@ -101,14 +101,28 @@ struct InstLane {
 // `primary_cache`; the later ones are shaded from there (same record, same shading, same random numbers: the same bits) and only their
 // bounces are traversed.  Rays that are not traversed are not counted.  A separate instantiation, like INSTANCED.
 #ifndef HRT_FUSED_WAVES_PER_SIMD
-#define HRT_FUSED_WAVES_PER_SIMD 4      // 128 VGPRs, a dozen kernel constants spilled; 5 waves (96 VGPRs, 95 spilled around the shading): 2560 against 3122 Mrays/s
+#define HRT_FUSED_WAVES_PER_SIMD 4      // 128 VGPRs, the probe launch's clock spilled; 5 waves (96 VGPRs, 95 spilled around the shading): 2560 against 3122 Mrays/s
 #endif
 #ifndef HRT_INST_WAVES_PER_SIMD
 #define HRT_INST_WAVES_PER_SIMD 3       // the INSTANCED instantiation: 160 VGPRs, nothing spilled, 12 waves per CU (at 4 waves per SIMD it spills 47 registers around
                                         // the shading: 2 % slower on both particle clouds, profiles/r04_two_level_sweep.txt)
 #endif
+// The kernel's arguments as the regeneration reads them: straight from the kernel-argument segment, with scalar loads (s_load_dword*, the
+// scalar cache) where a value is used.  Read through the by-value parameter the 108 dwords are loaded at the kernel's entry and stay live
+// across the traversal loop, which has no scalar register to spare: hipcc spilled them into VGPR lanes (69 SGPRs in k_path_blocks<false>)
+// and the regeneration fetched them back with v_readlane_b32, 16 at a time to use two or three.  The empty asm hides from the compiler
+// that this is the memory the parameter came from, so it neither merges these loads with the entry's nor hoists them over the loop.
+// REQUIRES the TraverseArgs to be the kernel's only explicit argument, at offset 0 of the segment (k_fused, k_path_blocks).
+__device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();           // (a pointer into the constant address space, address_space(4))
+    asm volatile("" : "+s"(p));
+    return *(const TraverseArgs *)p;
+}
+
 // The kernel's body: k_fused below, and -- BLOCKS -- k_path_blocks, which hands pixels out in sample blocks (path_lane.h).  A kernel of its own
-// because the hand-over costs the regeneration a dozen spilled registers more, which the launches without blocks need not pay.
+// because the hand-over costs the regeneration spilled registers, which the launches without blocks need not pay.
+// `a`: the kernel's only argument (see kernarg_traverse_args); what the traversal loop consumes comes from it, the regeneration's
+// constants from the segment.
 template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
@@ -165,6 +179,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         if (force_regen || idle == ~0ull || (exhausted ? (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
             stats.regeneration();
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
+            const TraverseArgs &a = kernarg_traverse_args();      // (hides the parameter on purpose: nothing in this block reads the entry's copy)
             PathStep st;                            // st.launch: this lane starts the ray (st.ro, st.rd) below
             [[maybe_unused]] bool reshade = false;
             [[maybe_unused]] const bool was_forced = force_regen;
@@ -244,8 +259,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         }
         else traverse_to_regen<HAS_SPHERES, INSTANCED, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
-    stats.report(a.path.rays_closest, tx);
-    path_report_rays(P, a, tx);
+    const TraverseArgs &k = kernarg_traverse_args();          // (the counters' addresses need not live in registers until here)
+    stats.report(k.path.rays_closest, tx);
+    path_report_rays(P, k, tx);
 }
 
 }  // namespace hrt

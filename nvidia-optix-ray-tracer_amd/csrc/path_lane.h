@@ -220,9 +220,11 @@ template <bool RECOMPUTE_DIRECTION>
 __device__ __forceinline__ PathRay path_primary(PathLane &P, const TraverseArgs &a) {
     PathRay r;
     if (a.path.trace_rays) {
-        const RayRec q = a.path.trace_rays[P.px_local];
+        // (read as device memory, which it is: through generic pointers hipcc merges these loads with the other branch's into loads through
+        // a pointer that is either the caller's ray or the camera in the kernel-argument segment -- a flat_load of kernel arguments)
+        const global_floats q = (global_floats)reinterpret_cast<const float *>(a.path.trace_rays + P.px_local);
         P.px_depth = a.path.trace_any ? kRayTraceDepth : 1u;      // any-hit queries take the depth-limit ray's early exit
-        r.o = mk3(q.o.x, q.o.y, q.o.z); r.d = mk3(q.d.x, q.d.y, q.d.z);
+        r.o = mk3(q[0], q[1], q[2]); r.d = mk3(q[4], q[5], q[6]);
     } else {
         P.px_depth = 1u;
         r.o = mk3(a.path.center[0], a.path.center[1], a.path.center[2]); r.d = mk3(P.px_pdx, P.px_pdy, P.px_pdz);

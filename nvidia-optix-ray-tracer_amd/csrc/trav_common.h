@@ -140,16 +140,19 @@ __device__ __forceinline__ V3 hit_point(V3 rayOrigin, V3 rayDirection, float t) 
 // the normal a closest-hit program scatters about, shader/Shader.cu:122-155: the sphere's (hitPoint - centre) / radius with the
 // object-space centre (quirk Q1) or the interpolated vertex normal, neither transformed nor normalised (Q2), turned against the ray.
 // One definition for the programs below and the denoiser's guide pass (denoise.hip), which normalises it as the depth-1 AOV does (:216-227).
+typedef const __attribute__((address_space(1))) float *global_floats;      // floats known to lie in device (global) memory: global_load, not flat_load
 template <bool HAS_SPHERES>
 __device__ __forceinline__ V3 hit_normal(bool sphere, const HitGroup &hg, V3 hitPoint, V3 rayDirection, float u, float v, uint32_t primitiveIndex) {
     V3 _normal;
     if (HAS_SPHERES && sphere) {                                          // :122-136
-        const float *cp = reinterpret_cast<const float *>(hg.ptr0) + 3 * (size_t)primitiveIndex;
+        const global_floats cp = (global_floats)(reinterpret_cast<const float *>(hg.ptr0) + 3 * (size_t)primitiveIndex);
         const V3 sphereCenter = mk3(cp[0], cp[1], cp[2]);
-        const float sphereRadius = reinterpret_cast<const float *>(hg.ptr1)[primitiveIndex];
+        const float sphereRadius = ((global_floats)reinterpret_cast<const float *>(hg.ptr1))[primitiveIndex];
         _normal = divs3(sub3(hitPoint, sphereCenter), sphereRadius);
     } else {                                                              // :137-155
-        const float *np = reinterpret_cast<const float *>(hg.ptr0) + 9 * (size_t)primitiveIndex;
+        // (the normals are device memory, and the load says so: through the generic pointer it is a flat_load, which counts in lgkmcnt as
+        // well as in vmcnt and makes the regeneration's scalar loads wait for it)
+        const global_floats np = (global_floats)(reinterpret_cast<const float *>(hg.ptr0) + 9 * (size_t)primitiveIndex);
         const V3 n1 = mk3(np[0], np[1], np[2]), n2 = mk3(np[3], np[4], np[5]), n3 = mk3(np[6], np[7], np[8]);
         const float w = 1.0f - u - v;
         _normal = add3(add3(muls3(n1, w), muls3(n2, u)), muls3(n3, v));
