@@ -206,7 +206,8 @@ void launch_pose_instances(const PoseArgs &a, hipStream_t s);
 void launch_debug_trig(int which, const float *a, const float *b, uint32_t first, uint32_t stride, uint64_t n, int force_slow, float *out, hipStream_t s);
 
 // denoiser (denoise.hip): the guide pass -- primary rays of a full frame, then their hits turned into HrtDenoiseGuide records (16 B,
-// uint4 here) -- and one a-trous pass of the filter
+// uint4 here) -- and one a-trous pass of the filter, which in the variance-guided mode (DESIGN.md 3e "Variance-guided mode") carries a
+// variance frame along with the colour
 struct DenoiseRayArgs {
     RayRec *rays; uint32_t width, height;
     float center[3], U[3], V[3], W[3];
@@ -222,6 +223,8 @@ struct DenoisePassArgs {
     float k_color, k_albedo;       // 1 / sigma_color_i^2, 1 / sigma_albedo^2
     float sigma_depth_step;        // sigma_depth * step
     uint32_t normal_squarings;
+    const float *var_src; float *var_dst;      // the variance-guided form (var_src == NULL: the plain one, which reads none of these)
+    float k_luminance, variance_floor;         // sigma_luminance^2; k_color is not read by this form
 };
 // the temporal mode's reprojection and blend: one thread per pixel of the frame; prev_* are the last call's history (has_history == 0:
 // none), cur_* this call's
@@ -236,23 +239,13 @@ struct DenoiseTemporalArgs {
     float alpha_min, max_history, depth_tolerance;
     const float2 *prev_moments; float2 *moments;             // the variance-guided mode's luminance moments (moments == NULL: not carried)
 };
-// the variance-guided mode (DESIGN.md 3e "Variance-guided mode"): the per-pixel variance from the moments, and one filter pass that
-// carries a variance frame along with the colour
+// the variance-guided mode: the per-pixel variance from the moments
 struct DenoiseVarianceArgs {
     const float2 *moments; const float *length; const uint2 *id; float *variance;
     uint32_t width, height;
     float history_min;                                       // L below it: the spatial estimate
 };
-struct DenoisePassVarArgs {
-    const float4 *src; const float *var_src; const uint4 *guides; float4 *dst; float *var_dst;
-    uint32_t width, height, step;
-    float k_luminance;             // sigma_luminance^2
-    float variance_floor;
-    float k_albedo, sigma_depth_step;
-    uint32_t normal_squarings;
-};
 void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s);
-void launch_denoise_pass_var(const DenoisePassVarArgs &a, hipStream_t s);
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
 void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);

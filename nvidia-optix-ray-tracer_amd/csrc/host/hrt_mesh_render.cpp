@@ -8,23 +8,15 @@
 // particle plus the file's IAS ON THE DEVICE (readVTKFileCache, :93-157).  Per frame: every particle drifts by its velocity
 // (hrt_pose_instances in Mesh mode replaces the host loop :379-391 and the H2D copy :395-397) -> updateIAS -> launch + sync ->
 // convert to 8 bit; the last frame is written as PPM.
-#include "renderer_host.hpp"
-#include "hrt_io.h"
+#include "driver_common.hpp"
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstring>
 #include <deque>
 #include <string>
 #include <thread>
 
-using namespace project;
-
-#define hipCheck(x) do { hipError_t e = (x); if (e != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e)); std::exit(-100); } } while (0)
-#define ioCheck(x) do { if ((x) != 0) { std::fprintf(stderr, "%s\n", hrt_io_last_error()); std::exit(-1); } } while (0)   // VTK_READER_ERROR_EXIT_CODE
-
-static std::string join(const std::string &base, const std::string &p) { return (!p.empty() && p[0] == '/') ? p : base + "/" + p; }
+using namespace driver;
 
 template <typename T> static T *toDevice(const T *host, size_t count, hipStream_t stream = nullptr) {
     T *dev = nullptr;
@@ -57,16 +49,8 @@ struct FileData {
 };
 
 int main(int argc, char **argv) {
-    // --denoise (anywhere): every frame goes through denoiseOutput before the conversion, as the reference's default display does
-    // (RendererTime.cu / RendererMesh.cu: launch -> denoiseOutput -> convertFloat4ToUchar4Kernel); without it the raw frame is shown, skipDenoise
-    // --denoise-temporal (anywhere): the same slot in the library's temporal mode, each frame blended into the history of the ones before
-    // --denoise-variance (anywhere): the temporal mode with variance-guided edge stops (denoiseOutputVariance)
-    bool denoise = false, denoiseTemporal = false, denoiseVariance = false;
-    { int k = 1; for (int i = 1; i < argc; ++i) { if (std::strcmp(argv[i], "--denoise") == 0) denoise = true;
-                                                  else if (std::strcmp(argv[i], "--denoise-temporal") == 0) denoiseTemporal = true;
-                                                  else if (std::strcmp(argv[i], "--denoise-variance") == 0) denoiseVariance = true; else argv[k++] = argv[i]; } argc = k; }
-    if ((int)denoise + (int)denoiseTemporal + (int)denoiseVariance > 1) { std::fprintf(stderr, "--denoise, --denoise-temporal and --denoise-variance exclude each other\n"); return 2; }
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]\n", argv[0]); return 2; }
+    const DenoiseMode denoiseMode = parseDenoiseMode(argc, argv);
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s\n", argv[0], kDenoiseUsage); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -170,13 +154,7 @@ int main(int argc, char **argv) {
     // materials: the config's, then the baked ramp with one colour per cell of the largest file (:222-232)
     uint64_t maxCellCount = 0;
     ioCheck(hrt_io_read_metadata_cache(cacheDir.c_str(), &maxCellCount));
-    std::vector<float> ramp(3 * std::max<uint64_t>(1, maxCellCount));
-    ioCheck(hrt_io_bake_color_ramp(cfg.particle_material_preset, maxCellCount, ramp.data()));
-    RendererMaterial materials;
-    for (uint64_t i = 0; i < cfg.n_roughs; ++i) materials.roughs.push_back({cfg.roughs[3 * i], cfg.roughs[3 * i + 1], cfg.roughs[3 * i + 2]});
-    for (uint64_t i = 0; i < cfg.n_metals; ++i) materials.metals.push_back({{cfg.metals[4 * i], cfg.metals[4 * i + 1], cfg.metals[4 * i + 2]}, cfg.metals[4 * i + 3]});
-    const size_t materialOffset = materials.roughs.size();
-    for (uint64_t i = 0; i < maxCellCount; ++i) materials.roughs.push_back({ramp[3 * i], ramp[3 * i + 1], ramp[3 * i + 2]});
+    const auto [materials, materialOffset] = materialsFromConfig(cfg, maxCellCount);
     const std::vector<HitGroupSbtRecord> addGeoRecord = createAddSphereTriangleSBTRecord(ctx, addSpheres, {}, materials);
     for (auto &fd : perFile) {                      // per file: the records of its instances, extra geometry first (:262-282)
         std::vector<std::pair<size_t, HrtFloat3 *>> particleSBTData;
@@ -194,15 +172,9 @@ int main(int argc, char **argv) {
 
     HrtRngState *dev_stateArray = nullptr;
     RandomGenerator::initDeviceRandomGenerators(ctx, dev_stateArray, W, H, 0x5EED0000C0FFEEull);
-    const auto camera = SDL_GraphicsWindowConfigureCamera({cfg.camera_center[0], cfg.camera_center[1], cfg.camera_center[2]},
-                                                          {cfg.camera_target[0], cfg.camera_target[1], cfg.camera_target[2]},
-                                                          {cfg.up_direction[0], cfg.up_direction[1], cfg.up_direction[2]}, cfg.api_is_opengl != 0);
-    HrtFloat4 *color = nullptr; HrtUchar4 *rgba = nullptr;
-    hipCheck(hipMalloc((void **)&color, sizeof(HrtFloat4) * (size_t)W * H));
-    hipCheck(hipMalloc((void **)&rgba, sizeof(HrtUchar4) * (size_t)W * H));
-    HrtRayGenParams raygen{};
-    raygen.width = W; raygen.height = H; raygen.colorBuffer = color;
-    raygen.cameraCenter = camera.cameraCenter; raygen.cameraU = camera.cameraU; raygen.cameraV = camera.cameraV; raygen.cameraW = camera.cameraW;
+    const Frame fb = frameFromConfig(cfg, W, H);
+    const HrtRayGenParams &raygen = fb.raygen;
+    HrtFloat4 *const color = fb.color; HrtUchar4 *const rgba = fb.rgba;
 
     long frames = 0;
     hrtCheckError(ctx, hrt_stats_reset(ctx));
@@ -220,29 +192,16 @@ int main(int argc, char **argv) {
             updateIAS(ctx, fd.ias, fd.dev_instances, fd.instanceCount);
             const HrtGlobalParams params{std::get<0>(fd.ias), dev_stateArray};
             hrtCheckError(ctx, hrt_render_launch(ctx, &params, &raygen, 1, nullptr, nullptr));      // (launch, conversion, then the frame's one synchronisation)
-            if (denoise) denoiseOutput(ctx, params, raygen, color);                                   // (in place: the colour buffer is not read again)
-            if (denoiseTemporal) denoiseOutputTemporal(ctx, params, raygen, color);
-            if (denoiseVariance) denoiseOutputVariance(ctx, params, raygen, color);
+            denoiseFrame(denoiseMode, ctx, params, raygen, color);
             hrtCheckError(ctx, hrt_to_rgba8(ctx, color, rgba, W, H, nullptr));
             hrtCheckError(ctx, hrt_sync(ctx, nullptr));
         }
     }
     hipCheck(hipDeviceSynchronize());
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HrtStats st{};
-    hrtCheckError(ctx, hrt_stats_get(ctx, &st));
-    for (int k = 0; k < HRT_K_COUNT; ++k)
-        if (st.kernel_launches[k] && st.kernel_ms[k] > 0.0) std::printf("  kernel class %d: %.3f ms in %llu launches\n", k, st.kernel_ms[k], (unsigned long long)st.kernel_launches[k]);
-    std::printf("%ld frames %ux%u: %.3f ms/frame (%.0f frames/s), %.1f Mrays/s, refits %llu rebuilds %llu\n", frames, W, H, ms / std::max(1l, frames),
-                frames / ms * 1e3, st.rays / ms * 1e-3, (unsigned long long)st.tlas_refits, (unsigned long long)st.tlas_rebuilds);
+    printSummary(ctx, frames, W, H, ms);
 
-    std::vector<HrtUchar4> host((size_t)W * H);
-    hipCheck(hipMemcpy(host.data(), rgba, host.size() * sizeof(HrtUchar4), hipMemcpyDeviceToHost));
-    if (FILE *fp = std::fopen(out.c_str(), "wb")) {
-        std::fprintf(fp, "P6\n%u %u\n255\n", W, H);
-        for (uint32_t y = 0; y < H; ++y) for (uint32_t x = 0; x < W; ++x) std::fwrite(&host[(size_t)y * W + x], 1, 3, fp);
-        std::fclose(fp);
-    }
+    writePpm(out, rgba, W, H);
 
     RandomGenerator::freeDeviceRandomGenerators(ctx, dev_stateArray);
     for (auto &fd : perFile) {

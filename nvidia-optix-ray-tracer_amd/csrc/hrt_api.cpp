@@ -711,10 +711,8 @@ int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const Hr
     if (!h_params->stateArray) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.stateArray is NULL");
     if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
     Tlas *t;
-    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
-      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
-      t = it->second.get(); }
-    int rc = refresh_tables(ctx, h_params->handle, t, s);
+    int rc = find_tlas(ctx, h_params->handle, t);
+    if (rc == HRT_OK) rc = refresh_tables(ctx, h_params->handle, t, s);
     if (rc != HRT_OK) return rc;
 
     // ---- tile rows ----

@@ -2,9 +2,10 @@
 // Guide pass: the primary rays of the frame (denoise.hip k_denoise_rays) through hrt_trace_rays' traversal (hrt_api.cpp trace_records: the
 // path kernel in the context's configuration, flattened and two-level trees alike), their hits turned into HrtDenoiseGuide records with
 // the material tables of the launch.  Filter: `iterations` a-trous passes, one launch each, ping-ponging between two frames the context
-// owns.  The temporal and the variance-guided mode share the reprojection step (run_temporal) and the history; the variance-guided filter
-// (run_filter_variance) ping-pongs a variance frame next to the colour.  Every call only enqueues work (the material tables' upload
-// after hrt_materials_set synchronises once, as in hrt_render_launch).
+// owns; the variance-guided filter is the same path (pass_constants, run_filter) with a variance frame ping-ponged next to the colour.
+// The temporal and the variance-guided mode share the reprojection step (run_temporal), the history and everything around their filter
+// (temporal_launch).  Every call only enqueues work (the material tables' upload after hrt_materials_set synchronises once, as in
+// hrt_render_launch).
 #include "hrt_internal.hpp"
 
 namespace hrt {
@@ -37,35 +38,30 @@ int check_frame(HrtContext *ctx, uint32_t width, uint32_t height) {
     return HRT_OK;
 }
 
-// the per-pixel arrays for n pixels: the guide pass's (trace) or the filter's two frames
-int ensure_work(HrtContext *ctx, uint32_t n, bool trace) {
+// the per-pixel arrays for n pixels: the guide pass's, the filter's two frames, or those and the variance-guided filter's two variance
+// frames.  All are sized by d.capacity: free_denoise_work, called before the capacity grows, frees every one of them, so a non-NULL one
+// is large enough.
+enum Work { kTrace, kFilter, kFilterVariance };
+int ensure_work(HrtContext *ctx, uint32_t n, Work work) {
     DenoiseWork &d = ctx->denoise;
     if (n > d.capacity) {
         free_denoise_work(ctx);
         HIP_TRY(ctx, hipMalloc((void **)&d.fetch, sizeof(uint32_t) * 8 * 32));
         d.capacity = n;
     }
-    if (trace && !d.rays) {
+    if (work == kTrace && !d.rays) {
         HIP_TRY(ctx, hipMalloc((void **)&d.rays, sizeof(RayRec) * (size_t)d.capacity));
         HIP_TRY(ctx, hipMalloc((void **)&d.tuvp, sizeof(float4) * (size_t)d.capacity));
         HIP_TRY(ctx, hipMalloc((void **)&d.inst, sizeof(uint32_t) * (size_t)d.capacity));
         HIP_TRY(ctx, hipMalloc((void **)&d.guides, sizeof(uint4) * (size_t)d.capacity));
     }
-    if (!trace && !d.frame[0]) {
+    if (work != kTrace && !d.frame[0]) {
         HIP_TRY(ctx, hipMalloc((void **)&d.frame[0], sizeof(float4) * (size_t)d.capacity));
         HIP_TRY(ctx, hipMalloc((void **)&d.frame[1], sizeof(float4) * (size_t)d.capacity));
     }
-    return HRT_OK;
-}
-
-// ... and the variance-guided filter's two variance frames next to its colour frames.  They are sized by d.capacity like every other
-// array here: free_denoise_work, which ensure_work calls before the capacity grows, frees them too, so a non-NULL one is large enough.
-int ensure_variance_work(HrtContext *ctx, uint32_t n) {
-    int rc = ensure_work(ctx, n, false);
-    if (rc != HRT_OK) return rc;
-    DenoiseWork &d = ctx->denoise;
-    for (float *&v : d.var)
-        if (!v) HIP_TRY(ctx, hipMalloc((void **)&v, sizeof(float) * (size_t)d.capacity));
+    if (work == kFilterVariance)
+        for (float *&v : d.var)
+            if (!v) HIP_TRY(ctx, hipMalloc((void **)&v, sizeof(float) * (size_t)d.capacity));
     return HRT_OK;
 }
 
@@ -81,88 +77,60 @@ int filter_params(HrtContext *ctx, const HrtDenoiseParams *h_dparams, HrtDenoise
     return HRT_OK;
 }
 
-// pass i's step and the constants of the stops that both filters have (DenoisePassArgs, DenoisePassVarArgs); false: one is not finite
-template <class PassArgs>
-bool shared_pass_constants(PassArgs &a, const HrtDenoiseParams &p, uint32_t i) {
-    a.step = 1u << i;
-    a.k_albedo = 1.0f / (p.sigma_albedo * p.sigma_albedo);
-    a.sigma_depth_step = p.sigma_depth * (float)a.step;
-    a.normal_squarings = p.normal_power_log2;
-    return positive_finite(a.k_albedo) && positive_finite(a.sigma_depth_step);
+// the variance-guided mode's parameters (NULL: the defaults), not yet validated: pass_constants does that
+HrtDenoiseVarianceParams variance_params(const HrtDenoiseVarianceParams *h_vparams) {
+    HrtDenoiseVarianceParams vp;
+    hrt_denoise_variance_default_params(&vp);
+    if (h_vparams) vp = *h_vparams;
+    return vp;
 }
 
-// ... and the constants of every pass
-int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, std::vector<DenoisePassArgs> &passes) {
+// ... and the constants of every pass.  vp != NULL: the variance-guided filter's, which does not use sigma_color beyond filter_params'
+// range check; the other fields of HrtDenoiseParams it does
+int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *vp, std::vector<DenoisePassArgs> &passes) {
     HrtDenoiseParams p;
     int rc = filter_params(ctx, h_dparams, p);
     if (rc != HRT_OK) return rc;
+    const float k_luminance = vp ? vp->sigma_luminance * vp->sigma_luminance : 0.0f;
+    if (vp && (!positive_finite(vp->sigma_luminance) || !positive_finite(k_luminance) || vp->history_min < 1 || vp->history_min > 65536 ||
+               !positive_finite(vp->variance_floor) || vp->reserved != 0))
+        return fail(ctx, HRT_ERR_INVALID, "variance denoise parameters out of range (sigma_luminance > 0 with a finite, non-zero square, history_min 1..65536, variance_floor > 0 and finite, reserved 0)");
     passes.assign(p.iterations, DenoisePassArgs{});
     for (uint32_t i = 0; i < p.iterations; ++i) {
         DenoisePassArgs &a = passes[i];
-        const float sc = std::ldexp(p.sigma_color, -(int)i);                          // sigma_color * 2^-i, exact above the subnormals
-        a.k_color = 1.0f / (sc * sc);
-        if (!shared_pass_constants(a, p, i) || !positive_finite(a.k_color))
-            return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
+        a.step = 1u << i;
+        a.k_albedo = 1.0f / (p.sigma_albedo * p.sigma_albedo);
+        a.sigma_depth_step = p.sigma_depth * (float)a.step;
+        a.normal_squarings = p.normal_power_log2;
+        bool finite = positive_finite(a.k_albedo) && positive_finite(a.sigma_depth_step);
+        if (vp) { a.k_luminance = k_luminance; a.variance_floor = vp->variance_floor; }
+        else {
+            const float sc = std::ldexp(p.sigma_color, -(int)i);                      // sigma_color * 2^-i, exact above the subnormals
+            a.k_color = 1.0f / (sc * sc);
+            finite = finite && positive_finite(a.k_color);
+        }
+        if (!finite) return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
     }
     return HRT_OK;
 }
 
-int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, float4 *out, uint32_t width, uint32_t height,
-               std::vector<DenoisePassArgs> &passes, hipStream_t s) {
-    int rc = ensure_work(ctx, width * height, false);
-    if (rc != HRT_OK) return rc;
-    const float4 *src = color;
-    const size_t n = passes.size();
-    for (size_t i = 0; i < n; ++i) {
-        DenoisePassArgs &a = passes[i];
-        // the last pass writes d_out -- unless d_out is its source (one pass in place), which goes through a frame of the context's
-        float4 *dst = i + 1 < n || out == src ? ctx->denoise.frame[i & 1] : out;
-        a.src = src; a.guides = guides; a.dst = dst; a.width = width; a.height = height;
-        launch_denoise_pass(a, s);
-        src = dst;
-    }
-    if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipGetLastError());
-    return HRT_OK;
-}
-
-// the variance-guided mode's parameters (NULL: the defaults) and every pass's constants; sigma_color is not used by this mode beyond
-// filter_params' range check, the other fields of HrtDenoiseParams are
-int variance_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams,
-                       HrtDenoiseVarianceParams &vp, std::vector<DenoisePassVarArgs> &passes) {
-    HrtDenoiseParams p;
-    int rc = filter_params(ctx, h_dparams, p);
-    if (rc != HRT_OK) return rc;
-    hrt_denoise_variance_default_params(&vp);
-    if (h_vparams) vp = *h_vparams;
-    const float k_luminance = vp.sigma_luminance * vp.sigma_luminance;
-    if (!positive_finite(vp.sigma_luminance) || !positive_finite(k_luminance) || vp.history_min < 1 || vp.history_min > 65536 ||
-        !positive_finite(vp.variance_floor) || vp.reserved != 0)
-        return fail(ctx, HRT_ERR_INVALID, "variance denoise parameters out of range (sigma_luminance > 0 with a finite, non-zero square, history_min 1..65536, variance_floor > 0 and finite, reserved 0)");
-    passes.assign(p.iterations, DenoisePassVarArgs{});
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        DenoisePassVarArgs &a = passes[i];
-        a.k_luminance = k_luminance; a.variance_floor = vp.variance_floor;
-        if (!shared_pass_constants(a, p, i))
-            return fail(ctx, HRT_ERR_INVALID, "denoise parameters out of range: pass %u's constants are not finite", i);
-    }
-    return HRT_OK;
-}
-
-// run_filter with a variance frame alongside: the last pass writes `out` and, if given, `var_out`, by run_filter's rule each
-int run_filter_variance(HrtContext *ctx, const float4 *color, const uint4 *guides, const float *variance, float4 *out, float *var_out,
-                        uint32_t width, uint32_t height, std::vector<DenoisePassVarArgs> &passes, hipStream_t s) {
-    int rc = ensure_variance_work(ctx, width * height);
+// variance == NULL: the plain filter.  Else a variance frame goes through the passes next to the colour, and into var_out if given.
+int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, const float *variance, float4 *out, float *var_out,
+               uint32_t width, uint32_t height, std::vector<DenoisePassArgs> &passes, hipStream_t s) {
+    int rc = ensure_work(ctx, width * height, variance ? kFilterVariance : kFilter);
     if (rc != HRT_OK) return rc;
     const float4 *src = color;
     const float *vsrc = variance;
     const size_t n = passes.size();
     for (size_t i = 0; i < n; ++i) {
-        DenoisePassVarArgs &a = passes[i];
-        float4 *dst = i + 1 < n || out == src ? ctx->denoise.frame[i & 1] : out;
-        float *vdst = i + 1 < n || !var_out || var_out == vsrc ? ctx->denoise.var[i & 1] : var_out;
+        DenoisePassArgs &a = passes[i];
+        // the last pass writes what the caller gave -- unless that is its source (one pass in place), which goes through a frame of the
+        // context's, as every other pass does
+        auto target = [&](auto *given, const auto *source, auto *own) { return i + 1 < n || !given || given == source ? own : given; };
+        float4 *dst = target(out, src, ctx->denoise.frame[i & 1]);
+        float *vdst = variance ? target(var_out, vsrc, ctx->denoise.var[i & 1]) : nullptr;
         a.src = src; a.var_src = vsrc; a.guides = guides; a.dst = dst; a.var_dst = vdst; a.width = width; a.height = height;
-        launch_denoise_pass_var(a, s);
+        launch_denoise_pass(a, s);
         src = dst; vsrc = vdst;
     }
     if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
@@ -175,12 +143,11 @@ int run_filter_variance(HrtContext *ctx, const float4 *color, const uint4 *guide
 int run_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg, uint4 *guides, hipStream_t s) {
     if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
     Tlas *t;
-    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
-      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
-      t = it->second.get(); }
+    int rc = find_tlas(ctx, h_params->handle, t);
+    if (rc != HRT_OK) return rc;
     const uint32_t n = rg->width * rg->height;
-    int rc = refresh_tables(ctx, h_params->handle, t, s);
-    if (rc == HRT_OK) rc = ensure_work(ctx, n, true);
+    rc = refresh_tables(ctx, h_params->handle, t, s);
+    if (rc == HRT_OK) rc = ensure_work(ctx, n, kTrace);
     if (rc != HRT_OK) return rc;
     DenoiseWork &d = ctx->denoise;
     DenoiseRayArgs ra{};
@@ -248,10 +215,8 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     const uint32_t width = h_raygen->width, height = h_raygen->height, n = width * height;
     const bool moments = mode == DenoiseHistory::kVariance;
     Tlas *t;
-    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(h_params->handle);
-      if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)h_params->handle);
-      t = it->second.get(); }
-    int rc = ensure_history(ctx, n, t->n_instances, moments);
+    int rc = find_tlas(ctx, h_params->handle, t);
+    if (rc == HRT_OK) rc = ensure_history(ctx, n, t->n_instances, moments);
     if (rc != HRT_OK) return rc;
     DenoiseHistory &h = ctx->denoise_history;
     const bool has_history = h.valid && h.mode == mode && h.tlas == h_params->handle && h.width == width && h.height == height && h.n_instances == t->n_instances;
@@ -278,6 +243,39 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     h.mode = mode;
     h.called = true;
     h.tlas = h_params->handle; h.width = width; h.height = height; h.n_instances = t->n_instances;
+    return HRT_OK;
+}
+
+// hrt_denoise_temporal_launch, and with vp != NULL hrt_denoise_variance_launch: the checks, the reprojection and blend, the filter of the
+// accumulated frame.  The variance-guided mode differs between the two by its variance kernel, whose result its filter takes.
+int temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
+                    const HrtDenoiseTemporalParams *h_tparams, const HrtDenoiseVarianceParams *vp, HrtFloat4 *d_out, void *stream) {
+    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    const uint32_t width = h_raygen->width, height = h_raygen->height;
+    int rc = check_frame(ctx, width, height);
+    std::vector<DenoisePassArgs> passes;
+    HrtDenoiseTemporalParams tp;
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, vp, passes);
+    if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
+    if (rc != HRT_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    DenoiseHistory &h = ctx->denoise_history;
+    rc = run_temporal(ctx, h_params, h_raygen, tp, vp ? DenoiseHistory::kVariance : DenoiseHistory::kTemporal, s);
+    if (rc != HRT_OK) return rc;
+    const DenoiseHistorySet &next = h.set[h.cur];
+    if (vp) {
+        DenoiseVarianceArgs va{};
+        va.moments = next.moments; va.length = next.length; va.id = next.id; va.variance = h.variance;
+        va.width = width; va.height = height; va.history_min = (float)vp->history_min;
+        launch_denoise_variance(va, s);
+        h.variance_called = true;
+        h.variance_set = h.cur;
+    }
+    rc = run_filter(ctx, next.accum, next.guides, vp ? h.variance : nullptr, reinterpret_cast<float4 *>(d_out), nullptr, width, height, passes, s);
+    if (rc != HRT_OK) return rc;
+    h.valid = true;
     return HRT_OK;
 }
 
@@ -308,10 +306,10 @@ int hrt_denoise_filter(HrtContext *ctx, const HrtFloat4 *d_color, const HrtDenoi
     (void)hipSetDevice(ctx->device);
     int rc = check_frame(ctx, width, height);
     std::vector<DenoisePassArgs> passes;
-    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, nullptr, passes);
     if (rc != HRT_OK) return rc;
-    return run_filter(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), reinterpret_cast<float4 *>(d_out),
-                      width, height, passes, (hipStream_t)stream);
+    return run_filter(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), nullptr,
+                      reinterpret_cast<float4 *>(d_out), nullptr, width, height, passes, (hipStream_t)stream);
 }
 
 int hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
@@ -321,12 +319,12 @@ int hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const H
     if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
     int rc = check_frame(ctx, h_raygen->width, h_raygen->height);
     std::vector<DenoisePassArgs> passes;
-    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, nullptr, passes);
     const hipStream_t s = (hipStream_t)stream;
     if (rc == HRT_OK) rc = run_guides(ctx, h_params, h_raygen, nullptr, s);
     if (rc != HRT_OK) return rc;
-    return run_filter(ctx, reinterpret_cast<const float4 *>(h_raygen->colorBuffer), ctx->denoise.guides, reinterpret_cast<float4 *>(d_out),
-                      h_raygen->width, h_raygen->height, passes, s);
+    return run_filter(ctx, reinterpret_cast<const float4 *>(h_raygen->colorBuffer), ctx->denoise.guides, nullptr, reinterpret_cast<float4 *>(d_out),
+                      nullptr, h_raygen->width, h_raygen->height, passes, s);
 }
 
 int hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out) {
@@ -338,25 +336,7 @@ int hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out) {
 
 int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
                                 const HrtDenoiseTemporalParams *h_tparams, HrtFloat4 *d_out, void *stream) {
-    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
-    (void)hipSetDevice(ctx->device);
-    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
-    const uint32_t width = h_raygen->width, height = h_raygen->height;
-    int rc = check_frame(ctx, width, height);
-    std::vector<DenoisePassArgs> passes;
-    HrtDenoiseTemporalParams tp;
-    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, passes);
-    if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
-    if (rc != HRT_OK) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    DenoiseHistory &h = ctx->denoise_history;
-    rc = run_temporal(ctx, h_params, h_raygen, tp, DenoiseHistory::kTemporal, s);
-    if (rc != HRT_OK) return rc;
-    const DenoiseHistorySet &next = h.set[h.cur];
-    rc = run_filter(ctx, next.accum, next.guides, reinterpret_cast<float4 *>(d_out), width, height, passes, s);
-    if (rc != HRT_OK) return rc;
-    h.valid = true;
-    return HRT_OK;
+    return temporal_launch(ctx, h_params, h_raygen, h_dparams, h_tparams, nullptr, d_out, stream);
 }
 
 int hrt_denoise_temporal_reset(HrtContext *ctx) {
@@ -392,43 +372,19 @@ int hrt_denoise_filter_variance(HrtContext *ctx, const HrtFloat4 *d_color, const
     if (!ctx || !d_color || !d_guides || !d_variance || !d_out) return HRT_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
     int rc = check_frame(ctx, width, height);
-    std::vector<DenoisePassVarArgs> passes;
-    HrtDenoiseVarianceParams vp;
-    if (rc == HRT_OK) rc = variance_constants(ctx, h_dparams, h_vparams, vp, passes);
+    std::vector<DenoisePassArgs> passes;
+    const HrtDenoiseVarianceParams vp = variance_params(h_vparams);
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, &vp, passes);
     if (rc != HRT_OK) return rc;
-    return run_filter_variance(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), d_variance,
-                               reinterpret_cast<float4 *>(d_out), d_var_out, width, height, passes, (hipStream_t)stream);
+    return run_filter(ctx, reinterpret_cast<const float4 *>(d_color), reinterpret_cast<const uint4 *>(d_guides), d_variance,
+                      reinterpret_cast<float4 *>(d_out), d_var_out, width, height, passes, (hipStream_t)stream);
 }
 
 int hrt_denoise_variance_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtDenoiseParams *h_dparams,
                                 const HrtDenoiseTemporalParams *h_tparams, const HrtDenoiseVarianceParams *h_vparams, HrtFloat4 *d_out,
                                 void *stream) {
-    if (!ctx || !h_params || !h_raygen || !d_out) return HRT_ERR_INVALID;
-    (void)hipSetDevice(ctx->device);
-    if (!h_raygen->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
-    const uint32_t width = h_raygen->width, height = h_raygen->height;
-    int rc = check_frame(ctx, width, height);
-    std::vector<DenoisePassVarArgs> passes;
-    HrtDenoiseTemporalParams tp;
-    HrtDenoiseVarianceParams vp;
-    if (rc == HRT_OK) rc = variance_constants(ctx, h_dparams, h_vparams, vp, passes);
-    if (rc == HRT_OK) rc = temporal_constants(ctx, h_tparams, tp);
-    if (rc != HRT_OK) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    DenoiseHistory &h = ctx->denoise_history;
-    rc = run_temporal(ctx, h_params, h_raygen, tp, DenoiseHistory::kVariance, s);
-    if (rc != HRT_OK) return rc;
-    const DenoiseHistorySet &next = h.set[h.cur];
-    DenoiseVarianceArgs va{};
-    va.moments = next.moments; va.length = next.length; va.id = next.id; va.variance = h.variance;
-    va.width = width; va.height = height; va.history_min = (float)vp.history_min;
-    launch_denoise_variance(va, s);
-    h.variance_called = true;
-    h.variance_set = h.cur;
-    rc = run_filter_variance(ctx, next.accum, next.guides, h.variance, reinterpret_cast<float4 *>(d_out), nullptr, width, height, passes, s);
-    if (rc != HRT_OK) return rc;
-    h.valid = true;
-    return HRT_OK;
+    const HrtDenoiseVarianceParams vp = variance_params(h_vparams);
+    return temporal_launch(ctx, h_params, h_raygen, h_dparams, h_tparams, &vp, d_out, stream);
 }
 
 int hrt_debug_denoise_variance_state(HrtContext *ctx, float *d_moments, float *d_variance, void *stream) {

@@ -295,6 +295,15 @@ const char *last_error_of(const HrtContext *ctx);
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// the TLAS that a launch's GlobalParams.handle names
+inline int find_tlas(HrtContext *ctx, uint64_t handle, Tlas *&t) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->tlas.find(handle);
+    if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)handle);
+    t = it->second.get();
+    return HRT_OK;
+}
+
 constexpr int kMaxSubTiles = 8;
 
 struct Timer {

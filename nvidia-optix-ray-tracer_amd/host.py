@@ -13,6 +13,11 @@ import ctypes as C
 import numpy as np
 
 
+def _ref(p):
+    """byref of a ctypes structure, None (a NULL pointer: the library's defaults) passed through"""
+    return C.byref(p) if p is not None else None
+
+
 def _f32(x):
     return np.float32(x)
 
@@ -261,8 +266,7 @@ class Renderer:
     def render(self, spp=1, tile=None, sync=True):
         params, rg = self._launch_blocks()
         st = self._stream()
-        self._check(self.lib.hrt_render_launch(self.ctx, C.byref(params), C.byref(rg), spp,
-                                               C.byref(tile) if tile is not None else None, st), "hrt_render_launch")
+        self._check(self.lib.hrt_render_launch(self.ctx, C.byref(params), C.byref(rg), spp, _ref(tile), st), "hrt_render_launch")
         if sync:
             self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
 
@@ -275,14 +279,13 @@ class Renderer:
         return out
 
     # ---- the denoiser (denoiseOutput, src/Global/RendererImpl.cu:680-710) ----
-    def _denoise_params(self, params):
-        from . import DenoiseParams
-        if params is None:
-            return None
-        if isinstance(params, DenoiseParams):
+    def _params(self, cls, default_fn, params):
+        """None (the library's defaults), an instance of the ctypes class ``cls``, or a dict of its fields over the defaults that the
+        library's ``default_fn`` fills in."""
+        if params is None or isinstance(params, cls):
             return params
-        p = DenoiseParams()
-        self._check(self.lib.hrt_denoise_default_params(C.byref(p)), "hrt_denoise_default_params")
+        p = cls()
+        self._check(getattr(self.lib, default_fn)(C.byref(p)), default_fn)
         for k, v in dict(params).items():
             setattr(p, k, v)
         return p
@@ -306,10 +309,11 @@ class Renderer:
         h, w = int(color.shape[0]), int(color.shape[1])
         assert color.is_contiguous() and guides.is_contiguous() and tuple(guides.shape) == (h, w, 8) and guides.element_size() == 2
         out = torch.empty_like(color) if out is None else out
-        p = self._denoise_params(params)
+        from . import DenoiseParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
         st = self._stream()
-        self._check(self.lib.hrt_denoise_filter(self.ctx, color.data_ptr(), guides.data_ptr(), out.data_ptr(), w, h,
-                                                C.byref(p) if p is not None else None, st), "hrt_denoise_filter")
+        self._check(self.lib.hrt_denoise_filter(self.ctx, color.data_ptr(), guides.data_ptr(), out.data_ptr(), w, h, _ref(p), st),
+                    "hrt_denoise_filter")
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return out
 
@@ -318,24 +322,12 @@ class Renderer:
         wrote) -> a new (H, W, 4) float32 tensor, or ``out`` (which may be ``self.color``).  The AOV buffers are not touched."""
         params_blk, rg = self._launch_blocks()
         out = self._torch.empty_like(self.color) if out is None else out
-        p = self._denoise_params(params)
+        from . import DenoiseParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
         st = self._stream()
-        self._check(self.lib.hrt_denoise_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
-                                                out.data_ptr(), st), "hrt_denoise_launch")
+        self._check(self.lib.hrt_denoise_launch(self.ctx, C.byref(params_blk), C.byref(rg), _ref(p), out.data_ptr(), st), "hrt_denoise_launch")
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return out
-
-    def _denoise_temporal_params(self, tparams):
-        from . import DenoiseTemporalParams
-        if tparams is None:
-            return None
-        if isinstance(tparams, DenoiseTemporalParams):
-            return tparams
-        p = DenoiseTemporalParams()
-        self._check(self.lib.hrt_denoise_temporal_default_params(C.byref(p)), "hrt_denoise_temporal_default_params")
-        for k, v in dict(tparams).items():
-            setattr(p, k, v)
-        return p
 
     def denoise_temporal(self, params=None, tparams=None, out=None):
         """The temporal mode of denoiseOutput: the colour buffer blended into the reprojected history of the frames before it, then
@@ -344,10 +336,11 @@ class Renderer:
         change of scene or frame size, equals denoise()."""
         params_blk, rg = self._launch_blocks()
         out = self._torch.empty_like(self.color) if out is None else out
-        p, tp = self._denoise_params(params), self._denoise_temporal_params(tparams)
+        from . import DenoiseParams, DenoiseTemporalParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
+        tp = self._params(DenoiseTemporalParams, "hrt_denoise_temporal_default_params", tparams)
         st = self._stream()
-        self._check(self.lib.hrt_denoise_temporal_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
-                                                         C.byref(tp) if tp is not None else None, out.data_ptr(), st),
+        self._check(self.lib.hrt_denoise_temporal_launch(self.ctx, C.byref(params_blk), C.byref(rg), _ref(p), _ref(tp), out.data_ptr(), st),
                     "hrt_denoise_temporal_launch")
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         self._temporal_shape = (self.height, self.width)
@@ -370,18 +363,6 @@ class Renderer:
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return acc, length, motion
 
-    def _denoise_variance_params(self, vparams):
-        from . import DenoiseVarianceParams
-        if vparams is None:
-            return None
-        if isinstance(vparams, DenoiseVarianceParams):
-            return vparams
-        p = DenoiseVarianceParams()
-        self._check(self.lib.hrt_denoise_variance_default_params(C.byref(p)), "hrt_denoise_variance_default_params")
-        for k, v in dict(vparams).items():
-            setattr(p, k, v)
-        return p
-
     def denoise_filter_variance(self, color, guides, variance, params=None, vparams=None, out=None, var_out=None):
         """The variance-guided filter alone: ``color`` (H, W, 4) float32, ``guides`` (H, W, 8) 16-bit and ``variance`` (H, W) float32
         device tensors -> (colour, variance): new tensors, or ``out`` (may be ``color``) and ``var_out`` (may be ``variance``;
@@ -393,11 +374,12 @@ class Renderer:
         out = torch.empty_like(color) if out is None else out
         if var_out is None:
             var_out = torch.empty_like(variance)
-        p, vp = self._denoise_params(params), self._denoise_variance_params(vparams)
+        from . import DenoiseParams, DenoiseVarianceParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
+        vp = self._params(DenoiseVarianceParams, "hrt_denoise_variance_default_params", vparams)
         st = self._stream()
         self._check(self.lib.hrt_denoise_filter_variance(self.ctx, color.data_ptr(), guides.data_ptr(), variance.data_ptr(), out.data_ptr(),
-                                                         var_out.data_ptr() if var_out is not False else None, w, h,
-                                                         C.byref(p) if p is not None else None, C.byref(vp) if vp is not None else None, st),
+                                                         var_out.data_ptr() if var_out is not False else None, w, h, _ref(p), _ref(vp), st),
                     "hrt_denoise_filter_variance")
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return out, (var_out if var_out is not False else None)
@@ -408,10 +390,12 @@ class Renderer:
         ``out`` (which may be ``self.color``).  Shares its history with denoise_temporal: a call after the other mode starts afresh."""
         params_blk, rg = self._launch_blocks()
         out = self._torch.empty_like(self.color) if out is None else out
-        p, tp, vp = self._denoise_params(params), self._denoise_temporal_params(tparams), self._denoise_variance_params(vparams)
+        from . import DenoiseParams, DenoiseTemporalParams, DenoiseVarianceParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
+        tp = self._params(DenoiseTemporalParams, "hrt_denoise_temporal_default_params", tparams)
+        vp = self._params(DenoiseVarianceParams, "hrt_denoise_variance_default_params", vparams)
         st = self._stream()
-        self._check(self.lib.hrt_denoise_variance_launch(self.ctx, C.byref(params_blk), C.byref(rg), C.byref(p) if p is not None else None,
-                                                         C.byref(tp) if tp is not None else None, C.byref(vp) if vp is not None else None,
+        self._check(self.lib.hrt_denoise_variance_launch(self.ctx, C.byref(params_blk), C.byref(rg), _ref(p), _ref(tp), _ref(vp),
                                                          out.data_ptr(), st), "hrt_denoise_variance_launch")
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         self._temporal_shape = (self.height, self.width)

@@ -1,5 +1,5 @@
 """The denoiser's variance-guided mode on the MI355X (include/hrt.h "Variance-guided mode"; csrc/denoise.hip k_denoise_temporal<true>,
-k_denoise_variance, k_denoise_pass_var): everything bit for bit against the numpy specification (tests/denoise_variance_ref.py), no
+k_denoise_variance, k_denoise_pass<.., true>): everything bit for bit against the numpy specification (tests/denoise_variance_ref.py), no
 tolerance -- the filter alone on synthetic frames, whole sequences over the oracle's primary hits, the rules of the shared history,
 and the other two modes left as they were.  The inputs are tests/denoise_variance_cases.py's; tests/test_denoise_variance_cpu.py
 asserts on the specification that they reach the branches they are for."""
@@ -80,6 +80,30 @@ def test_filter_variance_one_context_grows_and_shrinks(hrt_gpu):
     try:
         for name in vc.GROW_SHRINK:
             _filter_and_check(r, name)
+    finally:
+        r.close()
+
+
+def test_plain_and_variance_filters_share_one_context(hrt_gpu):
+    """hrt_denoise_filter and hrt_denoise_filter_variance in alternation on one context, at sizes that make the frames they share grow
+    between the calls: the variance frames are allocated by the first variance call, after the plain filter has set the capacity, and
+    again after the plain filter has raised it."""
+    r = hrt_gpu.Renderer(0, 0)
+    try:
+        p = {"iterations": 3}
+        for variance, (w, h) in ((False, (5, 3)), (True, (37, 29)), (False, (64, 48)), (True, (17, 5))):
+            what = f"{'variance' if variance else 'plain'} {w}x{h}"
+            rng = np.random.default_rng(dc._seed(what))
+            c, g = dc.plain_color(rng, h, w), dc.random_guides(rng, h, w)
+            if variance:
+                v = vc.plain_variance(rng, h, w)
+                want, want_v = vref.filter_variance(c, g, v, p)
+                out, vo = r.denoise_filter_variance(_dev(c), _dev(g.view(np.int16)), _dev(v), p)
+                _check(_host(vo), want_v, what + " variance")
+            else:
+                want = ref.atrous(c, g, p)
+                out = r.denoise_filter(_dev(c), _dev(g.view(np.int16)), p)
+            _check_rgba(_host(out), want, what + " colour")
     finally:
         r.close()
 

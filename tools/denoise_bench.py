@@ -2,10 +2,10 @@
 first frame of Time mode).  Per scene: a 1-spp render, hrt_denoise_guides, hrt_denoise_filter and hrt_denoise_launch, each the median
 of --reps timed repetitions (HIP events around the Renderer method, after a warm-up: the figure includes the method's argument checks
 and its hrt_sync, so it is a whole-call time, not a sum of kernel times).  Under `rocprofv3 --kernel-trace --stats` the per-kernel
-split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_denoise_pass (one launch per filter pass).
+split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_denoise_pass<3, false> (one launch per filter pass).
 --temporal adds hrt_denoise_temporal_launch (the frame repeated, so that every call after the first blends with a history): its own
 kernel is k_denoise_temporal.  --variance adds hrt_denoise_variance_launch in the same way (k_denoise_temporal<true>,
-k_denoise_variance, k_denoise_pass_var) and hrt_denoise_filter_variance over the frame's guides and a constant variance.
+k_denoise_variance, k_denoise_pass<3, true>: the same pass kernel's variance form) and hrt_denoise_filter_variance over the frame's guides and a constant variance.
 
     python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal] [--variance]
 """
