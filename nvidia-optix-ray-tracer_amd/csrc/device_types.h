@@ -277,5 +277,6 @@ void launch_color_to_float4(const float4 *src, float4 *dst, uint32_t n, hipStrea
 void launch_pack_rays(const float *o, const float *d, uint32_t n, RayRec *rays, hipStream_t s);
 void launch_unpack_hits(const float4 *tuvp, const uint32_t *inst, uint32_t n, float *t, float *u, float *v,
                         uint32_t *prim, uint32_t *oinst, hipStream_t s);
+void launch_fill_misses(float4 *tuvp, uint32_t *inst, uint32_t n, float tmax, uint64_t *rays, hipStream_t s);
 
 }  // namespace hrt

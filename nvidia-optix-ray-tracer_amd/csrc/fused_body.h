@@ -67,6 +67,7 @@ struct InstLane {
                 inst_cur = rn1.y;
                 s.ox = ox; s.oy = oy; s.oz = oz; s.dx = dx; s.dy = dy; s.dz = dz;
                 s.idx = safe_rcp_dir<false>(dx); s.idy = safe_rcp_dir<false>(dy); s.idz = safe_rcp_dir<false>(dz);
+                if (kSlabInterval01) slab_cap_rcp(s.idx, s.idy, s.idz);      // (bt stays the world ray's: the parameter is shared)
                 const uint32_t oct = (dx < 0.0f ? 4u : 0u) | (dy < 0.0f ? 2u : 0u) | (dz < 0.0f ? 1u : 0u);
                 s.oct_inv4 = (7u - oct) * 0x01010101u;
                 child = make_uint2(rn1.x, 0x01000000u);      // one child, no inner-mask bits: the pick below is child base + 0 = the BLAS's root
@@ -189,7 +190,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                 const TravState &s = L.s;
                 // the finished ray and what it hit
                 V3 o = mk3(s.ox, s.oy, s.oz), d = mk3(s.dx, s.dy, s.dz);
-                float bt = s.bt, bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = s.binst;
+                float bt = lean_miss_t(s.bt, s.bprim, a.tmax), bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = s.binst;      // (a miss says tmax)
                 if constexpr (REUSE) {
                     float4 *slot = a.path.primary_cache + 2u * (blockIdx.x * kTraverseBlock + tx);
                     if (cached) {                   // ... or, for a primary ray that was not traversed again, what the pixel's first sample found

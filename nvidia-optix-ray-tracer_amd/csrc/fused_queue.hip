@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
             if (!F.alive && F.waiting) {
                 F.waiting = false;
                 const TravState &s = L.s;
-                queue_write_hit(a, queue_pos(q_index, n_a), s.bt, s.bu, s.bv, s.bprim, s.binst);
+                queue_write_hit(a, queue_pos(q_index, n_a), lean_miss_t(s.bt, s.bprim, tmax_ray), s.bu, s.bv, s.bprim, s.binst);
             }
             const uint64_t need = __ballot(!F.alive);
             bool launch = false;

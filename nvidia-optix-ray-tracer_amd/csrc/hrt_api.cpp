@@ -337,7 +337,11 @@ int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n
         ta.postpone_pct = pk.kernel != PathKernel::Round1 ? ctx->fused_postpone_pct : ctx->postpone_pct;
         const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * pk.blocks_per_cu, (n_rays + 63u) / 64u);
         Timer tm(ctx, s, HRT_K_PATHS);
-        launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s);
+        // An empty interval (tmax <= tmin, or a NaN): every ray misses.  The path kernels' node step divides by bt - tmin (trav_common.h), so
+        // they are not launched on one: the records are filled and the rays counted as the kernel would have.  (k_traverse, below, has no
+        // such limit and takes every interval.)
+        if (pk.kernel != PathKernel::Round1 && !(tmax > tmin)) launch_fill_misses(tuvp, inst, n_rays, tmax, any_hit ? pa.rays_any : pa.rays_closest, s);
+        else launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s);
     } else {
         ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
         ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;

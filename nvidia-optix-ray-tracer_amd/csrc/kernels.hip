@@ -295,7 +295,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             if (alive && !done && has_node) {
                 if (COUNT) { if (in_b) ++cnt_nodes_b; else ++cnt_nodes; }
                 uint2 child;
-                node_slab_test(s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+                node_slab_test<false>(s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
                 s.cur = child;
             }
             has_node = false; nidx = 0u;
@@ -608,6 +608,14 @@ __global__ __launch_bounds__(256) void k_unpack_hits(const float4 *tuvp, const u
     const float4 h = tuvp[i];
     t[i] = h.x; u[i] = h.y; v[i] = h.z; prim[i] = __float_as_uint(h.w); oinst[i] = inst[i];
 }
+// the hit records of n rays that cannot hit anything (an empty interval, tmax <= tmin: answered without a traversal); `rays`: the counter
+// the path kernel would have added them to
+__global__ __launch_bounds__(256) void k_fill_misses(float4 *tuvp, uint32_t *inst, uint32_t n, float tmax, uint64_t *rays) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0u && rays) atomicAdd(reinterpret_cast<unsigned long long *>(rays), (unsigned long long)n);
+    if (i >= n) return;
+    tuvp[i] = make_float4(tmax, 0.0f, 0.0f, __uint_as_float(kMissPrim)); inst[i] = kMissPrim;
+}
 
 // ---------------------------------------------------------------------------------------
 // host launchers
@@ -668,6 +676,9 @@ void launch_pack_rays(const float *o, const float *d, uint32_t n, RayRec *rays, 
 void launch_unpack_hits(const float4 *tuvp, const uint32_t *inst, uint32_t n, float *t, float *u, float *v,
                         uint32_t *prim, uint32_t *oinst, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_unpack_hits, dim3(ceil_div(n, 256)), dim3(256), 0, s, tuvp, inst, n, t, u, v, prim, oinst);
+}
+void launch_fill_misses(float4 *tuvp, uint32_t *inst, uint32_t n, float tmax, uint64_t *rays, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_fill_misses, dim3(ceil_div(n, 256)), dim3(256), 0, s, tuvp, inst, n, tmax, rays);
 }
 
 }  // namespace hrt

@@ -387,17 +387,60 @@ __device__ __forceinline__ void wait_node_loads(u32x4 &a, u32x4 &b, u32x4 &c, u3
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) :: "memory");
 }
 
+// The slab test's two forms.  0: the planes' distances clamped to the ray's interval [tmin, bt] with a max and a min per child (the form
+// k_traverse keeps: exact reciprocals in its counting build, no limits).  1, the path kernels' (trav_loop.h): the interval mapped onto
+// [0, 1] once per node step, in essence t' = (t - tmin) k with k = 1 / (bt - tmin) folded into the six coefficients, so that the clamp rides on the
+// z axis' FMAs as their `clamp` output modifier: max3(tnx', tny', clamp(tnz')) = max(N', 0), min3(tfx', tfy', clamp(tfz')) = min(F', 1).
+// -DHRT_SLAB_INTERVAL01=0 builds form 0 everywhere (A/B of two libraries; DESIGN.md 4.1 has the ranges and the error budget).
+#ifndef HRT_SLAB_INTERVAL01
+#define HRT_SLAB_INTERVAL01 1
+#endif
+constexpr bool kSlabInterval01 = HRT_SLAB_INTERVAL01 != 0;
+// Exactly: t' = (t (1 - 2^-20) - tmin) k with k = 1 / ((bt - tmin) + 2^-36).
+//   * The factor makes the bt end conservative: bt maps to 1 - 2^-20 at most, 2^4 ulps below the clamp and far above the one ulp of
+//     v_rcp_f32 (tmin maps to -2^-20 tmin k <= 0: conservative too).  It is folded into the ray's reciprocals where the ray starts, so the
+//     loop does not pay for it.
+//   * The floor keeps k finite (<= 2^36) when a hit has come within nothing of tmin -- a denormal bt - tmin would make k infinite,
+//     0 * inf a NaN and the clamp a 0 on both sides: a cull.  It is a literal of the add; it only lowers k (bt maps lower still) and
+//     vanishes in the rounding once bt - tmin > 2^-12.  (A ray whose hits all lie below 2^-36 -- a direction of length 1e30 with
+//     tmin = 0 -- is culled at its bt end by nothing any more: slower, not wrong.)
+constexpr float kSlabSpanSlack = 1.0f - 0x1p-20f, kSlabSpanFloor = 0x1p-36f;
+// The products idx k, (p - o) idx k and the per-cell step 2^e idx k must neither underflow nor overflow.  That is settled where a ray
+// starts (lean_start; slab_cap_rcp also where the instanced kernel's lane enters an instance), not in the loop:
+//   * the culling bound starts at min(tmax, kSlabReach / max |d_c|), so |d_c| (bt - tmin) <= 2^64 and |idx k| >= 2^-65 for the largest
+//     component, more for the others: the step 2^e idx k stays a normal float for cells down to 2^-60 (a scene of 2^-52);
+//   * a reciprocal is at most kSlabRcpRatio times the smallest of the three, i.e. a component below 2^-40 of the largest counts as that
+//     (safe_rcp_dir's 1e-20 is the same approximation with an absolute bound: over a scene of extent S the ray it stands for leaves the
+//     true one by 2^-40 * 12 S, against a padding of 4e-6 S).  With k <= 2^36, |idx| <= 1e20 and |p - o| <= 2^25 every product is finite.
+constexpr float kSlabReach = 0x1p64f, kSlabRcpRatio = 0x1p40f;
+// caps idx / idy / idz and folds the slack into them; returns the smallest of their magnitudes before that, 1 / max |d_c|
+__device__ __forceinline__ float slab_cap_rcp(float &idx, float &idy, float &idz) {
+    const float m = fminf(fminf(fabsf(idx), fabsf(idy)), fabsf(idz)), cap = m * kSlabRcpRatio;
+    idx = copysignf(fminf(fabsf(idx), cap) * kSlabSpanSlack, idx); idy = copysignf(fminf(fabsf(idy), cap) * kSlabSpanSlack, idy);
+    idz = copysignf(fminf(fabsf(idz), cap) * kSlabSpanSlack, idz);
+    return m;
+}
+
 // the node step: slab test of the eight quantised children of the node in rn0..rn4 against the ray in `s`; returns the children's
 // sibling group (first child, hit bits 31..24 | inner mask; y <= 0xffffff: none) and leaf group (first primitive, bit per primitive that
 // may be hit; y == 0: none)
+template <bool kInterval01>
 __device__ __forceinline__ void node_slab_test(const TravState &s, float tmin, const u32x4 rn0, const u32x4 rn1, const u32x4 rn2, const u32x4 rn3,
                                           const u32x4 rn4, uint2 &child, uint2 &tri) {
     const float px = __uint_as_float(rn0.x), py = __uint_as_float(rn0.y), pz = __uint_as_float(rn0.z);
     const uint32_t e_imask = rn0.w;
-    const float aix = __uint_as_float((e_imask & 0xffu) << 23) * s.idx;
-    const float aiy = __uint_as_float(((e_imask >> 8) & 0xffu) << 23) * s.idy;
-    const float aiz = __uint_as_float(((e_imask >> 16) & 0xffu) << 23) * s.idz;
-    const float aox = (px - s.ox) * s.idx, aoy = (py - s.oy) * s.idy, aoz = (pz - s.oz) * s.idz;
+    float kx = s.idx, ky = s.idy, kz = s.idz, c0 = 0.0f;
+    if (kInterval01) {
+        // (k is made again in every node step: a value kept alive across the loop costs more here than these three instructions)
+        const float k = __builtin_amdgcn_rcpf((s.bt - tmin) + kSlabSpanFloor);
+        kx = s.idx * k; ky = s.idy * k; kz = s.idz * k; c0 = -(tmin * k);
+    }
+    const float aix = __uint_as_float((e_imask & 0xffu) << 23) * kx;
+    const float aiy = __uint_as_float(((e_imask >> 8) & 0xffu) << 23) * ky;
+    const float aiz = __uint_as_float(((e_imask >> 16) & 0xffu) << 23) * kz;
+    const float aox = kInterval01 ? fmaf(px - s.ox, kx, c0) : (px - s.ox) * kx;
+    const float aoy = kInterval01 ? fmaf(py - s.oy, ky, c0) : (py - s.oy) * ky;
+    const float aoz = kInterval01 ? fmaf(pz - s.oz, kz, c0) : (pz - s.oz) * kz;
     const bool nx = s.dx < 0.0f, ny = s.dy < 0.0f, nz = s.dz < 0.0f;
     uint32_t hitmask = 0u;
 #pragma unroll
@@ -417,12 +460,20 @@ __device__ __forceinline__ void node_slab_test(const TravState &s, float tmin, c
             const float tnx = fmaf(HRT_BYTE_F(xn, j), aix, aox), tfx = fmaf(HRT_BYTE_F(xf, j), aix, aox);
             const float tny = fmaf(HRT_BYTE_F(yn, j), aiy, aoy), tfy = fmaf(HRT_BYTE_F(yf, j), aiy, aoy);
             const float tnz = fmaf(HRT_BYTE_F(zn, j), aiz, aoz), tfz = fmaf(HRT_BYTE_F(zf, j), aiz, aoz);
-            const float tlo = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
-            const float thi = fminf(fminf(tfx, tfy), fminf(tfz, s.bt));
             const uint32_t cb = (child_bits4 >> (8 * j)) & 0xffu;
             const uint32_t bi = (bit_index4 >> (8 * j)) & 0xffu;
             // conservative: the builder pads and rounds the child boxes outwards
-            if (tlo <= thi) hitmask |= cb << bi;
+            if (kInterval01) {
+                // med3(x, 0, 1) of an FMA's result is the FMA's clamp modifier (DX10 clamp: NaN -> 0).  Strict: with both ends clamped a box
+                // wholly before tmin gives 0 against 0 and one wholly beyond bt 1 against 1; padded boxes have thickness.
+                const float tlo = fmaxf(fmaxf(tnx, tny), __builtin_amdgcn_fmed3f(tnz, 0.0f, 1.0f));
+                const float thi = fminf(fminf(tfx, tfy), __builtin_amdgcn_fmed3f(tfz, 0.0f, 1.0f));
+                if (tlo < thi) hitmask |= cb << bi;
+            } else {
+                const float tlo = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
+                const float thi = fminf(fminf(tfx, tfy), fminf(tfz, s.bt));
+                if (tlo <= thi) hitmask |= cb << bi;
+            }
         }
     }
     child = make_uint2(rn1.x, (hitmask & 0xff000000u) | (e_imask >> 24));

@@ -43,12 +43,19 @@ __device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray) {
     L.s.ox = L.s.oy = L.s.oz = 0.0f; L.s.dx = L.s.dy = 0.0f; L.s.dz = 1.0f; L.s.idx = L.s.idy = L.s.idz = 1.0f; L.s.oct_inv4 = 0u;
 }
 
-// a new ray: the root is its first node
+// a new ray: the root is its first node.  The node step's interval form (trav_common.h: kSlabInterval01) wants the ray's range settled
+// here: slab_cap_rcp caps the reciprocals, and the culling bound starts at min(tmax, 2^64 / max |d_c|) -- a reach of 2^64 world units
+// that no scene comes near; a normalised ray's 1e16 is untouched.  A ray that misses therefore may end with bt below tmax: lean_miss_t
+// is what its record says.
 __device__ __forceinline__ void lean_start(LeanLane &L, V3 o, V3 d, float tmax_ray) {
     trav_start<false>(L.s, o, d, tmax_ray);
+    if (kSlabInterval01) L.s.bt = fminf(tmax_ray, kSlabReach * slab_cap_rcp(L.s.idx, L.s.idy, L.s.idz));
     lean_reset(L);
     L.nidx = 0u;
 }
+
+// the t of a finished ray's hit record: tmax for a miss, whatever lean_start made of the culling bound
+__device__ __forceinline__ float lean_miss_t(float bt, uint32_t bprim, float tmax_ray) { return kSlabInterval01 && bprim == kMissPrim ? tmax_ray : bt; }
 
 // the next node of a lane that has just been handed a sibling group (tail splitting): its nearest child -- step (7) of
 // lean_bookkeeping_masked in C++

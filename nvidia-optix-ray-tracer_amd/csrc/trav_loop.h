@@ -203,10 +203,10 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         wait_node_loads(rn0, rn1, rn2, rn3, rn4);
         [[maybe_unused]] bool enter = false;
         if constexpr (!INSTANCED) {
-            node_slab_test(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            node_slab_test<kSlabInterval01>(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
         } else {
             enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
-            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test<kSlabInterval01>(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
             enter = I.enter_instance(enter, L.s, child, rn0, rn1, rn2, rn3, rn4, mb, tx);
             stats.entered(enter);
         }
