@@ -171,13 +171,13 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     [[maybe_unused]] bool force_regen = false;      // (REUSE, wave-uniform)
     [[maybe_unused]] bool cached = false;           // (REUSE) this lane waits to be shaded with its pixel's cached primary hit
     for (;;) {
-        const uint64_t idle = __ballot(!F.alive);
+        const uint64_t idle = ~F.alive;
         const uint32_t n_idle = (uint32_t)__popcll(idle);
         // ---- regenerate: shade finished rays in place, start the next sample / pixel ----
         // (once the tile is used up the lanes without a pixel stay idle and the render ends with the slowest pixels' sample chains:
         // what counts then is how soon a finished ray's successor starts, against what a regeneration costs the rays still under
         // way -- a dozen waiting rays, or nothing else left to do: 1/8 of the C4 frame 142 ms with 1, 129 ms with 8 to 16)
-        if (force_regen || idle == ~0ull || (exhausted ? (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
+        if (force_regen || idle == ~0ull || (exhausted ? (uint32_t)__popcll(F.waiting) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
             stats.regeneration();
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
             const TraverseArgs &a = kernarg_traverse_args();      // (hides the parameter on purpose: nothing in this block reads the entry's copy)
@@ -185,8 +185,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             [[maybe_unused]] bool reshade = false;
             [[maybe_unused]] const bool was_forced = force_regen;
             force_regen = false;
-            if (!F.alive && F.waiting) {
-                F.waiting = false;
+            const uint64_t finished = F.waiting & ~F.alive;
+            F.waiting &= F.alive;
+            if (lane_bit(finished)) {
                 const TravState &s = L.s;
                 // the finished ray and what it hit
                 V3 o = mk3(s.ox, s.oy, s.oz), d = mk3(s.dx, s.dy, s.dz);
@@ -204,32 +205,36 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                 }
                 st = path_finish<HAS_SPHERES, REUSE, BLOCKS>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
             }
-            exhausted = path_take<BLOCKS>(P, st, a, n_pixels, !F.alive && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
+            exhausted = path_take<BLOCKS>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
             stats.drained(exhausted);
             if (st.want_primary) {
                 bool from_cache = false;
                 if constexpr (REUSE) from_cache = !a.path.trace_rays && P.px_sample > 0u;
                 if (from_cache) {
                     // a pixel's later primary rays are not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
-                    P.px_depth = 1u; F.waiting = true; cached = true; reshade = true;
+                    P.px_depth = 1u; cached = true; reshade = true;      // (F.waiting: below)
                 } else {
                     const PathRay r = path_primary<false>(P, a);
                     st.ro = r.o; st.rd = r.d; st.launch = true;
                 }
             }
+            bool any_hit = false;
             if (st.launch) {
-                F.any = path_count_ray(P);
+                any_hit = path_count_ray(P);
                 lean_start(L, st.ro, st.rd, tmax_ray);
                 if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
-                F.alive = true;
             }
+            // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
+            const uint64_t launched = __ballot(st.launch);
+            F.alive |= launched; F.any = (F.any & ~launched) | __ballot(any_hit);
+            if constexpr (REUSE) F.waiting |= __ballot(reshade);
             // REUSE: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that
             // their bounces start together with the other lanes' rays (one extra round, not more: the others are waiting)
             if constexpr (REUSE) { if (!was_forced && __ballot(reshade) != 0ull) { force_regen = true; continue; } }
         }
         // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, REUSE, a lane with a cached hit to shade:
         // an empty pass through the loop below brings it back here)
-        if (__ballot(REUSE ? F.alive || F.waiting : F.alive) == 0ull) {
+        if ((REUSE ? F.alive | F.waiting : F.alive) == 0ull) {
             bool leave = true;
             if constexpr (BLOCKS) leave = B.need == 0u;
             if (leave) break;

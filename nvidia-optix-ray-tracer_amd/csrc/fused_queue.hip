@@ -51,16 +51,17 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
     const uint32_t home_shard = blockIdx.x & (kFetchShards - 1);
 
     for (;;) {
-        const uint64_t idle = __ballot(!F.alive);
+        const uint64_t idle = ~F.alive;
         const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (idle == ~0ull || (exhausted ? (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
+        if (idle == ~0ull || (exhausted ? (uint32_t)__popcll(F.waiting) >= (uint32_t)a.tail_regen : n_idle >= (uint32_t)a.refill_threshold)) {
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
-            if (!F.alive && F.waiting) {
-                F.waiting = false;
+            const uint64_t finished = F.waiting & ~F.alive;
+            F.waiting &= F.alive;
+            if (lane_bit(finished)) {
                 const TravState &s = L.s;
                 queue_write_hit(a, queue_pos(q_index, n_a), lean_miss_t(s.bt, s.bprim, tmax_ray), s.bu, s.bv, s.bprim, s.binst);
             }
-            const uint64_t need = __ballot(!F.alive);
+            const uint64_t need = ~F.alive;
             bool launch = false;
             if (need != 0ull && !exhausted) {
                 if (wbeg >= wend) {
@@ -73,18 +74,20 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
                     const uint32_t rank = lane_prefix(need);
                     const uint32_t mine = wbeg + rank;
                     wbeg += take;
-                    if (!F.alive && rank < take) { q_index = mine; launch = true; }
+                    if (lane_bit(need) && rank < take) { q_index = mine; launch = true; }
                 }
             }
+            bool any_hit = false;
             if (launch) {
                 const QueuePos qp = queue_pos(q_index, n_a);
                 const RayRec r = queue_ray(a, qp);
-                F.any = queue_any_hit(a, qp);
+                any_hit = queue_any_hit(a, qp);
                 lean_start(L, mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z), tmax_ray);
-                F.alive = true;
             }
+            const uint64_t launched = __ballot(launch);
+            F.alive |= launched; F.any = (F.any & ~launched) | __ballot(any_hit);
         }
-        if (__ballot(F.alive) == 0ull) break;
+        if (F.alive == 0ull) break;
 
         // ---- traverse until enough lanes have finished (trav_loop.h); once the queue is used up, the copy with tail splitting: every idle
         //      lane may take a piece.  The leaf stack is used to its full depth (leaf_hold 4). ----

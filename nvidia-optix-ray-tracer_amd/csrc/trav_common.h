@@ -274,6 +274,20 @@ __device__ __forceinline__ void trav_start(TravState &s, V3 o, V3 d, float tmax_
     s.bt = tmax_ray; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
 }
 
+// A condition of the primitive test as the WHOLE WAVE's: one bit per lane in a scalar register pair, where `bool` is one lane's.  Made
+// from a bool it is that compare's ballot, and & and | are scalar instructions -- the very instructions the compiler makes of a chain of
+// per-lane bools.  What differs is that the outcome is there as a mask: the path kernels' loop (trav_loop.h) does mask arithmetic with
+// it, where the ballot of a per-lane bool that is no single compare costs a v_cndmask 0 / 1 and a v_cmp.  All lanes must be active.
+struct WaveCond {
+    uint64_t m;
+    __device__ __forceinline__ WaveCond(bool c) : m(__ballot(c)) {}
+    __device__ __forceinline__ explicit WaveCond(uint64_t mask) : m(mask) {}
+    __device__ __forceinline__ WaveCond operator&(WaveCond o) const { return WaveCond(m & o.m); }
+    __device__ __forceinline__ WaveCond operator|(WaveCond o) const { return WaveCond(m | o.m); }
+};
+__device__ __forceinline__ bool cond_lane(bool c) { return c; }                  // this lane's outcome of a condition of either kind
+__device__ __forceinline__ bool cond_lane(WaveCond c) { return __builtin_amdgcn_inverse_ballot_w64(c.m); }
+
 // canonical primitive test (DESIGN.md "canonical intersector"); updates the best hit.
 // INSTANCED (two-level trees, fused.hip): the record is a shared BLAS's, in object space, and so is the ray in `s` by now (the transform
 // node did that for triangles and spheres alike); the record does not know who instances it: `inst_cur` does.
@@ -281,11 +295,13 @@ __device__ __forceinline__ void trav_start(TravState &s, V3 o, V3 d, float tmax_
 // instance's object-space ray in LDS while its registers hold the world ray again)
 // (live, triangles only: false rejects the record -- the caller's lane has none and A / B / C are whatever its registers held; the
 // test still runs, so that the caller needs no per-lane branch round it)
-template <bool HAS_SPHERES, bool INSTANCED = false>
-__device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
+// (Cond: bool, or WaveCond -- triangles only, every lane active -- for the outcome as a wave mask)
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool>
+__device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
                                               const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
-                                              bool live = true) {
+                                              Cond live = true) {
+    static_assert(!HAS_SPHERES || sizeof(Cond) == sizeof(bool), "spheres are tested under per-lane control flow");
     float t, u = 0.0f, v = 0.0f;
     uint32_t prim = __float_as_uint(A.w), inst;
     if (HAS_SPHERES && __float_as_uint(C.w) == 1u) {
@@ -330,15 +346,16 @@ __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, co
         const V3 qvec = cross3(tvec, e1);
         v = dot3(d, qvec) * inv;
         t = dot3(e2, qvec) * inv;
-        const bool ok = live & (det != 0.0f) & (u >= 0.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (t > tmin) & (t < tmax_ray);
+        const Cond ok = live & Cond(det != 0.0f) & Cond(u >= 0.0f) & Cond(v >= 0.0f) & Cond(u + v <= 1.0f) & Cond(t > tmin) & Cond(t < tmax_ray);
         if (!HAS_SPHERES) {
             // closest hit: min t, ties -> lowest (instance, primitive); predicated update
-            const bool better = ok & ((t < s.bt) | ((t == s.bt) & ((inst < s.binst) | ((inst == s.binst) & (prim < s.bprim)))));
-            s.bt = better ? t : s.bt; s.bu = better ? u : s.bu; s.bv = better ? v : s.bv;
-            s.bprim = better ? prim : s.bprim; s.binst = better ? inst : s.binst;
+            const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & (Cond(inst < s.binst) | (Cond(inst == s.binst) & Cond(prim < s.bprim)))));
+            const bool mine = cond_lane(better);
+            s.bt = mine ? t : s.bt; s.bu = mine ? u : s.bu; s.bv = mine ? v : s.bv;
+            s.bprim = mine ? prim : s.bprim; s.binst = mine ? inst : s.binst;
             return better;
         }
-        if (!ok) return false;
+        if (!cond_lane(ok)) return false;
     }
     // closest hit: min t, ties -> lowest (instance, primitive)
     bool better = t < s.bt;
@@ -350,12 +367,12 @@ __device__ __forceinline__ bool test_prim_ray(const float4 A, const float4 B, co
     return better;
 }
 
-template <bool HAS_SPHERES, bool INSTANCED = false>
-__device__ __forceinline__ bool test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool>
+__device__ __forceinline__ Cond test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
                                           const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
-                                          bool live = true) {
-    return test_prim_ray<HAS_SPHERES, INSTANCED>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
+                                          Cond live = true) {
+    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))

@@ -23,14 +23,22 @@ namespace hrt {
 #define HRT_PRIO_REGEN 2     // the kernels' own phase: shading or hit stores, next pixel or queue entry, new ray
 #endif
 
-// what a lane is doing with its ray
+// What a lane is doing with its ray.  `alive`, `waiting` and `any` are WAVE MASKS, one bit per lane, the same value in every lane (scalar
+// registers): all the loop does with them is wave-level -- the lanes the bookkeeping runs for, the population counts of the exit rules --
+// and as a per-lane bool each cost a conversion to a mask and back in every iteration.  A lane reads its bit with lane_bit(); a write
+// under per-lane control flow is a mask update from a ballot of the condition, made where every lane of the wave is active.
 struct LaneFlags {
-    bool alive = false;         // a ray is being traversed in this lane
-    bool waiting = false;       // ... has finished and waits for the next regeneration
-    bool any = false;           // this lane's ray only needs to know whether anything is hit
+    uint64_t alive = 0ull;      // a ray is being traversed in this lane
+    uint64_t waiting = 0ull;    // ... has finished and waits for the next regeneration
+    uint64_t any = 0ull;        // this lane's ray only needs to know whether anything is hit
     bool shared = false;        // this lane works on a piece of a ray that has been split across lanes (tail splitting)
     uint32_t home;              // ... whose owner is this lane (the lane itself while nothing is shared)
 };
+
+// a wave mask that the compiler holds per lane, in a scalar register pair again (it IS the same in every lane)
+__device__ __forceinline__ uint64_t wave_first_u64(uint64_t v) { return ((uint64_t)wave_first_u32((uint32_t)(v >> 32)) << 32) | wave_first_u32((uint32_t)v); }
+// this lane's bit of a wave mask (no instruction: the mask is used as the lane condition it is)
+__device__ __forceinline__ bool lane_bit(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
 // The wave's tail-splitting mailboxes: __shared__ arrays of kTraverseBlock entries each, declared in the kernels.  One mailbox
 // per lane that owns a split ray (indexed by its home lane) collects the pieces' hits; `pending` counts the pieces still under
@@ -57,12 +65,12 @@ struct NoInstLane { static constexpr uint32_t inst_cur = 0u; };
 // (one donation per busy lane and iteration: more rounds of this change nothing, r02_sweep_tile_tail.txt)
 __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmax_ray) {
     const uint64_t free_m = __ballot(is_free);
-    const uint64_t donors = __ballot(F.alive && L.nsp > L.base);
+    const uint64_t donors = F.alive & __ballot(L.nsp > L.base);
     const uint32_t n_free = (uint32_t)__popcll(free_m), n_don = (uint32_t)__popcll(donors);
     const uint32_t n_pairs = n_free < n_don ? n_free : n_don;
     if (n_pairs) {
         const uint32_t drank = lane_prefix(donors), irank = lane_prefix(free_m);
-        const bool is_donor = F.alive && L.nsp > L.base && drank < n_pairs;
+        const bool is_donor = lane_bit(donors) && drank < n_pairs;
         const bool is_recv = is_free && irank < n_pairs;
         uint2 give = make_uint2(0u, 0u);
         if (is_donor) {
@@ -82,15 +90,17 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
         TravState &s = L.s;
         const float r_ox = __shfl(s.ox, src), r_oy = __shfl(s.oy, src), r_oz = __shfl(s.oz, src);
         const float r_dx = __shfl(s.dx, src), r_dy = __shfl(s.dy, src), r_dz = __shfl(s.dz, src);
-        const uint32_t r_home = (uint32_t)__shfl((int)(F.home | (F.any ? 0x100u : 0u)), src);
+        const uint32_t r_home = (uint32_t)__shfl((int)(F.home | (lane_bit(F.any) ? 0x100u : 0u)), src);
         const uint32_t r_gx = (uint32_t)__shfl((int)give.x, src), r_gy = (uint32_t)__shfl((int)give.y, src);
         if (is_recv) {
             lean_start(L, mk3(r_ox, r_oy, r_oz), mk3(r_dx, r_dy, r_dz), tmax_ray);     // the same reciprocals and octant as the owner's
-            F.home = r_home & 0xffu; F.any = (r_home & 0x100u) != 0u; F.shared = true; F.alive = true;
+            F.home = r_home & 0xffu; F.shared = true;
             s.bt = mb.t[F.home]; s.bu = mb.u[F.home]; s.bv = mb.v[F.home]; s.bprim = mb.prim[F.home]; s.binst = mb.inst[F.home];
             s.cur = make_uint2(r_gx, r_gy);           // a sibling group with hits: only those are pushed
             lean_pick_node(L);                        // (replaces the root lean_start chose)
         }
+        const uint64_t recv = __ballot(is_recv);
+        F.alive |= recv; F.any = (F.any & ~recv) | (recv & __ballot((r_home & 0x100u) != 0u));      // (a piece asks what its ray asks)
     }
 }
 
@@ -105,7 +115,7 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
             const float mt = mb.t[F.home];
             const uint64_t mid = ((uint64_t)mb.inst[F.home] << 32) | mb.prim[F.home];
             const uint64_t id = ((uint64_t)s.binst << 32) | s.bprim;
-            if (F.any ? mb.prim[F.home] == kMissPrim : (s.bt < mt || (s.bt == mt && id < mid))) {
+            if (lane_bit(F.any) ? mb.prim[F.home] == kMissPrim : (s.bt < mt || (s.bt == mt && id < mid))) {
                 mb.t[F.home] = s.bt; mb.u[F.home] = s.bu; mb.v[F.home] = s.bv; mb.prim[F.home] = s.bprim; mb.inst[F.home] = s.binst;
             }
         }
@@ -117,8 +127,8 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
 // ... and take over what another piece has found closer; an any-hit ray is done once any piece has hit.  Returns the lane's hit_any
 // (by value on purpose: as a `bool &` it cost each one-level k_fused three more spilled registers)
 __device__ __forceinline__ bool tail_adopt(LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool hit_any) {
-    if (F.alive && F.shared) {
-        if (F.any) hit_any = hit_any || mb.prim[F.home] != kMissPrim;
+    if (lane_bit(F.alive) && F.shared) {
+        if (lane_bit(F.any)) hit_any = hit_any || mb.prim[F.home] != kMissPrim;
         else if (mb.t[F.home] < L.s.bt) {
             L.s.bt = mb.t[F.home]; L.s.bu = mb.u[F.home]; L.s.bv = mb.v[F.home]; L.s.bprim = mb.prim[F.home]; L.s.binst = mb.inst[F.home];
         }
@@ -129,18 +139,21 @@ __device__ __forceinline__ bool tail_adopt(LeanLane &L, const LaneFlags &F, cons
 // a piece whose lane reports `done` retires; the owner of the ray takes the merged hit once the last piece has
 __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mailboxes &mb, bool done, uint32_t tx) {
     // a piece that has finished has nothing left to merge: the mailbox holds the ray's best hit
-    if (F.alive && done && F.shared) {
+    const bool retires = lane_bit(F.alive) && done && F.shared;
+    if (retires) {
         atomicSub(&mb.pending[F.home], 1u);
-        F.alive = false;
         if (F.home != tx) { F.shared = false; F.home = tx; }        // a helper is free again; the owner waits for the last piece
     }
+    F.alive &= ~__ballot(retires);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // the owner of a split ray picks the merged hit up once its last piece has finished
-    if (F.shared && !F.alive && F.home == tx && mb.pending[tx] == 0u) {
+    const bool merged = F.shared && !lane_bit(F.alive) && F.home == tx && mb.pending[tx] == 0u;
+    if (merged) {
         L.s.bt = mb.t[tx]; L.s.bu = mb.u[tx]; L.s.bv = mb.v[tx]; L.s.bprim = mb.prim[tx]; L.s.binst = mb.inst[tx];
-        F.shared = false; F.waiting = true;
+        F.shared = false;
     }
+    F.waiting |= __ballot(merged);
 }
 
 // ---- traverse until enough lanes have finished to make a regeneration worthwhile ----
@@ -161,41 +174,66 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
     f32x4 rpa, rpb, rpc;
     u32x4 rn0, rn1, rn2, rn3, rn4;
     asm volatile("" : "=v"(rpa), "=v"(rpb), "=v"(rpc), "=v"(rn0), "=v"(rn1), "=v"(rn2), "=v"(rn3), "=v"(rn4));
+    // The lanes that want a primitive / a node.  The bookkeeping sequence has just had both in exec and hands them out, so the one-level
+    // copy without tail splitting carries them round the loop; found by compare where something else writes pidx / nidx: a new ray (here,
+    // at the entry), tail_donate (the kTail copy), switch_frames (INSTANCED).
+    constexpr bool kCarryWork = !kTail && !INSTANCED;
+    // The same copy uses the blocks' exec-is-full forms (trav_lean.h: nothing saved, exec set back to all ones).  Every lane IS active at the
+    // top level of this loop's body: a workgroup is one wave of exactly kTraverseBlock = 64 lanes (static_assert and launch), and every
+    // branch round the loop and round this call -- the regeneration's, the choice of the copy, the exits -- is taken on a value that is the
+    // same in all lanes (counts of the flag masks, `exhausted`).  Nothing in this copy's body leaves a lane switched off: the primitive
+    // test's `if` is on a mask's emptiness, and the blocks restore exec themselves.  The other copies keep the saving forms: their bodies
+    // call helpers with per-lane control flow of their own (tail splitting, InstLane), which this argument does not cover.
+    constexpr bool kFull = kCarryWork;
+    // The flag masks in scalar registers for the loop.  Between two calls the compiler keeps them in vector register pairs: the kernels
+    // choose this copy or the other by `exhausted`, which is wave-uniform but a per-lane value to the compiler, and whatever is merged
+    // behind such a branch is per-lane to it as well.  (Making those branches scalar instead keeps the masks where they are, and spills
+    // 22 to 49 VGPRs round the regeneration of every one-level kernel: profiles/r17_wave_masks.txt.)
+    F.alive = wave_first_u64(F.alive); F.waiting = wave_first_u64(F.waiting); F.any = wave_first_u64(F.any);
+    uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
     for (;;) {
-        if (kSplit && a.tail_split) tail_donate(L, F, mb, nodes, !F.alive && !F.waiting && may_help && !F.shared, tx, tmax_ray);
+        if (kSplit && a.tail_split) tail_donate(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmax_ray);
 
         // ---- G. fetch what the lanes need next: primitives first, nodes second -- for the lanes that need one only (the
         //      instruction slots of the loads are not saved, but their L1 / TA cycles are).  The node loads are issued even when
         //      no lane wants one: they are then ALWAYS the five youngest vector-memory operations at the primitives' wait,
         //      whose vmcnt(5) is counted by hand. ----
-        const uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
+        if constexpr (!kCarryWork) { mask_p = __ballot(L.pidx != kNoWork); mask_n0 = __ballot(L.nidx != kNoWork); }
         {
             uint32_t po = L.pidx * a.prim_stride, no = L.nidx * a.node_stride;      // (garbage for kNoWork: masked out)
             asm volatile("" : "+v"(po), "+v"(no));          // both offsets before the first load
-            if (mask_p != 0ull) issue_prim_loads_off(mask_p, prim_bytes, po, rpa, rpb, rpc);
-            issue_node_loads_off(mask_n0, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
+            if (mask_p != 0ull) issue_prim_loads_off<kFull>(mask_p, prim_bytes, po, rpa, rpb, rpc);
+            issue_node_loads_off<kFull>(mask_n0, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
             __builtin_amdgcn_s_setprio(HRT_PRIO_PRIM);
         }
-        stats.iteration(F.alive, mask_n0, mask_p);
+        stats.iteration(lane_bit(F.alive), mask_n0, mask_p);
         // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight).  Triangles:
         //      every lane tests (straight-line arithmetic, no loads) and a lane without a primitive rejects whatever its
         //      registers hold -- some lane nearly always has one, so a per-lane branch would save nothing but cost a mask
         //      save, a branch and a restore.  Spheres read the instance table: only lanes with a primitive test. ----
-        bool hit_any = false, improved = false;
-        if (mask_p != 0ull) {
+        uint64_t hit_m = 0ull, improved_m = 0ull;           // wave masks: a closer hit was found; ... by an any-hit ray
+        // (the same test as at the loads, on a copy the compiler cannot see through: it would otherwise keep the first one's outcome in a
+        // register pair across the loads and test that -- two scalar instructions more than comparing again)
+        uint64_t any_p = mask_p;
+        asm volatile("" : "+s"(any_p));
+        if (any_p != 0ull) {
             wait_prim_loads(rpa, rpb, rpc);
             const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
                          pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
             if constexpr (!HAS_SPHERES)
-                improved = test_prim<false, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, L.pidx != kNoWork);
-            else if (L.pidx != kNoWork)
-                improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
-            hit_any = F.any & improved;
+                improved_m = test_prim<false, INSTANCED, WaveCond>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p)).m;
+            else {
+                bool improved = false;
+                if (L.pidx != kNoWork) improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
+                improved_m = __ballot(improved);
+            }
+            hit_m = F.any & improved_m;
         }
         if (kSplit && a.tail_split) {
-            tail_publish(L, F, mb, improved, tx);
-            hit_any = tail_adopt(L, F, mb, hit_any);
+            tail_publish(L, F, mb, lane_bit(improved_m), tx);
+            hit_m = __ballot(tail_adopt(L, F, mb, lane_bit(hit_m)));
         }
+        const bool hit_any = lane_bit(hit_m);
         // ---- A. node step: one-level trees, for the whole wave (arithmetic only; what lanes without a node made of their
         //      registers is not filed: mask_n0 below) ----
         uint2 child = make_uint2(0u, 0u), tri = make_uint2(0u, 0u);
@@ -219,27 +257,30 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         if (hit_any) { L.nidx = kNoWork; L.pidx = kNoWork; }
         // the sequence runs for the lanes that are alive and not finished by an any-hit, and files the groups of those that
         // made a node step (nidx is still what it was at the loads for them)
-        const uint64_t book = __ballot(F.alive) & ~__ballot(hit_any);
+        const uint64_t book = F.alive & ~hit_m;
         uint64_t fin;
         [[maybe_unused]] uint32_t lane = 0u;
         if constexpr (!INSTANCED) {
-            fin = lean_bookkeeping_masked(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0);
+            fin = lean_bookkeeping_masked<kFull>(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0, mask_p);
         } else {
             // (this instantiation is two registers over its budget and the compiler's choice of what to keep in scratch is the two
             // stack addresses, reloaded here in every iteration: they are a constant plus eight times the lane number -- two
             // instructions to make again)
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
             const uint32_t ldsn_i = (uint32_t)reinterpret_cast<uintptr_t>(&nodes[0][0]) + 8u * lane, ldsl_i = (uint32_t)reinterpret_cast<uintptr_t>(&leaves[0][0]) + 8u * lane;
-            fin = lean_bookkeeping_masked(L, child, tri, ldsn_i, ldsl_i, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, ~0ull);
+            mask_n0 = ~0ull;        // (every lane of `book` files: a lane without a node step has an empty child / tri, above)
+            fin = lean_bookkeeping_masked(L, child, tri, ldsn_i, ldsl_i, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0, mask_p);
         }
-        bool done = hit_any || __builtin_amdgcn_inverse_ballot_w64(fin);
-        if constexpr (INSTANCED) done = I.switch_frames(enter, done, hit_any, L, mb, nodes, tx, lane);
-        if (done && (!kTail || !F.shared)) { F.alive = false; F.waiting = true; }
-        if (kSplit && a.tail_split) tail_retire(L, F, mb, done, tx);
-        const uint64_t act = __ballot(F.alive);
+        // finished: by an any-hit, or with nothing left to do.  All of it is mask arithmetic (`fin` only has bits inside `book`)
+        uint64_t done_m = hit_m | fin;
+        if constexpr (INSTANCED) done_m = __ballot(I.switch_frames(enter, lane_bit(done_m), hit_any, L, mb, nodes, tx, lane));
+        // (a piece of a split ray does not wait for a regeneration: tail_retire signs it off.  Only tail_donate shares rays)
+        const uint64_t rest = kSplit ? done_m & ~__ballot(F.shared) : done_m;
+        F.alive &= ~rest; F.waiting |= rest;
+        if (kSplit && a.tail_split) tail_retire(L, F, mb, lane_bit(done_m), tx);
         if constexpr (kTail) {
-            if (act == 0ull || (uint32_t)__popcll(__ballot(F.waiting)) >= (uint32_t)a.tail_regen) break;
-        } else if ((uint32_t)__popcll(act) <= max_alive) break;      // (every lane finished included)
+            if (F.alive == 0ull || (uint32_t)__popcll(F.waiting) >= (uint32_t)a.tail_regen) break;
+        } else if ((uint32_t)__popcll(F.alive) <= max_alive) break;      // (every lane finished included)
     }
 }
 

@@ -3,8 +3,10 @@
 block that issues global_load_dwordx4 into VGPRs and the asm wait that retires them, the compiler must not read, copy or spill
 those registers -- it does not know the loads are in flight, and the hardware does not interlock.  Compiles both files to
 assembly with the Makefile's own flags (`make -pn`), then prints, per kernel instantiation, the instructions that touch the
-destinations of a group of loads before the wait that covers it (expected: none).  The scan follows the text order of the
-assembly, which for these loops (issue at the top of the body, waits further down the same body) is the order of execution.
+destinations of a group of loads before the wait that covers it (expected: none).  The scan follows the ORDER OF EXECUTION from
+the loads -- across s_branch, down both sides of every s_cbranch -- to the first wait that retires them on each path (for the
+primitives' loads the nodes' vmcnt(0) does too): the compiler lays these loops out as it likes, the header that issues the loads
+may stand below the rest of the body, and what follows it in the text is then the code after the loop.
 Run by tests/test_host_cpu.py; exit status 1 when anything is found.
 Usage: tools/audit_asm_loads.py [-v]"""
 import re, subprocess, sys, tempfile
@@ -19,6 +21,25 @@ def makefile_hipflags():
         raise SystemExit("HIPFLAGS not found in the Makefile")
     csrc = "nvidia-optix-ray-tracer_amd/csrc"
     return m.group(1).replace("$(ARCH)", "gfx950").replace("$(CSRC)", csrc).split()
+
+
+def executed_after(body, start, stops):
+    """indices of the lines that can execute after line `start`, up to (not including) a line of `stops` on every path"""
+    labels = {l.split(":")[0]: i for i, l in enumerate(body) if l.startswith(".L")}
+    seen, todo, out = set(), [start + 1], []
+    while todo:
+        k = todo.pop()
+        while k < len(body) and k not in seen and k not in stops:
+            seen.add(k)
+            out.append(k)
+            t = body[k].split()
+            if t and t[0] == "s_branch":
+                k = labels[t[1]]
+                continue
+            if t and t[0].startswith("s_cbranch"):
+                todo.append(labels[t[1]])
+            k += 1
+    return sorted(out)
 
 
 def audit(source, kernel_prefix, verbose=False):
@@ -41,19 +62,18 @@ def audit(source, kernel_prefix, verbose=False):
         in_asm = set()
         for b in blocks:
             in_asm.update(range(b[0], b[1] + 1))
-        for what, n_loads, wait in (("node", 5, "s_waitcnt vmcnt(0)"), ("prim", 3, "s_waitcnt vmcnt(5)")):
+        for what, n_loads, wait in (("node", 5, ("s_waitcnt vmcnt(0)",)), ("prim", 3, ("s_waitcnt vmcnt(5)", "s_waitcnt vmcnt(0)"))):
             loads = [b for b in blocks if b[2].count("global_load_dwordx4 v[") == n_loads]
-            waits = [b for b in blocks if wait in b[2]]
+            waits = {b[0] for b in blocks if any(w in b[2] for w in wait)}
             for lb in loads:
                 regs = set()
                 for r in re.finditer(r"global_load_dwordx4 v\[(\d+):(\d+)\]", lb[2]):
                     regs.update(range(int(r.group(1)), int(r.group(2)) + 1))
-                stop = [w for w in waits if w[0] > lb[1]]
-                if not stop:
+                if not waits:
                     continue
                 n_groups += 1
                 bad = []
-                for k in range(lb[1] + 1, stop[0][0]):
+                for k in executed_after(body, lb[1], waits):
                     l = body[k]
                     if k in in_asm or l.strip().startswith(";") or "implicit-def" in l:
                         continue

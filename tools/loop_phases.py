@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The traversal loop of k_fused (csrc/trav_loop.h, shared with k_trace_queue; tools/loop_stats.py: the same loop, the same counts) split into its phases, so that a change to one
 phase can be checked against the others.  The phases are found by the markers the loop already has, in layout order:
-    exit  the loop test (the compiler lays the latch out before the header) and whatever follows the bookkeeping sequence
+    exit  the loop test and whatever follows the bookkeeping sequence (wherever the compiler lays the latch out)
     G     from the loop header to the first s_setprio: tail hand-over (kTail copy only), work masks, load issue
     C     to the next s_setprio: the primitives' wait and test
     A     to the next s_setprio: the nodes' wait and the node step
@@ -21,6 +21,9 @@ PHASES = ("G", "C", "A", "B", "exit")
 def phases(lines):
     """{phase: Counter of instruction kinds}, {phase: Counter of scalar opcodes} of one loop body (layout order)"""
     hdr = next(i for i, l in enumerate(lines) if "Loop Header: Depth=2" in l)
+    # (the walk below starts at the header: the layout may put the rest of the body in front of it)
+    top = max(i for i, l in enumerate(lines[:hdr + 1]) if l.startswith(".LBB"))
+    lines, hdr = lines[top:] + lines[:top], hdr - top
     ends = [i for i, l in enumerate(lines) if "#ASMEND" in l and i > hdr]
     book = [i for i, l in enumerate(lines) if "ds_write2_b32" in l and i > hdr]
     if not book:

@@ -32,30 +32,37 @@ def instructions(lines):
 
 def loop_bodies(source, prefix, asm=None):
     """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields (kernel, lines of
-    its traversal loop in layout order)."""
+    its traversal loop in layout order).  The loop is the depth-2 loop whose header is the last one before the first copy's node loads;
+    its lines are those of the basic blocks the compiler's own comments put into it ("in Loop: Header=..."), loops nested in it
+    included, wherever the layout has placed them (the latch may come before the header or after it)."""
     asm = str(asm or Path(tempfile.gettempdir()) / f"hrt_loops_{Path(source).stem}.s")
     flags = [f for f in makefile_hipflags() if f != "-fPIC"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", asm, source], cwd=ROOT, stderr=subprocess.DEVNULL)
     text = open(asm).read()
     for m in re.finditer(r"^(" + prefix + r"\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
-        labels = {l.split(":")[0]: i for i, l in enumerate(body) if l.startswith(".LBB")}
         loads = [i for i, l in enumerate(body) if "global_load_dwordx4" in l and "offset:64" in l]
         if not loads:
             continue
-        idx = loads[0]
-        hdrs = [i for i, l in enumerate(body) if "Loop Header: Depth=2" in l and i < idx]
+        hdrs = [i for i, l in enumerate(body) if "Loop Header: Depth=2" in l and i < loads[0]]
         if not hdrs:
             continue
-        hdr = max(hdrs)
-        nxt = [i for i, l in enumerate(body) if ("Loop Header: Depth=1" in l or "Loop Header: Depth=2" in l) and i > idx]
-        limit = min(nxt) if nxt else len(body)
-        back = [(i, labels[l.strip().split()[-1]]) for i, l in enumerate(body)
-                if idx < i < limit and "branch" in l and l.strip().split()[-1] in labels and hdr - 60 <= labels[l.strip().split()[-1]] <= hdr]
-        if not back:
-            continue
-        end, start = back[-1]
-        yield name, body[start:end + 1]
+        # basic blocks: (first line, label, header of the loop the block is in, headers of the loops round a block that is a header)
+        blocks = []
+        for i, l in enumerate(body):
+            if l.startswith(".LBB") or l.startswith("; %bb."):
+                inl = re.search(r"in Loop: Header=(BB\d+_\d+)", l)
+                blocks.append([i, "BB" + l.split(":")[0][4:] if l.startswith(".LBB") else None, inl.group(1) if inl else None, re.findall(r"Parent Loop (BB\d+_\d+)", l)])
+            elif blocks and l.lstrip().startswith(";") and "Parent Loop" in l:
+                blocks[-1][3] += re.findall(r"Parent Loop (BB\d+_\d+)", l)
+        header = max((b for b in blocks if b[0] <= hdrs[-1]), key=lambda b: b[0])[1]
+        inside = {header} | {b[1] for b in blocks if b[1] and header in b[3]}
+        lines = []
+        for k, b in enumerate(blocks):
+            if b[1] in inside or b[2] in inside:
+                lines += body[b[0]:blocks[k + 1][0] if k + 1 < len(blocks) else len(body)]
+        if lines:
+            yield name, lines
 
 
 def loops(source, prefix, asm=None):
