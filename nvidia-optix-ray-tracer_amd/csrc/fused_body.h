@@ -127,6 +127,7 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
     __shared__ uint2 s_nodes[kNodeStackLds][kTraverseBlock];     // sibling groups: one per tree level (hrt_api.cpp sends deeper trees to k_traverse)
     __shared__ uint2 s_leaves[kLeafStackLds][kTraverseBlock];    // leaf groups
     // tail splitting: one mailbox per lane that owns a split ray (indexed by its home lane) collects the pieces' hits
@@ -203,9 +204,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                st = path_finish<HAS_SPHERES, REUSE, BLOCKS>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
+                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
             }
-            exhausted = path_take<BLOCKS>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
+            exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
             stats.drained(exhausted);
             if (st.want_primary) {
                 bool from_cache = false;
@@ -221,7 +222,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             bool any_hit = false;
             if (st.launch) {
                 any_hit = path_count_ray(P);
-                lean_start(L, st.ro, st.rd, tmax_ray);
+                // a primary ray of a pixel the lane already holds starts bounded at the hit its previous sample found (PathLane::px_seed; tmax after
+                // path_take): counted and walked from the root like any other, the primitive test keeps the launch's tmax
+                lean_start(L, st.ro, st.rd, kSeed && st.want_primary ? P.px_seed : tmax_ray);
                 if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
             }
             // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
@@ -231,6 +234,10 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             // REUSE: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that
             // their bounces start together with the other lanes' rays (one extra round, not more: the others are waiting)
             if constexpr (REUSE) { if (!was_forced && __ballot(reshade) != 0ull) { force_regen = true; continue; } }
+            // s_waitcnt lgkmcnt(0): no scalar load of this block is under way when the traversal loop is entered.  A load issued in front of a
+            // branch that skips its wait counts as pending to the compiler, which then waits INSIDE the loop wherever the loop reuses the
+            // load's register (two s_waitcnt in the sphere kernels' loops, as the registers happened to fall)
+            __builtin_amdgcn_s_waitcnt(0xc07f);
         }
         // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, REUSE, a lane with a cached hit to shade:
         // an empty pass through the loop below brings it back here)

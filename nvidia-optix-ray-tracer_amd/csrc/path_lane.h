@@ -25,6 +25,11 @@ struct PathLane {
     float px_pdx = 0.0f, px_pdy = 0.0f, px_pdz = 1.0f;      // the pixel's primary direction: the same for every sample (no jitter, Shader.cu:249-261)
     Xorwow px_rng{};
     uint32_t px_rays_closest = 0u, px_rays_any = 0u;
+    // the culling bound the pixel's next primary ray may start with: the hit distance its last one found, exactly as found, or tmax (none:
+    // a miss, a pixel just taken, HRT_SEED_PRIMARY=0).  Every sample's primary ray is the same ray, so it ends in the same hit again: a
+    // complete closest-hit walk from the root that never enters what lies behind that hit.  Reset by path_take, so it
+    // never outlives the lane's hold on the pixel; kept by the kernels that seed (SEED: fused_body.h) only.
+    float px_seed = kFloatInfinity;
 };
 
 // what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
@@ -80,10 +85,12 @@ __device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, b
 // sum written), wants the next sample's primary ray, or launches the bounce.
 // REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
 // BLOCKS: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
-template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false>
+// SEED: the kernel starts repeat primary rays at PathLane::px_seed, so a finished primary ray records it (and path_take resets it).
+template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst) {
     PathStep st;
     const bool miss = bprim == kMissPrim;
+    if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) P.px_seed = bt; }      // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
     if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
         a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
         a.path.trace_inst[P.px_local] = binst;
@@ -136,7 +143,7 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // i / slices of slice i % slices, and an item of a later pass waits for its predecessor: while the slice's progress word says that pixels of
 // (b - 1, q) are still under way the wave keeps the item, starts none of its pixels and looks again at its next regeneration.  It never
 // waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
-template <bool BLOCKS = false>
+template <bool BLOCKS = false, bool SEED = false>
 __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
                                           bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr) {
     const uint64_t need = __ballot(free_lane);
@@ -186,6 +193,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                 const uint32_t j = a.path.first_pixel + mine;
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
+                if constexpr (SEED) P.px_seed = a.tmax;
                 if (!a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;
                     const uint32_t ix = j - row * a.path.width;
