@@ -59,10 +59,32 @@ static inline float dot3(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z;
 static inline f3 cross3(f3 a, f3 b) {                                                       /* :410-416 */
     return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
+/* Branch counters of the shading code (test-only: tests/test_shading_cases_cpu.py shows with them that a case reaches the guard it was
+ * made for).  They are filled per thread during oracle_render, summed over its rows like tot_rays, and read and reset through
+ * oracle_shade_counters; no arithmetic depends on them. */
+enum { SC_HIT_SPHERE_ROUGH = 0, SC_HIT_SPHERE_METAL, SC_HIT_TRIANGLE_ROUGH, SC_HIT_TRIANGLE_METAL,   /* closest-hit invocations per program */
+       SC_FLIP,                 /* back-face flips: dot(d, n) < 0 came out false                                        */
+       SC_FLIP_NAN,             /* ... of these, on a NaN dot product                                                    */
+       SC_NORMALIZE_ZERO,       /* normalize3 returned (0,0,1) for len2 <= 1e-12                                         */
+       SC_ROUGH_DEGENERATE,     /* normal + rsv replaced by the normal, Shader.cu:169-179                                */
+       SC_METAL_DRAW,           /* metal with fuzz > 0: the RNG was drawn                                                */
+       SC_METAL_NO_DRAW,        /* metal whose fuzz > 0 came out false (0, -0, negative, NaN)                            */
+       SC_FALLBACK_NORMAL,      /* the scattered direction was non-finite or too short: the normal instead, :202-209     */
+       SC_FALLBACK_NONFINITE,   /* ... of these, because a component was non-finite                                      */
+       SC_FALLBACK_Z,           /* ... and the normal was no better: (0,0,1), :210-212                                   */
+       SC_DEPTH_LIMIT,          /* closest-hit invocations that ended the path at rayTraceDepth, :102-107                */
+       SC_DEPTH5_RAYS,          /* rays traced at depth 5 (paths that got that far; hit or miss)                         */
+       SC_PRIMARY_ZERO,         /* primary directions that are normalize3's zero-length return                           */
+       SC_SAMPLES,              /* raygen invocations                                                                    */
+       SC_NONFINITE_SAMPLES,    /* ... whose linear result has a NaN or inf component                                    */
+       SC_COUNT };
+static _Thread_local uint64_t tl_sc[SC_COUNT];
+static uint64_t g_shade_counters[SC_COUNT];
+
 /* normalize, DeviceFunctions.cuh:397-404; rsqrtf pinned as 1/sqrtf (see header) */
 static inline f3 normalize3(f3 a) {
     const float len2 = len2_3(a);
-    if (len2 <= FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE) return mk3(0.0f, 0.0f, 1.0f);
+    if (len2 <= FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE) { tl_sc[SC_NORMALIZE_ZERO]++; return mk3(0.0f, 0.0f, 1.0f); }
     const float invLen = 1.0f / sqrtf(len2);
     return muls3(a, invLen);
 }
@@ -100,11 +122,14 @@ static float pow_inv_gamma_cr(float xf) {
 float oracle_pow_inv_gamma(float x) { return pow_inv_gamma_cr(x); }
 float oracle_pow_inv_gamma_libm_powf(float x) { return powf(x, 1.0f / 2.4f); }      /* tolerance cross-check only */
 
+/* fmaxf(0.0f, x) with the one case C leaves open pinned: the reference's fmaxf is PTX max.f32, which orders -0.0 below +0.0, so a
+ * channel of -0.0 (a background or albedo of -0.0, tests/shading_cases.py) clamps to +0.0; glibc's fmaxf returns whichever zero came second */
+static inline float fmaxf_zero(float x) { const float m = fmaxf(0.0f, x); return m == 0.0f ? 0.0f : m; }
 static inline float srgb_channel(float c) {
-    const float cx = fmaxf(0.0f, fminf(c, 1.0f));                    /* :190 */
+    const float cx = fmaxf_zero(fminf(c, 1.0f));                     /* :190 */
     const float px = pow_inv_gamma_cr(cx);                           /* :195-196, pinned as above */
     const float sx = cx < 0.0031308f ? 12.92f * cx : 1.055f * px - 0.055f;   /* :199 */
-    return fmaxf(0.0f, fminf(sx, 1.0f));                             /* :204 */
+    return fmaxf_zero(fminf(sx, 1.0f));                              /* :204 */
 }
 /* n colours (float4 in, float4 out): colorToFloat4 over an array, for the exhaustive sweeps of the tests */
 void oracle_color_to_float4_n(const float *src4, float *dst4, uint64_t n) {
@@ -655,7 +680,9 @@ static void closesthit_impl(launch_ctx *lc, const hit_rec *hit, f3 rayOrigin, f3
                             f4 *payload, f4 *albedo, f4 *normal) {
     const f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
     const oracle_instance *hp = &lc->sc->inst[hit->inst];           /* SBT record of the instance, :108 */
+    tl_sc[(hp->geometry == GEOM_SPHERE ? SC_HIT_SPHERE_ROUGH : SC_HIT_TRIANGLE_ROUGH) + (hp->material == MAT_ROUGH ? 0 : 1)]++;
     if (payload->w >= (float)RAY_TRACE_DEPTH) {                     /* :102-107 */
+        tl_sc[SC_DEPTH_LIMIT]++;
         payload->x = 0.0f; payload->y = 0.0f; payload->z = 0.0f;
         *albedo = z; *normal = z;
         return;
@@ -670,6 +697,7 @@ static void closesthit_impl(launch_ctx *lc, const hit_rec *hit, f3 rayOrigin, f3
         const float sphereRadius = hp->radii[primitiveIndex];
         const f3 outwardNormal = divs3(sub3(hitPoint, sphereCenter), sphereRadius);   /* Q1: object-space centre */
         const int hitFrontFace = dot3(rayDirection, outwardNormal) < 0.0f;
+        if (!hitFrontFace) { tl_sc[SC_FLIP]++; if (isnan(dot3(rayDirection, outwardNormal))) tl_sc[SC_FLIP_NAN]++; }
         normalVector = hitFrontFace ? outwardNormal : neg3(outwardNormal);
     } else {                                                        /* :137-155 */
         const float *nn = hp->normals + 9 * (size_t)primitiveIndex;
@@ -678,6 +706,7 @@ static void closesthit_impl(launch_ctx *lc, const hit_rec *hit, f3 rayOrigin, f3
         const float w = 1.0f - u - v;
         const f3 _normal = add3(add3(muls3(n1, w), muls3(n2, u)), muls3(n3, v));      /* Q2: not transformed, not normalised */
         const int hitFrontFace = dot3(rayDirection, _normal) < 0.0f;
+        if (!hitFrontFace) { tl_sc[SC_FLIP]++; if (isnan(dot3(rayDirection, _normal))) tl_sc[SC_FLIP_NAN]++; }
         normalVector = hitFrontFace ? _normal : neg3(_normal);
     }
 
@@ -686,12 +715,15 @@ static void closesthit_impl(launch_ctx *lc, const hit_rec *hit, f3 rayOrigin, f3
     rng_state *state = lc->stateArray + lc->tid;
     if (hp->material == MAT_ROUGH) {                                /* :169-179 */
         reflectDirection = add3(normalVector, random_space_vector(state, 1.0f));
-        if (float_value_equals(len2_3(reflectDirection), FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE))
+        if (float_value_equals(len2_3(reflectDirection), FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE)) {
+            tl_sc[SC_ROUGH_DEGENERATE]++;
             reflectDirection = normalVector;
+        }
         _albedo = mk3(hp->albedo[0], hp->albedo[1], hp->albedo[2]);
     } else {                                                        /* :180-192 */
         const f3 v = rayDirection, n = normalVector;
         reflectDirection = normalize3(sub3(v, muls3(n, 2.0f * dot3(v, n))));
+        tl_sc[hp->fuzz > 0.0f ? SC_METAL_DRAW : SC_METAL_NO_DRAW]++;
         if (hp->fuzz > 0.0f)
             reflectDirection = add3(reflectDirection, muls3(random_space_vector(state, 1.0f), hp->fuzz));
         _albedo = mk3(hp->albedo[0], hp->albedo[1], hp->albedo[2]);
@@ -700,10 +732,14 @@ static void closesthit_impl(launch_ctx *lc, const hit_rec *hit, f3 rayOrigin, f3
     /* :202-213 */
     if (!isfinite(reflectDirection.x) || !isfinite(reflectDirection.y) || !isfinite(reflectDirection.z) ||
         len2_3(reflectDirection) <= FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE) {
+        tl_sc[SC_FALLBACK_NORMAL]++;
+        if (!isfinite(reflectDirection.x) || !isfinite(reflectDirection.y) || !isfinite(reflectDirection.z)) tl_sc[SC_FALLBACK_NONFINITE]++;
         reflectDirection = normalVector;
         if (len2_3(reflectDirection) <= FLOAT_ZERO_VALUE * FLOAT_ZERO_VALUE ||
-            !isfinite(reflectDirection.x) || !isfinite(reflectDirection.y) || !isfinite(reflectDirection.z))
+            !isfinite(reflectDirection.x) || !isfinite(reflectDirection.y) || !isfinite(reflectDirection.z)) {
+            tl_sc[SC_FALLBACK_Z]++;
             reflectDirection = mk3(0.0f, 0.0f, 1.0f);
+        }
     }
 
     if (float_value_equals(payload->w, 1.0f)) {                     /* :216-227 (overwritten later: Q3) */
@@ -730,6 +766,7 @@ static void ray_trace(launch_ctx *lc, f3 origin, f3 direction, float tMin, float
     /* a hit at depth >= rayTraceDepth returns black whatever it is (Shader.cu:102-107), so the
      * oracle may stop at the first accepted intersection there; the result is identical */
     const int any_hit = payload->w >= (float)RAY_TRACE_DEPTH;
+    if (any_hit) tl_sc[SC_DEPTH5_RAYS]++;
     closest_hit(lc->sc, origin, direction, tMin, tMax, any_hit, &hit, &lc->cnt);
     if (tl_ray_log && tl_ray_log_n < tl_ray_log_cap) {
         float *q = tl_ray_log + 10 * (size_t)tl_ray_log_n++;
@@ -748,7 +785,10 @@ static f4 raygen_program(launch_ctx *lc, uint32_t ix, uint32_t iy, uint32_t dimx
     const f3 origin = mk3(cam[0], cam[1], cam[2]);
     const f3 U = mk3(cam[3], cam[4], cam[5]), V = mk3(cam[6], cam[7], cam[8]), W = mk3(cam[9], cam[10], cam[11]);
     const float aspect = (float)dimx / (float)dimy;                          /* :260 (data->width/height == dim) */
+    const uint64_t zero_returns = tl_sc[SC_NORMALIZE_ZERO];
     const f3 direction = normalize3(add3(add3(muls3(U, ndcx * aspect), muls3(V, ndcy)), W));   /* :261 */
+    tl_sc[SC_PRIMARY_ZERO] += tl_sc[SC_NORMALIZE_ZERO] - zero_returns;
+    tl_sc[SC_SAMPLES]++;
     f4 result = {0.0f, 0.0f, 0.0f, 1.0f}, albedo = {0, 0, 0, 0}, normal = {0, 0, 0, 0};          /* :264 */
     lc->tid = iy * dimx + ix;
     ray_trace(lc, origin, direction, FLOAT_ZERO_VALUE, FLOAT_INFINITY_VALUE, &result, &albedo, &normal);
@@ -769,11 +809,12 @@ void oracle_render(const oracle_scene *sc, const float *cam12, uint32_t width, u
                    uint64_t *out_counters /* rays, node_visits, prim_tests */) {
     oracle_init();
     const long nr = rows ? (long)n_rows : (long)height;
-    uint64_t tot_rays = 0, tot_nodes = 0, tot_prims = 0;
-    #pragma omp parallel for schedule(dynamic, 1) reduction(+:tot_rays, tot_nodes, tot_prims)
+    uint64_t tot_rays = 0, tot_nodes = 0, tot_prims = 0, tot_sc[SC_COUNT] = {0};
+    #pragma omp parallel for schedule(dynamic, 1) reduction(+:tot_rays, tot_nodes, tot_prims, tot_sc[:SC_COUNT])
     for (long ri = 0; ri < nr; ++ri) {
         const uint32_t y = rows ? rows[ri] : (uint32_t)ri;
         launch_ctx lc; memset(&lc, 0, sizeof lc);
+        memset(tl_sc, 0, sizeof tl_sc);
         lc.sc = sc; lc.stateArray = (rng_state *)states;
         lc.backgroundColor = mk3(bg3[0], bg3[1], bg3[2]);
         for (uint32_t x = 0; x < width; ++x) {
@@ -781,6 +822,7 @@ void oracle_render(const oracle_scene *sc, const float *cam12, uint32_t width, u
             f3 sum = {0.0f, 0.0f, 0.0f};
             for (uint32_t s = 0; s < spp; ++s) {
                 const f4 r = raygen_program(&lc, x, y, width, height, cam12, &a, &n);
+                if (!isfinite(r.x) || !isfinite(r.y) || !isfinite(r.z)) tl_sc[SC_NONFINITE_SAMPLES]++;
                 if (s == 0) sum = mk3(r.x, r.y, r.z); else sum = add3(sum, mk3(r.x, r.y, r.z));
             }
             if (spp > 1) sum = divs3(sum, (float)spp);
@@ -791,8 +833,18 @@ void oracle_render(const oracle_scene *sc, const float *cam12, uint32_t width, u
             if (normal) { normal[4 * p] = n.x; normal[4 * p + 1] = n.y; normal[4 * p + 2] = n.z; normal[4 * p + 3] = n.w; }
         }
         tot_rays += lc.cnt.rays; tot_nodes += lc.cnt.node_visits; tot_prims += lc.cnt.prim_tests;
+        for (int k = 0; k < SC_COUNT; ++k) tot_sc[k] += tl_sc[k];
     }
     if (out_counters) { out_counters[0] = tot_rays; out_counters[1] = tot_nodes; out_counters[2] = tot_prims; }
+    for (int k = 0; k < SC_COUNT; ++k) g_shade_counters[k] += tot_sc[k];
+}
+
+/* The branch counters (SC_*) summed over every oracle_render since the last reset: copies min(n, SC_COUNT) of them to out (NULL: none),
+ * then clears them if reset is set.  Returns SC_COUNT.  Not for use while a render runs. */
+int oracle_shade_counters(uint64_t *out, int n, int reset) {
+    for (int k = 0; out && k < n && k < SC_COUNT; ++k) out[k] = g_shade_counters[k];
+    if (reset) memset(g_shade_counters, 0, sizeof g_shade_counters);
+    return SC_COUNT;
 }
 
 /* One sample of one pixel, its rays logged (10 floats per ray, see tl_ray_log); the pixel's RNG state advances as in a render.  Returns the

@@ -69,6 +69,8 @@ def lib():
     L.oracle_trig.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     L.oracle_trig_bits.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]
     L.oracle_trig_libm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.oracle_shade_counters.restype = C.c_int
+    L.oracle_shade_counters.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.oracle_num_threads.restype = C.c_int
     L.oracle_set_threads.argtypes = [C.c_int]
     L.oracle_init()
@@ -126,6 +128,9 @@ class OracleScene:
         out = np.zeros(12, dtype=np.float32)
         out[0:3] = c
         u, v, w = out[3:6], out[6:9], out[9:12]
+        if "uvw" in cam:                                   # the basis given outright (tests/shading_cases.py: bases configure_camera never makes)
+            out[3:12] = np.ascontiguousarray(cam["uvw"], dtype=np.float32).reshape(9)
+            return out
         uu, vv, ww = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
         L.oracle_configure_camera(_p(c), _p(t), _p(up), int(cam.get("opengl", True)), _p(uu), _p(vv), _p(ww))
         u[:], v[:], w[:] = uu, vv, ww
@@ -189,6 +194,20 @@ class OracleScene:
             self.close()
         except Exception:
             pass
+
+
+# oracle.c's SC_* enumeration, in its order
+SHADE_COUNTERS = ("hit_sphere_rough", "hit_sphere_metal", "hit_triangle_rough", "hit_triangle_metal", "flip", "flip_nan", "normalize_zero",
+                  "rough_degenerate", "metal_draw", "metal_no_draw", "fallback_normal", "fallback_nonfinite", "fallback_z", "depth_limit",
+                  "depth5_rays", "primary_zero", "samples", "nonfinite_samples")
+
+
+def shade_counters(reset=True):
+    """The oracle's shading branch counters, summed over every OracleScene.render since the last reset, as a dict."""
+    out = np.zeros(len(SHADE_COUNTERS), np.uint64)
+    n = lib().oracle_shade_counters(_p(out), len(out), int(reset))
+    assert n == len(SHADE_COUNTERS), "oracle_py.SHADE_COUNTERS is out of step with oracle.c"
+    return {k: int(v) for k, v in zip(SHADE_COUNTERS, out)}
 
 
 def construct_transform(shift, rotate_deg, scale):
