@@ -313,7 +313,15 @@ typedef struct HrtStats {
     uint64_t tail[8];                      /* instrumented build only (make stats, tools/tail_profile.py): the path kernel's drained phase --
                                               wave iterations, alive lanes over them, clock base, ~first drained clock, last exit clock,
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
+    uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
+                                              at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
 } HrtStats;
+
+/* The sample blocks a path-kernel launch of spp samples is cut into (host only, no context, no GPU): block_big = N, block_min = 0 -- uniform
+ * blocks of N, HRT_SAMPLE_BLOCK=N; block_big : block_min, powers of two -- the tapered schedule, HRT_SAMPLE_TAPER.  Writes the first sample
+ * of every pass and, behind the last, spp into first[0 .. *n_passes] (capacity: entries of first; HRT_ERR_INVALID when too small or
+ * the sizes are not as above).  Pass b is samples first[b] .. first[b + 1]; the last block ends where the samples do, short if need be. */
+int  hrt_sample_schedule(uint32_t spp, uint32_t block_big, uint32_t block_min, uint32_t *first, uint32_t capacity, uint32_t *n_passes);
 
 int  hrt_stats_reset(HrtContext *ctx);
 int  hrt_stats_get(HrtContext *ctx, HrtStats *out);       /* synchronises the device */

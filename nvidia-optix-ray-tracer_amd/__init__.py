@@ -81,7 +81,8 @@ class Stats(C.Structure):
                 ("bvh_bytes", C.c_uint64), ("debug", C.c_uint64 * 4),
                 ("tlas_refits", C.c_uint64), ("tlas_rebuilds", C.c_uint64), ("tlas_refit_ratio", C.c_double),
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
-                ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8)]
+                ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
+                ("sample_block_schedule", C.c_uint64 * 4)]
 
 
 class BvhBlob(C.Structure):
@@ -121,7 +122,7 @@ EXPORTS = [
     "hrt_tlas_build", "hrt_tlas_update", "hrt_tlas_destroy", "hrt_pose_instances",
     "hrt_sbt_record_pack_header", "hrt_materials_set", "hrt_miss_set",
     "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_to_rgba8", "hrt_color_to_float4",
-    "hrt_stats_reset", "hrt_stats_get", "hrt_trace_rays", "hrt_debug_set_linear_output",
+    "hrt_stats_reset", "hrt_stats_get", "hrt_sample_schedule", "hrt_trace_rays", "hrt_debug_set_linear_output",
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
@@ -181,6 +182,7 @@ def load_library():
     lib.hrt_color_to_float4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.hrt_stats_reset.argtypes = [C.c_void_p]
     lib.hrt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
+    lib.hrt_sample_schedule.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
     lib.hrt_trace_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_debug_set_linear_output.argtypes = [C.c_void_p, C.c_void_p]

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 
 namespace hrt {
 
@@ -63,21 +64,51 @@ struct PathArgs {
     uint32_t *slice_cost;          // probe launch: per slice of fetch_chunk pixels, the time its pixels' samples took (clock / 16); else NULL
     const uint32_t *slice_order;   // order in which the slices are handed out (most expensive first); NULL: as they lie
     float center[3], U[3], V[3], W[3], bg[3];
+    uint32_t block_min;            // sample blocks, tapered: the smallest block (below; in what was padding: the offsets of everything else are as before)
     RngState *states;
     const HitGroup *hitgroups; const uint32_t *inst_program;
     float4 *accum;                 // per tile pixel: sum of the samples' linear radiance
     uint64_t *rays_closest, *rays_any;
     const RayRec *trace_rays;      // fused kernel as hrt_trace_rays: the "pixels" are these rays, traced once; results below (else NULL)
     float4 *trace_tuvp; uint32_t *trace_inst; uint32_t trace_any;
+    uint32_t block_taper_end;      // sample blocks, tapered: the sample at which the halving blocks end (below; in what was padding)
     float4 *primary_cache;         // k_fused<.., REUSE>: two float4 per lane of the grid, the primary hit of the lane's pixel (else NULL)
     // sample blocks (path_lane.h; k_fused's one-level instantiations without REUSE): 0 = a lane keeps its pixel for all samples of the launch
-    uint32_t sample_block;         // K: samples a lane takes of a pixel before it gives it back
-    uint32_t block_magic;          // min(2^32 / K, 2^32 - 1): path_finish's test for a multiple of K (0 with K = 0)
+    // The launch's samples are cut into blocks by a schedule (block_first, block_ends below), one of two kinds:
+    //   uniform   block_magic != 0: blocks of K = sample_block samples, any K >= 1 (HRT_SAMPLE_BLOCK=N)
+    //   tapered   block_magic == 0: powers of two that never grow -- blocks of sample_block = K_big up to T = block_taper_end - K_big (a
+    //             multiple of K_big), then K_big / 2, K_big / 4, ... block_min, block_min, which end at block_taper_end, then block_min
+    //             for as long as the launch lasts (HRT_SAMPLE_TAPER); the launch's last block is cut short where its samples end
+    uint32_t sample_block;         // K, K_big: samples a lane takes of a pixel before it gives it back
+    uint32_t block_magic;          // min(2^32 / K, 2^32 - 1): path_finish's test for a multiple of K (0: tapered, or K = 0)
     uint32_t block_slices;         // slices of the tile
     uint32_t block_slices_magic, block_chunk_magic;   // min(2^32 / d, 2^32 - 1) for d = block_slices, fetch_chunk (path_lane.h: div_magic)
     uint32_t block_items;          // passes x slices: what the slice counters hand out (x fetch_chunk below 2^32)
     uint32_t *block_progress;      // per slice: blocks ended by its pixels, zeroed before the launch
 };
+
+static_assert(sizeof(PathArgs) == 232 && offsetof(PathArgs, states) == 112 && offsetof(PathArgs, primary_cache) == 192 && offsetof(PathArgs, block_progress) == 224,
+              "block_min and block_taper_end sit in what was padding: nothing else has moved");
+
+// The block schedule in closed form, for the kernel (path_lane.h) and the host (hrt_api.cpp: sample_schedule) alike.
+// block_first: the first sample of pass b.
+__host__ __device__ inline uint32_t block_first(uint32_t k_big, uint32_t k_min, uint32_t taper_end, bool tapered, uint32_t pass) {
+    if (!tapered) return pass * k_big;
+    const uint32_t log_big = (uint32_t)__builtin_ctz(k_big), n_big = (taper_end - k_big) >> log_big;      // passes of K_big in front of the halvings
+    if (pass <= n_big) return pass << log_big;
+    const uint32_t j = pass - n_big, halvings = log_big - (uint32_t)__builtin_ctz(k_min);
+    const uint32_t h = j < halvings ? j : halvings;                          // pass n_big + j starts where K_big >> j samples are left of the window ...
+    return taper_end - (k_big >> h) + (j - h) * k_min;                       // ... and K_min later for every pass after the last halving
+}
+// block_ends: a tapered schedule has a boundary at sample p >= 1.  With q = taper_end - p: a multiple of K_big in front of the window
+// (q >= K_big), a power of two that is at least K_min, or 0, inside it, a multiple of K_min behind it (q < 0) -- that is, q has no bit in
+// common with min(q - 1, K_big - 1) | (K_min - 1), behind the window q modulo K_min.  All three K = 0 (no blocks): never.
+__host__ __device__ inline bool block_ends(uint32_t k_big, uint32_t k_min, uint32_t taper_end, uint32_t p) {
+    uint32_t q = taper_end - p;
+    if ((int32_t)q < 0) q &= k_min - 1u;
+    const uint32_t below = q - 1u < k_big - 1u ? q - 1u : k_big - 1u;
+    return (q & (below | (k_min - 1u))) == 0u;
+}
 
 struct TraverseArgs {
     const void *nodes;             // Bvh8Node[]
@@ -257,7 +288,8 @@ void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t
 void launch_generate(const GenerateArgs &a, hipStream_t s);
 void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
 void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // round 1's fused kernel k_traverse<.., FUSED>: trees k_fused cannot take
-constexpr int kSampleBlockAuto = 32;   // HRT_SAMPLE_BLOCK=auto: samples per block (profiles/r13_sample_blocks.txt)
+constexpr int kSampleBlockAuto = 32;   // HRT_SAMPLE_BLOCK=auto with HRT_SAMPLE_TAPER=0: samples per block (profiles/r13_sample_blocks.txt); with a taper: `auto` wants 2 x this many samples in a launch
+constexpr int kSampleTaperBig = 64, kSampleTaperMin = 8;   // HRT_SAMPLE_TAPER: the largest and the smallest block of the tapered schedule (profiles/r19_sample_taper.txt)
 constexpr int kFusedBlocksPerCu = 16;  // k_fused is compiled for 4 waves per SIMD (125 VGPRs, nothing spilled): more workgroups per CU would only queue
 constexpr int kFusedInstancedBlocksPerCu = 12;   // k_fused<.., INSTANCED> is compiled for 3 waves per SIMD (fused.hip)
 constexpr uint32_t kFetchShards = 8;         // slice counters (one per XCD-group of blocks)

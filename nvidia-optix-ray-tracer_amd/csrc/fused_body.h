@@ -258,7 +258,12 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             // Either way some wave is not stuck (the grid is sized to what is resident; were it not, workgroups 0 to kFetchShards - 1, one
             // home wave per counter, are the first to be).  (With fewer waves than counters the second case fails: the only wave of an 8 x 6 frame
             // takes item 0, then item 8 of its home counter -- pass 2 of a slice whose passes 0 and 1 are items of counters nobody
-            // visits.)  An empty pass through the loop below brings the wave back to its regeneration: a `continue` here costs the
+            // visits.)  None of this asks how many samples a pass has: the schedule (device_types.h: block_first -- uniform blocks, or
+            // tapered ones that start large and end small) only says at which sample a lane's hold on its pixel begins and ends.  What the
+            // argument uses is that every pixel of a slice ends exactly one block per pass -- at a boundary of the schedule, or, the last
+            // pass, where the launch's samples end -- so that item (b, q) is done when the slice's word stands at (b + 1) x its pixels and
+            // ready when it stands at b x its pixels; the numbering of the items, the home counters and the floor of 8 waves are as they
+            // were.  An empty pass through the loop below brings the wave back to its regeneration: a `continue` here costs the
             // kernel a hundred spilled registers.
             __builtin_amdgcn_s_sleep(32);
         }

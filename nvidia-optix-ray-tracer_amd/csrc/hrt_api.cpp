@@ -367,6 +367,35 @@ struct LaunchFrame {
     hipStream_t s;
 };
 
+// ---- sample blocks: the schedule of one path-kernel launch (device_types.h: PathArgs, block_first, block_ends) ----
+struct SampleSchedule { uint32_t k_big = 0, k_min = 0, taper_end = 0; bool tapered = false; uint32_t passes = 0; };
+static uint32_t schedule_first(const SampleSchedule &sc, uint32_t pass) { return block_first(sc.k_big, sc.k_min, sc.taper_end, sc.tapered, pass); }
+// passes: the first pass that would start at or behind the launch's last sample (block_first grows with the pass, by 1 at least)
+static void count_passes(SampleSchedule &sc, uint32_t spp) {
+    uint32_t lo = 0, hi = spp;
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2u; if (schedule_first(sc, mid) >= spp) hi = mid; else lo = mid + 1u; }
+    sc.passes = lo;
+}
+static SampleSchedule uniform_schedule(uint32_t spp, uint32_t k) {
+    SampleSchedule sc; sc.k_big = sc.k_min = k; sc.passes = (uint32_t)(((uint64_t)spp + k - 1u) / k); return sc;
+}
+// The tapered schedule of a launch of spp samples: blocks of K_big = `big` (no more than the launch has samples) up to T, then the sizes
+// K_big / 2, K_big / 4, ... K_min, K_min, which fill the window [T, T + K_big), and K_min behind it.  T + K_big is the last multiple of
+// K_big the launch reaches: the halvings are its last whole window, what is left behind them (less than K_big samples) goes in blocks
+// of K_min, and the launch's last block ends with its samples, short if need be -- every launch ends on K_min, with K_big / K_min - 1
+// more hand-overs at the most than it takes to get there.  Powers of two that never grow, so every boundary is a multiple of the block
+// that ends there.  256 samples, 64 : 8 -- 64, 64, 64, 32, 16, 8, 8.  (32-bit arithmetic: for launches of spp x big below 2^31, taper_fits.)
+static bool taper_fits(uint32_t spp, uint32_t big) { return (uint64_t)spp * big < (1ull << 31); }
+static SampleSchedule sample_schedule(uint32_t spp, uint32_t big, uint32_t min) {
+    SampleSchedule sc; sc.tapered = true;
+    sc.k_big = big; while (sc.k_big > 1u && sc.k_big > spp) sc.k_big >>= 1;
+    sc.k_min = std::min(min, sc.k_big);
+    sc.taper_end = spp / sc.k_big * sc.k_big;
+    count_passes(sc, spp);
+    return sc;
+}
+
+
 // ---- fused path mode: ONE launch, every lane owns a pixel and runs all its samples (generate, traverse, shade, accumulate in place).
 //      No stage barriers.  The default (HRT_FUSED=1); trees outside k_fused's limits take round 1's path kernel. ----
 static int render_fused(const LaunchFrame &f) {
@@ -456,12 +485,16 @@ static int render_fused(const LaunchFrame &f) {
     // Never, forced or not, on a grid of fewer waves than slice counters: a wave keeps an item that is not ready until it is, and takes
     // from another counter only once its own is drained, so every counter needs a wave whose home it is -- otherwise the predecessor of
     // a held item can sit behind a counter that nobody visits and the wave waits for ever (the argument: fused_body.h).
-    uint32_t K = 0;
+    // What a launch of `now` samples is cut into is a schedule (device_types.h: block_first): HRT_SAMPLE_BLOCK=N forces uniform blocks of N;
+    // `auto` takes HRT_SAMPLE_TAPER's -- large blocks while the machine is full, so that a pixel changes hands seldom, halved down to small
+    // ones over the last samples, so that the frame ends on a short tail (sample_schedule above) -- or, with HRT_SAMPLE_TAPER=0, uniform
+    // blocks of kSampleBlockAuto.
+    bool want_blocks = false, forced = false;
     if (pk.kernel == PathKernel::Fused && !pa.primary_cache && !lpt && ctx->sample_block != 0 && grid >= kFetchShards) {
-        if (ctx->sample_block > 0) K = (uint32_t)ctx->sample_block;
-        else if ((uint64_t)n_slices * ta.fetch_chunk >= 4ull * 64ull * (uint64_t)grid) K = (uint32_t)kSampleBlockAuto;
+        forced = ctx->sample_block > 0 || (ctx->taper_big > 0 && ctx->taper_forced);
+        want_blocks = forced || (uint64_t)n_slices * ta.fetch_chunk >= 4ull * 64ull * (uint64_t)grid;
     }
-    if (K != 0u && n_slices > w.block_capacity) {
+    if (want_blocks && n_slices > w.block_capacity) {
         if (w.block_progress) (void)hipFree(w.block_progress);
         w.block_progress = nullptr; w.block_capacity = 0;
         HIP_TRY(ctx, hipMalloc((void **)&w.block_progress, sizeof(uint32_t) * n_slices));
@@ -472,15 +505,18 @@ static int render_fused(const LaunchFrame &f) {
     while (done_spp < spp) {
         const uint32_t now = std::min<uint32_t>(spp - done_spp, (uint32_t)ctx->fused_max_spp);
         pa.spp = now; pa.continue_sum = done_spp > 0 ? 1u : 0u;
-        // this launch in blocks: at least two of them (`auto`: two whole ones), and the counters' numbers, in pixels, within 32 bits
-        const uint64_t passes = K ? ((uint64_t)now + K - 1u) / K : 0u;
-        const bool blocks = passes >= 2u && (ctx->sample_block > 0 || now >= 2u * K) && passes * n_slices * ta.fetch_chunk < (1ull << 32);
+        // this launch in blocks: at least two of them (`auto`: 2 kSampleBlockAuto samples), and the counters' numbers, in pixels, within 32 bits
+        SampleSchedule sc;
+        if (want_blocks) sc = ctx->sample_block > 0 ? uniform_schedule(now, (uint32_t)ctx->sample_block) : ctx->taper_big > 0 && taper_fits(now, (uint32_t)ctx->taper_big) ? sample_schedule(now, (uint32_t)ctx->taper_big, (uint32_t)ctx->taper_min) : uniform_schedule(now, (uint32_t)kSampleBlockAuto);
+        const bool blocks = sc.passes >= 2u && (forced || now >= 2u * (uint32_t)kSampleBlockAuto) && (uint64_t)sc.passes * n_slices * ta.fetch_chunk < (1ull << 32);
         auto magic = [](uint32_t d) { return d ? (uint32_t)std::min<uint64_t>((1ull << 32) / d, 0xffffffffull) : 0u; };      // (an empty tile has no slices)
-        pa.sample_block = blocks ? K : 0u; pa.block_magic = blocks ? magic(K) : 0u;
-        pa.block_slices = n_slices; pa.block_slices_magic = magic(n_slices); pa.block_chunk_magic = magic(ta.fetch_chunk); pa.block_items = blocks ? (uint32_t)(passes * n_slices) : 0u; pa.block_progress = blocks ? w.block_progress : nullptr;
+        pa.sample_block = blocks ? sc.k_big : 0u; pa.block_magic = blocks && !sc.tapered ? magic(sc.k_big) : 0u;
+        pa.block_min = blocks && sc.tapered ? sc.k_min : 0u; pa.block_taper_end = blocks && sc.tapered ? sc.taper_end : 0u;
+        pa.block_slices = n_slices; pa.block_slices_magic = magic(n_slices); pa.block_chunk_magic = magic(ta.fetch_chunk); pa.block_items = blocks ? (uint32_t)((uint64_t)sc.passes * n_slices) : 0u; pa.block_progress = blocks ? w.block_progress : nullptr;
         if (blocks) {
             HIP_TRY(ctx, hipMemsetAsync(w.block_progress, 0, sizeof(uint32_t) * n_slices, s));
             ctx->sample_block_launches++;
+            ctx->last_schedule[0] = sc.k_big; ctx->last_schedule[1] = sc.k_min; ctx->last_schedule[2] = sc.tapered ? sc.taper_end : 0u; ctx->last_schedule[3] = sc.passes;
         }
         // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
@@ -777,6 +813,25 @@ int hrt_color_to_float4(HrtContext *ctx, const HrtFloat4 *d_src, HrtFloat4 *d_ds
 }
 
 // ---- measurement ----------------------------------------------------------------------
+int hrt_sample_schedule(uint32_t spp, uint32_t block_big, uint32_t block_min, uint32_t *first, uint32_t capacity, uint32_t *n_passes) {
+    const bool tapered = block_min != 0u;
+    if (!first || !n_passes || spp == 0u || block_big == 0u || block_min > block_big) return HRT_ERR_INVALID;
+    if (tapered && ((block_big & (block_big - 1u)) != 0u || (block_min & (block_min - 1u)) != 0u || !taper_fits(spp, block_big))) return HRT_ERR_INVALID;
+    const SampleSchedule sc = tapered ? sample_schedule(spp, block_big, block_min) : uniform_schedule(spp, block_big);
+    if (sc.passes >= capacity) return HRT_ERR_INVALID;
+    for (uint32_t b = 0; b < sc.passes; ++b) first[b] = schedule_first(sc, b);
+    first[sc.passes] = spp;
+    // what the kernel's lanes see: a boundary behind sample p exactly where a pass starts (block_ends is path_finish's test)
+    if (tapered)
+        for (uint32_t p = 1, b = 1; p < spp; ++p) {
+            const bool starts = b < sc.passes && first[b] == p;
+            if (block_ends(sc.k_big, sc.k_min, sc.taper_end, p) != starts) return HRT_ERR_STATE;
+            if (starts) ++b;
+        }
+    *n_passes = sc.passes;
+    return HRT_OK;
+}
+
 int hrt_stats_reset(HrtContext *ctx) {
     if (!ctx) return HRT_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
@@ -813,6 +868,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     }
     out->fused_fallback_launches = ctx->fused_fallback_launches; out->graph_replays = ctx->graph_replays;
     out->sample_block_launches = ctx->sample_block_launches;
+    for (int i = 0; i < 4; ++i) out->sample_block_schedule[i] = ctx->last_schedule[i];
     return HRT_OK;
 }
 

@@ -247,6 +247,9 @@ struct HrtContext {
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)
     uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks
+    int taper_big = kSampleTaperBig, taper_min = kSampleTaperMin;      // HRT_SAMPLE_TAPER: what `auto` hands out -- blocks that start at taper_big samples and end on taper_min (0: uniform blocks of kSampleBlockAuto)
+    bool taper_forced = false;                  // ... whatever the tile, like HRT_SAMPLE_BLOCK=N (tests)
+    uint32_t last_schedule[4] = {0u, 0u, 0u, 0u};      // the last launch in sample blocks: largest block, smallest block, end of the halvings (0: uniform), passes
     int fused_max_spp = 512;                    // samples per fused launch
     int fetch_chunk = 64;
     int substream_min_pixels = 32768;

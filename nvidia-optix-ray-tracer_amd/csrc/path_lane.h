@@ -39,8 +39,9 @@ struct PathStep {
 };
 
 // Sample blocks (PathArgs::sample_block = K > 0): the work item is not a slice of pixels with all their samples but
-// (pass b, slice q) = samples [b K, (b + 1) K) of the slice's pixels; the counters hand all items of pass 0 out, then pass 1's, ... so
-// that only the last pass has an end-of-frame tail, K / spp of a whole pixel's.  A lane that finishes a block leaves sum and RNG state
+// (pass b, slice q) = samples [first(b), first(b + 1)) of the slice's pixels, first(b) = b K or a tapered schedule that starts on large
+// blocks and ends on small ones (device_types.h: block_first); the counters hand all items of pass 0 out, then pass 1's, ... so
+// that only the last pass has an end-of-frame tail, its share of a whole pixel's -- while the large blocks keep the hand-overs few.  A lane that finishes a block leaves sum and RNG state
 // where a finished pixel's go and the lane that takes the pixel's next block continues from there: the same additions in the same
 // order from the same stream, the same bits.  What a wave knows about the item it holds (wave-uniform):
 struct BlockSlice {
@@ -110,10 +111,15 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             atomicAdd(a.path.slice_cost + P.px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - P.px_t0) >> 4);
         bool ends = P.px_sample >= a.path.spp;
         if constexpr (BLOCKS) {
-            // ... or px_sample is a multiple of K: with M = min(2^32 / K, 2^32 - 1) the quotient is short by one at most, so the remainder
-            // comes out as 0 or K exactly then (every px_sample, every K >= 1; K = 0, M = 0: never, px_sample is at least 1 here)
-            const uint32_t rem = P.px_sample - __umulhi(P.px_sample, a.path.block_magic) * a.path.sample_block;
-            ends = ends || rem == 0u || rem == a.path.sample_block;
+            if (a.path.block_magic != 0u) {
+                // ... or, uniform blocks, px_sample is a multiple of K: with M = min(2^32 / K, 2^32 - 1) the quotient is short by one at most, so
+                // the remainder comes out as 0 or K exactly then (every px_sample, every K >= 1)
+                const uint32_t rem = P.px_sample - __umulhi(P.px_sample, a.path.block_magic) * a.path.sample_block;
+                ends = ends || rem == 0u || rem == a.path.sample_block;
+            } else {
+                // ... or the tapered schedule has a boundary there (device_types.h; no blocks, all three 0: never)
+                ends = ends || block_ends(a.path.sample_block, a.path.block_min, a.path.block_taper_end, P.px_sample);
+            }
         }
         if (ends) {
             if (BLOCKS && a.path.sample_block != 0u) handover_store(a.path, P, a.fetch_chunk);
@@ -202,7 +208,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                     P.px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
                     if (by_blocks) {
                         if constexpr (BLOCKS) {                     // ... and so do later blocks of a launch
-                            P.px_sample = B->pass * a.path.sample_block;
+                            P.px_sample = block_first(a.path.sample_block, a.path.block_min, a.path.block_taper_end, a.path.block_magic == 0u, B->pass);
                             P.px_first = P.px_first && B->pass == 0u;
                             handover_load(a.path, P, !P.px_first);
                         }

@@ -16,6 +16,24 @@ TICK_MS = 1e-5          # one tick of the 100 MHz clock
 BIAS = 1 << 40          # LaneStats::report keeps clocks relative to the first reporting wave's, plus this
 
 
+def schedule(s, spp):
+    """the blocks the launch ran in: HrtStats.sample_block_schedule (a library from before it existed leaves the field zero) through hrt_sample_schedule"""
+    import ctypes as C
+    big, small, end, passes = (int(x) for x in getattr(s, "sample_block_schedule", (0, 0, 0, 0)))
+    if int(s.sample_block_launches) == 0:
+        return "no blocks"
+    if big == 0:
+        return "blocks (this library does not say which)"
+    lib = hrt.load_library()
+    if not hasattr(lib, "hrt_sample_schedule"):
+        return f"largest {big}, smallest {small}, {passes} passes"
+    first, n = (C.c_uint32 * (spp + 1))(), C.c_uint32(0)
+    if lib.hrt_sample_schedule(spp, big, small if end else 0, first, spp + 1, C.byref(n)) != 0 or n.value != passes:
+        return f"largest {big}, smallest {small}, {passes} passes"
+    sizes = [first[i + 1] - first[i] for i in range(n.value)]
+    return ("tapered " if end else "uniform ") + " ".join(str(k) for k in sizes) + f" ({passes} passes, {passes - 1} hand-overs per pixel)"
+
+
 def profile(r, spp, width, height):
     r.set_frame(width, height, hrt.scenes.SEED_SALT, aov=False)
     r.render(2)
@@ -37,7 +55,9 @@ def profile(r, spp, width, height):
     idle = gone + t[6]
     slots = kernel_ms / TICK_MS * waves * 64
     it_all, alive_all = s.debug[0], s.debug[1]
-    print(f"C4 {width}x{height}, {spp} spp, sample_block {os.environ.get('HRT_SAMPLE_BLOCK', 'default')}: kernel {kernel_ms:.2f} ms, {waves} waves, {s.rays} rays")
+    print(f"C4 {width}x{height}, {spp} spp, sample_block {os.environ.get('HRT_SAMPLE_BLOCK', 'default')}, sample_taper {os.environ.get('HRT_SAMPLE_TAPER', 'default')}: "
+          f"kernel {kernel_ms:.2f} ms, {waves} waves, {s.rays} rays")
+    print(f"  schedule: {schedule(s, spp)}")
     print(f"  drained copy of the loop: {t[0]} of {it_all} wave iterations ({100.0 * t[0] / max(it_all, 1):.2f} %), "
           f"{t[1] / max(t[0], 1):.1f} lanes alive per iteration there against {alive_all / max(it_all, 1):.1f} over all")
     print(f"  first wave drained -> end of kernel: {span_ms:.2f} ms = {100.0 * span_ms / kernel_ms:.2f} % of the kernel's time")
