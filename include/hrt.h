@@ -71,6 +71,21 @@ typedef struct HrtContext HrtContext;
                                     for bit, a third fewer rays on the reference's scenes.  HrtStats.rays counts TRAVERSED rays only, so Mrays/s figures
                                     with and without the flag are not comparable -- compare times.  Off by default (all published figures are without);
                                     ignored by the other execution modes (HRT_FUSED != 1, HRT_CTX_COUNT). */
+#define HRT_CTX_CAPTURE_PRIMARY 0x40u /* hrt_render_launch keeps every pixel's PRIMARY HIT -- (t, u, v, primitive, instance) of the first primary ray the path
+                                    kernel traces for the pixel, hrt_trace_rays' record, a miss as (tmax, ., ., 0xffffffff) -- in the context.  The denoiser's
+                                    guide pass (hrt_denoise_guides, hrt_denoise_launch, hrt_denoise_temporal_launch, hrt_denoise_variance_launch) traces exactly
+                                    those rays again; while the capture is valid for its call -- same TLAS handle, no update, rebuild or destruction of it
+                                    since, same frame size, the same camera bit for bit -- it takes the capture instead: the same guides and output bit for
+                                    bit, one traversal of the frame less, and its rays are not counted in HrtStats.rays.  hrt_primary_hits_get hands the
+                                    records out (picking, depth / id AOVs).  The image, the RNG states and the launch's ray counts are what they are
+                                    without the flag.  A launch captures when it renders the whole frame (tile == NULL or every row) with the plain path
+                                    kernel: not with HRT_CTX_REUSE_PRIMARY at spp > 1, sample blocks (HRT_SAMPLE_BLOCK: by themselves from 64 samples on),
+                                    the cost-order probe of small tiles, round 1's path kernel, HRT_FUSED != 1 or HRT_CTX_COUNT -- renders of many
+                                    samples, where one more traversal does not count; higher-spp captures are deliberately left out.  Of a render cut
+                                    into several launches (HRT_FUSED_MAX_SPP) the first captures.  Every other hrt_render_launch, hrt_tlas_update /
+                                    hrt_tlas_destroy of the handle, hrt_ctx_set_flags, hrt_rng_free of the launch's states and a guide pass for another
+                                    frame (camera, size, tree) leave the context without a capture, and the guide pass traces as ever.  The capture is ordered like the colour buffer: enqueue the render and the
+                                    denoiser on the same stream, or synchronise between them.  HRT_CAPTURE_PRIMARY=1: every context.  32 B per pixel. */
 #define HRT_CTX_FAST_TRACE 0x4u  /* hrt_tlas_build prefers trace speed to build speed: the reference's OPTIX_BUILD_FLAG_PREFER_FAST_TRACE
                                     (its GAS builds, RendererImpl.cu:94,118,144).  The tree is then built WITH SPATIAL SPLITS: on the device
                                     (csrc/build_split.hip: top-down SAH splits of references level by level, PLOC within the cells that
@@ -99,7 +114,7 @@ typedef struct HrtContext HrtContext;
 /* replaces createContext / destroyContext, src/Global/RendererImpl.cu:6-27 */
 int  hrt_ctx_create(int device_id, uint32_t flags, HrtContext **out_ctx);
 int  hrt_ctx_destroy(HrtContext *ctx);
-int  hrt_ctx_set_flags(HrtContext *ctx, uint32_t flags);   /* switch HRT_CTX_TIMING / HRT_CTX_COUNT / HRT_CTX_REUSE_PRIMARY at run time */
+int  hrt_ctx_set_flags(HrtContext *ctx, uint32_t flags);   /* switch HRT_CTX_TIMING / HRT_CTX_COUNT / HRT_CTX_REUSE_PRIMARY / HRT_CTX_CAPTURE_PRIMARY at run time; forgets the primary-hit capture */
 const char *hrt_last_error(const HrtContext *ctx);        /* ctx may be NULL: creation errors */
 const char *hrt_version(void);
 
@@ -169,6 +184,10 @@ int  hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params,
                        const HrtRayGenParams *h_raygen, uint32_t spp,
                        const HrtTile *tile, void *stream);
 int  hrt_sync(HrtContext *ctx, void *stream);
+/* HRT_CTX_CAPTURE_PRIMARY: the primary hits the last hrt_render_launch captured, width * height of each in frame order, in
+ * hrt_trace_rays' output form (on a miss t = tmax, the shader's FLOAT_INFINITY_VALUE 1e16, and prim = inst = 0xffffffff); a NULL pointer skips its array.
+ * HRT_ERR_STATE when the context holds no valid capture (see the flag).  Enqueued only, behind the launch on the same stream. */
+int  hrt_primary_hits_get(HrtContext *ctx, float *d_t, float *d_u, float *d_v, uint32_t *d_prim, uint32_t *d_inst, void *stream);
 
 /* replaces convertFloat4ToUchar4Kernel, src/Global/RendererImpl.cu:672-678 (second sRGB
  * encode: quirk Q7) */
@@ -191,7 +210,8 @@ int  hrt_color_to_float4(HrtContext *ctx, const HrtFloat4 *d_src, HrtFloat4 *d_d
  * own inf - inf) has a NaN weight sum and keeps its colour unfiltered; otherwise an infinite tap turns the channels it is infinite in
  * to NaN; later passes carry this at most 2 (2^iterations - 1) pixels far.  The alpha channel is always the centre pixel's bits. */
 
-/* one pixel's guide: the primary hit of the ray the path kernel traces first for the pixel (same origin, direction, tmin, tmax) */
+/* one pixel's guide: the primary hit of the ray the path kernel traces first for the pixel (same origin, direction, tmin, tmax) --
+ * traced by the guide pass, or, under HRT_CTX_CAPTURE_PRIMARY, taken from what the render launch itself found (the same bits) */
 typedef struct HrtDenoiseGuide {
     uint16_t normal[3];            /* IEEE half, round to nearest even: normalize(normalVector) as Shader.cu:224-226 (front-face flipped) */
     uint16_t albedo[3];            /* IEEE half, round to nearest even: the hit material's albedo                                          */
@@ -315,6 +335,9 @@ typedef struct HrtStats {
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
     uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
                                               at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
+    uint64_t primary_capture_launches;     /* path-kernel launches since the context was created that captured primary hits (HRT_CTX_CAPTURE_PRIMARY) */
+    uint64_t guide_passes_traced;          /* denoiser guide passes since the context was created that traced their rays ...                          */
+    uint64_t guide_passes_captured;        /* ... and that took the render launch's capture instead (they add nothing to `rays`)                      */
 } HrtStats;
 
 /* The sample blocks a path-kernel launch of spp samples is cut into (host only, no context, no GPU): block_big = N, block_min = 0 -- uniform

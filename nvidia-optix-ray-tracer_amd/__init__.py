@@ -82,7 +82,8 @@ class Stats(C.Structure):
                 ("tlas_refits", C.c_uint64), ("tlas_rebuilds", C.c_uint64), ("tlas_refit_ratio", C.c_double),
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
                 ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
-                ("sample_block_schedule", C.c_uint64 * 4)]
+                ("sample_block_schedule", C.c_uint64 * 4),
+                ("primary_capture_launches", C.c_uint64), ("guide_passes_traced", C.c_uint64), ("guide_passes_captured", C.c_uint64)]
 
 
 class BvhBlob(C.Structure):
@@ -113,7 +114,7 @@ assert C.sizeof(GlobalParams) == 16 and C.sizeof(RayGenParams) == 80 and C.sizeo
 assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof(Instance) == 80
 
 PROGRAM_SPHERE_ROUGH, PROGRAM_SPHERE_METAL, PROGRAM_TRIANGLE_ROUGH, PROGRAM_TRIANGLE_METAL = range(4)
-CTX_TIMING, CTX_COUNT, CTX_FAST_TRACE, CTX_ASYNC_UPDATE, CTX_TWO_LEVEL, CTX_REUSE_PRIMARY = 1, 2, 4, 8, 16, 32
+CTX_TIMING, CTX_COUNT, CTX_FAST_TRACE, CTX_ASYNC_UPDATE, CTX_TWO_LEVEL, CTX_REUSE_PRIMARY, CTX_CAPTURE_PRIMARY = 1, 2, 4, 8, 16, 32, 64
 
 # every symbol include/hrt.h declares (checked by the CPU test-suite)
 EXPORTS = [
@@ -121,7 +122,7 @@ EXPORTS = [
     "hrt_blas_build_triangles", "hrt_blas_build_spheres", "hrt_blas_destroy",
     "hrt_tlas_build", "hrt_tlas_update", "hrt_tlas_destroy", "hrt_pose_instances",
     "hrt_sbt_record_pack_header", "hrt_materials_set", "hrt_miss_set",
-    "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_to_rgba8", "hrt_color_to_float4",
+    "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_primary_hits_get", "hrt_to_rgba8", "hrt_color_to_float4",
     "hrt_stats_reset", "hrt_stats_get", "hrt_sample_schedule", "hrt_trace_rays", "hrt_debug_set_linear_output",
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
@@ -178,6 +179,7 @@ def load_library():
     lib.hrt_render_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_uint32,
                                       C.POINTER(Tile), C.c_void_p]
     lib.hrt_sync.argtypes = [C.c_void_p, C.c_void_p]
+    lib.hrt_primary_hits_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_to_rgba8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.hrt_color_to_float4.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.hrt_stats_reset.argtypes = [C.c_void_p]

@@ -1,5 +1,6 @@
-// fused_body.h -- the body of the persistent path kernel, ONCE, for the kernels that run it: k_fused (fused.hip) and k_path_blocks
-// (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h).  What the body does is described at the top of fused.hip.
+// fused_body.h -- the body of the persistent path kernel, ONCE, for the kernels that run it: k_fused (fused.hip), k_path_blocks
+// (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h) and k_path_capture (fused_capture.hip: primary hits kept per pixel).
+// What the body does is described at the top of fused.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,9 +125,11 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 // because the hand-over costs the regeneration spilled registers, which the launches without blocks need not pay.
 // `a`: the kernel's only argument (see kernarg_traverse_args); what the traversal loop consumes comes from it, the regeneration's
 // constants from the segment.
-template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS>
+// CAPTURE: k_path_capture (fused_capture.hip) -- every pixel's primary hit is left in frame order as well (path_lane.h: path_finish).
+template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    static_assert(!CAPTURE || (!REUSE && !BLOCKS), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
     __shared__ uint2 s_nodes[kNodeStackLds][kTraverseBlock];     // sibling groups: one per tree level (hrt_api.cpp sends deeper trees to k_traverse)
     __shared__ uint2 s_leaves[kLeafStackLds][kTraverseBlock];    // leaf groups
@@ -204,7 +207,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
+                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
             }
             exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
             stats.drained(exhausted);

@@ -22,7 +22,7 @@ inline std::string join(const std::string &base, const std::string &p) { return 
 // --denoise-temporal (anywhere): the same slot in the library's temporal mode, each frame blended into the history of the ones before
 // --denoise-variance (anywhere): the temporal mode with variance-guided edge stops (denoiseOutputVariance)
 enum class DenoiseMode { kNone, kSpatial, kTemporal, kVariance };
-constexpr const char *kDenoiseUsage = "[--denoise | --denoise-temporal | --denoise-variance]";
+constexpr const char *kDenoiseUsage = "[--denoise | --denoise-temporal | --denoise-variance] [--no-capture]";
 
 // takes the switches out of argv; two different ones end the program with status 2
 inline DenoiseMode parseDenoiseMode(int &argc, char **argv) {
@@ -40,6 +40,20 @@ inline DenoiseMode parseDenoiseMode(int &argc, char **argv) {
     argc = k;
     if (clash) { std::fprintf(stderr, "--denoise, --denoise-temporal and --denoise-variance exclude each other\n"); std::exit(2); }
     return mode;
+}
+
+// What a driver adds to its context's flags for the denoiser: HRT_CTX_CAPTURE_PRIMARY, so that the guide pass of every frame takes the
+// primary hits the render launch has just found instead of tracing them again (the same image bit for bit; include/hrt.h).
+// --no-capture (anywhere, taken out of argv): the guide pass traces, as it does in a context without the flag.
+inline uint32_t denoiseContextFlags(DenoiseMode mode, int &argc, char **argv) {
+    bool capture = mode != DenoiseMode::kNone;
+    int k = 1;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--no-capture") == 0) capture = false;
+        else argv[k++] = argv[i];
+    }
+    argc = k;
+    return capture ? HRT_CTX_CAPTURE_PRIMARY : 0u;
 }
 
 // the denoiser's slot of a frame, in place: the colour buffer is not read again

@@ -2,7 +2,7 @@
 // main() (src/Global/Main.cu:21-36) -> RendererMesh::writeCacheFilesAndExit (src/Util/VTKMeshReader.cu:146-215) when the
 // config says "cache", else RendererMesh::commitRendererData (src/Global/RendererMesh.cu:160-310) -> RendererMesh::startRender's
 // frame loop (:312-440) with the window and camera input left out; the denoiser (denoiseOutput, :420-426) runs with --denoise.
-//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]
+//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
 // Loading: up to cache-process-thread-count loader threads, each with its own stream, read particleN.cache and build one GAS per
 // particle plus the file's IAS ON THE DEVICE (readVTKFileCache, :93-157).  Per frame: every particle drifts by its velocity
@@ -50,6 +50,7 @@ struct FileData {
 
 int main(int argc, char **argv) {
     const DenoiseMode denoiseMode = parseDenoiseMode(argc, argv);
+    const uint32_t denoiseFlags = denoiseContextFlags(denoiseMode, argc, argv);
     if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s\n", argv[0], kDenoiseUsage); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
@@ -88,7 +89,7 @@ int main(int argc, char **argv) {
 
     HrtContext *ctx = createContext(0, false);
     // the frame loop only moves instances: pose kernel, updateIAS and the launch are enqueued back to back with no read-back in between
-    const uint32_t flags = (std::getenv("HRT_MESH_RENDER_KERNEL_TIMES") ? HRT_CTX_TIMING : 0u) | (std::getenv("HRT_MESH_RENDER_SYNC_UPDATE") ? 0u : HRT_CTX_ASYNC_UPDATE);
+    const uint32_t flags = (std::getenv("HRT_MESH_RENDER_KERNEL_TIMES") ? HRT_CTX_TIMING : 0u) | (std::getenv("HRT_MESH_RENDER_SYNC_UPDATE") ? 0u : HRT_CTX_ASYNC_UPDATE) | denoiseFlags;
     hrtCheckError(ctx, hrt_ctx_set_flags(ctx, flags));
 
     // extra geometry: one GAS per sphere of the config (buildAddDataGAS, RendererMesh.cu:79-91), shared by every file

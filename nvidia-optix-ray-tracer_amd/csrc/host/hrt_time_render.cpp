@@ -2,7 +2,7 @@
 // main() (src/Global/Main.cu:12-50) -> RendererTime::commitRendererData (src/Global/RendererTime.cu:160-290)
 // -> RendererTime::startRender's frame loop (:373-520) with the window and camera input left out; the denoiser (denoiseOutput, :501-510)
 // runs with --denoise.
-//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance]
+//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
 // Per frame: hrt_pose_instances -> updateIAS -> launch + sync -> (denoiseOutput) -> convert to 8 bit; the last frame is written as PPM.
 #include "driver_common.hpp"
@@ -22,6 +22,7 @@ template <typename T> static T *toDevice(const T *host, size_t count) {
 
 int main(int argc, char **argv) {
     const DenoiseMode denoiseMode = parseDenoiseMode(argc, argv);
+    const uint32_t denoiseFlags = denoiseContextFlags(denoiseMode, argc, argv);
     if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s\n", argv[0], kDenoiseUsage); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
@@ -37,7 +38,7 @@ int main(int argc, char **argv) {
     HrtContext *ctx = createContext(0, false);
     // the frame loop below only moves instances (same shapes, same records): updates may be asynchronous -- pose kernel, updateIAS and
     // the launch are then enqueued back to back with no read-back in between (HRT_TIME_RENDER_SYNC_UPDATE=1: the synchronous update)
-    const uint32_t flags = (std::getenv("HRT_TIME_RENDER_KERNEL_TIMES") ? HRT_CTX_TIMING : 0u) | (std::getenv("HRT_TIME_RENDER_SYNC_UPDATE") ? 0u : HRT_CTX_ASYNC_UPDATE);
+    const uint32_t flags = (std::getenv("HRT_TIME_RENDER_KERNEL_TIMES") ? HRT_CTX_TIMING : 0u) | (std::getenv("HRT_TIME_RENDER_SYNC_UPDATE") ? 0u : HRT_CTX_ASYNC_UPDATE) | denoiseFlags;
     hrtCheckError(ctx, hrt_ctx_set_flags(ctx, flags));
 
     // extra geometry first (buildAddDataGAS, RendererTime.cu:73-84), then one GAS per STL shape in name order (:183-190)

@@ -163,6 +163,17 @@ inline void launch(HrtContext *ctx, const HrtGlobalParams &params, const HrtRayG
     hrtCheckError(ctx, hrt_sync(ctx, stream));
 }
 
+// HRT_CTX_CAPTURE_PRIMARY (include/hrt.h; no reference counterpart): the primary hit of every pixel as the last full-frame launch found
+// it, width * height of each in frame order (a NULL pointer skips its array) -- picking, depth and id buffers without a second trace.
+// false when the context holds no valid capture.  With the flag set, the three denoiseOutput calls below take the capture for their
+// guides instead of tracing the frame's primary rays again (launch and denoiser on the same stream).
+inline bool primaryHits(HrtContext *ctx, float *dev_t, float *dev_u, float *dev_v, uint32_t *dev_prim, uint32_t *dev_inst, hipStream_t stream = nullptr) {
+    const int rc = hrt_primary_hits_get(ctx, dev_t, dev_u, dev_v, dev_prim, dev_inst, stream);
+    if (rc == HRT_ERR_STATE) return false;
+    hrtCheckError(ctx, rc);
+    return true;
+}
+
 // denoiseOutput, src/Global/RendererImpl.cu:680-710: the OptiX denoiser's slot, filled by the library's guided a-trous filter (include/hrt.h);
 // like the reference it reads the frame's colour buffer and leaves the result for convertFloat4ToUchar4Kernel (hrt_to_rgba8).  The
 // skipDenoise branch (Tab held) converts the colour buffer directly.

@@ -1142,6 +1142,7 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     hipStream_t s = (hipStream_t)stream;
     Tlas *t;
     { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(tlas); if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "unknown TLAS handle"); t = it->second.get(); }
+    if (ctx->capture.tlas == tlas) ctx->capture.valid = false;      // (the primary hits of the tree as it was: a refit keeps the generation)
     if (n != t->n_instances) return fail(ctx, HRT_ERR_INVALID, "update must keep the instance count (%u != %u)", n, t->n_instances);
     if (n && !d_instances) return fail(ctx, HRT_ERR_INVALID, "d_instances is NULL");
     bool force_rebuild = false, sbt_sync = false;
@@ -1267,6 +1268,7 @@ int hrt_tlas_destroy(HrtContext *ctx, HrtTraversable tlas) {
     auto it = ctx->tlas.find(tlas);
     if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "unknown TLAS handle");
     (void)hipDeviceSynchronize();
+    if (ctx->capture.tlas == tlas) ctx->capture.valid = false;
     free_tlas_device(ctx, *it->second); free_tlas_host(*it->second);
     ctx->tlas.erase(it);
     return HRT_OK;

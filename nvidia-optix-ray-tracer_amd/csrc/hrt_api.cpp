@@ -154,6 +154,7 @@ int hrt_ctx_set_flags(HrtContext *ctx, uint32_t flags) {
     HIP_TRY(ctx, hipDeviceSynchronize());
     drain_spans(ctx);
     ctx->flags = flags;
+    ctx->capture.valid = false;      // (what a capture may stand in for depends on the flags: a two-level tree is not traced under HRT_CTX_COUNT)
     return HRT_OK;
 }
 
@@ -171,7 +172,8 @@ int hrt_ctx_destroy(HrtContext *ctx) {
     free_denoise_work(ctx);
     free_denoise_history(ctx);
     if (ctx->pin_stage) (void)hipHostFree(ctx->pin_stage);
-    void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.block_progress, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program};
+    void *ptrs[] = {w.accum, w.slice_cost, w.slice_order, w.block_progress, w.primary_cache, w.rows, ctx->d_jump, ctx->d_stats, ctx->d_hitgroups, ctx->d_inst_program,
+                    ctx->capture.tuvp, ctx->capture.inst};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (const ScratchArena &a : ctx->scratch_free) (void)hipFree(a.p);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -233,6 +235,7 @@ int hrt_rng_free(HrtContext *ctx, HrtRngState *d_states, void *stream) {
     if (!ctx) return HRT_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
     HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
+    if (d_states && ctx->capture.states == d_states) ctx->capture.valid = false;      // (the frame the capture is of ends with its RNG states)
     HIP_TRY(ctx, hipFree(d_states));
     return HRT_OK;
 }
@@ -441,6 +444,22 @@ static int render_fused(const LaunchFrame &f) {
         }
         pa.primary_cache = w.primary_cache;
     }
+    // HRT_CTX_CAPTURE_PRIMARY: a launch that would run plain k_fused<S, I, false> over the whole frame runs k_path_capture instead, which
+    // also leaves every pixel's primary hit in the context (PrimaryCapture).  Not with the primary-hit cache, the cost-order probe or
+    // sample blocks (below), not on round 1's kernel: frames of many samples, where one more traversal for the guides does not count.
+    const bool full_frame = (uint64_t)n == (uint64_t)rg->width * rg->height;      // (the tile's rows are distinct: every row of the frame)
+    bool capture = lean && !pa.primary_cache && full_frame && ((ctx->flags & HRT_CTX_CAPTURE_PRIMARY) != 0u || ctx->capture_primary);
+    if (capture && n > ctx->capture.capacity) {
+        PrimaryCapture &c = ctx->capture;
+        HIP_TRY(ctx, hipStreamSynchronize(s));      // (a guide pass that reads the arrays may be under way)
+        if (c.tuvp) (void)hipFree(c.tuvp);
+        if (c.inst) (void)hipFree(c.inst);
+        c.tuvp = nullptr; c.inst = nullptr; c.capacity = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&c.tuvp, sizeof(float4) * (size_t)n));
+        HIP_TRY(ctx, hipMalloc((void **)&c.inst, sizeof(uint32_t) * (size_t)n));
+        c.capacity = n;
+    }
+    bool captured = false;
     auto launch = [&]() { launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s); };
     // Longest-processing-time-first: a pixel's samples run one after the other in one lane, so a render ends with
     // whatever pixels were started last.  For renders of many samples the first sample is a probe launch of its own
@@ -477,6 +496,7 @@ static int render_fused(const LaunchFrame &f) {
         pa.slice_cost = nullptr; pa.slice_order = w.slice_order;
         done_spp = probe_spp;
         lpt = true;
+        capture = false;
     }
     // Sample blocks (path_lane.h): a lane gives its pixel back after K samples and the slices go round pass by pass, so only the last K
     // samples of a frame run in a draining GPU.  k_fused's one-level kernels without the primary-hit cache (which wants a pixel's samples in
@@ -521,7 +541,14 @@ static int render_fused(const LaunchFrame &f) {
         // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         ctx->fused_counters_clean = false;
-        { Timer tm(ctx, s, HRT_K_PATHS); launch(); }
+        if (capture && done_spp == 0u && !blocks) {
+            // (of a render cut into several launches the first one captures: the primary ray of a pixel's first sample is every sample's)
+            pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst;
+            { Timer tm(ctx, s, HRT_K_PATHS); launch_fused_capture(ta, t->has_spheres, pk.kernel == PathKernel::FusedInstanced, grid, s); }
+            pa.trace_tuvp = nullptr; pa.trace_inst = nullptr;
+            ctx->primary_capture_launches++;
+            captured = true;
+        } else { Timer tm(ctx, s, HRT_K_PATHS); launch(); }
         done_spp += now;
     }
     FinalizeArgs fa{};
@@ -535,6 +562,13 @@ static int render_fused(const LaunchFrame &f) {
     ctx->fused_counters_clean = fa.reset_counters != nullptr;
     ctx->paths += (uint64_t)n * spp;
     ctx->last_tlas = h_params->handle;
+    if (captured) {
+        PrimaryCapture &c = ctx->capture;
+        c.tlas = h_params->handle; c.generation = t->generation; c.width = rg->width; c.height = rg->height; c.states = h_params->stateArray;
+        std::memcpy(c.camera, &rg->cameraCenter, 12); std::memcpy(c.camera + 12, &rg->cameraU, 12);
+        std::memcpy(c.camera + 24, &rg->cameraV, 12); std::memcpy(c.camera + 36, &rg->cameraW, 12);
+        c.valid = true;
+    }
     return HRT_OK;
 }
 
@@ -745,6 +779,7 @@ int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const Hr
     if (!ctx || !h_params || !rg) return HRT_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     (void)hipSetDevice(ctx->device);
+    ctx->capture.valid = false;      // (whatever this launch does: only a complete capture of its own makes it valid again, render_fused)
     if (spp == 0) return fail(ctx, HRT_ERR_INVALID, "spp must be >= 1");
     if (rg->width == 0 || rg->height == 0 || (uint64_t)rg->width * rg->height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", rg->width, rg->height);
     if (!rg->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
@@ -869,6 +904,18 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->fused_fallback_launches = ctx->fused_fallback_launches; out->graph_replays = ctx->graph_replays;
     out->sample_block_launches = ctx->sample_block_launches;
     for (int i = 0; i < 4; ++i) out->sample_block_schedule[i] = ctx->last_schedule[i];
+    out->primary_capture_launches = ctx->primary_capture_launches;
+    out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
+    return HRT_OK;
+}
+
+int hrt_primary_hits_get(HrtContext *ctx, float *d_t, float *d_u, float *d_v, uint32_t *d_prim, uint32_t *d_inst, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    const PrimaryCapture &c = ctx->capture;
+    if (!c.valid) return fail(ctx, HRT_ERR_STATE, "no valid primary-hit capture: the last hrt_render_launch did not capture the whole frame (HRT_CTX_CAPTURE_PRIMARY), or the scene, the flags or the frame have changed since");
+    launch_unpack_hits(c.tuvp, c.inst, c.width * c.height, d_t, d_u, d_v, d_prim, d_inst, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
     return HRT_OK;
 }
 

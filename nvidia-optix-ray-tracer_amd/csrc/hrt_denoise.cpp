@@ -154,10 +154,21 @@ int run_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGen
     ra.rays = d.rays; ra.width = rg->width; ra.height = rg->height;
     std::memcpy(ra.center, &rg->cameraCenter, 12); std::memcpy(ra.U, &rg->cameraU, 12); std::memcpy(ra.V, &rg->cameraV, 12); std::memcpy(ra.W, &rg->cameraW, 12);
     launch_denoise_rays(ra, s);
-    rc = trace_records(ctx, *t, d.rays, n, kFloatZero, kFloatInfinity, false, d.tuvp, d.inst, d.fetch, s);      // Shader.cu:266
-    if (rc != HRT_OK) return rc;
+    // The hit records: what the last hrt_render_launch captured (HRT_CTX_CAPTURE_PRIMARY) when that is the hits of exactly these rays --
+    // the path kernel has just traced them as every pixel's first primary ray -- and a traversal of them otherwise.  Ordered after the
+    // capturing launch by the stream, as the colour buffer is.
+    if (capture_matches(ctx, h_params->handle, *t, rg)) {
+        d.hit_tuvp = ctx->capture.tuvp; d.hit_inst = ctx->capture.inst;
+        ctx->guide_passes_captured++;
+    } else {
+        ctx->capture.valid = false;      // (asked for another frame -- camera, size, tree -- than the one it holds, the context keeps no capture)
+        rc = trace_records(ctx, *t, d.rays, n, kFloatZero, kFloatInfinity, false, d.tuvp, d.inst, d.fetch, s);      // Shader.cu:266
+        if (rc != HRT_OK) return rc;
+        d.hit_tuvp = d.tuvp; d.hit_inst = d.inst;
+        ctx->guide_passes_traced++;
+    }
     DenoiseGuideArgs ga{};
-    ga.rays = d.rays; ga.tuvp = d.tuvp; ga.inst = d.inst; ga.n = n;
+    ga.rays = d.rays; ga.tuvp = d.hit_tuvp; ga.inst = d.hit_inst; ga.n = n;
     ga.hitgroups = ctx->d_hitgroups; ga.inst_program = ctx->d_inst_program; ga.guides = guides ? guides : d.guides;
     launch_denoise_guides(ga, s);
     HIP_TRY(ctx, hipGetLastError());
@@ -226,7 +237,7 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     if (rc != HRT_OK) return rc;
     const DenoiseWork &d = ctx->denoise;
     DenoiseTemporalArgs ta{};
-    ta.rays = d.rays; ta.tuvp = d.tuvp; ta.inst = d.inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
+    ta.rays = d.rays; ta.tuvp = d.hit_tuvp; ta.inst = d.hit_inst; ta.color = reinterpret_cast<const float4 *>(h_raygen->colorBuffer);
     ta.inst_inv = t->dev.d_inst_inv; ta.prev_xf = prev.xf;
     ta.prev_accum = prev.accum; ta.prev_length = prev.length; ta.prev_guides = prev.guides; ta.prev_id = prev.id;
     ta.accum = next.accum; ta.length = next.length; ta.id = next.id; ta.motion = h.motion;

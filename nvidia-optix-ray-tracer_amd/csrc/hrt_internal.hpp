@@ -149,6 +149,19 @@ struct DenoiseWork {
     float4 *frame[2] = {nullptr, nullptr};
     float *var[2] = {nullptr, nullptr};
     uint32_t *fetch = nullptr;              // 8 x 32 slice counters of the traversal
+    const float4 *hit_tuvp = nullptr; const uint32_t *hit_inst = nullptr;      // the hit records the last guide pass took: tuvp / inst (traced) or the context's primary capture
+};
+
+// HRT_CTX_CAPTURE_PRIMARY: every pixel's primary hit as the path kernel of the last hrt_render_launch found it (k_path_capture), in frame
+// order and hrt_trace_rays' form, and what it is the hit of.  The denoiser's guide pass takes it instead of tracing when its call asks
+// for exactly that (capture_matches); hrt_primary_hits_get hands it out.
+struct PrimaryCapture {
+    float4 *tuvp = nullptr; uint32_t *inst = nullptr; uint32_t capacity = 0;      // pixels the two arrays hold
+    bool valid = false;                     // a launch that captured covered every row of the frame, and nothing has changed since
+    uint64_t tlas = 0, generation = 0;      // the tree: handle and Tlas::generation (updates of the handle clear `valid` themselves: a refit keeps the generation)
+    uint32_t width = 0, height = 0;
+    unsigned char camera[48];               // cameraCenter, U, V, W as the launch had them, compared bitwise
+    const void *states = nullptr;           // the launch's RNG states: hrt_rng_free of them ends the frame the capture is of
 };
 
 // the temporal mode's history (hrt_denoise.cpp): two sets, the last call's and the one this call writes, swapped per call; each holds the
@@ -244,6 +257,10 @@ struct HrtContext {
     int fused = 1;                              // 1: fused persistent path kernel k_fused (default), 0: wavefront kernels, -1: fused only for small tiles
     int fused_max_pixels = 700000;
     bool reuse_primary = false;                 // HRT_REUSE_PRIMARY: every launch as under HRT_CTX_REUSE_PRIMARY
+    bool capture_primary = false;               // HRT_CAPTURE_PRIMARY: every launch as under HRT_CTX_CAPTURE_PRIMARY
+    hrt::PrimaryCapture capture;
+    uint64_t primary_capture_launches = 0;      // path-kernel launches that ran k_path_capture
+    uint64_t guide_passes_traced = 0, guide_passes_captured = 0;      // the denoiser's guide passes: traced / served from the capture
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)
     uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks
@@ -306,6 +323,15 @@ inline int find_tlas(HrtContext *ctx, uint64_t handle, Tlas *&t) {
     if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.handle 0x%llx is not a TLAS", (unsigned long long)handle);
     t = it->second.get();
     return HRT_OK;
+}
+
+// the capture is the primary hits of exactly this call's rays: same tree (handle and generation), frame size and camera bits
+inline bool capture_matches(const HrtContext *ctx, uint64_t handle, const Tlas &t, const HrtRayGenParams *rg) {
+    const PrimaryCapture &c = ctx->capture;
+    static_assert(sizeof(rg->cameraCenter) == 12 && sizeof(c.camera) == 48, "four float3");
+    return c.valid && c.tlas == handle && c.generation == t.generation && c.width == rg->width && c.height == rg->height &&
+           std::memcmp(c.camera, &rg->cameraCenter, 12) == 0 && std::memcmp(c.camera + 12, &rg->cameraU, 12) == 0 &&
+           std::memcmp(c.camera + 24, &rg->cameraV, 12) == 0 && std::memcmp(c.camera + 36, &rg->cameraW, 12) == 0;
 }
 
 constexpr int kMaxSubTiles = 8;

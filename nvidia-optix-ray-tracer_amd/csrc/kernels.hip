@@ -606,7 +606,12 @@ __global__ __launch_bounds__(256) void k_unpack_hits(const float4 *tuvp, const u
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 h = tuvp[i];
-    t[i] = h.x; u[i] = h.y; v[i] = h.z; prim[i] = __float_as_uint(h.w); oinst[i] = inst[i];
+    // (hrt_primary_hits_get: a NULL pointer skips its array)
+    if (t) t[i] = h.x;
+    if (u) u[i] = h.y;
+    if (v) v[i] = h.z;
+    if (prim) prim[i] = __float_as_uint(h.w);
+    if (oinst) oinst[i] = inst[i];
 }
 // the hit records of n rays that cannot hit anything (an empty interval, tmax <= tmin: answered without a traversal); `rays`: the counter
 // the path kernel would have added them to

@@ -87,11 +87,20 @@ __device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, b
 // REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
 // BLOCKS: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
 // SEED: the kernel starts repeat primary rays at PathLane::px_seed, so a finished primary ray records it (and path_take resets it).
-template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false>
+// CAPTURE (k_path_capture, fused_capture.hip; HRT_CTX_CAPTURE_PRIMARY): the primary ray of the first sample the launch takes of a pixel
+// leaves its hit record in frame order, in hrt_trace_rays' form (a miss: tmax, kMissPrim), where the denoiser's guide pass and
+// hrt_primary_hits_get find it.  PathArgs::trace_tuvp / trace_inst are free in a render (trace_rays == NULL) and carry the two arrays.
+template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst) {
     PathStep st;
     const bool miss = bprim == kMissPrim;
     if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) P.px_seed = bt; }      // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
+    if constexpr (CAPTURE) {
+        if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // (the primary-hit cache's condition, fused_body.h)
+            a.path.trace_tuvp[P.px_tid] = make_float4(bt, bu, bv, __uint_as_float(bprim));
+            a.path.trace_inst[P.px_tid] = binst;
+        }
+    }
     if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
         a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
         a.path.trace_inst[P.px_local] = binst;

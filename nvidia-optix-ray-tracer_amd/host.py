@@ -270,6 +270,20 @@ class Renderer:
         if sync:
             self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
 
+    def primary_hits(self):
+        """CTX_CAPTURE_PRIMARY: the primary hit of every pixel as the last render() found it, (t, u, v, prim, inst) numpy arrays of
+        width * height in frame order -- trace_rays' form, a miss as (tmax = 1e16, ., ., 0xffffffff, 0xffffffff).  Raises HrtError (status -5)
+        when the context holds no valid capture."""
+        torch = self._torch
+        n = self.width * self.height
+        t, u, v = (torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(3))
+        prim, inst = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
+        st = self._stream()
+        self._check(self.lib.hrt_primary_hits_get(self.ctx, t.data_ptr(), u.data_ptr(), v.data_ptr(), prim.data_ptr(), inst.data_ptr(), st),
+                    "hrt_primary_hits_get")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return (t.cpu().numpy(), u.cpu().numpy(), v.cpu().numpy(), prim.cpu().numpy().view(np.uint32), inst.cpu().numpy().view(np.uint32))
+
     def to_rgba8(self):
         torch = self._torch
         out = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=self.device)

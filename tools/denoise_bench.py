@@ -6,8 +6,12 @@ split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_de
 --temporal adds hrt_denoise_temporal_launch (the frame repeated, so that every call after the first blends with a history): its own
 kernel is k_denoise_temporal.  --variance adds hrt_denoise_variance_launch in the same way (k_denoise_temporal<true>,
 k_denoise_variance, k_denoise_pass<3, true>: the same pass kernel's variance form) and hrt_denoise_filter_variance over the frame's guides and a constant variance.
+--capture sets HRT_CTX_CAPTURE_PRIMARY: the render launch runs k_path_capture and the guide pass of every denoise call takes its
+primary hits instead of tracing (guides_ms is then the pass without its traversal).  With or without it, frame_ms is what the switch is
+about -- a 1-spp render and hrt_denoise_launch enqueued back to back, one synchronisation --, and path_kernel_ms the path kernel of
+the render alone, from the context's own HIP events (HRT_CTX_TIMING), so that k_path_capture can be set against k_fused.
 
-    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal] [--variance]
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal] [--variance] [--capture]
 """
 from __future__ import annotations
 
@@ -42,13 +46,15 @@ def main():
     ap.add_argument("--scenes", default="c4,sample")
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--variance", action="store_true")
+    ap.add_argument("--capture", action="store_true")
     args = ap.parse_args()
     import torch
     hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
     io = importlib.import_module("nvidia-optix-ray-tracer_amd.io")
     w, h = args.width, args.height
     for name in args.scenes.split(","):
-        r = hrt.Renderer(0, 0)
+        flags = hrt.CTX_CAPTURE_PRIMARY if args.capture else 0
+        r = hrt.Renderer(0, flags)
         if name == "c4":
             r.load_scene(hrt.scenes.BASELINE_CONFIGS["C4"]())
             r.set_frame(w, h, hrt.scenes.SEED_SALT, aov=False)
@@ -66,7 +72,12 @@ def main():
         guides = r.denoise_guides()
         r.denoise_filter(r.color, guides, out=out)
         r.denoise(out=out)
-        res = {"scene": name, "width": w, "height": h,
+        def frame():
+            r.render(1, sync=False)
+            r.denoise(out=out)
+
+        res = {"scene": name, "width": w, "height": h, "capture": bool(args.capture),
+               "frame_ms": median_ms(torch, frame, args.reps),
                "render_1spp_ms": median_ms(torch, lambda: r.render(1, sync=False), args.reps),
                "guides_ms": median_ms(torch, r.denoise_guides, args.reps),
                "filter_ms": median_ms(torch, lambda: r.denoise_filter(r.color, guides, out=out), args.reps),
@@ -84,6 +95,13 @@ def main():
             r.denoise_filter_variance(r.color, guides, var, out=out, var_out=var_out)
             res["filter_variance_ms"] = median_ms(torch, lambda: r.denoise_filter_variance(r.color, guides, var, out=out, var_out=var_out), args.reps)
             res["filter_variance_per_pass_ms"] = res["filter_variance_ms"] / dp.iterations
+        r.set_flags(flags | hrt.CTX_TIMING)
+        r.reset_stats()
+        for _ in range(args.reps):
+            r.render(1)
+        st = r.stats()
+        res["path_kernel_ms"] = st.kernel_ms[hrt.K_PATHS] / max(1, st.kernel_launches[hrt.K_PATHS])
+        res["guide_passes"] = {"captured": st.guide_passes_captured, "traced": st.guide_passes_traced}
         print(json.dumps(res), flush=True)
         r.close()
 
