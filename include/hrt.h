@@ -250,8 +250,8 @@ int  hrt_denoise_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const 
  * last call's camera), blends the colour buffer into the bilinearly fetched history of the same instance and primitive at the expected
  * depth -- A = H + alpha (C - H), alpha = max(1 / L, alpha_min), L the history length, at most max_history -- and filters A as
  * hrt_denoise_launch filters the colour buffer.  A call without history (the first, after hrt_denoise_temporal_reset, or after a
- * change of TLAS handle, frame size or instance count) starts it afresh and returns hrt_denoise_launch's result bit for bit.
- * The history (about 100 B per pixel) lives in the context. */
+ * change of frame size, of instance count, or of TLAS handle that hrt_denoise_temporal_rebind has not announced) starts it afresh
+ * and returns hrt_denoise_launch's result bit for bit.  The history (about 100 B per pixel) lives in the context. */
 typedef struct HrtDenoiseTemporalParams {
     float    alpha_min;            /* smallest blend weight of the current frame, 0 < alpha_min <= 1                      (default 0.8)  */
     uint32_t max_history;          /* cap of the history length L, 1..65536                                                 (default 32)   */
@@ -265,8 +265,30 @@ int  hrt_denoise_temporal_default_params(HrtDenoiseTemporalParams *out);
 int  hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
                                  const HrtDenoiseParams *h_dparams, const HrtDenoiseTemporalParams *h_tparams,
                                  HrtFloat4 *d_out, void *stream);
-/* forget the history: the next hrt_denoise_temporal_launch (or hrt_denoise_variance_launch) starts afresh */
+/* forget the history (and a pending hrt_denoise_temporal_rebind): the next hrt_denoise_temporal_launch (or hrt_denoise_variance_launch)
+ * starts afresh */
 int  hrt_denoise_temporal_reset(HrtContext *ctx);
+/* Hand the history over to another TLAS of the same scene (DESIGN.md 3e "History across TLAS handles"; tests/denoise_handoff_ref.py
+ * restates it): the caller declares that next_tlas continues the scene of the TLAS the context's history was made for -- the next
+ * file's IAS of a Time-mode loop (RendererTime.cu:443-447), whose instance k is the body instance k was.
+ * h_prev_instance[i] (host memory, copied; n_instances entries) is the index, in the history's TLAS, of the body that is instance i of
+ * next_tlas, or HRT_NO_INSTANCE for a body that was not there.  NULL: the identity over the first min(n_prev, n_next) instances, every
+ * further instance new.  n_instances must be next_tlas's count; the two counts may differ; an index may appear more than once.  An
+ * instance whose BLAS handle differs from its predecessor's is treated as HRT_NO_INSTANCE (another geometry's primitive ids mean
+ * nothing), compared at this call: both TLASes must be alive.  hrt_mesh_render's program flow, which builds a new GAS per particle
+ * and file, would therefore carry nothing and does not call this; stable topology across different BLAS handles is not promised.
+ * The map is uploaded on `stream` (4 B per instance, kept by the context) and forms one pending link.  The next
+ * hrt_denoise_temporal_launch / hrt_denoise_variance_launch takes it if it is on next_tlas, in the history's mode and frame size, and
+ * the history is valid: a hit pixel of instance i with pi = map[i] reprojects by P' = X_prev(pi) (X_inv(i) P) and takes the taps
+ * that hold (pi, primitive); pi == HRT_NO_INSTANCE: A = C, L = 1, no motion.  After that call the history is next_tlas's and the link
+ * is gone.  hrt_tlas_update of next_tlas in between keeps the link (rebind, pose, update, launch is the normal order; instance
+ * indices persist through refits and rebuilds).  The link is dropped by hrt_denoise_temporal_reset, by a temporal or variance call on
+ * any other handle, frame size or mode (which starts afresh as ever), by hrt_tlas_destroy of next_tlas, and by another rebind, which
+ * replaces it.  With no valid history, or the history's TLAS destroyed, the call returns HRT_OK and links nothing.  HRT_ERR_INVALID:
+ * next_tlas unknown, n_instances not its count, an entry neither below the history's instance count nor HRT_NO_INSTANCE. */
+#define HRT_NO_INSTANCE 0xffffffffu
+int  hrt_denoise_temporal_rebind(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances,
+                                 void *stream);
 /* the last hrt_denoise_temporal_launch's intermediates, width * height each (a NULL pointer skips its buffer): the accumulated colour
  * A (float4, what the filter took), the history length L (float; 0 on background), and the reprojected position (x', y') in the
  * previous frame's pixel coordinates (float2; NaN where no projection was made).  HRT_ERR_STATE before the first call.  Enqueued only. */
@@ -281,7 +303,7 @@ int  hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float
  * variance_floor)), in place of the colour stop, and filters the variance as that of the weighted mean.  sigma_color is not used,
  * but is still refused (HRT_ERR_INVALID) unless it is > 0 and finite, like every other field of HrtDenoiseParams.
  * The history is the temporal mode's: a call whose predecessor was hrt_denoise_temporal_launch (or the reverse) starts afresh, as
- * after hrt_denoise_temporal_reset or a change of TLAS handle, frame size or instance count.  A call that starts afresh is NOT
+ * after hrt_denoise_temporal_reset or a change of frame size, instance count or (without hrt_denoise_temporal_rebind) TLAS handle.  A call that starts afresh is NOT
  * hrt_denoise_launch's result: it is the definition with L = 1 on every hit pixel, so the 5x5 variance applies everywhere. */
 typedef struct HrtDenoiseVarianceParams {
     float    sigma_luminance;      /* luminance edge stop in standard deviations, > 0                                       (default 4.0)  */
@@ -335,6 +357,9 @@ typedef struct HrtStats {
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
     uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
                                               at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
+    uint64_t denoise_history_rebinds;      /* temporal / variance denoiser calls since the context was created that began from a history handed over
+                                              from another TLAS (hrt_denoise_temporal_rebind).  Added ahead of the three counters below, which
+                                              tests/test_primary_capture_cpu.py pins as the structure's last: rebuild against this header */
     uint64_t primary_capture_launches;     /* path-kernel launches since the context was created that captured primary hits (HRT_CTX_CAPTURE_PRIMARY) */
     uint64_t guide_passes_traced;          /* denoiser guide passes since the context was created that traced their rays ...                          */
     uint64_t guide_passes_captured;        /* ... and that took the render launch's capture instead (they add nothing to `rays`)                      */

@@ -83,6 +83,7 @@ class Stats(C.Structure):
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
                 ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
                 ("sample_block_schedule", C.c_uint64 * 4),
+                ("denoise_history_rebinds", C.c_uint64),
                 ("primary_capture_launches", C.c_uint64), ("guide_passes_traced", C.c_uint64), ("guide_passes_captured", C.c_uint64)]
 
 
@@ -115,6 +116,7 @@ assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof
 
 PROGRAM_SPHERE_ROUGH, PROGRAM_SPHERE_METAL, PROGRAM_TRIANGLE_ROUGH, PROGRAM_TRIANGLE_METAL = range(4)
 CTX_TIMING, CTX_COUNT, CTX_FAST_TRACE, CTX_ASYNC_UPDATE, CTX_TWO_LEVEL, CTX_REUSE_PRIMARY, CTX_CAPTURE_PRIMARY = 1, 2, 4, 8, 16, 32, 64
+NO_INSTANCE = 0xFFFFFFFF        # HRT_NO_INSTANCE: hrt_denoise_temporal_rebind's "a body that was not there before"
 
 # every symbol include/hrt.h declares (checked by the CPU test-suite)
 EXPORTS = [
@@ -127,6 +129,7 @@ EXPORTS = [
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
+    "hrt_denoise_temporal_rebind",
     "hrt_denoise_variance_default_params", "hrt_denoise_filter_variance", "hrt_denoise_variance_launch", "hrt_debug_denoise_variance_state",
 ]
 
@@ -201,6 +204,7 @@ def load_library():
     lib.hrt_denoise_temporal_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
                                                 C.POINTER(DenoiseTemporalParams), C.c_void_p, C.c_void_p]
     lib.hrt_denoise_temporal_reset.argtypes = [C.c_void_p]
+    lib.hrt_denoise_temporal_rebind.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]
     lib.hrt_debug_denoise_temporal_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_denoise_variance_default_params.argtypes = [C.POINTER(DenoiseVarianceParams)]
     lib.hrt_denoise_filter_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,

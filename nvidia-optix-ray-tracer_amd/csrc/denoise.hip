@@ -16,6 +16,7 @@
 #include "device_types.h"
 #include "trav_common.h"
 #include "bvh8_geom.h"
+#include "denoise_temporal_body.h"
 
 #pragma clang fp contract(off)
 
@@ -27,8 +28,7 @@ constexpr int kDenoiseTile = 16;          // 16 x 16 pixels per workgroup: a tap
 __device__ __forceinline__ uint32_t half_bits(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }     // RNE
 __device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
 __device__ __forceinline__ bool guide_hit(float z) { return z > 0.0f && z < INFINITY; }
-// luminance of an sRGB-encoded colour (the variance-guided mode's edge stop and moments)
-__device__ __forceinline__ float luminance(const float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+// (luminance(), the variance-guided mode's edge stop and moments: denoise_temporal_body.h)
 
 // one HrtDenoiseGuide as 4 words: normal[0..2], albedo[0..2] (halves, little-endian), depth
 struct Guide { V3 n, a; float z; };
@@ -178,99 +178,13 @@ __global__ __launch_bounds__(kDenoiseTile * kDenoiseTile) void k_denoise_pass(De
     if constexpr (kVariance) a.var_dst[p] = filtered ? sv / (sw * sw) : vp;
 }
 
-// The temporal mode's reprojection and blend (DESIGN.md 3e "Temporal mode"; tests/denoise_temporal_ref.py), one thread per pixel.  A hit
-// pixel of instance i at distance t:
-//   P = o + d t;  P' = X_prev(i) (X_inv(i) P)   (xf_point: ((m0 x + m1 y) + m2 z) + m3 per row)
-//   r = P' - C';  s = dot(r, W') / dot(W', W')   (dot: (a.x b.x + a.y b.y) + a.z b.z);  no projection unless s > 0
-//   ndcx = (dot(r, U') / dot(U', U')) / (s aspect),  ndcy = (dot(r, V') / dot(V', V')) / s,  aspect = width / height
-//   x' = ((ndcx + 1) 0.5) width - 0.5,  y' = ((ndcy + 1) 0.5) height - 0.5,  z' = sqrt(dot(r, r))
-// then the bilinear taps (x0, y0) (x0+1, y0) (x0, y0+1) (x0+1, y0+1), x0 = floor(x'), fx = x' - x0, weights (1-fx)(1-fy), fx(1-fy),
-// (1-fx)fy, fx fy, each taken if it lies in the frame and holds the same (instance, primitive) at |z_prev - z'| <= tol z'.  With the sum
-// of the taken weights sw > 0: H = (sum w A_prev) / sw, Lh = (sum w L_prev) / sw (sums in tap order), L = min(Lh + 1, max_history),
-// alpha = max(1 / L, alpha_min), A = H + alpha (C - H) per colour channel, alpha the current pixel's; else A = C, L = 1.  Background:
-// A = C, L = 0.  (x', y') goes to `motion` (NaN without a projection).  The four taps' ids and depths, which decide whether a tap counts,
-// are loaded together from clamped addresses; A_prev, L_prev (and M_prev) are then read for the taps that count only.
-// kMoments (the variance-guided mode): M = (m1, m2), the moments of the luminance l(C), go through the same taps, weights and alpha:
-// with mc = (l(C), l(C) l(C)), M = Hm + alpha (mc - Hm), Hm = (sum w M_prev) / sw; without history M = mc; background M = (0, 0).
+// The temporal mode's reprojection and blend, one thread per pixel: denoise_temporal_body.h has the definition and the code.  These are
+// its unlinked instantiations; the linked one, for a history handed over from another TLAS, is denoise_link.hip's.
 template <bool kMoments>
 __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.width * a.height) return;
-    const float4 c = a.color[p];
-    const uint32_t inst = a.inst[p];
-    const float nan = __builtin_nanf("");
-    float4 acc = c;
-    float len = 0.0f;
-    float2 mom = make_float2(0.0f, 0.0f);
-    float2 mo = make_float2(nan, nan);
-    uint2 id = make_uint2(kMissPrim, 0u);
-    if (inst != kMissPrim) {
-        const float4 h = a.tuvp[p];
-        const uint32_t prim = __float_as_uint(h.w);
-        id = make_uint2(inst, prim);
-        len = 1.0f;
-        float lc = 0.0f;
-        if (kMoments) { lc = luminance(c); mom = make_float2(lc, lc * lc); }
-        if (a.has_history) {
-            const RayRec ray = a.rays[p];
-            const float hp[3] = {ray.o.x + ray.d.x * h.x, ray.o.y + ray.d.y * h.x, ray.o.z + ray.d.z * h.x};      // hit_point
-            float po[3], pw[3];
-            xf_point(a.inst_inv + 12 * (size_t)inst, hp, po);
-            xf_point(a.prev_xf + 12 * (size_t)inst, po, pw);
-            const V3 r = mk3(pw[0] - a.prev_center[0], pw[1] - a.prev_center[1], pw[2] - a.prev_center[2]);
-            const V3 U = mk3(a.prev_U[0], a.prev_U[1], a.prev_U[2]), V = mk3(a.prev_V[0], a.prev_V[1], a.prev_V[2]);
-            const V3 W = mk3(a.prev_W[0], a.prev_W[1], a.prev_W[2]);
-            const float s = dot3(r, W) / dot3(W, W);
-            if (s > 0.0f) {
-                const float fw = (float)a.width, fh = (float)a.height;
-                const float aspect = fw / fh;
-                const float ndcx = (dot3(r, U) / dot3(U, U)) / (s * aspect);
-                const float ndcy = (dot3(r, V) / dot3(V, V)) / s;
-                const float xp = ((ndcx + 1.0f) * 0.5f) * fw - 0.5f, yp = ((ndcy + 1.0f) * 0.5f) * fh - 0.5f;
-                const float zp = sqrtf(dot3(r, r));
-                mo = make_float2(xp, yp);
-                const float x0 = floorf(xp), y0 = floorf(yp);
-                const float fx = xp - x0, fy = yp - y0, gx = 1.0f - fx, gy = 1.0f - fy;
-                const float w[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
-                size_t q[4]; bool in[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float qx = x0 + (float)(k & 1), qy = y0 + (float)(k >> 1);
-                    in[k] = qx >= 0.0f && qx <= fw - 1.0f && qy >= 0.0f && qy <= fh - 1.0f;
-                    const float cx = fminf(fmaxf(qx, 0.0f), fw - 1.0f), cy = fminf(fmaxf(qy, 0.0f), fh - 1.0f);      // (NaN -> 0)
-                    q[k] = (size_t)(uint32_t)cy * a.width + (size_t)(uint32_t)cx;
-                }
-                uint2 qid[4]; float qz[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { qid[k] = a.prev_id[q[k]]; qz[k] = __uint_as_float(a.prev_guides[q[k]].w); }
-                float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const bool take = in[k] && qid[k].x == inst && qid[k].y == prim && fabsf(qz[k] - zp) <= a.depth_tolerance * zp;
-                    if (take) {
-                        const float4 ha = a.prev_accum[q[k]];
-                        const float hl = a.prev_length[q[k]];
-                        sw = sw + w[k];
-                        sr = sr + w[k] * ha.x; sg = sg + w[k] * ha.y; sb = sb + w[k] * ha.z;
-                        sl = sl + w[k] * hl;
-                        if (kMoments) { const float2 hm = a.prev_moments[q[k]]; sm1 = sm1 + w[k] * hm.x; sm2 = sm2 + w[k] * hm.y; }
-                    }
-                }
-                if (sw > 0.0f) {
-                    const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
-                    len = fminf(sl / sw + 1.0f, a.max_history);
-                    const float alpha = fmaxf(1.0f / len, a.alpha_min);
-                    acc = make_float4(hr + alpha * (c.x - hr), hg + alpha * (c.y - hg), hb + alpha * (c.z - hb), c.w);
-                    if (kMoments) { const float h1 = sm1 / sw, h2 = sm2 / sw; mom = make_float2(h1 + alpha * (mom.x - h1), h2 + alpha * (mom.y - h2)); }
-                }
-            }
-        }
-    }
-    a.accum[p] = acc;
-    a.length[p] = len;
-    a.id[p] = id;
-    a.motion[p] = mo;
-    if (kMoments) a.moments[p] = mom;
+    constexpr bool kLinked = false;
+    const uint32_t *prev_index = nullptr;
+#include "denoise_temporal_body.inc"
 }
 
 // The variance-guided mode's variance of the luminance, one thread per pixel (DESIGN.md 3e "Variance-guided mode";

@@ -271,6 +271,14 @@ struct DenoiseTemporalArgs {
     float alpha_min, max_history, depth_tolerance;
     const float2 *prev_moments; float2 *moments;             // the variance-guided mode's luminance moments (moments == NULL: not carried)
 };
+// ... of the first call after hrt_denoise_temporal_rebind (denoise_link.hip): the history is another TLAS's, prev_index[i] the index
+// instance i had there (kNoInstance: none).  The table rides behind the unlinked kernels' arguments, not among them: their kernel-argument
+// segment, and with it the offsets of the hidden arguments their code reads, stays what it was.
+constexpr uint32_t kNoInstance = 0xffffffffu;               // HRT_NO_INSTANCE
+struct DenoiseTemporalLinkedArgs {
+    DenoiseTemporalArgs t;
+    const uint32_t *prev_index;
+};
 // the variance-guided mode: the per-pixel variance from the moments
 struct DenoiseVarianceArgs {
     const float2 *moments; const float *length; const uint2 *id; float *variance;
@@ -279,6 +287,7 @@ struct DenoiseVarianceArgs {
 };
 void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s);
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
+void launch_denoise_temporal_linked(const DenoiseTemporalLinkedArgs &a, hipStream_t s);      // denoise_link.hip
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
 void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);
 void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s);

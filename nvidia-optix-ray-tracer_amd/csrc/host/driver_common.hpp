@@ -56,6 +56,21 @@ inline uint32_t denoiseContextFlags(DenoiseMode mode, int &argc, char **argv) {
     return capture ? HRT_CTX_CAPTURE_PRIMARY : 0u;
 }
 
+// Whether a frame loop that changes IAS (Time mode: one per particle file) hands the denoiser's history over to the next one
+// (rebindDenoiseHistory): under --denoise-temporal and --denoise-variance, unless --no-history-handoff (anywhere, taken out of argv)
+// keeps every file's first frame a fresh start.
+constexpr const char *kHandoffUsage = "[--no-history-handoff]";
+inline bool denoiseHistoryHandoff(DenoiseMode mode, int &argc, char **argv) {
+    bool handoff = mode == DenoiseMode::kTemporal || mode == DenoiseMode::kVariance;
+    int k = 1;
+    for (int i = 1; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--no-history-handoff") == 0) handoff = false;
+        else argv[k++] = argv[i];
+    }
+    argc = k;
+    return handoff;
+}
+
 // the denoiser's slot of a frame, in place: the colour buffer is not read again
 inline void denoiseFrame(DenoiseMode mode, HrtContext *ctx, const HrtGlobalParams &params, const HrtRayGenParams &raygen, HrtFloat4 *color) {
     switch (mode) {

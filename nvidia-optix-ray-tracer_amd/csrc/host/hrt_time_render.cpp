@@ -2,8 +2,10 @@
 // main() (src/Global/Main.cu:12-50) -> RendererTime::commitRendererData (src/Global/RendererTime.cu:160-290)
 // -> RendererTime::startRender's frame loop (:373-520) with the window and camera input left out; the denoiser (denoiseOutput, :501-510)
 // runs with --denoise.
-//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture]
+//   hrt_time_render <config.json> [exe_dir] [max_frames=all] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture] [--no-history-handoff]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
+// Under --denoise-temporal and --denoise-variance the denoiser's history follows the loop from one file's IAS to the next
+// (rebindDenoiseHistory; --no-history-handoff: every file's first frame starts afresh).
 // Per frame: hrt_pose_instances -> updateIAS -> launch + sync -> (denoiseOutput) -> convert to 8 bit; the last frame is written as PPM.
 #include "driver_common.hpp"
 
@@ -23,7 +25,8 @@ template <typename T> static T *toDevice(const T *host, size_t count) {
 int main(int argc, char **argv) {
     const DenoiseMode denoiseMode = parseDenoiseMode(argc, argv);
     const uint32_t denoiseFlags = denoiseContextFlags(denoiseMode, argc, argv);
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s\n", argv[0], kDenoiseUsage); return 2; }
+    const bool historyHandoff = denoiseHistoryHandoff(denoiseMode, argc, argv);
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s %s\n", argv[0], kDenoiseUsage, kHandoffUsage); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -150,6 +153,8 @@ int main(int argc, char **argv) {
         FileData &fd = perFile[f];
         timed(1, kMaterials, [&] { hrtCheckError(ctx, hrt_materials_set(ctx, fd.records.data(), (uint32_t)fd.records.size())); });
         const uint64_t next = f + 1 < series.n ? f + 1 : f;                                   // :443-447
+        // the loop moves to this file's IAS: particle k of it is the body particle k of the last file was posed towards, through the same GAS
+        if (historyHandoff && f > 0) rebindDenoiseHistory(ctx, std::get<0>(fd.ias), fd.instanceCount);
         const size_t frameCountThisFile = (size_t)(series.durations[f] * (float)(cfg.fps * cfg.render_speed_ratio));   // :427-428
         HrtPoseParams pose{};
         pose.duration = series.durations[f]; pose.frame_count = (uint32_t)frameCountThisFile;

@@ -198,4 +198,13 @@ inline void denoiseOutputVariance(HrtContext *ctx, const HrtGlobalParams &params
     hrtCheckError(ctx, hrt_denoise_variance_launch(ctx, &params, &raygen, denoiseParams, temporalParams, varianceParams, output, stream));
 }
 
+// The frame loop moves on to another IAS of the same scene (the next file's, RendererTime.cu:443-447): the history of the two calls
+// above goes with it (hrt_denoise_temporal_rebind, include/hrt.h).  previousInstance[i]: the index instance i of `next` had in the IAS
+// the history was made for, HRT_NO_INSTANCE for a new body; NULL: the same index.  Call it before the first denoiseOutputTemporal /
+// denoiseOutputVariance on `next`, before or after that frame's pose step and updateIAS.
+inline void rebindDenoiseHistory(HrtContext *ctx, HrtTraversable next, size_t instanceCount, const uint32_t *previousInstance = nullptr,
+                                 hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_denoise_temporal_rebind(ctx, next, previousInstance, (uint32_t)instanceCount, stream));
+}
+
 }  // namespace project

@@ -906,6 +906,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     for (int i = 0; i < 4; ++i) out->sample_block_schedule[i] = ctx->last_schedule[i];
     out->primary_capture_launches = ctx->primary_capture_launches;
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
+    out->denoise_history_rebinds = ctx->denoise_history_rebinds;
     return HRT_OK;
 }
 

@@ -25,6 +25,7 @@ void free_denoise_history(HrtContext *ctx) {
     }
     if (h.motion) (void)hipFree(h.motion);
     if (h.variance) (void)hipFree(h.variance);
+    if (h.link) (void)hipFree(h.link);
     h = DenoiseHistory{};
 }
 
@@ -186,7 +187,9 @@ int temporal_constants(HrtContext *ctx, const HrtDenoiseTemporalParams *h_tparam
     return HRT_OK;
 }
 
-// the history's arrays for n pixels and n_inst instances; a new size forgets the history.  moments: the variance-guided mode's arrays too
+// the history's arrays for n pixels, and room for n_inst instances in the object -> world table of the set the next call writes; a new
+// frame size forgets the history (and a pending link).  The last call's set keeps its table, sized for its own instance count: a linked
+// call reads it through the link.  moments: the variance-guided mode's arrays too
 int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst, bool moments) {
     DenoiseHistory &h = ctx->denoise_history;
     if (h.pixels != n) {
@@ -206,14 +209,12 @@ int ensure_history(HrtContext *ctx, uint32_t n, uint32_t n_inst, bool moments) {
         HIP_TRY(ctx, hipMalloc((void **)&h.variance, sizeof(float) * (size_t)n));
     }
     const uint32_t need = std::max(n_inst, 1u);
-    if (need > h.xf_capacity) {
-        h.valid = false;
-        for (DenoiseHistorySet &s : h.set) {
-            if (s.xf) (void)hipFree(s.xf);
-            s.xf = nullptr;
-            HIP_TRY(ctx, hipMalloc((void **)&s.xf, sizeof(float) * 12 * (size_t)need));
-        }
-        h.xf_capacity = need;
+    DenoiseHistorySet &next = h.set[h.cur ^ 1u];
+    if (need > next.xf_capacity) {
+        if (next.xf) (void)hipFree(next.xf);      // (hipFree waits for the device: the call that read this table two calls ago is done)
+        next.xf = nullptr; next.xf_capacity = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&next.xf, sizeof(float) * 12 * (size_t)need));
+        next.xf_capacity = need;
     }
     return HRT_OK;
 }
@@ -230,7 +231,11 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     if (rc == HRT_OK) rc = ensure_history(ctx, n, t->n_instances, moments);
     if (rc != HRT_OK) return rc;
     DenoiseHistory &h = ctx->denoise_history;
-    const bool has_history = h.valid && h.mode == mode && h.tlas == h_params->handle && h.width == width && h.height == height && h.n_instances == t->n_instances;
+    const bool same_frames = h.valid && h.mode == mode && h.width == width && h.height == height;
+    // a pending link (hrt_denoise_temporal_rebind) to this call's TLAS: the history is blended through it.  Whatever this call is, the
+    // link ends with it (below)
+    const bool linked = same_frames && h.link_pending && h.link_tlas == h_params->handle && h.link_n == t->n_instances;
+    const bool has_history = linked || (same_frames && h.tlas == h_params->handle && h.n_instances == t->n_instances);
     const DenoiseHistorySet &prev = h.set[h.cur];
     DenoiseHistorySet &next = h.set[h.cur ^ 1u];
     rc = run_guides(ctx, h_params, h_raygen, next.guides, s);
@@ -245,11 +250,15 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     std::memcpy(ta.prev_center, prev.center, 12); std::memcpy(ta.prev_U, prev.U, 12); std::memcpy(ta.prev_V, prev.V, 12); std::memcpy(ta.prev_W, prev.W, 12);
     ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
     if (moments) { ta.prev_moments = prev.moments; ta.moments = next.moments; }
-    launch_denoise_temporal(ta, s);
+    if (linked) {
+        launch_denoise_temporal_linked(DenoiseTemporalLinkedArgs{ta, h.link}, s);
+        ctx->denoise_history_rebinds++;
+    } else launch_denoise_temporal(ta, s);
     HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->dev.d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
     std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
     std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
     h.cur ^= 1u;
+    h.link_pending = false;
     h.valid = false;                  // (until the caller has enqueued the filter as well)
     h.mode = mode;
     h.called = true;
@@ -353,6 +362,48 @@ int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params
 int hrt_denoise_temporal_reset(HrtContext *ctx) {
     if (!ctx) return HRT_ERR_INVALID;
     ctx->denoise_history.valid = false;
+    ctx->denoise_history.link_pending = false;
+    return HRT_OK;
+}
+
+int hrt_denoise_temporal_rebind(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    DenoiseHistory &h = ctx->denoise_history;
+    std::vector<uint32_t> link;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const auto next = ctx->tlas.find(next_tlas);
+        if (next == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: 0x%llx is not a TLAS", (unsigned long long)next_tlas);
+        const Tlas &tn = *next->second;
+        if (n_instances != tn.n_instances)
+            return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: n_instances %u is not the TLAS's %u", n_instances, tn.n_instances);
+        const auto prev = ctx->tlas.find(h.tlas);
+        if (!h.valid || prev == ctx->tlas.end()) {      // nothing to hand over: the next call starts afresh, as without this one
+            h.link_pending = false;
+            return HRT_OK;
+        }
+        const Tlas &tp = *prev->second;
+        link.assign(std::max(n_instances, 1u), HRT_NO_INSTANCE);
+        for (uint32_t i = 0; i < n_instances; ++i) {
+            uint32_t pi = h_prev_instance ? h_prev_instance[i] : (i < tp.n_instances ? i : HRT_NO_INSTANCE);
+            if (pi != HRT_NO_INSTANCE && pi >= tp.n_instances)
+                return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: h_prev_instance[%u] = %u, the history's TLAS has %u instances", i, pi, tp.n_instances);
+            // (another geometry's primitive ids mean nothing: such a body starts afresh)
+            if (pi != HRT_NO_INSTANCE && tn.sig_handle[i] != tp.sig_handle[pi]) pi = HRT_NO_INSTANCE;
+            link[i] = pi;
+        }
+    }
+    if (link.size() > h.link_capacity) {
+        if (h.link) (void)hipFree(h.link);
+        h.link = nullptr; h.link_capacity = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&h.link, sizeof(uint32_t) * link.size()));
+        h.link_capacity = (uint32_t)link.size();
+    }
+    h.link_pending = false;                    // (replaced: a failed upload leaves none)
+    h.h_link.swap(link);
+    HIP_TRY(ctx, hipMemcpyAsync(h.link, h.h_link.data(), sizeof(uint32_t) * h.h_link.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+    h.link_pending = true; h.link_tlas = next_tlas; h.link_n = n_instances;
     return HRT_OK;
 }
 

@@ -169,11 +169,12 @@ struct PrimaryCapture {
 struct DenoiseHistorySet {
     float4 *accum = nullptr; float *length = nullptr; uint4 *guides = nullptr; uint2 *id = nullptr;
     float2 *moments = nullptr;              // the variance-guided mode's (m1, m2), allocated by its first call
-    float *xf = nullptr;
+    float *xf = nullptr; uint32_t xf_capacity = 0;      // instances the table holds: each set's own, so that a call on a TLAS of another
+                                                        // instance count (a linked one) grows the set it writes and keeps the last call's
     float center[3], U[3], V[3], W[3];
 };
 struct DenoiseHistory {
-    uint32_t pixels = 0, xf_capacity = 0;   // pixels of every per-pixel array, instances the xf tables hold
+    uint32_t pixels = 0;                    // pixels of every per-pixel array
     DenoiseHistorySet set[2];
     float2 *motion = nullptr;               // the last call's (x', y')
     uint32_t cur = 0;                       // set[cur] is the last call's; a call writes set[cur ^ 1], then flips cur
@@ -185,6 +186,12 @@ struct DenoiseHistory {
     bool variance_called = false;           // hrt_debug_denoise_variance_state: set[variance_set].moments and `variance` are a call's
     uint32_t variance_set = 0;
     uint64_t tlas = 0; uint32_t width = 0, height = 0, n_instances = 0;     // what it was made for
+    // hrt_denoise_temporal_rebind: one pending link from the history's TLAS to link_tlas.  link[i], i < link_n, is the index instance i
+    // of link_tlas had in the history's TLAS, or HRT_NO_INSTANCE.  The next temporal / variance call takes it if it is on link_tlas (and
+    // in the history's mode and frame size); that call, any other one, a reset, hrt_tlas_destroy of link_tlas or another rebind ends it.
+    uint32_t *link = nullptr; uint32_t link_capacity = 0;      // device table, grown on demand
+    std::vector<uint32_t> h_link;                               // its staging
+    bool link_pending = false; uint64_t link_tlas = 0; uint32_t link_n = 0;
 };
 
 struct TimedSpan { int kind; hipEvent_t a, b; };
@@ -261,6 +268,7 @@ struct HrtContext {
     hrt::PrimaryCapture capture;
     uint64_t primary_capture_launches = 0;      // path-kernel launches that ran k_path_capture
     uint64_t guide_passes_traced = 0, guide_passes_captured = 0;      // the denoiser's guide passes: traced / served from the capture
+    uint64_t denoise_history_rebinds = 0;       // temporal / variance calls that began from a linked history (hrt_denoise_temporal_rebind)
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)
     uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks

@@ -101,6 +101,7 @@ class Renderer:
         self._blas = []
         self._n_inst = None
         self.tlas = None
+        self._tlases = {}           # handle -> (host instance array, device instance array, count, SBT records): load_scene's and build_tlas's
         self.states = None
         self.width = self.height = 0
         self.color = self.albedo = self.normal = self.linear = None
@@ -174,6 +175,9 @@ class Renderer:
         self._d_inst = d_inst
         self._h_inst = h_inst
         self._n_inst = n
+        self._n_scene = n
+        self._scene_inst, self._scene_rec = bytes(h_inst), bytes(h_rec)      # the loaded scene's instances and records: what build_tlas draws from
+        self._tlases[self.tlas] = (h_inst, d_inst, n, h_rec)
         self._check(lib.hrt_materials_set(self.ctx, h_rec, n), "hrt_materials_set")
         bg = scene.get("background", np.array([0.7, 0.8, 0.9], dtype=np.float32))
         miss = MissParams(Float3(float(bg[0]), float(bg[1]), float(bg[2])))
@@ -181,6 +185,49 @@ class Renderer:
         cam = scene["camera"]
         self.set_camera(cam["center"], cam["target"], cam["up"], cam.get("opengl", True))
         return self
+
+    def build_tlas(self, order=None, transforms=None):
+        """Another TLAS over the loaded scene's BLASes: instance j is the scene's instance ``order[j]`` (None: all of them in order; a
+        subset, a permutation, repeats) with ``transforms[j]`` (12 floats; None: the scene's), sbtOffset j and the material record of
+        its source.  Returns the handle; the renderer stays on the TLAS it was on (use_tlas switches)."""
+        from . import Instance, SbtRecord
+        n_scene = self._n_scene
+        order = list(range(n_scene)) if order is None else [int(k) for k in order]
+        n = len(order)
+        src_inst = (Instance * max(n_scene, 1)).from_buffer_copy(self._scene_inst)
+        src_rec = (SbtRecord * max(n_scene, 1)).from_buffer_copy(self._scene_rec)
+        h_inst = (Instance * max(n, 1))()
+        h_rec = (SbtRecord * max(n, 1))()
+        for j, k in enumerate(order):
+            if not 0 <= k < n_scene:
+                raise self._err(f"build_tlas: the scene has no instance {k}")
+            C.memmove(C.byref(h_inst[j]), C.byref(src_inst[k]), C.sizeof(Instance))
+            C.memmove(C.byref(h_rec[j]), C.byref(src_rec[k]), C.sizeof(SbtRecord))
+            h_inst[j].sbtOffset = j
+            if transforms is not None:
+                for c in range(12):
+                    h_inst[j].transform[c] = float(transforms[j][c])
+        d_inst = self._dev(np.frombuffer(bytes(h_inst), dtype=np.uint8).copy())
+        tl = C.c_uint64()
+        self._check(self.lib.hrt_tlas_build(self.ctx, d_inst.data_ptr(), n, self._stream(), C.byref(tl)), "hrt_tlas_build")
+        self._tlases[tl.value] = (h_inst, d_inst, n, h_rec)
+        return tl.value
+
+    def use_tlas(self, tlas):
+        """Render, update and denoise on ``tlas`` (load_scene's or one of build_tlas's) from now on: its instance array and count, and
+        its material records through hrt_materials_set.  The denoiser's history does not follow by itself: denoise_temporal_rebind."""
+        if tlas not in self._tlases:
+            raise self._err(f"use_tlas: 0x{tlas:x} is not a TLAS of this renderer")
+        self._h_inst, self._d_inst, self._n_inst, h_rec = self._tlases[tlas]
+        self.tlas = tlas
+        self._check(self.lib.hrt_materials_set(self.ctx, h_rec, self._n_inst), "hrt_materials_set")
+
+    def destroy_tlas(self, tlas):
+        """hrt_tlas_destroy of one of build_tlas's trees that the renderer is not on."""
+        if tlas == self.tlas or tlas not in self._tlases:
+            raise self._err(f"destroy_tlas: 0x{tlas:x} is in use or not a TLAS of this renderer")
+        self._check(self.lib.hrt_tlas_destroy(self.ctx, tlas), "hrt_tlas_destroy")
+        del self._tlases[tlas]
 
     def update_instances(self, transforms):
         """Per-frame instance update + updateIAS (src/Global/RendererMesh.cu:379-401)."""
@@ -362,6 +409,17 @@ class Renderer:
 
     def denoise_temporal_reset(self):
         self._check(self.lib.hrt_denoise_temporal_reset(self.ctx), "hrt_denoise_temporal_reset")
+
+    def denoise_temporal_rebind(self, tlas, prev_instance=None):
+        """hrt_denoise_temporal_rebind: the next denoise_temporal / denoise_variance on ``tlas`` continues the history made on the TLAS
+        the last one ran on.  prev_instance[i]: the index instance i of ``tlas`` had there, NO_INSTANCE for a new body; None: the
+        identity over the instances both have.  Call before use_tlas / the poses of the next frame or after: the order is free."""
+        n = self._tlases[tlas][2] if tlas in self._tlases else 0
+        arr = None
+        if prev_instance is not None:
+            arr = (C.c_uint32 * max(len(prev_instance), 1))(*[int(x) for x in prev_instance])
+            n = len(prev_instance)
+        self._check(self.lib.hrt_denoise_temporal_rebind(self.ctx, tlas, arr, n, self._stream()), "hrt_denoise_temporal_rebind")
 
     def denoise_temporal_state(self):
         """The last denoise_temporal's intermediates: (accumulated colour (H, W, 4), history length (H, W), reprojected position

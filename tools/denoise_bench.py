@@ -6,12 +6,15 @@ split is k_fused (render and guide rays), k_denoise_rays, k_denoise_guides, k_de
 --temporal adds hrt_denoise_temporal_launch (the frame repeated, so that every call after the first blends with a history): its own
 kernel is k_denoise_temporal.  --variance adds hrt_denoise_variance_launch in the same way (k_denoise_temporal<true>,
 k_denoise_variance, k_denoise_pass<3, true>: the same pass kernel's variance form) and hrt_denoise_filter_variance over the frame's guides and a constant variance.
+--handoff (with --temporal) adds the same call begun from a history handed over from another TLAS every time (hrt_denoise_temporal_rebind
+between two identical trees, alternating): its kernel is k_denoise_temporal_linked, to be set against k_denoise_temporal in the same
+trace; the whole-call figure also pays hrt_materials_set and the material tables of the other tree.
 --capture sets HRT_CTX_CAPTURE_PRIMARY: the render launch runs k_path_capture and the guide pass of every denoise call takes its
 primary hits instead of tracing (guides_ms is then the pass without its traversal).  With or without it, frame_ms is what the switch is
 about -- a 1-spp render and hrt_denoise_launch enqueued back to back, one synchronisation --, and path_kernel_ms the path kernel of
 the render alone, from the context's own HIP events (HRT_CTX_TIMING), so that k_path_capture can be set against k_fused.
 
-    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal] [--variance] [--capture]
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal [--handoff]] [--variance] [--capture]
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--scenes", default="c4,sample")
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--variance", action="store_true")
+    ap.add_argument("--handoff", action="store_true")
     ap.add_argument("--capture", action="store_true")
     args = ap.parse_args()
     import torch
@@ -86,6 +90,18 @@ def main():
         if args.temporal:
             r.denoise_temporal(out=out)
             res["denoise_temporal_ms"] = median_ms(torch, lambda: r.denoise_temporal(out=out), args.reps)
+            if args.handoff:
+                trees = [r.tlas, r.build_tlas(None, r.instance_transforms())]
+
+                def linked():
+                    trees.reverse()
+                    r.denoise_temporal_rebind(trees[0])
+                    r.use_tlas(trees[0])
+                    r.denoise_temporal(out=out)
+
+                linked()
+                res["denoise_temporal_linked_ms"] = median_ms(torch, linked, args.reps)
+                res["history_rebinds"] = r.stats().denoise_history_rebinds
         if args.variance:
             var = torch.full((h, w), 1e-3, dtype=torch.float32, device=r.device)
             var_out = torch.empty_like(var)
