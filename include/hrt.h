@@ -178,8 +178,9 @@ int  hrt_rng_free(HrtContext *ctx, HrtRngState *d_states, void *stream);
  * tile are left untouched.  The call returns after the work has been ENQUEUED on stream;
  * hrt_sync (or any stream sync) completes it.  (Renders of >= 16 samples on small tiles synchronise
  * the stream once in the middle: a probe launch orders the pixel slices by cost for the rest.)
- * With spp > 1 the path kernels start a pixel's repeat primary rays bounded at the hit its previous sample found
- * (HRT_SEED_PRIMARY, on by default): the same image, the same ray counts, fewer node steps. */
+ * With spp > 1 the path kernels start a pixel's repeat primary rays bounded at the hit its previous sample found,
+ * from above and, in a window under it, from below (HRT_SEED_PRIMARY, level 2 by default): the same image, the same
+ * ray counts, fewer node steps. */
 int  hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params,
                        const HrtRayGenParams *h_raygen, uint32_t spp,
                        const HrtTile *tile, void *stream);

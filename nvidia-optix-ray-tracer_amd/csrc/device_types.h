@@ -126,7 +126,7 @@ struct TraverseArgs {
     int leaf_quorum;               // k_fused: ... and fewer than this many lanes have nothing but leaf work (they wait; >= 1)
     int leaf_hold;                 // k_fused: a lane with this many leaf groups queued takes no new node until some are tested (2 .. 4 = the leaf stack's depth)
     int tail_regen;                // k_fused, tile used up: regenerate once this many finished rays wait (>= 1)
-    int seed_primary;              // k_fused / k_path_blocks: 1 = a pixel's repeat primary rays start bounded at its known hit (path_lane.h: px_seed)
+    int seed_primary;              // k_fused / k_path_blocks: a pixel's repeat primary rays start bounded at its known hit -- 1 = from above, 2 = and in a window under it (fused_body.h: s_seed, kSeedWindow)
     PathArgs path;                 // FUSED only
 };
 

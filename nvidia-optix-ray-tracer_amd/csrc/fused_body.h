@@ -131,6 +131,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
     static_assert(!CAPTURE || (!REUSE && !BLOCKS), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
+    // kSeed: the hit distance the lane's pixel last found along its primary ray (path_lane.h), read once per sample: a word of LDS, so that
+    // its register is the ray's TravState::tlo.  (One-level kernels: 9984 + 256 = 10240 bytes, still 16 waves per CU.)
+    __shared__ float s_seed[kTraverseBlock];
     __shared__ uint2 s_nodes[kNodeStackLds][kTraverseBlock];     // sibling groups: one per tree level (hrt_api.cpp sends deeper trees to k_traverse)
     __shared__ uint2 s_leaves[kLeafStackLds][kTraverseBlock];    // leaf groups
     // tail splitting: one mailbox per lane that owns a split ray (indexed by its home lane) collects the pieces' hits
@@ -157,7 +160,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     if constexpr (INSTANCED) { I.park_idx = s_park_idx; I.park_idy = s_park_idy; I.park_idz = s_park_idz; I.park_oct = s_park_oct; }
 
     LeanLane L;
-    lean_idle(L, tmax_ray);
+    lean_idle(L, tmax_ray, tmin);
     LaneFlags F;                            // alive / waiting / any / shared: trav_loop.h
     F.home = tx;
     bool exhausted = false;                 // wave-uniform: no pixels left to start
@@ -207,9 +210,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE>(P, chain, a, o, d, bt, bu, bv, bprim, binst);
+                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
             }
-            exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B);
+            exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx);
             stats.drained(exhausted);
             if (st.want_primary) {
                 bool from_cache = false;
@@ -225,9 +228,19 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             bool any_hit = false;
             if (st.launch) {
                 any_hit = path_count_ray(P);
-                // a primary ray of a pixel the lane already holds starts bounded at the hit its previous sample found (PathLane::px_seed; tmax after
-                // path_take): counted and walked from the root like any other, the primitive test keeps the launch's tmax
-                lean_start(L, st.ro, st.rd, kSeed && st.want_primary ? P.px_seed : tmax_ray);
+                // a primary ray of a pixel the lane already holds starts bounded at the hit its previous sample found (s_seed; tmax after
+                // path_take): counted and walked from the root like any other, the primitive test keeps the launch's tmin and tmax.  At level
+                // 2 it is bounded from below as well: the same ray has found nothing before that hit, so the node step's interval begins a
+                // window (trav_common.h: kSeedWindow) below it.  Every other ray -- a bounce, a first sample, after a miss (the seed says
+                // tmax), a caller's ray -- begins at the launch's tmin.
+                float hi = tmax_ray, lo = tmin;
+                if constexpr (kSeed) {
+                    if (st.want_primary) {
+                        hi = s_seed[tx];
+                        if (a.seed_primary >= 2 && hi < tmax_ray) lo = seed_window_lo(st.rd, hi, tmin);
+                    }
+                }
+                lean_start(L, st.ro, st.rd, hi, lo);
                 if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
             }
             // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
@@ -275,10 +288,10 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         //      and the drained phase's exit rule runs once the tile is used up ----
         if (exhausted) {
             stats.tail_begin();
-            traverse_to_regen<HAS_SPHERES, INSTANCED, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
             stats.tail_end();
         }
-        else traverse_to_regen<HAS_SPHERES, INSTANCED, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
     const TraverseArgs &k = kernarg_traverse_args();          // (the counters' addresses need not live in registers until here)
     stats.report(k.path.rays_closest, tx);

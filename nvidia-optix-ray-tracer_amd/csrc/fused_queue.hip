@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
     const Mailboxes mb{s_mb_t, s_mb_u, s_mb_v, s_mb_prim, s_mb_inst, s_mb_pending, s_pair};
 
     LeanLane L;
-    lean_idle(L, tmax_ray);
+    lean_idle(L, tmax_ray, tmin);
     LaneFlags F;                            // alive / waiting (the hit record is written at the next refill) / any / shared: trav_loop.h
     F.home = tx;
     NoInstLane I;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
                 const QueuePos qp = queue_pos(q_index, n_a);
                 const RayRec r = queue_ray(a, qp);
                 any_hit = queue_any_hit(a, qp);
-                lean_start(L, mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z), tmax_ray);
+                lean_start(L, mk3(r.o.x, r.o.y, r.o.z), mk3(r.d.x, r.d.y, r.d.z), tmax_ray, tmin);      // (the loop culls with the uniform tmin here: no windows)
             }
             const uint64_t launched = __ballot(launch);
             F.alive |= launched; F.any = (F.any & ~launched) | __ballot(any_hit);

@@ -264,7 +264,7 @@ static TraverseArgs traverse_args(const HrtContext *ctx, const Tlas &t, float tm
     ta.nodes = t.dev.d_nodes; ta.prims = t.dev.d_prims; ta.node_stride = t.node_stride; ta.prim_stride = t.prim_stride;
     ta.inst_inv = t.dev.d_inst_inv; ta.inst_identity = t.dev.d_inst_identity;
     ta.tmin = tmin; ta.tmax = tmax;
-    ta.leaf_quorum = ctx->leaf_quorum; ta.tail_regen = ctx->fused_tail_regen; ta.seed_primary = ctx->seed_primary ? 1 : 0;
+    ta.leaf_quorum = ctx->leaf_quorum; ta.tail_regen = ctx->fused_tail_regen; ta.seed_primary = ctx->seed_primary;
     ta.tail_split = t.two_level ? 0 : ctx->tail_split;      // (the pieces of a split ray would have to carry the instance they are in)
     return ta;
 }

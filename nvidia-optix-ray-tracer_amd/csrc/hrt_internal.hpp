@@ -254,7 +254,7 @@ struct HrtContext {
     int fused_tail_regen = 12;                  // k_fused, tile used up: finished rays that wait before a regeneration (HRT_TAIL_REGEN; 1/8 of C4: 142 ms with 1, 129 with 8..16)
     bool refill_auto = true;                    // HRT_REFILL_THRESHOLD not set: two-level launches regenerate at 12 waiting lanes (profiles/r04_leaf_hold.txt)
     int leaf_hold = 0;                          // HRT_LEAF_HOLD: leaf groups a lane may queue before its node work waits for primitive tests; 0 = by scene (render_fused)
-    bool seed_primary = true;                   // HRT_SEED_PRIMARY: a pixel's repeat primary rays start with the culling bound at the hit its previous sample found (path_lane.h)
+    int seed_primary = 2;                       // HRT_SEED_PRIMARY: a pixel's repeat primary rays start with the culling bound at the hit its previous sample found (path_lane.h): 1 = from above, 2 = from below too (a window under the hit), 0 = off
     int leaf_quorum = 1;                        // k_fused: lanes with nothing but leaf work wait until this many of them have gathered (HRT_LEAF_QUORUM)
     int tail_split = 1;
     int node_stride = 80, prim_stride = 64;     // bytes between records in HBM (80/48 packed; 128/64 = one cache line each)

@@ -25,11 +25,12 @@ struct PathLane {
     float px_pdx = 0.0f, px_pdy = 0.0f, px_pdz = 1.0f;      // the pixel's primary direction: the same for every sample (no jitter, Shader.cu:249-261)
     Xorwow px_rng{};
     uint32_t px_rays_closest = 0u, px_rays_any = 0u;
-    // the culling bound the pixel's next primary ray may start with: the hit distance its last one found, exactly as found, or tmax (none:
-    // a miss, a pixel just taken, HRT_SEED_PRIMARY=0).  Every sample's primary ray is the same ray, so it ends in the same hit again: a
-    // complete closest-hit walk from the root that never enters what lies behind that hit.  Reset by path_take, so it
-    // never outlives the lane's hold on the pixel; kept by the kernels that seed (SEED: fused_body.h) only.
-    float px_seed = kFloatInfinity;
+    // (The seed -- the culling bound the pixel's next primary ray may start with: the hit distance its last one found, exactly as found, or
+    // tmax (none: a miss, a pixel just taken, HRT_SEED_PRIMARY=0) -- is NOT here: it is read once per sample, so it waits in the lane's
+    // word of the wave's LDS (`seed` of path_finish / path_take; fused_body.h: s_seed) and the register it had is the traversal's
+    // TravState::tlo.  Every sample's primary ray is the same ray, so it ends in the same hit again: a complete closest-hit walk from the
+    // root that never enters what lies behind that hit nor, with the window, what ends before it.  Reset by
+    // path_take, so it never outlives the lane's hold on the pixel; kept by the kernels that seed (SEED: fused_body.h) only.)
 };
 
 // what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
@@ -86,15 +87,16 @@ __device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, b
 // sum written), wants the next sample's primary ray, or launches the bounce.
 // REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
 // BLOCKS: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
-// SEED: the kernel starts repeat primary rays at PathLane::px_seed, so a finished primary ray records it (and path_take resets it).
+// SEED: the kernel starts repeat primary rays at the lane's seed (`seed`: its word in LDS), so a finished primary ray records it (and path_take resets it).
 // CAPTURE (k_path_capture, fused_capture.hip; HRT_CTX_CAPTURE_PRIMARY): the primary ray of the first sample the launch takes of a pixel
 // leaves its hit record in frame order, in hrt_trace_rays' form (a miss: tmax, kMissPrim), where the denoiser's guide pass and
 // hrt_primary_hits_get find it.  PathArgs::trace_tuvp / trace_inst are free in a render (trace_rays == NULL) and carry the two arrays.
 template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false>
-__device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst) {
+__device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
+                                            [[maybe_unused]] float *seed = nullptr) {
     PathStep st;
     const bool miss = bprim == kMissPrim;
-    if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) P.px_seed = bt; }      // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
+    if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
     if constexpr (CAPTURE) {
         if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // (the primary-hit cache's condition, fused_body.h)
             a.path.trace_tuvp[P.px_tid] = make_float4(bt, bu, bv, __uint_as_float(bprim));
@@ -160,7 +162,8 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
 template <bool BLOCKS = false, bool SEED = false>
 __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
-                                          bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr) {
+                                          bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
+                                          [[maybe_unused]] float *seed = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
         bool by_blocks = false;
@@ -208,7 +211,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                 const uint32_t j = a.path.first_pixel + mine;
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
-                if constexpr (SEED) P.px_seed = a.tmax;
+                if constexpr (SEED) *seed = a.tmax;
                 if (!a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;
                     const uint32_t ix = j - row * a.path.width;

@@ -241,6 +241,7 @@ struct TravState {
     float ox, oy, oz, dx, dy, dz;
     float idx, idy, idz;
     float bt, bu, bv;
+    float tlo;                    // the path kernels' node step culls below it (per lane: the launch's tmin, or a repeat primary ray's window -- kSeedWindow)
     uint32_t bprim, binst;
     uint32_t oct_inv4;
     uint2 cur;
@@ -252,9 +253,10 @@ struct TravState {
 // 1 / d for the slab test.  The counting build divides exactly, so that its node / primitive counts equal the CPU walk of
 // the same bytes (tests); the production build takes v_rcp_f32 (1 ULP, one instruction instead of the ~10 of the IEEE
 // sequence, three times per ray): the slab test only culls, and its boxes are padded by far more than an ULP.
+constexpr float kRcpDirFloor = 1e-20f;      // a direction component below it counts as it
 template <bool EXACT>
 __device__ __forceinline__ float safe_rcp_dir(float d) {
-    const float lim = 1e-20f;
+    const float lim = kRcpDirFloor;
     // (the sign is the one the slab test's near / far choice and the octant use, `d < 0`: a component of -0.0 -- a ray mirrored by an axis-aligned
     // wall -- counts as positive there, and with copysignf here its reciprocal was negative: near and far swapped, every box culled, the ray left
     // a closed room.  Found in round 4 by tools/stress_modes.py: one pixel of a Cornell box; tests/test_gpu_parity.py has the rays.)
@@ -430,6 +432,19 @@ constexpr float kSlabSpanSlack = 1.0f - 0x1p-20f, kSlabSpanFloor = 0x1p-36f;
 //     (safe_rcp_dir's 1e-20 is the same approximation with an absolute bound: over a scene of extent S the ray it stands for leaves the
 //     true one by 2^-40 * 12 S, against a padding of 4e-6 S).  With k <= 2^36, |idx| <= 1e20 and |p - o| <= 2^25 every product is finite.
 constexpr float kSlabReach = 0x1p64f, kSlabRcpRatio = 0x1p40f;
+// The interval's lower end is the LANE's (TravState::tlo; the `tmin` operand of node_slab_test): the launch's tmin for every ray but a pixel's
+// repeat primary ray, which has a known hit at t (HRT_SEED_PRIMARY=2; fused_body.h) and starts with bt = t and tlo = t (1 - kSeedWindow):
+// the identical ray has proved that nothing lies before t, so a box whose far plane is before t need not be opened.  The window is far
+// wider than everything that rounds -- the slack 2^-20, the ulp of v_rcp_f32, half an ulp of t in the offset's FMA -- so a box that
+// holds the hit keeps F' > 0 (DESIGN.md 4.1 has the argument); below 2^-10 the CPU walks gain nothing more.
+// seed_window_lo: the lower end for a ray (direction d) whose known hit is at `seed`.  The argument wants the slab test's distances to be the
+// ray's own, which they are not when ALL of d is below safe_rcp_dir's floor (a direction of length 1e-30: every plane then seems 1e10 times
+// nearer than it is -- harmless for a bound from above, not for one from below): such a ray keeps tmin.  A camera ray is normalised.
+constexpr float kSeedWindow = 0x1p-10f;
+__device__ __forceinline__ float seed_window_lo(V3 d, float seed, float tmin) {
+    const bool plain = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) >= kRcpDirFloor;
+    return plain ? fmaxf(tmin, seed * (1.0f - kSeedWindow)) : tmin;
+}
 // caps idx / idy / idz and folds the slack into them; returns the smallest of their magnitudes before that, 1 / max |d_c|
 __device__ __forceinline__ float slab_cap_rcp(float &idx, float &idy, float &idz) {
     const float m = fminf(fminf(fabsf(idx), fabsf(idy)), fabsf(idz)), cap = m * kSlabRcpRatio;

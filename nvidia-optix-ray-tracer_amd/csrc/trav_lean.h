@@ -37,9 +37,9 @@ __device__ __forceinline__ void lean_reset(LeanLane &L) {
 }
 
 // a lane without a ray: nothing to fetch, a ray and a best hit that are harmless to compute with (the wave-wide steps run for every lane)
-__device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray) {
+__device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray, float tlo) {
     lean_reset(L);
-    L.s.bt = tmax_ray; L.s.bu = 0.0f; L.s.bv = 0.0f; L.s.bprim = kMissPrim; L.s.binst = kMissPrim;
+    L.s.bt = tmax_ray; L.s.tlo = tlo; L.s.bu = 0.0f; L.s.bv = 0.0f; L.s.bprim = kMissPrim; L.s.binst = kMissPrim;
     L.s.ox = L.s.oy = L.s.oz = 0.0f; L.s.dx = L.s.dy = 0.0f; L.s.dz = 1.0f; L.s.idx = L.s.idy = L.s.idz = 1.0f; L.s.oct_inv4 = 0u;
 }
 
@@ -47,8 +47,10 @@ __device__ __forceinline__ void lean_idle(LeanLane &L, float tmax_ray) {
 // here: slab_cap_rcp caps the reciprocals, and the culling bound starts at min(tmax, 2^64 / max |d_c|) -- a reach of 2^64 world units
 // that no scene comes near; a normalised ray's 1e16 is untouched.  A ray that misses therefore may end with bt below tmax: lean_miss_t
 // is what its record says.
-__device__ __forceinline__ void lean_start(LeanLane &L, V3 o, V3 d, float tmax_ray) {
+// `tlo`: where the node step's interval begins for this ray (TravState::tlo) -- the launch's tmin, or the window of a repeat primary ray.
+__device__ __forceinline__ void lean_start(LeanLane &L, V3 o, V3 d, float tmax_ray, float tlo) {
     trav_start<false>(L.s, o, d, tmax_ray);
+    L.s.tlo = tlo;
     if (kSlabInterval01) L.s.bt = fminf(tmax_ray, kSlabReach * slab_cap_rcp(L.s.idx, L.s.idy, L.s.idz));
     lean_reset(L);
     L.nidx = 0u;

@@ -63,7 +63,7 @@ struct NoInstLane { static constexpr uint32_t inst_cur = 0u; };
 //      `is_free`: this lane has nothing of its own to do and may take a piece. ----
 
 // (one donation per busy lane and iteration: more rounds of this change nothing, r02_sweep_tile_tail.txt)
-__device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmax_ray) {
+__device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmin, float tmax_ray) {
     const uint64_t free_m = __ballot(is_free);
     const uint64_t donors = F.alive & __ballot(L.nsp > L.base);
     const uint32_t n_free = (uint32_t)__popcll(free_m), n_don = (uint32_t)__popcll(donors);
@@ -93,7 +93,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
         const uint32_t r_home = (uint32_t)__shfl((int)(F.home | (lane_bit(F.any) ? 0x100u : 0u)), src);
         const uint32_t r_gx = (uint32_t)__shfl((int)give.x, src), r_gy = (uint32_t)__shfl((int)give.y, src);
         if (is_recv) {
-            lean_start(L, mk3(r_ox, r_oy, r_oz), mk3(r_dx, r_dy, r_dz), tmax_ray);     // the same reciprocals and octant as the owner's
+            lean_start(L, mk3(r_ox, r_oy, r_oz), mk3(r_dx, r_dy, r_dz), tmax_ray, tmin);     // the same reciprocals and octant as the owner's (a piece culls from the launch's tmin)
             F.home = r_home & 0xffu; F.shared = true;
             s.bt = mb.t[F.home]; s.bu = mb.u[F.home]; s.bv = mb.v[F.home]; s.bprim = mb.prim[F.home]; s.binst = mb.inst[F.home];
             s.cur = make_uint2(r_gx, r_gy);           // a sibling group with hits: only those are pushed
@@ -164,7 +164,9 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
 //   nodes / leaves: the wave's LDS stacks; ldsn / ldsl: byte address in LDS of this lane's column of each
 //   leaf_hold: lean_bookkeeping_masked's `hold`;  may_help: the lane has no work of its own outside the loop either (tail splitting)
 // `a` is the kernel's argument block, by reference: only scalars are read from it, where they are used.
-template <bool HAS_SPHERES, bool INSTANCED, bool kTail, class Inst>
+// kLaneLo: the node step's interval begins at the lane's TravState::tlo (the kernels that give repeat primary rays a window) instead of the
+// wave-uniform tmin -- the same instructions, one operand a vector register where it was a scalar one.
+template <bool HAS_SPHERES, bool INSTANCED, bool kTail, bool kLaneLo = false, class Inst>
 __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Inst &I, LaneStats &stats, const Mailboxes &mb,
                                                   uint2 (*nodes)[kTraverseBlock], uint2 (*leaves)[kTraverseBlock], uint32_t ldsn, uint32_t ldsl,
                                                   const TraverseArgs &a, const char *node_bytes, const char *prim_bytes,
@@ -192,7 +194,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
     F.alive = wave_first_u64(F.alive); F.waiting = wave_first_u64(F.waiting); F.any = wave_first_u64(F.any);
     uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
     for (;;) {
-        if (kSplit && a.tail_split) tail_donate(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmax_ray);
+        if (kSplit && a.tail_split) tail_donate(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmin, tmax_ray);
 
         // ---- G. fetch what the lanes need next: primitives first, nodes second -- for the lanes that need one only (the
         //      instruction slots of the loads are not saved, but their L1 / TA cycles are).  The node loads are issued even when
@@ -241,10 +243,10 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         wait_node_loads(rn0, rn1, rn2, rn3, rn4);
         [[maybe_unused]] bool enter = false;
         if constexpr (!INSTANCED) {
-            node_slab_test<kSlabInterval01>(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            node_slab_test<kSlabInterval01>(L.s, kLaneLo ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
         } else {
             enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
-            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test<kSlabInterval01>(L.s, tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test<kSlabInterval01>(L.s, kLaneLo ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
             enter = I.enter_instance(enter, L.s, child, rn0, rn1, rn2, rn3, rn4, mb, tx);
             stats.entered(enter);
         }
