@@ -306,8 +306,8 @@ constexpr uint32_t kFetchShardStride = 32;   // u32s between counters: one 128-b
 constexpr int kFusedMaxDepth = 12;     // deepest tree (levels below the root) k_fused takes: its per-lane node stack in LDS (trav_lean.h: kNodeStackLds)
 constexpr uint32_t kTraversalStackEntries = 64;   // per-lane stack of round 1's kernels, which take what k_fused cannot (trav_common.h: kLdsStack + kSpillStack); a tree of
                                                   // depth d needs 2 d + 2 of them, and a build that comes out deeper fails (hrt_accel.cpp)
-void launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
-void launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // two-level trees (transform nodes, bvh8.h)
+bool launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);                // false: the launch was refused (fused.hip: sample blocks with a mode k_path_blocks does not have)
+bool launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // two-level trees (transform nodes, bvh8.h)
 void launch_fused_capture(const TraverseArgs &a, bool has_spheres, bool instanced, uint32_t grid_blocks, hipStream_t s);   // k_path_capture (fused_capture.hip): k_fused<S, I, false> that also keeps every pixel's primary hit
 void launch_trace_queue(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // k_trace_queue (fused_queue.hip): wavefront mode's traverse kernel, k_fused's traversal over ray queues
 void launch_sum(float4 *accum, const float4 *result, uint32_t n, uint32_t first_sample, hipStream_t s);

@@ -20,7 +20,7 @@
 
 namespace hrt {
 
-void launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // fused_blocks.hip
+bool launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // fused_blocks.hip (false: refused, nothing launched)
 
 // (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
 // from the segment itself, fused_body.h: kernarg_traverse_args)
@@ -32,13 +32,13 @@ __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD
 // one launch renders every sample of every pixel of the tile: the instantiation for the scene's primitives and, where the caller has set
 // a primary-hit cache up, primary reuse
 template <bool INSTANCED>
-static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
+static bool launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
     if constexpr (!INSTANCED) {
-        if (a.path.sample_block != 0u) {        // (render_fused sets it for one-level trees without a primary-hit cache only)
-            launch_fused_blocks(a, has_spheres, grid_blocks, s);
-            return;
-        }
+        // INVARIANT: k_path_blocks is compiled for sample_block != 0 with trace_rays, slice_cost and slice_order all NULL and never looks at
+        // them (path_lane.h).  render_fused (hrt_api.cpp), the only caller that sets sample_block, does so for one-level trees without a
+        // primary-hit cache, outside the cost probe and its slice order only; launch_fused_blocks refuses everything else (false).
+        if (a.path.sample_block != 0u) return launch_fused_blocks(a, has_spheres, grid_blocks, s);
     }
     switch ((has_spheres ? 2 : 0) | (a.path.primary_cache != nullptr ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((k_fused<false, INSTANCED, false>), g, b, 0, s, a); break;
@@ -46,9 +46,10 @@ static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t gr
         case 2: hipLaunchKernelGGL((k_fused<true, INSTANCED, false>), g, b, 0, s, a); break;
         default: hipLaunchKernelGGL((k_fused<true, INSTANCED, true>), g, b, 0, s, a); break;
     }
+    return true;
 }
-void launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { launch_fused_as<false>(a, has_spheres, grid_blocks, s); }
+bool launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { return launch_fused_as<false>(a, has_spheres, grid_blocks, s); }
 // ... through a two-level tree (transform nodes over shared BLASes)
-void launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { launch_fused_as<true>(a, has_spheres, grid_blocks, s); }
+bool launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { return launch_fused_as<true>(a, has_spheres, grid_blocks, s); }
 
 }  // namespace hrt

@@ -188,6 +188,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             stats.regeneration();
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
             const TraverseArgs &a = kernarg_traverse_args();      // (hides the parameter on purpose: nothing in this block reads the entry's copy)
+            // (Tried for BLOCKS: the block's constants -- samples, tmax, the seed's level, the schedule, the tables' and the hand-over's bases --
+            // made to exist here by an empty asm with them as inputs, so that their loads go out back to back behind one wait: 33 -> 16
+            // s_waitcnt lgkmcnt(0) in the block, nothing spilled, and 0.1 % SLOWER in five of five alternating runs, profiles/r23_block_regen.txt.)
             PathStep st;                            // st.launch: this lane starts the ray (st.ro, st.rd) below
             [[maybe_unused]] bool reshade = false;
             [[maybe_unused]] const bool was_forced = force_regen;
@@ -221,7 +224,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                     // a pixel's later primary rays are not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
                     P.px_depth = 1u; cached = true; reshade = true;      // (F.waiting: below)
                 } else {
-                    const PathRay r = path_primary<false>(P, a);
+                    const PathRay r = path_primary<false, BLOCKS>(P, a);
                     st.ro = r.o; st.rd = r.d; st.launch = true;
                 }
             }
@@ -229,7 +232,8 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             if (st.launch) {
                 any_hit = path_count_ray(P);
                 // a primary ray of a pixel the lane already holds starts bounded at the hit its previous sample found (s_seed; tmax after
-                // path_take): counted and walked from the root like any other, the primitive test keeps the launch's tmin and tmax.  At level
+                // path_take -- or, BLOCKS, what the pixel's previous block left for it, path_lane.h: handover_load):
+                // counted and walked from the root like any other, the primitive test keeps the launch's tmin and tmax.  At level
                 // 2 it is bounded from below as well: the same ray has found nothing before that hit, so the node step's interval begins a
                 // window (trav_common.h: kSeedWindow) below it.  Every other ray -- a bounce, a first sample, after a miss (the seed says
                 // tmax), a caller's ray -- begins at the launch's tmin.
@@ -253,7 +257,11 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             // s_waitcnt lgkmcnt(0): no scalar load of this block is under way when the traversal loop is entered.  A load issued in front of a
             // branch that skips its wait counts as pending to the compiler, which then waits INSIDE the loop wherever the loop reuses the
             // load's register (two s_waitcnt in the sphere kernels' loops, as the registers happened to fall)
-            __builtin_amdgcn_s_waitcnt(0xc07f);
+            // BLOCKS: ... and no vector load either (vmcnt(0) as well).  The words of a hand-over (path_lane.h: handover_load) are not needed before
+            // the lane's next regeneration, so with nothing else in the block waiting for them the compiler lets them fly into the loop
+            // and waits at the loop's header, in every iteration; here they have had the pixel's set-up and the ray's start to arrive
+            if constexpr (BLOCKS) __builtin_amdgcn_s_waitcnt(0x0070);
+            else __builtin_amdgcn_s_waitcnt(0xc07f);
         }
         // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, REUSE, a lane with a cached hit to shade:
         // an empty pass through the loop below brings it back here)

@@ -278,12 +278,14 @@ static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
     if (t.two_level) return {PathKernel::FusedInstanced, std::min<uint32_t>(knob, (uint32_t)kFusedInstancedBlocksPerCu)};
     return {PathKernel::Fused, std::min<uint32_t>(knob, (uint32_t)kFusedBlocksPerCu)};
 }
-static void launch_path_kernel(PathKernel k, const TraverseArgs &ta, bool has_spheres, uint32_t grid, hipStream_t s) {
+// (false: refused -- a launch in sample blocks that asks for what k_path_blocks is not compiled for, fused.hip)
+static bool launch_path_kernel(PathKernel k, const TraverseArgs &ta, bool has_spheres, uint32_t grid, hipStream_t s) {
     switch (k) {
-        case PathKernel::Fused: launch_fused(ta, has_spheres, grid, s); break;
-        case PathKernel::FusedInstanced: launch_fused_instanced(ta, has_spheres, grid, s); break;
+        case PathKernel::Fused: return launch_fused(ta, has_spheres, grid, s);
+        case PathKernel::FusedInstanced: return launch_fused_instanced(ta, has_spheres, grid, s);
         case PathKernel::Round1: launch_paths_v1(ta, has_spheres, grid, s); break;
     }
+    return true;
 }
 extern "C++" {      // (helpers of hrt_internal.hpp, shared with hrt_denoise.cpp)
 namespace hrt {
@@ -344,7 +346,7 @@ int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n
         // they are not launched on one: the records are filled and the rays counted as the kernel would have.  (k_traverse, below, has no
         // such limit and takes every interval.)
         if (pk.kernel != PathKernel::Round1 && !(tmax > tmin)) launch_fill_misses(tuvp, inst, n_rays, tmax, any_hit ? pa.rays_any : pa.rays_closest, s);
-        else launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s);
+        else if (!launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s)) return fail(ctx, HRT_ERR_STATE, "the path kernel refused the launch (sample blocks with callers' rays)");
     } else {
         ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
         ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;
@@ -460,7 +462,7 @@ static int render_fused(const LaunchFrame &f) {
         c.capacity = n;
     }
     bool captured = false;
-    auto launch = [&]() { launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s); };
+    auto launch = [&]() { return launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s); };
     // Longest-processing-time-first: a pixel's samples run one after the other in one lane, so a render ends with
     // whatever pixels were started last.  For renders of many samples the first sample is a probe launch of its own
     // that records how long each slice's pixels took over their sample; the slices are then handed out slowest first,
@@ -484,7 +486,7 @@ static int render_fused(const LaunchFrame &f) {
         HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         const uint32_t probe_spp = (uint32_t)std::min<int>(std::max(ctx->fused_lpt, 1), (int)spp / 4);
         pa.spp = probe_spp; pa.continue_sum = 0u; pa.slice_cost = w.slice_cost; pa.slice_order = nullptr;
-        { Timer tm(ctx, s, HRT_K_PATHS); launch(); }
+        { Timer tm(ctx, s, HRT_K_PATHS); (void)launch(); }       // (sample_block is still 0: nothing to refuse)
         ctx->fused_counters_clean = false;
         ctx->h_slice_cost.resize(n_slices); ctx->h_slice_order.resize(n_slices);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_slice_cost.data(), w.slice_cost, sizeof(uint32_t) * n_slices, hipMemcpyDeviceToHost, s));
@@ -548,7 +550,11 @@ static int render_fused(const LaunchFrame &f) {
             pa.trace_tuvp = nullptr; pa.trace_inst = nullptr;
             ctx->primary_capture_launches++;
             captured = true;
-        } else { Timer tm(ctx, s, HRT_K_PATHS); launch(); }
+        } else {
+            bool admitted;
+            { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch(); }
+            if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
+        }
         done_spp += now;
     }
     FinalizeArgs fa{};

@@ -30,7 +30,8 @@ struct PathLane {
     // word of the wave's LDS (`seed` of path_finish / path_take; fused_body.h: s_seed) and the register it had is the traversal's
     // TravState::tlo.  Every sample's primary ray is the same ray, so it ends in the same hit again: a complete closest-hit walk from the
     // root that never enters what lies behind that hit nor, with the window, what ends before it.  Reset by
-    // path_take, so it never outlives the lane's hold on the pixel; kept by the kernels that seed (SEED: fused_body.h) only.)
+    // path_take, so it never outlives the launch's hold on the pixel -- the lane's, or, in a render by sample blocks, that of the lanes
+    // that hand the pixel on within one launch (handover_store / handover_load); kept by the kernels that seed (SEED: fused_body.h) only.)
 };
 
 // what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
@@ -62,17 +63,22 @@ struct BlockSlice {
 // x / d for a divisor the host knows, m = min(2^32 / d, 2^32 - 1): the product's high word is short by one at most (every x, every d >= 1)
 __device__ __forceinline__ uint32_t div_magic(uint32_t x, uint32_t d, uint32_t m) { const uint32_t q = __umulhi(x, m); return x - q * d >= d ? q + 1u : q; }
 __device__ __forceinline__ unsigned long long pack_u64(uint32_t lo, uint32_t hi) { return (unsigned long long)lo | ((unsigned long long)hi << 32); }
-__device__ __forceinline__ void handover_store(const PathArgs &pa, const PathLane &P, uint32_t fetch_chunk) {
+// The second half of the sum's 16 bytes is nobody's: k_finalize, the non-block take of a continued render and k_sum read x, y, z only.  It
+// carries the pixel's seed (`seed`: the lane's LDS word, PathLane above) to the lane that takes the pixel's next block, whose first
+// primary ray is the same ray from the same camera in the same launch; handover_load hands it back for the caller to believe (a pass
+// b > 0) or not (pass 0: whatever is there comes from an earlier launch).
+__device__ __forceinline__ void handover_store(const PathArgs &pa, const PathLane &P, uint32_t fetch_chunk, float seed = 0.0f) {
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(pa.accum + P.px_local), *st = reinterpret_cast<unsigned long long *>(pa.states + P.px_tid);
     __hip_atomic_store(acc, pack_u64(__float_as_uint(P.px_ax), __float_as_uint(P.px_ay)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(acc + 1, pack_u64(__float_as_uint(P.px_az), 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(acc + 1, pack_u64(__float_as_uint(P.px_az), __float_as_uint(seed)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(st, pack_u64(P.px_rng.d, P.px_rng.v0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(st + 1, pack_u64(P.px_rng.v1, P.px_rng.v2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(st + 2, pack_u64(P.px_rng.v3, P.px_rng.v4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every store of the wave has been written through before any lane says so
     __hip_atomic_fetch_add(pa.block_progress + div_magic(P.px_local, fetch_chunk, pa.block_chunk_magic), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, bool with_sum) {
+// (returns the word next to the sum's z, `none` where the sum is not read)
+__device__ __forceinline__ float handover_load(const PathArgs &pa, PathLane &P, bool with_sum, float none = 0.0f) {
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(pa.accum + P.px_local), *st = reinterpret_cast<unsigned long long *>(pa.states + P.px_tid);
     const unsigned long long r0 = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r1 = __hip_atomic_load(st + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                              r2 = __hip_atomic_load(st + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -80,7 +86,32 @@ __device__ __forceinline__ void handover_load(const PathArgs &pa, PathLane &P, b
     if (with_sum) {
         const unsigned long long a0 = __hip_atomic_load(acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a1 = __hip_atomic_load(acc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         P.px_ax = __uint_as_float((uint32_t)a0); P.px_ay = __uint_as_float((uint32_t)(a0 >> 32)); P.px_az = __uint_as_float((uint32_t)a1);
+        none = __uint_as_float((uint32_t)(a1 >> 32));
     }
+    return none;
+}
+
+// fold_chain (trav_common.h) for a kernel that keeps the chain in registers (BLOCKS): the loop there loads hitgroups[chain[k]] and waits,
+// level by level, up to four round trips one behind the other, although all four addresses are known at once.  Here the albedos of
+// the levels below the depth are all asked for first, then multiplied in in the loop's order, innermost bounce first: the same
+// products in the same order, the same bits.
+__device__ __forceinline__ V3 fold_chain_together(bool miss, const float *bg, const uint32_t (&chain)[4], uint32_t depth, const HitGroup *__restrict__ hitgroups) {
+    static_assert(kRayTraceDepth <= 5u, "a path's chain has four entries");
+    V3 r = miss ? mk3(bg[0], bg[1], bg[2]) : mk3(0.0f, 0.0f, 0.0f);
+    float al[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        al[k][0] = al[k][1] = al[k][2] = 0.0f;
+        if ((uint32_t)k + 1u < depth) {
+            const global_floats ap = (global_floats)hitgroups[chain[k]].albedo;
+            al[k][0] = ap[0]; al[k][1] = ap[1]; al[k][2] = ap[2];
+        }
+    }
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {
+        if ((uint32_t)k + 1u < depth) { r.x *= al[k][0]; r.y *= al[k][1]; r.z *= al[k][2]; }
+    }
+    return r;
 }
 
 // A ray (o, d) has finished with the hit record (bt, bu, bv, bprim, binst).  The lane gives its pixel up (have_pixel = false: record or
@@ -103,13 +134,17 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             a.path.trace_inst[P.px_tid] = binst;
         }
     }
-    if (a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
+    // (BLOCKS: a block render has no callers' rays, no cost probe and no slice order, and its sample_block is not 0 -- facts of the
+    // instantiation, which launch_fused_blocks holds every launch to, so its regeneration neither loads nor tests them)
+    if (!BLOCKS && a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
         a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
         a.path.trace_inst[P.px_local] = binst;
         P.have_pixel = false;
     } else if (miss || P.px_depth >= kRayTraceDepth) {
         // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
-        const V3 r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        V3 r;
+        if constexpr (BLOCKS) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        else r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         if (P.px_first) { P.px_ax = r.x; P.px_ay = r.y; P.px_az = r.z; P.px_first = false; }
         else { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
         ++P.px_sample;
@@ -118,7 +153,7 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             if (miss && P.px_depth == 1u && !a.path.slice_cost)
                 for (; P.px_sample < a.path.spp; ++P.px_sample) { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
         }
-        if (a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
+        if (!BLOCKS && a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
             atomicAdd(a.path.slice_cost + P.px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - P.px_t0) >> 4);
         bool ends = P.px_sample >= a.path.spp;
         if constexpr (BLOCKS) {
@@ -133,7 +168,12 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             }
         }
         if (ends) {
-            if (BLOCKS && a.path.sample_block != 0u) handover_store(a.path, P, a.fetch_chunk);
+            if constexpr (BLOCKS) {
+                // (the seed travels with the pixel: what its last primary ray found, tmax after a miss or with HRT_SEED_PRIMARY=0)
+                float carried = 0.0f;
+                if constexpr (SEED) carried = *seed;
+                handover_store(a.path, P, a.fetch_chunk, carried);
+            }
             else {
                 a.path.accum[P.px_local] = make_float4(P.px_ax, P.px_ay, P.px_az, 0.0f);
                 rng_store(a.path.states + P.px_tid, P.px_rng);
@@ -166,8 +206,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                                           [[maybe_unused]] float *seed = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
-        bool by_blocks = false;
-        if constexpr (BLOCKS) by_blocks = a.path.sample_block != 0u;
+        constexpr bool by_blocks = BLOCKS;      // (launch_fused_blocks: sample_block != 0)
         if (by_blocks) {
             if constexpr (BLOCKS) {
                 if (wbeg >= wend) {
@@ -211,8 +250,9 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                 const uint32_t j = a.path.first_pixel + mine;
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
-                if constexpr (SEED) *seed = a.tmax;
-                if (!a.path.trace_rays) {
+                if constexpr (SEED && !BLOCKS) *seed = a.tmax;
+                [[maybe_unused]] float carried = 0.0f;      // (BLOCKS) the seed the pixel brings along
+                if (BLOCKS || !a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;
                     const uint32_t ix = j - row * a.path.width;
                     const uint32_t iy = a.path.rows[row];
@@ -222,15 +262,22 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                         if constexpr (BLOCKS) {                     // ... and so do later blocks of a launch
                             P.px_sample = block_first(a.path.sample_block, a.path.block_min, a.path.block_taper_end, a.path.block_magic == 0u, B->pass);
                             P.px_first = P.px_first && B->pass == 0u;
-                            handover_load(a.path, P, !P.px_first);
+                            // The seed comes with the pixel from the lane that ended its previous block IN THIS LAUNCH (a pass b > 0: the
+                            // same ray from the same camera, so what that lane's last primary ray found is what this lane's first will
+                            // find; a miss left tmax).  Pass 0 believes nothing it finds in memory -- the word is an earlier launch's,
+                            // perhaps another camera's -- and starts at tmax, whether or not the launch continues a sum.
+                            // (Stored below, behind the camera arithmetic, which the loads then have to arrive under.)
+                            carried = handover_load(a.path, P, !P.px_first, a.tmax);
+                            if (B->pass == 0u) carried = a.tmax;
                         }
                     } else {
                         P.px_sample = 0u; P.px_rng = rng_load(a.path.states + P.px_tid);
                         if (!P.px_first) { const float4 acc = a.path.accum[P.px_local]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; }
                     }
-                    if (a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
+                    if (!BLOCKS && a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
                     const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
                     P.px_pdx = pd.x; P.px_pdy = pd.y; P.px_pdz = pd.z;
+                    if constexpr (SEED && BLOCKS) *seed = carried;
                 }
             }
         }
@@ -242,10 +289,10 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
 // RECOMPUTE_DIRECTION: make the pixel's direction again instead of keeping px_pd* alive across the traversal (a kernel at its
 // register limit: k_traverse<.., HAS_SPHERES, FUSED>).
 struct PathRay { V3 o, d; };
-template <bool RECOMPUTE_DIRECTION>
+template <bool RECOMPUTE_DIRECTION, bool BLOCKS = false>
 __device__ __forceinline__ PathRay path_primary(PathLane &P, const TraverseArgs &a) {
     PathRay r;
-    if (a.path.trace_rays) {
+    if (!BLOCKS && a.path.trace_rays) {
         // (read as device memory, which it is: through generic pointers hipcc merges these loads with the other branch's into loads through
         // a pointer that is either the caller's ray or the camera in the kernel-argument segment -- a flat_load of kernel arguments)
         const global_floats q = (global_floats)reinterpret_cast<const float *>(a.path.trace_rays + P.px_local);
