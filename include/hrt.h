@@ -358,6 +358,9 @@ typedef struct HrtStats {
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
     uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
                                               at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
+    uint64_t one_group_launches;           /* of sample_block_launches: those that ran k_path_one, the kernel for a scene with one hit group -- a one-level
+                                              tree of triangles over exactly one instance (HRT_ONE_GROUP).  Added ahead of the counters below, like
+                                              denoise_history_rebinds: rebuild against this header */
     uint64_t denoise_history_rebinds;      /* temporal / variance denoiser calls since the context was created that began from a history handed over
                                               from another TLAS (hrt_denoise_temporal_rebind).  Added ahead of the three counters below, which
                                               tests/test_primary_capture_cpu.py pins as the structure's last: rebuild against this header */

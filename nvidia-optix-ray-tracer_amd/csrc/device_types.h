@@ -309,6 +309,9 @@ constexpr uint32_t kTraversalStackEntries = 64;   // per-lane stack of round 1's
 bool launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);                // false: the launch was refused (fused.hip: sample blocks with a mode k_path_blocks does not have)
 bool launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // two-level trees (transform nodes, bvh8.h)
 void launch_fused_capture(const TraverseArgs &a, bool has_spheres, bool instanced, uint32_t grid_blocks, hipStream_t s);   // k_path_capture (fused_capture.hip): k_fused<S, I, false> that also keeps every pixel's primary hit
+// k_path_one (fused_one.hip): the block render of a scene with one hit group.  The caller says what the launch's tree is; false: refused, nothing
+// launched -- whatever launch_fused_blocks would refuse, and any scene but a one-level tree of triangles over exactly one instance
+bool launch_fused_one(const TraverseArgs &a, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
 void launch_trace_queue(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // k_trace_queue (fused_queue.hip): wavefront mode's traverse kernel, k_fused's traversal over ray queues
 void launch_sum(float4 *accum, const float4 *result, uint32_t n, uint32_t first_sample, hipStream_t s);
 void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s);

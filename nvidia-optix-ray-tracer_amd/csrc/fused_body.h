@@ -1,5 +1,6 @@
 // fused_body.h -- the body of the persistent path kernel, ONCE, for the kernels that run it: k_fused (fused.hip), k_path_blocks
-// (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h) and k_path_capture (fused_capture.hip: primary hits kept per pixel).
+// (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h), k_path_one (fused_one.hip: k_path_blocks for a scene with one hit group)
+// and k_path_capture (fused_capture.hip: primary hits kept per pixel).
 // What the body does is described at the top of fused.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -126,9 +127,13 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 // `a`: the kernel's only argument (see kernarg_traverse_args); what the traversal loop consumes comes from it, the regeneration's
 // constants from the segment.
 // CAPTURE: k_path_capture (fused_capture.hip) -- every pixel's primary hit is left in frame order as well (path_lane.h: path_finish).
-template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false>
+// ONE_GROUP: k_path_one (fused_one.hip) -- a block render of triangles of ONE instance: every hit is instance 0's, so the regeneration reads
+// entry 0 of the per-instance tables with scalar loads and keeps no albedo chain (path_lane.h: path_finish), and the loop's primitive test
+// decides ties by the primitive id alone (trav_common.h: test_prim_ray).
+template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false, bool ONE_GROUP = false>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    static_assert(!ONE_GROUP || (BLOCKS && !HAS_SPHERES && !CAPTURE), "one hit group: the block render of a one-level tree of triangles");
     static_assert(!CAPTURE || (!REUSE && !BLOCKS), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
     // kSeed: the hit distance the lane's pixel last found along its primary ray (path_lane.h), read once per sample: a word of LDS, so that
@@ -166,7 +171,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     bool exhausted = false;                 // wave-uniform: no pixels left to start
 
     PathLane P;                             // the lane's pixel: path_lane.h
-    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path
+    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path (ONE_GROUP: never written, never read)
     LaneStats stats;
 
     // the wave's slice of the tile: [wbeg, wend); slices of fetch_chunk pixels are handed out by kFetchShards counters
@@ -201,7 +206,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                 const TravState &s = L.s;
                 // the finished ray and what it hit
                 V3 o = mk3(s.ox, s.oy, s.oz), d = mk3(s.dx, s.dy, s.dz);
-                float bt = lean_miss_t(s.bt, s.bprim, a.tmax), bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = s.binst;      // (a miss says tmax)
+                float bt = lean_miss_t(s.bt, s.bprim, a.tmax), bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = ONE_GROUP ? 0u : s.binst;      // (a miss says tmax)
                 if constexpr (REUSE) {
                     float4 *slot = a.path.primary_cache + 2u * (blockIdx.x * kTraverseBlock + tx);
                     if (cached) {                   // ... or, for a primary ray that was not traversed again, what the pixel's first sample found
@@ -213,7 +218,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
+                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
             }
             exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx);
             stats.drained(exhausted);
@@ -296,10 +301,10 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         //      and the drained phase's exit rule runs once the tile is used up ----
         if (exhausted) {
             stats.tail_begin();
-            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed, ONE_GROUP>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
             stats.tail_end();
         }
-        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed, ONE_GROUP>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
     const TraverseArgs &k = kernarg_traverse_args();          // (the counters' addresses need not live in registers until here)
     stats.report(k.path.rays_closest, tx);

@@ -551,8 +551,13 @@ static int render_fused(const LaunchFrame &f) {
             ctx->primary_capture_launches++;
             captured = true;
         } else {
+            // A launch in blocks of a scene with ONE hit group -- a one-level tree of triangles over exactly one instance, any single-mesh
+            // render -- takes k_path_one (fused_one.hip; HRT_ONE_GROUP=0: k_path_blocks like everything else).  Decided here, per launch,
+            // from the tree that is launched: an update that adds an instance sends the next launch back to k_path_blocks.
+            const bool one_group = blocks && ctx->one_group && !t->two_level && t->n_instances == 1u && !t->has_spheres;
             bool admitted;
-            { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch(); }
+            { Timer tm(ctx, s, HRT_K_PATHS); admitted = one_group ? launch_fused_one(ta, !t->two_level, t->n_instances, t->has_spheres, grid, s) : launch(); }
+            if (admitted && one_group) ctx->one_group_launches++;
             if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
         }
         done_spp += now;
@@ -913,6 +918,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->primary_capture_launches = ctx->primary_capture_launches;
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
     out->denoise_history_rebinds = ctx->denoise_history_rebinds;
+    out->one_group_launches = ctx->one_group_launches;
     return HRT_OK;
 }
 

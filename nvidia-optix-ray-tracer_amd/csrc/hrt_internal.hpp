@@ -272,6 +272,8 @@ struct HrtContext {
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)
     uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks
+    bool one_group = true;                      // HRT_ONE_GROUP: a launch in sample blocks of a one-level tree of triangles over exactly one instance runs k_path_one (fused_one.hip)
+    uint64_t one_group_launches = 0;            // ... and how many did
     int taper_big = kSampleTaperBig, taper_min = kSampleTaperMin;      // HRT_SAMPLE_TAPER: what `auto` hands out -- blocks that start at taper_big samples and end on taper_min (0: uniform blocks of kSampleBlockAuto)
     bool taper_forced = false;                  // ... whatever the tile, like HRT_SAMPLE_BLOCK=N (tests)
     uint32_t last_schedule[4] = {0u, 0u, 0u, 0u};      // the last launch in sample blocks: largest block, smallest block, end of the halvings (0: uniform), passes

@@ -114,6 +114,25 @@ __device__ __forceinline__ V3 fold_chain_together(bool miss, const float *bg, co
     return r;
 }
 
+// ONE_GROUP (k_path_one, fused_one.hip: every hit is instance 0's): the per-instance tables have one entry, the same for every lane, and it
+// is read as such -- through the constant address space, with scalar loads (s_load_dword*) into scalar registers, where it is used.  The
+// tables are written by the host before the launch and by nobody during it.
+typedef const __attribute__((address_space(4))) HitGroup *constant_hitgroup;
+typedef const __attribute__((address_space(4))) uint32_t *constant_words;
+// fold_chain for a path all of whose bounces hit the one group: the albedo is asked for once and no chain is kept.  The same products in
+// the same order as fold_chain_together makes of chain = {0, 0, 0, 0} (0 x inf, NaN and negative albedos included).
+__device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_t depth, const HitGroup *hitgroups) {
+    static_assert(kRayTraceDepth <= 5u, "a path's chain has four entries");
+    const constant_hitgroup hg = (constant_hitgroup)hitgroups;
+    const float a0 = hg->albedo[0], a1 = hg->albedo[1], a2 = hg->albedo[2];
+    V3 r = miss ? mk3(bg[0], bg[1], bg[2]) : mk3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {
+        if ((uint32_t)k + 1u < depth) { r.x *= a0; r.y *= a1; r.z *= a2; }
+    }
+    return r;
+}
+
 // A ray (o, d) has finished with the hit record (bt, bu, bv, bprim, binst).  The lane gives its pixel up (have_pixel = false: record or
 // sum written), wants the next sample's primary ray, or launches the bounce.
 // REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
@@ -122,7 +141,8 @@ __device__ __forceinline__ V3 fold_chain_together(bool miss, const float *bg, co
 // CAPTURE (k_path_capture, fused_capture.hip; HRT_CTX_CAPTURE_PRIMARY): the primary ray of the first sample the launch takes of a pixel
 // leaves its hit record in frame order, in hrt_trace_rays' form (a miss: tmax, kMissPrim), where the denoiser's guide pass and
 // hrt_primary_hits_get find it.  PathArgs::trace_tuvp / trace_inst are free in a render (trace_rays == NULL) and carry the two arrays.
-template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false>
+// ONE_GROUP: see above -- `binst` is 0, `px_chain` is neither written nor read.
+template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false, bool ONE_GROUP = false>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
                                             [[maybe_unused]] float *seed = nullptr) {
     PathStep st;
@@ -143,7 +163,8 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
     } else if (miss || P.px_depth >= kRayTraceDepth) {
         // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
         V3 r;
-        if constexpr (BLOCKS) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        if constexpr (ONE_GROUP) r = fold_chain_one(miss, a.path.bg, P.px_depth, a.path.hitgroups);
+        else if constexpr (BLOCKS) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         else r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         if (P.px_first) { P.px_ax = r.x; P.px_ay = r.y; P.px_az = r.z; P.px_first = false; }
         else { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
@@ -180,6 +201,17 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             }
             P.have_pixel = false;
         } else st.want_primary = true;
+    } else if constexpr (ONE_GROUP) {
+        // entry 0 of both tables, in scalar registers: the normals' loads go out as soon as the pointer is there, and what the program is --
+        // rough or metal, fuzz or none -- is the same in every lane, so scatter_programs' choices are the wave's
+        const constant_hitgroup hp0 = (constant_hitgroup)a.path.hitgroups;
+        HitGroup hg;
+        hg.ptr0 = hp0->ptr0; hg.ptr1 = nullptr; hg.albedo[0] = hg.albedo[1] = hg.albedo[2] = 0.0f; hg.fuzz = hp0->fuzz;      // (what a triangle program reads)
+        const uint32_t program = *(constant_words)a.path.inst_program;
+        V3 hp, nd;
+        scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
+        ++P.px_depth;
+        st.ro = hp; st.rd = nd; st.launch = true;
     } else {
         const uint32_t inst = binst;
         const HitGroup hg = a.path.hitgroups[inst];

@@ -298,7 +298,10 @@ __device__ __forceinline__ bool cond_lane(WaveCond c) { return __builtin_amdgcn_
 // (live, triangles only: false rejects the record -- the caller's lane has none and A / B / C are whatever its registers held; the
 // test still runs, so that the caller needs no per-lane branch round it)
 // (Cond: bool, or WaveCond -- triangles only, every lane active -- for the outcome as a wave mask)
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool>
+// ONE_GROUP (k_path_one, fused_one.hip: triangles of ONE instance): every record's instance is 0, so it is not read from the record, a
+// tie at the same distance goes to the lower primitive id -- what the (instance, primitive) order says when both instances are 0; a
+// ray that has no hit yet holds bprim == kMissPrim, above every id -- and TravState::binst is left alone: whoever reads it takes 0.
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false>
 __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
                                               const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
@@ -349,6 +352,14 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
         v = dot3(d, qvec) * inv;
         t = dot3(e2, qvec) * inv;
         const Cond ok = live & Cond(det != 0.0f) & Cond(u >= 0.0f) & Cond(v >= 0.0f) & Cond(u + v <= 1.0f) & Cond(t > tmin) & Cond(t < tmax_ray);
+        if constexpr (ONE_GROUP) {
+            static_assert(!ONE_GROUP || (!HAS_SPHERES && !INSTANCED), "one hit group: triangles, one level");
+            const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & Cond(prim < s.bprim)));
+            const bool mine = cond_lane(better);
+            s.bt = mine ? t : s.bt; s.bu = mine ? u : s.bu; s.bv = mine ? v : s.bv;
+            s.bprim = mine ? prim : s.bprim;
+            return better;
+        }
         if (!HAS_SPHERES) {
             // closest hit: min t, ties -> lowest (instance, primitive); predicated update
             const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & (Cond(inst < s.binst) | (Cond(inst == s.binst) & Cond(prim < s.bprim)))));
@@ -369,12 +380,12 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
     return better;
 }
 
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool>
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false>
 __device__ __forceinline__ Cond test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
                                           const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
                                           Cond live = true) {
-    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
+    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond, ONE_GROUP>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))

@@ -48,7 +48,9 @@ def phases(lines):
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if a != "-v"]
     want = args[0] if args else "ILb0ELb0ELb0E"
-    for name, lines in loop_bodies("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"):
+    # (k_path_one, fused_one.hip, is no template: ask for it by name -- tools/loop_phases.py k_path_one)
+    source = ("nvidia-optix-ray-tracer_amd/csrc/fused_one.hip", "_ZN3hrt10k_path_one") if "k_path_one" in want else ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused")
+    for name, lines in loop_bodies(*source):
         if want not in name:
             continue
         cs, sops = phases(lines)
