@@ -276,8 +276,8 @@ int  hrt_denoise_temporal_reset(HrtContext *ctx);
  * next_tlas, or HRT_NO_INSTANCE for a body that was not there.  NULL: the identity over the first min(n_prev, n_next) instances, every
  * further instance new.  n_instances must be next_tlas's count; the two counts may differ; an index may appear more than once.  An
  * instance whose BLAS handle differs from its predecessor's is treated as HRT_NO_INSTANCE (another geometry's primitive ids mean
- * nothing), compared at this call: both TLASes must be alive.  hrt_mesh_render's program flow, which builds a new GAS per particle
- * and file, would therefore carry nothing and does not call this; stable topology across different BLAS handles is not promised.
+ * nothing), compared at this call: both TLASes must be alive.  A caller whose BLASes are rebuilt with the same triangles -- Mesh
+ * mode's program flow, which builds a new GAS per particle and file -- declares that with hrt_denoise_temporal_rebind_geometry below.
  * The map is uploaded on `stream` (4 B per instance, kept by the context) and forms one pending link.  The next
  * hrt_denoise_temporal_launch / hrt_denoise_variance_launch takes it if it is on next_tlas, in the history's mode and frame size, and
  * the history is valid: a hit pixel of instance i with pi = map[i] reprojects by P' = X_prev(pi) (X_inv(i) P) and takes the taps
@@ -290,6 +290,22 @@ int  hrt_denoise_temporal_reset(HrtContext *ctx);
 #define HRT_NO_INSTANCE 0xffffffffu
 int  hrt_denoise_temporal_rebind(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances,
                                  void *stream);
+/* ... across rebuilt BLASes as well (DESIGN.md 3e "History across rebuilt BLASes"; tests/denoise_by_primitive_ref.py restates it):
+ * hrt_denoise_temporal_rebind in everything -- the map, NULL, the checks, the one pending link and what keeps and drops it, HRT_OK
+ * with nothing linked when there is no valid history -- except for an instance i whose BLAS handle differs from its predecessor pi's.
+ * If both BLASes are triangle BLASes with the same, non-zero primitive count, the instance is linked BY PRIMITIVE: the caller declares
+ * that primitive k at barycentrics (u, v) of the new BLAS is the material point (k, u, v) of the old one -- a mesh uploaded again,
+ * deformed, or baked at other world positions (RendererMesh.cu's GAS per particle and file), its triangles in the same order.  A hit
+ * pixel of such an instance reprojects from Po = (a w + b u) + c v, w = (1 - u) - v, with a, b, c primitive k's vertices in the OLD
+ * BLAS in the caller's order (u weighs the second vertex, v the third, as in the shading normal), P' = X_prev(pi) Po; this frame's
+ * X_inv(i) is not used for it.  The taps, the (pi, k) id test, the depth test and the blend are the rigid path's.  A sphere BLAS on
+ * either side, differing counts, or triangles against spheres: HRT_NO_INSTANCE as above.  Instances whose handle is unchanged take the
+ * rigid path, and a link without a by-primitive entry is hrt_denoise_temporal_rebind's bit for bit.
+ * The link keeps every old BLAS it reads alive (its device vertices, 36 B per triangle) until it is consumed, replaced or dropped:
+ * hrt_blas_destroy / hrt_tlas_destroy of the old objects between this call and the launch is allowed.  Uploads 4 + 8 B per instance
+ * on `stream`.  HrtStats.denoise_by_primitive_links counts the instances linked by primitive, at this call. */
+int  hrt_denoise_temporal_rebind_geometry(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances,
+                                          void *stream);
 /* the last hrt_denoise_temporal_launch's intermediates, width * height each (a NULL pointer skips its buffer): the accumulated colour
  * A (float4, what the filter took), the history length L (float; 0 on background), and the reprojected position (x', y') in the
  * previous frame's pixel coordinates (float2; NaN where no projection was made).  HRT_ERR_STATE before the first call.  Enqueued only. */
@@ -361,6 +377,9 @@ typedef struct HrtStats {
     uint64_t one_group_launches;           /* of sample_block_launches: those that ran k_path_one, the kernel for a scene with one hit group -- a one-level
                                               tree of triangles over exactly one instance (HRT_ONE_GROUP).  Added ahead of the counters below, like
                                               denoise_history_rebinds: rebuild against this header */
+    uint64_t denoise_by_primitive_links;   /* instances that hrt_denoise_temporal_rebind_geometry calls since the context was created have linked by
+                                              primitive (counted at the call).  Added ahead of denoise_history_rebinds, which
+                                              tests/test_denoise_handoff_cpu.py pins in front of the last three: rebuild against this header */
     uint64_t denoise_history_rebinds;      /* temporal / variance denoiser calls since the context was created that began from a history handed over
                                               from another TLAS (hrt_denoise_temporal_rebind).  Added ahead of the three counters below, which
                                               tests/test_primary_capture_cpu.py pins as the structure's last: rebuild against this header */

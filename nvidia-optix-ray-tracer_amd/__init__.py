@@ -83,7 +83,7 @@ class Stats(C.Structure):
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
                 ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
                 ("sample_block_schedule", C.c_uint64 * 4),
-                ("one_group_launches", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
+                ("one_group_launches", C.c_uint64), ("denoise_by_primitive_links", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
                 ("primary_capture_launches", C.c_uint64), ("guide_passes_traced", C.c_uint64), ("guide_passes_captured", C.c_uint64)]
 
 
@@ -129,7 +129,7 @@ EXPORTS = [
     "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
-    "hrt_denoise_temporal_rebind",
+    "hrt_denoise_temporal_rebind", "hrt_denoise_temporal_rebind_geometry",
     "hrt_denoise_variance_default_params", "hrt_denoise_filter_variance", "hrt_denoise_variance_launch", "hrt_debug_denoise_variance_state",
 ]
 
@@ -205,6 +205,7 @@ def load_library():
                                                 C.POINTER(DenoiseTemporalParams), C.c_void_p, C.c_void_p]
     lib.hrt_denoise_temporal_reset.argtypes = [C.c_void_p]
     lib.hrt_denoise_temporal_rebind.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]
+    lib.hrt_denoise_temporal_rebind_geometry.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p]
     lib.hrt_debug_denoise_temporal_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_denoise_variance_default_params.argtypes = [C.POINTER(DenoiseVarianceParams)]
     lib.hrt_denoise_filter_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,

@@ -183,7 +183,9 @@ __global__ __launch_bounds__(kDenoiseTile * kDenoiseTile) void k_denoise_pass(De
 template <bool kMoments>
 __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseTemporalArgs a) {
     constexpr bool kLinked = false;
+    constexpr bool kByPrim = false;
     const uint32_t *prev_index = nullptr;
+    const float *const *prev_verts = nullptr;
 #include "denoise_temporal_body.inc"
 }
 

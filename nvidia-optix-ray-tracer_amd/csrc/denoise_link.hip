@@ -12,8 +12,10 @@ namespace hrt {
 template <bool kMoments>
 __global__ __launch_bounds__(256) void k_denoise_temporal_linked(DenoiseTemporalLinkedArgs args) {
     constexpr bool kLinked = true;
+    constexpr bool kByPrim = false;
     const DenoiseTemporalArgs &a = args.t;
     const uint32_t *prev_index = args.prev_index;
+    const float *const *prev_verts = nullptr;
 #include "denoise_temporal_body.inc"
 }
 

@@ -1,12 +1,15 @@
 // denoise_temporal_body.h -- the temporal mode's reprojection and blend as device code, for the translation units that make kernels of
-// it: denoise.hip (k_denoise_temporal<kMoments>, the unlinked form) and denoise_link.hip (k_denoise_temporal_linked<kMoments>: the first
-// call after hrt_denoise_temporal_rebind, whose history was made for another TLAS of the same scene), as fused_body.h serves fused.hip
-// and fused_capture.hip.  This header holds what stands at file scope; the statements are denoise_temporal_body.inc, which a kernel
+// it: denoise.hip (k_denoise_temporal<kMoments>, the unlinked form), denoise_link.hip (k_denoise_temporal_linked<kMoments>: the first
+// call after hrt_denoise_temporal_rebind, whose history was made for another TLAS of the same scene) and denoise_link_prim.hip
+// (k_denoise_temporal_by_prim<kMoments>: ... after hrt_denoise_temporal_rebind_geometry, with rebuilt BLASes among the instances), as
+// fused_body.h serves fused.hip and fused_capture.hip.  This header holds what stands at file scope; the statements are denoise_temporal_body.inc, which a kernel
 // includes as its body with these names in scope:
 //   a           const DenoiseTemporalArgs (or a reference to one)
 //   kMoments    constexpr bool: the variance-guided mode's moments ride along
 //   kLinked     constexpr bool: the history is another TLAS's; every use sits under `if constexpr`
 //   prev_index  const uint32_t *: per instance of this frame's TLAS, its index in the history's (kNoInstance: none); read if kLinked only
+//   kByPrim     constexpr bool: the link has instances whose BLAS was rebuilt (denoise_link_prim.hip); every use sits under `if constexpr`
+//   prev_verts  const float *const *: per instance of this frame's TLAS, the vertices of its predecessor's BLAS or NULL; read if kByPrim only
 // The statements stand in the kernels themselves rather than in a __device__ function the kernels call: through a function, by value or
 // by reference, the unlinked kernels come out with commutative operands swapped in a few instructions, and they are to stay instruction
 // for instruction what they were when the body stood in denoise.hip (profiles/r21_denoise_handoff.txt has the comparison).
@@ -28,6 +31,12 @@
 // kLinked (DESIGN.md 3e "History across TLAS handles"; tests/denoise_handoff_ref.py): pi = prev_index[i].  pi == kNoInstance: a body
 // that was not there, so no history -- A = C, L = 1, M = mc, no motion.  Otherwise P' = X_prev(pi) (X_inv(i) P) and a tap counts if it
 // holds (pi, primitive); everything else as above.  The id written for the next call is (i, primitive) in both forms.
+// kByPrim (DESIGN.md 3e "History across rebuilt BLASes"; tests/denoise_by_primitive_ref.py): s = prev_verts[i], asked for next to
+// prev_index[i].  s == NULL: the rigid path above.  Otherwise, with the hit's (u, v) and primitive k: a = s[9k .. 9k+2],
+// b = s[9k+3 .. 9k+5], c = s[9k+6 .. 9k+8], w = (1 - u) - v, Po = (a w + b u) + c v per component (hit_normal's order, trav_common.h:
+// u weighs the second vertex, v the third), P' = X_prev(pi) Po; X_inv(i) is not used.  Taps, id test (pi, k), depth test, blend and
+// moments as above.  The triangle is loaded with the ray record, by every lane (a rigid lane's address is its own world -> object
+// row), and Po is selected, not branched on.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
-// denoise_temporal_body.inc -- the statements of the temporal mode's reprojection and blend: the body of k_denoise_temporal (denoise.hip)
-// and of k_denoise_temporal_linked (denoise_link.hip).  denoise_temporal_body.h has the definition and the names this expects in scope.
+// denoise_temporal_body.inc -- the statements of the temporal mode's reprojection and blend: the body of k_denoise_temporal (denoise.hip),
+// of k_denoise_temporal_linked (denoise_link.hip) and of k_denoise_temporal_by_prim (denoise_link_prim.hip).  denoise_temporal_body.h has the definition and the names this expects in scope.
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.width * a.height) return;
     const float4 c = a.color[p];
@@ -19,11 +19,23 @@
         if (kMoments) { lc = luminance(c); mom = make_float2(lc, lc * lc); }
         uint32_t pinst = inst;                                     // the instance's index in the history
         if constexpr (kLinked) pinst = prev_index[inst];
+        const float *sv = nullptr;                                 // by primitive: the vertices of the instance's BLAS in the history
+        if constexpr (kByPrim) sv = ((const float *const __attribute__((address_space(1))) *)prev_verts)[inst];
         if (a.has_history && (!kLinked || pinst != kNoInstance)) {
             const RayRec ray = a.rays[p];
             const float hp[3] = {ray.o.x + ray.d.x * h.x, ray.o.y + ray.d.y * h.x, ray.o.z + ray.d.z * h.x};      // hit_point
             float po[3], pw[3];
             xf_point(a.inst_inv + 12 * (size_t)inst, hp, po);
+            if constexpr (kByPrim) {
+                // the material point (prim, u, v) of the previous BLAS, hit_normal's vertex order (trav_common.h).  Every lane loads a
+                // triangle -- the rigid ones (sv == NULL) nine floats of their own world -> object row, which are there -- and the
+                // position is selected: lanes of one wave sit on both paths, and the projection below stands once
+                const global_floats tv = sv ? (global_floats)sv + 9 * (size_t)prim : (global_floats)(a.inst_inv + 12 * (size_t)inst);
+                const float va[3] = {tv[0], tv[1], tv[2]}, vb[3] = {tv[3], tv[4], tv[5]}, vc[3] = {tv[6], tv[7], tv[8]};
+                const float bw = (1.0f - h.y) - h.z;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { const float pb = (va[k] * bw + vb[k] * h.y) + vc[k] * h.z; po[k] = sv ? pb : po[k]; }
+            }
             xf_point(a.prev_xf + 12 * (size_t)pinst, po, pw);
             const V3 r = mk3(pw[0] - a.prev_center[0], pw[1] - a.prev_center[1], pw[2] - a.prev_center[2]);
             const V3 U = mk3(a.prev_U[0], a.prev_U[1], a.prev_U[2]), V = mk3(a.prev_V[0], a.prev_V[1], a.prev_V[2]);

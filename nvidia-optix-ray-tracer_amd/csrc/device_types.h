@@ -279,6 +279,14 @@ struct DenoiseTemporalLinkedArgs {
     DenoiseTemporalArgs t;
     const uint32_t *prev_index;
 };
+// ... of the first call after hrt_denoise_temporal_rebind_geometry when the link has by-primitive entries (denoise_link_prim.hip):
+// prev_verts[i] is the object-space vertex array (9 floats per triangle, Blas::d_verts) of the BLAS instance i had in the history's TLAS
+// where the two BLASes differ, NULL where instance i takes the rigid path or has no predecessor.  Behind the unlinked arguments too.
+struct DenoiseTemporalByPrimArgs {
+    DenoiseTemporalArgs t;
+    const uint32_t *prev_index;
+    const float *const *prev_verts;
+};
 // the variance-guided mode: the per-pixel variance from the moments
 struct DenoiseVarianceArgs {
     const float2 *moments; const float *length; const uint2 *id; float *variance;
@@ -288,6 +296,7 @@ struct DenoiseVarianceArgs {
 void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s);
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
 void launch_denoise_temporal_linked(const DenoiseTemporalLinkedArgs &a, hipStream_t s);      // denoise_link.hip
+void launch_denoise_temporal_by_prim(const DenoiseTemporalByPrimArgs &a, hipStream_t s);     // denoise_link_prim.hip
 void launch_denoise_rays(const DenoiseRayArgs &a, hipStream_t s);
 void launch_denoise_guides(const DenoiseGuideArgs &a, hipStream_t s);
 void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s);

@@ -2,8 +2,11 @@
 // main() (src/Global/Main.cu:21-36) -> RendererMesh::writeCacheFilesAndExit (src/Util/VTKMeshReader.cu:146-215) when the
 // config says "cache", else RendererMesh::commitRendererData (src/Global/RendererMesh.cu:160-310) -> RendererMesh::startRender's
 // frame loop (:312-440) with the window and camera input left out; the denoiser (denoiseOutput, :420-426) runs with --denoise.
-//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture]
+//   hrt_mesh_render <config.json> [exe_dir] [max_frames=one pass over the files] [out.ppm] [width height] [--denoise | --denoise-temporal | --denoise-variance] [--no-capture] [--no-history-handoff]
 // exe_dir is the directory the config's relative paths are relative to (the reference runs from bin/).
+// Under --denoise-temporal and --denoise-variance the denoiser's history follows the loop from one file's IAS to the next: a particle
+// is found again by its id, and since its GAS was built anew from the file's vertices, it is linked primitive by primitive
+// (rebindDenoiseHistoryGeometry; --no-history-handoff: every file's first frame starts afresh).
 // Loading: up to cache-process-thread-count loader threads, each with its own stream, read particleN.cache and build one GAS per
 // particle plus the file's IAS ON THE DEVICE (readVTKFileCache, :93-157).  Per frame: every particle drifts by its velocity
 // (hrt_pose_instances in Mesh mode replaces the host loop :379-391 and the H2D copy :395-397) -> updateIAS -> launch + sync ->
@@ -15,6 +18,7 @@
 #include <deque>
 #include <string>
 #include <thread>
+#include <unordered_map>
 
 using namespace driver;
 
@@ -51,7 +55,8 @@ struct FileData {
 int main(int argc, char **argv) {
     const DenoiseMode denoiseMode = parseDenoiseMode(argc, argv);
     const uint32_t denoiseFlags = denoiseContextFlags(denoiseMode, argc, argv);
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s\n", argv[0], kDenoiseUsage); return 2; }
+    const bool historyHandoff = denoiseHistoryHandoff(denoiseMode, argc, argv);
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <config.json> [exe_dir] [max_frames] [out.ppm] [width height] %s %s\n", argv[0], kDenoiseUsage, kHandoffUsage); return 2; }
     const std::string configPath = argv[1];
     const std::string exeDir = argc > 2 ? argv[2] : ".";
     const long maxFrames = argc > 3 ? std::atol(argv[3]) : -1;
@@ -183,6 +188,20 @@ int main(int argc, char **argv) {
     for (uint64_t f = 0; f < series.n && (maxFrames < 0 || frames < maxFrames); ++f) {     // (the reference loops the animation; one pass here)
         FileData &fd = perFile[f];
         hrtCheckError(ctx, hrt_materials_set(ctx, fd.records.data(), (uint32_t)fd.records.size()));
+        if (historyHandoff && f > 0) {
+            // the loop moves to this file's IAS: the extra spheres are the last file's, through the same GAS; a particle is the one of
+            // the last file with its id, its triangles the same ones at this file's positions; an id the last file did not have is new
+            const FileData &last = perFile[f - 1];
+            std::unordered_map<uint64_t, uint32_t> instanceOfId;
+            for (size_t p = 0; p < last.particleCount; ++p) instanceOfId.emplace(last.ids[p], (uint32_t)(addGeoCount + p));
+            std::vector<uint32_t> previousInstance(fd.instanceCount, HRT_NO_INSTANCE);
+            for (size_t i = 0; i < addGeoCount; ++i) previousInstance[i] = (uint32_t)i;
+            for (size_t p = 0; p < fd.particleCount; ++p) {
+                const auto it = instanceOfId.find(fd.ids[p]);
+                if (it != instanceOfId.end()) previousInstance[addGeoCount + p] = it->second;
+            }
+            rebindDenoiseHistoryGeometry(ctx, std::get<0>(fd.ias), fd.instanceCount, previousInstance.data());
+        }
         const size_t frameCountPerFile = (size_t)(series.durations[f] * (float)(cfg.fps * cfg.render_speed_ratio));   // :366-367
         HrtPoseParams pose{};
         pose.duration = series.durations[f]; pose.frame_count = (uint32_t)frameCountPerFile; pose.mesh_mode = 1;

@@ -207,4 +207,12 @@ inline void rebindDenoiseHistory(HrtContext *ctx, HrtTraversable next, size_t in
     hrtCheckError(ctx, hrt_denoise_temporal_rebind(ctx, next, previousInstance, (uint32_t)instanceCount, stream));
 }
 
+// ... on to an IAS whose GASes were built anew from the same triangles (Mesh mode: a GAS per particle and file, RendererMesh.cu:93-157):
+// an instance whose GAS differs from its predecessor's keeps its history primitive by primitive, through the previous GAS's vertices
+// (hrt_denoise_temporal_rebind_geometry).  The previous file's GASes and IAS may be cleaned up right after this call.
+inline void rebindDenoiseHistoryGeometry(HrtContext *ctx, HrtTraversable next, size_t instanceCount, const uint32_t *previousInstance = nullptr,
+                                         hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_denoise_temporal_rebind_geometry(ctx, next, previousInstance, (uint32_t)instanceCount, stream));
+}
+
 }  // namespace project

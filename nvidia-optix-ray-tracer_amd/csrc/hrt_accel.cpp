@@ -1269,7 +1269,7 @@ int hrt_tlas_destroy(HrtContext *ctx, HrtTraversable tlas) {
     if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "unknown TLAS handle");
     (void)hipDeviceSynchronize();
     if (ctx->capture.tlas == tlas) ctx->capture.valid = false;
-    if (ctx->denoise_history.link_tlas == tlas) ctx->denoise_history.link_pending = false;      // (hrt_denoise_temporal_rebind's link to it)
+    if (ctx->denoise_history.link_tlas == tlas) ctx->denoise_history.drop_link();      // (hrt_denoise_temporal_rebind's link to it)
     free_tlas_device(ctx, *it->second); free_tlas_host(*it->second);
     ctx->tlas.erase(it);
     return HRT_OK;

@@ -918,6 +918,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->primary_capture_launches = ctx->primary_capture_launches;
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
     out->denoise_history_rebinds = ctx->denoise_history_rebinds;
+    out->denoise_by_primitive_links = ctx->denoise_by_primitive_links;
     out->one_group_launches = ctx->one_group_launches;
     return HRT_OK;
 }

@@ -26,6 +26,7 @@ void free_denoise_history(HrtContext *ctx) {
     if (h.motion) (void)hipFree(h.motion);
     if (h.variance) (void)hipFree(h.variance);
     if (h.link) (void)hipFree(h.link);
+    if (h.link_verts) (void)hipFree((void *)h.link_verts);
     h = DenoiseHistory{};
 }
 
@@ -251,14 +252,16 @@ int run_temporal(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayG
     ta.alpha_min = tp.alpha_min; ta.max_history = (float)tp.max_history; ta.depth_tolerance = tp.depth_tolerance;
     if (moments) { ta.prev_moments = prev.moments; ta.moments = next.moments; }
     if (linked) {
-        launch_denoise_temporal_linked(DenoiseTemporalLinkedArgs{ta, h.link}, s);
+        // (a link with no by-primitive entry is hrt_denoise_temporal_rebind's, whichever call made it)
+        if (h.link_by_prim) launch_denoise_temporal_by_prim(DenoiseTemporalByPrimArgs{ta, h.link, h.link_verts}, s);
+        else launch_denoise_temporal_linked(DenoiseTemporalLinkedArgs{ta, h.link}, s);
         ctx->denoise_history_rebinds++;
     } else launch_denoise_temporal(ta, s);
     HIP_TRY(ctx, hipMemcpyAsync(next.xf, t->dev.d_inst_xf, sizeof(float) * 12 * (size_t)std::max(t->n_instances, 1u), hipMemcpyDeviceToDevice, s));
     std::memcpy(next.center, &h_raygen->cameraCenter, 12); std::memcpy(next.U, &h_raygen->cameraU, 12);
     std::memcpy(next.V, &h_raygen->cameraV, 12); std::memcpy(next.W, &h_raygen->cameraW, 12);
     h.cur ^= 1u;
-    h.link_pending = false;
+    h.drop_link();                    // (consumed or not.  The old BLASes it owned go here: ~Blas's hipFree waits for the kernel above)
     h.valid = false;                  // (until the caller has enqueued the filter as well)
     h.mode = mode;
     h.called = true;
@@ -296,6 +299,78 @@ int temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtR
     rc = run_filter(ctx, next.accum, next.guides, vp ? h.variance : nullptr, reinterpret_cast<float4 *>(d_out), nullptr, width, height, passes, s);
     if (rc != HRT_OK) return rc;
     h.valid = true;
+    return HRT_OK;
+}
+
+// hrt_denoise_temporal_rebind, and with by_primitive hrt_denoise_temporal_rebind_geometry (`name`: whose messages these are): the link
+// from the history's TLAS to next_tlas.  An instance whose BLAS handle differs from its predecessor's has no history in the first; in
+// the second it is linked by primitive where both BLASes are triangle BLASes of the same, non-zero primitive count, decided here from
+// the BLAS each TLAS keeps per instance (Tlas::blas_refs, filled by every build path: build_tlas_fresh).
+int rebind_history(HrtContext *ctx, const char *name, bool by_primitive, HrtTraversable next_tlas, const uint32_t *h_prev_instance,
+                   uint32_t n_instances, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    DenoiseHistory &h = ctx->denoise_history;
+    std::vector<uint32_t> link;
+    std::vector<const float *> verts;
+    std::vector<std::shared_ptr<Blas>> owned;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const auto next = ctx->tlas.find(next_tlas);
+        if (next == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "%s: 0x%llx is not a TLAS", name, (unsigned long long)next_tlas);
+        const Tlas &tn = *next->second;
+        if (n_instances != tn.n_instances)
+            return fail(ctx, HRT_ERR_INVALID, "%s: n_instances %u is not the TLAS's %u", name, n_instances, tn.n_instances);
+        const auto prev = ctx->tlas.find(h.tlas);
+        if (!h.valid || prev == ctx->tlas.end()) {      // nothing to hand over: the next call starts afresh, as without this one
+            h.drop_link();
+            return HRT_OK;
+        }
+        const Tlas &tp = *prev->second;
+        link.assign(std::max(n_instances, 1u), HRT_NO_INSTANCE);
+        if (by_primitive) verts.assign(link.size(), nullptr);
+        for (uint32_t i = 0; i < n_instances; ++i) {
+            uint32_t pi = h_prev_instance ? h_prev_instance[i] : (i < tp.n_instances ? i : HRT_NO_INSTANCE);
+            if (pi != HRT_NO_INSTANCE && pi >= tp.n_instances)
+                return fail(ctx, HRT_ERR_INVALID, "%s: h_prev_instance[%u] = %u, the history's TLAS has %u instances", name, i, pi, tp.n_instances);
+            if (pi != HRT_NO_INSTANCE && tn.sig_handle[i] != tp.sig_handle[pi]) {
+                // another geometry: its primitive ids mean nothing (such a body starts afresh) unless the caller has declared the
+                // triangles the same ones, which two triangle BLASes of one count can be
+                const std::shared_ptr<Blas> &bn = tn.blas_refs[i], &bp = tp.blas_refs[pi];
+                const bool same_triangles = by_primitive && bn && bp && bn->kind == kPrimKindTriangle && bp->kind == kPrimKindTriangle &&
+                                            bn->n_prims != 0 && bn->n_prims == bp->n_prims && bp->d_verts;
+                if (same_triangles) { verts[i] = bp->d_verts; owned.push_back(bp); }
+                else pi = HRT_NO_INSTANCE;
+            }
+            link[i] = pi;
+        }
+    }
+    h.drop_link();                             // (replaced: a failed upload leaves none)
+    if (link.size() > h.link_capacity) {
+        if (h.link) (void)hipFree(h.link);
+        h.link = nullptr; h.link_capacity = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&h.link, sizeof(uint32_t) * link.size()));
+        h.link_capacity = (uint32_t)link.size();
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    h.h_link.swap(link);
+    HIP_TRY(ctx, hipMemcpyAsync(h.link, h.h_link.data(), sizeof(uint32_t) * h.h_link.size(), hipMemcpyHostToDevice, s));
+    if (!owned.empty()) {
+        if (verts.size() > h.link_verts_capacity) {
+            if (h.link_verts) (void)hipFree((void *)h.link_verts);
+            h.link_verts = nullptr; h.link_verts_capacity = 0;
+            HIP_TRY(ctx, hipMalloc((void **)&h.link_verts, sizeof(const float *) * verts.size()));
+            h.link_verts_capacity = (uint32_t)verts.size();
+        }
+        h.h_link_verts.swap(verts);
+        HIP_TRY(ctx, hipMemcpyAsync(h.link_verts, h.h_link_verts.data(), sizeof(const float *) * h.h_link_verts.size(), hipMemcpyHostToDevice, s));
+        // The link owns the predecessors' BLASes from here until it is consumed, replaced or dropped (DenoiseHistory::drop_link).  The
+        // last reference's ~Blas runs hipFree, which waits for the device: a kernel that reads these vertices has finished by then.
+        h.link_by_prim = (uint32_t)owned.size();
+        h.link_blas.swap(owned);
+        ctx->denoise_by_primitive_links += h.link_by_prim;
+    }
+    h.link_pending = true; h.link_tlas = next_tlas; h.link_n = n_instances;
     return HRT_OK;
 }
 
@@ -362,49 +437,16 @@ int hrt_denoise_temporal_launch(HrtContext *ctx, const HrtGlobalParams *h_params
 int hrt_denoise_temporal_reset(HrtContext *ctx) {
     if (!ctx) return HRT_ERR_INVALID;
     ctx->denoise_history.valid = false;
-    ctx->denoise_history.link_pending = false;
+    ctx->denoise_history.drop_link();
     return HRT_OK;
 }
 
 int hrt_denoise_temporal_rebind(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances, void *stream) {
-    if (!ctx) return HRT_ERR_INVALID;
-    (void)hipSetDevice(ctx->device);
-    DenoiseHistory &h = ctx->denoise_history;
-    std::vector<uint32_t> link;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        const auto next = ctx->tlas.find(next_tlas);
-        if (next == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: 0x%llx is not a TLAS", (unsigned long long)next_tlas);
-        const Tlas &tn = *next->second;
-        if (n_instances != tn.n_instances)
-            return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: n_instances %u is not the TLAS's %u", n_instances, tn.n_instances);
-        const auto prev = ctx->tlas.find(h.tlas);
-        if (!h.valid || prev == ctx->tlas.end()) {      // nothing to hand over: the next call starts afresh, as without this one
-            h.link_pending = false;
-            return HRT_OK;
-        }
-        const Tlas &tp = *prev->second;
-        link.assign(std::max(n_instances, 1u), HRT_NO_INSTANCE);
-        for (uint32_t i = 0; i < n_instances; ++i) {
-            uint32_t pi = h_prev_instance ? h_prev_instance[i] : (i < tp.n_instances ? i : HRT_NO_INSTANCE);
-            if (pi != HRT_NO_INSTANCE && pi >= tp.n_instances)
-                return fail(ctx, HRT_ERR_INVALID, "hrt_denoise_temporal_rebind: h_prev_instance[%u] = %u, the history's TLAS has %u instances", i, pi, tp.n_instances);
-            // (another geometry's primitive ids mean nothing: such a body starts afresh)
-            if (pi != HRT_NO_INSTANCE && tn.sig_handle[i] != tp.sig_handle[pi]) pi = HRT_NO_INSTANCE;
-            link[i] = pi;
-        }
-    }
-    if (link.size() > h.link_capacity) {
-        if (h.link) (void)hipFree(h.link);
-        h.link = nullptr; h.link_capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&h.link, sizeof(uint32_t) * link.size()));
-        h.link_capacity = (uint32_t)link.size();
-    }
-    h.link_pending = false;                    // (replaced: a failed upload leaves none)
-    h.h_link.swap(link);
-    HIP_TRY(ctx, hipMemcpyAsync(h.link, h.h_link.data(), sizeof(uint32_t) * h.h_link.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
-    h.link_pending = true; h.link_tlas = next_tlas; h.link_n = n_instances;
-    return HRT_OK;
+    return rebind_history(ctx, "hrt_denoise_temporal_rebind", false, next_tlas, h_prev_instance, n_instances, stream);
+}
+
+int hrt_denoise_temporal_rebind_geometry(HrtContext *ctx, HrtTraversable next_tlas, const uint32_t *h_prev_instance, uint32_t n_instances, void *stream) {
+    return rebind_history(ctx, "hrt_denoise_temporal_rebind_geometry", true, next_tlas, h_prev_instance, n_instances, stream);
 }
 
 int hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float *d_length, float *d_motion, void *stream) {

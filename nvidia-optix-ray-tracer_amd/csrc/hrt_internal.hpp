@@ -192,6 +192,16 @@ struct DenoiseHistory {
     uint32_t *link = nullptr; uint32_t link_capacity = 0;      // device table, grown on demand
     std::vector<uint32_t> h_link;                               // its staging
     bool link_pending = false; uint64_t link_tlas = 0; uint32_t link_n = 0;
+    // hrt_denoise_temporal_rebind_geometry: next to `link`, per instance of link_tlas the device vertices (Blas::d_verts) of the BLAS its
+    // predecessor had where the instance is linked by primitive, NULL elsewhere.  link_blas owns those BLASes from the rebind until the
+    // link is consumed, replaced or dropped (drop_link), so that hrt_blas_destroy / hrt_tlas_destroy of the old file's objects in
+    // between is harmless.  Releasing the last reference runs ~Blas, whose hipFree waits for the device: the kernel that read the
+    // vertices has finished by then.  link_by_prim: entries linked by primitive (0: the call runs k_denoise_temporal_linked).
+    const float **link_verts = nullptr; uint32_t link_verts_capacity = 0;
+    std::vector<const float *> h_link_verts;
+    std::vector<std::shared_ptr<Blas>> link_blas;
+    uint32_t link_by_prim = 0;
+    void drop_link() { link_pending = false; link_by_prim = 0; link_blas.clear(); }
 };
 
 struct TimedSpan { int kind; hipEvent_t a, b; };
@@ -268,6 +278,7 @@ struct HrtContext {
     hrt::PrimaryCapture capture;
     uint64_t primary_capture_launches = 0;      // path-kernel launches that ran k_path_capture
     uint64_t guide_passes_traced = 0, guide_passes_captured = 0;      // the denoiser's guide passes: traced / served from the capture
+    uint64_t denoise_by_primitive_links = 0;    // instances hrt_denoise_temporal_rebind_geometry has linked by primitive
     uint64_t denoise_history_rebinds = 0;       // temporal / variance calls that began from a linked history (hrt_denoise_temporal_rebind)
     int fused_lpt = 2;                          // samples of the probe launch that orders the slices by cost for the rest of the render (0: off)
     int sample_block = -1;                      // samples a lane takes of a pixel before it gives it back (-1: kSampleBlockAuto where the frame is large enough; 0: off)

@@ -101,6 +101,8 @@ class Renderer:
         self._blas = []
         self._n_inst = None
         self.tlas = None
+        self._built_blas = {}       # BLAS handle -> its normals: the BLASes build_tlas(vertices=...) made
+        self._tlas_blas = {}        # TLAS handle -> those of them it was built over
         self._tlases = {}           # handle -> (host instance array, device instance array, count, SBT records): load_scene's and build_tlas's
         self.states = None
         self.width = self.height = 0
@@ -186,11 +188,14 @@ class Renderer:
         self.set_camera(cam["center"], cam["target"], cam["up"], cam.get("opengl", True))
         return self
 
-    def build_tlas(self, order=None, transforms=None):
+    def build_tlas(self, order=None, transforms=None, vertices=None, normals=None):
         """Another TLAS over the loaded scene's BLASes: instance j is the scene's instance ``order[j]`` (None: all of them in order; a
         subset, a permutation, repeats) with ``transforms[j]`` (12 floats; None: the scene's), sbtOffset j and the material record of
-        its source.  Returns the handle; the renderer stays on the TLAS it was on (use_tlas switches)."""
-        from . import Instance, SbtRecord
+        its source.  ``vertices``: {j: (t, 3, 3) float32} -- instance j gets a triangle BLAS of its own built from these object-space
+        vertices, and a normals buffer of its own, ``normals[j]`` ((t, 3, 3); default scenes.face_normals of the vertices), which its
+        record points at.  The renderer owns those BLASes (destroy_built_blases frees them early, close() the rest).  Returns the
+        handle; the renderer stays on the TLAS it was on (use_tlas switches)."""
+        from . import Instance, SbtRecord, scenes
         n_scene = self._n_scene
         order = list(range(n_scene)) if order is None else [int(k) for k in order]
         n = len(order)
@@ -207,11 +212,39 @@ class Renderer:
             if transforms is not None:
                 for c in range(12):
                     h_inst[j].transform[c] = float(transforms[j][c])
+        own = []
+        for j, v in sorted((vertices or {}).items()):
+            if not 0 <= j < n:
+                raise self._err(f"build_tlas: vertices for instance {j} of {n}")
+            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3, 3)
+            nrm = normals[j] if normals is not None and j in normals else scenes.face_normals(v)
+            nrm = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3, 3)
+            if nrm.shape != v.shape:
+                raise self._err(f"build_tlas: instance {j} has {v.shape[0]} triangles and normals for {nrm.shape[0]}")
+            d_v, d_n = self._dev(v.reshape(-1, 3)), self._dev(nrm.reshape(-1, 3))
+            handle = C.c_uint64()
+            self._check(self.lib.hrt_blas_build_triangles(self.ctx, d_v.data_ptr(), d_v.shape[0], self._stream(), C.byref(handle)),
+                        "hrt_blas_build_triangles")
+            del d_v
+            own.append(handle.value)
+            self._built_blas[handle.value] = d_n           # (the normals live as long as the BLAS does)
+            h_inst[j].traversableHandle = handle.value
+            h_rec[j].data.ptr0 = d_n.data_ptr()
         d_inst = self._dev(np.frombuffer(bytes(h_inst), dtype=np.uint8).copy())
         tl = C.c_uint64()
         self._check(self.lib.hrt_tlas_build(self.ctx, d_inst.data_ptr(), n, self._stream(), C.byref(tl)), "hrt_tlas_build")
         self._tlases[tl.value] = (h_inst, d_inst, n, h_rec)
+        self._tlas_blas[tl.value] = own
         return tl.value
+
+    def destroy_built_blases(self, tlas):
+        """hrt_blas_destroy of the BLASes build_tlas(vertices=...) made for ``tlas``, with their normals.  The TLAS must not be traced
+        afterwards -- destroy it too, or never use it again; a pending denoise_temporal_rebind(by_primitive=True) from it keeps what it
+        reads."""
+        for handle in self._tlas_blas.pop(tlas, []):
+            self._check(self.lib.hrt_blas_destroy(self.ctx, handle), "hrt_blas_destroy")
+            self._torch.cuda.synchronize(self.device)      # (the normals go with the BLAS: no launch that shades with them is in flight)
+            del self._built_blas[handle]
 
     def use_tlas(self, tlas):
         """Render, update and denoise on ``tlas`` (load_scene's or one of build_tlas's) from now on: its instance array and count, and
@@ -410,16 +443,19 @@ class Renderer:
     def denoise_temporal_reset(self):
         self._check(self.lib.hrt_denoise_temporal_reset(self.ctx), "hrt_denoise_temporal_reset")
 
-    def denoise_temporal_rebind(self, tlas, prev_instance=None):
+    def denoise_temporal_rebind(self, tlas, prev_instance=None, by_primitive=False):
         """hrt_denoise_temporal_rebind: the next denoise_temporal / denoise_variance on ``tlas`` continues the history made on the TLAS
         the last one ran on.  prev_instance[i]: the index instance i of ``tlas`` had there, NO_INSTANCE for a new body; None: the
-        identity over the instances both have.  Call before use_tlas / the poses of the next frame or after: the order is free."""
+        identity over the instances both have.  by_primitive: hrt_denoise_temporal_rebind_geometry -- an instance whose BLAS was
+        rebuilt with the same triangles (build_tlas's ``vertices``) keeps its history, primitive by primitive.  Call before use_tlas /
+        the poses of the next frame or after: the order is free."""
         n = self._tlases[tlas][2] if tlas in self._tlases else 0
         arr = None
         if prev_instance is not None:
             arr = (C.c_uint32 * max(len(prev_instance), 1))(*[int(x) for x in prev_instance])
             n = len(prev_instance)
-        self._check(self.lib.hrt_denoise_temporal_rebind(self.ctx, tlas, arr, n, self._stream()), "hrt_denoise_temporal_rebind")
+        name = "hrt_denoise_temporal_rebind_geometry" if by_primitive else "hrt_denoise_temporal_rebind"
+        self._check(getattr(self.lib, name)(self.ctx, tlas, arr, n, self._stream()), name)
 
     def denoise_temporal_state(self):
         """The last denoise_temporal's intermediates: (accumulated colour (H, W, 4), history length (H, W), reprojected position

@@ -9,12 +9,17 @@ k_denoise_variance, k_denoise_pass<3, true>: the same pass kernel's variance for
 --handoff (with --temporal) adds the same call begun from a history handed over from another TLAS every time (hrt_denoise_temporal_rebind
 between two identical trees, alternating): its kernel is k_denoise_temporal_linked, to be set against k_denoise_temporal in the same
 trace; the whole-call figure also pays hrt_materials_set and the material tables of the other tree.
+--by-primitive (with --temporal --handoff) adds the call begun from a history handed over across REBUILT BLASes every time
+(hrt_denoise_temporal_rebind_geometry between two trees in which every second triangle instance -- the only one, in a one-mesh scene --
+has a BLAS of its own, from the scene's vertices): its kernel is k_denoise_temporal_by_prim, with lanes on the rigid and on the
+by-primitive path in the same waves where the scene has both, to be set against k_denoise_temporal_linked in the same trace; with
+--variance as well, both hand-overs are repeated in the variance-guided mode (the kernels' <true> instantiations).
 --capture sets HRT_CTX_CAPTURE_PRIMARY: the render launch runs k_path_capture and the guide pass of every denoise call takes its
 primary hits instead of tracing (guides_ms is then the pass without its traversal).  With or without it, frame_ms is what the switch is
 about -- a 1-spp render and hrt_denoise_launch enqueued back to back, one synchronisation --, and path_kernel_ms the path kernel of
 the render alone, from the context's own HIP events (HRT_CTX_TIMING), so that k_path_capture can be set against k_fused.
 
-    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal [--handoff]] [--variance] [--capture]
+    python tools/denoise_bench.py [--reps 20] [--width 1920 --height 1080] [--scenes c4,sample] [--temporal [--handoff [--by-primitive]]] [--variance] [--capture]
 """
 from __future__ import annotations
 
@@ -50,6 +55,7 @@ def main():
     ap.add_argument("--temporal", action="store_true")
     ap.add_argument("--variance", action="store_true")
     ap.add_argument("--handoff", action="store_true")
+    ap.add_argument("--by-primitive", action="store_true")
     ap.add_argument("--capture", action="store_true")
     args = ap.parse_args()
     import torch
@@ -60,12 +66,13 @@ def main():
         flags = hrt.CTX_CAPTURE_PRIMARY if args.capture else 0
         r = hrt.Renderer(0, flags)
         if name == "c4":
-            r.load_scene(hrt.scenes.BASELINE_CONFIGS["C4"]())
+            scene = hrt.scenes.BASELINE_CONFIGS["C4"]()
+            r.load_scene(scene)
             r.set_frame(w, h, hrt.scenes.SEED_SALT, aov=False)
         else:
             tm = io.time_mode_scene(ROOT / "tests" / "golden" / "files" / "config.json", width=w, height=h)
-            cfg = tm["config"]
-            r.load_scene(tm["scene"])
+            cfg, scene = tm["config"], tm["scene"]
+            r.load_scene(scene)
             r.set_frame(w, h, hrt.scenes.SEED_SALT, aov=False)
             r.pose_instances(tm["states"][0], tm["states"][min(1, len(tm["states"]) - 1)], float(tm["durations"][0]), 0,
                              tm["frame_counts"][0], first_instance=tm["n_extra"], offset=cfg["particle-shift"], scale=cfg["particle-scale"])
@@ -102,6 +109,36 @@ def main():
                 linked()
                 res["denoise_temporal_linked_ms"] = median_ms(torch, linked, args.reps)
                 res["history_rebinds"] = r.stats().denoise_history_rebinds
+                if args.by_primitive:
+                    tri = [j for j, it in enumerate(scene["instances"]) if it["geometry"] == "triangles"]
+                    own = {j: scene["instances"][j]["vertices"] for j in (tri[1::2] if len(tri) > 1 else tri)}
+                    normals = {j: scene["instances"][j]["normals"] for j in own}
+                    rebuilt = [r.build_tlas(None, r.instance_transforms(), vertices=own, normals=normals) for _ in range(2)]
+
+                    def by_primitive():
+                        rebuilt.reverse()
+                        r.denoise_temporal_rebind(rebuilt[0], by_primitive=True)
+                        r.use_tlas(rebuilt[0])
+                        r.denoise_temporal(out=out)
+
+                    by_primitive()
+                    by_primitive()
+                    res["denoise_temporal_by_primitive_ms"] = median_ms(torch, by_primitive, args.reps)
+                    res["by_primitive_instances"] = len(own)
+                    res["by_primitive_links"] = r.stats().denoise_by_primitive_links
+                    if args.variance:      # the same two hand-overs in the variance-guided mode: the kernels' <true> instantiations
+                        def handed_variance(pair, by_prim):
+                            pair.reverse()
+                            r.denoise_temporal_rebind(pair[0], by_primitive=by_prim)
+                            r.use_tlas(pair[0])
+                            r.denoise_variance(out=out)
+
+                        for pair, by_prim, key in ((trees, False, "denoise_variance_linked_ms"), (rebuilt, True, "denoise_variance_by_primitive_ms")):
+                            r.use_tlas(pair[0])
+                            r.denoise_variance(out=out)
+                            handed_variance(pair, by_prim)
+                            res[key] = median_ms(torch, lambda: handed_variance(pair, by_prim), args.reps)
+                    r.use_tlas(trees[0])
         if args.variance:
             var = torch.full((h, w), 1e-3, dtype=torch.float32, device=r.device)
             var_out = torch.empty_like(var)
