@@ -33,6 +33,10 @@ $(LIBDIR)/fused_one.o: $(CSRC)/fused_one.hip $(CSRC)/fused_body.h $(CSRC)/device
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/fused_restart.o: $(CSRC)/fused_restart.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/fused_capture.o: $(CSRC)/fused_capture.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -95,7 +99,7 @@ $(LIBDIR)/bvh8_host_api.o: $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h include/hrt.
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-$(LIBDIR)/libhrt.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/fused_blocks.o $(LIBDIR)/fused_one.o $(LIBDIR)/fused_capture.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o
+$(LIBDIR)/libhrt.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/fused_blocks.o $(LIBDIR)/fused_one.o $(LIBDIR)/fused_restart.o $(LIBDIR)/fused_capture.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 	@cat $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc $(CSRC)/*.hpp $(CSRC)/*.cpp include/*.h)) | sha256sum | cut -c1-16 > $(LIBDIR)/BUILD_ID
 
@@ -136,13 +140,14 @@ clean:
 
 # instrumented build for tools/lane_stats.py: lane-utilisation counters compiled into the path kernels
 stats: $(LIBDIR)/libhrt_stats.so
-$(LIBDIR)/libhrt_stats.so: $(LIBDIR)/fused_queue.o $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/fused_blocks.hip $(CSRC)/fused_one.hip $(CSRC)/fused_capture.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h $(LIBDIR)/libhrt.so
+$(LIBDIR)/libhrt_stats.so: $(LIBDIR)/fused_queue.o $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/fused_blocks.hip $(CSRC)/fused_one.hip $(CSRC)/fused_restart.hip $(CSRC)/fused_capture.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h $(LIBDIR)/libhrt.so
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/kernels.hip -o $(LIBDIR)/kernels_stats.o
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused.hip -o $(LIBDIR)/fused_stats.o
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_blocks.hip -o $(LIBDIR)/fused_blocks_stats.o
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_capture.hip -o $(LIBDIR)/fused_capture_stats.o
 	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_one.hip -o $(LIBDIR)/fused_one_stats.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/kernels_stats.o $(LIBDIR)/fused_stats.o $(LIBDIR)/fused_blocks_stats.o $(LIBDIR)/fused_one_stats.o $(LIBDIR)/fused_capture_stats.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o -pthread
+	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_restart.hip -o $(LIBDIR)/fused_restart_stats.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/kernels_stats.o $(LIBDIR)/fused_stats.o $(LIBDIR)/fused_blocks_stats.o $(LIBDIR)/fused_one_stats.o $(LIBDIR)/fused_restart_stats.o $(LIBDIR)/fused_capture_stats.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o -pthread
 
 # ---- sanitizer build (CPU only; GPU AddressSanitizer is not available and is never attempted): the host-side code that takes
 # untrusted files or builds trees on the host -- the format readers, the host BVH8 builder, the test oracle -- compiled with

@@ -374,7 +374,10 @@ typedef struct HrtStats {
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
     uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
                                               at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
-    uint64_t one_group_launches;           /* of sample_block_launches: those that ran k_path_one, the kernel for a scene with one hit group -- a one-level
+    uint64_t restart_launches;             /* of one_group_launches: those that ran k_path_restart, whose repeat primary rays start at the node of their
+                                              known hit (HRT_PRIMARY_RESTART).  Added ahead of one_group_launches, which
+                                              tests/test_denoise_by_primitive_cpu.py pins in front of the counters below: rebuild against this header */
+    uint64_t one_group_launches;           /* of sample_block_launches: those that ran k_path_one (or k_path_restart, above), the kernel for a scene with one hit group -- a one-level
                                               tree of triangles over exactly one instance (HRT_ONE_GROUP).  Added ahead of the counters below, like
                                               denoise_history_rebinds: rebuild against this header */
     uint64_t denoise_by_primitive_links;   /* instances that hrt_denoise_temporal_rebind_geometry calls since the context was created have linked by
@@ -431,6 +434,13 @@ int  hrt_host_build_bvh8(const float *h_triangles, uint32_t n_triangles, HrtBvhB
 /* Copy the flattened world-space BVH of a TLAS, as it is in device memory now (after any refit), back to
  * the host (same blob format). */
 int  hrt_tlas_download(HrtContext *ctx, HrtTraversable tlas, HrtBvhBlob *out);
+/* The table record -> node of a blob (host only): out[r] = index of the node whose leaf slot covers record r, for the blob's
+ * n_triangles records (capacity: entries of out).  HRT_ERR_STATE when a record is covered by no slot or by two.  It is what the
+ * path kernel's repeat primary rays start from (HRT_PRIMARY_RESTART). */
+int  hrt_host_leaf_parent(const HrtBvhBlob *blob, uint32_t *out, uint64_t capacity);
+/* ... and the same table as the device made it for a TLAS (a one-level tree of triangles; made now if no launch has asked for it yet),
+ * copied to the host: h_out holds capacity entries, *n_records says how many the tree has.  Synchronises the device. */
+int  hrt_tlas_leaf_parent(HrtContext *ctx, HrtTraversable tlas, uint32_t *h_out, uint64_t capacity, uint64_t *n_records);
 void hrt_host_free(HrtBvhBlob *blob);
 
 #ifdef __cplusplus

@@ -83,7 +83,7 @@ class Stats(C.Structure):
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
                 ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
                 ("sample_block_schedule", C.c_uint64 * 4),
-                ("one_group_launches", C.c_uint64), ("denoise_by_primitive_links", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
+                ("restart_launches", C.c_uint64), ("one_group_launches", C.c_uint64), ("denoise_by_primitive_links", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
                 ("primary_capture_launches", C.c_uint64), ("guide_passes_traced", C.c_uint64), ("guide_passes_captured", C.c_uint64)]
 
 
@@ -126,7 +126,7 @@ EXPORTS = [
     "hrt_sbt_record_pack_header", "hrt_materials_set", "hrt_miss_set",
     "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_primary_hits_get", "hrt_to_rgba8", "hrt_color_to_float4",
     "hrt_stats_reset", "hrt_stats_get", "hrt_sample_schedule", "hrt_trace_rays", "hrt_debug_set_linear_output",
-    "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_free", "hrt_debug_trig",
+    "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_leaf_parent", "hrt_tlas_leaf_parent", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
     "hrt_denoise_temporal_rebind", "hrt_denoise_temporal_rebind_geometry",
@@ -194,6 +194,8 @@ def load_library():
     lib.hrt_debug_trig.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     lib.hrt_host_build_bvh8.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BvhBlob)]
     lib.hrt_tlas_download.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BvhBlob)]
+    lib.hrt_host_leaf_parent.argtypes = [C.POINTER(BvhBlob), C.POINTER(C.c_uint32), C.c_uint64]
+    lib.hrt_tlas_leaf_parent.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
     lib.hrt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
     lib.hrt_denoise_guides.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_void_p, C.c_void_p]
     lib.hrt_denoise_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,

@@ -69,6 +69,30 @@ int hrt_host_build_bvh8(const float *h_triangles, uint32_t n_triangles, HrtBvhBl
     return HRT_OK;
 }
 
+// leaf_parent[record] = the node whose leaf slot covers the record (device_types.h: LeafParentArgs; refit.hip's k_leaf_parent makes the same
+// table from the same bytes on the device).  Checks what the kernel takes for granted: every record is covered exactly once.
+int hrt_host_leaf_parent(const HrtBvhBlob *blob, uint32_t *out, uint64_t capacity) {
+    if (!blob || (blob->n_triangles && !out) || (blob->n_nodes && !blob->nodes)) return HRT_ERR_INVALID;
+    if (capacity < blob->n_triangles) return host_fail(HRT_ERR_INVALID, "leaf_parent: room for %llu records, the tree has %llu", (unsigned long long)capacity, (unsigned long long)blob->n_triangles);
+    const uint32_t none = 0xffffffffu;
+    std::fill(out, out + blob->n_triangles, none);
+    const Bvh8Node *nodes = static_cast<const Bvh8Node *>(blob->nodes);
+    for (uint64_t n = 0; n < blob->n_nodes; ++n)
+        for (int slot = 0; slot < 8; ++slot) {
+            const uint32_t meta = nodes[n].meta[slot];
+            if (meta == 0u || (meta & 0x18u) == 0x18u) continue;          // empty, inner
+            const uint64_t first = (uint64_t)nodes[n].prim_base + (meta & 0x1fu);
+            for (uint32_t k = 0, count = (uint32_t)__builtin_popcount(meta >> 5); k < count; ++k) {
+                if (first + k >= blob->n_triangles) return host_fail(HRT_ERR_STATE, "leaf_parent: node %llu slot %d names record %llu of %llu", (unsigned long long)n, slot, (unsigned long long)(first + k), (unsigned long long)blob->n_triangles);
+                if (out[first + k] != none) return host_fail(HRT_ERR_STATE, "leaf_parent: record %llu is covered twice (nodes %u and %llu)", (unsigned long long)(first + k), out[first + k], (unsigned long long)n);
+                out[first + k] = (uint32_t)n;
+            }
+        }
+    for (uint64_t r = 0; r < blob->n_triangles; ++r)
+        if (out[r] == none) return host_fail(HRT_ERR_STATE, "leaf_parent: record %llu is covered by no leaf slot", (unsigned long long)r);
+    return HRT_OK;
+}
+
 void hrt_host_free(HrtBvhBlob *blob) {
     if (!blob) return;
     std::free(blob->nodes); std::free(blob->triangles);

@@ -63,6 +63,8 @@ struct PathArgs {
     uint32_t continue_sum;         // 1: accum already holds the sum of earlier samples of this render
     uint32_t *slice_cost;          // probe launch: per slice of fetch_chunk pixels, the time its pixels' samples took (clock / 16); else NULL
     const uint32_t *slice_order;   // order in which the slices are handed out (most expensive first); NULL: as they lie
+                                   // (k_path_restart, a block render, which has no slice order: the tree's leaf_parent table, one word per record --
+                                   // put here by launch_fused_restart, never by the caller)
     float center[3], U[3], V[3], W[3], bg[3];
     uint32_t block_min;            // sample blocks, tapered: the smallest block (below; in what was padding: the offsets of everything else are as before)
     RngState *states;
@@ -321,6 +323,14 @@ void launch_fused_capture(const TraverseArgs &a, bool has_spheres, bool instance
 // k_path_one (fused_one.hip): the block render of a scene with one hit group.  The caller says what the launch's tree is; false: refused, nothing
 // launched -- whatever launch_fused_blocks would refuse, and any scene but a one-level tree of triangles over exactly one instance
 bool launch_fused_one(const TraverseArgs &a, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
+// k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit.  leaf_parent: the tree's table
+// record -> node (below); false: refused -- whatever launch_fused_one would refuse, no table, or a launch without the window (seed_primary < 2)
+bool launch_fused_restart(const TraverseArgs &a, const uint32_t *leaf_parent, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
+// leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
+// counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
+// primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.
+struct LeafParentArgs { const unsigned char *nodes; uint32_t node_stride, n_nodes, n_records; uint32_t *leaf_parent; };
+void launch_leaf_parent(const LeafParentArgs &a, hipStream_t s);
 void launch_trace_queue(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // k_trace_queue (fused_queue.hip): wavefront mode's traverse kernel, k_fused's traversal over ray queues
 void launch_sum(float4 *accum, const float4 *result, uint32_t n, uint32_t first_sample, hipStream_t s);
 void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s);

@@ -130,9 +130,12 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 // ONE_GROUP: k_path_one (fused_one.hip) -- a block render of triangles of ONE instance: every hit is instance 0's, so the regeneration reads
 // entry 0 of the per-instance tables with scalar loads and keeps no albedo chain (path_lane.h: path_finish), and the loop's primitive test
 // decides ties by the primitive id alone (trav_common.h: test_prim_ray).
-template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false, bool ONE_GROUP = false>
+// RESTART: k_path_restart (fused_restart.hip) -- k_path_one whose repeat primary rays, which already start inside a window under their known hit,
+// also start at the NODE whose leaf slot holds that hit's record instead of at the root (path_lane.h: path_finish).
+template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false, bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    static_assert(!RESTART || ONE_GROUP, "the restart: the one-group block render");
     static_assert(!ONE_GROUP || (BLOCKS && !HAS_SPHERES && !CAPTURE), "one hit group: the block render of a one-level tree of triangles");
     static_assert(!CAPTURE || (!REUSE && !BLOCKS), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
@@ -160,6 +163,9 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     const uint32_t ldsn = (uint32_t)reinterpret_cast<uintptr_t>(&s_nodes[0][tx]), ldsl = (uint32_t)reinterpret_cast<uintptr_t>(&s_leaves[0][tx]);
 
     const Mailboxes mb{s_mb_t, s_mb_u, s_mb_v, s_mb_prim, s_mb_inst, s_mb_pending, s_pair};
+    // RESTART: the node the lane's pixel's next primary ray starts at (0: the root), a word per lane like the seed.  It lives in the mailboxes'
+    // `inst` array, which a one-group kernel only ever filled with zeros and which the RESTART forms of the tail-splitting blocks leave alone.
+    [[maybe_unused]] uint32_t *const s_restart = s_mb_inst;
 
     std::conditional_t<INSTANCED, InstLane, NoInstLane> I;
     if constexpr (INSTANCED) { I.park_idx = s_park_idx; I.park_idy = s_park_idy; I.park_idz = s_park_idz; I.park_oct = s_park_oct; }
@@ -218,9 +224,12 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
+                // (RESTART: s.binst is the record the hit was accepted from, and the walk had a window if it began above the launch's tmin)
+                if constexpr (RESTART) st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP, true>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx, s.binst, s.tlo > tmin, s_restart + tx);
+                else st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
             }
-            exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx);
+            if constexpr (RESTART) exhausted = path_take<BLOCKS, kSeed, true>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx, s_restart + tx);
+            else exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx);
             stats.drained(exhausted);
             if (st.want_primary) {
                 bool from_cache = false;
@@ -242,14 +251,19 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                 // 2 it is bounded from below as well: the same ray has found nothing before that hit, so the node step's interval begins a
                 // window (trav_common.h: kSeedWindow) below it.  Every other ray -- a bounce, a first sample, after a miss (the seed says
                 // tmax), a caller's ray -- begins at the launch's tmin.
+                // RESTART: ... and a ray that got a window starts at the node its predecessor left for it (s_restart: the root unless that ray
+                // accepted its hit itself, inside the same window) -- still launched, counted and decided by the canonical primitive test.
                 float hi = tmax_ray, lo = tmin;
+                [[maybe_unused]] uint32_t first_node = 0u;
                 if constexpr (kSeed) {
                     if (st.want_primary) {
                         hi = s_seed[tx];
                         if (a.seed_primary >= 2 && hi < tmax_ray) lo = seed_window_lo(st.rd, hi, tmin);
+                        if constexpr (RESTART) { if (a.seed_primary >= 2 && hi < tmax_ray) first_node = s_restart[tx]; }
                     }
                 }
                 lean_start(L, st.ro, st.rd, hi, lo);
+                if constexpr (RESTART) L.nidx = first_node;
                 if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
             }
             // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
@@ -301,10 +315,14 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         //      and the drained phase's exit rule runs once the tile is used up ----
         if (exhausted) {
             stats.tail_begin();
-            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed, ONE_GROUP>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed, ONE_GROUP, RESTART>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
             stats.tail_end();
+            // RESTART: s_waitcnt lgkmcnt(0) -- the drained copy's last block (tail_retire) takes a merged hit out of the mailboxes, and as the
+            // registers fall in this kernel the compiler lets those LDS reads fly out of that loop.  To the compiler `exhausted` may turn false
+            // again, so it then waits for them INSIDE the other copy of the loop, which this path can never reach: two s_waitcnt per iteration.
+            if constexpr (RESTART) __builtin_amdgcn_s_waitcnt(0xc07f);
         }
-        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed, ONE_GROUP>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed, ONE_GROUP, RESTART>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
     const TraverseArgs &k = kernarg_traverse_args();          // (the counters' addresses need not live in registers until here)
     stats.report(k.path.rays_closest, tx);

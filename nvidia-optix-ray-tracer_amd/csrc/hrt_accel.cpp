@@ -35,6 +35,23 @@ void free_tlas_device(HrtContext *ctx, Tlas &t) {
     d = TlasDevice();
     t.area_pending = false;
 }
+// The table record -> node of a one-level tree of triangles (device_types.h: LeafParentArgs), which k_path_restart starts a pixel's repeat
+// primary rays from.  Made from the finished nodes, once per tree: every builder leaves a new TlasDevice behind (build_tlas_fresh frees first,
+// a rebuild swaps a fresh Tlas in), so a tree without the table is a tree nobody has asked yet; a refit rewrites boxes and records in
+// place and keeps both the topology and the record order.  Filled with the root first, so that a record no slot names sends its ray
+// the long way instead of anywhere else.  The stream is synchronised once, here: launches on other streams may read the table next.
+int ensure_leaf_parent(HrtContext *ctx, Tlas &t, hipStream_t s) {
+    TlasDevice &d = t.dev;
+    if (d.d_leaf_parent || t.n_prims == 0u || t.n_nodes == 0u) return HRT_OK;
+    if (t.two_level || t.has_spheres) return fail(ctx, HRT_ERR_STATE, "leaf_parent: one-level trees of triangles only");
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_leaf_parent, sizeof(uint32_t) * (size_t)t.n_prims));
+    HIP_TRY(ctx, hipMemsetAsync(d.d_leaf_parent, 0, sizeof(uint32_t) * (size_t)t.n_prims, s));
+    LeafParentArgs la{reinterpret_cast<const unsigned char *>(d.d_nodes), t.node_stride, t.n_nodes, t.n_prims, d.d_leaf_parent};
+    launch_leaf_parent(la, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return HRT_OK;
+}
 void free_tlas_host(Tlas &t) {
     if (t.h_area) (void)hipHostFree(t.h_area);
     if (t.h_update_flags) (void)hipHostFree(t.h_update_flags);
@@ -1289,6 +1306,21 @@ int hrt_tlas_download(HrtContext *ctx, HrtTraversable tlas, HrtBvhBlob *out) {
     const size_t n_nodes = t->n_nodes, n_prims = t->n_prims;
     HIP_TRY(ctx, hipMemcpy2D(out->nodes, sizeof(Bvh8Node), t->dev.d_nodes, t->node_stride, sizeof(Bvh8Node), n_nodes, hipMemcpyDeviceToHost));
     if (n_prims) HIP_TRY(ctx, hipMemcpy2D(out->triangles, sizeof(PrimRecord), t->dev.d_prims, t->prim_stride, sizeof(PrimRecord), n_prims, hipMemcpyDeviceToHost));
+    return HRT_OK;
+}
+
+int hrt_tlas_leaf_parent(HrtContext *ctx, HrtTraversable tlas, uint32_t *h_out, uint64_t capacity, uint64_t *n_records) {
+    if (!ctx || !n_records) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    Tlas *t;
+    { std::lock_guard<std::mutex> lk(ctx->mu); auto it = ctx->tlas.find(tlas); if (it == ctx->tlas.end()) return fail(ctx, HRT_ERR_INVALID, "unknown TLAS handle"); t = it->second.get(); }
+    if (t->two_level || t->has_spheres) return fail(ctx, HRT_ERR_STATE, "leaf_parent: a one-level tree of triangles has the table, this one is %s", t->two_level ? "a two-level tree" : "a tree with spheres");
+    *n_records = t->n_prims;
+    if (capacity < t->n_prims || (t->n_prims && !h_out)) return fail(ctx, HRT_ERR_INVALID, "leaf_parent: room for %llu records, the tree has %u", (unsigned long long)capacity, t->n_prims);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const int rc = ensure_leaf_parent(ctx, *t, nullptr);
+    if (rc != HRT_OK) return rc;
+    if (t->n_prims) HIP_TRY(ctx, hipMemcpy(h_out, t->dev.d_leaf_parent, sizeof(uint32_t) * (size_t)t->n_prims, hipMemcpyDeviceToHost));
     return HRT_OK;
 }
 

@@ -555,9 +555,23 @@ static int render_fused(const LaunchFrame &f) {
             // render -- takes k_path_one (fused_one.hip; HRT_ONE_GROUP=0: k_path_blocks like everything else).  Decided here, per launch,
             // from the tree that is launched: an update that adds an instance sends the next launch back to k_path_blocks.
             const bool one_group = blocks && ctx->one_group && !t->two_level && t->n_instances == 1u && !t->has_spheres;
+            // ... and, where its repeat primary rays get their window (HRT_SEED_PRIMARY=2), k_path_restart (fused_restart.hip), which also starts
+            // them at the node of their known hit: it wants the tree's leaf_parent table, made here the first time (HRT_PRIMARY_RESTART=0, or a
+            // tree without records: k_path_one, the launch as it was).
+            bool restart = one_group && ctx->primary_restart && ta.seed_primary == 2;
+            if (restart) {
+                const int rc = ensure_leaf_parent(ctx, *t, s);
+                if (rc != HRT_OK) return rc;
+                restart = t->dev.d_leaf_parent != nullptr;
+            }
             bool admitted;
-            { Timer tm(ctx, s, HRT_K_PATHS); admitted = one_group ? launch_fused_one(ta, !t->two_level, t->n_instances, t->has_spheres, grid, s) : launch(); }
+            {
+                Timer tm(ctx, s, HRT_K_PATHS);
+                admitted = restart ? launch_fused_restart(ta, t->dev.d_leaf_parent, !t->two_level, t->n_instances, t->has_spheres, grid, s)
+                         : one_group ? launch_fused_one(ta, !t->two_level, t->n_instances, t->has_spheres, grid, s) : launch();
+            }
             if (admitted && one_group) ctx->one_group_launches++;
+            if (admitted && restart) ctx->restart_launches++;
             if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
         }
         done_spp += now;
@@ -919,7 +933,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
     out->denoise_history_rebinds = ctx->denoise_history_rebinds;
     out->denoise_by_primitive_links = ctx->denoise_by_primitive_links;
-    out->one_group_launches = ctx->one_group_launches;
+    out->one_group_launches = ctx->one_group_launches; out->restart_launches = ctx->restart_launches;
     return HRT_OK;
 }
 

@@ -74,6 +74,8 @@ struct TlasDevice {
     unsigned long long *d_sig_handle = nullptr; uint32_t *d_sig_visibility = nullptr, *d_sig_sbt = nullptr; float *d_blas_box = nullptr;
     uint32_t *d_update_flags = nullptr;                  // [0] scene scale (float bits), [1] bit 0: handle / visibility changed, bit 1: an sbtOffset changed
     float *d_rec_box = nullptr;                          // small trees: 6 floats per record, the refit's per-record pass (refit.hip k_refit_records)
+    uint32_t *d_leaf_parent = nullptr;                   // one-level trees of triangles: per record, the node whose leaf slot covers it (ensure_leaf_parent: made at the first launch that wants
+                                                         // it; a refit keeps topology and record order, hence the table; a rebuild is a new Tlas and starts without one)
 };
 static_assert(std::is_standard_layout<TlasDevice>::value && std::is_trivially_copyable<TlasDevice>::value && sizeof(TlasDevice) % sizeof(void *) == 0,
               "TlasDevice holds pool blocks only: free_tlas_device walks it as an array of pointers");
@@ -285,6 +287,8 @@ struct HrtContext {
     uint64_t sample_block_launches = 0;         // path-kernel launches that handed pixels out in sample blocks
     bool one_group = true;                      // HRT_ONE_GROUP: a launch in sample blocks of a one-level tree of triangles over exactly one instance runs k_path_one (fused_one.hip)
     uint64_t one_group_launches = 0;            // ... and how many did
+    bool primary_restart = true;                // HRT_PRIMARY_RESTART: ... of those, the launches with the seed window (seed_primary == 2) run k_path_restart (fused_restart.hip) over the tree's leaf_parent table
+    uint64_t restart_launches = 0;              // ... and how many did
     int taper_big = kSampleTaperBig, taper_min = kSampleTaperMin;      // HRT_SAMPLE_TAPER: what `auto` hands out -- blocks that start at taper_big samples and end on taper_min (0: uniform blocks of kSampleBlockAuto)
     bool taper_forced = false;                  // ... whatever the tile, like HRT_SAMPLE_BLOCK=N (tests)
     uint32_t last_schedule[4] = {0u, 0u, 0u, 0u};      // the last launch in sample blocks: largest block, smallest block, end of the halvings (0: uniform), passes
@@ -390,5 +394,6 @@ void pool_drain(HrtContext *ctx);
 // hrt_accel.cpp
 void free_tlas_device(HrtContext *ctx, Tlas &t);
 void free_tlas_host(Tlas &t);
+int ensure_leaf_parent(HrtContext *ctx, Tlas &t, hipStream_t s);      // Tlas::dev.d_leaf_parent, made on `s` if the tree has none yet (enqueued only)
 
 }  // namespace hrt

@@ -142,9 +142,18 @@ __device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_
 // leaves its hit record in frame order, in hrt_trace_rays' form (a miss: tmax, kMissPrim), where the denoiser's guide pass and
 // hrt_primary_hits_get find it.  PathArgs::trace_tuvp / trace_inst are free in a render (trace_rays == NULL) and carry the two arrays.
 // ONE_GROUP: see above -- `binst` is 0, `px_chain` is neither written nor read.
-template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false, bool ONE_GROUP = false>
+// RESTART (k_path_restart, fused_restart.hip; DESIGN.md section 4.1 "The start under the known hit"): a primary ray that ends in a hit leaves, in
+// the lane's word `restart` of LDS, the node the pixel's next primary ray starts at instead of the root: leaf_parent[brec], the node whose
+// leaf slot holds the record the hit was accepted from (`brec`; the table rides in PathArgs::slice_order, which a block render does not
+// have).  Only where `restartable` -- the lane accepted the hit itself (brec != kNoWork) in a walk that had the window the next one will
+// have, so that the node step of that node passes the slot again, bit for bit; everything else leaves 0, the root.  The table's load goes
+// out in front of the normals', on the same round trip.
+typedef const __attribute__((address_space(1))) uint32_t *global_words;
+template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false, bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
-                                            [[maybe_unused]] float *seed = nullptr) {
+                                            [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t brec = 0u, [[maybe_unused]] bool restartable = false,
+                                            [[maybe_unused]] uint32_t *restart = nullptr) {
+    static_assert(!RESTART || (ONE_GROUP && SEED), "the restart: the one-group block render, whose repeat primary rays have a window");
     PathStep st;
     const bool miss = bprim == kMissPrim;
     if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
@@ -208,8 +217,16 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
         HitGroup hg;
         hg.ptr0 = hp0->ptr0; hg.ptr1 = nullptr; hg.albedo[0] = hg.albedo[1] = hg.albedo[2] = 0.0f; hg.fuzz = hp0->fuzz;      // (what a triangle program reads)
         const uint32_t program = *(constant_words)a.path.inst_program;
+        [[maybe_unused]] uint32_t node = 0u;
+        if constexpr (RESTART) {
+            // (no branch: every lane here loads -- entry 0 where it has nothing to look up -- and keeps the word or 0)
+            const bool look = P.px_depth == 1u && restartable && brec != kMissPrim;
+            node = ((global_words)a.path.slice_order)[look ? brec : 0u];
+            node = look ? node : 0u;
+        }
         V3 hp, nd;
         scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
+        if constexpr (RESTART) { if (P.px_depth == 1u) *restart = node; }
         ++P.px_depth;
         st.ro = hp; st.rd = nd; st.launch = true;
     } else {
@@ -232,10 +249,12 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // i / slices of slice i % slices, and an item of a later pass waits for its predecessor: while the slice's progress word says that pixels of
 // (b - 1, q) are still under way the wave keeps the item, starts none of its pixels and looks again at its next regeneration.  It never
 // waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
-template <bool BLOCKS = false, bool SEED = false>
+// RESTART (path_finish): a pixel just taken has no restart node -- the word in LDS is the lane's previous pixel's, while the seed (BLOCKS, a
+// pass b > 0) comes with the pixel and switches the window on: a block's first primary ray walks from the root, inside its window.
+template <bool BLOCKS = false, bool SEED = false, bool RESTART = false>
 __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
                                           bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
-                                          [[maybe_unused]] float *seed = nullptr) {
+                                          [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t *restart = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
         constexpr bool by_blocks = BLOCKS;      // (launch_fused_blocks: sample_block != 0)
@@ -283,6 +302,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
                 if constexpr (SEED && !BLOCKS) *seed = a.tmax;
+                if constexpr (RESTART) *restart = 0u;
                 [[maybe_unused]] float carried = 0.0f;      // (BLOCKS) the seed the pixel brings along
                 if (BLOCKS || !a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;

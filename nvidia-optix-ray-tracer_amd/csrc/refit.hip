@@ -307,6 +307,27 @@ void launch_pack_blas(const PackBlasArgs &a, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_pack_blas, dim3((n + 255u) / 256u), dim3(256), 0, s, a);
 }
 
+// ---- leaf_parent (device_types.h: LeafParentArgs): one thread per (node, slot) of a finished one-level tree.  A leaf slot names its records --
+// the node's primitive base + the meta byte's offset (bits 4..0), as many as the unary count (bits 7..5: 1, 3, 7) has bits -- and writes its
+// node's index for each; inner slots (meta bits 4 and 3 both set, bvh8.h) and empty ones (0) write nothing.  Every record has exactly one slot,
+// so nothing is written twice; a record number past the table (a damaged node) is not written at all. ----
+__global__ __launch_bounds__(256) void k_leaf_parent(LeafParentArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t node = (uint32_t)(i >> 3), slot = (uint32_t)i & 7u;
+    if ((i >> 3) >= (uint64_t)a.n_nodes) return;
+    const unsigned char *nb = a.nodes + (size_t)node * a.node_stride;
+    const uint32_t meta = nb[24u + slot];
+    if (meta == 0u || (meta & 0x18u) == 0x18u) return;
+    const uint32_t first = reinterpret_cast<const uint32_t *>(nb)[5] + (meta & 0x1fu), count = (uint32_t)__popc(meta >> 5);
+    for (uint32_t k = 0; k < count; ++k)
+        if (first + k < a.n_records) a.leaf_parent[first + k] = node;
+}
+void launch_leaf_parent(const LeafParentArgs &a, hipStream_t s) {
+    if (a.n_nodes == 0u || a.n_records == 0u) return;
+    const uint64_t threads = (uint64_t)a.n_nodes * 8u;
+    hipLaunchKernelGGL(k_leaf_parent, dim3((uint32_t)((threads + 255u) / 256u)), dim3(256), 0, s, a);
+}
+
 void launch_refit_level(const RefitArgs &a, hipStream_t s) {
     if (a.n_nodes == 0) return;
     const uint32_t threads = a.n_nodes * 8u;

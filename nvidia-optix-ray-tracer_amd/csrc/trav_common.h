@@ -301,12 +301,16 @@ __device__ __forceinline__ bool cond_lane(WaveCond c) { return __builtin_amdgcn_
 // ONE_GROUP (k_path_one, fused_one.hip: triangles of ONE instance): every record's instance is 0, so it is not read from the record, a
 // tie at the same distance goes to the lower primitive id -- what the (instance, primitive) order says when both instances are 0; a
 // ray that has no hit yet holds bprim == kMissPrim, above every id -- and TravState::binst is left alone: whoever reads it takes 0.
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false>
+// RESTART (k_path_restart, fused_restart.hip: ONE_GROUP, whose TravState::binst is free): binst keeps the RECORD the best hit was accepted from
+// (`rec`: the record's index, the lane's pidx) -- kMissPrim, which trav_start leaves there, where the lane has accepted none itself.  The
+// regeneration looks up the node whose leaf slot holds that record, where the pixel's next primary ray starts (fused_body.h: s_restart).
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
                                               const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
-                                              Cond live = true) {
+                                              Cond live = true, [[maybe_unused]] uint32_t rec = 0u) {
     static_assert(!HAS_SPHERES || sizeof(Cond) == sizeof(bool), "spheres are tested under per-lane control flow");
+    static_assert(!RESTART || ONE_GROUP, "the record rides in binst, which only the one-group kernels leave free");
     float t, u = 0.0f, v = 0.0f;
     uint32_t prim = __float_as_uint(A.w), inst;
     if (HAS_SPHERES && __float_as_uint(C.w) == 1u) {
@@ -358,6 +362,7 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
             const bool mine = cond_lane(better);
             s.bt = mine ? t : s.bt; s.bu = mine ? u : s.bu; s.bv = mine ? v : s.bv;
             s.bprim = mine ? prim : s.bprim;
+            if constexpr (RESTART) s.binst = mine ? rec : s.binst;
             return better;
         }
         if (!HAS_SPHERES) {
@@ -380,12 +385,12 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
     return better;
 }
 
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false>
+template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ Cond test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
                                           const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
-                                          Cond live = true) {
-    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond, ONE_GROUP>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live);
+                                          Cond live = true, uint32_t rec = 0u) {
+    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond, ONE_GROUP, RESTART>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live, rec);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))

@@ -65,7 +65,10 @@ struct NoInstLane { static constexpr uint32_t inst_cur = 0u; };
 // (one donation per busy lane and iteration: more rounds of this change nothing, r02_sweep_tile_tail.txt)
 // ONE_GROUP, here and in the three blocks below (k_path_one, fused_one.hip): every hit is instance 0's, so TravState::binst is not kept --
 // a mailbox's `inst` is given 0, and nobody takes a lane's binst from there.
-template <bool ONE_GROUP = false>
+// RESTART (k_path_restart, fused_restart.hip: ONE_GROUP with the best hit's record in binst, trav_common.h: test_prim_ray): the mailboxes' `inst`
+// array is not theirs any more -- it holds the lanes' restart nodes (fused_body.h: s_restart) -- so it is neither written nor read here, and a
+// hit that comes out of a mailbox has no record: binst = kNoWork, the pixel's next primary ray walks from the root.
+template <bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmin, float tmax_ray) {
     const uint64_t free_m = __ballot(is_free);
     const uint64_t donors = F.alive & __ballot(L.nsp > L.base);
@@ -82,7 +85,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
             if (!F.shared) {
                 F.shared = true; F.home = tx;
                 mb.t[tx] = L.s.bt; mb.u[tx] = L.s.bu; mb.v[tx] = L.s.bv; mb.prim[tx] = L.s.bprim;
-                mb.inst[tx] = ONE_GROUP ? 0u : L.s.binst;
+                if constexpr (!RESTART) mb.inst[tx] = ONE_GROUP ? 0u : L.s.binst;
                 mb.pending[tx] = 2u;
             } else atomicAdd(&mb.pending[F.home], 1u);
             mb.pair[drank] = tx;
@@ -110,7 +113,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
 }
 
 // pieces of split rays publish their improvements one lane at a time (rare: a few per ray) ...
-template <bool ONE_GROUP = false>
+template <bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool improved, uint32_t tx) {
     uint64_t pub = __ballot(improved && F.shared);
     while (pub) {
@@ -119,11 +122,11 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
         if (tx == l) {
             const TravState &s = L.s;
             const float mt = mb.t[F.home];
-            const uint64_t mid = ((uint64_t)mb.inst[F.home] << 32) | mb.prim[F.home];
+            const uint64_t mid = ((uint64_t)(RESTART ? 0u : mb.inst[F.home]) << 32) | mb.prim[F.home];
             const uint64_t id = ((uint64_t)(ONE_GROUP ? 0u : s.binst) << 32) | s.bprim;
             if (lane_bit(F.any) ? mb.prim[F.home] == kMissPrim : (s.bt < mt || (s.bt == mt && id < mid))) {
                 mb.t[F.home] = s.bt; mb.u[F.home] = s.bu; mb.v[F.home] = s.bv; mb.prim[F.home] = s.bprim;
-                mb.inst[F.home] = ONE_GROUP ? 0u : s.binst;
+                if constexpr (!RESTART) mb.inst[F.home] = ONE_GROUP ? 0u : s.binst;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -133,20 +136,21 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
 
 // ... and take over what another piece has found closer; an any-hit ray is done once any piece has hit.  Returns the lane's hit_any
 // (by value on purpose: as a `bool &` it cost each one-level k_fused three more spilled registers)
-template <bool ONE_GROUP = false>
+template <bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ bool tail_adopt(LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool hit_any) {
     if (lane_bit(F.alive) && F.shared) {
         if (lane_bit(F.any)) hit_any = hit_any || mb.prim[F.home] != kMissPrim;
         else if (mb.t[F.home] < L.s.bt) {
             L.s.bt = mb.t[F.home]; L.s.bu = mb.u[F.home]; L.s.bv = mb.v[F.home]; L.s.bprim = mb.prim[F.home];
             if constexpr (!ONE_GROUP) L.s.binst = mb.inst[F.home];
+            if constexpr (RESTART) L.s.binst = kNoWork;
         }
     }
     return hit_any;
 }
 
 // a piece whose lane reports `done` retires; the owner of the ray takes the merged hit once the last piece has
-template <bool ONE_GROUP = false>
+template <bool ONE_GROUP = false, bool RESTART = false>
 __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mailboxes &mb, bool done, uint32_t tx) {
     // a piece that has finished has nothing left to merge: the mailbox holds the ray's best hit
     const bool retires = lane_bit(F.alive) && done && F.shared;
@@ -162,6 +166,7 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
     if (merged) {
         L.s.bt = mb.t[tx]; L.s.bu = mb.u[tx]; L.s.bv = mb.v[tx]; L.s.bprim = mb.prim[tx];
         if constexpr (!ONE_GROUP) L.s.binst = mb.inst[tx];
+        if constexpr (RESTART) L.s.binst = kNoWork;
         F.shared = false;
     }
     F.waiting |= __ballot(merged);
@@ -178,7 +183,8 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
 // kLaneLo: the node step's interval begins at the lane's TravState::tlo (the kernels that give repeat primary rays a window) instead of the
 // wave-uniform tmin -- the same instructions, one operand a vector register where it was a scalar one.
 // ONE_GROUP (k_path_one): the primitive test and the tail-splitting blocks in their one-instance forms (trav_common.h: test_prim_ray).
-template <bool HAS_SPHERES, bool INSTANCED, bool kTail, bool kLaneLo = false, bool ONE_GROUP = false, class Inst>
+// RESTART (k_path_restart): ... which also keep the record of the lane's best hit (the primitive test is told the record it tests: pidx).
+template <bool HAS_SPHERES, bool INSTANCED, bool kTail, bool kLaneLo = false, bool ONE_GROUP = false, bool RESTART = false, class Inst>
 __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Inst &I, LaneStats &stats, const Mailboxes &mb,
                                                   uint2 (*nodes)[kTraverseBlock], uint2 (*leaves)[kTraverseBlock], uint32_t ldsn, uint32_t ldsl,
                                                   const TraverseArgs &a, const char *node_bytes, const char *prim_bytes,
@@ -206,7 +212,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
     F.alive = wave_first_u64(F.alive); F.waiting = wave_first_u64(F.waiting); F.any = wave_first_u64(F.any);
     uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
     for (;;) {
-        if (kSplit && a.tail_split) tail_donate<ONE_GROUP>(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmin, tmax_ray);
+        if (kSplit && a.tail_split) tail_donate<ONE_GROUP, RESTART>(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmin, tmax_ray);
 
         // ---- G. fetch what the lanes need next: primitives first, nodes second -- for the lanes that need one only (the
         //      instruction slots of the loads are not saved, but their L1 / TA cycles are).  The node loads are issued even when
@@ -235,7 +241,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
                          pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
             if constexpr (!HAS_SPHERES)
-                improved_m = test_prim<false, INSTANCED, WaveCond, ONE_GROUP>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p)).m;
+                improved_m = test_prim<false, INSTANCED, WaveCond, ONE_GROUP, RESTART>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p), L.pidx).m;
             else {
                 bool improved = false;
                 if (L.pidx != kNoWork) improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
@@ -244,8 +250,8 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             hit_m = F.any & improved_m;
         }
         if (kSplit && a.tail_split) {
-            tail_publish<ONE_GROUP>(L, F, mb, lane_bit(improved_m), tx);
-            hit_m = __ballot(tail_adopt<ONE_GROUP>(L, F, mb, lane_bit(hit_m)));
+            tail_publish<ONE_GROUP, RESTART>(L, F, mb, lane_bit(improved_m), tx);
+            hit_m = __ballot(tail_adopt<ONE_GROUP, RESTART>(L, F, mb, lane_bit(hit_m)));
         }
         const bool hit_any = lane_bit(hit_m);
         // ---- A. node step: one-level trees, for the whole wave (arithmetic only; what lanes without a node made of their
@@ -291,7 +297,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         // (a piece of a split ray does not wait for a regeneration: tail_retire signs it off.  Only tail_donate shares rays)
         const uint64_t rest = kSplit ? done_m & ~__ballot(F.shared) : done_m;
         F.alive &= ~rest; F.waiting |= rest;
-        if (kSplit && a.tail_split) tail_retire<ONE_GROUP>(L, F, mb, lane_bit(done_m), tx);
+        if (kSplit && a.tail_split) tail_retire<ONE_GROUP, RESTART>(L, F, mb, lane_bit(done_m), tx);
         if constexpr (kTail) {
             if (F.alive == 0ull || (uint32_t)__popcll(F.waiting) >= (uint32_t)a.tail_regen) break;
         } else if ((uint32_t)__popcll(F.alive) <= max_alive) break;      // (every lane finished included)
