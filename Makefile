@@ -17,31 +17,11 @@ all: lib oracle tools
 
 lib: $(LIBDIR)/libhrt.so $(LIBDIR)/libhrt_io.so
 
-$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused.o: $(CSRC)/fused.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused_blocks.o: $(CSRC)/fused_blocks.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused_one.o: $(CSRC)/fused_one.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused_restart.o: $(CSRC)/fused_restart.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused_capture.o: $(CSRC)/fused_capture.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/fused_queue.o: $(CSRC)/fused_queue.hip $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h
+# the path kernels: one translation unit per kernel over the shared headers (trav_common.h, PathVariant: what each one is)
+PATH_UNITS := kernels fused fused_blocks fused_one fused_restart fused_capture fused_queue
+PATH_HDRS  := $(addprefix $(CSRC)/,device_types.h srgb_pow.h trav_common.h trav_lean.h trav_loop.h path_lane.h fused_body.h)
+PATH_OBJS  := $(PATH_UNITS:%=$(LIBDIR)/%.o)
+$(PATH_OBJS): $(LIBDIR)/%.o: $(CSRC)/%.hip $(PATH_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -99,7 +79,8 @@ $(LIBDIR)/bvh8_host_api.o: $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h include/hrt.
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-$(LIBDIR)/libhrt.so: $(LIBDIR)/kernels.o $(LIBDIR)/fused.o $(LIBDIR)/fused_blocks.o $(LIBDIR)/fused_one.o $(LIBDIR)/fused_restart.o $(LIBDIR)/fused_capture.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o
+OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o refit.o pose.o denoise.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
+$(LIBDIR)/libhrt.so: $(PATH_OBJS) $(OTHER_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 	@cat $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc $(CSRC)/*.hpp $(CSRC)/*.cpp include/*.h)) | sha256sum | cut -c1-16 > $(LIBDIR)/BUILD_ID
 
@@ -140,14 +121,13 @@ clean:
 
 # instrumented build for tools/lane_stats.py: lane-utilisation counters compiled into the path kernels
 stats: $(LIBDIR)/libhrt_stats.so
-$(LIBDIR)/libhrt_stats.so: $(LIBDIR)/fused_queue.o $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/fused_blocks.hip $(CSRC)/fused_one.hip $(CSRC)/fused_restart.hip $(CSRC)/fused_capture.hip $(CSRC)/fused_body.h $(CSRC)/device_types.h $(CSRC)/srgb_pow.h $(CSRC)/trav_common.h $(CSRC)/trav_lean.h $(CSRC)/trav_loop.h $(CSRC)/path_lane.h $(LIBDIR)/libhrt.so
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/kernels.hip -o $(LIBDIR)/kernels_stats.o
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused.hip -o $(LIBDIR)/fused_stats.o
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_blocks.hip -o $(LIBDIR)/fused_blocks_stats.o
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_capture.hip -o $(LIBDIR)/fused_capture_stats.o
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_one.hip -o $(LIBDIR)/fused_one_stats.o
-	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $(CSRC)/fused_restart.hip -o $(LIBDIR)/fused_restart_stats.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(LIBDIR)/kernels_stats.o $(LIBDIR)/fused_stats.o $(LIBDIR)/fused_blocks_stats.o $(LIBDIR)/fused_one_stats.o $(LIBDIR)/fused_restart_stats.o $(LIBDIR)/fused_capture_stats.o $(LIBDIR)/fused_queue.o $(LIBDIR)/build.o $(LIBDIR)/build_split.o $(LIBDIR)/refit.o $(LIBDIR)/pose.o $(LIBDIR)/denoise.o $(LIBDIR)/denoise_link.o $(LIBDIR)/denoise_link_prim.o $(LIBDIR)/hrt_api.o $(LIBDIR)/hrt_denoise.o $(LIBDIR)/hrt_accel.o $(LIBDIR)/hrt_mem.o $(LIBDIR)/bvh8_build.o $(LIBDIR)/bvh8_host_api.o -pthread
+STATS_UNITS := $(filter-out fused_queue,$(PATH_UNITS))      # (k_trace_queue has no counters: its object is the product's)
+STATS_OBJS  := $(STATS_UNITS:%=$(LIBDIR)/%_stats.o)
+$(STATS_OBJS): $(LIBDIR)/%_stats.o: $(CSRC)/%.hip $(PATH_HDRS)
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -DHRT_LANE_STATS -c $< -o $@
+$(LIBDIR)/libhrt_stats.so: $(STATS_OBJS) $(LIBDIR)/fused_queue.o $(LIBDIR)/libhrt.so
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(STATS_OBJS) $(LIBDIR)/fused_queue.o $(OTHER_OBJS) -pthread
 
 # ---- sanitizer build (CPU only; GPU AddressSanitizer is not available and is never attempted): the host-side code that takes
 # untrusted files or builds trees on the host -- the format readers, the host BVH8 builder, the test oracle -- compiled with

@@ -64,7 +64,7 @@ struct PathArgs {
     uint32_t *slice_cost;          // probe launch: per slice of fetch_chunk pixels, the time its pixels' samples took (clock / 16); else NULL
     const uint32_t *slice_order;   // order in which the slices are handed out (most expensive first); NULL: as they lie
                                    // (k_path_restart, a block render, which has no slice order: the tree's leaf_parent table, one word per record --
-                                   // put here by launch_fused_restart, never by the caller)
+                                   // put here by the restart launch, fused_restart.hip, never by the caller)
     float center[3], U[3], V[3], W[3], bg[3];
     uint32_t block_min;            // sample blocks, tapered: the smallest block (below; in what was padding: the offsets of everything else are as before)
     RngState *states;
@@ -307,7 +307,6 @@ void launch_denoise_pass(const DenoisePassArgs &a, hipStream_t s);
 void launch_rng_init(RngState *states, uint32_t n, uint64_t salt, const uint32_t *d_jump, hipStream_t s);
 void launch_generate(const GenerateArgs &a, hipStream_t s);
 void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
-void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);   // round 1's fused kernel k_traverse<.., FUSED>: trees k_fused cannot take
 constexpr int kSampleBlockAuto = 32;   // HRT_SAMPLE_BLOCK=auto with HRT_SAMPLE_TAPER=0: samples per block (profiles/r13_sample_blocks.txt); with a taper: `auto` wants 2 x this many samples in a launch
 constexpr int kSampleTaperBig = 64, kSampleTaperMin = 8;   // HRT_SAMPLE_TAPER: the largest and the smallest block of the tapered schedule (profiles/r19_sample_taper.txt)
 constexpr int kFusedBlocksPerCu = 16;  // k_fused is compiled for 4 waves per SIMD (125 VGPRs, nothing spilled): more workgroups per CU would only queue
@@ -317,15 +316,38 @@ constexpr uint32_t kFetchShardStride = 32;   // u32s between counters: one 128-b
 constexpr int kFusedMaxDepth = 12;     // deepest tree (levels below the root) k_fused takes: its per-lane node stack in LDS (trav_lean.h: kNodeStackLds)
 constexpr uint32_t kTraversalStackEntries = 64;   // per-lane stack of round 1's kernels, which take what k_fused cannot (trav_common.h: kLdsStack + kSpillStack); a tree of
                                                   // depth d needs 2 d + 2 of them, and a build that comes out deeper fails (hrt_accel.cpp)
-bool launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);                // false: the launch was refused (fused.hip: sample blocks with a mode k_path_blocks does not have)
-bool launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // two-level trees (transform nodes, bvh8.h)
-void launch_fused_capture(const TraverseArgs &a, bool has_spheres, bool instanced, uint32_t grid_blocks, hipStream_t s);   // k_path_capture (fused_capture.hip): k_fused<S, I, false> that also keeps every pixel's primary hit
-// k_path_one (fused_one.hip): the block render of a scene with one hit group.  The caller says what the launch's tree is; false: refused, nothing
-// launched -- whatever launch_fused_blocks would refuse, and any scene but a one-level tree of triangles over exactly one instance
-bool launch_fused_one(const TraverseArgs &a, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
-// k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit.  leaf_parent: the tree's table
-// record -> node (below); false: refused -- whatever launch_fused_one would refuse, no table, or a launch without the window (seed_primary < 2)
-bool launch_fused_restart(const TraverseArgs &a, const uint32_t *leaf_parent, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s);
+// ---- the path kernels: one launch renders every sample of every pixel of a tile (or traces callers' rays, PathArgs::trace_rays) ----
+enum class PathKernel {
+    Fused, FusedInstanced,      // k_fused (fused.hip): one-level trees, two-level trees (transform nodes, bvh8.h); with PathArgs::primary_cache, its primary-reuse instantiation
+    Capture,            // k_path_capture (fused_capture.hip): k_fused<S, I, false> that also keeps every pixel's primary hit
+    Blocks,             // k_path_blocks (fused_blocks.hip): pixels handed out in sample blocks
+    OneGroup,           // k_path_one (fused_one.hip): the block render of a scene with one hit group
+    Restart,            // k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit
+    Round1,             // k_traverse<.., FUSED> (kernels.hip): round 1's fused kernel, for the trees k_fused cannot take
+};
+struct PathScene { bool one_level; uint32_t n_instances; bool has_spheres; const uint32_t *leaf_parent; };      // what the TraverseArgs do not say about the tree (leaf_parent: below, or NULL)
+// What each kernel takes for granted, in one place: its regeneration does not look at the fields it is compiled without, so a launch that
+// contradicts the kernel it names is refused instead of rendering something else.  Plain host code: no device, nothing launched.
+inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const PathScene &scene) {
+    const PathArgs &p = a.path;
+    // a render in sample blocks: a one-level tree, no callers' rays, no cost probe, no slice order; ... of triangles over exactly one instance, whose table entries exist
+    const bool in_blocks = scene.one_level && p.sample_block != 0u && p.trace_rays == nullptr && p.slice_cost == nullptr && p.slice_order == nullptr;
+    const bool one_group = in_blocks && scene.n_instances == 1u && !scene.has_spheres && p.hitgroups != nullptr && p.inst_program != nullptr;
+    switch (kernel) {
+        case PathKernel::Fused: return scene.one_level && p.sample_block == 0u;           // (the caller names the block kernels: nothing forwards)
+        case PathKernel::FusedInstanced: return !scene.one_level && p.sample_block == 0u;
+        case PathKernel::Capture: return p.sample_block == 0u && p.trace_rays == nullptr && p.primary_cache == nullptr;      // (trace_tuvp / trace_inst carry its arrays)
+        case PathKernel::Blocks: return in_blocks;
+        case PathKernel::OneGroup: return one_group;
+        case PathKernel::Restart: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;      // (the table, and the window its rays start in)
+        case PathKernel::Round1: return true;
+    }
+    return false;
+}
+// The one launch entry of the path kernels (fused.hip).  false: refused (path_launch_admitted), nothing launched.
+bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);
+using PathLauncher = void(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);      // (its halves in the other kernels' translation units: each launches its own kernel)
+PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_round1;
 // leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
 // counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
 // primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.

@@ -12,44 +12,49 @@
 // for all programs, an issue priority per loop phase, and tail splitting once the tile is used up (lanes without a pixel take
 // subtrees off the busy lanes' stacks; the pieces of a ray share one best hit in LDS).  The loop between two regenerations is
 // trav_loop.h's, shared with k_trace_queue (fused_queue.hip); the steps of the regeneration phase are path_lane.h's, shared with
-// k_traverse<.., FUSED>.  What is here is when a regeneration happens, the primary-hit cache (REUSE) round those steps, and the
-// two-level tree's transform-node steps.
+// k_traverse<.., FUSED>.  What is here is when a regeneration happens, the primary-hit cache (kReuse) round those steps, and the
+// two-level tree's transform-node steps -- and launch_path_kernel, the one way every path kernel is launched.
 #include "fused_body.h"
 
 #pragma clang fp contract(off)
 
 namespace hrt {
 
-bool launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s);      // fused_blocks.hip (false: refused, nothing launched)
-
+template <bool HAS_SPHERES, bool INSTANCED, bool REUSE>
+struct FusedVariant : FusedBodyVariant<REUSE> { static constexpr bool kSpheres = HAS_SPHERES, kInstanced = INSTANCED; };
 // (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
 // from the segment itself, fused_body.h: kernarg_traverse_args)
 template <bool HAS_SPHERES, bool INSTANCED, bool REUSE>
 __global__ __launch_bounds__(kTraverseBlock, INSTANCED ? HRT_INST_WAVES_PER_SIMD : HRT_FUSED_WAVES_PER_SIMD) void k_fused(TraverseArgs a) {
-    fused_body<HAS_SPHERES, INSTANCED, REUSE, false>(a);
+    fused_body<FusedVariant<HAS_SPHERES, INSTANCED, REUSE>>(a);
 }
 
 // one launch renders every sample of every pixel of the tile: the instantiation for the scene's primitives and, where the caller has set
 // a primary-hit cache up, primary reuse
 template <bool INSTANCED>
-static bool launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
+static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    if constexpr (!INSTANCED) {
-        // INVARIANT: k_path_blocks is compiled for sample_block != 0 with trace_rays, slice_cost and slice_order all NULL and never looks at
-        // them (path_lane.h).  render_fused (hrt_api.cpp), the only caller that sets sample_block, does so for one-level trees without a
-        // primary-hit cache, outside the cost probe and its slice order only; launch_fused_blocks refuses everything else (false).
-        if (a.path.sample_block != 0u) return launch_fused_blocks(a, has_spheres, grid_blocks, s);
-    }
     switch ((has_spheres ? 2 : 0) | (a.path.primary_cache != nullptr ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((k_fused<false, INSTANCED, false>), g, b, 0, s, a); break;
         case 1: hipLaunchKernelGGL((k_fused<false, INSTANCED, true>), g, b, 0, s, a); break;
         case 2: hipLaunchKernelGGL((k_fused<true, INSTANCED, false>), g, b, 0, s, a); break;
         default: hipLaunchKernelGGL((k_fused<true, INSTANCED, true>), g, b, 0, s, a); break;
     }
+}
+
+// The one way a path kernel is launched: the launch is held to what the kernel the caller names takes for granted, and that kernel's own translation unit launches it
+bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
+    if (!path_launch_admitted(kernel, a, scene)) return false;
+    switch (kernel) {
+        case PathKernel::Fused: launch_fused_as<false>(a, scene.has_spheres, grid_blocks, s); break;
+        case PathKernel::FusedInstanced: launch_fused_as<true>(a, scene.has_spheres, grid_blocks, s); break;      // (transform nodes over shared BLASes)
+        case PathKernel::Capture: launch_path_capture(a, scene, grid_blocks, s); break;
+        case PathKernel::Blocks: launch_path_blocks(a, scene, grid_blocks, s); break;
+        case PathKernel::OneGroup: launch_path_one(a, scene, grid_blocks, s); break;
+        case PathKernel::Restart: launch_path_restart(a, scene, grid_blocks, s); break;
+        case PathKernel::Round1: launch_path_round1(a, scene, grid_blocks, s); break;
+    }
     return true;
 }
-bool launch_fused(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { return launch_fused_as<false>(a, has_spheres, grid_blocks, s); }
-// ... through a two-level tree (transform nodes over shared BLASes)
-bool launch_fused_instanced(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) { return launch_fused_as<true>(a, has_spheres, grid_blocks, s); }
 
 }  // namespace hrt

@@ -7,26 +7,21 @@
 
 namespace hrt {
 
+template <bool HAS_SPHERES>
+struct BlocksVariant : FusedBodyVariant<false> { static constexpr bool kSpheres = HAS_SPHERES, kBlocks = true; };
 // (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
 // from the segment itself, fused_body.h: kernarg_traverse_args)
 template <bool HAS_SPHERES>
 __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_path_blocks(TraverseArgs a) {
-    fused_body<HAS_SPHERES, false, false, true>(a);
+    fused_body<BlocksVariant<HAS_SPHERES>>(a);
 }
 
-// What the BLOCKS instantiation takes for granted (path_lane.h: path_finish, path_take, path_primary): a render in sample blocks, with no
-// callers' rays, no cost probe and no slice order.  Its regeneration does not look at these fields, so a launch that contradicts them is
-// refused here (false: nothing was launched) instead of rendering something else.
-bool blocks_launch_admitted(const TraverseArgs &a) {
-    return a.path.sample_block != 0u && a.path.trace_rays == nullptr && a.path.slice_cost == nullptr && a.path.slice_order == nullptr;
-}
-
-bool launch_fused_blocks(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
-    if (!blocks_launch_admitted(a)) return false;
+// (what the kBlocks instantiations take for granted -- a render in sample blocks, with no callers' rays, no cost probe and no slice order,
+// fields their regeneration does not look at -- every launch is held to before it gets here: device_types.h, path_launch_admitted)
+void launch_path_blocks(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    if (has_spheres) hipLaunchKernelGGL((k_path_blocks<true>), g, b, 0, s, a);
+    if (scene.has_spheres) hipLaunchKernelGGL((k_path_blocks<true>), g, b, 0, s, a);
     else hipLaunchKernelGGL((k_path_blocks<false>), g, b, 0, s, a);
-    return true;
 }
 
 }  // namespace hrt

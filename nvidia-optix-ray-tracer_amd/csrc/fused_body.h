@@ -16,9 +16,9 @@
 namespace hrt {
 
 #ifndef HRT_SPHERE_CULL
-#define HRT_SPHERE_CULL 1     // INSTANCED: a ray that misses an instance's bounding sphere does not enter it (0: enters every instance whose box it crosses)
+#define HRT_SPHERE_CULL 1     // kInstanced: a ray that misses an instance's bounding sphere does not enter it (0: enters every instance whose box it crosses)
 #endif
-// INSTANCED: the tree has two levels (bvh8.h: transform nodes; the reference's IAS over shared GASes, RendererImpl.cu:174-206).  A lane
+// kInstanced: the tree has two levels (bvh8.h: transform nodes; the reference's IAS over shared GASes, RendererImpl.cu:174-206).  A lane
 // whose next node turns out to be a transform node leaves its world ray in LDS, goes on with the ray in the instance's object space
 // (row-major 3x4 inverse from the node; identity: copied) and the BLAS's root as the only child; its node stack continues ABOVE what it
 // held (`base` = the frame's bottom), so the bookkeeping sequence is the one-level kernel's, unchanged.  When it reports the frame
@@ -99,15 +99,15 @@ struct InstLane {
     }
 };
 
-// REUSE (HRT_CTX_REUSE_PRIMARY): the reference's raygen has no pixel jitter (Shader.cu:249-261), so the primary ray of a pixel -- and its
+// kReuse (HRT_CTX_REUSE_PRIMARY): the reference's raygen has no pixel jitter (Shader.cu:249-261), so the primary ray of a pixel -- and its
 // hit -- is the same for every sample.  The first sample a launch takes of a pixel traces it and leaves the hit record in the lane's slot of
 // `primary_cache`; the later ones are shaded from there (same record, same shading, same random numbers: the same bits) and only their
-// bounces are traversed.  Rays that are not traversed are not counted.  A separate instantiation, like INSTANCED.
+// bounces are traversed.  Rays that are not traversed are not counted.  A separate instantiation, like kInstanced.
 #ifndef HRT_FUSED_WAVES_PER_SIMD
 #define HRT_FUSED_WAVES_PER_SIMD 4      // 128 VGPRs, the probe launch's clock spilled; 5 waves (96 VGPRs, 95 spilled around the shading): 2560 against 3122 Mrays/s
 #endif
 #ifndef HRT_INST_WAVES_PER_SIMD
-#define HRT_INST_WAVES_PER_SIMD 3       // the INSTANCED instantiation: 160 VGPRs, nothing spilled, 12 waves per CU (at 4 waves per SIMD it spills 47 registers around
+#define HRT_INST_WAVES_PER_SIMD 3       // the kInstanced instantiation: 160 VGPRs, nothing spilled, 12 waves per CU (at 4 waves per SIMD it spills 47 registers around
                                         // the shading: 2 % slower on both particle clouds, profiles/r04_two_level_sweep.txt)
 #endif
 // The kernel's arguments as the regeneration reads them: straight from the kernel-argument segment, with scalar loads (s_load_dword*, the
@@ -122,23 +122,20 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
     return *(const TraverseArgs *)p;
 }
 
-// The kernel's body: k_fused below, and -- BLOCKS -- k_path_blocks, which hands pixels out in sample blocks (path_lane.h).  A kernel of its own
+// The kernel's body: k_fused below, and -- kBlocks -- k_path_blocks, which hands pixels out in sample blocks (path_lane.h).  A kernel of its own
 // because the hand-over costs the regeneration spilled registers, which the launches without blocks need not pay.
 // `a`: the kernel's only argument (see kernarg_traverse_args); what the traversal loop consumes comes from it, the regeneration's
 // constants from the segment.
-// CAPTURE: k_path_capture (fused_capture.hip) -- every pixel's primary hit is left in frame order as well (path_lane.h: path_finish).
-// ONE_GROUP: k_path_one (fused_one.hip) -- a block render of triangles of ONE instance: every hit is instance 0's, so the regeneration reads
+// kCapture: k_path_capture (fused_capture.hip) -- every pixel's primary hit is left in frame order as well (path_lane.h: path_finish).
+// kOneGroup: k_path_one (fused_one.hip) -- a block render of triangles of ONE instance: every hit is instance 0's, so the regeneration reads
 // entry 0 of the per-instance tables with scalar loads and keeps no albedo chain (path_lane.h: path_finish), and the loop's primitive test
 // decides ties by the primitive id alone (trav_common.h: test_prim_ray).
-// RESTART: k_path_restart (fused_restart.hip) -- k_path_one whose repeat primary rays, which already start inside a window under their known hit,
+// kRestart: k_path_restart (fused_restart.hip) -- k_path_one whose repeat primary rays, which already start inside a window under their known hit,
 // also start at the NODE whose leaf slot holds that hit's record instead of at the root (path_lane.h: path_finish).
-template <bool HAS_SPHERES, bool INSTANCED, bool REUSE, bool BLOCKS, bool CAPTURE = false, bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
-    static_assert(!RESTART || ONE_GROUP, "the restart: the one-group block render");
-    static_assert(!ONE_GROUP || (BLOCKS && !HAS_SPHERES && !CAPTURE), "one hit group: the block render of a one-level tree of triangles");
-    static_assert(!CAPTURE || (!REUSE && !BLOCKS), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
-    constexpr bool kSeed = !REUSE;          // (REUSE does not traverse a pixel's repeat primary rays at all)
+    static_assert(path_variant_checked<V>(), "trav_common.h: the constraints between a variant's flags");
     // kSeed: the hit distance the lane's pixel last found along its primary ray (path_lane.h), read once per sample: a word of LDS, so that
     // its register is the ray's TravState::tlo.  (One-level kernels: 9984 + 256 = 10240 bytes, still 16 waves per CU.)
     __shared__ float s_seed[kTraverseBlock];
@@ -148,7 +145,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     __shared__ float s_mb_t[kTraverseBlock], s_mb_u[kTraverseBlock], s_mb_v[kTraverseBlock];
     __shared__ uint32_t s_mb_prim[kTraverseBlock], s_mb_inst[kTraverseBlock], s_mb_pending[kTraverseBlock];
     __shared__ uint32_t s_pair[kTraverseBlock];
-    // INSTANCED: the rest of a world ray that waits while its lane is inside an instance (reciprocals, octant)
+    // kInstanced: the rest of a world ray that waits while its lane is inside an instance (reciprocals, octant)
     __shared__ float s_park_idx[kTraverseBlock], s_park_idy[kTraverseBlock], s_park_idz[kTraverseBlock];
     __shared__ uint32_t s_park_oct[kTraverseBlock];
 
@@ -163,12 +160,12 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     const uint32_t ldsn = (uint32_t)reinterpret_cast<uintptr_t>(&s_nodes[0][tx]), ldsl = (uint32_t)reinterpret_cast<uintptr_t>(&s_leaves[0][tx]);
 
     const Mailboxes mb{s_mb_t, s_mb_u, s_mb_v, s_mb_prim, s_mb_inst, s_mb_pending, s_pair};
-    // RESTART: the node the lane's pixel's next primary ray starts at (0: the root), a word per lane like the seed.  It lives in the mailboxes'
-    // `inst` array, which a one-group kernel only ever filled with zeros and which the RESTART forms of the tail-splitting blocks leave alone.
+    // kRestart: the node the lane's pixel's next primary ray starts at (0: the root), a word per lane like the seed.  It lives in the mailboxes'
+    // `inst` array, which a one-group kernel only ever filled with zeros and which the kRestart forms of the tail-splitting blocks leave alone.
     [[maybe_unused]] uint32_t *const s_restart = s_mb_inst;
 
-    std::conditional_t<INSTANCED, InstLane, NoInstLane> I;
-    if constexpr (INSTANCED) { I.park_idx = s_park_idx; I.park_idy = s_park_idy; I.park_idz = s_park_idz; I.park_oct = s_park_oct; }
+    std::conditional_t<V::kInstanced, InstLane, NoInstLane> I;
+    if constexpr (V::kInstanced) { I.park_idx = s_park_idx; I.park_idy = s_park_idy; I.park_idz = s_park_idz; I.park_oct = s_park_oct; }
 
     LeanLane L;
     lean_idle(L, tmax_ray, tmin);
@@ -177,17 +174,16 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     bool exhausted = false;                 // wave-uniform: no pixels left to start
 
     PathLane P;                             // the lane's pixel: path_lane.h
-    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path (ONE_GROUP: never written, never read)
+    uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path (kOneGroup: never written, never read)
     LaneStats stats;
 
     // the wave's slice of the tile: [wbeg, wend); slices of fetch_chunk pixels are handed out by kFetchShards counters
     uint32_t wbeg = 0, wend = 0, kstart = 0;
     const uint32_t home_shard = blockIdx.x & (kFetchShards - 1);
-    static_assert(!BLOCKS || (!INSTANCED && !REUSE), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
-    [[maybe_unused]] BlockSlice B;                  // (BLOCKS) the item the wave holds
+    [[maybe_unused]] BlockSlice B;                  // (kBlocks) the item the wave holds
 
-    [[maybe_unused]] bool force_regen = false;      // (REUSE, wave-uniform)
-    [[maybe_unused]] bool cached = false;           // (REUSE) this lane waits to be shaded with its pixel's cached primary hit
+    [[maybe_unused]] bool force_regen = false;      // (kReuse, wave-uniform)
+    [[maybe_unused]] bool cached = false;           // (kReuse) this lane waits to be shaded with its pixel's cached primary hit
     for (;;) {
         const uint64_t idle = ~F.alive;
         const uint32_t n_idle = (uint32_t)__popcll(idle);
@@ -199,7 +195,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             stats.regeneration();
             __builtin_amdgcn_s_setprio(HRT_PRIO_REGEN);
             const TraverseArgs &a = kernarg_traverse_args();      // (hides the parameter on purpose: nothing in this block reads the entry's copy)
-            // (Tried for BLOCKS: the block's constants -- samples, tmax, the seed's level, the schedule, the tables' and the hand-over's bases --
+            // (Tried for kBlocks: the block's constants -- samples, tmax, the seed's level, the schedule, the tables' and the hand-over's bases --
             // made to exist here by an empty asm with them as inputs, so that their loads go out back to back behind one wait: 33 -> 16
             // s_waitcnt lgkmcnt(0) in the block, nothing spilled, and 0.1 % SLOWER in five of five alternating runs, profiles/r23_block_regen.txt.)
             PathStep st;                            // st.launch: this lane starts the ray (st.ro, st.rd) below
@@ -212,8 +208,8 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                 const TravState &s = L.s;
                 // the finished ray and what it hit
                 V3 o = mk3(s.ox, s.oy, s.oz), d = mk3(s.dx, s.dy, s.dz);
-                float bt = lean_miss_t(s.bt, s.bprim, a.tmax), bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = ONE_GROUP ? 0u : s.binst;      // (a miss says tmax)
-                if constexpr (REUSE) {
+                float bt = lean_miss_t(s.bt, s.bprim, a.tmax), bu = s.bu, bv = s.bv; uint32_t bprim = s.bprim, binst = V::kOneGroup ? 0u : s.binst;      // (a miss says tmax)
+                if constexpr (V::kReuse) {
                     float4 *slot = a.path.primary_cache + 2u * (blockIdx.x * kTraverseBlock + tx);
                     if (cached) {                   // ... or, for a primary ray that was not traversed again, what the pixel's first sample found
                         const float4 c0 = slot[0]; const float4 c1 = slot[1];
@@ -224,21 +220,19 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                         slot[0] = make_float4(bt, bu, bv, __uint_as_float(bprim)); slot[1] = make_float4(__uint_as_float(binst), 0.0f, 0.0f, 0.0f);
                     }
                 }
-                // (RESTART: s.binst is the record the hit was accepted from, and the walk had a window if it began above the launch's tmin)
-                if constexpr (RESTART) st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP, true>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx, s.binst, s.tlo > tmin, s_restart + tx);
-                else st = path_finish<HAS_SPHERES, REUSE, BLOCKS, kSeed, CAPTURE, ONE_GROUP>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx);
+                // (kRestart: s.binst is the record the hit was accepted from, and the walk had a window if it began above the launch's tmin)
+                st = path_finish<V>(P, chain, a, o, d, bt, bu, bv, bprim, binst, s_seed + tx, s.binst, s.tlo > tmin, s_restart + tx);
             }
-            if constexpr (RESTART) exhausted = path_take<BLOCKS, kSeed, true>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx, s_restart + tx);
-            else exhausted = path_take<BLOCKS, kSeed>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx);
+            exhausted = path_take<V>(P, st, a, n_pixels, !lane_bit(F.alive) && !P.have_pixel && !st.want_primary && !st.launch, wbeg, wend, kstart, exhausted, home_shard, tx, &B, s_seed + tx, s_restart + tx);
             stats.drained(exhausted);
             if (st.want_primary) {
                 bool from_cache = false;
-                if constexpr (REUSE) from_cache = !a.path.trace_rays && P.px_sample > 0u;
+                if constexpr (V::kReuse) from_cache = !a.path.trace_rays && P.px_sample > 0u;
                 if (from_cache) {
                     // a pixel's later primary rays are not traversed again: the lane waits for its shading as if the ray had just finished (the hit is in the cache)
                     P.px_depth = 1u; cached = true; reshade = true;      // (F.waiting: below)
                 } else {
-                    const PathRay r = path_primary<false, BLOCKS>(P, a);
+                    const PathRay r = path_primary<V, false>(P, a);
                     st.ro = r.o; st.rd = r.d; st.launch = true;
                 }
             }
@@ -246,47 +240,47 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             if (st.launch) {
                 any_hit = path_count_ray(P);
                 // a primary ray of a pixel the lane already holds starts bounded at the hit its previous sample found (s_seed; tmax after
-                // path_take -- or, BLOCKS, what the pixel's previous block left for it, path_lane.h: handover_load):
+                // path_take -- or, kBlocks, what the pixel's previous block left for it, path_lane.h: handover_load):
                 // counted and walked from the root like any other, the primitive test keeps the launch's tmin and tmax.  At level
                 // 2 it is bounded from below as well: the same ray has found nothing before that hit, so the node step's interval begins a
                 // window (trav_common.h: kSeedWindow) below it.  Every other ray -- a bounce, a first sample, after a miss (the seed says
                 // tmax), a caller's ray -- begins at the launch's tmin.
-                // RESTART: ... and a ray that got a window starts at the node its predecessor left for it (s_restart: the root unless that ray
+                // kRestart: ... and a ray that got a window starts at the node its predecessor left for it (s_restart: the root unless that ray
                 // accepted its hit itself, inside the same window) -- still launched, counted and decided by the canonical primitive test.
                 float hi = tmax_ray, lo = tmin;
                 [[maybe_unused]] uint32_t first_node = 0u;
-                if constexpr (kSeed) {
+                if constexpr (V::kSeed) {
                     if (st.want_primary) {
                         hi = s_seed[tx];
                         if (a.seed_primary >= 2 && hi < tmax_ray) lo = seed_window_lo(st.rd, hi, tmin);
-                        if constexpr (RESTART) { if (a.seed_primary >= 2 && hi < tmax_ray) first_node = s_restart[tx]; }
+                        if constexpr (V::kRestart) { if (a.seed_primary >= 2 && hi < tmax_ray) first_node = s_restart[tx]; }
                     }
                 }
                 lean_start(L, st.ro, st.rd, hi, lo);
-                if constexpr (RESTART) L.nidx = first_node;
-                if constexpr (INSTANCED) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
+                if constexpr (V::kRestart) L.nidx = first_node;
+                if constexpr (V::kInstanced) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
             }
             // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
             const uint64_t launched = __ballot(st.launch);
             F.alive |= launched; F.any = (F.any & ~launched) | __ballot(any_hit);
-            if constexpr (REUSE) F.waiting |= __ballot(reshade);
-            // REUSE: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that
+            if constexpr (V::kReuse) F.waiting |= __ballot(reshade);
+            // kReuse: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that
             // their bounces start together with the other lanes' rays (one extra round, not more: the others are waiting)
-            if constexpr (REUSE) { if (!was_forced && __ballot(reshade) != 0ull) { force_regen = true; continue; } }
+            if constexpr (V::kReuse) { if (!was_forced && __ballot(reshade) != 0ull) { force_regen = true; continue; } }
             // s_waitcnt lgkmcnt(0): no scalar load of this block is under way when the traversal loop is entered.  A load issued in front of a
             // branch that skips its wait counts as pending to the compiler, which then waits INSIDE the loop wherever the loop reuses the
             // load's register (two s_waitcnt in the sphere kernels' loops, as the registers happened to fall)
-            // BLOCKS: ... and no vector load either (vmcnt(0) as well).  The words of a hand-over (path_lane.h: handover_load) are not needed before
+            // kBlocks: ... and no vector load either (vmcnt(0) as well).  The words of a hand-over (path_lane.h: handover_load) are not needed before
             // the lane's next regeneration, so with nothing else in the block waiting for them the compiler lets them fly into the loop
             // and waits at the loop's header, in every iteration; here they have had the pixel's set-up and the ray's start to arrive
-            if constexpr (BLOCKS) __builtin_amdgcn_s_waitcnt(0x0070);
+            if constexpr (V::kBlocks) __builtin_amdgcn_s_waitcnt(0x0070);
             else __builtin_amdgcn_s_waitcnt(0xc07f);
         }
-        // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, REUSE, a lane with a cached hit to shade:
+        // the tile is used up and every lane has finished (nothing waits after a full regeneration -- but, kReuse, a lane with a cached hit to shade:
         // an empty pass through the loop below brings it back here)
-        if ((REUSE ? F.alive | F.waiting : F.alive) == 0ull) {
+        if ((V::kReuse ? F.alive | F.waiting : F.alive) == 0ull) {
             bool leave = true;
-            if constexpr (BLOCKS) leave = B.need == 0u;
+            if constexpr (V::kBlocks) leave = B.need == 0u;
             if (leave) break;
             // Sample blocks: the wave holds an item whose predecessor is still under way and has nothing else to do.  It must not leave
             // (the item's pixels would never be rendered), so it looks again after a short sleep.  This cannot hang, PROVIDED every one of
@@ -315,14 +309,14 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
         //      and the drained phase's exit rule runs once the tile is used up ----
         if (exhausted) {
             stats.tail_begin();
-            traverse_to_regen<HAS_SPHERES, INSTANCED, true, kSeed, ONE_GROUP, RESTART>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+            traverse_to_regen<V, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
             stats.tail_end();
-            // RESTART: s_waitcnt lgkmcnt(0) -- the drained copy's last block (tail_retire) takes a merged hit out of the mailboxes, and as the
+            // kRestart: s_waitcnt lgkmcnt(0) -- the drained copy's last block (tail_retire) takes a merged hit out of the mailboxes, and as the
             // registers fall in this kernel the compiler lets those LDS reads fly out of that loop.  To the compiler `exhausted` may turn false
             // again, so it then waits for them INSIDE the other copy of the loop, which this path can never reach: two s_waitcnt per iteration.
-            if constexpr (RESTART) __builtin_amdgcn_s_waitcnt(0xc07f);
+            if constexpr (V::kRestart) __builtin_amdgcn_s_waitcnt(0xc07f);
         }
-        else traverse_to_regen<HAS_SPHERES, INSTANCED, false, kSeed, ONE_GROUP, RESTART>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
+        else traverse_to_regen<V, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, leaf_hold, max_alive, !P.have_pixel, tx);
     }
     const TraverseArgs &k = kernarg_traverse_args();          // (the counters' addresses need not live in registers until here)
     stats.report(k.path.rays_closest, tx);

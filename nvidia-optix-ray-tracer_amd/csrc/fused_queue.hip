@@ -19,6 +19,7 @@ namespace hrt {
 template <bool HAS_SPHERES>
 __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
+    using V = PlainVariant<HAS_SPHERES>;      // (no pixels, no seed: the loop with the uniform tmin, primitive test and tail splitting in their plain forms)
     __shared__ uint2 s_nodes[kNodeStackLds][kTraverseBlock];
     __shared__ uint2 s_leaves[kLeafStackLds][kTraverseBlock];
     __shared__ float s_mb_t[kTraverseBlock], s_mb_u[kTraverseBlock], s_mb_v[kTraverseBlock];
@@ -91,8 +92,8 @@ __global__ __launch_bounds__(kTraverseBlock, 4) void k_trace_queue(TraverseArgs 
 
         // ---- traverse until enough lanes have finished (trav_loop.h); once the queue is used up, the copy with tail splitting: every idle
         //      lane may take a piece.  The leaf stack is used to its full depth (leaf_hold 4). ----
-        if (exhausted) traverse_to_regen<HAS_SPHERES, false, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, 4u, max_alive, true, tx);
-        else traverse_to_regen<HAS_SPHERES, false, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, 4u, max_alive, true, tx);
+        if (exhausted) traverse_to_regen<V, true>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, 4u, max_alive, true, tx);
+        else traverse_to_regen<V, false>(L, F, I, stats, mb, s_nodes, s_leaves, ldsn, ldsl, a, node_bytes, prim_bytes, tmin, tmax_ray, 4u, max_alive, true, tx);
     }
 }
 

@@ -12,24 +12,20 @@
 
 namespace hrt {
 
-bool blocks_launch_admitted(const TraverseArgs &a);      // fused_blocks.hip
-
+struct RestartVariant : FusedBodyVariant<false> { static constexpr bool kBlocks = true, kOneGroup = true, kRestart = true; };
 // (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
 // from the segment itself, fused_body.h: kernarg_traverse_args)
 __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_path_restart(TraverseArgs a) {
-    fused_body<false, false, false, true, false, true, true>(a);
+    fused_body<RestartVariant>(a);
 }
 
-// What k_path_one takes for granted (launch_fused_one), and the table: `leaf_parent` has one word per record of the launch's tree.  It rides in
-// PathArgs::slice_order, which a launch in blocks must not have (blocks_launch_admitted) and whose place the kernel therefore has free; the
-// caller's TraverseArgs is checked as it came and the launch gets a copy with the table in it.  false: refused, nothing launched.
-bool launch_fused_restart(const TraverseArgs &a, const uint32_t *leaf_parent, bool one_level, uint32_t n_instances, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
-    if (!blocks_launch_admitted(a) || leaf_parent == nullptr || a.seed_primary < 2) return false;
-    if (!one_level || n_instances != 1u || has_spheres || a.path.hitgroups == nullptr || a.path.inst_program == nullptr) return false;
+// The table: scene.leaf_parent has one word per record of the launch's tree.  It rides in PathArgs::slice_order, which a launch in blocks
+// must not have (path_launch_admitted, which has checked the caller's TraverseArgs as it came) and whose place the kernel therefore has
+// free: the launch gets a copy with the table in it.
+void launch_path_restart(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
     TraverseArgs b = a;
-    b.path.slice_order = leaf_parent;
+    b.path.slice_order = scene.leaf_parent;
     hipLaunchKernelGGL(k_path_restart, dim3(grid_blocks), dim3(kTraverseBlock), 0, s, b);
-    return true;
 }
 
 }  // namespace hrt

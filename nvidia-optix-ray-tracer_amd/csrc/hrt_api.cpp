@@ -270,7 +270,6 @@ static TraverseArgs traverse_args(const HrtContext *ctx, const Tlas &t, float tm
 }
 // The path kernel of a tree: k_fused, its instanced form for two-level trees, or -- for a tree outside k_fused's limits -- round 1's
 // fused kernel, counted in fused_fallback_launches.  blocks_per_cu: one-wave workgroups per CU at most.
-enum class PathKernel { Fused, FusedInstanced, Round1 };
 struct PathKernelChoice { PathKernel kernel; uint32_t blocks_per_cu; };
 static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
     const uint32_t knob = (uint32_t)ctx->fused_blocks_per_cu;
@@ -278,14 +277,17 @@ static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
     if (t.two_level) return {PathKernel::FusedInstanced, std::min<uint32_t>(knob, (uint32_t)kFusedInstancedBlocksPerCu)};
     return {PathKernel::Fused, std::min<uint32_t>(knob, (uint32_t)kFusedBlocksPerCu)};
 }
-// (false: refused -- a launch in sample blocks that asks for what k_path_blocks is not compiled for, fused.hip)
-static bool launch_path_kernel(PathKernel k, const TraverseArgs &ta, bool has_spheres, uint32_t grid, hipStream_t s) {
-    switch (k) {
-        case PathKernel::Fused: return launch_fused(ta, has_spheres, grid, s);
-        case PathKernel::FusedInstanced: return launch_fused_instanced(ta, has_spheres, grid, s);
-        case PathKernel::Round1: launch_paths_v1(ta, has_spheres, grid, s); break;
-    }
-    return true;
+static PathScene path_scene(const Tlas &t) { return {!t.two_level, t.n_instances, t.has_spheres, t.dev.d_leaf_parent}; }
+// The kernel of ONE launch of render_fused, from what is decided by then: the tree's kernel (choose_path_kernel), whether the render captures
+// primary hits -- of a render cut into several launches the first one does: the primary ray of a pixel's first sample is every sample's --,
+// whether this launch goes in sample blocks, and how many samples earlier launches have taken.  A launch in blocks of a scene with ONE hit
+// group -- a one-level tree of triangles over exactly one instance, any single-mesh render -- takes k_path_one (HRT_ONE_GROUP=0: k_path_blocks
+// like everything else) or, where its repeat primary rays get their window (HRT_SEED_PRIMARY=2), k_path_restart (HRT_PRIMARY_RESTART=0:
+// k_path_one).  Decided per launch, from the tree that is launched: an update that adds an instance sends the next launch back to k_path_blocks.
+static PathKernel launch_kernel(const HrtContext *ctx, const Tlas &t, PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary) {
+    if (!blocks) return capture && done_spp == 0u ? PathKernel::Capture : tree_kernel;
+    if (!(ctx->one_group && !t.two_level && t.n_instances == 1u && !t.has_spheres)) return PathKernel::Blocks;
+    return ctx->primary_restart && seed_primary == 2 ? PathKernel::Restart : PathKernel::OneGroup;
 }
 extern "C++" {      // (helpers of hrt_internal.hpp, shared with hrt_denoise.cpp)
 namespace hrt {
@@ -346,7 +348,7 @@ int trace_records(HrtContext *ctx, const Tlas &t, const RayRec *rays, uint32_t n
         // they are not launched on one: the records are filled and the rays counted as the kernel would have.  (k_traverse, below, has no
         // such limit and takes every interval.)
         if (pk.kernel != PathKernel::Round1 && !(tmax > tmin)) launch_fill_misses(tuvp, inst, n_rays, tmax, any_hit ? pa.rays_any : pa.rays_closest, s);
-        else if (!launch_path_kernel(pk.kernel, ta, t.has_spheres, grid, s)) return fail(ctx, HRT_ERR_STATE, "the path kernel refused the launch (sample blocks with callers' rays)");
+        else if (!launch_path_kernel(pk.kernel, ta, path_scene(t), grid, s)) return fail(ctx, HRT_ERR_STATE, "the path kernel refused the launch (sample blocks with callers' rays)");
     } else {
         ta.seg[0].rays = rays; ta.seg[0].n_ptr = nullptr; ta.seg[0].n = n_rays; ta.seg[0].any_hit = any_hit ? 1u : 0u;
         ta.seg[0].hit_tuvp = tuvp; ta.seg[0].hit_inst = inst;
@@ -462,7 +464,6 @@ static int render_fused(const LaunchFrame &f) {
         c.capacity = n;
     }
     bool captured = false;
-    auto launch = [&]() { return launch_path_kernel(pk.kernel, ta, t->has_spheres, grid, s); };
     // Longest-processing-time-first: a pixel's samples run one after the other in one lane, so a render ends with
     // whatever pixels were started last.  For renders of many samples the first sample is a probe launch of its own
     // that records how long each slice's pixels took over their sample; the slices are then handed out slowest first,
@@ -486,7 +487,7 @@ static int render_fused(const LaunchFrame &f) {
         HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         const uint32_t probe_spp = (uint32_t)std::min<int>(std::max(ctx->fused_lpt, 1), (int)spp / 4);
         pa.spp = probe_spp; pa.continue_sum = 0u; pa.slice_cost = w.slice_cost; pa.slice_order = nullptr;
-        { Timer tm(ctx, s, HRT_K_PATHS); (void)launch(); }       // (sample_block is still 0: nothing to refuse)
+        { Timer tm(ctx, s, HRT_K_PATHS); (void)launch_path_kernel(pk.kernel, ta, path_scene(*t), grid, s); }       // (sample_block is still 0: nothing to refuse)
         ctx->fused_counters_clean = false;
         ctx->h_slice_cost.resize(n_slices); ctx->h_slice_order.resize(n_slices);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_slice_cost.data(), w.slice_cost, sizeof(uint32_t) * n_slices, hipMemcpyDeviceToHost, s));
@@ -543,37 +544,19 @@ static int render_fused(const LaunchFrame &f) {
         // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         ctx->fused_counters_clean = false;
-        if (capture && done_spp == 0u && !blocks) {
-            // (of a render cut into several launches the first one captures: the primary ray of a pixel's first sample is every sample's)
-            pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst;
-            { Timer tm(ctx, s, HRT_K_PATHS); launch_fused_capture(ta, t->has_spheres, pk.kernel == PathKernel::FusedInstanced, grid, s); }
-            pa.trace_tuvp = nullptr; pa.trace_inst = nullptr;
-            ctx->primary_capture_launches++;
-            captured = true;
-        } else {
-            // A launch in blocks of a scene with ONE hit group -- a one-level tree of triangles over exactly one instance, any single-mesh
-            // render -- takes k_path_one (fused_one.hip; HRT_ONE_GROUP=0: k_path_blocks like everything else).  Decided here, per launch,
-            // from the tree that is launched: an update that adds an instance sends the next launch back to k_path_blocks.
-            const bool one_group = blocks && ctx->one_group && !t->two_level && t->n_instances == 1u && !t->has_spheres;
-            // ... and, where its repeat primary rays get their window (HRT_SEED_PRIMARY=2), k_path_restart (fused_restart.hip), which also starts
-            // them at the node of their known hit: it wants the tree's leaf_parent table, made here the first time (HRT_PRIMARY_RESTART=0, or a
-            // tree without records: k_path_one, the launch as it was).
-            bool restart = one_group && ctx->primary_restart && ta.seed_primary == 2;
-            if (restart) {
-                const int rc = ensure_leaf_parent(ctx, *t, s);
-                if (rc != HRT_OK) return rc;
-                restart = t->dev.d_leaf_parent != nullptr;
-            }
-            bool admitted;
-            {
-                Timer tm(ctx, s, HRT_K_PATHS);
-                admitted = restart ? launch_fused_restart(ta, t->dev.d_leaf_parent, !t->two_level, t->n_instances, t->has_spheres, grid, s)
-                         : one_group ? launch_fused_one(ta, !t->two_level, t->n_instances, t->has_spheres, grid, s) : launch();
-            }
-            if (admitted && one_group) ctx->one_group_launches++;
-            if (admitted && restart) ctx->restart_launches++;
-            if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
+        PathKernel kernel = launch_kernel(ctx, *t, pk.kernel, capture, blocks, done_spp, ta.seed_primary);
+        if (kernel == PathKernel::Restart) {      // it wants the tree's leaf_parent table, made here the first time (a tree without records: k_path_one, the launch as it was)
+            const int rc = ensure_leaf_parent(ctx, *t, s);
+            if (rc != HRT_OK) return rc;
+            if (t->dev.d_leaf_parent == nullptr) kernel = PathKernel::OneGroup;
         }
+        if (kernel == PathKernel::Capture) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
+        bool admitted;
+        { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, path_scene(*t), grid, s); }
+        if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
+        if (kernel == PathKernel::Capture) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
+        if (kernel == PathKernel::OneGroup || kernel == PathKernel::Restart) ctx->one_group_launches++;
+        if (kernel == PathKernel::Restart) ctx->restart_launches++;
         done_spp += now;
     }
     FinalizeArgs fa{};

@@ -89,6 +89,7 @@ template <bool COUNT, bool HAS_SPHERES, bool FUSED>
 // which costs less than the fifth wave gives: profiles/r01_sweep_occupancy.txt)
 __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the LDS stack and the mailboxes are per wave");
+    using V = PlainVariant<HAS_SPHERES>;      // (the regeneration and the primitive test in their plain forms: no seed, no blocks, one level)
     __shared__ uint2 s_stack[kLdsStack][kTraverseBlock];
     // tail splitting: one mailbox per lane that owns a split ray (indexed by its home lane)
     __shared__ float s_mb_t[kTraverseBlock], s_mb_u[kTraverseBlock], s_mb_v[kTraverseBlock];
@@ -182,13 +183,13 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                 PathStep st;
                 if (!alive && waiting) {
                     waiting = false;
-                    st = path_finish<HAS_SPHERES, false>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), s.bt, s.bu, s.bv, s.bprim, s.binst);
+                    st = path_finish<V>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), s.bt, s.bu, s.bv, s.bprim, s.binst);
                     if (st.launch) launch(st.ro, st.rd);
                 }
-                exhausted = path_take(P, st, a, n_rays, !alive && !P.have_pixel && !st.want_primary, wbeg, wend, kstart, exhausted, home_shard, tx);
+                exhausted = path_take<V>(P, st, a, n_rays, !alive && !P.have_pixel && !st.want_primary, wbeg, wend, kstart, exhausted, home_shard, tx);
                 if (st.want_primary) {
                     // (the sphere build is at its register limit: it makes the pixel's primary direction again instead of keeping it)
-                    const PathRay r = path_primary<HAS_SPHERES>(P, a);
+                    const PathRay r = path_primary<V, HAS_SPHERES>(P, a);
                     launch(r.o, r.d);
                 }
             }
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
             if (!COUNT && alive && !done && has_prim) {
                 const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w);
                 const float4 pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
-                const bool better = test_prim<HAS_SPHERES>(pa, pb, pc, s, tmin, tmax_ray, a.inst_inv, a.inst_identity);
+                const bool better = test_prim<V>(pa, pb, pc, s, tmin, tmax_ray, a.inst_inv, a.inst_identity);
                 if (any && better) done = true;
             }
             has_prim = false; pidx = 0u;
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(kTraverseBlock, 5) void k_traverse(TraverseArgs a) 
                     tri.y &= tri.y - 1u;
                     if (in_b) ++cnt_prims_b; else ++cnt_prims;
                     const float4 *pp = reinterpret_cast<const float4 *>(prim_bytes + (size_t)(tri.x + k) * a.prim_stride);
-                    const bool better = test_prim<HAS_SPHERES>(pp[0], pp[1], pp[2], s, tmin, tmax_ray, a.inst_inv, a.inst_identity);
+                    const bool better = test_prim<V>(pp[0], pp[1], pp[2], s, tmin, tmax_ray, a.inst_inv, a.inst_identity);
                     if (any && better) done = true;
                 }
             }
@@ -642,10 +643,10 @@ void launch_traverse(const TraverseArgs &a, bool count, bool has_spheres, uint32
         default: hipLaunchKernelGGL((k_traverse<true, true, false>), g, b, 0, s, a); break;
     }
 }
-// fused path mode: one launch renders every sample of every pixel of the tile
-void launch_paths_v1(const TraverseArgs &a, bool has_spheres, uint32_t grid_blocks, hipStream_t s) {
+// fused path mode: one launch renders every sample of every pixel of the tile (PathKernel::Round1: the trees k_fused cannot take)
+void launch_path_round1(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
     const dim3 g(grid_blocks), b(kTraverseBlock);
-    if (has_spheres) hipLaunchKernelGGL((k_traverse<false, true, true>), g, b, 0, s, a);
+    if (scene.has_spheres) hipLaunchKernelGGL((k_traverse<false, true, true>), g, b, 0, s, a);
     else hipLaunchKernelGGL((k_traverse<false, false, true>), g, b, 0, s, a);
 }
 void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s) {

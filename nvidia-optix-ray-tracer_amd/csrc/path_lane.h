@@ -6,7 +6,7 @@
 //   path_take      lanes without a pixel take the next ones of the wave's slice of the tile
 //   path_primary   the ray a lane that wants a primary ray starts
 // and path_count_ray / path_report_rays for the ray counters.  The kernels keep what is theirs: WHEN a regeneration happens, how a
-// ray is started in their traversal state, k_fused's primary-hit cache (REUSE) and its instance state.
+// ray is started in their traversal state, k_fused's primary-hit cache (kReuse) and its instance state.
 // Everything is inlined; PathLane is a plain struct of scalars, passed by reference, results come back by value, so that the state
 // stays in registers exactly as when the kernels spelled it out (k_fused has none to spare: check the ISA after any change here).
 #pragma once
@@ -31,7 +31,7 @@ struct PathLane {
     // TravState::tlo.  Every sample's primary ray is the same ray, so it ends in the same hit again: a complete closest-hit walk from the
     // root that never enters what lies behind that hit nor, with the window, what ends before it.  Reset by
     // path_take, so it never outlives the launch's hold on the pixel -- the lane's, or, in a render by sample blocks, that of the lanes
-    // that hand the pixel on within one launch (handover_store / handover_load); kept by the kernels that seed (SEED: fused_body.h) only.)
+    // that hand the pixel on within one launch (handover_store / handover_load); kept by the kernels that seed (kSeed: fused_body.h) only.)
 };
 
 // what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
@@ -91,7 +91,7 @@ __device__ __forceinline__ float handover_load(const PathArgs &pa, PathLane &P, 
     return none;
 }
 
-// fold_chain (trav_common.h) for a kernel that keeps the chain in registers (BLOCKS): the loop there loads hitgroups[chain[k]] and waits,
+// fold_chain (trav_common.h) for a kernel that keeps the chain in registers (kBlocks): the loop there loads hitgroups[chain[k]] and waits,
 // level by level, up to four round trips one behind the other, although all four addresses are known at once.  Here the albedos of
 // the levels below the depth are all asked for first, then multiplied in in the loop's order, innermost bounce first: the same
 // products in the same order, the same bits.
@@ -114,7 +114,7 @@ __device__ __forceinline__ V3 fold_chain_together(bool miss, const float *bg, co
     return r;
 }
 
-// ONE_GROUP (k_path_one, fused_one.hip: every hit is instance 0's): the per-instance tables have one entry, the same for every lane, and it
+// kOneGroup (k_path_one, fused_one.hip: every hit is instance 0's): the per-instance tables have one entry, the same for every lane, and it
 // is read as such -- through the constant address space, with scalar loads (s_load_dword*) into scalar registers, where it is used.  The
 // tables are written by the host before the launch and by nobody during it.
 typedef const __attribute__((address_space(4))) HitGroup *constant_hitgroup;
@@ -135,58 +135,57 @@ __device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_
 
 // A ray (o, d) has finished with the hit record (bt, bu, bv, bprim, binst).  The lane gives its pixel up (have_pixel = false: record or
 // sum written), wants the next sample's primary ray, or launches the bounce.
-// REUSE (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
-// BLOCKS: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
-// SEED: the kernel starts repeat primary rays at the lane's seed (`seed`: its word in LDS), so a finished primary ray records it (and path_take resets it).
-// CAPTURE (k_path_capture, fused_capture.hip; HRT_CTX_CAPTURE_PRIMARY): the primary ray of the first sample the launch takes of a pixel
+// kReuse (k_fused's primary-hit cache): a primary ray that leaves the scene does so in every sample of the pixel.
+// kBlocks: the instantiation knows sample blocks -- the lane's hold on its pixel also ends where a block does.
+// kSeed: the kernel starts repeat primary rays at the lane's seed (`seed`: its word in LDS), so a finished primary ray records it (and path_take resets it).
+// kCapture (k_path_capture, fused_capture.hip; HRT_CTX_CAPTURE_PRIMARY): the primary ray of the first sample the launch takes of a pixel
 // leaves its hit record in frame order, in hrt_trace_rays' form (a miss: tmax, kMissPrim), where the denoiser's guide pass and
 // hrt_primary_hits_get find it.  PathArgs::trace_tuvp / trace_inst are free in a render (trace_rays == NULL) and carry the two arrays.
-// ONE_GROUP: see above -- `binst` is 0, `px_chain` is neither written nor read.
-// RESTART (k_path_restart, fused_restart.hip; DESIGN.md section 4.1 "The start under the known hit"): a primary ray that ends in a hit leaves, in
+// kOneGroup: see above -- `binst` is 0, `px_chain` is neither written nor read.
+// kRestart (k_path_restart, fused_restart.hip; DESIGN.md section 4.1 "The start under the known hit"): a primary ray that ends in a hit leaves, in
 // the lane's word `restart` of LDS, the node the pixel's next primary ray starts at instead of the root: leaf_parent[brec], the node whose
 // leaf slot holds the record the hit was accepted from (`brec`; the table rides in PathArgs::slice_order, which a block render does not
 // have).  Only where `restartable` -- the lane accepted the hit itself (brec != kNoWork) in a walk that had the window the next one will
 // have, so that the node step of that node passes the slot again, bit for bit; everything else leaves 0, the root.  The table's load goes
 // out in front of the normals', on the same round trip.
 typedef const __attribute__((address_space(1))) uint32_t *global_words;
-template <bool HAS_SPHERES, bool REUSE, bool BLOCKS = false, bool SEED = false, bool CAPTURE = false, bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
                                             [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t brec = 0u, [[maybe_unused]] bool restartable = false,
                                             [[maybe_unused]] uint32_t *restart = nullptr) {
-    static_assert(!RESTART || (ONE_GROUP && SEED), "the restart: the one-group block render, whose repeat primary rays have a window");
     PathStep st;
     const bool miss = bprim == kMissPrim;
-    if constexpr (SEED) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
-    if constexpr (CAPTURE) {
+    if constexpr (V::kSeed) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
+    if constexpr (V::kCapture) {
         if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // (the primary-hit cache's condition, fused_body.h)
             a.path.trace_tuvp[P.px_tid] = make_float4(bt, bu, bv, __uint_as_float(bprim));
             a.path.trace_inst[P.px_tid] = binst;
         }
     }
-    // (BLOCKS: a block render has no callers' rays, no cost probe and no slice order, and its sample_block is not 0 -- facts of the
-    // instantiation, which launch_fused_blocks holds every launch to, so its regeneration neither loads nor tests them)
-    if (!BLOCKS && a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
+    // (kBlocks: a block render has no callers' rays, no cost probe and no slice order, and its sample_block is not 0 -- facts of the
+    // instantiation, which path_launch_admitted (device_types.h) holds every launch to, so its regeneration neither loads nor tests them)
+    if (!V::kBlocks && a.path.trace_rays) {           // hrt_trace_rays on this kernel: the "pixel" is a caller's ray, its hit record the result
         a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
         a.path.trace_inst[P.px_local] = binst;
         P.have_pixel = false;
     } else if (miss || P.px_depth >= kRayTraceDepth) {
         // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
         V3 r;
-        if constexpr (ONE_GROUP) r = fold_chain_one(miss, a.path.bg, P.px_depth, a.path.hitgroups);
-        else if constexpr (BLOCKS) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        if constexpr (V::kOneGroup) r = fold_chain_one(miss, a.path.bg, P.px_depth, a.path.hitgroups);
+        else if constexpr (V::kBlocks) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         else r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         if (P.px_first) { P.px_ax = r.x; P.px_ay = r.y; P.px_az = r.z; P.px_first = false; }
         else { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
         ++P.px_sample;
-        if constexpr (REUSE) {
+        if constexpr (V::kReuse) {
             // a primary ray that leaves the scene: every sample of the pixel is the background colour, added one by one
             if (miss && P.px_depth == 1u && !a.path.slice_cost)
                 for (; P.px_sample < a.path.spp; ++P.px_sample) { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
         }
-        if (!BLOCKS && a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
+        if (!V::kBlocks && a.path.slice_cost)     // probe launch: how long this pixel's sample took, start of its primary ray to here
             atomicAdd(a.path.slice_cost + P.px_local / a.fetch_chunk, ((uint32_t)__builtin_amdgcn_s_memtime() - P.px_t0) >> 4);
         bool ends = P.px_sample >= a.path.spp;
-        if constexpr (BLOCKS) {
+        if constexpr (V::kBlocks) {
             if (a.path.block_magic != 0u) {
                 // ... or, uniform blocks, px_sample is a multiple of K: with M = min(2^32 / K, 2^32 - 1) the quotient is short by one at most, so
                 // the remainder comes out as 0 or K exactly then (every px_sample, every K >= 1)
@@ -198,10 +197,10 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             }
         }
         if (ends) {
-            if constexpr (BLOCKS) {
+            if constexpr (V::kBlocks) {
                 // (the seed travels with the pixel: what its last primary ray found, tmax after a miss or with HRT_SEED_PRIMARY=0)
                 float carried = 0.0f;
-                if constexpr (SEED) carried = *seed;
+                if constexpr (V::kSeed) carried = *seed;
                 handover_store(a.path, P, a.fetch_chunk, carried);
             }
             else {
@@ -210,7 +209,7 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
             }
             P.have_pixel = false;
         } else st.want_primary = true;
-    } else if constexpr (ONE_GROUP) {
+    } else if constexpr (V::kOneGroup) {
         // entry 0 of both tables, in scalar registers: the normals' loads go out as soon as the pointer is there, and what the program is --
         // rough or metal, fuzz or none -- is the same in every lane, so scatter_programs' choices are the wave's
         const constant_hitgroup hp0 = (constant_hitgroup)a.path.hitgroups;
@@ -218,15 +217,15 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
         hg.ptr0 = hp0->ptr0; hg.ptr1 = nullptr; hg.albedo[0] = hg.albedo[1] = hg.albedo[2] = 0.0f; hg.fuzz = hp0->fuzz;      // (what a triangle program reads)
         const uint32_t program = *(constant_words)a.path.inst_program;
         [[maybe_unused]] uint32_t node = 0u;
-        if constexpr (RESTART) {
+        if constexpr (V::kRestart) {
             // (no branch: every lane here loads -- entry 0 where it has nothing to look up -- and keeps the word or 0)
             const bool look = P.px_depth == 1u && restartable && brec != kMissPrim;
             node = ((global_words)a.path.slice_order)[look ? brec : 0u];
             node = look ? node : 0u;
         }
         V3 hp, nd;
-        scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
-        if constexpr (RESTART) { if (P.px_depth == 1u) *restart = node; }
+        scatter_programs<V::kSpheres>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
+        if constexpr (V::kRestart) { if (P.px_depth == 1u) *restart = node; }
         ++P.px_depth;
         st.ro = hp; st.rd = nd; st.launch = true;
     } else {
@@ -234,7 +233,7 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
         const HitGroup hg = a.path.hitgroups[inst];
         const uint32_t program = a.path.inst_program[inst];
         V3 hp, nd;
-        scatter_programs<HAS_SPHERES>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
+        scatter_programs<V::kSpheres>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
         px_chain[P.px_depth - 1u] = inst;
         ++P.px_depth;
         st.ro = hp; st.rd = nd; st.launch = true;
@@ -245,21 +244,21 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // Lanes without a pixel (`free_lane`) take the next ones of the wave's slice [wbeg, wend) of the tile's n_pixels, in lane order, and
 // initialise them; a lane that took one wants a primary ray (st.want_primary).  Returns `exhausted` (wave-uniform): the tile is used up
 // (in and out by value on purpose: as a `bool &` it moved k_fused's sphere instantiations' loops by an instruction).
-// BLOCKS (B: the wave's item): in block mode the counters hand out block_items = passes x slices numbers, number i standing for pass
+// kBlocks (B: the wave's item): in block mode the counters hand out block_items = passes x slices numbers, number i standing for pass
 // i / slices of slice i % slices, and an item of a later pass waits for its predecessor: while the slice's progress word says that pixels of
 // (b - 1, q) are still under way the wave keeps the item, starts none of its pixels and looks again at its next regeneration.  It never
 // waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
-// RESTART (path_finish): a pixel just taken has no restart node -- the word in LDS is the lane's previous pixel's, while the seed (BLOCKS, a
+// kRestart (path_finish): a pixel just taken has no restart node -- the word in LDS is the lane's previous pixel's, while the seed (kBlocks, a
 // pass b > 0) comes with the pixel and switches the window on: a block's first primary ray walks from the root, inside its window.
-template <bool BLOCKS = false, bool SEED = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
                                           bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
                                           [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t *restart = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
-        constexpr bool by_blocks = BLOCKS;      // (launch_fused_blocks: sample_block != 0)
+        constexpr bool by_blocks = V::kBlocks;      // (path_launch_admitted: sample_block != 0)
         if (by_blocks) {
-            if constexpr (BLOCKS) {
+            if constexpr (V::kBlocks) {
                 if (wbeg >= wend) {
                     uint32_t item = 0u;
                     wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, a.path.block_items * a.fetch_chunk, tx,
@@ -290,7 +289,7 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
             if (wbeg >= wend) exhausted = true;
         }
         bool ready = true;
-        if constexpr (BLOCKS) ready = B->need == 0u;
+        if constexpr (V::kBlocks) ready = B->need == 0u;
         if (!exhausted && ready) {
             const uint32_t n_need = (uint32_t)__popcll(need);
             const uint32_t take = n_need < wend - wbeg ? n_need : wend - wbeg;
@@ -301,17 +300,17 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                 const uint32_t j = a.path.first_pixel + mine;
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
-                if constexpr (SEED && !BLOCKS) *seed = a.tmax;
-                if constexpr (RESTART) *restart = 0u;
-                [[maybe_unused]] float carried = 0.0f;      // (BLOCKS) the seed the pixel brings along
-                if (BLOCKS || !a.path.trace_rays) {
+                if constexpr (V::kSeed && !V::kBlocks) *seed = a.tmax;
+                if constexpr (V::kRestart) *restart = 0u;
+                [[maybe_unused]] float carried = 0.0f;      // (kBlocks) the seed the pixel brings along
+                if (V::kBlocks || !a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;
                     const uint32_t ix = j - row * a.path.width;
                     const uint32_t iy = a.path.rows[row];
                     P.px_tid = iy * a.path.width + ix;
                     P.px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
                     if (by_blocks) {
-                        if constexpr (BLOCKS) {                     // ... and so do later blocks of a launch
+                        if constexpr (V::kBlocks) {                     // ... and so do later blocks of a launch
                             P.px_sample = block_first(a.path.sample_block, a.path.block_min, a.path.block_taper_end, a.path.block_magic == 0u, B->pass);
                             P.px_first = P.px_first && B->pass == 0u;
                             // The seed comes with the pixel from the lane that ended its previous block IN THIS LAUNCH (a pass b > 0: the
@@ -326,10 +325,10 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                         P.px_sample = 0u; P.px_rng = rng_load(a.path.states + P.px_tid);
                         if (!P.px_first) { const float4 acc = a.path.accum[P.px_local]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; }
                     }
-                    if (!BLOCKS && a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
+                    if (!V::kBlocks && a.path.slice_cost) P.px_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
                     const V3 pd = primary_direction(ix, iy, a.path.width, a.path.height, a.path.U, a.path.V, a.path.W);
                     P.px_pdx = pd.x; P.px_pdy = pd.y; P.px_pdz = pd.z;
-                    if constexpr (SEED && BLOCKS) *seed = carried;
+                    if constexpr (V::kSeed && V::kBlocks) *seed = carried;
                 }
             }
         }
@@ -339,12 +338,12 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
 
 // The primary ray of a lane that wants one: the caller's ray (hrt_trace_rays) or the camera ray of the lane's pixel; sets the depth.
 // RECOMPUTE_DIRECTION: make the pixel's direction again instead of keeping px_pd* alive across the traversal (a kernel at its
-// register limit: k_traverse<.., HAS_SPHERES, FUSED>).
+// register limit: k_traverse<.., kSpheres, FUSED>).
 struct PathRay { V3 o, d; };
-template <bool RECOMPUTE_DIRECTION, bool BLOCKS = false>
+template <class V, bool RECOMPUTE_DIRECTION>
 __device__ __forceinline__ PathRay path_primary(PathLane &P, const TraverseArgs &a) {
     PathRay r;
-    if (!BLOCKS && a.path.trace_rays) {
+    if (!V::kBlocks && a.path.trace_rays) {
         // (read as device memory, which it is: through generic pointers hipcc merges these loads with the other branch's into loads through
         // a pointer that is either the caller's ray or the camera in the kernel-argument segment -- a flat_load of kernel arguments)
         const global_floats q = (global_floats)reinterpret_cast<const float *>(a.path.trace_rays + P.px_local);

@@ -13,6 +13,31 @@
 
 namespace hrt {
 
+// ---- what a path kernel IS, as one type: the shared device code (here, path_lane.h, trav_loop.h, fused_body.h) is compiled once per kernel, and
+//      every function of it that depends on the kernel takes that kernel's variant V and reads V::kBlocks, V::kOneGroup, ... where it is explained
+//      what the flag means.  Each translation unit names the variant of its kernel and sets only what the kernel is. ----
+struct PathVariant {      // every flag false
+    static constexpr bool kSpheres = false, kInstanced = false;     // the tree: spheres as well as triangles; two levels (fused_body.h: InstLane)
+    static constexpr bool kReuse = false, kSeed = false;            // repeat primary rays: not traversed (the primary-hit cache); bounded at their known hit (fused_body.h)
+    static constexpr bool kBlocks = false, kCapture = false;        // pixels go round in sample blocks; every pixel's primary hit is kept (path_lane.h)
+    static constexpr bool kOneGroup = false, kRestart = false;      // every hit is instance 0's; ... and repeat primary rays start at their known hit's node (path_lane.h)
+};
+// a kernel that is none of these -- k_traverse (kernels.hip), k_trace_queue (fused_queue.hip): no pixels of its own or no seed, every block in its plain form
+template <bool HAS_SPHERES>
+struct PlainVariant : PathVariant { static constexpr bool kSpheres = HAS_SPHERES; };
+// the persistent kernel (fused_body.h) seeds, unless it does not traverse a pixel's repeat primary rays at all
+template <bool REUSE>
+struct FusedBodyVariant : PathVariant { static constexpr bool kReuse = REUSE, kSeed = !REUSE; };
+// The constraints between the flags, in one place: fused_body asserts this of its variant, once.
+template <class V>
+constexpr bool path_variant_checked() {
+    static_assert(!V::kSeed || !V::kReuse, "the seed bounds the walk of a repeat primary ray, which the primary-hit cache does not traverse");
+    static_assert(!V::kRestart || (V::kOneGroup && V::kSeed), "the restart: the one-group block render (the record rides in binst, which it leaves free), whose repeat primary rays have a window");
+    static_assert(!V::kOneGroup || (V::kBlocks && !V::kSpheres && !V::kCapture), "one hit group: the block render of a one-level tree of triangles");
+    static_assert(!V::kCapture || (!V::kReuse && !V::kBlocks), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
+    static_assert(!V::kBlocks || (!V::kInstanced && !V::kReuse), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
+    return true;
+}
 
 // ---------------------------------------------------------------------------------------
 // small helpers
@@ -291,32 +316,31 @@ __device__ __forceinline__ bool cond_lane(bool c) { return c; }                 
 __device__ __forceinline__ bool cond_lane(WaveCond c) { return __builtin_amdgcn_inverse_ballot_w64(c.m); }
 
 // canonical primitive test (DESIGN.md "canonical intersector"); updates the best hit.
-// INSTANCED (two-level trees, fused.hip): the record is a shared BLAS's, in object space, and so is the ray in `s` by now (the transform
+// kInstanced (two-level trees, fused.hip): the record is a shared BLAS's, in object space, and so is the ray in `s` by now (the transform
 // node did that for triangles and spheres alike); the record does not know who instances it: `inst_cur` does.
 // (test_prim_ray: the ray given explicitly -- a lane of the instanced kernel that has left an instance with leaf tests still to make keeps that
 // instance's object-space ray in LDS while its registers hold the world ray again)
 // (live, triangles only: false rejects the record -- the caller's lane has none and A / B / C are whatever its registers held; the
 // test still runs, so that the caller needs no per-lane branch round it)
 // (Cond: bool, or WaveCond -- triangles only, every lane active -- for the outcome as a wave mask)
-// ONE_GROUP (k_path_one, fused_one.hip: triangles of ONE instance): every record's instance is 0, so it is not read from the record, a
+// kOneGroup (k_path_one, fused_one.hip: triangles of ONE instance): every record's instance is 0, so it is not read from the record, a
 // tie at the same distance goes to the lower primitive id -- what the (instance, primitive) order says when both instances are 0; a
 // ray that has no hit yet holds bprim == kMissPrim, above every id -- and TravState::binst is left alone: whoever reads it takes 0.
-// RESTART (k_path_restart, fused_restart.hip: ONE_GROUP, whose TravState::binst is free): binst keeps the RECORD the best hit was accepted from
+// kRestart (k_path_restart, fused_restart.hip: kOneGroup, whose TravState::binst is free): binst keeps the RECORD the best hit was accepted from
 // (`rec`: the record's index, the lane's pidx) -- kMissPrim, which trav_start leaves there, where the lane has accepted none itself.  The
 // regeneration looks up the node whose leaf slot holds that record, where the pixel's next primary ray starts (fused_body.h: s_restart).
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false, bool RESTART = false>
+template <class V, class Cond = bool>
 __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
                                               const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
                                               Cond live = true, [[maybe_unused]] uint32_t rec = 0u) {
-    static_assert(!HAS_SPHERES || sizeof(Cond) == sizeof(bool), "spheres are tested under per-lane control flow");
-    static_assert(!RESTART || ONE_GROUP, "the record rides in binst, which only the one-group kernels leave free");
+    static_assert(!V::kSpheres || sizeof(Cond) == sizeof(bool), "spheres are tested under per-lane control flow");
     float t, u = 0.0f, v = 0.0f;
     uint32_t prim = __float_as_uint(A.w), inst;
-    if (HAS_SPHERES && __float_as_uint(C.w) == 1u) {
-        inst = INSTANCED ? inst_cur : __float_as_uint(B.w);
+    if (V::kSpheres && __float_as_uint(C.w) == 1u) {
+        inst = V::kInstanced ? inst_cur : __float_as_uint(B.w);
         V3 oo = o, dd = d;
-        if (!INSTANCED && !inst_identity[inst]) {
+        if (!V::kInstanced && !inst_identity[inst]) {
             const float *m = inst_inv + 12 * (size_t)inst;
             oo = mk3(((m[0] * o.x + m[1] * o.y) + m[2] * o.z) + m[3], ((m[4] * o.x + m[5] * o.y) + m[6] * o.z) + m[7],
                      ((m[8] * o.x + m[9] * o.y) + m[10] * o.z) + m[11]);
@@ -345,7 +369,7 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
         // (profiles/r02_valu_issue_patterns_microbench.txt).  Same decisions, same values: a rejected lane's later
         // quantities are never used, det == 0 gives inv = inf and u = NaN or +-inf, which fails the u test like the
         // explicit one does.  (u <= 1 is not tested: v >= 0 and u + v <= 1 imply it, the rounded sum included.)
-        inst = INSTANCED ? inst_cur : __float_as_uint(B.w);
+        inst = V::kInstanced ? inst_cur : __float_as_uint(B.w);
         const V3 e1 = mk3(B.x, B.y, B.z), e2 = mk3(C.x, C.y, C.z);
         const V3 pvec = cross3(d, e2);
         const float det = dot3(e1, pvec);
@@ -356,16 +380,15 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
         v = dot3(d, qvec) * inv;
         t = dot3(e2, qvec) * inv;
         const Cond ok = live & Cond(det != 0.0f) & Cond(u >= 0.0f) & Cond(v >= 0.0f) & Cond(u + v <= 1.0f) & Cond(t > tmin) & Cond(t < tmax_ray);
-        if constexpr (ONE_GROUP) {
-            static_assert(!ONE_GROUP || (!HAS_SPHERES && !INSTANCED), "one hit group: triangles, one level");
+        if constexpr (V::kOneGroup) {
             const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & Cond(prim < s.bprim)));
             const bool mine = cond_lane(better);
             s.bt = mine ? t : s.bt; s.bu = mine ? u : s.bu; s.bv = mine ? v : s.bv;
             s.bprim = mine ? prim : s.bprim;
-            if constexpr (RESTART) s.binst = mine ? rec : s.binst;
+            if constexpr (V::kRestart) s.binst = mine ? rec : s.binst;
             return better;
         }
-        if (!HAS_SPHERES) {
+        if (!V::kSpheres) {
             // closest hit: min t, ties -> lowest (instance, primitive); predicated update
             const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & (Cond(inst < s.binst) | (Cond(inst == s.binst) & Cond(prim < s.bprim)))));
             const bool mine = cond_lane(better);
@@ -385,12 +408,12 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
     return better;
 }
 
-template <bool HAS_SPHERES, bool INSTANCED = false, class Cond = bool, bool ONE_GROUP = false, bool RESTART = false>
+template <class V, class Cond = bool>
 __device__ __forceinline__ Cond test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
                                           const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
                                           Cond live = true, uint32_t rec = 0u) {
-    return test_prim_ray<HAS_SPHERES, INSTANCED, Cond, ONE_GROUP, RESTART>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live, rec);
+    return test_prim_ray<V, Cond>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live, rec);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))

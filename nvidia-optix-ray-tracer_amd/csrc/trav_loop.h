@@ -42,7 +42,7 @@ __device__ __forceinline__ bool lane_bit(uint64_t mask) { return __builtin_amdgc
 
 // The wave's tail-splitting mailboxes: __shared__ arrays of kTraverseBlock entries each, declared in the kernels.  One mailbox
 // per lane that owns a split ray (indexed by its home lane) collects the pieces' hits; `pending` counts the pieces still under
-// way, `pair` matches donors with free lanes for one hand-over.  (k_fused's INSTANCED instantiation, where tail splitting is
+// way, `pair` matches donors with free lanes for one hand-over.  (k_fused's kInstanced instantiation, where tail splitting is
 // off, parks a lane's world ray in the same memory while the lane is inside an instance: fused.hip, InstLane.)
 struct Mailboxes {
     float *t, *u, *v;
@@ -63,12 +63,12 @@ struct NoInstLane { static constexpr uint32_t inst_cur = 0u; };
 //      `is_free`: this lane has nothing of its own to do and may take a piece. ----
 
 // (one donation per busy lane and iteration: more rounds of this change nothing, r02_sweep_tile_tail.txt)
-// ONE_GROUP, here and in the three blocks below (k_path_one, fused_one.hip): every hit is instance 0's, so TravState::binst is not kept --
+// kOneGroup, here and in the three blocks below (k_path_one, fused_one.hip): every hit is instance 0's, so TravState::binst is not kept --
 // a mailbox's `inst` is given 0, and nobody takes a lane's binst from there.
-// RESTART (k_path_restart, fused_restart.hip: ONE_GROUP with the best hit's record in binst, trav_common.h: test_prim_ray): the mailboxes' `inst`
+// kRestart (k_path_restart, fused_restart.hip: kOneGroup with the best hit's record in binst, trav_common.h: test_prim_ray): the mailboxes' `inst`
 // array is not theirs any more -- it holds the lanes' restart nodes (fused_body.h: s_restart) -- so it is neither written nor read here, and a
 // hit that comes out of a mailbox has no record: binst = kNoWork, the pixel's next primary ray walks from the root.
-template <bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mailboxes &mb, uint2 (*nodes)[kTraverseBlock], bool is_free, uint32_t tx, float tmin, float tmax_ray) {
     const uint64_t free_m = __ballot(is_free);
     const uint64_t donors = F.alive & __ballot(L.nsp > L.base);
@@ -85,7 +85,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
             if (!F.shared) {
                 F.shared = true; F.home = tx;
                 mb.t[tx] = L.s.bt; mb.u[tx] = L.s.bu; mb.v[tx] = L.s.bv; mb.prim[tx] = L.s.bprim;
-                if constexpr (!RESTART) mb.inst[tx] = ONE_GROUP ? 0u : L.s.binst;
+                if constexpr (!V::kRestart) mb.inst[tx] = V::kOneGroup ? 0u : L.s.binst;
                 mb.pending[tx] = 2u;
             } else atomicAdd(&mb.pending[F.home], 1u);
             mb.pair[drank] = tx;
@@ -103,7 +103,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
             lean_start(L, mk3(r_ox, r_oy, r_oz), mk3(r_dx, r_dy, r_dz), tmax_ray, tmin);     // the same reciprocals and octant as the owner's (a piece culls from the launch's tmin)
             F.home = r_home & 0xffu; F.shared = true;
             s.bt = mb.t[F.home]; s.bu = mb.u[F.home]; s.bv = mb.v[F.home]; s.bprim = mb.prim[F.home];
-            if constexpr (!ONE_GROUP) s.binst = mb.inst[F.home];
+            if constexpr (!V::kOneGroup) s.binst = mb.inst[F.home];
             s.cur = make_uint2(r_gx, r_gy);           // a sibling group with hits: only those are pushed
             lean_pick_node(L);                        // (replaces the root lean_start chose)
         }
@@ -113,7 +113,7 @@ __device__ __forceinline__ void tail_donate(LeanLane &L, LaneFlags &F, const Mai
 }
 
 // pieces of split rays publish their improvements one lane at a time (rare: a few per ray) ...
-template <bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool improved, uint32_t tx) {
     uint64_t pub = __ballot(improved && F.shared);
     while (pub) {
@@ -122,11 +122,11 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
         if (tx == l) {
             const TravState &s = L.s;
             const float mt = mb.t[F.home];
-            const uint64_t mid = ((uint64_t)(RESTART ? 0u : mb.inst[F.home]) << 32) | mb.prim[F.home];
-            const uint64_t id = ((uint64_t)(ONE_GROUP ? 0u : s.binst) << 32) | s.bprim;
+            const uint64_t mid = ((uint64_t)(V::kRestart ? 0u : mb.inst[F.home]) << 32) | mb.prim[F.home];
+            const uint64_t id = ((uint64_t)(V::kOneGroup ? 0u : s.binst) << 32) | s.bprim;
             if (lane_bit(F.any) ? mb.prim[F.home] == kMissPrim : (s.bt < mt || (s.bt == mt && id < mid))) {
                 mb.t[F.home] = s.bt; mb.u[F.home] = s.bu; mb.v[F.home] = s.bv; mb.prim[F.home] = s.bprim;
-                if constexpr (!RESTART) mb.inst[F.home] = ONE_GROUP ? 0u : s.binst;
+                if constexpr (!V::kRestart) mb.inst[F.home] = V::kOneGroup ? 0u : s.binst;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -136,21 +136,21 @@ __device__ __forceinline__ void tail_publish(const LeanLane &L, const LaneFlags 
 
 // ... and take over what another piece has found closer; an any-hit ray is done once any piece has hit.  Returns the lane's hit_any
 // (by value on purpose: as a `bool &` it cost each one-level k_fused three more spilled registers)
-template <bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ bool tail_adopt(LeanLane &L, const LaneFlags &F, const Mailboxes &mb, bool hit_any) {
     if (lane_bit(F.alive) && F.shared) {
         if (lane_bit(F.any)) hit_any = hit_any || mb.prim[F.home] != kMissPrim;
         else if (mb.t[F.home] < L.s.bt) {
             L.s.bt = mb.t[F.home]; L.s.bu = mb.u[F.home]; L.s.bv = mb.v[F.home]; L.s.bprim = mb.prim[F.home];
-            if constexpr (!ONE_GROUP) L.s.binst = mb.inst[F.home];
-            if constexpr (RESTART) L.s.binst = kNoWork;
+            if constexpr (!V::kOneGroup) L.s.binst = mb.inst[F.home];
+            if constexpr (V::kRestart) L.s.binst = kNoWork;
         }
     }
     return hit_any;
 }
 
 // a piece whose lane reports `done` retires; the owner of the ray takes the merged hit once the last piece has
-template <bool ONE_GROUP = false, bool RESTART = false>
+template <class V>
 __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mailboxes &mb, bool done, uint32_t tx) {
     // a piece that has finished has nothing left to merge: the mailbox holds the ray's best hit
     const bool retires = lane_bit(F.alive) && done && F.shared;
@@ -165,8 +165,8 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
     const bool merged = F.shared && !lane_bit(F.alive) && F.home == tx && mb.pending[tx] == 0u;
     if (merged) {
         L.s.bt = mb.t[tx]; L.s.bu = mb.u[tx]; L.s.bv = mb.v[tx]; L.s.bprim = mb.prim[tx];
-        if constexpr (!ONE_GROUP) L.s.binst = mb.inst[tx];
-        if constexpr (RESTART) L.s.binst = kNoWork;
+        if constexpr (!V::kOneGroup) L.s.binst = mb.inst[tx];
+        if constexpr (V::kRestart) L.s.binst = kNoWork;
         F.shared = false;
     }
     F.waiting |= __ballot(merged);
@@ -180,24 +180,24 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
 //   nodes / leaves: the wave's LDS stacks; ldsn / ldsl: byte address in LDS of this lane's column of each
 //   leaf_hold: lean_bookkeeping_masked's `hold`;  may_help: the lane has no work of its own outside the loop either (tail splitting)
 // `a` is the kernel's argument block, by reference: only scalars are read from it, where they are used.
-// kLaneLo: the node step's interval begins at the lane's TravState::tlo (the kernels that give repeat primary rays a window) instead of the
-// wave-uniform tmin -- the same instructions, one operand a vector register where it was a scalar one.
-// ONE_GROUP (k_path_one): the primitive test and the tail-splitting blocks in their one-instance forms (trav_common.h: test_prim_ray).
-// RESTART (k_path_restart): ... which also keep the record of the lane's best hit (the primitive test is told the record it tests: pidx).
-template <bool HAS_SPHERES, bool INSTANCED, bool kTail, bool kLaneLo = false, bool ONE_GROUP = false, bool RESTART = false, class Inst>
+// V: the kernel's variant (trav_common.h: PathVariant).  kSeed: the node step's interval begins at the lane's TravState::tlo (the kernels
+// that give repeat primary rays a window) instead of the wave-uniform tmin -- the same instructions, one operand a vector register, not a scalar one.
+// kOneGroup (k_path_one): the primitive test and the tail-splitting blocks in their one-instance forms (trav_common.h: test_prim_ray).
+// kRestart (k_path_restart): ... which also keep the record of the lane's best hit (the primitive test is told the record it tests: pidx).
+template <class V, bool kTail, class Inst>
 __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Inst &I, LaneStats &stats, const Mailboxes &mb,
                                                   uint2 (*nodes)[kTraverseBlock], uint2 (*leaves)[kTraverseBlock], uint32_t ldsn, uint32_t ldsl,
                                                   const TraverseArgs &a, const char *node_bytes, const char *prim_bytes,
                                                   float tmin, float tmax_ray, uint32_t leaf_hold, uint32_t max_alive, bool may_help, uint32_t tx) {
-    constexpr bool kSplit = kTail && !INSTANCED;        // (tail splitting is off for two-level trees)
+    constexpr bool kSplit = kTail && !V::kInstanced;        // (tail splitting is off for two-level trees)
     // the registers the loads land in: "defined" without an instruction (lanes that load nothing never look at theirs)
     f32x4 rpa, rpb, rpc;
     u32x4 rn0, rn1, rn2, rn3, rn4;
     asm volatile("" : "=v"(rpa), "=v"(rpb), "=v"(rpc), "=v"(rn0), "=v"(rn1), "=v"(rn2), "=v"(rn3), "=v"(rn4));
     // The lanes that want a primitive / a node.  The bookkeeping sequence has just had both in exec and hands them out, so the one-level
     // copy without tail splitting carries them round the loop; found by compare where something else writes pidx / nidx: a new ray (here,
-    // at the entry), tail_donate (the kTail copy), switch_frames (INSTANCED).
-    constexpr bool kCarryWork = !kTail && !INSTANCED;
+    // at the entry), tail_donate (the kTail copy), switch_frames (kInstanced).
+    constexpr bool kCarryWork = !kTail && !V::kInstanced;
     // The same copy uses the blocks' exec-is-full forms (trav_lean.h: nothing saved, exec set back to all ones).  Every lane IS active at the
     // top level of this loop's body: a workgroup is one wave of exactly kTraverseBlock = 64 lanes (static_assert and launch), and every
     // branch round the loop and round this call -- the regeneration's, the choice of the copy, the exits -- is taken on a value that is the
@@ -212,7 +212,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
     F.alive = wave_first_u64(F.alive); F.waiting = wave_first_u64(F.waiting); F.any = wave_first_u64(F.any);
     uint64_t mask_p = __ballot(L.pidx != kNoWork), mask_n0 = __ballot(L.nidx != kNoWork);
     for (;;) {
-        if (kSplit && a.tail_split) tail_donate<ONE_GROUP, RESTART>(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmin, tmax_ray);
+        if (kSplit && a.tail_split) tail_donate<V>(L, F, mb, nodes, !lane_bit(F.alive | F.waiting) && may_help && !F.shared, tx, tmin, tmax_ray);
 
         // ---- G. fetch what the lanes need next: primitives first, nodes second -- for the lanes that need one only (the
         //      instruction slots of the loads are not saved, but their L1 / TA cycles are).  The node loads are issued even when
@@ -240,18 +240,18 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             wait_prim_loads(rpa, rpb, rpc);
             const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
                          pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
-            if constexpr (!HAS_SPHERES)
-                improved_m = test_prim<false, INSTANCED, WaveCond, ONE_GROUP, RESTART>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p), L.pidx).m;
+            if constexpr (!V::kSpheres)
+                improved_m = test_prim<V, WaveCond>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p), L.pidx).m;
             else {
                 bool improved = false;
-                if (L.pidx != kNoWork) improved = test_prim<true, INSTANCED>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
+                if (L.pidx != kNoWork) improved = test_prim<V>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
                 improved_m = __ballot(improved);
             }
             hit_m = F.any & improved_m;
         }
         if (kSplit && a.tail_split) {
-            tail_publish<ONE_GROUP, RESTART>(L, F, mb, lane_bit(improved_m), tx);
-            hit_m = __ballot(tail_adopt<ONE_GROUP, RESTART>(L, F, mb, lane_bit(hit_m)));
+            tail_publish<V>(L, F, mb, lane_bit(improved_m), tx);
+            hit_m = __ballot(tail_adopt<V>(L, F, mb, lane_bit(hit_m)));
         }
         const bool hit_any = lane_bit(hit_m);
         // ---- A. node step: one-level trees, for the whole wave (arithmetic only; what lanes without a node made of their
@@ -260,11 +260,11 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         __builtin_amdgcn_s_setprio(HRT_PRIO_NODE);
         wait_node_loads(rn0, rn1, rn2, rn3, rn4);
         [[maybe_unused]] bool enter = false;
-        if constexpr (!INSTANCED) {
-            node_slab_test<kSlabInterval01>(L.s, kLaneLo ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+        if constexpr (!V::kInstanced) {
+            node_slab_test<kSlabInterval01>(L.s, V::kSeed ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
         } else {
             enter = L.nidx != kNoWork && !hit_any && rn0.w == 0u;          // a transform node: word 3 == 0
-            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test<kSlabInterval01>(L.s, kLaneLo ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
+            if (L.nidx != kNoWork && !hit_any && !enter) node_slab_test<kSlabInterval01>(L.s, V::kSeed ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
             enter = I.enter_instance(enter, L.s, child, rn0, rn1, rn2, rn3, rn4, mb, tx);
             stats.entered(enter);
         }
@@ -280,7 +280,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         const uint64_t book = F.alive & ~hit_m;
         uint64_t fin;
         [[maybe_unused]] uint32_t lane = 0u;
-        if constexpr (!INSTANCED) {
+        if constexpr (!V::kInstanced) {
             fin = lean_bookkeeping_masked<kFull>(L, child, tri, ldsn, ldsl, (uint32_t)a.postpone_pct, (uint32_t)a.leaf_quorum, leaf_hold, book, mask_n0, mask_p);
         } else {
             // (this instantiation is two registers over its budget and the compiler's choice of what to keep in scratch is the two
@@ -293,11 +293,11 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         }
         // finished: by an any-hit, or with nothing left to do.  All of it is mask arithmetic (`fin` only has bits inside `book`)
         uint64_t done_m = hit_m | fin;
-        if constexpr (INSTANCED) done_m = __ballot(I.switch_frames(enter, lane_bit(done_m), hit_any, L, mb, nodes, tx, lane));
+        if constexpr (V::kInstanced) done_m = __ballot(I.switch_frames(enter, lane_bit(done_m), hit_any, L, mb, nodes, tx, lane));
         // (a piece of a split ray does not wait for a regeneration: tail_retire signs it off.  Only tail_donate shares rays)
         const uint64_t rest = kSplit ? done_m & ~__ballot(F.shared) : done_m;
         F.alive &= ~rest; F.waiting |= rest;
-        if (kSplit && a.tail_split) tail_retire<ONE_GROUP, RESTART>(L, F, mb, lane_bit(done_m), tx);
+        if (kSplit && a.tail_split) tail_retire<V>(L, F, mb, lane_bit(done_m), tx);
         if constexpr (kTail) {
             if (F.alive == 0ull || (uint32_t)__popcll(F.waiting) >= (uint32_t)a.tail_regen) break;
         } else if ((uint32_t)__popcll(F.alive) <= max_alive) break;      // (every lane finished included)

@@ -1,5 +1,5 @@
-"""What the regeneration of k_path_blocks no longer does (path_lane.h): the BLOCKS instantiation takes a render in
-sample blocks for granted -- no callers' rays, no cost probe, no slice order, sample_block != 0 (launch_fused_blocks refuses anything
+"""What the regeneration of k_path_blocks no longer does (path_lane.h): the kBlocks instantiation takes a render in
+sample blocks for granted -- no callers' rays, no cost probe, no slice order, sample_block != 0 (path_launch_admitted refuses anything
 else) -- so its code neither loads PathArgs::trace_rays, slice_cost and slice_order from the kernel-argument segment nor branches on
 them, and the scalar round trips of a regeneration are held to what the build shows.  Read from the assembly the Makefile's flags
 produce, compiled once for the module; the fields' offsets come from a host program built against device_types.h."""

@@ -125,7 +125,8 @@ def test_the_regeneration_has_fewer_vector_loads(compiled):
 
 def test_the_other_translation_units_do_not_name_the_flag():
     for stem in ("fused", "fused_blocks", "fused_capture", "fused_queue", "kernels"):
-        assert "ONE_GROUP" not in (ROOT / CSRC / f"{stem}.hip").read_text(), stem
+        text = (ROOT / CSRC / f"{stem}.hip").read_text()
+        assert "ONE_GROUP" not in text and "kOneGroup" not in text, stem
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait():

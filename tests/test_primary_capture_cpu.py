@@ -77,13 +77,18 @@ def test_hand_issued_loads_of_the_capture_kernels_are_not_touched_before_their_w
 
 
 def test_the_capture_is_compiled_into_its_own_kernels_only():
-    """The flag is a template parameter that defaults to false: fused.hip, fused_blocks.hip and kernels.hip do not name it, so their
+    """The flag is false in the variant every kernel starts from (trav_common.h: PathVariant): fused.hip, fused_blocks.hip and kernels.hip do not name it, so their
     kernels' instruction streams are what they were (tests/test_host_cpu.py and tests/test_path_kernel_spills_cpu.py pin them)."""
     for stem in ("fused", "fused_blocks", "kernels", "fused_queue"):
         text = (ROOT / CSRC / f"{stem}.hip").read_text()
-        assert "CAPTURE" not in text and "k_path_capture" not in text, stem
+        assert "CAPTURE" not in text and "kCapture" not in text and "k_path_capture" not in text, stem
+    # ... and the file instantiates exactly the capture variant, with exactly the flags it had: the kernel's spheres and levels, the capture
+    # -- no primary-hit cache, no sample blocks
     body = (ROOT / CSRC / "fused_capture.hip").read_text()
-    assert "fused_body<HAS_SPHERES, INSTANCED, false, false, true>" in body
+    assert re.findall(r"fused_body<([^;]*)>\(", body) == ["CaptureVariant<HAS_SPHERES, INSTANCED>"]
+    variant = re.search(r"template <bool HAS_SPHERES, bool INSTANCED>\nstruct CaptureVariant : (\S+) \{(.*?)\};", body, re.S)
+    assert variant.group(1) == "FusedBodyVariant<false>"
+    assert re.sub(r"\s+", " ", variant.group(2)).strip() == "static constexpr bool kSpheres = HAS_SPHERES, kInstanced = INSTANCED, kCapture = true;"
 
 
 def test_stats_mirror_and_entry_point(hrt):

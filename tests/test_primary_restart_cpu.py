@@ -309,8 +309,15 @@ def test_hand_issued_loads_are_not_touched_before_their_wait():
 
 def test_the_other_translation_units_do_not_name_the_flag():
     for stem in ("fused", "fused_blocks", "fused_one", "fused_capture", "fused_queue", "kernels"):
-        assert "RESTART" not in (ROOT / CSRC / f"{stem}.hip").read_text(), stem
-    assert "fused_body<false, false, false, true, false, true, true>" in (ROOT / CSRC / "fused_restart.hip").read_text()
+        text = (ROOT / CSRC / f"{stem}.hip").read_text()
+        assert "RESTART" not in text and "kRestart" not in text, stem
+    # ... and the file instantiates exactly the restart variant (trav_common.h: PathVariant), with exactly the flags it had: one group, in blocks, restart
+    # -- no spheres, one level, no capture, no primary-hit cache (hence the seed)
+    body = (ROOT / CSRC / "fused_restart.hip").read_text()
+    assert re.findall(r"fused_body<([^;]*)>\(", body) == ["RestartVariant"]
+    variant = re.search(r"struct RestartVariant : (\S+) \{(.*?)\};", body, re.S)
+    assert variant.group(1) == "FusedBodyVariant<false>"
+    assert re.sub(r"\s+", " ", variant.group(2)).strip() == "static constexpr bool kBlocks = true, kOneGroup = true, kRestart = true;"
 
 
 def test_the_knob_and_the_counter(hrt):
