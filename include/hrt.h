@@ -190,6 +190,48 @@ int  hrt_sync(HrtContext *ctx, void *stream);
  * HRT_ERR_STATE when the context holds no valid capture (see the flag).  Enqueued only, behind the launch on the same stream. */
 int  hrt_primary_hits_get(HrtContext *ctx, float *d_t, float *d_u, float *d_v, uint32_t *d_prim, uint32_t *d_inst, void *stream);
 
+/* ---- adaptive sampling: per-pixel sample counts ----
+ * hrt_render_accumulate is hrt_render_launch over sums the CALLER keeps, every pixel with a sample count of its own.
+ *   d_sum, d_taken   in and out, width * height entries each in frame order (p = y * width + x).  d_sum[p].xyz is the sum of the linear
+ *                    radiance of the samples pixel p has taken so far, d_sum[p].w the sum of l * l over them, l = (0.2126 r.x + 0.7152 r.y)
+ *                    + 0.0722 r.z the luminance of one sample's radiance r; d_taken[p] is how many samples that is.  A frame starts with
+ *                    d_taken zeroed; d_sum need not be.
+ *   d_counts         frame order, may be NULL: pixel p takes c = d_counts ? min(d_counts[p], spp) : spp more samples.  spp is 1 .. 65536.
+ * Per pixel of the tile: the c samples are taken in order on the pixel's RNG stream, exactly as hrt_render_launch takes them, and added to
+ * the sum in that order -- where d_taken[p] is 0 on entry the first one is assigned, not added, .w included; d_taken[p] += c; the RNG state
+ * is stored.  c == 0: sum, count and state are untouched and no ray is traced.  Then every tile pixel with d_taken[p] > 0 gets colorBuffer[p] =
+ * colorToFloat4(sum.xyz / (float)d_taken[p]) (alpha 1; the linear debug output likewise; albedoBuffer / normalBuffer zeroed), hrt_render_launch's
+ * arithmetic; a tile pixel whose d_taken[p] is still 0 keeps whatever it had.  Rows outside the tile are neither read nor written.
+ * THE INVARIANT: after any sequence of these calls on a frame, pixel p's sum.xyz / taken, colour, linear output and RNG state are bit for bit
+ * those of ONE hrt_render_launch(spp = d_taken[p]) from the same initial states.  The caller keeps every total below 2^24 (float sums of counts).
+ * One launch of one kernel (k_path_counts): no sample blocks, no cost-order probe, no cutting into launches of HRT_FUSED_MAX_SPP;
+ * HRT_CTX_REUSE_PRIMARY and HRT_CTX_CAPTURE_PRIMARY are ignored and a capture the context holds is invalidated, as by any other launch;
+ * HRT_SEED_PRIMARY applies.  HrtStats.rays* count the traced rays, HrtStats.paths grows by the samples taken.
+ * HRT_ERR_STATE: a context under HRT_CTX_COUNT, HRT_FUSED != 1, a tree outside k_fused's limits (HRT_FUSED_MAX_DEPTH, HRT_FUSED_MAX_BYTES), a
+ * call before hrt_materials_set.  HRT_ERR_INVALID: NULL d_sum / d_taken / colorBuffer, spp out of range.  A refused call touches nothing.
+ * Enqueued only. */
+int  hrt_render_accumulate(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                           uint32_t spp, const uint32_t *d_counts,
+                           HrtFloat4 *d_sum, uint32_t *d_taken,
+                           const HrtTile *tile, void *stream);
+
+/* hrt_sample_counts: from a frame's sums (above), how many MORE samples each pixel should take -- d_counts for the next hrt_render_accumulate.
+ * Per pixel, in float32 without contraction, in this order: n = (float)taken; taken < 2: v = +inf (nothing known yet), else m1 = l(sum.xyz) / n,
+ * m2 = sum.w / n, v = fmaxf(0, m2 - m1 * m1) (a NaN gives 0); V = the fmaxf of v over the pixels of the (2 radius + 1)^2 window that lie
+ * inside the frame; x = V / (target_sigma * target_sigma); total = x >= (float)max_total ? max_total : (uint32_t)ceilf(x) (a NaN x: 0), then
+ * total = max(total, min_total); d_counts[p] = total > taken ? total - taken : 0.  No global reduction: the result does not depend on the
+ * launch's geometry.  NULL h_params: the defaults.  HRT_ERR_INVALID for parameters out of range; nothing is written then.  Enqueued only. */
+typedef struct HrtSampleCountParams {
+    float    target_sigma;   /* wanted standard deviation of a pixel's mean luminance (linear), > 0, finite   (default 0.05) */
+    uint32_t min_total;      /* every pixel ends with at least this many samples in total, 1..65536           (default 1)    */
+    uint32_t max_total;      /* ... and at most this many, min_total..65536                                   (default 64)   */
+    uint32_t radius;         /* a pixel takes the largest variance within this many pixels, 0..2              (default 1)    */
+    uint32_t reserved[2];    /* must be 0 */
+} HrtSampleCountParams;
+int  hrt_sample_counts_default_params(HrtSampleCountParams *out);
+int  hrt_sample_counts(HrtContext *ctx, const HrtFloat4 *d_sum, const uint32_t *d_taken, uint32_t width, uint32_t height,
+                       const HrtSampleCountParams *h_params, uint32_t *d_counts, void *stream);
+
 /* replaces convertFloat4ToUchar4Kernel, src/Global/RendererImpl.cu:672-678 (second sRGB
  * encode: quirk Q7) */
 int  hrt_to_rgba8(HrtContext *ctx, const HrtFloat4 *d_src, HrtUchar4 *d_dst,

@@ -108,9 +108,15 @@ class DenoiseVarianceParams(C.Structure):
     _fields_ = [("sigma_luminance", C.c_float), ("history_min", C.c_uint32), ("variance_floor", C.c_float), ("reserved", C.c_uint32)]
 
 
+class SampleCountParams(C.Structure):
+    """HrtSampleCountParams (include/hrt.h): the allocator's target, the limits of a pixel's total and the window of the variance."""
+    _fields_ = [("target_sigma", C.c_float), ("min_total", C.c_uint32), ("max_total", C.c_uint32), ("radius", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 DENOISE_GUIDE_BYTES = 16        # HrtDenoiseGuide: normal[3], albedo[3] as IEEE halves, depth (float)
 
 assert C.sizeof(DenoiseParams) == 24 and C.sizeof(DenoiseTemporalParams) == 16 and C.sizeof(DenoiseVarianceParams) == 16
+assert C.sizeof(SampleCountParams) == 24
 assert C.sizeof(GlobalParams) == 16 and C.sizeof(RayGenParams) == 80 and C.sizeof(MissParams) == 12
 assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof(Instance) == 80
 
@@ -131,6 +137,7 @@ EXPORTS = [
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
     "hrt_denoise_temporal_rebind", "hrt_denoise_temporal_rebind_geometry",
     "hrt_denoise_variance_default_params", "hrt_denoise_filter_variance", "hrt_denoise_variance_launch", "hrt_debug_denoise_variance_state",
+    "hrt_render_accumulate", "hrt_sample_counts_default_params", "hrt_sample_counts",
 ]
 
 
@@ -215,6 +222,10 @@ def load_library():
     lib.hrt_denoise_variance_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
                                                 C.POINTER(DenoiseTemporalParams), C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p]
     lib.hrt_debug_denoise_variance_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hrt_render_accumulate.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(Tile), C.c_void_p]
+    lib.hrt_sample_counts_default_params.argtypes = [C.POINTER(SampleCountParams)]
+    lib.hrt_sample_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SampleCountParams), C.c_void_p, C.c_void_p]
     lib.hrt_host_free.argtypes = [C.POINTER(BvhBlob)]
     lib.hrt_host_free.restype = None
     _lib = lib
@@ -226,4 +237,4 @@ from . import scenes  # noqa: E402
 
 __all__ = ["load_library", "Renderer", "configure_camera", "tile_for_rank", "reduce_tiles", "scenes", "HrtError",
            "GlobalParams", "RayGenParams", "MissParams", "HitGroupParams", "SbtRecord", "Instance", "Tile", "Stats", "DenoiseParams",
-           "DenoiseTemporalParams", "DenoiseVarianceParams"]
+           "DenoiseTemporalParams", "DenoiseVarianceParams", "SampleCountParams"]

@@ -65,6 +65,8 @@ struct PathArgs {
     const uint32_t *slice_order;   // order in which the slices are handed out (most expensive first); NULL: as they lie
                                    // (k_path_restart, a block render, which has no slice order: the tree's leaf_parent table, one word per record --
                                    // put here by the restart launch, fused_restart.hip, never by the caller)
+                                   // (k_path_counts, which has no slice order either: the per-pixel sample counts in frame order, or NULL; its sums, also in
+                                   // frame order, ride in accum and the samples they hold in trace_inst -- put there by hrt_render_accumulate, path_lane.h: kCounts)
     float center[3], U[3], V[3], W[3], bg[3];
     uint32_t block_min;            // sample blocks, tapered: the smallest block (below; in what was padding: the offsets of everything else are as before)
     RngState *states;
@@ -324,6 +326,7 @@ enum class PathKernel {
     OneGroup,           // k_path_one (fused_one.hip): the block render of a scene with one hit group
     Restart,            // k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit
     Round1,             // k_traverse<.., FUSED> (kernels.hip): round 1's fused kernel, for the trees k_fused cannot take
+    Counts              // k_path_counts (fused_counts.hip): k_fused<S, I, false> over a caller's sums, every pixel with a sample count of its own (hrt_render_accumulate)
 };
 struct PathScene { bool one_level; uint32_t n_instances; bool has_spheres; const uint32_t *leaf_parent; };      // what the TraverseArgs do not say about the tree (leaf_parent: below, or NULL)
 // What each kernel takes for granted, in one place: its regeneration does not look at the fields it is compiled without, so a launch that
@@ -341,13 +344,16 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
         case PathKernel::OneGroup: return one_group;
         case PathKernel::Restart: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;      // (the table, and the window its rays start in)
         case PathKernel::Round1: return true;
+        // (accum: the caller's sums, trace_inst: the samples they hold, slice_order: the counts or NULL -- so no callers' rays, no cost probe, no order)
+        case PathKernel::Counts: return p.sample_block == 0u && p.trace_rays == nullptr && p.primary_cache == nullptr && p.slice_cost == nullptr &&
+                                        p.accum != nullptr && p.trace_inst != nullptr && p.spp != 0u;
     }
     return false;
 }
 // The one launch entry of the path kernels (fused.hip).  false: refused (path_launch_admitted), nothing launched.
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);
 using PathLauncher = void(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);      // (its halves in the other kernels' translation units: each launches its own kernel)
-PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_round1;
+PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_round1, launch_path_counts;
 // leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
 // counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
 // primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.
@@ -359,6 +365,23 @@ void launch_bin(const BinArgs &a, uint32_t grid_blocks, hipStream_t s);
 void launch_shade(const ShadeArgs &a, int program, uint32_t grid_blocks, hipStream_t s);
 void launch_accumulate(const AccumArgs &a, uint32_t grid_blocks, hipStream_t s);
 void launch_finalize(const FinalizeArgs &a, hipStream_t s);
+// hrt_render_accumulate's finalize (sample_counts.hip): per tile pixel taken += c, colour from sum / taken where that is not 0; c = counts ?
+// min(counts[p], spp) : spp as the path kernel took it.  The slice counters are zeroed as by k_finalize; with counts set the launch's samples are added to *paths.
+struct FinalizeCountsArgs {
+    const float4 *sum; uint32_t *taken; const uint32_t *counts; const uint32_t *rows;
+    uint32_t n_tile_pixels, width, spp;
+    float4 *color, *albedo, *normal, *linear;
+    uint32_t *reset_counters; uint32_t n_reset;
+    unsigned long long *paths;
+};
+void launch_finalize_counts(const FinalizeCountsArgs &a, hipStream_t s);
+// hrt_sample_counts (sample_counts.hip): how many more samples each pixel of a frame takes, from its sums (include/hrt.h)
+struct SampleCountArgs {
+    const float4 *sum; const uint32_t *taken; uint32_t *counts;
+    uint32_t width, height, radius, min_total, max_total;
+    float target_sigma;
+};
+void launch_sample_counts(const SampleCountArgs &a, hipStream_t s);
 void launch_to_rgba8(const float4 *src, uchar4 *dst, uint32_t n, hipStream_t s);
 void launch_color_to_float4(const float4 *src, float4 *dst, uint32_t n, hipStream_t s);
 void launch_pack_rays(const float *o, const float *d, uint32_t n, RayRec *rays, hipStream_t s);

@@ -53,6 +53,7 @@ bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScen
         case PathKernel::OneGroup: launch_path_one(a, scene, grid_blocks, s); break;
         case PathKernel::Restart: launch_path_restart(a, scene, grid_blocks, s); break;
         case PathKernel::Round1: launch_path_round1(a, scene, grid_blocks, s); break;
+        case PathKernel::Counts: launch_path_counts(a, scene, grid_blocks, s); break;
     }
     return true;
 }

@@ -1,6 +1,6 @@
 // fused_body.h -- the body of the persistent path kernel, ONCE, for the kernels that run it: k_fused (fused.hip), k_path_blocks
 // (fused_blocks.hip: pixels handed out in sample blocks, path_lane.h), k_path_one (fused_one.hip: k_path_blocks for a scene with one hit group)
-// and k_path_capture (fused_capture.hip: primary hits kept per pixel).
+// k_path_capture (fused_capture.hip: primary hits kept per pixel) and k_path_counts (fused_counts.hip: a sample count per pixel, the caller's sums).
 // What the body does is described at the top of fused.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -132,6 +132,7 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 // decides ties by the primitive id alone (trav_common.h: test_prim_ray).
 // kRestart: k_path_restart (fused_restart.hip) -- k_path_one whose repeat primary rays, which already start inside a window under their known hit,
 // also start at the NODE whose leaf slot holds that hit's record instead of at the root (path_lane.h: path_finish).
+// kCounts: k_path_counts (fused_counts.hip) -- every pixel takes its own number of samples and continues a sum the caller keeps (path_lane.h).
 template <class V>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
@@ -173,7 +174,7 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     F.home = tx;
     bool exhausted = false;                 // wave-uniform: no pixels left to start
 
-    PathLane P;                             // the lane's pixel: path_lane.h
+    std::conditional_t<V::kCounts, CountsLane, PathLane> P;      // the lane's pixel: path_lane.h
     uint32_t chain[4] = {0u, 0u, 0u, 0u};   // ... and the albedo chain of its path (kOneGroup: never written, never read)
     LaneStats stats;
 

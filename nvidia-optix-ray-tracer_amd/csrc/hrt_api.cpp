@@ -405,24 +405,42 @@ static SampleSchedule sample_schedule(uint32_t spp, uint32_t big, uint32_t min) 
 
 // ---- fused path mode: ONE launch, every lane owns a pixel and runs all its samples (generate, traverse, shade, accumulate in place).
 //      No stage barriers.  The default (HRT_FUSED=1); trees outside k_fused's limits take round 1's path kernel. ----
+// What every launch of a path kernel over a tile's pixels starts from (render_fused, hrt_render_accumulate): the tree, the regeneration's
+// thresholds, the slice counters, the tile, the camera, the miss colour, the RNG states, the material tables, the ray counters.
+static TraverseArgs fused_render_args(const LaunchFrame &f) {
+    HrtContext *ctx = f.ctx; const Tlas *t = f.t; const HrtRayGenParams *rg = f.rg;
+    Workspace &w = ctx->ws;
+    TraverseArgs ta = traverse_args(ctx, *t, kFloatZero, kFloatInfinity);
+    ta.fetch_counter = w.set[0].stages[0].fetch;
+    ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
+    ta.leaf_hold = leaf_hold_for(ctx, *t);
+    if (ctx->refill_auto && t->two_level) ta.refill_threshold = 12;      // (a two-level ray is long and its lanes finish far apart: 12 against 20 is +1.4-2.3 %, flattened trees lose 4 %)
+    PathArgs &pa = ta.path;
+    pa.rows = w.rows; pa.first_pixel = 0; pa.n_tile_pixels = f.n; pa.width = rg->width; pa.height = rg->height; pa.spp = f.spp;
+    std::memcpy(pa.center, &rg->cameraCenter, 12); std::memcpy(pa.U, &rg->cameraU, 12);
+    std::memcpy(pa.V, &rg->cameraV, 12); std::memcpy(pa.W, &rg->cameraW, 12);
+    pa.bg[0] = ctx->miss.backgroundColor.x; pa.bg[1] = ctx->miss.backgroundColor.y; pa.bg[2] = ctx->miss.backgroundColor.z;
+    pa.states = reinterpret_cast<RngState *>(f.h_params->stateArray);
+    pa.hitgroups = ctx->d_hitgroups; pa.inst_program = ctx->d_inst_program; pa.accum = w.accum;
+    pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
+    return ta;
+}
+// ... and the grid of such a launch: one-wave workgroups, blocks_per_cu of them per CU at most (render_fused: why fewer on a small tile)
+static uint32_t fused_render_grid(const HrtContext *ctx, uint32_t blocks_per_cu, uint32_t n) {
+    if (ctx->traverse_blocks_auto) {
+        const uint32_t fit = (uint32_t)((10ull * n + 14ull * 64ull * (uint64_t)ctx->n_cu - 1ull) / (14ull * 64ull * (uint64_t)ctx->n_cu));
+        blocks_per_cu = std::min(blocks_per_cu, std::max(fit, 4u));
+    }
+    return std::min<uint32_t>((uint32_t)ctx->n_cu * blocks_per_cu, (n + 63u) / 64u);
+}
+
 static int render_fused(const LaunchFrame &f) {
     HrtContext *ctx = f.ctx; Tlas *t = f.t; const HrtGlobalParams *h_params = f.h_params; const HrtRayGenParams *rg = f.rg;
     const uint32_t spp = f.spp, n = f.n; hipStream_t s = f.s;
     Workspace &w = ctx->ws;
     StageCounters *stg = w.set[0].stages;
-    TraverseArgs ta = traverse_args(ctx, *t, kFloatZero, kFloatInfinity);
-    ta.fetch_counter = stg[0].fetch;
-    ta.refill_threshold = ctx->fused_refill_threshold; ta.fetch_chunk = (uint32_t)ctx->fused_fetch_chunk;
-    ta.leaf_hold = leaf_hold_for(ctx, *t);
-    if (ctx->refill_auto && t->two_level) ta.refill_threshold = 12;      // (a two-level ray is long and its lanes finish far apart: 12 against 20 is +1.4-2.3 %, flattened trees lose 4 %)
+    TraverseArgs ta = fused_render_args(f);
     PathArgs &pa = ta.path;
-    pa.rows = w.rows; pa.first_pixel = 0; pa.n_tile_pixels = n; pa.width = rg->width; pa.height = rg->height; pa.spp = spp;
-    std::memcpy(pa.center, &rg->cameraCenter, 12); std::memcpy(pa.U, &rg->cameraU, 12);
-    std::memcpy(pa.V, &rg->cameraV, 12); std::memcpy(pa.W, &rg->cameraW, 12);
-    pa.bg[0] = ctx->miss.backgroundColor.x; pa.bg[1] = ctx->miss.backgroundColor.y; pa.bg[2] = ctx->miss.backgroundColor.z;
-    pa.states = reinterpret_cast<RngState *>(h_params->stateArray);
-    pa.hitgroups = ctx->d_hitgroups; pa.inst_program = ctx->d_inst_program; pa.accum = w.accum;
-    pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
     // Waves per CU: a lane runs its pixel's samples one after the other, so a small tile (the multi-GPU split) ends
     // with its slowest pixels; about 1.4 pixels per lane lets the lanes that drew cheap pixels take a second one
     // while fewer waves share each SIMD (measured, profiles/r01_sweep_tile_waves.txt: 1/8 of the C4 frame takes
@@ -432,12 +450,7 @@ static int render_fused(const LaunchFrame &f) {
     const PathKernelChoice pk = choose_path_kernel(ctx, *t);
     const bool lean = pk.kernel != PathKernel::Round1;
     ta.postpone_pct = lean ? ctx->fused_postpone_pct : ctx->postpone_pct;
-    uint32_t blocks_per_cu = pk.blocks_per_cu;
-    if (ctx->traverse_blocks_auto) {
-        const uint32_t fit = (uint32_t)((10ull * n + 14ull * 64ull * (uint64_t)ctx->n_cu - 1ull) / (14ull * 64ull * (uint64_t)ctx->n_cu));
-        blocks_per_cu = std::min(blocks_per_cu, std::max(fit, 4u));
-    }
-    const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * blocks_per_cu, (n + 63u) / 64u);
+    const uint32_t grid = fused_render_grid(ctx, pk.blocks_per_cu, n);
     // HRT_CTX_REUSE_PRIMARY: the lanes' slots for their pixels' primary hits (k_fused<.., REUSE>, fused.hip)
     if (lean && spp > 1u && ((ctx->flags & HRT_CTX_REUSE_PRIMARY) != 0u || ctx->reuse_primary)) {
         if (grid * 64u > w.primary_cache_lanes) {
@@ -782,6 +795,35 @@ static int render_wavefront(const LaunchFrame &f, bool count) {
     return HRT_OK;
 }
 
+// The tile of a launch (NULL: the whole frame): its rows uploaded -- the list of the previous launch is kept while frame and tile are the
+// same --, the workspace sized.  n: the tile's pixels; 0: an empty tile, nothing to do.
+static int prepare_tile(HrtContext *ctx, const HrtRayGenParams *rg, const HrtTile *tile, hipStream_t s, uint32_t &n) {
+    n = 0;
+    HrtTile tl = tile ? *tile : HrtTile{0, rg->height, 1, 1, 0};
+    if (tl.stripe_rows == 0 || tl.stripe_period == 0 || tl.stripe_phase >= tl.stripe_period || tl.y_begin > tl.y_end || tl.y_end > rg->height)
+        return fail(ctx, HRT_ERR_INVALID, "bad tile");
+    const bool same_rows = ctx->rows_w == rg->width && ctx->rows_h == rg->height && std::memcmp(&ctx->rows_tile, &tl, sizeof tl) == 0 && ctx->ws.rows;
+    if (!same_rows) {
+        ctx->rows_w = ctx->rows_h = 0;       // the cached row list is being replaced: its key is valid again only once the upload below has succeeded
+        ctx->h_rows.clear();
+        for (uint32_t y = tl.y_begin; y < tl.y_end; ++y)
+            if ((y / tl.stripe_rows) % tl.stripe_period == tl.stripe_phase) ctx->h_rows.push_back(y);
+    }
+    const uint32_t n_rows = (uint32_t)ctx->h_rows.size();
+    const uint64_t n64 = (uint64_t)n_rows * rg->width;
+    if (n64 == 0) return HRT_OK;
+    const int rc = ensure_workspace(ctx, (uint32_t)n64, rg->height);
+    if (rc != HRT_OK) return rc;
+    Workspace &w = ctx->ws;
+    if (!same_rows) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.rows, ctx->h_rows.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        ctx->rows_tile = tl; ctx->rows_w = rg->width; ctx->rows_h = rg->height;
+    }
+    n = (uint32_t)n64;
+    return HRT_OK;
+}
+
 int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg, uint32_t spp,
                       const HrtTile *tile, void *stream) {
     if (!ctx || !h_params || !rg) return HRT_ERR_INVALID;
@@ -798,35 +840,101 @@ int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const Hr
     if (rc == HRT_OK) rc = refresh_tables(ctx, h_params->handle, t, s);
     if (rc != HRT_OK) return rc;
 
-    // ---- tile rows ----
-    HrtTile tl = tile ? *tile : HrtTile{0, rg->height, 1, 1, 0};
-    if (tl.stripe_rows == 0 || tl.stripe_period == 0 || tl.stripe_phase >= tl.stripe_period || tl.y_begin > tl.y_end || tl.y_end > rg->height)
-        return fail(ctx, HRT_ERR_INVALID, "bad tile");
-    const bool same_rows = ctx->rows_w == rg->width && ctx->rows_h == rg->height && std::memcmp(&ctx->rows_tile, &tl, sizeof tl) == 0 && ctx->ws.rows;
-    if (!same_rows) {
-        ctx->rows_w = ctx->rows_h = 0;       // the cached row list is being replaced: its key is valid again only once the upload below has succeeded
-        ctx->h_rows.clear();
-        for (uint32_t y = tl.y_begin; y < tl.y_end; ++y)
-            if ((y / tl.stripe_rows) % tl.stripe_period == tl.stripe_phase) ctx->h_rows.push_back(y);
-    }
-    const uint32_t n_rows = (uint32_t)ctx->h_rows.size();
-    const uint64_t n64 = (uint64_t)n_rows * rg->width;
-    if (n64 == 0) return HRT_OK;
-    const uint32_t n = (uint32_t)n64;
-    rc = ensure_workspace(ctx, n, rg->height);
-    if (rc != HRT_OK) return rc;
-    Workspace &w = ctx->ws;
-    if (!same_rows) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.rows, ctx->h_rows.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        ctx->rows_tile = tl; ctx->rows_w = rg->width; ctx->rows_h = rg->height;
-    }
+    uint32_t n;
+    rc = prepare_tile(ctx, rg, tile, s, n);
+    if (rc != HRT_OK || n == 0u) return rc;
 
     const bool count = (ctx->flags & HRT_CTX_COUNT) != 0;
     if (!two_level_admitted(ctx, *t, count)) return fail(ctx, HRT_ERR_STATE, "a two-level TLAS is traced by the default path kernel only (not under HRT_CTX_COUNT / HRT_FUSED != 1, and not beyond its limits)");
     const LaunchFrame frame{ctx, t, h_params, rg, spp, n, s};
     const bool use_fused = !count && (ctx->fused > 0 || (ctx->fused < 0 && n <= (uint32_t)ctx->fused_max_pixels));
     return use_fused ? render_fused(frame) : render_wavefront(frame, count);
+}
+
+// ---- adaptive sampling (include/hrt.h): one launch of k_path_counts over the caller's sums, then its finalize kernel.  Every refusal comes
+//      before anything of the context or the caller's is touched. ----
+int hrt_render_accumulate(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg, uint32_t spp, const uint32_t *d_counts,
+                          HrtFloat4 *d_sum, uint32_t *d_taken, const HrtTile *tile, void *stream) {
+    if (!ctx || !h_params || !rg) return HRT_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipSetDevice(ctx->device);
+    if (spp == 0 || spp > 65536u) return fail(ctx, HRT_ERR_INVALID, "spp must be 1..65536 (got %u)", spp);
+    if (!d_sum || !d_taken) return fail(ctx, HRT_ERR_INVALID, "d_sum / d_taken is NULL");
+    if (rg->width == 0 || rg->height == 0 || (uint64_t)rg->width * rg->height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", rg->width, rg->height);
+    if (!rg->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    if (!h_params->stateArray) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.stateArray is NULL");
+    if ((ctx->flags & HRT_CTX_COUNT) != 0u) return fail(ctx, HRT_ERR_STATE, "hrt_render_accumulate runs the path kernel k_path_counts: not under HRT_CTX_COUNT");
+    if (ctx->fused != 1) return fail(ctx, HRT_ERR_STATE, "hrt_render_accumulate runs the path kernel k_path_counts: not with HRT_FUSED != 1");
+    if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
+    Tlas *t;
+    int rc = find_tlas(ctx, h_params->handle, t);
+    if (rc != HRT_OK) return rc;
+    if (!fits_fused_kernel(ctx, *t)) return fail(ctx, HRT_ERR_STATE, "hrt_render_accumulate: the tree is outside k_fused's limits (depth %u, HRT_FUSED_MAX_DEPTH / HRT_FUSED_MAX_BYTES)", t->max_depth);
+    rc = refresh_tables(ctx, h_params->handle, t, s);
+    if (rc != HRT_OK) return rc;
+    uint32_t n;
+    rc = prepare_tile(ctx, rg, tile, s, n);
+    if (rc != HRT_OK) return rc;
+    ctx->capture.valid = false;
+    if (n == 0u) return HRT_OK;
+
+    const LaunchFrame frame{ctx, t, h_params, rg, spp, n, s};
+    TraverseArgs ta = fused_render_args(frame);
+    ta.postpone_pct = ctx->fused_postpone_pct;
+    PathArgs &pa = ta.path;
+    // (the fields that are free in this launch carry the caller's arrays, all in frame order: path_lane.h, kCounts)
+    pa.accum = reinterpret_cast<float4 *>(d_sum); pa.trace_inst = d_taken; pa.slice_order = d_counts;
+    const PathKernelChoice pk = choose_path_kernel(ctx, *t);
+    const uint32_t grid = fused_render_grid(ctx, pk.blocks_per_cu, n);
+    // the slice counters: render_fused's protocol -- zero on entry (left so by the previous launch's finalize kernel, or set here), zeroed
+    // again by this launch's finalize kernel for whichever launch comes next
+    StageCounters *stg = ctx->ws.set[0].stages;
+    if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
+    ctx->fused_counters_clean = false;
+    bool admitted;
+    { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(PathKernel::Counts, ta, path_scene(*t), grid, s); }
+    if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused the counts launch");
+    FinalizeCountsArgs fa{};
+    fa.sum = pa.accum; fa.taken = d_taken; fa.counts = d_counts; fa.rows = ctx->ws.rows; fa.n_tile_pixels = n; fa.width = rg->width; fa.spp = spp;
+    fa.color = reinterpret_cast<float4 *>(rg->colorBuffer); fa.albedo = reinterpret_cast<float4 *>(rg->albedoBuffer);
+    fa.normal = reinterpret_cast<float4 *>(rg->normalBuffer); fa.linear = ctx->d_linear;
+    constexpr uint32_t kCounterWords = (uint32_t)(sizeof(StageCounters) / sizeof(uint32_t));
+    if (n >= kCounterWords) { fa.reset_counters = reinterpret_cast<uint32_t *>(stg); fa.n_reset = kCounterWords; }
+    // HrtStats.paths: a uniform launch's samples are known here, a map's are summed by the finalize kernel (read in hrt_stats_get)
+    if (d_counts) fa.paths = reinterpret_cast<unsigned long long *>(&ctx->d_stats->paths);
+    else ctx->paths += (uint64_t)n * spp;
+    { Timer tm(ctx, s, HRT_K_FINALIZE); launch_finalize_counts(fa, s); }
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->fused_counters_clean = fa.reset_counters != nullptr;
+    ctx->last_tlas = h_params->handle;
+    return HRT_OK;
+}
+
+int hrt_sample_counts_default_params(HrtSampleCountParams *out) {
+    if (!out) return HRT_ERR_INVALID;
+    *out = HrtSampleCountParams{0.05f, 1u, 64u, 1u, {0u, 0u}};
+    return HRT_OK;
+}
+
+int hrt_sample_counts(HrtContext *ctx, const HrtFloat4 *d_sum, const uint32_t *d_taken, uint32_t width, uint32_t height,
+                      const HrtSampleCountParams *h_params, uint32_t *d_counts, void *stream) {
+    if (!ctx || !d_sum || !d_taken || !d_counts) return HRT_ERR_INVALID;
+    if ((uint64_t)width * height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "frame too large");
+    HrtSampleCountParams p;
+    (void)hrt_sample_counts_default_params(&p);
+    if (h_params) p = *h_params;
+    if (!(p.target_sigma > 0.0f) || !std::isfinite(p.target_sigma)) return fail(ctx, HRT_ERR_INVALID, "HrtSampleCountParams.target_sigma must be > 0 and finite");
+    if (p.min_total < 1u || p.min_total > 65536u || p.max_total < p.min_total || p.max_total > 65536u)
+        return fail(ctx, HRT_ERR_INVALID, "HrtSampleCountParams: 1 <= min_total <= max_total <= 65536 (got %u, %u)", p.min_total, p.max_total);
+    if (p.radius > 2u) return fail(ctx, HRT_ERR_INVALID, "HrtSampleCountParams.radius must be 0..2 (got %u)", p.radius);
+    if (p.reserved[0] != 0u || p.reserved[1] != 0u) return fail(ctx, HRT_ERR_INVALID, "HrtSampleCountParams.reserved must be 0");
+    (void)hipSetDevice(ctx->device);
+    SampleCountArgs a{};
+    a.sum = reinterpret_cast<const float4 *>(d_sum); a.taken = d_taken; a.counts = d_counts;
+    a.width = width; a.height = height; a.radius = p.radius; a.min_total = p.min_total; a.max_total = p.max_total; a.target_sigma = p.target_sigma;
+    launch_sample_counts(a, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
 }
 
 
@@ -895,7 +1003,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     HIP_TRY(ctx, hipMemcpy(&ds, ctx->d_stats, sizeof ds, hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
     out->rays_closest = ds.rays_closest; out->rays_any = ds.rays_any; out->rays = ds.rays_closest + ds.rays_any;
-    out->paths = ctx->paths; out->node_visits = ds.nodes_closest + ds.nodes_any; out->prim_tests = ds.prims_closest + ds.prims_any;
+    out->paths = ctx->paths + ds.paths; out->node_visits = ds.nodes_closest + ds.nodes_any; out->prim_tests = ds.prims_closest + ds.prims_any;
     out->node_visits_closest = ds.nodes_closest; out->prim_tests_closest = ds.prims_closest;
     for (int k = 0; k < 4; ++k) out->debug[k] = ds.debug[k];
     for (int k = 0; k < 8; ++k) out->tail[k] = ds.tail[k];

@@ -120,7 +120,10 @@ struct Tlas {
 struct StageCounters { uint32_t bin_count[32]; uint32_t fetch[8 * 32]; };
 static_assert(sizeof(StageCounters) == 128 + 8 * 128, "stage counters layout");
 
-struct DeviceStats { uint64_t rays_closest, rays_any, nodes_closest, prims_closest, nodes_any, prims_any; uint64_t debug[4]; uint64_t tail[8]; };
+struct DeviceStats {
+    uint64_t rays_closest, rays_any, nodes_closest, prims_closest, nodes_any, prims_any; uint64_t debug[4]; uint64_t tail[8];
+    uint64_t paths;      // samples taken by hrt_render_accumulate launches with a count map: known on the device only (HrtStats.paths adds it to the host's count)
+};
 
 // Everything one sample needs besides the per-pixel state.  Two sets (sample parity): the stages of
 // two consecutive samples overlap in time (hrt_render_launch), never more.

@@ -568,6 +568,64 @@ __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs a) {
     if (a.normal) a.normal[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// hrt_render_accumulate's finalize: k_path_counts has added c = counts ? min(counts[p], spp) : spp samples to pixel p's sum; here the pixel's
+// total follows, and the colour is k_finalize's arithmetic over sum / total wherever the sum holds a sample.  A pixel without one keeps its colour.
+__global__ __launch_bounds__(256) void k_finalize_counts(FinalizeCountsArgs a) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.reset_counters && j < a.n_reset) a.reset_counters[j] = 0u;      // (as k_finalize: the slice counters are zero again for the next launch)
+    uint32_t c = 0u;
+    if (j < a.n_tile_pixels) {
+        const uint32_t row = j / a.width;
+        const uint32_t ix = j - row * a.width;
+        const uint32_t p = a.rows[row] * a.width + ix;
+        c = a.spp;
+        if (a.counts) { const uint32_t want = a.counts[p]; c = want < c ? want : c; }
+        uint32_t total = a.taken[p];
+        if (c != 0u) { total += c; a.taken[p] = total; }
+        if (total != 0u) {
+            float4 acc = a.sum[p];
+            if (total > 1u) { const float n = (float)total; acc.x /= n; acc.y /= n; acc.z /= n; }
+            if (a.linear) a.linear[p] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+            a.color[p] = make_float4(srgb_channel(acc.x), srgb_channel(acc.y), srgb_channel(acc.z), 1.0f);
+            if (a.albedo) a.albedo[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (a.normal) a.normal[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    // HrtStats.paths: the samples this launch took, one atomic per wave (a uniform launch is counted on the host: paths == NULL)
+    if (a.paths) {
+        for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_down((int)c, off);
+        if ((threadIdx.x & 63u) == 0u && c != 0u) atomicAdd(a.paths, (unsigned long long)c);
+    }
+}
+
+// hrt_sample_counts (include/hrt.h; tests/sample_counts_ref.py restates it): the variance of a pixel's luminance from its sums, the largest
+// of a window, and from it the samples the pixel should hold in total.  One thread per pixel, no reduction: nothing depends on the launch's geometry.
+__device__ __forceinline__ float luminance_variance(const float4 sum, uint32_t taken) {
+    if (taken < 2u) return __uint_as_float(0x7f800000u);         // nothing known yet
+    const float n = (float)taken;
+    const float m1 = ((0.2126f * sum.x + 0.7152f * sum.y) + 0.0722f * sum.z) / n, m2 = sum.w / n;
+    return fmaxf(0.0f, m2 - m1 * m1);                            // (a NaN gives 0)
+}
+__global__ __launch_bounds__(256) void k_sample_counts(SampleCountArgs a) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.width * a.height) return;
+    const int y = (int)(p / a.width), x = (int)(p - (uint32_t)y * a.width), r = (int)a.radius;
+    float v = 0.0f;
+    for (int dy = -r; dy <= r; ++dy)
+        for (int dx = -r; dx <= r; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qy < 0 || qx >= (int)a.width || qy >= (int)a.height) continue;
+            const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+            v = fmaxf(v, luminance_variance(a.sum[q], a.taken[q]));
+        }
+    const float wanted = v / (a.target_sigma * a.target_sigma);
+    // (0 / 0 and inf / inf -- a target whose square leaves the floats -- are NaN: neither comparison holds, 0)
+    uint32_t total = wanted >= (float)a.max_total ? a.max_total : wanted > 0.0f ? (uint32_t)ceilf(wanted) : 0u;
+    total = total > a.min_total ? total : a.min_total;
+    const uint32_t have = a.taken[p];
+    a.counts[p] = total > have ? total - have : 0u;
+}
+
 // convertFloat4ToUchar4Kernel, src/Global/RendererImpl.cu:672-678 (colorToUchar4, DeviceFunctions.cuh:153-183)
 __global__ __launch_bounds__(256) void k_to_rgba8(const float4 *src, uchar4 *dst, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -669,6 +727,12 @@ void launch_sum(float4 *accum, const float4 *result, uint32_t n, uint32_t first_
 }
 void launch_finalize(const FinalizeArgs &a, hipStream_t s) {
     if (a.n_tile_pixels) hipLaunchKernelGGL(k_finalize, dim3(ceil_div(a.n_tile_pixels, 256)), dim3(256), 0, s, a);
+}
+void launch_finalize_counts(const FinalizeCountsArgs &a, hipStream_t s) {
+    if (a.n_tile_pixels) hipLaunchKernelGGL(k_finalize_counts, dim3(ceil_div(a.n_tile_pixels, 256)), dim3(256), 0, s, a);
+}
+void launch_sample_counts(const SampleCountArgs &a, hipStream_t s) {
+    if (a.width * a.height) hipLaunchKernelGGL(k_sample_counts, dim3(ceil_div(a.width * a.height, 256)), dim3(256), 0, s, a);
 }
 void launch_to_rgba8(const float4 *src, uchar4 *dst, uint32_t n, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_to_rgba8, dim3(ceil_div(n, 256)), dim3(256), 0, s, src, dst, n);

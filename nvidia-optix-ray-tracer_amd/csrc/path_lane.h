@@ -34,6 +34,13 @@ struct PathLane {
     // that hand the pixel on within one launch (handover_store / handover_load); kept by the kernels that seed (kSeed: fused_body.h) only.)
 };
 
+// kCounts (k_path_counts, fused_counts.hip): what the lane of that kernel carries besides.  A type of its own, which path_finish and path_take
+// take as their lane's: one more member of PathLane, even one that no other kernel touches, lets the registers of all of them fall differently.
+struct CountsLane : PathLane {
+    float px_aw = 0.0f;         // the sum of the samples' squared luminances: the w of the pixel's 16-byte sum
+    bool gave_up = false;       // path_take: the pixel this lane drew has count 0 and is given up already
+};
+
 // what a lane does next: `launch` the ray (ro, rd), or -- `want_primary` -- a primary ray that path_primary has yet to make
 struct PathStep {
     bool launch = false, want_primary = false;
@@ -148,9 +155,15 @@ __device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_
 // have).  Only where `restartable` -- the lane accepted the hit itself (brec != kNoWork) in a walk that had the window the next one will
 // have, so that the node step of that node passes the slot again, bit for bit; everything else leaves 0, the root.  The table's load goes
 // out in front of the normals', on the same round trip.
+// kCounts (k_path_counts, fused_counts.hip; hrt_render_accumulate): every pixel takes a sample count of its own and continues a sum the caller
+// keeps, in FRAME order.  Fields that are free in such a launch carry the arrays: PathArgs::accum the sums (xyz: radiance, w: squared luminances),
+// trace_inst how many samples each sum holds on entry (0: the first sample is assigned), slice_order the counts (NULL: spp everywhere).
+// The lane of such a kernel is a CountsLane (above): px_aw, the fourth accumulator next to px_ax / px_ay / px_az, and gave_up.
+// A pixel of count c = min(counts[p], spp) starts at px_sample = spp - c, so that it ends where every pixel does, at px_sample >= spp, and
+// the count needs no register; c == 0 is given up in path_take, before anything of it is loaded or stored.
 typedef const __attribute__((address_space(1))) uint32_t *global_words;
-template <class V>
-__device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
+template <class V, class Lane>
+__device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
                                             [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t brec = 0u, [[maybe_unused]] bool restartable = false,
                                             [[maybe_unused]] uint32_t *restart = nullptr) {
     PathStep st;
@@ -174,6 +187,11 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
         if constexpr (V::kOneGroup) r = fold_chain_one(miss, a.path.bg, P.px_depth, a.path.hitgroups);
         else if constexpr (V::kBlocks) r = fold_chain_together(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
         else r = fold_chain(miss, a.path.bg, px_chain, P.px_depth, a.path.hitgroups);
+        if constexpr (V::kCounts) {
+            // the sample's luminance, squared, joins its own sum by the radiance's rule: the first sample of a frame is assigned
+            const float l = (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z;
+            if (P.px_first) P.px_aw = l * l; else P.px_aw += l * l;
+        }
         if (P.px_first) { P.px_ax = r.x; P.px_ay = r.y; P.px_az = r.z; P.px_first = false; }
         else { P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z; }
         ++P.px_sample;
@@ -202,6 +220,11 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
                 float carried = 0.0f;
                 if constexpr (V::kSeed) carried = *seed;
                 handover_store(a.path, P, a.fetch_chunk, carried);
+            }
+            else if constexpr (V::kCounts) {
+                // the caller's sum, in frame order; how many samples it now holds is the launch's finalize kernel's to add (k_finalize_counts)
+                a.path.accum[P.px_tid] = make_float4(P.px_ax, P.px_ay, P.px_az, P.px_aw);
+                rng_store(a.path.states + P.px_tid, P.px_rng);
             }
             else {
                 a.path.accum[P.px_local] = make_float4(P.px_ax, P.px_ay, P.px_az, 0.0f);
@@ -250,10 +273,11 @@ __device__ __forceinline__ PathStep path_finish(PathLane &P, uint32_t (&px_chain
 // waits here: the lane that has the predecessor's pixel may be one of this wave's own, so the wave must go on traversing.
 // kRestart (path_finish): a pixel just taken has no restart node -- the word in LDS is the lane's previous pixel's, while the seed (kBlocks, a
 // pass b > 0) comes with the pixel and switches the window on: a block's first primary ray walks from the root, inside its window.
-template <class V>
-__device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
-                                          bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
-                                          [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t *restart = nullptr) {
+// kCounts (path_finish): one round of path_take below -- P.gave_up says that the pixel this lane took has count 0 and is given up already.
+template <class V, class Lane>
+__device__ __forceinline__ bool path_take_slice(Lane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
+                                                bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
+                                                [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t *restart = nullptr) {
     const uint64_t need = __ballot(free_lane);
     if (need != 0ull && !exhausted) {
         constexpr bool by_blocks = V::kBlocks;      // (path_launch_admitted: sample_block != 0)
@@ -285,7 +309,10 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
             // the q-th slice handed out is slice slice_order[q] of the tile: the expensive slices first, so that the render
             // ends on cheap pixels (longest-processing-time-first; a pixel's samples run one after the other)
             wave_next_slice(wbeg, wend, kstart, home_shard, a.fetch_counter, a.fetch_chunk, n_pixels, tx,
-                            [&](uint64_t q) { return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q; });
+                            [&](uint64_t q) {
+                                if constexpr (V::kCounts) return q;      // (slice_order carries the counts: the slices go out as they lie)
+                                else return a.path.slice_order ? (uint64_t)a.path.slice_order[q] : q;
+                            });
             if (wbeg >= wend) exhausted = true;
         }
         bool ready = true;
@@ -309,7 +336,17 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
                     const uint32_t iy = a.path.rows[row];
                     P.px_tid = iy * a.path.width + ix;
                     P.px_first = a.path.continue_sum == 0u;         // later launches of a long render continue the pixel's sum
-                    if (by_blocks) {
+                    if constexpr (V::kCounts) {
+                        // the pixel's count, then -- unless that is 0: no ray, no store, the lane is free again -- what the caller's arrays hold of it
+                        uint32_t c = a.path.spp;
+                        if (a.path.slice_order) { const uint32_t want = ((global_words)a.path.slice_order)[P.px_tid]; c = want < c ? want : c; }
+                        if (c == 0u) { P.have_pixel = false; st.want_primary = false; P.gave_up = true; }
+                        else {
+                            P.px_sample = a.path.spp - c; P.px_rng = rng_load(a.path.states + P.px_tid);
+                            P.px_first = ((global_words)a.path.trace_inst)[P.px_tid] == 0u;
+                            if (!P.px_first) { const float4 acc = a.path.accum[P.px_tid]; P.px_ax = acc.x; P.px_ay = acc.y; P.px_az = acc.z; P.px_aw = acc.w; }
+                        }
+                    } else if (by_blocks) {
                         if constexpr (V::kBlocks) {                     // ... and so do later blocks of a launch
                             P.px_sample = block_first(a.path.sample_block, a.path.block_min, a.path.block_taper_end, a.path.block_magic == 0u, B->pass);
                             P.px_first = P.px_first && B->pass == 0u;
@@ -334,6 +371,25 @@ __device__ __forceinline__ bool path_take(PathLane &P, PathStep &st, const Trave
         }
     }
     return exhausted;
+}
+// kCounts: a lane that drew a pixel of count 0 takes again at once, until every free lane holds a pixel with samples to take, the slice ran out
+// on pixels that have some, or the tile is used up.  Without this a wave whose whole slice has count 0 would start no ray, and a wave
+// with no ray under way and none to start is taken for one that has finished the tile (fused_body.h).  Every round hands out at least
+// one pixel or finds the tile used up, so runs of zeros of any length end; after the last round either the tile is used up or some
+// lane of the wave wants a primary ray.
+template <class V, class Lane>
+__device__ __forceinline__ bool path_take(Lane &P, PathStep &st, const TraverseArgs &a, uint32_t n_pixels, bool free_lane, uint32_t &wbeg, uint32_t &wend, uint32_t &kstart,
+                                          bool exhausted, uint32_t home_shard, uint32_t tx, [[maybe_unused]] BlockSlice *B = nullptr,
+                                          [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t *restart = nullptr) {
+    if constexpr (V::kCounts) {
+        for (;;) {
+            P.gave_up = false;
+            exhausted = path_take_slice<V>(P, st, a, n_pixels, free_lane, wbeg, wend, kstart, exhausted, home_shard, tx, B, seed, restart);
+            if (__ballot(P.gave_up) == 0ull) break;
+            free_lane = free_lane && !P.have_pixel;
+        }
+        return exhausted;
+    } else return path_take_slice<V>(P, st, a, n_pixels, free_lane, wbeg, wend, kstart, exhausted, home_shard, tx, B, seed, restart);
 }
 
 // The primary ray of a lane that wants one: the caller's ray (hrt_trace_rays) or the camera ray of the lane's pixel; sets the depth.

@@ -21,6 +21,7 @@ struct PathVariant {      // every flag false
     static constexpr bool kReuse = false, kSeed = false;            // repeat primary rays: not traversed (the primary-hit cache); bounded at their known hit (fused_body.h)
     static constexpr bool kBlocks = false, kCapture = false;        // pixels go round in sample blocks; every pixel's primary hit is kept (path_lane.h)
     static constexpr bool kOneGroup = false, kRestart = false;      // every hit is instance 0's; ... and repeat primary rays start at their known hit's node (path_lane.h)
+    static constexpr bool kCounts = false;                          // every pixel takes a sample count of its own and continues a caller's sum (path_lane.h)
 };
 // a kernel that is none of these -- k_traverse (kernels.hip), k_trace_queue (fused_queue.hip): no pixels of its own or no seed, every block in its plain form
 template <bool HAS_SPHERES>
@@ -36,6 +37,7 @@ constexpr bool path_variant_checked() {
     static_assert(!V::kOneGroup || (V::kBlocks && !V::kSpheres && !V::kCapture), "one hit group: the block render of a one-level tree of triangles");
     static_assert(!V::kCapture || (!V::kReuse && !V::kBlocks), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     static_assert(!V::kBlocks || (!V::kInstanced && !V::kReuse), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
+    static_assert(!V::kCounts || (!V::kReuse && !V::kBlocks && !V::kCapture), "per-pixel counts: plain launches only (no primary-hit cache, no sample blocks, no capture)");
     return true;
 }
 

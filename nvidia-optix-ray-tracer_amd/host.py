@@ -107,6 +107,7 @@ class Renderer:
         self.states = None
         self.width = self.height = 0
         self.color = self.albedo = self.normal = self.linear = None
+        self.sum = self.taken = self.counts = None      # adaptive sampling: the frame's sums, sample totals and last count map
         self.cam = None
 
     # ---- helpers ----
@@ -311,6 +312,10 @@ class Renderer:
         self.albedo = torch.full((height, width, 4), 7.0, dtype=torch.float32, device=self.device) if aov else None
         self.normal = torch.full((height, width, 4), 7.0, dtype=torch.float32, device=self.device) if aov else None
         self.linear = torch.zeros((height, width, 4), dtype=torch.float32, device=self.device) if linear else None
+        # adaptive sampling (accumulate / sample_counts): per pixel the sums of radiance and squared luminance, and how many samples they hold
+        self.sum = torch.zeros((height, width, 4), dtype=torch.float32, device=self.device)
+        self.taken = torch.zeros((height, width), dtype=torch.int32, device=self.device)
+        self.counts = None
         self._check(self.lib.hrt_debug_set_linear_output(self.ctx, self.linear.data_ptr() if linear else None),
                     "hrt_debug_set_linear_output")
         return self
@@ -349,6 +354,49 @@ class Renderer:
         self._check(self.lib.hrt_render_launch(self.ctx, C.byref(params), C.byref(rg), spp, _ref(tile), st), "hrt_render_launch")
         if sync:
             self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+
+    # ---- adaptive sampling: pilot -> counts -> refine (include/hrt.h: hrt_render_accumulate, hrt_sample_counts) ----
+    def accumulation_reset(self):
+        """A new frame of accumulate(): no pixel holds a sample (the sums need no reset: a pixel's first sample is assigned)."""
+        self.taken.zero_()
+        self.counts = None
+
+    def accumulate(self, spp=1, counts=None, tile=None, sync=True):
+        """hrt_render_accumulate over ``self.sum`` / ``self.taken``: every pixel of the tile takes min(counts, spp) more samples (``counts``: an
+        (H, W) int32 device tensor; None: spp each) on its RNG stream, and ``self.color`` becomes colorToFloat4(sum / taken) wherever taken > 0.
+        After any sequence of these calls a pixel holds bit for bit what render(spp = its total) gives it from the same initial states."""
+        params, rg = self._launch_blocks()
+        st = self._stream()
+        if counts is not None and (counts.dtype != self._torch.int32 or tuple(counts.shape) != (self.height, self.width) or not counts.is_contiguous()):
+            raise self._err("accumulate: counts must be a contiguous (height, width) int32 tensor on the device")
+        self._check(self.lib.hrt_render_accumulate(self.ctx, C.byref(params), C.byref(rg), spp, counts.data_ptr() if counts is not None else None,
+                                                   self.sum.data_ptr(), self.taken.data_ptr(), _ref(tile), st), "hrt_render_accumulate")
+        if sync:
+            self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+
+    def sample_counts(self, params=None):
+        """hrt_sample_counts of the frame's sums: the (H, W) int32 tensor of how many MORE samples each pixel should take (kept in
+        ``self.counts``).  ``params``: None, a SampleCountParams or a dict of its fields over the defaults."""
+        from . import SampleCountParams
+        p = self._params(SampleCountParams, "hrt_sample_counts_default_params", params)
+        self.counts = self._torch.empty((self.height, self.width), dtype=self._torch.int32, device=self.device)
+        self._check(self.lib.hrt_sample_counts(self.ctx, self.sum.data_ptr(), self.taken.data_ptr(), self.width, self.height,
+                                               C.byref(p) if p is not None else None, self.counts.data_ptr(), self._stream()), "hrt_sample_counts")
+        return self.counts
+
+    def render_adaptive(self, pilot, params=None):
+        """One adaptive frame: reset, ``pilot`` samples everywhere, the count map from their variance, one refinement launch in which every
+        pixel takes its count (never more than max_total).  Returns the count map; ``self.taken`` holds the totals."""
+        from . import SampleCountParams
+        p = self._params(SampleCountParams, "hrt_sample_counts_default_params", params)
+        if p is None:
+            p = SampleCountParams()
+            self._check(self.lib.hrt_sample_counts_default_params(C.byref(p)), "hrt_sample_counts_default_params")
+        self.accumulation_reset()
+        self.accumulate(pilot, sync=False)
+        counts = self.sample_counts(p)
+        self.accumulate(p.max_total, counts=counts)
+        return counts
 
     def primary_hits(self):
         """CTX_CAPTURE_PRIMARY: the primary hit of every pixel as the last render() found it, (t, u, v, prim, inst) numpy arrays of

@@ -10,7 +10,7 @@ sys.path.insert(0, str(ROOT / "tools"))
 import loop_stats
 
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
-FILES = (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_one", "_ZN3hrt10k_path_one"), ("fused_restart", "_ZN3hrt14k_path_restart"), ("fused_capture", "_ZN3hrt14k_path_capture"), ("fused_queue", "_ZN3hrt13k_trace_queue"))
+FILES = (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_one", "_ZN3hrt10k_path_one"), ("fused_restart", "_ZN3hrt14k_path_restart"), ("fused_capture", "_ZN3hrt14k_path_capture"), ("fused_counts", "_ZN3hrt13k_path_counts"), ("fused_queue", "_ZN3hrt13k_trace_queue"))
 
 
 def short(name):
