@@ -416,6 +416,13 @@ typedef struct HrtStats {
                                               sum of exit clocks, idle lane-ticks between draining and exit, waves (100 MHz ticks)        */
     uint64_t sample_block_schedule[4];     /* the last launch that handed pixels out in sample blocks: largest block, smallest block, the sample
                                               at which the halving blocks end (0: uniform blocks), passes (hrt_sample_schedule) */
+    uint64_t wave_clock[60];               /* instrumented build only (make stats, tools/wave_clock.py): the clock the path kernel's waves ran at, from the shader
+                                              clock's counter and the 100 MHz one read at a wave's first regeneration and at its exit -- waves, sum of
+                                              their cycles, sum of their ticks, reserved, then 56 bins of 16 MHz from 1600 MHz (the ends take what lies
+                                              beyond).  Added with mask_idle_launches: rebuild against this header */
+    uint64_t mask_idle_launches;           /* of restart_launches: those that ran k_path_idle, k_path_restart with idle lanes switched off in the loop's
+                                              primitive test and node step (HRT_MASK_IDLE).  Added ahead of restart_launches, which
+                                              tests/test_primary_restart_cpu.py pins in front of one_group_launches: rebuild against this header */
     uint64_t restart_launches;             /* of one_group_launches: those that ran k_path_restart, whose repeat primary rays start at the node of their
                                               known hit (HRT_PRIMARY_RESTART).  Added ahead of one_group_launches, which
                                               tests/test_denoise_by_primitive_cpu.py pins in front of the counters below: rebuild against this header */

@@ -327,6 +327,7 @@ enum class PathKernel {
     Restart,            // k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit
     Round1,             // k_traverse<.., FUSED> (kernels.hip): round 1's fused kernel, for the trees k_fused cannot take
     Counts              // k_path_counts (fused_counts.hip): k_fused<S, I, false> over a caller's sums, every pixel with a sample count of its own (hrt_render_accumulate)
+    , MaskIdle          // k_path_idle (fused_idle.hip): k_path_restart whose loop switches idle lanes off for the primitive test and the node step
 };
 struct PathScene { bool one_level; uint32_t n_instances; bool has_spheres; const uint32_t *leaf_parent; };      // what the TraverseArgs do not say about the tree (leaf_parent: below, or NULL)
 // What each kernel takes for granted, in one place: its regeneration does not look at the fields it is compiled without, so a launch that
@@ -343,6 +344,7 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
         case PathKernel::Blocks: return in_blocks;
         case PathKernel::OneGroup: return one_group;
         case PathKernel::Restart: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;      // (the table, and the window its rays start in)
+        case PathKernel::MaskIdle: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;     // (exactly what Restart takes)
         case PathKernel::Round1: return true;
         // (accum: the caller's sums, trace_inst: the samples they hold, slice_order: the counts or NULL -- so no callers' rays, no cost probe, no order)
         case PathKernel::Counts: return p.sample_block == 0u && p.trace_rays == nullptr && p.primary_cache == nullptr && p.slice_cost == nullptr &&
@@ -353,7 +355,7 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
 // The one launch entry of the path kernels (fused.hip).  false: refused (path_launch_admitted), nothing launched.
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);
 using PathLauncher = void(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);      // (its halves in the other kernels' translation units: each launches its own kernel)
-PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_round1, launch_path_counts;
+PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_idle, launch_path_round1, launch_path_counts;
 // leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
 // counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
 // primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.

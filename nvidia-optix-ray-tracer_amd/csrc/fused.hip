@@ -52,6 +52,7 @@ bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScen
         case PathKernel::Blocks: launch_path_blocks(a, scene, grid_blocks, s); break;
         case PathKernel::OneGroup: launch_path_one(a, scene, grid_blocks, s); break;
         case PathKernel::Restart: launch_path_restart(a, scene, grid_blocks, s); break;
+        case PathKernel::MaskIdle: launch_path_idle(a, scene, grid_blocks, s); break;
         case PathKernel::Round1: launch_path_round1(a, scene, grid_blocks, s); break;
         case PathKernel::Counts: launch_path_counts(a, scene, grid_blocks, s); break;
     }

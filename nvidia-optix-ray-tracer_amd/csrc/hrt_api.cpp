@@ -287,7 +287,8 @@ static PathScene path_scene(const Tlas &t) { return {!t.two_level, t.n_instances
 static PathKernel launch_kernel(const HrtContext *ctx, const Tlas &t, PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary) {
     if (!blocks) return capture && done_spp == 0u ? PathKernel::Capture : tree_kernel;
     if (!(ctx->one_group && !t.two_level && t.n_instances == 1u && !t.has_spheres)) return PathKernel::Blocks;
-    return ctx->primary_restart && seed_primary == 2 ? PathKernel::Restart : PathKernel::OneGroup;
+    if (!(ctx->primary_restart && seed_primary == 2)) return PathKernel::OneGroup;
+    return ctx->mask_idle ? PathKernel::MaskIdle : PathKernel::Restart;       // (HRT_MASK_IDLE: the same launch, the same table)
 }
 extern "C++" {      // (helpers of hrt_internal.hpp, shared with hrt_denoise.cpp)
 namespace hrt {
@@ -558,7 +559,7 @@ static int render_fused(const LaunchFrame &f) {
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         ctx->fused_counters_clean = false;
         PathKernel kernel = launch_kernel(ctx, *t, pk.kernel, capture, blocks, done_spp, ta.seed_primary);
-        if (kernel == PathKernel::Restart) {      // it wants the tree's leaf_parent table, made here the first time (a tree without records: k_path_one, the launch as it was)
+        if (kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) {      // it wants the tree's leaf_parent table, made here the first time (a tree without records: k_path_one, the launch as it was)
             const int rc = ensure_leaf_parent(ctx, *t, s);
             if (rc != HRT_OK) return rc;
             if (t->dev.d_leaf_parent == nullptr) kernel = PathKernel::OneGroup;
@@ -568,8 +569,9 @@ static int render_fused(const LaunchFrame &f) {
         { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, path_scene(*t), grid, s); }
         if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
         if (kernel == PathKernel::Capture) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
-        if (kernel == PathKernel::OneGroup || kernel == PathKernel::Restart) ctx->one_group_launches++;
-        if (kernel == PathKernel::Restart) ctx->restart_launches++;
+        if (kernel == PathKernel::OneGroup || kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->one_group_launches++;
+        if (kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->restart_launches++;
+        if (kernel == PathKernel::MaskIdle) ctx->mask_idle_launches++;
         done_spp += now;
     }
     FinalizeArgs fa{};
@@ -1007,6 +1009,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->node_visits_closest = ds.nodes_closest; out->prim_tests_closest = ds.prims_closest;
     for (int k = 0; k < 4; ++k) out->debug[k] = ds.debug[k];
     for (int k = 0; k < 8; ++k) out->tail[k] = ds.tail[k];
+    for (int k = 0; k < 60; ++k) out->wave_clock[k] = ds.wave_clock[k];
     out->tlas_refits = ctx->tlas_refits; out->tlas_rebuilds = ctx->tlas_rebuilds; out->tlas_refit_ratio = ctx->tlas_refit_ratio;
     for (int k = 0; k < HRT_K_COUNT; ++k) { out->kernel_ms[k] = ctx->kernel_ms[k]; out->kernel_launches[k] = ctx->kernel_launches[k]; }
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1024,7 +1027,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
     out->denoise_history_rebinds = ctx->denoise_history_rebinds;
     out->denoise_by_primitive_links = ctx->denoise_by_primitive_links;
-    out->one_group_launches = ctx->one_group_launches; out->restart_launches = ctx->restart_launches;
+    out->one_group_launches = ctx->one_group_launches; out->restart_launches = ctx->restart_launches; out->mask_idle_launches = ctx->mask_idle_launches;
     return HRT_OK;
 }
 

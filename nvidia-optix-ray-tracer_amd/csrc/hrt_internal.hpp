@@ -123,7 +123,9 @@ static_assert(sizeof(StageCounters) == 128 + 8 * 128, "stage counters layout");
 struct DeviceStats {
     uint64_t rays_closest, rays_any, nodes_closest, prims_closest, nodes_any, prims_any; uint64_t debug[4]; uint64_t tail[8];
     uint64_t paths;      // samples taken by hrt_render_accumulate launches with a count map: known on the device only (HrtStats.paths adds it to the host's count)
+    uint64_t wave_clock[60];      // instrumented build only (trav_common.h: LaneStats::report, which addresses it as word 19 of this structure)
 };
+static_assert(offsetof(DeviceStats, wave_clock) == 19 * sizeof(uint64_t), "LaneStats::report writes the waves' clocks behind `paths`");
 
 // Everything one sample needs besides the per-pixel state.  Two sets (sample parity): the stages of
 // two consecutive samples overlap in time (hrt_render_launch), never more.
@@ -292,6 +294,8 @@ struct HrtContext {
     uint64_t one_group_launches = 0;            // ... and how many did
     bool primary_restart = true;                // HRT_PRIMARY_RESTART: ... of those, the launches with the seed window (seed_primary == 2) run k_path_restart (fused_restart.hip) over the tree's leaf_parent table
     uint64_t restart_launches = 0;              // ... and how many did
+    bool mask_idle = true;                      // HRT_MASK_IDLE: ... of those, k_path_idle (fused_idle.hip) instead: idle lanes off in the loop's primitive test and node step
+    uint64_t mask_idle_launches = 0;            // ... and how many did
     int taper_big = kSampleTaperBig, taper_min = kSampleTaperMin;      // HRT_SAMPLE_TAPER: what `auto` hands out -- blocks that start at taper_big samples and end on taper_min (0: uniform blocks of kSampleBlockAuto)
     bool taper_forced = false;                  // ... whatever the tile, like HRT_SAMPLE_BLOCK=N (tests)
     uint32_t last_schedule[4] = {0u, 0u, 0u, 0u};      // the last launch in sample blocks: largest block, smallest block, end of the halvings (0: uniform), passes

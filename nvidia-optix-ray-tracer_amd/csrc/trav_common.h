@@ -22,6 +22,7 @@ struct PathVariant {      // every flag false
     static constexpr bool kBlocks = false, kCapture = false;        // pixels go round in sample blocks; every pixel's primary hit is kept (path_lane.h)
     static constexpr bool kOneGroup = false, kRestart = false;      // every hit is instance 0's; ... and repeat primary rays start at their known hit's node (path_lane.h)
     static constexpr bool kCounts = false;                          // every pixel takes a sample count of its own and continues a caller's sum (path_lane.h)
+    static constexpr bool kMaskIdle = false;                        // the loop's primitive test and node step run with the lanes that have none switched off (trav_loop.h)
 };
 // a kernel that is none of these -- k_traverse (kernels.hip), k_trace_queue (fused_queue.hip): no pixels of its own or no seed, every block in its plain form
 template <bool HAS_SPHERES>
@@ -38,6 +39,7 @@ constexpr bool path_variant_checked() {
     static_assert(!V::kCapture || (!V::kReuse && !V::kBlocks), "the capture: plain launches only (no primary-hit cache, no sample blocks)");
     static_assert(!V::kBlocks || (!V::kInstanced && !V::kReuse), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
     static_assert(!V::kCounts || (!V::kReuse && !V::kBlocks && !V::kCapture), "per-pixel counts: plain launches only (no primary-hit cache, no sample blocks, no capture)");
+    static_assert(!V::kMaskIdle || (!V::kInstanced && !V::kSpheres), "idle lanes off: the loop copy whose primitive test and node step are straight-line arithmetic for the whole wave (one level, triangles)");
     return true;
 }
 
@@ -331,7 +333,10 @@ __device__ __forceinline__ bool cond_lane(WaveCond c) { return __builtin_amdgcn_
 // kRestart (k_path_restart, fused_restart.hip: kOneGroup, whose TravState::binst is free): binst keeps the RECORD the best hit was accepted from
 // (`rec`: the record's index, the lane's pidx) -- kMissPrim, which trav_start leaves there, where the lane has accepted none itself.  The
 // regeneration looks up the node whose leaf slot holds that record, where the pixel's next primary ray starts (fused_body.h: s_restart).
-template <class V, class Cond = bool>
+// kLiveIsExec (k_path_idle's loop copy with idle lanes off, trav_loop.h: kIdleOff -- not its drained copy, which tests for the whole wave): the
+// caller has switched the lanes without a record off, so `live` is implied -- a compare writes 0 for a lane that is off -- and is not
+// and-ed in; the best hit is updated in place (a lane that is off keeps its own).
+template <class V, class Cond = bool, bool kLiveIsExec = false>
 __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, const float4 C, TravState &s, const V3 o, const V3 d,
                                               float tmin, float tmax_ray,
                                               const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
@@ -381,7 +386,8 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
         const V3 qvec = cross3(tvec, e1);
         v = dot3(d, qvec) * inv;
         t = dot3(e2, qvec) * inv;
-        const Cond ok = live & Cond(det != 0.0f) & Cond(u >= 0.0f) & Cond(v >= 0.0f) & Cond(u + v <= 1.0f) & Cond(t > tmin) & Cond(t < tmax_ray);
+        const Cond nonzero(det != 0.0f);
+        const Cond ok = (kLiveIsExec ? nonzero : live & nonzero) & Cond(u >= 0.0f) & Cond(v >= 0.0f) & Cond(u + v <= 1.0f) & Cond(t > tmin) & Cond(t < tmax_ray);
         if constexpr (V::kOneGroup) {
             const Cond better = ok & (Cond(t < s.bt) | (Cond(t == s.bt) & Cond(prim < s.bprim)));
             const bool mine = cond_lane(better);
@@ -410,12 +416,12 @@ __device__ __forceinline__ Cond test_prim_ray(const float4 A, const float4 B, co
     return better;
 }
 
-template <class V, class Cond = bool>
+template <class V, class Cond = bool, bool kLiveIsExec = false>
 __device__ __forceinline__ Cond test_prim(const float4 A, const float4 B, const float4 C, TravState &s,
                                           float tmin, float tmax_ray,
                                           const float *__restrict__ inst_inv, const uint32_t *__restrict__ inst_identity, uint32_t inst_cur = 0u,
                                           Cond live = true, uint32_t rec = 0u) {
-    return test_prim_ray<V, Cond>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live, rec);
+    return test_prim_ray<V, Cond, kLiveIsExec>(A, B, C, s, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), tmin, tmax_ray, inst_inv, inst_identity, inst_cur, live, rec);
 }
 
 #define HRT_BYTE_F(w, k) ((float)(((w) >> (8 * (k))) & 0xffu))
@@ -554,12 +560,16 @@ __device__ __forceinline__ void node_slab_test(const TravState &s, float tmin, c
 }
 
 // Lane-utilisation counters of the instrumented build (`make stats`, tools/lane_stats.py); empty otherwise.
+constexpr unsigned long long kWaveClockLow = 1600ull, kWaveClockStep = 16ull, kWaveClockBins = 56ull;      // MHz: 1600 .. 2496 (HrtStats.wave_clock, include/hrt.h)
 struct LaneStats {
 #ifdef HRT_LANE_STATS
     unsigned long long iter = 0, alive = 0, node = 0, prim = 0, ppass = 0, regen = 0, enter = 0;
     // the drained phase (tools/tail_profile.py): iterations and alive lanes of the kTail copy of the loop, the wave's clock
     // (s_memrealtime: one 100 MHz counter for the whole device) when it first found the work used up
     unsigned long long tail_iter = 0, tail_alive = 0, t_drained = 0, mark_iter = 0, mark_alive = 0;
+    // the clock the wave ran at (tools/wave_clock.py): the shader clock's counter (s_memtime) beside the 100 MHz one, both read at the wave's
+    // first regeneration and at its exit -- clock = cycles / ticks x 100 MHz.  To the statistics slots only, never into an output.
+    unsigned long long c_first = 0, r_first = 0;
 #endif
     // the wave has found the tile used up (every regeneration from then on says so: the first one counts)
     __device__ __forceinline__ void drained([[maybe_unused]] bool exhausted) {
@@ -580,12 +590,20 @@ struct LaneStats {
     }
     __device__ __forceinline__ void regeneration() {
 #ifdef HRT_LANE_STATS
+        if (regen == 0ull) { r_first = __builtin_amdgcn_s_memrealtime(); c_first = __builtin_amdgcn_s_memtime(); }
         ++regen;
 #endif
     }
     __device__ __forceinline__ void iteration([[maybe_unused]] bool lane_alive, [[maybe_unused]] uint64_t mask_n, [[maybe_unused]] uint64_t mask_p) {
 #ifdef HRT_LANE_STATS
         ++iter; alive += __popcll(__ballot(lane_alive)); node += __popcll(mask_n); prim += __popcll(mask_p); ppass += mask_p != 0ull;
+#endif
+    }
+    // k_path_idle's loop copy with idle lanes off (trav_loop.h: kIdleOff) counts between two of these, where every lane is on: the counters
+    // are per-lane registers to the compiler, which would otherwise be free to add where lane 0, which reports, may be off
+    __device__ __forceinline__ void pin() {
+#ifdef HRT_LANE_STATS
+        asm volatile("" : "+v"(iter), "+v"(alive), "+v"(node), "+v"(prim), "+v"(ppass));
 #endif
     }
     __device__ __forceinline__ void entered([[maybe_unused]] bool lane_enters) {
@@ -613,6 +631,16 @@ struct LaneStats {
             // lane-ticks without a ray between draining and exit: the share of idle lanes over the drained iterations, times that span
             atomicAdd(t + 6, tail_iter ? (now - t_drained) * (lane_iters - tail_alive) / tail_iter : (now - t_drained) * 64ull);
             atomicAdd(t + 7, 1ull);
+            // DeviceStats::wave_clock, behind `paths`: waves, their cycles, their ticks, and the histogram of their clocks -- kWaveClockBins bins of
+            // kWaveClockStep MHz from kWaveClockLow (the ends take what lies beyond).  A wave that lived less than 10 us says nothing.
+            unsigned long long *c = d + 19;
+            const unsigned long long cycles = __builtin_amdgcn_s_memtime() - c_first, ticks = now - r_first;
+            if (regen != 0ull && ticks >= 1000ull) {
+                const unsigned long long mhz = cycles * 100ull / ticks;
+                const unsigned long long bin = mhz < kWaveClockLow ? 0ull : (mhz - kWaveClockLow) / kWaveClockStep;
+                atomicAdd(c + 0, 1ull); atomicAdd(c + 1, cycles); atomicAdd(c + 2, ticks);
+                atomicAdd(c + 4 + (bin < kWaveClockBins ? bin : kWaveClockBins - 1ull), 1ull);
+            }
         }
 #endif
     }

@@ -124,6 +124,42 @@ __device__ __forceinline__ void issue_node_loads_off(uint64_t mask, const void *
                  : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "=&s"(save) : "v"(off), "s"(base), "s"(mask) : "memory");
 }
 
+// kMaskIdle (k_path_idle, fused_idle.hip; trav_loop.h has the argument): the wave-wide primitive test / node step run for the lanes that loaded
+// a record / a node only, in the loop copy where every lane is active (kFull).  The masks are the ones the loads go out under, so the moves
+// are shared with them: the primitive group leaves its mask in exec, the node group sets its own and puts the PRIMITIVE mask back behind its
+// loads -- what the primitive test, which comes next, runs under (an empty mask: the pass is skipped, and nothing but scalar instructions
+// stands between here and the node step's move) --, the node step's wait sets the node mask, and all_lanes puts the literal back in front of
+// the bookkeeping sequence.  Five moves where the plain forms have four, nothing saved, no branch.  The compiler does not know that exec
+// changes, so each statement names, in/out, the registers that tie the arithmetic to its side of it: the landing registers (the phase's
+// arithmetic all hangs on them: it comes after), for the node step also the best hit (the primitive test's updates come before it; the
+// interval's k hangs on bt), for all_lanes what the node step made and the two work indices (the any-hit select on them comes after;
+// child.x / tri.x ARE landing registers, and naming them would cost a copy each).  The node mask is set in one statement with the wait
+// (trav_common.h: wait_node_loads), because the compiler puts an s_nop behind every statement that a vector instruction follows.
+__device__ __forceinline__ void issue_prim_loads_lanes(uint64_t mask, const void *base, uint32_t off, f32x4 &a, f32x4 &b, f32x4 &c) {
+    asm volatile("s_mov_b64 exec, %5\n\t"
+                 "global_load_dwordx4 %0, %3, %4\n\t"
+                 "global_load_dwordx4 %1, %3, %4 offset:16\n\t"
+                 "global_load_dwordx4 %2, %3, %4 offset:32"
+                 : "+v"(a), "+v"(b), "+v"(c) : "v"(off), "s"(base), "s"(mask) : "memory");
+}
+__device__ __forceinline__ void issue_node_loads_lanes(uint64_t mask, uint64_t prim_mask, const void *base, uint32_t off, u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, u32x4 &e) {
+    asm volatile("s_mov_b64 exec, %7\n\t"
+                 "global_load_dwordx4 %0, %5, %6\n\t"
+                 "global_load_dwordx4 %1, %5, %6 offset:16\n\t"
+                 "global_load_dwordx4 %2, %5, %6 offset:32\n\t"
+                 "global_load_dwordx4 %3, %5, %6 offset:48\n\t"
+                 "global_load_dwordx4 %4, %5, %6 offset:64\n\t"
+                 "s_mov_b64 exec, %8"
+                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "v"(off), "s"(base), "s"(mask), "s"(prim_mask) : "memory");
+}
+__device__ __forceinline__ void wait_node_loads_lanes(uint64_t mask, u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d, u32x4 &e, TravState &s) {
+    asm volatile("s_mov_b64 exec, %10\n\ts_waitcnt vmcnt(0)"
+                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(s.bt), "+v"(s.bu), "+v"(s.bv), "+v"(s.bprim), "+v"(s.binst) : "s"(mask) : "memory");
+}
+__device__ __forceinline__ void all_lanes(uint2 &child, uint2 &tri, uint32_t &nidx, uint32_t &pidx) {
+    asm volatile("s_mov_b64 exec, -1" : "+v"(child.y), "+v"(tri.y), "+v"(nidx), "+v"(pidx));
+}
+
 // Everything after the node step as ONE hand-written instruction sequence: file the node's two groups, decide on the leaf pass,
 // choose the primitive and the node of the next iteration, report finished rays.  (Written in C++ this is ~250 instructions,
 // two thirds of them mask bookkeeping: every `if` on per-lane data a mask save, a branch and a restore; here it is 97.)

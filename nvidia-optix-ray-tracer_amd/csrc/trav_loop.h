@@ -184,6 +184,7 @@ __device__ __forceinline__ void tail_retire(LeanLane &L, LaneFlags &F, const Mai
 // that give repeat primary rays a window) instead of the wave-uniform tmin -- the same instructions, one operand a vector register, not a scalar one.
 // kOneGroup (k_path_one): the primitive test and the tail-splitting blocks in their one-instance forms (trav_common.h: test_prim_ray).
 // kRestart (k_path_restart): ... which also keep the record of the lane's best hit (the primitive test is told the record it tests: pidx).
+// kMaskIdle (k_path_idle): the copy without tail splitting switches the lanes without a record / a node off for the primitive test / the node step (kIdleOff below).
 template <class V, bool kTail, class Inst>
 __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Inst &I, LaneStats &stats, const Mailboxes &mb,
                                                   uint2 (*nodes)[kTraverseBlock], uint2 (*leaves)[kTraverseBlock], uint32_t ldsn, uint32_t ldsl,
@@ -205,6 +206,22 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
     // test's `if` is on a mask's emptiness, and the blocks restore exec themselves.  The other copies keep the saving forms: their bodies
     // call helpers with per-lane control flow of their own (tail splitting, InstLane), which this argument does not cover.
     constexpr bool kFull = kCarryWork;
+    // kMaskIdle (k_path_idle, fused_idle.hip): in that copy the primitive test runs with exec = mask_p and the node step with exec = mask_n0 -- the
+    // lanes that loaded a record / a node; the others no longer compute on what their landing registers hold -- and exec is all ones again
+    // in front of the bookkeeping sequence.  The load groups already set these masks, so the moves are shared with them (trav_lean.h:
+    // issue_prim_loads_lanes, issue_node_loads_lanes, wait_node_loads_lanes, all_lanes): five moves to exec per iteration where the plain
+    // forms have four, nothing saved, no branch.  The argument above, extended to those writes: each is made at the top level of the body,
+    // on a wave-uniform mask; exec is all ones from all_lanes to the loads -- the bookkeeping sequence, the exit counts, the addresses -- and
+    // the only branch between the loads and all_lanes is the skip of an empty primitive pass, which is taken with exec = mask_p = 0 and
+    // rejoins in front of the node step's move with nothing but scalar instructions on the way.  What runs with lanes off is straight-line
+    // arithmetic that only a lane's own registers enter and leave:
+    //   C: a lane that is off writes 0 in every compare (so `live` is implied: test_prim_ray) and keeps its best hit, which is updated in place;
+    //   A: a lane that is off keeps stale child / tri, which is what mask_n0 already covers in the bookkeeping -- what lanes without a node
+    //      made of their registers is not filed;
+    // and everything that reads across lanes or is filed for every lane -- the any-hit select on nidx / pidx, the bookkeeping sequence, the
+    // exit counts, the next iteration's addresses -- runs behind all_lanes, as before.  tests/test_mask_idle_cpu.py reads the moves, their
+    // order and what the masked stretches write from the assembly.
+    constexpr bool kIdleOff = kFull && V::kMaskIdle;
     // The flag masks in scalar registers for the loop.  Between two calls the compiler keeps them in vector register pairs: the kernels
     // choose this copy or the other by `exhausted`, which is wave-uniform but a per-lane value to the compiler, and whatever is merged
     // behind such a branch is per-lane to it as well.  (Making those branches scalar instead keeps the masks where they are, and spills
@@ -222,11 +239,17 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         {
             uint32_t po = L.pidx * a.prim_stride, no = L.nidx * a.node_stride;      // (garbage for kNoWork: masked out)
             asm volatile("" : "+v"(po), "+v"(no));          // both offsets before the first load
-            if (mask_p != 0ull) issue_prim_loads_off<kFull>(mask_p, prim_bytes, po, rpa, rpb, rpc);
-            issue_node_loads_off<kFull>(mask_n0, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
+            if constexpr (kIdleOff) {
+                stats.pin(); stats.iteration(lane_bit(F.alive), mask_n0, mask_p); stats.pin();      // (counted here, where every lane is still on)
+                if (mask_p != 0ull) issue_prim_loads_lanes(mask_p, prim_bytes, po, rpa, rpb, rpc);
+                issue_node_loads_lanes(mask_n0, mask_p, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
+            } else {
+                if (mask_p != 0ull) issue_prim_loads_off<kFull>(mask_p, prim_bytes, po, rpa, rpb, rpc);
+                issue_node_loads_off<kFull>(mask_n0, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
+            }
             __builtin_amdgcn_s_setprio(HRT_PRIO_PRIM);
         }
-        stats.iteration(lane_bit(F.alive), mask_n0, mask_p);
+        if constexpr (!kIdleOff) stats.iteration(lane_bit(F.alive), mask_n0, mask_p);
         // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight).  Triangles:
         //      every lane tests (straight-line arithmetic, no loads) and a lane without a primitive rejects whatever its
         //      registers hold -- some lane nearly always has one, so a per-lane branch would save nothing but cost a mask
@@ -241,7 +264,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             const float4 pa = make_float4(rpa.x, rpa.y, rpa.z, rpa.w), pb = make_float4(rpb.x, rpb.y, rpb.z, rpb.w),
                          pc = make_float4(rpc.x, rpc.y, rpc.z, rpc.w);
             if constexpr (!V::kSpheres)
-                improved_m = test_prim<V, WaveCond>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p), L.pidx).m;
+                improved_m = test_prim<V, WaveCond, kIdleOff>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur, WaveCond(any_p), L.pidx).m;
             else {
                 bool improved = false;
                 if (L.pidx != kNoWork) improved = test_prim<V>(pa, pb, pc, L.s, tmin, tmax_ray, a.inst_inv, a.inst_identity, I.inst_cur);
@@ -258,7 +281,8 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         //      registers is not filed: mask_n0 below) ----
         uint2 child = make_uint2(0u, 0u), tri = make_uint2(0u, 0u);
         __builtin_amdgcn_s_setprio(HRT_PRIO_NODE);
-        wait_node_loads(rn0, rn1, rn2, rn3, rn4);
+        if constexpr (kIdleOff) wait_node_loads_lanes(mask_n0, rn0, rn1, rn2, rn3, rn4, L.s);
+        else wait_node_loads(rn0, rn1, rn2, rn3, rn4);
         [[maybe_unused]] bool enter = false;
         if constexpr (!V::kInstanced) {
             node_slab_test<kSlabInterval01>(L.s, V::kSeed ? L.s.tlo : tmin, rn0, rn1, rn2, rn3, rn4, child, tri);
@@ -272,6 +296,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
         //      primitive per lane, skipped while few lanes have leaf work and none depends on it); the primitive and the node of
         //      the next iteration; finished? ----
         __builtin_amdgcn_s_setprio(HRT_PRIO_BOOK);
+        if constexpr (kIdleOff) all_lanes(child, tri, L.nidx, L.pidx);
         // an any-hit ray is done with its first accepted intersection: nothing more to fetch (what is left on its stacks is
         // dropped when the lane's next ray starts, lean_start)
         if (hit_any) { L.nidx = kNoWork; L.pidx = kNoWork; }
