@@ -18,7 +18,7 @@ all: lib oracle tools
 lib: $(LIBDIR)/libhrt.so $(LIBDIR)/libhrt_io.so
 
 # the path kernels: one translation unit per kernel over the shared headers (trav_common.h, PathVariant: what each one is)
-PATH_UNITS := kernels fused fused_blocks fused_one fused_restart fused_idle fused_capture fused_counts fused_queue
+PATH_UNITS := kernels fused fused_blocks fused_one fused_restart fused_idle fused_direct fused_capture fused_counts fused_queue
 PATH_HDRS  := $(addprefix $(CSRC)/,device_types.h srgb_pow.h trav_common.h trav_lean.h trav_loop.h path_lane.h fused_body.h)
 PATH_OBJS  := $(PATH_UNITS:%=$(LIBDIR)/%.o)
 $(PATH_OBJS): $(LIBDIR)/%.o: $(CSRC)/%.hip $(PATH_HDRS)

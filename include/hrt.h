@@ -420,6 +420,9 @@ typedef struct HrtStats {
                                               clock's counter and the 100 MHz one read at a wave's first regeneration and at its exit -- waves, sum of
                                               their cycles, sum of their ticks, reserved, then 56 bins of 16 MHz from 1600 MHz (the ends take what lies
                                               beyond).  Added with mask_idle_launches: rebuild against this header */
+    uint64_t direct_launches;              /* of mask_idle_launches: those that ran k_path_direct, k_path_idle whose repeat primary rays test their known hit's
+                                              record in the regeneration and never enter the traversal loop (HRT_PRIMARY_DIRECT).  Added ahead of
+                                              mask_idle_launches, which tests/test_mask_idle_cpu.py pins in front of restart_launches: rebuild against this header */
     uint64_t mask_idle_launches;           /* of restart_launches: those that ran k_path_idle, k_path_restart with idle lanes switched off in the loop's
                                               primitive test and node step (HRT_MASK_IDLE).  Added ahead of restart_launches, which
                                               tests/test_primary_restart_cpu.py pins in front of one_group_launches: rebuild against this header */

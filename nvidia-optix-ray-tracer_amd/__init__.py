@@ -83,7 +83,7 @@ class Stats(C.Structure):
                 ("bvh_depth", C.c_uint64), ("fused_fallback_launches", C.c_uint64), ("graph_replays", C.c_uint64), ("bvh_alloc_bytes", C.c_uint64),
                 ("sample_block_launches", C.c_uint64), ("tail", C.c_uint64 * 8),
                 ("sample_block_schedule", C.c_uint64 * 4),
-                ("wave_clock", C.c_uint64 * 60), ("mask_idle_launches", C.c_uint64), ("restart_launches", C.c_uint64), ("one_group_launches", C.c_uint64), ("denoise_by_primitive_links", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
+                ("wave_clock", C.c_uint64 * 60), ("direct_launches", C.c_uint64), ("mask_idle_launches", C.c_uint64), ("restart_launches", C.c_uint64), ("one_group_launches", C.c_uint64), ("denoise_by_primitive_links", C.c_uint64), ("denoise_history_rebinds", C.c_uint64),
                 ("primary_capture_launches", C.c_uint64), ("guide_passes_traced", C.c_uint64), ("guide_passes_captured", C.c_uint64)]
 
 

@@ -356,6 +356,7 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);
 using PathLauncher = void(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);      // (its halves in the other kernels' translation units: each launches its own kernel)
 PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_idle, launch_path_round1, launch_path_counts;
+PathLauncher launch_path_direct;       // k_path_direct (fused_direct.hip): no enumerator -- launch_path_idle hands it the MaskIdle launches whose seed_primary is 3 (HRT_PRIMARY_DIRECT)
 // leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
 // counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
 // primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.

@@ -133,6 +133,8 @@ __device__ __forceinline__ const TraverseArgs &kernarg_traverse_args() {
 // kRestart: k_path_restart (fused_restart.hip) -- k_path_one whose repeat primary rays, which already start inside a window under their known hit,
 // also start at the NODE whose leaf slot holds that hit's record instead of at the root (path_lane.h: path_finish).
 // kCounts: k_path_counts (fused_counts.hip) -- every pixel takes its own number of samples and continues a sum the caller keeps (path_lane.h).
+// kDirect: k_path_direct (fused_direct.hip) -- k_path_idle whose repeat primary rays test their known hit's record in the regeneration that makes
+// them and never enter the loop: the regeneration block in its five-step order (below, at `finished`); the loop is untouched.
 template <class V>
 __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
     static_assert(kTraverseBlock == 64, "one wave per workgroup: the stacks are per wave");
@@ -205,6 +207,43 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
             force_regen = false;
             const uint64_t finished = F.waiting & ~F.alive;
             F.waiting &= F.alive;
+            // kDirect (k_path_direct; DESIGN.md section 2.1 "The record tested where the ray is made"): the block in the order
+            //   (a) what ends a path  (b) path_take  (c) the primary rays, and their records' tests  (d) the scatter, once  (e) the launch
+            // A lane whose path ends here and whose pixel goes on wants the pixel's primary ray again: the same ray, which a complete walk has
+            // shown to end in the hit accepted from record R (s_restart: the lane's word holds R, path_lane.h) -- no primitive computes a
+            // smaller (t, primitive id), and the canonical test of R with the identical ray recomputes the identical t, u, v.  So (c) tests R alone,
+            // with the culling bound at the seed as the loop would have it, and an accepted test leaves the lane with px_depth == 1 and the hit
+            // in L.s: it is shaded in (d), together with the lanes whose rays came back from the loop with a hit, and launches its bounce.  The
+            // ray is counted (path_count_ray), fetches its primitive and is decided by the canonical test against the launch's tmin and tmax;
+            // it never enters the loop and never waits.  A test that does not accept -- by the argument it cannot happen -- launches the ray
+            // from the root, bounded by seed and window, as k_path_idle would.  R's 48 bytes are asked for here, at the top, by the lanes that may
+            // come to test them -- a record, and a finished bounce that is a miss or at the depth limit -- and waited for in (c).
+            [[maybe_unused]] bool shade = false, may_test = false;
+            [[maybe_unused]] uint32_t rec = kNoWork;
+            // (the record's words the one-group test reads: A with the primitive id, and three floats each of B and C -- a fourth word that nobody
+            // reads is a register the compiler hands out again at once, and then waits for the load in front of whatever it put there)
+            typedef float f32x3 __attribute__((ext_vector_type(3)));
+            [[maybe_unused]] f32x4 ra;
+            [[maybe_unused]] f32x3 rb, rc;
+            if constexpr (V::kDirect) {
+                asm volatile("" : "=v"(ra), "=v"(rb), "=v"(rc));        // ("defined" without an instruction, like the loop's landing registers)
+                rec = s_restart[tx];
+                const bool ends_path = lane_bit(finished) && (L.s.bprim == kMissPrim || P.px_depth >= kRayTraceDepth);
+                shade = lane_bit(finished) && !ends_path;
+                may_test = ends_path && P.px_depth > 1u && rec != kNoWork;      // (a primary ray that ends its path is a miss: it leaves no record)
+                if (may_test) {
+                    typedef const __attribute__((address_space(1))) f32x4 *global_f32x4;
+                    typedef const __attribute__((address_space(1))) f32x3 *global_f32x3;
+                    const global_f32x4 rp = (global_f32x4)reinterpret_cast<const f32x4 *>(prim_bytes + rec * a.prim_stride);       // (32-bit byte offsets, as in the loop)
+                    ra = rp[0]; rb = *(global_f32x3)(rp + 1); rc = *(global_f32x3)(rp + 2);
+                }
+                if (lane_bit(finished)) {
+                    const TravState &s = L.s;
+                    st = path_finish<V, PathLane, 1>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), lean_miss_t(s.bt, s.bprim, a.tmax), s.bu, s.bv, s.bprim, 0u,
+                                                     s_seed + tx, s.binst, false, s_restart + tx);
+                }
+                may_test = may_test && st.want_primary;      // (the pixel goes on in this lane: a pixel that path_take hands out has no record)
+            } else
             if (lane_bit(finished)) {
                 const TravState &s = L.s;
                 // the finished ray and what it hit
@@ -237,6 +276,27 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                     st.ro = r.o; st.rd = r.d; st.launch = true;
                 }
             }
+            [[maybe_unused]] bool stat_primary = false, stat_quick = false, stat_direct = false;        // (the instrumented build's: LaneStats::started)
+            if constexpr (V::kDirect) {
+                // (c) the record's test, in place: the loop's inline function under the loop's `fp contract(off)`, on the ray path_primary has
+                // just made, with what lean_start would leave as the best hit -- the seed as the culling bound, no primitive
+                if (may_test && a.seed_primary >= 2 && s_seed[tx] < tmax_ray) {
+                    TravState &s = L.s;
+                    s.bt = s_seed[tx]; s.bu = 0.0f; s.bv = 0.0f; s.bprim = kMissPrim; s.binst = kMissPrim;
+                    const bool accepted = test_prim_ray<V>(make_float4(ra.x, ra.y, ra.z, ra.w), make_float4(rb.x, rb.y, rb.z, 0.0f), make_float4(rc.x, rc.y, rc.z, 0.0f), s, st.ro, st.rd,
+                                                           tmin, tmax_ray, a.inst_inv, a.inst_identity, 0u, true, rec);
+                    if (accepted) {
+                        (void)path_count_ray(P);        // (px_depth == 1: a closest-hit ray)
+                        s.ox = st.ro.x; s.oy = st.ro.y; s.oz = st.ro.z; s.dx = st.rd.x; s.dy = st.rd.y; s.dz = st.rd.z;
+                        st.launch = false; shade = true; stat_direct = true;
+                    }
+                }
+                // (d) the scatter, once: the finished lanes with a hit below the depth limit and the lanes whose test has just accepted
+                if (shade) {
+                    const TravState &s = L.s;
+                    st = path_finish<V, PathLane, 2>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), s.bt, s.bu, s.bv, s.bprim, 0u);
+                }
+            }
             bool any_hit = false;
             if (st.launch) {
                 any_hit = path_count_ray(P);
@@ -254,15 +314,18 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                     if (st.want_primary) {
                         hi = s_seed[tx];
                         if (a.seed_primary >= 2 && hi < tmax_ray) lo = seed_window_lo(st.rd, hi, tmin);
-                        if constexpr (V::kRestart) { if (a.seed_primary >= 2 && hi < tmax_ray) first_node = s_restart[tx]; }
+                        // (kDirect: the word holds a record, and a primary ray that is launched at all walks from the root)
+                        if constexpr (V::kRestart && !V::kDirect) { if (a.seed_primary >= 2 && hi < tmax_ray) first_node = s_restart[tx]; }
                     }
                 }
+                stat_primary = st.want_primary; stat_quick = st.want_primary && first_node != 0u;
                 lean_start(L, st.ro, st.rd, hi, lo);
                 if constexpr (V::kRestart) L.nidx = first_node;
                 if constexpr (V::kInstanced) I.inst_cur = kNoWork;      // (an any-hit ray may have ended inside an instance)
             }
             // the flags are wave masks (trav_loop.h): the lanes that have started a ray, and those that wait with a cached hit
             const uint64_t launched = __ballot(st.launch);
+            stats.started(stat_primary, stat_quick, stat_direct, launched);
             F.alive |= launched; F.any = (F.any & ~launched) | __ballot(any_hit);
             if constexpr (V::kReuse) F.waiting |= __ballot(reshade);
             // kReuse: lanes that have just taken their primary hit from the cache are shaded in a second regeneration, at once, so that

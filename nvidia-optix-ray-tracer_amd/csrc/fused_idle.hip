@@ -23,7 +23,10 @@ __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_pa
 }
 
 // (the leaf_parent table rides in PathArgs::slice_order, as in launch_path_restart)
+// (seed_primary == 3 -- render_fused under HRT_PRIMARY_DIRECT, never the environment's HRT_SEED_PRIMARY -- asks for k_path_direct, fused_direct.hip:
+// this kernel whose repeat primary rays test their known hit's record in the regeneration)
 void launch_path_idle(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
+    if (a.seed_primary == 3) { launch_path_direct(a, scene, grid_blocks, s); return; }
     TraverseArgs b = a;
     b.path.slice_order = scene.leaf_parent;
     hipLaunchKernelGGL(k_path_idle, dim3(grid_blocks), dim3(kTraverseBlock), 0, s, b);

@@ -565,13 +565,20 @@ static int render_fused(const LaunchFrame &f) {
             if (t->dev.d_leaf_parent == nullptr) kernel = PathKernel::OneGroup;
         }
         if (kernel == PathKernel::Capture) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
+        // HRT_PRIMARY_DIRECT: a launch that gets k_path_idle says seed_primary = 3, which its launcher reads as "k_path_direct" (fused_idle.hip) -- this
+        // launch only; the environment's HRT_SEED_PRIMARY stays 0..2, and what the window is and who gets one is seed_primary >= 2 as before
+        const bool direct = kernel == PathKernel::MaskIdle && ctx->primary_direct;
+        const int seed_primary = ta.seed_primary;
+        if (direct) ta.seed_primary = 3;
         bool admitted;
         { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, path_scene(*t), grid, s); }
+        ta.seed_primary = seed_primary;
         if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
         if (kernel == PathKernel::Capture) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
         if (kernel == PathKernel::OneGroup || kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->one_group_launches++;
         if (kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->restart_launches++;
         if (kernel == PathKernel::MaskIdle) ctx->mask_idle_launches++;
+        if (direct) ctx->direct_launches++;
         done_spp += now;
     }
     FinalizeArgs fa{};
@@ -1027,7 +1034,7 @@ int hrt_stats_get(HrtContext *ctx, HrtStats *out) {
     out->guide_passes_traced = ctx->guide_passes_traced; out->guide_passes_captured = ctx->guide_passes_captured;
     out->denoise_history_rebinds = ctx->denoise_history_rebinds;
     out->denoise_by_primitive_links = ctx->denoise_by_primitive_links;
-    out->one_group_launches = ctx->one_group_launches; out->restart_launches = ctx->restart_launches; out->mask_idle_launches = ctx->mask_idle_launches;
+    out->one_group_launches = ctx->one_group_launches; out->restart_launches = ctx->restart_launches; out->mask_idle_launches = ctx->mask_idle_launches; out->direct_launches = ctx->direct_launches;
     return HRT_OK;
 }
 

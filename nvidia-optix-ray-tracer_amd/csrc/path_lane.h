@@ -161,14 +161,23 @@ __device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_
 // The lane of such a kernel is a CountsLane (above): px_aw, the fourth accumulator next to px_ax / px_ay / px_az, and gave_up.
 // A pixel of count c = min(counts[p], spp) starts at px_sample = spp - c, so that it ends where every pixel does, at px_sample >= spp, and
 // the count needs no register; c == 0 is given up in path_take, before anything of it is loaded or stored.
+// kDirect (k_path_direct, fused_direct.hip; DESIGN.md section 2.1 "The record tested where the ray is made"): the lane's word `restart` holds the
+// RECORD a primary ray accepted its hit from (kNoWork: none -- a miss, or a hit that came out of a mailbox), not a node, and no table is read:
+// the regeneration tests that record against the pixel's next primary ray where it makes the ray (fused_body.h).  Its block runs this function
+// in two parts, with path_take and the primary rays between them: kPart 1, for every finished lane -- the seed, the record, and what ends a
+// path (a lane whose ray goes on to be shaded comes back with nothing to do) -- and kPart 2, the shading branch alone, for the lanes that
+// have a hit to shade: the finished ones and those whose record's test accepted.  kPart 0: all of it, one call, every other kernel.
 typedef const __attribute__((address_space(1))) uint32_t *global_words;
-template <class V, class Lane>
+template <class V, class Lane, int kPart = 0>
 __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
                                             [[maybe_unused]] float *seed = nullptr, [[maybe_unused]] uint32_t brec = 0u, [[maybe_unused]] bool restartable = false,
                                             [[maybe_unused]] uint32_t *restart = nullptr) {
+    static_assert((kPart == 0) == !V::kDirect, "path_finish in two parts: k_path_direct's regeneration, and only that");
     PathStep st;
     const bool miss = bprim == kMissPrim;
-    if constexpr (V::kSeed) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
+    constexpr bool kEnds = kPart != 2, kShades = kPart != 1;      // which of the branches below this call has
+    if constexpr (V::kSeed && kEnds) { if (P.px_depth == 1u && a.seed_primary) *seed = bt; }    // the pixel's primary ray (a miss says tmax: none; a caller's ray: its lane takes anew)
+    if constexpr (V::kDirect && kEnds) { if (P.px_depth == 1u) *restart = miss ? kMissPrim : brec; }      // (kMissPrim is the word's "none", trav_lean.h: kNoWork)
     if constexpr (V::kCapture) {
         if (!a.path.trace_rays && P.px_depth == 1u && P.px_sample == 0u) {      // (the primary-hit cache's condition, fused_body.h)
             a.path.trace_tuvp[P.px_tid] = make_float4(bt, bu, bv, __uint_as_float(bprim));
@@ -181,7 +190,7 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
         a.path.trace_tuvp[P.px_local] = make_float4(bt, bu, bv, __uint_as_float(bprim));
         a.path.trace_inst[P.px_local] = binst;
         P.have_pixel = false;
-    } else if (miss || P.px_depth >= kRayTraceDepth) {
+    } else if (kEnds && (miss || P.px_depth >= kRayTraceDepth)) {
         // the path ends: miss colour or black at the depth limit, folded through the albedo chain (Shader.cu:102-107, :236-238, :276-287)
         V3 r;
         if constexpr (V::kOneGroup) r = fold_chain_one(miss, a.path.bg, P.px_depth, a.path.hitgroups);
@@ -232,6 +241,8 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
             }
             P.have_pixel = false;
         } else st.want_primary = true;
+    } else if constexpr (V::kOneGroup && !kShades) {
+        // (kPart 1: this lane's hit is shaded by the block's second call)
     } else if constexpr (V::kOneGroup) {
         // entry 0 of both tables, in scalar registers: the normals' loads go out as soon as the pointer is there, and what the program is --
         // rough or metal, fuzz or none -- is the same in every lane, so scatter_programs' choices are the wave's
@@ -240,7 +251,7 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
         hg.ptr0 = hp0->ptr0; hg.ptr1 = nullptr; hg.albedo[0] = hg.albedo[1] = hg.albedo[2] = 0.0f; hg.fuzz = hp0->fuzz;      // (what a triangle program reads)
         const uint32_t program = *(constant_words)a.path.inst_program;
         [[maybe_unused]] uint32_t node = 0u;
-        if constexpr (V::kRestart) {
+        if constexpr (V::kRestart && !V::kDirect) {
             // (no branch: every lane here loads -- entry 0 where it has nothing to look up -- and keeps the word or 0)
             const bool look = P.px_depth == 1u && restartable && brec != kMissPrim;
             node = ((global_words)a.path.slice_order)[look ? brec : 0u];
@@ -248,7 +259,7 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
         }
         V3 hp, nd;
         scatter_programs<V::kSpheres>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
-        if constexpr (V::kRestart) { if (P.px_depth == 1u) *restart = node; }
+        if constexpr (V::kRestart && !V::kDirect) { if (P.px_depth == 1u) *restart = node; }
         ++P.px_depth;
         st.ro = hp; st.rd = nd; st.launch = true;
     } else {
@@ -328,7 +339,7 @@ __device__ __forceinline__ bool path_take_slice(Lane &P, PathStep &st, const Tra
                 P.px_local = j;
                 P.have_pixel = true; st.want_primary = true;
                 if constexpr (V::kSeed && !V::kBlocks) *seed = a.tmax;
-                if constexpr (V::kRestart) *restart = 0u;
+                if constexpr (V::kRestart) *restart = V::kDirect ? kMissPrim : 0u;      // (kDirect: no record -- record 0 is a record)
                 [[maybe_unused]] float carried = 0.0f;      // (kBlocks) the seed the pixel brings along
                 if (V::kBlocks || !a.path.trace_rays) {
                     const uint32_t row = j / a.path.width;

@@ -23,6 +23,7 @@ struct PathVariant {      // every flag false
     static constexpr bool kOneGroup = false, kRestart = false;      // every hit is instance 0's; ... and repeat primary rays start at their known hit's node (path_lane.h)
     static constexpr bool kCounts = false;                          // every pixel takes a sample count of its own and continues a caller's sum (path_lane.h)
     static constexpr bool kMaskIdle = false;                        // the loop's primitive test and node step run with the lanes that have none switched off (trav_loop.h)
+    static constexpr bool kDirect = false;                          // repeat primary rays test their known hit's record in the regeneration and never enter the loop (fused_body.h)
 };
 // a kernel that is none of these -- k_traverse (kernels.hip), k_trace_queue (fused_queue.hip): no pixels of its own or no seed, every block in its plain form
 template <bool HAS_SPHERES>
@@ -30,6 +31,8 @@ struct PlainVariant : PathVariant { static constexpr bool kSpheres = HAS_SPHERES
 // the persistent kernel (fused_body.h) seeds, unless it does not traverse a pixel's repeat primary rays at all
 template <bool REUSE>
 struct FusedBodyVariant : PathVariant { static constexpr bool kReuse = REUSE, kSeed = !REUSE; };
+// k_path_direct (fused_direct.hip): k_path_idle's variant (fused_idle.hip: MaskIdleVariant, flag for flag) plus kDirect
+struct DirectVariant : FusedBodyVariant<false> { static constexpr bool kBlocks = true, kOneGroup = true, kRestart = true, kMaskIdle = true, kDirect = true; };
 // The constraints between the flags, in one place: fused_body asserts this of its variant, once.
 template <class V>
 constexpr bool path_variant_checked() {
@@ -40,6 +43,7 @@ constexpr bool path_variant_checked() {
     static_assert(!V::kBlocks || (!V::kInstanced && !V::kReuse), "sample blocks: one-level trees, no primary-hit cache (which wants a pixel's samples in one lane)");
     static_assert(!V::kCounts || (!V::kReuse && !V::kBlocks && !V::kCapture), "per-pixel counts: plain launches only (no primary-hit cache, no sample blocks, no capture)");
     static_assert(!V::kMaskIdle || (!V::kInstanced && !V::kSpheres), "idle lanes off: the loop copy whose primitive test and node step are straight-line arithmetic for the whole wave (one level, triangles)");
+    static_assert(!V::kDirect || (V::kRestart && V::kOneGroup && V::kBlocks && V::kSeed), "the record tested where the ray is made: the record rides in binst (kRestart), the seed is the test's bound, and the regeneration is the one-group block render's");
     return true;
 }
 
@@ -570,6 +574,13 @@ struct LaneStats {
     // the clock the wave ran at (tools/wave_clock.py): the shader clock's counter (s_memtime) beside the 100 MHz one, both read at the wave's
     // first regeneration and at its exit -- clock = cycles / ticks x 100 MHz.  To the statistics slots only, never into an output.
     unsigned long long c_first = 0, r_first = 0;
+#ifdef HRT_LANE_STATS_PRIMARY
+    // what a pixel's repeat primary rays cost (make stats EXTRA_HIPFLAGS=-DHRT_LANE_STATS_PRIMARY, tools/lane_stats.py primary):
+    // primary rays that entered the loop, those of them that started at a node other than the root (`quick`: their lanes, a wave mask), the
+    // iterations those were alive and the iterations they waited for their regeneration, and the rays decided in the regeneration
+    // (kDirect).  They take the drained phase's slots (HrtStats.tail), which such a build does not fill.
+    unsigned long long quick = 0, prim_rays = 0, quick_rays = 0, quick_alive = 0, quick_wait = 0, direct_rays = 0;
+#endif
 #endif
     // the wave has found the tile used up (every regeneration from then on says so: the first one counts)
     __device__ __forceinline__ void drained([[maybe_unused]] bool exhausted) {
@@ -599,11 +610,30 @@ struct LaneStats {
         ++iter; alive += __popcll(__ballot(lane_alive)); node += __popcll(mask_n); prim += __popcll(mask_p); ppass += mask_p != 0ull;
 #endif
     }
+    // a regeneration has started its rays: `primary` -- the lane's is its pixel's primary ray, `quick` -- ... which does not start at the root,
+    // `direct` -- the lane's primary ray was decided here, by its record's test (counted as a primitive test), and `launched`: the wave's new rays
+    __device__ __forceinline__ void started([[maybe_unused]] bool primary, [[maybe_unused]] bool quick_lane, [[maybe_unused]] bool direct, [[maybe_unused]] uint64_t launched) {
+#if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
+        const unsigned long long q = __ballot(quick_lane);
+        quick = (quick & ~launched) | q;
+        prim_rays += __popcll(__ballot(primary)); quick_rays += __popcll(q);
+        const unsigned long long n = __popcll(__ballot(direct));
+        direct_rays += n; prim += n;
+#endif
+    }
+    __device__ __forceinline__ void primary_slots([[maybe_unused]] uint64_t alive_m, [[maybe_unused]] uint64_t waiting_m) {
+#if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
+        quick_alive += __popcll(quick & alive_m); quick_wait += __popcll(quick & waiting_m);
+#endif
+    }
     // k_path_idle's loop copy with idle lanes off (trav_loop.h: kIdleOff) counts between two of these, where every lane is on: the counters
     // are per-lane registers to the compiler, which would otherwise be free to add where lane 0, which reports, may be off
     __device__ __forceinline__ void pin() {
 #ifdef HRT_LANE_STATS
         asm volatile("" : "+v"(iter), "+v"(alive), "+v"(node), "+v"(prim), "+v"(ppass));
+#ifdef HRT_LANE_STATS_PRIMARY
+        asm volatile("" : "+v"(quick), "+v"(quick_alive), "+v"(quick_wait));
+#endif
 #endif
     }
     __device__ __forceinline__ void entered([[maybe_unused]] bool lane_enters) {
@@ -626,11 +656,16 @@ struct LaneStats {
             if (base == 0ull) base = now;
             if (t_drained == 0ull) t_drained = now;
             const unsigned long long bias = 1ull << 40, exit_rel = now - base + bias, lane_iters = 64ull * tail_iter;
+#ifdef HRT_LANE_STATS_PRIMARY
+            (void)bias; (void)lane_iters; (void)exit_rel;
+            atomicAdd(t + 0, prim_rays); atomicAdd(t + 1, quick_rays); atomicAdd(t + 3, quick_alive); atomicAdd(t + 4, quick_wait); atomicAdd(t + 5, direct_rays);
+#else
             atomicAdd(t + 0, tail_iter); atomicAdd(t + 1, tail_alive);
             atomicMax(t + 3, ~(t_drained - base + bias)); atomicMax(t + 4, exit_rel); atomicAdd(t + 5, exit_rel);
             // lane-ticks without a ray between draining and exit: the share of idle lanes over the drained iterations, times that span
             atomicAdd(t + 6, tail_iter ? (now - t_drained) * (lane_iters - tail_alive) / tail_iter : (now - t_drained) * 64ull);
             atomicAdd(t + 7, 1ull);
+#endif
             // DeviceStats::wave_clock, behind `paths`: waves, their cycles, their ticks, and the histogram of their clocks -- kWaveClockBins bins of
             // kWaveClockStep MHz from kWaveClockLow (the ends take what lies beyond).  A wave that lived less than 10 us says nothing.
             unsigned long long *c = d + 19;

@@ -240,7 +240,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             uint32_t po = L.pidx * a.prim_stride, no = L.nidx * a.node_stride;      // (garbage for kNoWork: masked out)
             asm volatile("" : "+v"(po), "+v"(no));          // both offsets before the first load
             if constexpr (kIdleOff) {
-                stats.pin(); stats.iteration(lane_bit(F.alive), mask_n0, mask_p); stats.pin();      // (counted here, where every lane is still on)
+                stats.pin(); stats.iteration(lane_bit(F.alive), mask_n0, mask_p); stats.primary_slots(F.alive, F.waiting); stats.pin();      // (counted here, where every lane is still on)
                 if (mask_p != 0ull) issue_prim_loads_lanes(mask_p, prim_bytes, po, rpa, rpb, rpc);
                 issue_node_loads_lanes(mask_n0, mask_p, node_bytes, no, rn0, rn1, rn2, rn3, rn4);
             } else {
@@ -249,7 +249,7 @@ __device__ __forceinline__ void traverse_to_regen(LeanLane &L, LaneFlags &F, Ins
             }
             __builtin_amdgcn_s_setprio(HRT_PRIO_PRIM);
         }
-        if constexpr (!kIdleOff) stats.iteration(lane_bit(F.alive), mask_n0, mask_p);
+        if constexpr (!kIdleOff) { stats.iteration(lane_bit(F.alive), mask_n0, mask_p); stats.primary_slots(F.alive, F.waiting); }
         // ---- C. leaf test: waits for the primitive pieces only (the node loads issued behind them stay in flight).  Triangles:
         //      every lane tests (straight-line arithmetic, no loads) and a lane without a primitive rejects whatever its
         //      registers hold -- some lane nearly always has one, so a per-lane branch would save nothing but cost a mask

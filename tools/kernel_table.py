@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The static table of the nineteen kernels that run the lean traversal loop (k_fused, k_path_blocks, k_path_one, k_path_restart, k_path_idle, k_path_capture, k_trace_queue), as the profile files
+"""The static table of the twenty kernels that run the lean traversal loop (k_fused, k_path_blocks, k_path_one, k_path_restart, k_path_idle, k_path_direct, k_path_capture, k_trace_queue), as the profile files
 give it: tools/loop_stats.py's counts of the first loop copy, registers, spills and LDS from the code object's metadata, v_readlane_b32
 in the whole kernel -- all from the assembly the Makefile's flags produce.
 Usage: tools/kernel_table.py"""
@@ -10,7 +10,7 @@ sys.path.insert(0, str(ROOT / "tools"))
 import loop_stats
 
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
-FILES = (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_one", "_ZN3hrt10k_path_one"), ("fused_restart", "_ZN3hrt14k_path_restart"), ("fused_idle", "_ZN3hrt11k_path_idle"), ("fused_capture", "_ZN3hrt14k_path_capture"), ("fused_counts", "_ZN3hrt13k_path_counts"), ("fused_queue", "_ZN3hrt13k_trace_queue"))
+FILES = (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_one", "_ZN3hrt10k_path_one"), ("fused_restart", "_ZN3hrt14k_path_restart"), ("fused_idle", "_ZN3hrt11k_path_idle"), ("fused_direct", "_ZN3hrt13k_path_direct"), ("fused_capture", "_ZN3hrt14k_path_capture"), ("fused_counts", "_ZN3hrt13k_path_counts"), ("fused_queue", "_ZN3hrt13k_trace_queue"))
 
 
 def short(name):

@@ -2,7 +2,9 @@
 """Lane utilisation of the fused path kernel per phase (C4, 16 spp; `tools/lane_stats.py spp N`: N samples, e.g. 256 for the schedule bench.py
 times, and HRT_SAMPLE_BLOCK=4 with 16 for a block render of few samples).  Needs a library built with the counters compiled in:
     touch nvidia-optix-ray-tracer_amd/csrc/kernels.hip && make lib HIPFLAGS="$(make -pn | sed -n 's/^HIPFLAGS := //p') -DHRT_LANE_STATS"
-(the counters reuse HrtStats.debug[] and the two counting fields the production kernels leave at zero)."""
+(the counters reuse HrtStats.debug[] and the two counting fields the production kernels leave at zero).
+`tools/lane_stats.py spp 256 primary`, on `make stats EXTRA_HIPFLAGS=-DHRT_LANE_STATS_PRIMARY` through HRT_LIB: also what a pixel's repeat
+primary rays cost -- how many there are, how many start at a node or are decided in the regeneration, the iterations they are alive and wait."""
 import importlib, sys
 sys.path.insert(0, str(__import__("pathlib").Path(__file__).resolve().parent.parent))
 hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
@@ -24,3 +26,14 @@ print("rays", s.rays, "wave iterations", it, "regenerations", regen, "iters/ray-
 print("alive lanes/iter %.1f  node lanes/iter %.1f  prim lanes/iter %.1f" % (alive/it, node/it, prim/it))
 print("prim passes per iteration %.3f  lanes per prim pass %.1f  regens per iteration %.4f (every %.1f iterations)" % (ppass/it, prim/max(ppass,1), regen/it, it/max(regen,1)))
 print("node steps per ray %.2f  prim tests per ray %.2f" % (node/s.rays, prim/s.rays))
+if "primary" in sys.argv:
+    # a library built with `make stats EXTRA_HIPFLAGS=-DHRT_LANE_STATS_PRIMARY` (trav_common.h: LaneStats): what a pixel's repeat primary rays cost.
+    # The counters take the drained phase's slots (HrtStats.tail); a record tested in the regeneration (k_path_direct) counts as a primitive test.
+    t = s.tail
+    prim_rays, quick, q_alive, q_wait, direct = t[0], t[1], t[3], t[4], t[5]
+    all_primary = prim_rays + direct
+    print("kernel", "k_path_direct" if s.direct_launches else "k_path_idle" if s.mask_idle_launches else "another")
+    print("primary rays", all_primary, "walked from the root", prim_rays - quick, "started at a node other than the root", quick, "decided in the regeneration", direct)
+    print("h = share of primary rays with a record %.4f" % ((quick + direct) / max(all_primary, 1)))
+    print("iterations the rays started at a node were alive", q_alive, "(%.2f each)  waited for their regeneration" % (q_alive / max(quick, 1)), q_wait, "(%.2f each)" % (q_wait / max(quick, 1)))
+    print("their lane-slots %d of %d = %.2f %%" % (q_alive + q_wait, 64 * it, 100.0 * (q_alive + q_wait) / (64 * it)))

@@ -84,7 +84,7 @@ if __name__ == "__main__":
     want = sys.argv[1:]
     for src, prefix in (("nvidia-optix-ray-tracer_amd/csrc/kernels.hip", "_ZN3hrt10k_traverse"), ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"),
                         ("nvidia-optix-ray-tracer_amd/csrc/fused_blocks.hip", "_ZN3hrt13k_path_blocks"), ("nvidia-optix-ray-tracer_amd/csrc/fused_one.hip", "_ZN3hrt10k_path_one"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_restart.hip", "_ZN3hrt14k_path_restart"), ("nvidia-optix-ray-tracer_amd/csrc/fused_idle.hip", "_ZN3hrt11k_path_idle"),
+                        ("nvidia-optix-ray-tracer_amd/csrc/fused_restart.hip", "_ZN3hrt14k_path_restart"), ("nvidia-optix-ray-tracer_amd/csrc/fused_idle.hip", "_ZN3hrt11k_path_idle"), ("nvidia-optix-ray-tracer_amd/csrc/fused_direct.hip", "_ZN3hrt13k_path_direct"),
                         ("nvidia-optix-ray-tracer_amd/csrc/fused_capture.hip", "_ZN3hrt14k_path_capture"),
                         ("nvidia-optix-ray-tracer_amd/csrc/fused_counts.hip", "_ZN3hrt13k_path_counts")):
         for name, cs, ops in loops(src, prefix):
