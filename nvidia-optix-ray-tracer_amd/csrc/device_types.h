@@ -1,4 +1,5 @@
-// device_types.h -- records and kernel argument blocks shared by kernels.hip and the host API.
+// device_types.h -- records and kernel argument blocks shared by the kernels' translation units and the host API, and the path kernels'
+// launch path: the list of kernels, the choice of a launch's kernel and the admission rule.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -319,17 +320,33 @@ constexpr int kFusedMaxDepth = 12;     // deepest tree (levels below the root) k
 constexpr uint32_t kTraversalStackEntries = 64;   // per-lane stack of round 1's kernels, which take what k_fused cannot (trav_common.h: kLdsStack + kSpillStack); a tree of
                                                   // depth d needs 2 d + 2 of them, and a build that comes out deeper fails (hrt_accel.cpp)
 // ---- the path kernels: one launch renders every sample of every pixel of a tile (or traces callers' rays, PathArgs::trace_rays) ----
+// Every kernel is an enumerator; which one a launch gets (choose_path_launch), what it takes for granted (path_launch_admitted) and the one
+// entry that launches it (launch_path_kernel) follow, the first two as plain host code that tests/test_path_launch_cpu.py runs without a device.
 enum class PathKernel {
-    Fused, FusedInstanced,      // k_fused (fused.hip): one-level trees, two-level trees (transform nodes, bvh8.h); with PathArgs::primary_cache, its primary-reuse instantiation
+    Fused,              // k_fused (fused.hip): one-level trees; with PathArgs::primary_cache, its primary-reuse instantiation
+    FusedInstanced,     // k_fused<.., INSTANCED> (fused.hip): two-level trees (transform nodes, bvh8.h)
     Capture,            // k_path_capture (fused_capture.hip): k_fused<S, I, false> that also keeps every pixel's primary hit
     Blocks,             // k_path_blocks (fused_blocks.hip): pixels handed out in sample blocks
     OneGroup,           // k_path_one (fused_one.hip): the block render of a scene with one hit group
     Restart,            // k_path_restart (fused_restart.hip): k_path_one whose repeat primary rays start at the node of their known hit
     Round1,             // k_traverse<.., FUSED> (kernels.hip): round 1's fused kernel, for the trees k_fused cannot take
-    Counts              // k_path_counts (fused_counts.hip): k_fused<S, I, false> over a caller's sums, every pixel with a sample count of its own (hrt_render_accumulate)
-    , MaskIdle          // k_path_idle (fused_idle.hip): k_path_restart whose loop switches idle lanes off for the primitive test and the node step
+    Counts,             // k_path_counts (fused_counts.hip): k_fused<S, I, false> over a caller's sums, every pixel with a sample count of its own (hrt_render_accumulate)
+    MaskIdle,           // k_path_idle (fused_idle.hip): k_path_restart whose loop switches idle lanes off for the primitive test and the node step
+    Direct              // k_path_direct (fused_direct.hip): k_path_idle whose repeat primary rays test their known hit's record in the regeneration
 };
 struct PathScene { bool one_level; uint32_t n_instances; bool has_spheres; const uint32_t *leaf_parent; };      // what the TraverseArgs do not say about the tree (leaf_parent: below, or NULL)
+// The ladder of the one-group block kernels, each the one before it plus one thing: k_path_one (1), k_path_restart (2), k_path_idle (3),
+// k_path_direct (4); every other kernel 0.  A kernel takes for granted what every rung up to its own does, and a launch of it counts for each
+// of them (HrtStats: one_group_launches >= restart_launches >= mask_idle_launches >= direct_launches).
+inline int path_ladder_rung(PathKernel kernel) {
+    switch (kernel) {
+        case PathKernel::OneGroup: return 1;
+        case PathKernel::Restart: return 2;
+        case PathKernel::MaskIdle: return 3;
+        case PathKernel::Direct: return 4;
+        default: return 0;
+    }
+}
 // What each kernel takes for granted, in one place: its regeneration does not look at the fields it is compiled without, so a launch that
 // contradicts the kernel it names is refused instead of rendering something else.  Plain host code: no device, nothing launched.
 inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const PathScene &scene) {
@@ -337,26 +354,39 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
     // a render in sample blocks: a one-level tree, no callers' rays, no cost probe, no slice order; ... of triangles over exactly one instance, whose table entries exist
     const bool in_blocks = scene.one_level && p.sample_block != 0u && p.trace_rays == nullptr && p.slice_cost == nullptr && p.slice_order == nullptr;
     const bool one_group = in_blocks && scene.n_instances == 1u && !scene.has_spheres && p.hitgroups != nullptr && p.inst_program != nullptr;
+    // the ladder: one hit group; from the restart on the table, and the window its rays start in (k_path_idle and k_path_direct: the same launch, the kernel alone differs)
+    if (const int rung = path_ladder_rung(kernel)) return one_group && (rung < 2 || (scene.leaf_parent != nullptr && a.seed_primary >= 2));
     switch (kernel) {
         case PathKernel::Fused: return scene.one_level && p.sample_block == 0u;           // (the caller names the block kernels: nothing forwards)
         case PathKernel::FusedInstanced: return !scene.one_level && p.sample_block == 0u;
         case PathKernel::Capture: return p.sample_block == 0u && p.trace_rays == nullptr && p.primary_cache == nullptr;      // (trace_tuvp / trace_inst carry its arrays)
         case PathKernel::Blocks: return in_blocks;
-        case PathKernel::OneGroup: return one_group;
-        case PathKernel::Restart: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;      // (the table, and the window its rays start in)
-        case PathKernel::MaskIdle: return one_group && scene.leaf_parent != nullptr && a.seed_primary >= 2;     // (exactly what Restart takes)
         case PathKernel::Round1: return true;
         // (accum: the caller's sums, trace_inst: the samples they hold, slice_order: the counts or NULL -- so no callers' rays, no cost probe, no order)
         case PathKernel::Counts: return p.sample_block == 0u && p.trace_rays == nullptr && p.primary_cache == nullptr && p.slice_cost == nullptr &&
                                         p.accum != nullptr && p.trace_inst != nullptr && p.spp != 0u;
+        default: return false;
     }
-    return false;
+}
+// The kernel of ONE launch of a render (hrt_api.cpp: render_fused), from what is decided by then: the tree's kernel (Fused, FusedInstanced or
+// Round1), whether the render captures primary hits -- of a render cut into several launches the first one does, and never one in blocks: the
+// primary ray of a pixel's first sample is every sample's --, whether this launch goes in sample blocks, and how many samples earlier launches
+// have taken.  A launch in blocks of a scene with ONE hit group -- a one-level tree of triangles over exactly one instance, any single-mesh
+// render -- climbs the ladder as far as the knobs let it: k_path_one (HRT_ONE_GROUP=0: k_path_blocks like everything else); where its repeat
+// primary rays get their window (HRT_SEED_PRIMARY=2) and the tree has its leaf_parent table, k_path_restart (HRT_PRIMARY_RESTART=0: k_path_one);
+// k_path_idle (HRT_MASK_IDLE); k_path_direct (HRT_PRIMARY_DIRECT).  Decided per launch, from the tree that is launched: an update that adds an
+// instance sends the next launch back to k_path_blocks.  Plain host code like the rule above, which admits whatever this returns.
+struct PathKnobs { bool one_group, primary_restart, mask_idle, primary_direct; };
+inline PathKernel choose_path_launch(PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary, const PathKnobs &knobs, const PathScene &scene) {
+    if (!blocks) return capture && done_spp == 0u ? PathKernel::Capture : tree_kernel;
+    if (!(knobs.one_group && scene.one_level && scene.n_instances == 1u && !scene.has_spheres)) return PathKernel::Blocks;
+    if (!(knobs.primary_restart && seed_primary == 2 && scene.leaf_parent != nullptr)) return PathKernel::OneGroup;      // (a tree without records has no table)
+    return !knobs.mask_idle ? PathKernel::Restart : knobs.primary_direct ? PathKernel::Direct : PathKernel::MaskIdle;
 }
 // The one launch entry of the path kernels (fused.hip).  false: refused (path_launch_admitted), nothing launched.
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);
 using PathLauncher = void(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s);      // (its halves in the other kernels' translation units: each launches its own kernel)
-PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_idle, launch_path_round1, launch_path_counts;
-PathLauncher launch_path_direct;       // k_path_direct (fused_direct.hip): no enumerator -- launch_path_idle hands it the MaskIdle launches whose seed_primary is 3 (HRT_PRIMARY_DIRECT)
+PathLauncher launch_path_capture, launch_path_blocks, launch_path_one, launch_path_restart, launch_path_idle, launch_path_direct, launch_path_round1, launch_path_counts;
 // leaf_parent[record] = index of the node whose leaf slot covers that record, for every record of a finished one-level tree (refit.hip; the host's
 // counterpart, over a blob: hrt_host_leaf_parent).  A leaf slot's meta byte holds the unary count in bits 7..5 and the offset from the node's
 // primitive base in bits 4..0 (bvh8.h); split references have a record each, so every record has exactly one slot.

@@ -42,7 +42,8 @@ static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t gr
     }
 }
 
-// The one way a path kernel is launched: the launch is held to what the kernel the caller names takes for granted, and that kernel's own translation unit launches it
+// The one way a path kernel is launched: the launch is held to what the kernel the caller names takes for granted, and that kernel's own translation unit
+// launches it.  Every kernel has its enumerator and its case: no launcher forwards to another kernel, and no argument doubles as a selector.
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
     if (!path_launch_admitted(kernel, a, scene)) return false;
     switch (kernel) {
@@ -53,6 +54,7 @@ bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScen
         case PathKernel::OneGroup: launch_path_one(a, scene, grid_blocks, s); break;
         case PathKernel::Restart: launch_path_restart(a, scene, grid_blocks, s); break;
         case PathKernel::MaskIdle: launch_path_idle(a, scene, grid_blocks, s); break;
+        case PathKernel::Direct: launch_path_direct(a, scene, grid_blocks, s); break;
         case PathKernel::Round1: launch_path_round1(a, scene, grid_blocks, s); break;
         case PathKernel::Counts: launch_path_counts(a, scene, grid_blocks, s); break;
     }

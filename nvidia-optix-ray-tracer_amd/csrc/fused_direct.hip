@@ -8,14 +8,17 @@
 // fetches its primitive and is decided by the canonical test against the launch's tmin and tmax (fused_body.h: kDirect; DESIGN.md sections 2.1
 // and 4.1).  The traversal loop is k_path_idle's, instruction for instruction: everything new is in the regeneration.  Same pixels, same random
 // numbers, same ray counts, same bits.  A kernel and a translation unit of its own: the other kernels' instruction streams are not touched.
+// PathKernel::Direct (device_types.h): chosen where k_path_idle would be and HRT_PRIMARY_DIRECT is on, launched by the one entry like the rest.
 #include "fused_body.h"
 
 #pragma clang fp contract(off)
 
 namespace hrt {
 
-// (DirectVariant: trav_common.h.  The TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the
-// regeneration reads its constants from the segment itself, fused_body.h: kernarg_traverse_args)
+// k_path_idle's variant (fused_idle.hip: MaskIdleVariant, flag for flag) plus kDirect
+struct DirectVariant : FusedBodyVariant<false> { static constexpr bool kBlocks = true, kOneGroup = true, kRestart = true, kMaskIdle = true, kDirect = true; };
+// (the TraverseArgs must stay the ONLY explicit argument, at offset 0 of the kernel-argument segment: the regeneration reads its constants
+// from the segment itself, fused_body.h: kernarg_traverse_args)
 __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_path_direct(TraverseArgs a) {
     fused_body<DirectVariant>(a);
 }

@@ -8,7 +8,8 @@
 // what is not computed was never used.  The point is energy, not instructions: a quarter fewer active lane-operations per iteration, which the
 // chip returns as clock -- 2250 -> 2320 MHz under this kernel on C4, +1.2 % in time (profiles/r29_idle_lanes.txt).
 // A kernel and a translation unit of its own: k_path_restart's loop, registers and LDS are pinned by tests/test_primary_restart_cpu.py, and
-// the other kernels' instruction streams are not touched.
+// the other kernels' instruction streams are not touched.  PathKernel::MaskIdle (device_types.h); k_path_direct, which is this kernel plus
+// one flag, has its own enumerator, unit and launcher (fused_direct.hip).
 #include "fused_body.h"
 
 #pragma clang fp contract(off)
@@ -23,10 +24,7 @@ __global__ __launch_bounds__(kTraverseBlock, HRT_FUSED_WAVES_PER_SIMD) void k_pa
 }
 
 // (the leaf_parent table rides in PathArgs::slice_order, as in launch_path_restart)
-// (seed_primary == 3 -- render_fused under HRT_PRIMARY_DIRECT, never the environment's HRT_SEED_PRIMARY -- asks for k_path_direct, fused_direct.hip:
-// this kernel whose repeat primary rays test their known hit's record in the regeneration)
 void launch_path_idle(const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
-    if (a.seed_primary == 3) { launch_path_direct(a, scene, grid_blocks, s); return; }
     TraverseArgs b = a;
     b.path.slice_order = scene.leaf_parent;
     hipLaunchKernelGGL(k_path_idle, dim3(grid_blocks), dim3(kTraverseBlock), 0, s, b);

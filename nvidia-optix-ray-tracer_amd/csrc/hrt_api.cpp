@@ -278,17 +278,10 @@ static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
     return {PathKernel::Fused, std::min<uint32_t>(knob, (uint32_t)kFusedBlocksPerCu)};
 }
 static PathScene path_scene(const Tlas &t) { return {!t.two_level, t.n_instances, t.has_spheres, t.dev.d_leaf_parent}; }
-// The kernel of ONE launch of render_fused, from what is decided by then: the tree's kernel (choose_path_kernel), whether the render captures
-// primary hits -- of a render cut into several launches the first one does: the primary ray of a pixel's first sample is every sample's --,
-// whether this launch goes in sample blocks, and how many samples earlier launches have taken.  A launch in blocks of a scene with ONE hit
-// group -- a one-level tree of triangles over exactly one instance, any single-mesh render -- takes k_path_one (HRT_ONE_GROUP=0: k_path_blocks
-// like everything else) or, where its repeat primary rays get their window (HRT_SEED_PRIMARY=2), k_path_restart (HRT_PRIMARY_RESTART=0:
-// k_path_one).  Decided per launch, from the tree that is launched: an update that adds an instance sends the next launch back to k_path_blocks.
-static PathKernel launch_kernel(const HrtContext *ctx, const Tlas &t, PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary) {
-    if (!blocks) return capture && done_spp == 0u ? PathKernel::Capture : tree_kernel;
-    if (!(ctx->one_group && !t.two_level && t.n_instances == 1u && !t.has_spheres)) return PathKernel::Blocks;
-    if (!(ctx->primary_restart && seed_primary == 2)) return PathKernel::OneGroup;
-    return ctx->mask_idle ? PathKernel::MaskIdle : PathKernel::Restart;       // (HRT_MASK_IDLE: the same launch, the same table)
+// A launch counts for its kernel and for every kernel that one is built on (device_types.h: path_ladder_rung).
+static void count_ladder_launch(HrtContext *ctx, PathKernel kernel) {
+    uint64_t *const rungs[] = {&ctx->one_group_launches, &ctx->restart_launches, &ctx->mask_idle_launches, &ctx->direct_launches};
+    for (int r = 0; r < path_ladder_rung(kernel); ++r) ++*rungs[r];
 }
 extern "C++" {      // (helpers of hrt_internal.hpp, shared with hrt_denoise.cpp)
 namespace hrt {
@@ -558,27 +551,23 @@ static int render_fused(const LaunchFrame &f) {
         // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
         if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
         ctx->fused_counters_clean = false;
-        PathKernel kernel = launch_kernel(ctx, *t, pk.kernel, capture, blocks, done_spp, ta.seed_primary);
-        if (kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) {      // it wants the tree's leaf_parent table, made here the first time (a tree without records: k_path_one, the launch as it was)
+        // Which kernel (device_types.h: choose_path_launch, which says what decides it).  From k_path_restart on a launch wants the tree's
+        // leaf_parent table, made here the first time; a tree without records has none, and its launch stays k_path_one's.
+        const PathKnobs knobs{ctx->one_group, ctx->primary_restart, ctx->mask_idle, ctx->primary_direct};
+        PathScene scene = path_scene(*t), with_table = scene;
+        with_table.leaf_parent = &now;      // (any address: "if the table were there")
+        if (path_ladder_rung(choose_path_launch(pk.kernel, capture, blocks, done_spp, ta.seed_primary, knobs, with_table)) >= 2) {
             const int rc = ensure_leaf_parent(ctx, *t, s);
             if (rc != HRT_OK) return rc;
-            if (t->dev.d_leaf_parent == nullptr) kernel = PathKernel::OneGroup;
+            scene = path_scene(*t);
         }
+        const PathKernel kernel = choose_path_launch(pk.kernel, capture, blocks, done_spp, ta.seed_primary, knobs, scene);
         if (kernel == PathKernel::Capture) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
-        // HRT_PRIMARY_DIRECT: a launch that gets k_path_idle says seed_primary = 3, which its launcher reads as "k_path_direct" (fused_idle.hip) -- this
-        // launch only; the environment's HRT_SEED_PRIMARY stays 0..2, and what the window is and who gets one is seed_primary >= 2 as before
-        const bool direct = kernel == PathKernel::MaskIdle && ctx->primary_direct;
-        const int seed_primary = ta.seed_primary;
-        if (direct) ta.seed_primary = 3;
         bool admitted;
-        { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, path_scene(*t), grid, s); }
-        ta.seed_primary = seed_primary;
+        { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, scene, grid, s); }
         if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
         if (kernel == PathKernel::Capture) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
-        if (kernel == PathKernel::OneGroup || kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->one_group_launches++;
-        if (kernel == PathKernel::Restart || kernel == PathKernel::MaskIdle) ctx->restart_launches++;
-        if (kernel == PathKernel::MaskIdle) ctx->mask_idle_launches++;
-        if (direct) ctx->direct_launches++;
+        count_ladder_launch(ctx, kernel);
         done_spp += now;
     }
     FinalizeArgs fa{};

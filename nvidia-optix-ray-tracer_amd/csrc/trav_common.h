@@ -31,8 +31,6 @@ struct PlainVariant : PathVariant { static constexpr bool kSpheres = HAS_SPHERES
 // the persistent kernel (fused_body.h) seeds, unless it does not traverse a pixel's repeat primary rays at all
 template <bool REUSE>
 struct FusedBodyVariant : PathVariant { static constexpr bool kReuse = REUSE, kSeed = !REUSE; };
-// k_path_direct (fused_direct.hip): k_path_idle's variant (fused_idle.hip: MaskIdleVariant, flag for flag) plus kDirect
-struct DirectVariant : FusedBodyVariant<false> { static constexpr bool kBlocks = true, kOneGroup = true, kRestart = true, kMaskIdle = true, kDirect = true; };
 // The constraints between the flags, in one place: fused_body asserts this of its variant, once.
 template <class V>
 constexpr bool path_variant_checked() {

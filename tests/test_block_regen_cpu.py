@@ -12,6 +12,8 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "nvidia-optix-ray-tracer_amd" / "csrc"
+sys.path.insert(0, str(ROOT / "tools"))
+import path_kernels          # noqa: E402
 HIPCC = "/opt/rocm/bin/hipcc"
 FIELDS = ("trace_rays", "slice_cost", "slice_order")
 
@@ -34,16 +36,8 @@ int main() {
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     """{"offsets": {field: byte offset in TraverseArgs}, "bodies": {mangled kernel name: [lines]}}"""
-    sys.path.insert(0, str(ROOT / "tools"))
-    from audit_asm_loads import makefile_hipflags
     tmp = tmp_path_factory.mktemp("block_regen")
-    flags = [f for f in makefile_hipflags() if f != "-fPIC"]
-    bodies = {}
-    for stem, prefix in (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks")):
-        asm = tmp / f"{stem}.s"
-        subprocess.check_call([HIPCC, *flags, "-S", "--cuda-device-only", "-o", str(asm), str(CSRC / f"{stem}.hip")], cwd=ROOT, stderr=subprocess.DEVNULL)
-        for m in re.finditer(r"^(" + prefix + r"\w+):[^\n]*\n(.*?)s_endpgm", asm.read_text(), re.S | re.M):
-            bodies[m.group(1)] = m.group(2).split("\n")
+    bodies = {name: k["body"] for stem in ("fused", "fused_blocks") for name, k in path_kernels.compile_unit(stem, tmp / f"{stem}.s").items()}
     src, exe = tmp / "offsets.cpp", tmp / "offsets"
     src.write_text(OFFSETS_CPP)
     subprocess.check_call([HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-I" + str(ROOT / "include"), "-I" + str(CSRC), "-o", str(exe), str(src)], stderr=subprocess.DEVNULL)

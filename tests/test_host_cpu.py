@@ -296,34 +296,29 @@ def test_path_kernel_hot_loop_keeps_its_instruction_budget(tmp_path):
     scenes -- 171 of the single-pipe kind -- with no scratch access, at 4 waves per SIMD (<= 128 VGPRs).  tools/loop_stats.py
     compiles fused.hip with the Makefile's flags and counts; a compiler, flag or source change that fattens the loop, spills inside
     it or costs a wave of occupancy fails here, before anybody has to find it in a benchmark."""
-    import re
     import sys
     from pathlib import Path
-    root = Path(__file__).resolve().parent.parent
-    sys.path.insert(0, str(root / "tools"))
-    import loop_stats
-    found = {name: (cs, ops) for name, cs, ops in loop_stats.loops("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused", asm=tmp_path / "fused.s")}
-    tri = [v for k, v in found.items() if "ILb0ELb0ELb0E" in k]          # <HAS_SPHERES = false, INSTANCED = false, REUSE = false>: C4's kernel
-    assert len(found) == 8 and len(tri) == 1, sorted(found)
-    cs, ops = tri[0]
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
+    import path_kernels
+    found = path_kernels.compile_unit("fused", tmp_path / "fused.s")
+    assert len(found) == 8 and all(k["lines"] for k in found.values()), sorted(found)
+    tri = path_kernels.one(found, "ILb0ELb0ELb0E")          # <HAS_SPHERES = false, INSTANCED = false, REUSE = false>: C4's kernel
+    cs, ops = tri["loop"], tri["ops"]
     assert sum(cs.values()) <= 480, dict(cs)
     assert cs["valu_complex"] <= 175 and cs["salu"] <= 110, dict(cs)
     assert not any(op.startswith("scratch_") or op.startswith("buffer_") for op in ops), sorted(ops)
-    text = (tmp_path / "fused.s").read_text()
     # 4 waves per SIMD (<= 128 VGPRs) for the one-level kernels; the INSTANCED instantiations are compiled for 3 (<= 168)
-    counts = sorted(int(v) for v in re.findall(r"\.vgpr_count:\s+(\d+)", text))
-    assert len(counts) == 8 and counts[3] <= 128 and counts[7] <= 168, counts
+    counts = sorted(k["meta"]["vgpr_count"] for k in found.values())
+    assert counts[3] <= 128 and counts[7] <= 168, counts
     # ... and what they keep in scratch stays what it is (kernel constants, reloaded around the shading): a 12th register spilled by the C4
     # kernel was a reload in every regeneration (round 4: a second SGPR operand of the bookkeeping sequence had done that)
-    spills = {m.group(1): int(m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", text)}
-    by_kind = {k: v for k, v in spills.items() if "k_fused" in k}
-    assert len(by_kind) == 8, sorted(spills)
+    by_kind = {name: k["meta"]["vgpr_spill_count"] for name, k in found.items()}
     assert max(v for k, v in by_kind.items() if "ILb0ELb0ELb0E" in k) <= 11 and max(v for k, v in by_kind.items() if "ILb1ELb0ELb0E" in k) <= 14, by_kind
     assert all(v == 0 for k, v in by_kind.items() if "ELb1ELb" in k.split("k_fusedILb")[1][:9]), by_kind      # INSTANCED: nothing spilled at 3 waves per SIMD
     # the REUSE instantiations (HRT_CTX_REUSE_PRIMARY) keep the same loop: nothing of theirs is inside it
-    for k, (cs_k, ops_k) in found.items():
-        if "ILb0ELb0ELb1E" in k:
-            assert sum(cs_k.values()) <= 480 and not any(op.startswith("scratch_") for op in ops_k), (k, dict(cs_k))
+    for name, k in found.items():
+        if "ILb0ELb0ELb1E" in name:
+            assert sum(k["loop"].values()) <= 480 and not any(op.startswith("scratch_") for op in k["ops"]), (name, dict(k["loop"]))
 
 
 def test_context_flags_of_the_binding_are_the_headers(hrt):

@@ -14,44 +14,32 @@ the same compiler, not a constant:
       a register written in the node stretch is read by the bookkeeping sequence at most (whose masks cover it: trav_lean.h) and written
       again before anything reads it behind that; and no vector instruction stands between the skip of an empty primitive pass and the
       node stretch's move, where exec may be either;
-  (d) the launch entry admits for the new enumerator exactly what it admits for Restart, over Restart's cases of tests/test_path_launch_cpu.py;
+  (d) the launch entry admits for the enumerator exactly what it admits for Restart: tests/test_path_launch_cpu.py;
   (e) the flag, the knob and the counter are where the text says."""
 import re
-import subprocess
 import sys
 from pathlib import Path
 
 import pytest
 
-import test_path_launch_cpu as pl
-
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
 sys.path.insert(0, str(ROOT / "tools"))
+import audit_asm_loads, loop_stats, path_kernels          # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    import loop_stats
     tmp = tmp_path_factory.mktemp("mask_idle")
     out = {}
-    for key, stem, prefix in (("idle", "fused_idle", "_ZN3hrt11k_path_idle"), ("restart", "fused_restart", "_ZN3hrt14k_path_restart")):
-        asm = tmp / f"{stem}.s"
-        loops = dict(loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=asm))
-        assert len(loops) == 1, sorted(loops)
-        name, loop = next(iter(loops.items()))
-        text = asm.read_text()
-        body = re.search(r"^" + re.escape(name) + r":[^\n]*\n(.*?)s_endpgm", text, re.S | re.M).group(1).split("\n")
-        entry = [e for e in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:] if re.search(r"\.name:\s+(\S+)", e).group(1) == name]
-        assert len(entry) == 1
-        meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry[0], re.M)}
-        out[key] = {"text": text, "loop": [(op, l.strip()) for op, l in loop_stats.instructions(loop)], "body": body, "meta": meta}
+    for key, stem in (("idle", "fused_idle"), ("restart", "fused_restart")):
+        k = path_kernels.one(path_kernels.compile_unit(stem, tmp / f"{stem}.s"))
+        out[key] = {"text": (tmp / f"{stem}.s").read_text(), "loop": [(op, l.strip()) for op, l in loop_stats.instructions(k["lines"])], "body": k["body"], "meta": k["meta"]}
     return out
 
 
 # ---------------------------------------------------------------- (a) the budget ----------------------------------------------------------------
 def test_the_budget_against_k_path_restart(compiled):
-    import loop_stats
     idle, restart = compiled["idle"], compiled["restart"]
     n_i, n_r = len(idle["loop"]), len(restart["loop"])
     s_i, s_r = (sum(loop_stats.kind(op) == "salu" for op, _ in k["loop"]) for k in (idle, restart))
@@ -70,8 +58,7 @@ def test_the_budget_against_k_path_restart(compiled):
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait():
-    import audit_asm_loads
-    groups, bad = audit_asm_loads.audit(CSRC + "fused_idle.hip", "_ZN3hrt11k_path_idle")
+    groups, bad = audit_asm_loads.audit(*path_kernels.source("fused_idle"))
     assert groups > 0 and bad == 0, (groups, bad)
 
 
@@ -197,27 +184,13 @@ def test_what_runs_with_lanes_off_stays_in_its_stretch(compiled):
     assert not _read_before_written(seq[end + 1:] + seq[:ip], written)
 
 
-# ---------------------------------------------------------------- (d) the launch entry ----------------------------------------------------------------
-def test_the_entry_admits_what_it_admits_for_restart(tmp_path):
-    cases = [(change, ok) for k, change, ok in pl.CASES if k == "Restart"]
-    # the admitted launch, no table, seed_primary 0 and 1, callers' rays, a second instance -- and the rest of Restart's
-    for needle in ("", "scene.leaf_parent = nullptr;", "a.seed_primary = 0;", "a.seed_primary = 1;", "a.path.trace_rays = &ray;", "scene.n_instances = 2u;"):
-        assert any(change == needle for change, _ in cases), needle
-    scene, base = pl.BASE["Restart"]
-    lines = [pl.CASE % (scene, base, change, k) for change, _ in cases for k in ("MaskIdle", "Restart")]
-    src, exe = tmp_path / "admitted.cpp", tmp_path / "admitted"
-    src.write_text(pl.PROGRAM % "\n".join(lines))
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT / 'include'}", f"-I{ROOT / CSRC}", "-o", str(exe), str(src)])
-    out = [v == "1" for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert len(out) == 2 * len(cases)
-    for k, (change, want) in enumerate(cases):
-        assert out[2 * k] == want and out[2 * k + 1] == want, (change, want, out[2 * k], out[2 * k + 1])
+# (d) the launch entry: tests/test_path_launch_cpu.py, whose table holds every case of Restart for MaskIdle and Direct as well
 
 
 # ---------------------------------------------------------------- (e) the flag, the knob, the counter ----------------------------------------------------------------
 def test_the_flag_the_knob_and_the_counter(hrt):
     for path in sorted((ROOT / CSRC).glob("*.hip")):
-        assert ("kMaskIdle" in path.read_text()) == (path.name == "fused_idle.hip"), path.name
+        assert ("kMaskIdle" in path.read_text()) == (path.name in ("fused_idle.hip", "fused_direct.hip")), path.name          # (k_path_direct is k_path_idle plus kDirect)
     body = (ROOT / CSRC / "fused_idle.hip").read_text()
     assert re.findall(r"fused_body<([^;]*)>\(", body) == ["MaskIdleVariant"]
     variant = re.search(r"struct MaskIdleVariant : (\S+) \{(.*?)\};", body, re.S)
@@ -229,5 +202,4 @@ def test_the_flag_the_knob_and_the_counter(hrt):
     assert "ctx->mask_idle = std::atoi(e) != 0" in line
     names = [f[0] for f in hrt.Stats._fields_]
     assert names.index("mask_idle_launches") + 1 == names.index("restart_launches")
-    for tool in ("kernel_table.py", "loop_stats.py", "audit_asm_loads.py"):
-        assert "_ZN3hrt11k_path_idle" in (ROOT / "tools" / tool).read_text(), tool
+    assert ("fused_idle", "_ZN3hrt11k_path_idle", "k_path_idle") in path_kernels.UNITS

@@ -12,6 +12,8 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
+sys.path.insert(0, str(ROOT / "tools"))
+import audit_asm_loads, loop_stats, path_kernels          # noqa: E402
 
 # (instructions, scalar instructions, modelled cycles, single-pipe VALU instructions) of the first copy of k_path_one's loop: what the build
 # shows.  k_path_blocks<0>: 408 / 74 / 1185 / 144.
@@ -23,28 +25,14 @@ assert all(a <= b for a, b in zip(LOOP, CEILING))
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     """{"one" / "blocks": {"loop": lines of the first loop copy, "body": lines of the kernel, "meta": {key: int}, "args": [...], "text": the file}}"""
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
     tmp = tmp_path_factory.mktemp("one_group")
     out = {}
-    for key, stem, prefix, fragment in (("one", "fused_one", "_ZN3hrt10k_path_one", "k_path_one"), ("blocks", "fused_blocks", "_ZN3hrt13k_path_blocks", "k_path_blocksILb0E")):
-        asm = tmp / f"{stem}.s"
-        loops = {name: lines for name, lines in loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=asm) if fragment in name}
-        assert len(loops) == 1, sorted(loops)
-        name, loop = next(iter(loops.items()))
-        text = asm.read_text()
-        bodies = {m.group(1): m.group(2).split("\n") for m in re.finditer(r"^(" + prefix + r"\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)}
-        entry = [e for e in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:] if re.search(r"\.name:\s+(\S+)", e).group(1) == name]
-        assert len(entry) == 1
-        meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry[0], re.M)}
-        args = re.findall(r"- \.offset:\s+(\d+)\n\s+\.size:\s+(\d+)\n\s+\.value_kind:\s+(\w+)", entry[0])
-        out[key] = {"name": name, "loop": loop, "body": bodies[name], "meta": meta, "args": args, "text": text}
+    for key, stem, fragment in (("one", "fused_one", "k_path_one"), ("blocks", "fused_blocks", "k_path_blocksILb0E")):
+        found = {name: k for name, k in path_kernels.compile_unit(stem, tmp / f"{stem}.s").items() if fragment in name and k["lines"]}
+        assert len(found) == 1, sorted(found)
+        name, k = next(iter(found.items()))
+        out[key] = {"name": name, "loop": k["lines"], "body": k["body"], "meta": k["meta"], "args": k["args"], "text": (tmp / f"{stem}.s").read_text()}
     return out
-
-
-def _opcodes(lines):
-    import loop_stats
-    return [op for op, _ in loop_stats.instructions(lines)]
 
 
 def _regeneration(body):
@@ -60,9 +48,8 @@ def test_one_kernel_in_the_file(compiled):
 
 
 def test_the_loop_stays_within_what_this_build_shows(compiled):
-    import loop_stats
     kinds = {}
-    for op in _opcodes(compiled["one"]["loop"]):
+    for op in loop_stats.opcodes(compiled["one"]["loop"]):
         kinds[loop_stats.kind(op)] = kinds.get(loop_stats.kind(op), 0) + 1
     total, salu, single = sum(kinds.values()), kinds.get("salu", 0), kinds.get("valu_complex", 0)
     cycles = loop_stats.model_cycles({k: kinds.get(k, 0) for k in ("valu_simple", "valu_complex", "salu")})
@@ -71,7 +58,7 @@ def test_the_loop_stays_within_what_this_build_shows(compiled):
 
 
 def test_the_loop_is_no_larger_than_k_path_blocks(compiled):
-    assert len(_opcodes(compiled["one"]["loop"])) <= len(_opcodes(compiled["blocks"]["loop"]))
+    assert len(loop_stats.opcodes(compiled["one"]["loop"])) <= len(loop_stats.opcodes(compiled["blocks"]["loop"]))
 
 
 def test_no_mask_save_behind_the_bookkeeping_sequence(compiled):
@@ -84,25 +71,25 @@ def test_no_mask_save_behind_the_bookkeeping_sequence(compiled):
 def test_registers_and_spills(compiled):
     meta = compiled["one"]["meta"]
     assert meta["vgpr_count"] <= 128 and meta["vgpr_spill_count"] == 0 and meta["sgpr_spill_count"] == 0, meta
-    ops = _opcodes(compiled["one"]["body"])
+    ops = loop_stats.opcodes(compiled["one"]["body"])
     assert not any(op.startswith("scratch_") or op.startswith("buffer_") for op in ops)
     # a spilled scalar register comes back with v_readlane_b32: no more of them than k_path_blocks<0> has (the wave reduction at its end)
-    assert ops.count("v_readlane_b32") <= _opcodes(compiled["blocks"]["body"]).count("v_readlane_b32") <= 4
-    assert "v_readlane_b32" not in _opcodes(_regeneration(compiled["one"]["body"]))
+    assert ops.count("v_readlane_b32") <= loop_stats.opcodes(compiled["blocks"]["body"]).count("v_readlane_b32") <= 4
+    assert "v_readlane_b32" not in loop_stats.opcodes(_regeneration(compiled["one"]["body"]))
 
 
 def test_lds_and_no_flat_instruction(compiled):
     assert compiled["one"]["meta"]["group_segment_fixed_size"] == 10240, compiled["one"]["meta"]
-    assert not any(op.startswith("flat_") for op in _opcodes(compiled["one"]["body"]))
+    assert not any(op.startswith("flat_") for op in loop_stats.opcodes(compiled["one"]["body"]))
 
 
 def test_the_slab_tests_clamp(compiled):
     """the ray interval is folded into the slab test's FMAs (tests/test_slab_interval_cpu.py): DX10 clamping on, 16 clamped FMAs per loop copy"""
     text = compiled["one"]["text"]
     assert re.search(r"^\s*\.amdhsa_dx10_clamp 1\s*$", text, re.M)
-    clamped = [l for op, l in __import__("loop_stats").instructions(compiled["one"]["loop"]) if op == "v_fma_f32" and re.search(r"\bclamp\b", l)]
+    clamped = [l for op, l in loop_stats.instructions(compiled["one"]["loop"]) if op == "v_fma_f32" and re.search(r"\bclamp\b", l)]
     assert len(clamped) == 16, len(clamped)
-    in_kernel = [l for op, l in __import__("loop_stats").instructions(compiled["one"]["body"]) if op == "v_fma_f32" and re.search(r"\bclamp\b", l)]
+    in_kernel = [l for op, l in loop_stats.instructions(compiled["one"]["body"]) if op == "v_fma_f32" and re.search(r"\bclamp\b", l)]
     assert len(in_kernel) == 32, len(in_kernel)          # two copies of the loop
 
 
@@ -115,7 +102,7 @@ def test_the_traverse_args_are_the_only_explicit_argument(compiled):
 def test_the_regeneration_has_fewer_vector_loads(compiled):
     """hitgroups[0], inst_program[0] and the albedos are scalar loads: at least five global_load fewer than k_path_blocks<0> between the outer
     loop's header and the first traversal loop, and more scalar loads instead"""
-    one, blocks = _opcodes(_regeneration(compiled["one"]["body"])), _opcodes(_regeneration(compiled["blocks"]["body"]))
+    one, blocks = loop_stats.opcodes(_regeneration(compiled["one"]["body"])), loop_stats.opcodes(_regeneration(compiled["blocks"]["body"]))
     n_one, n_blocks = sum(op.startswith("global_load") for op in one), sum(op.startswith("global_load") for op in blocks)
     print("global_load", n_one, n_blocks, "s_load", sum(op.startswith("s_load") for op in one), sum(op.startswith("s_load") for op in blocks))
     assert n_one <= n_blocks - 5, (n_one, n_blocks)
@@ -130,7 +117,5 @@ def test_the_other_translation_units_do_not_name_the_flag():
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait():
-    sys.path.insert(0, str(ROOT / "tools"))
-    import audit_asm_loads
-    groups, bad = audit_asm_loads.audit(CSRC + "fused_one.hip", "_ZN3hrt10k_path_one")
+    groups, bad = audit_asm_loads.audit(*path_kernels.source("fused_one"))
     assert groups > 0 and bad == 0, (groups, bad)

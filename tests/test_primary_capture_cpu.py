@@ -10,34 +10,16 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
-CAPTURE = ("fused_capture", "_ZN3hrt14k_path_capture")
+sys.path.insert(0, str(ROOT / "tools"))
+import audit_asm_loads, path_kernels          # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     """{mangled kernel name: {"loop": Counter of kinds, "ops": Counter of the loop's opcodes, "meta": {key: int}, "args": [...]}}"""
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
     tmp = tmp_path_factory.mktemp("capture_kernels")
-    out = {}
-    for stem, prefix in (("fused", "_ZN3hrt7k_fused"), CAPTURE):
-        asm = tmp / f"{stem}.s"
-        loops = {name: (cs, ops) for name, cs, ops in loop_stats.loops(CSRC + f"{stem}.hip", prefix, asm=asm)}
-        text = asm.read_text()
-        for entry in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", entry).group(1)
-            if name not in loops:
-                continue
-            meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry, re.M)}
-            args = re.findall(r"- \.offset:\s+(\d+)\n\s+\.size:\s+(\d+)\n\s+\.value_kind:\s+(\w+)", entry)
-            out[name] = {"loop": loops[name][0], "ops": loops[name][1], "meta": meta, "args": args}
-    return out
-
-
-def _kernel(compiled, fragment):
-    found = [v for k, v in compiled.items() if fragment in k]
-    assert len(found) == 1, (fragment, sorted(compiled))
-    return found[0]
+    units = [path_kernels.compile_unit(stem, tmp / f"{stem}.s") for stem in ("fused", "fused_capture")]
+    return {name: k for unit in units for name, k in unit.items() if k["lines"]}
 
 
 def test_four_kernels_whose_only_argument_is_the_traverse_args(compiled):
@@ -58,8 +40,8 @@ SPILLS = {(0, 0): (0, 0), (1, 0): (0, 0), (0, 1): (0, 0), (1, 1): (0, 0)}
 def test_the_capture_kernel_keeps_k_fuseds_loop_and_registers(compiled, spheres, instanced):
     """No scratch or buffer access in the traversal loop; a loop no larger than the matching k_fused<S, I, false> loop plus 4
     instructions; the parent's occupancy (<= 128 VGPRs one-level, 4 waves per SIMD; <= 168 instanced, 3 waves); the spills recorded."""
-    capture = _kernel(compiled, f"k_path_captureILb{spheres}ELb{instanced}E")
-    fused = _kernel(compiled, f"k_fusedILb{spheres}ELb{instanced}ELb0E")
+    capture = path_kernels.one(compiled, f"k_path_captureILb{spheres}ELb{instanced}E")
+    fused = path_kernels.one(compiled, f"k_fusedILb{spheres}ELb{instanced}ELb0E")
     assert not any(op.startswith("scratch_") or op.startswith("buffer_") for op in capture["ops"]), sorted(capture["ops"])
     assert sum(capture["loop"].values()) <= sum(fused["loop"].values()) + 4, (dict(capture["loop"]), dict(fused["loop"]))
     assert capture["meta"]["vgpr_count"] <= (168 if instanced else 128), capture["meta"]
@@ -70,9 +52,7 @@ def test_the_capture_kernel_keeps_k_fuseds_loop_and_registers(compiled, spheres,
 
 def test_hand_issued_loads_of_the_capture_kernels_are_not_touched_before_their_wait():
     """tools/audit_asm_loads.py on the new file: 0 hazards."""
-    sys.path.insert(0, str(ROOT / "tools"))
-    import audit_asm_loads
-    groups, bad = audit_asm_loads.audit(CSRC + CAPTURE[0] + ".hip", CAPTURE[1])
+    groups, bad = audit_asm_loads.audit(*path_kernels.source("fused_capture"))
     assert groups > 0 and bad == 0, (groups, bad)
 
 

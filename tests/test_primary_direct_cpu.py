@@ -12,7 +12,7 @@ none needs a GPU:
       k_path_idle's, instruction for instruction (opcodes and their split into dual-pipe, single-pipe, scalar and memory), 10240 B of LDS, at
       most 128 VGPRs, nothing spilled, no scratch, no flat_ instruction, no load hazard, and the record's three loads stand in the regeneration in
       front of the path-end code;
-  (c) the flag, the variant, the knob and the counter are where the text says, and there is no enumerator for the kernel.
+  (c) the flag, the variant, the knob and the counter are where the text says, and the kernel has its enumerator and its case of the launch entry.
 (That the other translation units' assembly equals the parent commit's cannot be read from one tree: profiles/r30_primary_direct.txt says how it
 was checked.)"""
 import re
@@ -28,6 +28,8 @@ from test_primary_window_cpu import _delta
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
+sys.path.insert(0, str(ROOT / "tools"))
+import audit_asm_loads, loop_stats, path_kernels          # noqa: E402
 f32 = np.float32
 MISS = pr.MISS
 
@@ -98,26 +100,15 @@ def test_a_tie_in_t_is_decided_by_the_record_that_won_it(hrt, oracle, monkeypatc
 # ---------------------------------------------------------------- (b) static ----------------------------------------------------------------
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
     tmp = tmp_path_factory.mktemp("primary_direct")
     out = {}
-    for key, stem, prefix in (("direct", "fused_direct", "_ZN3hrt13k_path_direct"), ("idle", "fused_idle", "_ZN3hrt11k_path_idle")):
-        asm = tmp / f"{stem}.s"
-        loops = dict(loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=asm))
-        assert len(loops) == 1, sorted(loops)
-        name, loop = next(iter(loops.items()))
-        text = asm.read_text()
-        body = re.search(r"^" + re.escape(name) + r":[^\n]*\n(.*?)s_endpgm", text, re.S | re.M).group(1).split("\n")
-        entry = [e for e in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:] if re.search(r"\.name:\s+(\S+)", e).group(1) == name]
-        assert len(entry) == 1
-        meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry[0], re.M)}
-        out[key] = {"text": text, "loop": [op for op, _ in loop_stats.instructions(loop)], "body": body, "meta": meta}
+    for key, stem in (("direct", "fused_direct"), ("idle", "fused_idle")):
+        k = path_kernels.one(path_kernels.compile_unit(stem, tmp / f"{stem}.s"))
+        out[key] = {"text": (tmp / f"{stem}.s").read_text(), "loop": [op for op, _ in loop_stats.instructions(k["lines"])], "body": k["body"], "meta": k["meta"]}
     return out
 
 
 def test_the_loop_is_k_path_idles(compiled):
-    import loop_stats
     from collections import Counter
     direct, idle = compiled["direct"]["loop"], compiled["idle"]["loop"]
     split = lambda ops: Counter(loop_stats.kind(op) for op in ops)
@@ -128,7 +119,6 @@ def test_the_loop_is_k_path_idles(compiled):
 
 
 def test_one_kernel_its_lds_registers_and_no_spill(compiled):
-    import loop_stats
     k = compiled["direct"]
     assert len(re.findall(r"^\s*\.amdhsa_kernel\s", k["text"], re.M)) == 1
     meta = k["meta"]
@@ -143,7 +133,6 @@ def test_one_kernel_its_lds_registers_and_no_spill(compiled):
 def test_the_records_loads_stand_at_the_top_of_the_regeneration(compiled):
     """in layout order: the regeneration's priority, then the record's loads (A whole, three words each of B and C), and only then the first
     store of a path's end -- and k_path_idle has no such loads"""
-    import loop_stats
     ins = [(op, l.strip()) for op, l in loop_stats.instructions(compiled["direct"]["body"])]
     prio = next(i for i, (op, l) in enumerate(ins) if l == "s_setprio 2")
     rec = [i for i, (op, _) in enumerate(ins) if op == "global_load_dwordx3"]
@@ -156,9 +145,7 @@ def test_the_records_loads_stand_at_the_top_of_the_regeneration(compiled):
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait():
-    sys.path.insert(0, str(ROOT / "tools"))
-    import audit_asm_loads
-    groups, bad = audit_asm_loads.audit(CSRC + "fused_direct.hip", "_ZN3hrt13k_path_direct")
+    groups, bad = audit_asm_loads.audit(*path_kernels.source("fused_direct"))
     assert groups > 0 and bad == 0, (groups, bad)
 
 
@@ -173,12 +160,19 @@ def test_the_flag_the_variant_the_knob_and_the_counter(hrt):
     flags = lambda text, name: (re.search(r"struct " + name + r" : (\S+) \{(.*?)\};", text, re.S).group(1),
                                 re.sub(r"\s+", " ", re.search(r"struct " + name + r" : (\S+) \{(.*?)\};", text, re.S).group(2)).strip())
     base_i, flags_i = flags((ROOT / CSRC / "fused_idle.hip").read_text(), "MaskIdleVariant")
-    base_d, flags_d = flags(common, "DirectVariant")
+    base_d, flags_d = flags(body, "DirectVariant")
+    assert "DirectVariant" not in common          # (a kernel's variant lives in the kernel's own unit)
     assert base_d == base_i and flags_d == flags_i.rstrip(";") + ", kDirect = true;", (flags_i, flags_d)
-    # no enumerator: the launch entry and its table (tests/test_path_launch_cpu.py) are as they were, and k_path_idle's launcher forwards
+    # an enumerator and a case of the one launch entry like every other kernel: k_path_idle's launcher launches k_path_idle, and no value of
+    # seed_primary stands for a kernel
     enum = (ROOT / CSRC / "device_types.h").read_text().split("enum class PathKernel {")[1].split("};")[0]
-    assert "Direct" not in re.sub(r"//.*", "", enum)
-    assert "if (a.seed_primary == 3) { launch_path_direct(a, scene, grid_blocks, s); return; }" in (ROOT / CSRC / "fused_idle.hip").read_text()
+    assert re.search(r"\bDirect\b", re.sub(r"//.*", "", enum))
+    assert "case PathKernel::Direct: launch_path_direct(a, scene, grid_blocks, s); break;" in (ROOT / CSRC / "fused.hip").read_text()
+    idle = (ROOT / CSRC / "fused_idle.hip").read_text()
+    assert "launch_path_direct" not in idle and "seed_primary" not in idle
+    for path in sorted((ROOT / CSRC).rglob("*")):
+        if path.is_file():
+            assert not re.search(r"seed_primary\s*==?\s*3", path.read_text(errors="replace")), path.name
     knobs = (ROOT / CSRC / "knobs.def").read_text()
     line = next(l for l in knobs.splitlines() if l.startswith('HRT_KNOB("HRT_PRIMARY_DIRECT"'))
     assert "ctx->primary_direct = std::atoi(e) != 0" in line
@@ -186,5 +180,4 @@ def test_the_flag_the_variant_the_knob_and_the_counter(hrt):
     assert "v >= 0 && v <= 2" in seed                                   # the environment's stays 0..2
     names = [f[0] for f in hrt.Stats._fields_]
     assert names.index("direct_launches") + 1 == names.index("mask_idle_launches")
-    for tool in ("kernel_table.py", "loop_stats.py", "audit_asm_loads.py"):
-        assert "_ZN3hrt13k_path_direct" in (ROOT / "tools" / tool).read_text(), tool
+    assert ("fused_direct", "_ZN3hrt13k_path_direct", "k_path_direct") in path_kernels.UNITS

@@ -32,6 +32,8 @@ from test_primary_window_cpu import _delta
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
+sys.path.insert(0, str(ROOT / "tools"))
+import audit_asm_loads, loop_stats, path_kernels          # noqa: E402
 f32, f64 = np.float32, np.float64
 MISS = 0xFFFFFFFF
 TMIN, TMAX = f32(1e-6), f32(1e16)
@@ -254,27 +256,12 @@ def test_a_tie_in_t_goes_to_the_lower_id_from_the_restart_as_from_the_root(hrt, 
 # ---------------------------------------------------------------- (d) static ----------------------------------------------------------------
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
     tmp = tmp_path_factory.mktemp("primary_restart")
     out = {}
-    for key, stem, prefix in (("restart", "fused_restart", "_ZN3hrt14k_path_restart"), ("one", "fused_one", "_ZN3hrt10k_path_one")):
-        asm = tmp / f"{stem}.s"
-        loops = dict(loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=asm))
-        assert len(loops) == 1, sorted(loops)
-        name, loop = next(iter(loops.items()))
-        text = asm.read_text()
-        body = re.search(r"^" + re.escape(name) + r":[^\n]*\n(.*?)s_endpgm", text, re.S | re.M).group(1).split("\n")
-        entry = [e for e in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:] if re.search(r"\.name:\s+(\S+)", e).group(1) == name]
-        assert len(entry) == 1
-        meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry[0], re.M)}
-        out[key] = {"text": text, "loop": loop, "body": body, "meta": meta}
+    for key, stem in (("restart", "fused_restart"), ("one", "fused_one")):
+        k = path_kernels.one(path_kernels.compile_unit(stem, tmp / f"{stem}.s"))
+        out[key] = {"text": (tmp / f"{stem}.s").read_text(), "loop": k["lines"], "body": k["body"], "meta": k["meta"]}
     return out
-
-
-def _ops(lines):
-    import loop_stats
-    return [op for op, _ in loop_stats.instructions(lines)]
 
 
 def test_one_kernel_its_lds_registers_and_no_spill(compiled):
@@ -285,13 +272,12 @@ def test_one_kernel_its_lds_registers_and_no_spill(compiled):
     assert meta["group_segment_fixed_size"] == 10240, meta
     assert meta["vgpr_count"] <= 128 and meta["vgpr_spill_count"] == 0 and meta["sgpr_spill_count"] == 0, meta
     assert meta.get("private_segment_fixed_size", 0) == 0, meta
-    ops = _ops(k["body"])
+    ops = loop_stats.opcodes(k["body"])
     assert not any(op.startswith("flat_") or op.startswith("scratch_") for op in ops)
 
 
 def test_the_loop_is_k_path_ones_plus_the_select(compiled):
-    import loop_stats
-    restart, one = _ops(compiled["restart"]["loop"]), _ops(compiled["one"]["loop"])
+    restart, one = loop_stats.opcodes(compiled["restart"]["loop"]), loop_stats.opcodes(compiled["one"]["loop"])
     print("loop: k_path_restart", len(restart), "k_path_one", len(one))
     assert len(restart) <= len(one) + 1, (len(restart), len(one))
     assert restart.count("v_cndmask_b32") <= one.count("v_cndmask_b32") + 1
@@ -301,9 +287,7 @@ def test_the_loop_is_k_path_ones_plus_the_select(compiled):
 
 
 def test_hand_issued_loads_are_not_touched_before_their_wait():
-    sys.path.insert(0, str(ROOT / "tools"))
-    import audit_asm_loads
-    groups, bad = audit_asm_loads.audit(CSRC + "fused_restart.hip", "_ZN3hrt14k_path_restart")
+    groups, bad = audit_asm_loads.audit(*path_kernels.source("fused_restart"))
     assert groups > 0 and bad == 0, (groups, bad)
 
 

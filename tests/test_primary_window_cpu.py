@@ -10,8 +10,8 @@ has proved that nothing lies before t.  Three parts, none needs a GPU:
 delta is read from the source, so the test follows the constant."""
 import ctypes as C
 import re
-import subprocess
 import sys
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
@@ -175,14 +175,9 @@ def test_the_window_culls_what_ends_before_it(window_cases):
 # ---------------------------------------------------------------- 3. static ----------------------------------------------------------------
 def _metadata(stem):
     sys.path.insert(0, str(ROOT / "tools"))
-    from audit_asm_loads import makefile_hipflags
-    flags = [f for f in makefile_hipflags() if f != "-fPIC"]
-    text = subprocess.check_output(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", "-o", "-", str(CSRC / f"{stem}.hip")], cwd=ROOT, stderr=subprocess.DEVNULL, text=True)
-    out = {}
-    for entry in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", entry).group(1)
-        out[name] = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry, re.M)}
-    return out
+    import path_kernels
+    with tempfile.TemporaryDirectory() as tmp:
+        return {name: k["meta"] for name, k in path_kernels.compile_unit(stem, Path(tmp) / f"{stem}.s").items()}
 
 
 def test_one_level_kernels_keep_sixteen_waves_of_lds():

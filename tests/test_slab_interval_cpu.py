@@ -19,32 +19,29 @@ import ray_cases as rc
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
+sys.path.insert(0, str(ROOT / "tools"))
+import loop_stats, path_kernels          # noqa: E402
 f32, f64 = np.float32, np.float64
 
 
 # ---------------------------------------------------------------- assembly pins ----------------------------------------------------------------
-def _compile(tmp, stem, prefix, tag):
-    """{kernel: {"lines": the first traversal loop, "text": the kernel's body}} and the whole assembly text"""
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
+def _compile(tmp, stem, tag):
+    """{kernel: {"lines": the first traversal loop, "text": the kernel's body, "meta": its metadata}} and the whole assembly text"""
     asm = tmp / f"{stem}_{tag}.s"
-    loops = dict(loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=asm))
-    text = asm.read_text()
-    bodies = {m.group(1): m.group(2) for m in re.finditer(r"^(" + prefix + r"\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)}
-    return {k: {"lines": loops.get(k, []), "text": v} for k, v in bodies.items()}, text
+    kernels = path_kernels.compile_unit(stem, asm)
+    return {name: {"lines": k["lines"], "text": "\n".join(k["body"]), "meta": k["meta"]} for name, k in kernels.items()}, asm.read_text()
 
 
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("slab_interval")
     out = {}
-    for stem, prefix in (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_queue", "_ZN3hrt13k_trace_queue"),
-                         ("kernels", "_ZN3hrt10k_traverse")):
-        out[stem] = _compile(tmp, stem, prefix, "default")
+    for stem in ("fused", "fused_blocks", "fused_queue", "kernels"):
+        out[stem] = _compile(tmp, stem, "default")
     saved = os.environ.get("EXTRA_HIPFLAGS")
     os.environ["EXTRA_HIPFLAGS"] = "-DHRT_SLAB_INTERVAL01=0"          # (the Makefile's HIPFLAGS end with it: tools/audit_asm_loads.py reads them through make)
     try:
-        out["kernels_form0"] = _compile(tmp, "kernels", "_ZN3hrt10k_traverse", "form0")
+        out["kernels_form0"] = _compile(tmp, "kernels", "form0")
     finally:
         if saved is None:
             del os.environ["EXTRA_HIPFLAGS"]
@@ -53,14 +50,7 @@ def compiled(tmp_path_factory):
     return out
 
 
-def _one(kernels, fragment):
-    found = [v for k, v in kernels.items() if fragment in k]
-    assert len(found) == 1, (fragment, sorted(kernels))
-    return found[0]
-
-
 def _counts(lines):
-    import loop_stats
     from collections import Counter
     cs, ops = Counter(), Counter()
     for op, _ in loop_stats.instructions(lines):
@@ -75,7 +65,7 @@ def _clamped_fmas(lines):
 
 @pytest.mark.parametrize("stem, fragment", [("fused", "k_fusedILb0ELb0ELb0E"), ("fused_blocks", "k_path_blocksILb0E")])
 def test_the_flagship_loops_carry_sixteen_clamped_fmas_and_are_no_larger_than_stated(compiled, stem, fragment):
-    k = _one(compiled[stem][0], fragment)
+    k = path_kernels.one(compiled[stem][0], fragment)
     cs, ops = _counts(k["lines"])
     print(fragment, dict(cs))
     assert len(_clamped_fmas(k["lines"])) == 16
@@ -86,10 +76,7 @@ def test_the_flagship_loops_carry_sixteen_clamped_fmas_and_are_no_larger_than_st
 
 
 def test_k_path_blocks_spills_at_most_six_registers(compiled):
-    text = compiled["fused_blocks"][1]
-    entry = [e for e in text.split("amdhsa.kernels:")[1].split("\n  - .agpr_count:")[1:] if "k_path_blocksILb0E" in e]
-    assert len(entry) == 1
-    meta = {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)\s*$", entry[0], re.M)}
+    meta = path_kernels.one(compiled["fused_blocks"][0], "k_path_blocksILb0E")["meta"]
     assert meta["vgpr_spill_count"] <= 6 and meta["sgpr_spill_count"] == 0 and meta["vgpr_count"] <= 128, meta
 
 

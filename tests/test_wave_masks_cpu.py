@@ -12,6 +12,8 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = "nvidia-optix-ray-tracer_amd/csrc/"
+sys.path.insert(0, str(ROOT / "tools"))
+import loop_stats, path_kernels          # noqa: E402
 
 # kernel -> (instructions, scalar instructions, modelled cycles) of the first copy of its loop: what the build shows.  Before the flags
 # were masks: 432 / 89 / 1251, 432 / 89 / 1251 and 433 / 90 / 1254.
@@ -21,22 +23,19 @@ BUDGET = {"k_fusedILb0ELb0ELb0E": (408, 74, 1185), "k_path_blocksILb0E": (408, 7
 @pytest.fixture(scope="module")
 def loops(tmp_path_factory):
     """{fragment of BUDGET: lines of the kernel's first loop, in layout order}"""
-    sys.path.insert(0, str(ROOT / "tools"))
-    import loop_stats
     tmp = tmp_path_factory.mktemp("wave_masks")
     out = {}
-    for stem, prefix in (("fused", "_ZN3hrt7k_fused"), ("fused_blocks", "_ZN3hrt13k_path_blocks"), ("fused_queue", "_ZN3hrt13k_trace_queue")):
-        for name, lines in loop_stats.loop_bodies(CSRC + f"{stem}.hip", prefix, asm=tmp / f"{stem}.s"):
+    for stem in ("fused", "fused_blocks", "fused_queue"):
+        for name, k in path_kernels.compile_unit(stem, tmp / f"{stem}.s").items():
             for fragment in BUDGET:
                 if fragment in name:
-                    out[fragment] = lines
+                    out[fragment] = k["lines"]
     assert sorted(out) == sorted(BUDGET)
     return out
 
 
 @pytest.mark.parametrize("fragment", sorted(BUDGET))
 def test_the_loop_stays_within_what_this_build_shows(loops, fragment):
-    import loop_stats
     kinds = {}
     for op, _ in loop_stats.instructions(loops[fragment]):
         kinds[loop_stats.kind(op)] = kinds.get(loop_stats.kind(op), 0) + 1
@@ -57,7 +56,6 @@ def test_no_mask_save_behind_the_bookkeeping_sequence(loops, fragment):
 @pytest.mark.parametrize("fragment", sorted(BUDGET))
 def test_no_mask_goes_through_a_vector_register_and_back(loops, fragment):
     """No v_cndmask_b32 vN, 0, 1, <mask> whose vN a v_cmp_ne reads before it is written again"""
-    import loop_stats
     ins = [l.strip() for _, l in loop_stats.instructions(loops[fragment])]
     found = []
     for i, l in enumerate(ins):

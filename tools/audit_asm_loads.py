@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Audit of the hand-issued loads of the traversal kernels (k_traverse in kernels.hip, k_fused in fused.hip, k_path_blocks in fused_blocks.hip, k_path_one in fused_one.hip, k_path_restart in fused_restart.hip, k_path_idle in fused_idle.hip, k_path_direct in fused_direct.hip, k_path_capture in fused_capture.hip, k_path_counts in fused_counts.hip, k_trace_queue in fused_queue.hip): between an asm
+"""Audit of the hand-issued loads of the traversal kernels (every unit of tools/path_kernels.py: k_traverse, k_fused, the k_path_* kernels,
+k_trace_queue): between an asm
 block that issues global_load_dwordx4 into VGPRs and the asm wait that retires them, the compiler must not read, copy or spill
-those registers -- it does not know the loads are in flight, and the hardware does not interlock.  Compiles both files to
+those registers -- it does not know the loads are in flight, and the hardware does not interlock.  Compiles every unit to
 assembly with the Makefile's own flags (`make -pn`), then prints, per kernel instantiation, the instructions that touch the
 destinations of a group of loads before the wait that covers it (expected: none).  The scan follows the ORDER OF EXECUTION from
 the loads -- across s_branch, down both sides of every s_cbranch -- to the first wait that retires them on each path (for the
@@ -93,10 +94,10 @@ def audit(source, kernel_prefix, verbose=False):
 if __name__ == "__main__":
     v = "-v" in sys.argv
     total_groups = total_bad = 0
-    for src, prefix in (("nvidia-optix-ray-tracer_amd/csrc/kernels.hip", "_ZN3hrt10k_traverse"), ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"), ("nvidia-optix-ray-tracer_amd/csrc/fused_blocks.hip", "_ZN3hrt13k_path_blocks"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_one.hip", "_ZN3hrt10k_path_one"), ("nvidia-optix-ray-tracer_amd/csrc/fused_restart.hip", "_ZN3hrt14k_path_restart"), ("nvidia-optix-ray-tracer_amd/csrc/fused_idle.hip", "_ZN3hrt11k_path_idle"), ("nvidia-optix-ray-tracer_amd/csrc/fused_direct.hip", "_ZN3hrt13k_path_direct"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_capture.hip", "_ZN3hrt14k_path_capture"), ("nvidia-optix-ray-tracer_amd/csrc/fused_counts.hip", "_ZN3hrt13k_path_counts"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_queue.hip", "_ZN3hrt13k_trace_queue")):
+    sys.path.insert(0, str(ROOT / "tools"))
+    import path_kernels
+    for stem, _, _ in path_kernels.UNITS:
+        src, prefix = path_kernels.source(stem)
         g, b = audit(src, prefix, v)
         print(f"{src}: {g} groups of in-flight loads checked, {b} hazardous instructions")
         total_groups += g; total_bad += b

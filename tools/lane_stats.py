@@ -6,7 +6,8 @@ times, and HRT_SAMPLE_BLOCK=4 with 16 for a block render of few samples).  Needs
 `tools/lane_stats.py spp 256 primary`, on `make stats EXTRA_HIPFLAGS=-DHRT_LANE_STATS_PRIMARY` through HRT_LIB: also what a pixel's repeat
 primary rays cost -- how many there are, how many start at a node or are decided in the regeneration, the iterations they are alive and wait."""
 import importlib, sys
-sys.path.insert(0, str(__import__("pathlib").Path(__file__).resolve().parent.parent))
+sys.path[:0] = [str(__import__("pathlib").Path(__file__).resolve().parent.parent), str(__import__("pathlib").Path(__file__).resolve().parent)]
+import path_kernels
 hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
 spp = 16
 if len(sys.argv) > 1 and sys.argv[1] == "particles":       # tools/lane_stats.py particles N: the reference's kind of scene, 1200x800
@@ -32,7 +33,7 @@ if "primary" in sys.argv:
     t = s.tail
     prim_rays, quick, q_alive, q_wait, direct = t[0], t[1], t[3], t[4], t[5]
     all_primary = prim_rays + direct
-    print("kernel", "k_path_direct" if s.direct_launches else "k_path_idle" if s.mask_idle_launches else "another")
+    print("kernel", path_kernels.kernel_ran(s))
     print("primary rays", all_primary, "walked from the root", prim_rays - quick, "started at a node other than the root", quick, "decided in the regeneration", direct)
     print("h = share of primary rays with a record %.4f" % ((quick + direct) / max(all_primary, 1)))
     print("iterations the rays started at a node were alive", q_alive, "(%.2f each)  waited for their regeneration" % (q_alive / max(quick, 1)), q_wait, "(%.2f each)" % (q_wait / max(quick, 1)))

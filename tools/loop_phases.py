@@ -14,6 +14,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 from loop_stats import instructions, kind, loop_bodies, model_cycles
+import path_kernels
 
 PHASES = ("G", "C", "A", "B", "exit")
 
@@ -49,7 +50,7 @@ if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if a != "-v"]
     want = args[0] if args else "ILb0ELb0ELb0E"
     # (k_path_one, fused_one.hip, is no template: ask for it by name -- tools/loop_phases.py k_path_one)
-    source = ("nvidia-optix-ray-tracer_amd/csrc/fused_one.hip", "_ZN3hrt10k_path_one") if "k_path_one" in want else ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused")
+    source = path_kernels.source("fused_one" if "k_path_one" in want else "fused")
     for name, lines in loop_bodies(*source):
         if want not in name:
             continue

@@ -30,6 +30,11 @@ def instructions(lines):
         yield re.sub(r"_(e32|e64|sdwa|dpp)$", "", t[0]), l
 
 
+def opcodes(lines):
+    """the opcodes of the instructions among `lines`"""
+    return [op for op, _ in instructions(lines)]
+
+
 def loop_bodies(source, prefix, asm=None):
     """Compiles `source` to assembly at `asm` (default: hrt_loops_<stem>.s in the temporary directory) and yields (kernel, lines of
     its traversal loop in layout order).  The loop is the depth-2 loop whose header is the last one before the first copy's node loads;
@@ -82,11 +87,9 @@ def model_cycles(cs):
 
 if __name__ == "__main__":
     want = sys.argv[1:]
-    for src, prefix in (("nvidia-optix-ray-tracer_amd/csrc/kernels.hip", "_ZN3hrt10k_traverse"), ("nvidia-optix-ray-tracer_amd/csrc/fused.hip", "_ZN3hrt7k_fused"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_blocks.hip", "_ZN3hrt13k_path_blocks"), ("nvidia-optix-ray-tracer_amd/csrc/fused_one.hip", "_ZN3hrt10k_path_one"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_restart.hip", "_ZN3hrt14k_path_restart"), ("nvidia-optix-ray-tracer_amd/csrc/fused_idle.hip", "_ZN3hrt11k_path_idle"), ("nvidia-optix-ray-tracer_amd/csrc/fused_direct.hip", "_ZN3hrt13k_path_direct"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_capture.hip", "_ZN3hrt14k_path_capture"),
-                        ("nvidia-optix-ray-tracer_amd/csrc/fused_counts.hip", "_ZN3hrt13k_path_counts")):
+    import path_kernels          # (which imports this module: the list of units is needed here only)
+    for stem, _, _ in path_kernels.UNITS[:-1]:          # (k_trace_queue's loop is k_fused's)
+        src, prefix = path_kernels.source(stem)
         for name, cs, ops in loops(src, prefix):
             if want and not any(w in name for w in want):
                 continue

@@ -7,7 +7,8 @@ histogram of 16 MHz bins.  The production kernels have no stamp.
 Renders the configuration of bench.py back to back for that long, then reads the waves of as many launches again.  Prints the median
 over waves, the 5th and 95th percentile (to the bin: +-8 MHz), the mean (sum of cycles over sum of ticks) and which kernel ran."""
 import importlib, json, sys, time
-sys.path.insert(0, str(__import__("pathlib").Path(__file__).resolve().parent.parent))
+sys.path[:0] = [str(__import__("pathlib").Path(__file__).resolve().parent.parent), str(__import__("pathlib").Path(__file__).resolve().parent)]
+import path_kernels
 hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
 LOW, STEP, BINS = 1600, 16, 56          # trav_common.h: kWaveClockLow, kWaveClockStep, kWaveClockBins
 
@@ -45,8 +46,7 @@ def main():
     waves, cycles, ticks, hist = wc[0], wc[1], wc[2], wc[4:4 + BINS]
     if waves == 0:
         sys.exit("HrtStats.wave_clock is empty: load the instrumented build (make stats; HRT_LIB=.../libhrt_stats.so)")
-    kernel = "k_path_idle" if s.mask_idle_launches else "k_path_restart" if s.restart_launches else "k_path_one" if s.one_group_launches else "k_path_blocks" if s.sample_block_launches else "k_fused"
-    print(json.dumps({"config": config, "kernel": kernel, "launches": launches, "ms_per_launch": round(dt / launches * 1e3, 3), "waves": waves,
+    print(json.dumps({"config": config, "kernel": path_kernels.kernel_ran(s), "launches": launches, "ms_per_launch": round(dt / launches * 1e3, 3), "waves": waves,
                       "mhz_median": round(percentile(hist, 0.5), 1), "mhz_p05": round(percentile(hist, 0.05), 1), "mhz_p95": round(percentile(hist, 0.95), 1),
                       "mhz_mean": round(cycles / ticks * 100.0, 1), "below_range": hist[0], "above_range": hist[-1], "mean_wave_ms": round(ticks / waves / 1e5, 3),
                       "rays": int(s.rays)}))
