@@ -53,7 +53,7 @@ $(LIBDIR)/pose.o: $(CSRC)/pose.hip $(CSRC)/device_types.h $(CSRC)/cr_trig.h $(CS
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-API_DEPS := $(CSRC)/knobs.def $(CSRC)/build.h $(CSRC)/hrt_internal.hpp $(CSRC)/device_types.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h include/hrt.h include/hrt_params.h
+API_DEPS := $(CSRC)/knobs.def $(CSRC)/build.h $(CSRC)/hrt_internal.hpp $(CSRC)/device_types.h $(CSRC)/path_plan.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h include/hrt.h include/hrt_params.h
 
 $(LIBDIR)/hrt_accel.o: $(CSRC)/hrt_accel.cpp $(API_DEPS)
 	@mkdir -p $(LIBDIR)

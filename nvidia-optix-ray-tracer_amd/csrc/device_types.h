@@ -95,7 +95,7 @@ struct PathArgs {
 static_assert(sizeof(PathArgs) == 232 && offsetof(PathArgs, states) == 112 && offsetof(PathArgs, primary_cache) == 192 && offsetof(PathArgs, block_progress) == 224,
               "block_min and block_taper_end sit in what was padding: nothing else has moved");
 
-// The block schedule in closed form, for the kernel (path_lane.h) and the host (hrt_api.cpp: sample_schedule) alike.
+// The block schedule in closed form, for the kernel (path_lane.h) and the host (path_plan.h: sample_schedule) alike.
 // block_first: the first sample of pass b.
 __host__ __device__ inline uint32_t block_first(uint32_t k_big, uint32_t k_min, uint32_t taper_end, bool tapered, uint32_t pass) {
     if (!tapered) return pass * k_big;
@@ -322,6 +322,7 @@ constexpr uint32_t kTraversalStackEntries = 64;   // per-lane stack of round 1's
 // ---- the path kernels: one launch renders every sample of every pixel of a tile (or traces callers' rays, PathArgs::trace_rays) ----
 // Every kernel is an enumerator; which one a launch gets (choose_path_launch), what it takes for granted (path_launch_admitted) and the one
 // entry that launches it (launch_path_kernel) follow, the first two as plain host code that tests/test_path_launch_cpu.py runs without a device.
+// What a render decides before that choice -- grid, cache, probe, capture, the sample-block gate, the schedule -- is path_plan.h's, host code likewise.
 enum class PathKernel {
     Fused,              // k_fused (fused.hip): one-level trees; with PathArgs::primary_cache, its primary-reuse instantiation
     FusedInstanced,     // k_fused<.., INSTANCED> (fused.hip): two-level trees (transform nodes, bvh8.h)
@@ -348,11 +349,19 @@ inline int path_ladder_rung(PathKernel kernel) {
     }
 }
 // What each kernel takes for granted, in one place: its regeneration does not look at the fields it is compiled without, so a launch that
-// contradicts the kernel it names is refused instead of rendering something else.  Plain host code: no device, nothing launched.
-inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const PathScene &scene) {
+// contradicts the kernel it names is refused instead of rendering something else -- and a launch in blocks that could wait for ever is
+// refused instead of taking the GPU away.  Plain host code: no device, nothing launched.
+inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks) {
     const PathArgs &p = a.path;
-    // a render in sample blocks: a one-level tree, no callers' rays, no cost probe, no slice order; ... of triangles over exactly one instance, whose table entries exist
-    const bool in_blocks = scene.one_level && p.sample_block != 0u && p.trace_rays == nullptr && p.slice_cost == nullptr && p.slice_order == nullptr;
+    auto pow2 = [](uint32_t v) { return v != 0u && (v & (v - 1u)) == 0u; };
+    // the schedule is one of the two kinds PathArgs names, not a mixture: uniform blocks, or a taper of powers of two whose halvings end at or behind the first block
+    const bool uniform = p.block_magic != 0u && p.block_min == 0u && p.block_taper_end == 0u;
+    const bool tapered = p.block_magic == 0u && p.block_min != 0u && p.block_taper_end >= p.sample_block && pow2(p.sample_block) && pow2(p.block_min);
+    // a render in sample blocks: a one-level tree, no callers' rays, no cost probe, no slice order; the hand-over's memory -- the slices' progress words, and items
+    // to hand out; every slice counter some wave's home (fewer waves than counters: a held item's predecessor can sit behind a counter nobody visits, fused_body.h);
+    // ... of triangles over exactly one instance, whose table entries exist
+    const bool in_blocks = scene.one_level && p.sample_block != 0u && p.trace_rays == nullptr && p.slice_cost == nullptr && p.slice_order == nullptr &&
+                           grid_blocks >= kFetchShards && p.block_progress != nullptr && p.block_items != 0u && (uniform || tapered);
     const bool one_group = in_blocks && scene.n_instances == 1u && !scene.has_spheres && p.hitgroups != nullptr && p.inst_program != nullptr;
     // the ladder: one hit group; from the restart on the table, and the window its rays start in (k_path_idle and k_path_direct: the same launch, the kernel alone differs)
     if (const int rung = path_ladder_rung(kernel)) return one_group && (rung < 2 || (scene.leaf_parent != nullptr && a.seed_primary >= 2));
@@ -368,19 +377,19 @@ inline bool path_launch_admitted(PathKernel kernel, const TraverseArgs &a, const
         default: return false;
     }
 }
-// The kernel of ONE launch of a render (hrt_api.cpp: render_fused), from what is decided by then: the tree's kernel (Fused, FusedInstanced or
+// The kernel of ONE launch of a render (path_plan.h: plan_fused_launch), from what is decided by then: the tree's kernel (Fused, FusedInstanced or
 // Round1), whether the render captures primary hits -- of a render cut into several launches the first one does, and never one in blocks: the
 // primary ray of a pixel's first sample is every sample's --, whether this launch goes in sample blocks, and how many samples earlier launches
-// have taken.  A launch in blocks of a scene with ONE hit group -- a one-level tree of triangles over exactly one instance, any single-mesh
+// have taken; has_table: the tree has its leaf_parent table, or will by the time the launch runs (it has records and nodes).  A launch in blocks of a scene with ONE hit group -- a one-level tree of triangles over exactly one instance, any single-mesh
 // render -- climbs the ladder as far as the knobs let it: k_path_one (HRT_ONE_GROUP=0: k_path_blocks like everything else); where its repeat
 // primary rays get their window (HRT_SEED_PRIMARY=2) and the tree has its leaf_parent table, k_path_restart (HRT_PRIMARY_RESTART=0: k_path_one);
 // k_path_idle (HRT_MASK_IDLE); k_path_direct (HRT_PRIMARY_DIRECT).  Decided per launch, from the tree that is launched: an update that adds an
 // instance sends the next launch back to k_path_blocks.  Plain host code like the rule above, which admits whatever this returns.
 struct PathKnobs { bool one_group, primary_restart, mask_idle, primary_direct; };
-inline PathKernel choose_path_launch(PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary, const PathKnobs &knobs, const PathScene &scene) {
+inline PathKernel choose_path_launch(PathKernel tree_kernel, bool capture, bool blocks, uint32_t done_spp, int seed_primary, const PathKnobs &knobs, const PathScene &scene, bool has_table) {
     if (!blocks) return capture && done_spp == 0u ? PathKernel::Capture : tree_kernel;
     if (!(knobs.one_group && scene.one_level && scene.n_instances == 1u && !scene.has_spheres)) return PathKernel::Blocks;
-    if (!(knobs.primary_restart && seed_primary == 2 && scene.leaf_parent != nullptr)) return PathKernel::OneGroup;      // (a tree without records has no table)
+    if (!(knobs.primary_restart && seed_primary == 2 && has_table)) return PathKernel::OneGroup;      // (a tree without records has no table)
     return !knobs.mask_idle ? PathKernel::Restart : knobs.primary_direct ? PathKernel::Direct : PathKernel::MaskIdle;
 }
 // The one launch entry of the path kernels (fused.hip).  false: refused (path_launch_admitted), nothing launched.

@@ -45,7 +45,7 @@ static void launch_fused_as(const TraverseArgs &a, bool has_spheres, uint32_t gr
 // The one way a path kernel is launched: the launch is held to what the kernel the caller names takes for granted, and that kernel's own translation unit
 // launches it.  Every kernel has its enumerator and its case: no launcher forwards to another kernel, and no argument doubles as a selector.
 bool launch_path_kernel(PathKernel kernel, const TraverseArgs &a, const PathScene &scene, uint32_t grid_blocks, hipStream_t s) {
-    if (!path_launch_admitted(kernel, a, scene)) return false;
+    if (!path_launch_admitted(kernel, a, scene, grid_blocks)) return false;
     switch (kernel) {
         case PathKernel::Fused: launch_fused_as<false>(a, scene.has_spheres, grid_blocks, s); break;
         case PathKernel::FusedInstanced: launch_fused_as<true>(a, scene.has_spheres, grid_blocks, s); break;      // (transform nodes over shared BLASes)

@@ -3,6 +3,7 @@
 // There is deliberately no CPU fallback anywhere in this file: every compute path ends in a
 // HIP kernel launch, and context creation fails when no gfx950 device is present.
 #include "hrt_internal.hpp"
+#include "path_plan.h"
 
 namespace hrt {
 
@@ -66,34 +67,25 @@ std::vector<uint32_t> make_jump_tables() {
     return out;
 }
 
+// Device arrays that share one capacity grow on demand: all freed and the capacity cleared before any is allocated anew, so that a failed
+// hipMalloc leaves a consistent context (no dangling pointer, no capacity that promises memory).
+int grow_device_arrays(HrtContext *ctx, std::initializer_list<DeviceArray> arrays, uint32_t &capacity, uint32_t need) {
+    if (need <= capacity) return HRT_OK;
+    for (const DeviceArray &a : arrays) { if (*a.p) (void)hipFree(*a.p); *a.p = nullptr; }
+    capacity = 0;
+    for (const DeviceArray &a : arrays) HIP_TRY(ctx, hipMalloc(a.p, a.elem * (size_t)need));
+    capacity = need;
+    return HRT_OK;
+}
+
 int ensure_workspace(HrtContext *ctx, uint32_t n, uint32_t height) {
     Workspace &w = ctx->ws;
-    if (n > w.capacity) {
-        for (SampleSet &st : w.set) {
-            void *ptrs[] = {st.rays[0], st.rays[1], st.hit_tuvp, st.hit_inst, st.bin_items, st.chain, st.result};
-            for (void *p : ptrs) if (p) (void)hipFree(p);
-            st = SampleSet{{nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr, st.stages};
-        }
-        if (w.accum) (void)hipFree(w.accum);
-        w.accum = nullptr; w.capacity = 0;
-        for (SampleSet &st : w.set) {
-            HIP_TRY(ctx, hipMalloc((void **)&st.rays[0], sizeof(RayRec) * (size_t)n));
-            HIP_TRY(ctx, hipMalloc((void **)&st.rays[1], sizeof(RayRec) * (size_t)n));
-            HIP_TRY(ctx, hipMalloc((void **)&st.hit_tuvp, sizeof(float4) * (size_t)n));
-            HIP_TRY(ctx, hipMalloc((void **)&st.hit_inst, sizeof(uint32_t) * (size_t)n));
-            HIP_TRY(ctx, hipMalloc((void **)&st.bin_items, sizeof(uint32_t) * (size_t)n * kNumBins));
-            HIP_TRY(ctx, hipMalloc((void **)&st.chain, sizeof(uint32_t) * 4 * (size_t)n));
-            HIP_TRY(ctx, hipMalloc((void **)&st.result, sizeof(float4) * (size_t)n));
-        }
-        HIP_TRY(ctx, hipMalloc((void **)&w.accum, sizeof(float4) * (size_t)n));
-        w.capacity = n;
-    }
-    if (height > w.rows_capacity) {
-        if (w.rows) (void)hipFree(w.rows);
-        w.rows_capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&w.rows, sizeof(uint32_t) * (size_t)height));
-        w.rows_capacity = height;
-    }
+    SampleSet &s0 = w.set[0], &s1 = w.set[1];
+    int rc = grow_device_arrays(ctx, {s0.rays[0], s0.rays[1], s0.hit_tuvp, s0.hit_inst, {s0.bin_items, sizeof(uint32_t) * kNumBins}, {s0.chain, sizeof(uint32_t) * 4}, s0.result,
+                                      s1.rays[0], s1.rays[1], s1.hit_tuvp, s1.hit_inst, {s1.bin_items, sizeof(uint32_t) * kNumBins}, {s1.chain, sizeof(uint32_t) * 4}, s1.result,
+                                      w.accum}, w.capacity, n);
+    if (rc == HRT_OK) rc = grow_device_arrays(ctx, {w.rows}, w.rows_capacity, height);
+    if (rc != HRT_OK) return rc;
     for (SampleSet &st : w.set)
         if (!st.stages) { HIP_TRY(ctx, hipMalloc((void **)&st.stages, sizeof(StageCounters) * (kRayTraceDepth + 1) * kMaxSubTiles)); ctx->fused_counters_clean = false; }
     return HRT_OK;
@@ -268,14 +260,11 @@ static TraverseArgs traverse_args(const HrtContext *ctx, const Tlas &t, float tm
     ta.tail_split = t.two_level ? 0 : ctx->tail_split;      // (the pieces of a split ray would have to carry the instance they are in)
     return ta;
 }
-// The path kernel of a tree: k_fused, its instanced form for two-level trees, or -- for a tree outside k_fused's limits -- round 1's
-// fused kernel, counted in fused_fallback_launches.  blocks_per_cu: one-wave workgroups per CU at most.
-struct PathKernelChoice { PathKernel kernel; uint32_t blocks_per_cu; };
+// The path kernel of a tree (path_plan.h: tree_path_kernel); a launch on round 1's kernel is counted in fused_fallback_launches.
 static PathKernelChoice choose_path_kernel(HrtContext *ctx, const Tlas &t) {
-    const uint32_t knob = (uint32_t)ctx->fused_blocks_per_cu;
-    if (!fits_fused_kernel(ctx, t)) { ctx->fused_fallback_launches++; return {PathKernel::Round1, knob}; }
-    if (t.two_level) return {PathKernel::FusedInstanced, std::min<uint32_t>(knob, (uint32_t)kFusedInstancedBlocksPerCu)};
-    return {PathKernel::Fused, std::min<uint32_t>(knob, (uint32_t)kFusedBlocksPerCu)};
+    const PathKernelChoice pk = tree_path_kernel(fits_fused_kernel(ctx, t), t.two_level, ctx->fused_blocks_per_cu);
+    if (pk.kernel == PathKernel::Round1) ctx->fused_fallback_launches++;
+    return pk;
 }
 static PathScene path_scene(const Tlas &t) { return {!t.two_level, t.n_instances, t.has_spheres, t.dev.d_leaf_parent}; }
 // A launch counts for its kernel and for every kernel that one is built on (device_types.h: path_ladder_rung).
@@ -302,13 +291,8 @@ int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s) {
         prog[i] = program;
         ctx->program_present[program] = true;
     }
-    if (n > ctx->table_capacity) {
-        if (ctx->d_hitgroups) { (void)hipFree(ctx->d_hitgroups); (void)hipFree(ctx->d_inst_program); }
-        ctx->table_capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_hitgroups, sizeof(HitGroup) * n));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_inst_program, sizeof(uint32_t) * n));
-        ctx->table_capacity = n;
-    }
+    const int rc = grow_device_arrays(ctx, {ctx->d_hitgroups, ctx->d_inst_program}, ctx->table_capacity, n);
+    if (rc != HRT_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_hitgroups, hg.data(), sizeof(HitGroup) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_inst_program, prog.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -368,35 +352,6 @@ struct LaunchFrame {
     hipStream_t s;
 };
 
-// ---- sample blocks: the schedule of one path-kernel launch (device_types.h: PathArgs, block_first, block_ends) ----
-struct SampleSchedule { uint32_t k_big = 0, k_min = 0, taper_end = 0; bool tapered = false; uint32_t passes = 0; };
-static uint32_t schedule_first(const SampleSchedule &sc, uint32_t pass) { return block_first(sc.k_big, sc.k_min, sc.taper_end, sc.tapered, pass); }
-// passes: the first pass that would start at or behind the launch's last sample (block_first grows with the pass, by 1 at least)
-static void count_passes(SampleSchedule &sc, uint32_t spp) {
-    uint32_t lo = 0, hi = spp;
-    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2u; if (schedule_first(sc, mid) >= spp) hi = mid; else lo = mid + 1u; }
-    sc.passes = lo;
-}
-static SampleSchedule uniform_schedule(uint32_t spp, uint32_t k) {
-    SampleSchedule sc; sc.k_big = sc.k_min = k; sc.passes = (uint32_t)(((uint64_t)spp + k - 1u) / k); return sc;
-}
-// The tapered schedule of a launch of spp samples: blocks of K_big = `big` (no more than the launch has samples) up to T, then the sizes
-// K_big / 2, K_big / 4, ... K_min, K_min, which fill the window [T, T + K_big), and K_min behind it.  T + K_big is the last multiple of
-// K_big the launch reaches: the halvings are its last whole window, what is left behind them (less than K_big samples) goes in blocks
-// of K_min, and the launch's last block ends with its samples, short if need be -- every launch ends on K_min, with K_big / K_min - 1
-// more hand-overs at the most than it takes to get there.  Powers of two that never grow, so every boundary is a multiple of the block
-// that ends there.  256 samples, 64 : 8 -- 64, 64, 64, 32, 16, 8, 8.  (32-bit arithmetic: for launches of spp x big below 2^31, taper_fits.)
-static bool taper_fits(uint32_t spp, uint32_t big) { return (uint64_t)spp * big < (1ull << 31); }
-static SampleSchedule sample_schedule(uint32_t spp, uint32_t big, uint32_t min) {
-    SampleSchedule sc; sc.tapered = true;
-    sc.k_big = big; while (sc.k_big > 1u && sc.k_big > spp) sc.k_big >>= 1;
-    sc.k_min = std::min(min, sc.k_big);
-    sc.taper_end = spp / sc.k_big * sc.k_big;
-    count_passes(sc, spp);
-    return sc;
-}
-
-
 // ---- fused path mode: ONE launch, every lane owns a pixel and runs all its samples (generate, traverse, shade, accumulate in place).
 //      No stage barriers.  The default (HRT_FUSED=1); trees outside k_fused's limits take round 1's path kernel. ----
 // What every launch of a path kernel over a tile's pixels starts from (render_fused, hrt_render_accumulate): the tree, the regeneration's
@@ -419,82 +374,83 @@ static TraverseArgs fused_render_args(const LaunchFrame &f) {
     pa.rays_closest = &ctx->d_stats->rays_closest; pa.rays_any = &ctx->d_stats->rays_any;
     return ta;
 }
-// ... and the grid of such a launch: one-wave workgroups, blocks_per_cu of them per CU at most (render_fused: why fewer on a small tile)
-static uint32_t fused_render_grid(const HrtContext *ctx, uint32_t blocks_per_cu, uint32_t n) {
-    if (ctx->traverse_blocks_auto) {
-        const uint32_t fit = (uint32_t)((10ull * n + 14ull * 64ull * (uint64_t)ctx->n_cu - 1ull) / (14ull * 64ull * (uint64_t)ctx->n_cu));
-        blocks_per_cu = std::min(blocks_per_cu, std::max(fit, 4u));
-    }
-    return std::min<uint32_t>((uint32_t)ctx->n_cu * blocks_per_cu, (n + 63u) / 64u);
+// ... and what the plan of such a render reads (path_plan.h), by value
+static RenderPlanInput plan_input(const LaunchFrame &f) {
+    const HrtContext *ctx = f.ctx; const Tlas &t = *f.t;
+    RenderPlanInput in{};
+    in.n_cu = ctx->n_cu;
+    in.fits_fused = fits_fused_kernel(ctx, t); in.two_level = t.two_level; in.n_instances = t.n_instances; in.has_spheres = t.has_spheres;
+    in.has_records = t.n_prims != 0u && t.n_nodes != 0u;      // (what ensure_leaf_parent makes a table of)
+    in.n = f.n; in.full_frame = (uint64_t)f.n == (uint64_t)f.rg->width * f.rg->height; in.spp = f.spp;      // (the tile's rows are distinct: every row of the frame)
+    in.reuse_primary = (ctx->flags & HRT_CTX_REUSE_PRIMARY) != 0u || ctx->reuse_primary;
+    in.capture_primary = (ctx->flags & HRT_CTX_CAPTURE_PRIMARY) != 0u || ctx->capture_primary;
+    in.fused_blocks_per_cu = ctx->fused_blocks_per_cu; in.traverse_blocks_auto = ctx->traverse_blocks_auto; in.fused_fetch_chunk = ctx->fused_fetch_chunk;
+    in.fused_lpt = ctx->fused_lpt; in.sample_block = ctx->sample_block; in.taper_big = ctx->taper_big; in.taper_min = ctx->taper_min; in.taper_forced = ctx->taper_forced;
+    in.fused_max_spp = ctx->fused_max_spp; in.seed_primary = ctx->seed_primary;
+    in.knobs = PathKnobs{ctx->one_group, ctx->primary_restart, ctx->mask_idle, ctx->primary_direct};
+    return in;
 }
+// The slice counters' protocol of those launches: zero on entry -- left so by the previous launch's finalize kernel, or set here -- ...
+static int enter_slice_counters(HrtContext *ctx, hipStream_t s) {
+    if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(ctx->ws.set[0].stages, 0, sizeof(StageCounters), s));
+    ctx->fused_counters_clean = false;
+    return HRT_OK;
+}
+extern "C++" {
+// What FinalizeArgs and FinalizeCountsArgs share: the tile's rows, its pixels, the frame's width, the samples, the four output buffers.
+template <class Args>
+static void fill_finalize(Args &fa, const LaunchFrame &f) {
+    const HrtRayGenParams *rg = f.rg;
+    fa.rows = f.ctx->ws.rows; fa.n_tile_pixels = f.n; fa.width = rg->width; fa.spp = f.spp;
+    fa.color = reinterpret_cast<float4 *>(rg->colorBuffer); fa.albedo = reinterpret_cast<float4 *>(rg->albedoBuffer);
+    fa.normal = reinterpret_cast<float4 *>(rg->normalBuffer); fa.linear = f.ctx->d_linear;
+}
+// ... and zeroed again by the frame's finalize kernel (launch_finalize, launch_finalize_counts) for whichever launch comes next, where that
+// kernel has a thread per counter word; a smaller tile leaves them to the next entry.
+template <class Args, class Launch>
+static int finalize_and_reset_counters(const LaunchFrame &f, Args &fa, Launch launch) {
+    HrtContext *ctx = f.ctx;
+    fill_finalize(fa, f);
+    constexpr uint32_t kCounterWords = (uint32_t)(sizeof(StageCounters) / sizeof(uint32_t));
+    if (f.n >= kCounterWords) { fa.reset_counters = reinterpret_cast<uint32_t *>(ctx->ws.set[0].stages); fa.n_reset = kCounterWords; }
+    { Timer tm(ctx, f.s, HRT_K_FINALIZE); launch(fa, f.s); }
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->fused_counters_clean = fa.reset_counters != nullptr;
+    return HRT_OK;
+}
+}  // extern "C++"
 
+// The executor of a render's plan (path_plan.h says what is decided, and why): plan, size what the plan needs, run the probe if there is
+// one, then launch by launch fill the arguments, make the table if wanted, launch and count; finalize.
 static int render_fused(const LaunchFrame &f) {
     HrtContext *ctx = f.ctx; Tlas *t = f.t; const HrtGlobalParams *h_params = f.h_params; const HrtRayGenParams *rg = f.rg;
-    const uint32_t spp = f.spp, n = f.n; hipStream_t s = f.s;
+    const uint32_t n = f.n; hipStream_t s = f.s;
     Workspace &w = ctx->ws;
-    StageCounters *stg = w.set[0].stages;
+    const RenderPlanInput in = plan_input(f);
+    const RenderPlan plan = plan_fused_render(in);
+    const uint32_t grid = plan.grid, n_slices = plan.n_slices;
+    if (plan.round1) ctx->fused_fallback_launches++;
     TraverseArgs ta = fused_render_args(f);
     PathArgs &pa = ta.path;
-    // Waves per CU: a lane runs its pixel's samples one after the other, so a small tile (the multi-GPU split) ends
-    // with its slowest pixels; about 1.4 pixels per lane lets the lanes that drew cheap pixels take a second one
-    // while fewer waves share each SIMD (measured, profiles/r01_sweep_tile_waves.txt: 1/8 of the C4 frame takes
-    // 172 ms on 12 waves per CU, 210 ms on 16).  A full frame has many pixels per lane and keeps the maximum: 16 waves
-    // per CU = 4 per SIMD for k_fused (122 VGPRs, nothing spilled: 3120 Mrays/s on C4; compiled for 5 waves it spills 95
-    // registers around the shading: 2560), 20 = 5 per SIMD for round 1's kernel (96 VGPRs, a few spills: 2905).
-    const PathKernelChoice pk = choose_path_kernel(ctx, *t);
-    const bool lean = pk.kernel != PathKernel::Round1;
-    ta.postpone_pct = lean ? ctx->fused_postpone_pct : ctx->postpone_pct;
-    const uint32_t grid = fused_render_grid(ctx, pk.blocks_per_cu, n);
-    // HRT_CTX_REUSE_PRIMARY: the lanes' slots for their pixels' primary hits (k_fused<.., REUSE>, fused.hip)
-    if (lean && spp > 1u && ((ctx->flags & HRT_CTX_REUSE_PRIMARY) != 0u || ctx->reuse_primary)) {
-        if (grid * 64u > w.primary_cache_lanes) {
-            if (w.primary_cache) (void)hipFree(w.primary_cache);
-            w.primary_cache = nullptr; w.primary_cache_lanes = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&w.primary_cache, sizeof(float4) * 2u * grid * 64u));
-            w.primary_cache_lanes = grid * 64u;
-        }
+    ta.postpone_pct = plan.round1 ? ctx->postpone_pct : ctx->fused_postpone_pct;
+    // what the plan needs: the primary-hit cache, the capture's arrays, the probe's cost and order, the blocks' progress words
+    if (plan.primary_cache) {
+        RC_TRY(grow_device_arrays(ctx, {{w.primary_cache, 2u * sizeof(float4)}}, w.primary_cache_lanes, grid * 64u));
         pa.primary_cache = w.primary_cache;
     }
-    // HRT_CTX_CAPTURE_PRIMARY: a launch that would run plain k_fused<S, I, false> over the whole frame runs k_path_capture instead, which
-    // also leaves every pixel's primary hit in the context (PrimaryCapture).  Not with the primary-hit cache, the cost-order probe or
-    // sample blocks (below), not on round 1's kernel: frames of many samples, where one more traversal for the guides does not count.
-    const bool full_frame = (uint64_t)n == (uint64_t)rg->width * rg->height;      // (the tile's rows are distinct: every row of the frame)
-    bool capture = lean && !pa.primary_cache && full_frame && ((ctx->flags & HRT_CTX_CAPTURE_PRIMARY) != 0u || ctx->capture_primary);
-    if (capture && n > ctx->capture.capacity) {
+    if (plan.capture) {
         PrimaryCapture &c = ctx->capture;
-        HIP_TRY(ctx, hipStreamSynchronize(s));      // (a guide pass that reads the arrays may be under way)
-        if (c.tuvp) (void)hipFree(c.tuvp);
-        if (c.inst) (void)hipFree(c.inst);
-        c.tuvp = nullptr; c.inst = nullptr; c.capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&c.tuvp, sizeof(float4) * (size_t)n));
-        HIP_TRY(ctx, hipMalloc((void **)&c.inst, sizeof(uint32_t) * (size_t)n));
-        c.capacity = n;
+        if (n > c.capacity) HIP_TRY(ctx, hipStreamSynchronize(s));      // (a guide pass that reads the arrays may be under way)
+        RC_TRY(grow_device_arrays(ctx, {c.tuvp, c.inst}, c.capacity, n));
     }
-    bool captured = false;
-    // Longest-processing-time-first: a pixel's samples run one after the other in one lane, so a render ends with
-    // whatever pixels were started last.  For renders of many samples the first sample is a probe launch of its own
-    // that records how long each slice's pixels took over their sample; the slices are then handed out slowest first,
-    // and the render ends on pixels whose paths leave the scene at once.  (The image does not depend on the order.)
-    uint32_t done_spp = 0;
-    const uint32_t n_slices = (n + ta.fetch_chunk - 1u) / ta.fetch_chunk;
-    // Worth it when a lane gets only a few pixels (the tiles of the multi-GPU split: 1/4 of the C4 frame 238 -> 219 ms);
-    // a full frame has ~8 pixels per lane and keeps its single launch.  Its tail is not small either -- from the first wave that finds
-    // the tile used up to the end of the kernel is 22 % of the kernel's time on C4, and 9 % of the kernel's lane-slots stand idle in it, at 64
-    // spp as at 256 (tools/tail_profile.py, profiles/r13_sample_blocks.txt) -- but it is sample blocks, below, that shorten it.
-    bool lpt = false;
-    if (ctx->fused_lpt && spp >= 16u && n_slices >= 4096u && (uint64_t)n < 4ull * 64ull * (uint64_t)grid) {
-        if (n_slices > w.slice_capacity) {
-            for (uint32_t *p : {w.slice_cost, w.slice_order}) if (p) (void)hipFree(p);
-            w.slice_cost = w.slice_order = nullptr; w.slice_capacity = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&w.slice_cost, sizeof(uint32_t) * n_slices));
-            HIP_TRY(ctx, hipMalloc((void **)&w.slice_order, sizeof(uint32_t) * n_slices));
-            w.slice_capacity = n_slices;
-        }
+    if (plan.probe_spp) RC_TRY(grow_device_arrays(ctx, {w.slice_cost, w.slice_order}, w.slice_capacity, n_slices));
+    if (plan.want_blocks) RC_TRY(grow_device_arrays(ctx, {w.block_progress}, w.block_capacity, n_slices));
+    // the probe: a launch of its own that records each slice's cost; the slices are then handed out slowest first
+    if (plan.probe_spp) {
         HIP_TRY(ctx, hipMemsetAsync(w.slice_cost, 0, sizeof(uint32_t) * n_slices, s));
-        HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
-        const uint32_t probe_spp = (uint32_t)std::min<int>(std::max(ctx->fused_lpt, 1), (int)spp / 4);
-        pa.spp = probe_spp; pa.continue_sum = 0u; pa.slice_cost = w.slice_cost; pa.slice_order = nullptr;
-        { Timer tm(ctx, s, HRT_K_PATHS); (void)launch_path_kernel(pk.kernel, ta, path_scene(*t), grid, s); }       // (sample_block is still 0: nothing to refuse)
+        HIP_TRY(ctx, hipMemsetAsync(w.set[0].stages, 0, sizeof(StageCounters), s));
+        pa.spp = plan.probe_spp; pa.continue_sum = 0u; pa.slice_cost = w.slice_cost; pa.slice_order = nullptr;
+        { Timer tm(ctx, s, HRT_K_PATHS); (void)launch_path_kernel(plan.tree_kernel, ta, path_scene(*t), grid, s); }       // (sample_block is still 0: nothing to refuse)
         ctx->fused_counters_clean = false;
         ctx->h_slice_cost.resize(n_slices); ctx->h_slice_order.resize(n_slices);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_slice_cost.data(), w.slice_cost, sizeof(uint32_t) * n_slices, hipMemcpyDeviceToHost, s));
@@ -504,82 +460,34 @@ static int render_fused(const LaunchFrame &f) {
                          [&](uint32_t x, uint32_t y) { return ctx->h_slice_cost[x] > ctx->h_slice_cost[y]; });
         HIP_TRY(ctx, hipMemcpyAsync(w.slice_order, ctx->h_slice_order.data(), sizeof(uint32_t) * n_slices, hipMemcpyHostToDevice, s));
         pa.slice_cost = nullptr; pa.slice_order = w.slice_order;
-        done_spp = probe_spp;
-        lpt = true;
-        capture = false;
     }
-    // Sample blocks (path_lane.h): a lane gives its pixel back after K samples and the slices go round pass by pass, so only the last K
-    // samples of a frame run in a draining GPU.  k_fused's one-level kernels without the primary-hit cache (which wants a pixel's samples in
-    // one lane) and without the cost order (which keeps precedence on the small tiles where it applies).  `auto`: only where an item's
-    // predecessor was handed out at least three fills of the machine before it -- the hand-over then never has to wait.
-    // Never, forced or not, on a grid of fewer waves than slice counters: a wave keeps an item that is not ready until it is, and takes
-    // from another counter only once its own is drained, so every counter needs a wave whose home it is -- otherwise the predecessor of
-    // a held item can sit behind a counter that nobody visits and the wave waits for ever (the argument: fused_body.h).
-    // What a launch of `now` samples is cut into is a schedule (device_types.h: block_first): HRT_SAMPLE_BLOCK=N forces uniform blocks of N;
-    // `auto` takes HRT_SAMPLE_TAPER's -- large blocks while the machine is full, so that a pixel changes hands seldom, halved down to small
-    // ones over the last samples, so that the frame ends on a short tail (sample_schedule above) -- or, with HRT_SAMPLE_TAPER=0, uniform
-    // blocks of kSampleBlockAuto.
-    bool want_blocks = false, forced = false;
-    if (pk.kernel == PathKernel::Fused && !pa.primary_cache && !lpt && ctx->sample_block != 0 && grid >= kFetchShards) {
-        forced = ctx->sample_block > 0 || (ctx->taper_big > 0 && ctx->taper_forced);
-        want_blocks = forced || (uint64_t)n_slices * ta.fetch_chunk >= 4ull * 64ull * (uint64_t)grid;
-    }
-    if (want_blocks && n_slices > w.block_capacity) {
-        if (w.block_progress) (void)hipFree(w.block_progress);
-        w.block_progress = nullptr; w.block_capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&w.block_progress, sizeof(uint32_t) * n_slices));
-        w.block_capacity = n_slices;
-    }
-    // very long renders are cut into launches of at most fused_max_spp samples (a launch should stay in the
-    // range of seconds); the RNG states and the running sums carry over, so the result is the same bits
-    while (done_spp < spp) {
-        const uint32_t now = std::min<uint32_t>(spp - done_spp, (uint32_t)ctx->fused_max_spp);
-        pa.spp = now; pa.continue_sum = done_spp > 0 ? 1u : 0u;
-        // this launch in blocks: at least two of them (`auto`: 2 kSampleBlockAuto samples), and the counters' numbers, in pixels, within 32 bits
-        SampleSchedule sc;
-        if (want_blocks) sc = ctx->sample_block > 0 ? uniform_schedule(now, (uint32_t)ctx->sample_block) : ctx->taper_big > 0 && taper_fits(now, (uint32_t)ctx->taper_big) ? sample_schedule(now, (uint32_t)ctx->taper_big, (uint32_t)ctx->taper_min) : uniform_schedule(now, (uint32_t)kSampleBlockAuto);
-        const bool blocks = sc.passes >= 2u && (forced || now >= 2u * (uint32_t)kSampleBlockAuto) && (uint64_t)sc.passes * n_slices * ta.fetch_chunk < (1ull << 32);
-        auto magic = [](uint32_t d) { return d ? (uint32_t)std::min<uint64_t>((1ull << 32) / d, 0xffffffffull) : 0u; };      // (an empty tile has no slices)
-        pa.sample_block = blocks ? sc.k_big : 0u; pa.block_magic = blocks && !sc.tapered ? magic(sc.k_big) : 0u;
-        pa.block_min = blocks && sc.tapered ? sc.k_min : 0u; pa.block_taper_end = blocks && sc.tapered ? sc.taper_end : 0u;
-        pa.block_slices = n_slices; pa.block_slices_magic = magic(n_slices); pa.block_chunk_magic = magic(ta.fetch_chunk); pa.block_items = blocks ? (uint32_t)((uint64_t)sc.passes * n_slices) : 0u; pa.block_progress = blocks ? w.block_progress : nullptr;
-        if (blocks) {
+    bool captured = false;
+    for (uint32_t done_spp = plan.probe_spp; done_spp < f.spp;) {
+        const LaunchPlan l = plan_fused_launch(plan, in, done_spp);
+        pa.spp = l.now; pa.continue_sum = l.continue_sum;
+        pa.sample_block = l.sample_block; pa.block_magic = l.block_magic; pa.block_min = l.block_min; pa.block_taper_end = l.block_taper_end;
+        pa.block_slices = l.block_slices; pa.block_slices_magic = l.block_slices_magic; pa.block_chunk_magic = l.block_chunk_magic; pa.block_items = l.block_items;
+        pa.block_progress = l.blocks ? w.block_progress : nullptr;
+        if (l.blocks) {
             HIP_TRY(ctx, hipMemsetAsync(w.block_progress, 0, sizeof(uint32_t) * n_slices, s));
             ctx->sample_block_launches++;
-            ctx->last_schedule[0] = sc.k_big; ctx->last_schedule[1] = sc.k_min; ctx->last_schedule[2] = sc.tapered ? sc.taper_end : 0u; ctx->last_schedule[3] = sc.passes;
+            ctx->last_schedule[0] = l.sc.k_big; ctx->last_schedule[1] = l.sc.k_min; ctx->last_schedule[2] = l.block_taper_end; ctx->last_schedule[3] = l.sc.passes;
         }
-        // (the slice counters: zeroed by the finalize kernel of the previous launch when that was a path-kernel launch too)
-        if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
-        ctx->fused_counters_clean = false;
-        // Which kernel (device_types.h: choose_path_launch, which says what decides it).  From k_path_restart on a launch wants the tree's
-        // leaf_parent table, made here the first time; a tree without records has none, and its launch stays k_path_one's.
-        const PathKnobs knobs{ctx->one_group, ctx->primary_restart, ctx->mask_idle, ctx->primary_direct};
-        PathScene scene = path_scene(*t), with_table = scene;
-        with_table.leaf_parent = &now;      // (any address: "if the table were there")
-        if (path_ladder_rung(choose_path_launch(pk.kernel, capture, blocks, done_spp, ta.seed_primary, knobs, with_table)) >= 2) {
-            const int rc = ensure_leaf_parent(ctx, *t, s);
-            if (rc != HRT_OK) return rc;
-            scene = path_scene(*t);
-        }
-        const PathKernel kernel = choose_path_launch(pk.kernel, capture, blocks, done_spp, ta.seed_primary, knobs, scene);
-        if (kernel == PathKernel::Capture) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
+        RC_TRY(enter_slice_counters(ctx, s));
+        if (l.wants_table) RC_TRY(ensure_leaf_parent(ctx, *t, s));      // (made here the first time)
+        const bool capturing = l.kernel == PathKernel::Capture;
+        if (capturing) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
         bool admitted;
-        { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(kernel, ta, scene, grid, s); }
-        if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set)");
-        if (kernel == PathKernel::Capture) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
-        count_ladder_launch(ctx, kernel);
-        done_spp += now;
+        { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(l.kernel, ta, path_scene(*t), grid, s); }
+        if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set; fewer waves than slice counters, no progress array, no items, or a schedule neither uniform nor tapered)");
+        if (capturing) { pa.trace_tuvp = nullptr; pa.trace_inst = nullptr; ctx->primary_capture_launches++; captured = true; }
+        count_ladder_launch(ctx, l.kernel);
+        done_spp += l.now;
     }
     FinalizeArgs fa{};
-    fa.accum = w.accum; fa.rows = w.rows; fa.n_tile_pixels = n; fa.width = rg->width; fa.spp = spp;
-    fa.color = reinterpret_cast<float4 *>(rg->colorBuffer); fa.albedo = reinterpret_cast<float4 *>(rg->albedoBuffer);
-    fa.normal = reinterpret_cast<float4 *>(rg->normalBuffer); fa.linear = ctx->d_linear;
-    constexpr uint32_t kCounterWords = (uint32_t)(sizeof(StageCounters) / sizeof(uint32_t));
-    if (n >= kCounterWords) { fa.reset_counters = reinterpret_cast<uint32_t *>(stg); fa.n_reset = kCounterWords; }
-    { Timer tm(ctx, s, HRT_K_FINALIZE); launch_finalize(fa, s); }
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->fused_counters_clean = fa.reset_counters != nullptr;
-    ctx->paths += (uint64_t)n * spp;
+    fa.accum = w.accum;
+    RC_TRY(finalize_and_reset_counters(f, fa, launch_finalize));
+    ctx->paths += (uint64_t)n * f.spp;
     ctx->last_tlas = h_params->handle;
     if (captured) {
         PrimaryCapture &c = ctx->capture;
@@ -783,9 +691,7 @@ static int render_wavefront(const LaunchFrame &f, bool count) {
         }
     }
     FinalizeArgs fa{};
-    fa.accum = w.accum; fa.rows = w.rows; fa.n_tile_pixels = n; fa.width = rg->width; fa.spp = spp;
-    fa.color = reinterpret_cast<float4 *>(rg->colorBuffer); fa.albedo = reinterpret_cast<float4 *>(rg->albedoBuffer);
-    fa.normal = reinterpret_cast<float4 *>(rg->normalBuffer); fa.linear = ctx->d_linear;
+    fa.accum = w.accum; fill_finalize(fa, f);
     { Timer tm(ctx, s, HRT_K_FINALIZE); launch_finalize(fa, s); }
     HIP_TRY(ctx, hipGetLastError());
     ctx->paths += (uint64_t)n * spp;
@@ -822,6 +728,14 @@ static int prepare_tile(HrtContext *ctx, const HrtRayGenParams *rg, const HrtTil
     return HRT_OK;
 }
 
+// The frame of a launch (hrt_render_launch, hrt_render_accumulate): its size, the colour buffer, the RNG states.  Touches nothing.
+static int check_frame(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg) {
+    if (rg->width == 0 || rg->height == 0 || (uint64_t)rg->width * rg->height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", rg->width, rg->height);
+    if (!rg->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
+    if (!h_params->stateArray) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.stateArray is NULL");
+    return HRT_OK;
+}
+
 int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *rg, uint32_t spp,
                       const HrtTile *tile, void *stream) {
     if (!ctx || !h_params || !rg) return HRT_ERR_INVALID;
@@ -829,9 +743,7 @@ int hrt_render_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const Hr
     (void)hipSetDevice(ctx->device);
     ctx->capture.valid = false;      // (whatever this launch does: only a complete capture of its own makes it valid again, render_fused)
     if (spp == 0) return fail(ctx, HRT_ERR_INVALID, "spp must be >= 1");
-    if (rg->width == 0 || rg->height == 0 || (uint64_t)rg->width * rg->height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", rg->width, rg->height);
-    if (!rg->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
-    if (!h_params->stateArray) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.stateArray is NULL");
+    RC_TRY(check_frame(ctx, h_params, rg));
     if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
     Tlas *t;
     int rc = find_tlas(ctx, h_params->handle, t);
@@ -858,9 +770,7 @@ int hrt_render_accumulate(HrtContext *ctx, const HrtGlobalParams *h_params, cons
     (void)hipSetDevice(ctx->device);
     if (spp == 0 || spp > 65536u) return fail(ctx, HRT_ERR_INVALID, "spp must be 1..65536 (got %u)", spp);
     if (!d_sum || !d_taken) return fail(ctx, HRT_ERR_INVALID, "d_sum / d_taken is NULL");
-    if (rg->width == 0 || rg->height == 0 || (uint64_t)rg->width * rg->height > 0xffffffffull) return fail(ctx, HRT_ERR_INVALID, "bad frame size %ux%u", rg->width, rg->height);
-    if (!rg->colorBuffer) return fail(ctx, HRT_ERR_INVALID, "RayGenParams.colorBuffer is NULL");
-    if (!h_params->stateArray) return fail(ctx, HRT_ERR_INVALID, "GlobalParams.stateArray is NULL");
+    RC_TRY(check_frame(ctx, h_params, rg));
     if ((ctx->flags & HRT_CTX_COUNT) != 0u) return fail(ctx, HRT_ERR_STATE, "hrt_render_accumulate runs the path kernel k_path_counts: not under HRT_CTX_COUNT");
     if (ctx->fused != 1) return fail(ctx, HRT_ERR_STATE, "hrt_render_accumulate runs the path kernel k_path_counts: not with HRT_FUSED != 1");
     if (!ctx->have_records) return fail(ctx, HRT_ERR_STATE, "hrt_materials_set has not been called");
@@ -883,27 +793,17 @@ int hrt_render_accumulate(HrtContext *ctx, const HrtGlobalParams *h_params, cons
     // (the fields that are free in this launch carry the caller's arrays, all in frame order: path_lane.h, kCounts)
     pa.accum = reinterpret_cast<float4 *>(d_sum); pa.trace_inst = d_taken; pa.slice_order = d_counts;
     const PathKernelChoice pk = choose_path_kernel(ctx, *t);
-    const uint32_t grid = fused_render_grid(ctx, pk.blocks_per_cu, n);
-    // the slice counters: render_fused's protocol -- zero on entry (left so by the previous launch's finalize kernel, or set here), zeroed
-    // again by this launch's finalize kernel for whichever launch comes next
-    StageCounters *stg = ctx->ws.set[0].stages;
-    if (!ctx->fused_counters_clean) HIP_TRY(ctx, hipMemsetAsync(stg, 0, sizeof(StageCounters), s));
-    ctx->fused_counters_clean = false;
+    const uint32_t grid = fused_render_grid(ctx->n_cu, ctx->traverse_blocks_auto, pk.blocks_per_cu, n);
+    RC_TRY(enter_slice_counters(ctx, s));
     bool admitted;
     { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(PathKernel::Counts, ta, path_scene(*t), grid, s); }
     if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused the counts launch");
     FinalizeCountsArgs fa{};
-    fa.sum = pa.accum; fa.taken = d_taken; fa.counts = d_counts; fa.rows = ctx->ws.rows; fa.n_tile_pixels = n; fa.width = rg->width; fa.spp = spp;
-    fa.color = reinterpret_cast<float4 *>(rg->colorBuffer); fa.albedo = reinterpret_cast<float4 *>(rg->albedoBuffer);
-    fa.normal = reinterpret_cast<float4 *>(rg->normalBuffer); fa.linear = ctx->d_linear;
-    constexpr uint32_t kCounterWords = (uint32_t)(sizeof(StageCounters) / sizeof(uint32_t));
-    if (n >= kCounterWords) { fa.reset_counters = reinterpret_cast<uint32_t *>(stg); fa.n_reset = kCounterWords; }
+    fa.sum = pa.accum; fa.taken = d_taken; fa.counts = d_counts;
     // HrtStats.paths: a uniform launch's samples are known here, a map's are summed by the finalize kernel (read in hrt_stats_get)
     if (d_counts) fa.paths = reinterpret_cast<unsigned long long *>(&ctx->d_stats->paths);
     else ctx->paths += (uint64_t)n * spp;
-    { Timer tm(ctx, s, HRT_K_FINALIZE); launch_finalize_counts(fa, s); }
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->fused_counters_clean = fa.reset_counters != nullptr;
+    RC_TRY(finalize_and_reset_counters(frame, fa, launch_finalize_counts));
     ctx->last_tlas = h_params->handle;
     return HRT_OK;
 }

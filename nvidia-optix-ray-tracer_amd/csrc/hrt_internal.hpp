@@ -16,6 +16,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -350,6 +351,9 @@ const char *last_error_of(const HrtContext *ctx);
                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// ... and for a step that has reported its own failure: pass its code on
+#define RC_TRY(expr) do { const int _rc = (expr); if (_rc != HRT_OK) return _rc; } while (0)
+
 // the TLAS that a launch's GlobalParams.handle names
 inline int find_tlas(HrtContext *ctx, uint64_t handle, Tlas *&t) {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -385,6 +389,14 @@ struct Timer {
 };
 
 void drain_spans(HrtContext *ctx);
+
+// hrt_api.cpp: device arrays of one capacity, grown on demand (need <= capacity: nothing happens).  Freed, nulled and the capacity cleared before
+// anything is allocated, so a failed hipMalloc leaves the context consistent.  An array: its pointer and the bytes it holds per unit of capacity.
+struct DeviceArray {
+    void **p; size_t elem;
+    template <class T> DeviceArray(T *&array, size_t bytes_per_unit = sizeof(T)) : p((void **)&array), elem(bytes_per_unit) {}
+};
+int grow_device_arrays(HrtContext *ctx, std::initializer_list<DeviceArray> arrays, uint32_t &capacity, uint32_t need);
 
 // hrt_api.cpp: the launch's material tables for a TLAS, and hrt_trace_rays' traversal of rays in RayRec form (enqueued only)
 int refresh_tables(HrtContext *ctx, uint64_t handle, Tlas *t, hipStream_t s);

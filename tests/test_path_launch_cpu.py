@@ -1,7 +1,7 @@
 """The path kernels' one launch entry, as plain host code (device_types.h): the admission rule (path_launch_admitted, which launch_path_kernel
 calls before it launches anything) -- for every kernel one launch that is admitted, and every single contradiction of what that kernel is
-compiled to take for granted, refused -- and the choice of a launch's kernel (choose_path_launch, which render_fused calls), over every
-combination of what decides it.  A stand-alone program built against device_types.h calls both over the tables below and prints the
+compiled to take for granted, refused -- and the choice of a launch's kernel (choose_path_launch, which the render's plan calls: path_plan.h,
+tests/test_render_plan_cpu.py), over every combination of what decides it.  A stand-alone program built against device_types.h calls both over the tables below and prints the
 verdicts -- no device is opened, nothing is launched, nothing is loaded into this process."""
 import itertools
 import re
@@ -14,16 +14,18 @@ ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "nvidia-optix-ray-tracer_amd" / "csrc"
 
 # The admitted launch of each kernel: (scene = one_level, n_instances, has_spheres, leaf_parent; statements on the TraverseArgs `a`).
-# Every launch has the material tables; the block kernels have a block size; the restart and the kernels built on it have the table and the
-# window; the counts launch has the caller's sums and the samples they hold.
+# Every launch has the material tables and a grid of 8 waves; the block kernels have a block size, a uniform schedule of it (block_magic = 2^32 / 32),
+# the slices' progress words and items to hand out; the restart and the kernels built on it have the table and the window; the counts launch
+# has the caller's sums and the samples they hold.
 TABLES = "a.path.hitgroups = &hg; a.path.inst_program = &word;"
-RESTART = ("{true, 1u, false, &word}", TABLES + " a.path.sample_block = 32u; a.seed_primary = 2;")
+IN_BLOCKS = TABLES + " a.path.sample_block = 32u; a.path.block_magic = 0x08000000u; a.path.block_progress = &word; a.path.block_items = 2u;"
+RESTART = ("{true, 1u, false, &word}", IN_BLOCKS + " a.seed_primary = 2;")
 BASE = {
     "Fused":          ("{true, 3u, true, nullptr}", TABLES),
     "FusedInstanced": ("{false, 3u, true, nullptr}", TABLES),
     "Capture":        ("{true, 3u, true, nullptr}", TABLES + " a.path.trace_tuvp = &tuvp; a.path.trace_inst = &word;"),
-    "Blocks":         ("{true, 3u, true, nullptr}", TABLES + " a.path.sample_block = 32u;"),
-    "OneGroup":       ("{true, 1u, false, nullptr}", TABLES + " a.path.sample_block = 32u;"),
+    "Blocks":         ("{true, 3u, true, nullptr}", IN_BLOCKS),
+    "OneGroup":       ("{true, 1u, false, nullptr}", IN_BLOCKS),
     "Restart":        RESTART,
     "Round1":         ("{true, 3u, true, nullptr}", TABLES),
     "Counts":         ("{true, 3u, true, nullptr}", TABLES + " a.path.spp = 4u; a.path.accum = &sum; a.path.trace_inst = &word;"),
@@ -41,6 +43,16 @@ CASES += [(k, "a.path.sample_block = 0u;", False) for k in BLOCK_KERNELS]
 CASES += [(k, "a.path.trace_rays = &ray;", False) for k in BLOCK_KERNELS]
 CASES += [(k, "a.path.slice_cost = &word;", False) for k in BLOCK_KERNELS]
 CASES += [(k, "a.path.slice_order = &word;", False) for k in BLOCK_KERNELS]
+# ... on a grid that gives every one of the 8 slice counters a wave whose home it is (fewer: the launch could wait for ever), with the hand-over's
+# memory, and with a schedule that is purely uniform or purely tapered (powers of two, the halvings' end not in front of the first block)
+TAPERED = "a.path.block_magic = 0u; a.path.block_min = 8u; a.path.block_taper_end = 64u;"
+CASES += [(k, change, ok) for k in BLOCK_KERNELS for change, ok in
+          [("grid = 7u;", False), ("grid = 0u;", False), ("grid = 8u;", True), ("grid = 4096u;", True),
+           ("a.path.block_progress = nullptr;", False), ("a.path.block_items = 0u;", False),
+           ("a.path.block_min = 8u;", False), ("a.path.block_taper_end = 64u;", False), ("a.path.block_magic = 0u;", False),        # mixed; mixed; neither
+           (TAPERED, True), (TAPERED + " a.path.block_taper_end = 32u;", True), (TAPERED + " a.path.block_min = 32u;", True),
+           (TAPERED + " a.path.block_taper_end = 31u;", False), (TAPERED + " a.path.block_min = 0u;", False), (TAPERED + " a.path.block_min = 6u;", False),
+           (TAPERED + " a.path.sample_block = 48u; a.path.block_taper_end = 96u;", False)]]
 # one hit group: a one-level tree of triangles over exactly one instance, whose table entries exist
 CASES += [(k, "scene.n_instances = 2u;", False) for k in ONE_GROUP_KERNELS]
 CASES += [(k, "scene.has_spheres = true;", False) for k in ONE_GROUP_KERNELS]
@@ -109,16 +121,17 @@ int main() {
         if (blocks && tree != 0) continue;
         PathScene scene = scenes[sc]; scene.one_level = trees[tree] != PathKernel::FusedInstanced; scene.leaf_parent = table ? &word : nullptr;
         const PathKnobs knobs{(knob & 8) != 0, (knob & 4) != 0, (knob & 2) != 0, (knob & 1) != 0};
-        const PathKernel kernel = choose_path_launch(trees[tree], capture != 0, blocks != 0, done_spp, seed, knobs, scene);
+        const PathKernel kernel = choose_path_launch(trees[tree], capture != 0, blocks != 0, done_spp, seed, knobs, scene, table != 0);
         TraverseArgs a{}; a.path.hitgroups = &hg; a.path.inst_program = &word; a.seed_primary = seed;
-        a.path.sample_block = blocks ? 32u : 0u;        // (a launch in blocks has no callers' rays, cost probe or slice order)
+        a.path.sample_block = blocks ? 32u : 0u;        // (a launch in blocks has no callers' rays, cost probe or slice order; it has a schedule and the hand-over's memory)
+        if (blocks) { a.path.block_magic = 0x08000000u; a.path.block_progress = &word; a.path.block_items = 2u; }
         if (kernel == PathKernel::Capture) { a.path.trace_tuvp = &tuvp; a.path.trace_inst = &word; }
-        std::printf("%%d %%d\n", (int)kernel, (int)path_launch_admitted(kernel, a, scene));
+        std::printf("%%d %%d\n", (int)kernel, (int)path_launch_admitted(kernel, a, scene, 8u));
     }
     return 0;
 }
 """
-CASE = '    { TraverseArgs a{}; PathScene scene%s; %s %s std::printf("%%d\\n", (int)path_launch_admitted(PathKernel::%s, a, scene)); }'
+CASE = '    { TraverseArgs a{}; PathScene scene%s; uint32_t grid = 8u; %s %s std::printf("%%d\\n", (int)path_launch_admitted(PathKernel::%s, a, scene, grid)); }'
 
 
 def enumerators():
@@ -197,6 +210,7 @@ def test_the_rule_is_written_once():
         text = path.read_text()
         assert "blocks_launch_admitted" not in text and "launch_fused" not in text.replace("launch_fused_as", "") and "launch_paths_v1" not in text, path.name
         assert ("path_launch_admitted(" in text) == (path.name == "fused.hip"), path.name          # called by the entry, and only there
-        assert ("choose_path_launch(" in text) == (path.name == "hrt_api.cpp"), path.name          # called by render_fused, and only there
+        assert "choose_path_launch(" not in text, path.name          # called by the render's plan (below), and only there
+    assert (CSRC / "path_plan.h").read_text().count("choose_path_launch(") == 1
     header = (CSRC / "device_types.h").read_text()
     assert header.count("bool launch_path_kernel(") == 1 and header.count("inline bool path_launch_admitted(") == 1 and header.count("inline PathKernel choose_path_launch(") == 1

@@ -1,5 +1,5 @@
 """HRT_SAMPLE_TAPER: k_path_blocks hands a pixel out in blocks that start large and end small -- pass b is samples [first(b), first(b + 1))
-of a slice's pixels (device_types.h: block_first, block_ends; hrt_api.cpp: sample_schedule).  A pixel still adds its samples in sample
+of a slice's pixels (device_types.h: block_first, block_ends; path_plan.h: sample_schedule).  A pixel still adds its samples in sample
 order from one RNG stream, whichever lanes take its blocks.
 
 Bars, for every render: the same render with HRT_SAMPLE_BLOCK=0 (k_fused, a lane keeps its pixel) on a context of its own AND the oracle
