@@ -76,6 +76,7 @@ struct PathArgs {
     uint64_t *rays_closest, *rays_any;
     const RayRec *trace_rays;      // fused kernel as hrt_trace_rays: the "pixels" are these rays, traced once; results below (else NULL)
     float4 *trace_tuvp; uint32_t *trace_inst; uint32_t trace_any;
+                                   // (trace_any in a launch of k_path_direct, a block render, which has no callers' rays: HRT_MISS_BLOCK, path_lane.h: path_finish)
     uint32_t block_taper_end;      // sample blocks, tapered: the sample at which the halving blocks end (below; in what was padding)
     float4 *primary_cache;         // k_fused<.., REUSE>: two float4 per lane of the grid, the primary hit of the lane's pixel (else NULL)
     // sample blocks (path_lane.h; k_fused's one-level instantiations without REUSE): 0 = a lane keeps its pixel for all samples of the launch
@@ -113,6 +114,20 @@ __host__ __device__ inline bool block_ends(uint32_t k_big, uint32_t k_min, uint3
     if ((int32_t)q < 0) q &= k_min - 1u;
     const uint32_t below = q - 1u < k_big - 1u ? q - 1u : k_big - 1u;
     return (q & (below | (k_min - 1u))) == 0u;
+}
+// hold_ends: a lane that has taken sample p - 1 of its pixel gives the pixel back -- the launch's `spp` samples are taken, or the schedule
+// (magic != 0: uniform blocks of k_big, magic = min(2^32 / k_big, 2^32 - 1); else tapered) has a boundary at p.  path_finish's test
+// (path_lane.h), word for word, as a function: k_path_direct's miss block steps through a block's samples with it, and
+// hrt_sample_schedule holds it to the passes of every schedule it makes.
+__host__ __device__ inline bool hold_ends(uint32_t spp, uint32_t k_big, uint32_t magic, uint32_t k_min, uint32_t taper_end, uint32_t p) {
+    bool ends = p >= spp;
+    if (magic != 0u) {
+        const uint32_t rem = p - (uint32_t)(((uint64_t)p * magic) >> 32) * k_big;
+        ends = ends || rem == 0u || rem == k_big;
+    } else {
+        ends = ends || block_ends(k_big, k_min, taper_end, p);
+    }
+    return ends;
 }
 
 struct TraverseArgs {

@@ -237,11 +237,15 @@ __device__ __forceinline__ void fused_body(const TraverseArgs &a) {
                     const global_f32x4 rp = (global_f32x4)reinterpret_cast<const f32x4 *>(prim_bytes + rec * a.prim_stride);       // (32-bit byte offsets, as in the loop)
                     ra = rp[0]; rb = *(global_f32x3)(rp + 1); rc = *(global_f32x3)(rp + 2);
                 }
+                stats.finished_primary(lane_bit(finished) && P.px_depth == 1u && L.s.bprim == kMissPrim);
+                [[maybe_unused]] const uint32_t sample_was = P.px_sample;        // (the instrumented build's)
                 if (lane_bit(finished)) {
+                    // (s.tlo > tmin: the walk began inside a seed's window -- a miss from there does not take the block, path_lane.h)
                     const TravState &s = L.s;
                     st = path_finish<V, PathLane, 1>(P, chain, a, mk3(s.ox, s.oy, s.oz), mk3(s.dx, s.dy, s.dz), lean_miss_t(s.bt, s.bprim, a.tmax), s.bu, s.bv, s.bprim, 0u,
-                                                     s_seed + tx, s.binst, false, s_restart + tx);
+                                                     s_seed + tx, s.binst, s.tlo > tmin, s_restart + tx);
                 }
+                stats.fast_forwarded(ends_path && P.px_sample > sample_was ? P.px_sample - sample_was - 1u : 0u);
                 may_test = may_test && st.want_primary;      // (the pixel goes on in this lane: a pixel that path_take hands out has no record)
             } else
             if (lane_bit(finished)) {

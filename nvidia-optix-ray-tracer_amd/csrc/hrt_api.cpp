@@ -462,8 +462,10 @@ static int render_fused(const LaunchFrame &f) {
         pa.slice_cost = nullptr; pa.slice_order = w.slice_order;
     }
     bool captured = false;
+    const int render_refill = ta.refill_threshold;
     for (uint32_t done_spp = plan.probe_spp; done_spp < f.spp;) {
         const LaunchPlan l = plan_fused_launch(plan, in, done_spp);
+        ta.refill_threshold = launch_refill_threshold(l.kernel, render_refill, ctx->refill_auto);       // (k_path_direct's own, path_plan.h)
         pa.spp = l.now; pa.continue_sum = l.continue_sum;
         pa.sample_block = l.sample_block; pa.block_magic = l.block_magic; pa.block_min = l.block_min; pa.block_taper_end = l.block_taper_end;
         pa.block_slices = l.block_slices; pa.block_slices_magic = l.block_slices_magic; pa.block_chunk_magic = l.block_chunk_magic; pa.block_items = l.block_items;
@@ -477,6 +479,8 @@ static int render_fused(const LaunchFrame &f) {
         if (l.wants_table) RC_TRY(ensure_leaf_parent(ctx, *t, s));      // (made here the first time)
         const bool capturing = l.kernel == PathKernel::Capture;
         if (capturing) { pa.trace_tuvp = ctx->capture.tuvp; pa.trace_inst = ctx->capture.inst; }
+        // HRT_MISS_BLOCK travels in trace_any, which only a launch over callers' rays reads otherwise (path_lane.h: path_finish, kDirect)
+        pa.trace_any = l.kernel == PathKernel::Direct && ctx->miss_block ? 1u : 0u;
         bool admitted;
         { Timer tm(ctx, s, HRT_K_PATHS); admitted = launch_path_kernel(l.kernel, ta, path_scene(*t), grid, s); }
         if (!admitted) return fail(ctx, HRT_ERR_STATE, "the path kernel refused a launch in sample blocks (callers' rays, cost probe or slice order set; fewer waves than slice counters, no progress array, no items, or a schedule neither uniform nor tapered)");
@@ -877,6 +881,14 @@ int hrt_sample_schedule(uint32_t spp, uint32_t block_big, uint32_t block_min, ui
             if (block_ends(sc.k_big, sc.k_min, sc.taper_end, p) != starts) return HRT_ERR_STATE;
             if (starts) ++b;
         }
+    // ... and what k_path_direct's miss block steps with (device_types.h: hold_ends), uniform blocks too: a lane's hold ends behind sample p - 1
+    // exactly where a pass starts or the launch's samples end, with the block fields a launch of this schedule gets (path_plan.h)
+    const uint32_t magic = tapered ? 0u : (uint32_t)std::min<uint64_t>((1ull << 32) / sc.k_big, 0xffffffffull);
+    for (uint32_t p = 1, b = 1; p <= spp; ++p) {
+        const bool starts = b < sc.passes && first[b] == p;
+        if (hold_ends(spp, sc.k_big, magic, tapered ? sc.k_min : 0u, tapered ? sc.taper_end : 0u, p) != (starts || p == spp)) return HRT_ERR_STATE;
+        if (starts) ++b;
+    }
     *n_passes = sc.passes;
     return HRT_OK;
 }

@@ -299,6 +299,7 @@ struct HrtContext {
     uint64_t mask_idle_launches = 0;            // ... and how many did
     bool primary_direct = true;                 // HRT_PRIMARY_DIRECT: ... of those, k_path_direct (fused_direct.hip) instead: repeat primary rays test their known hit's record in the regeneration
     uint64_t direct_launches = 0;               // ... and how many did
+    bool miss_block = true;                     // HRT_MISS_BLOCK: k_path_direct's regeneration lets a primary ray that left the scene take the rest of its sample block (path_lane.h: path_finish)
     int taper_big = kSampleTaperBig, taper_min = kSampleTaperMin;      // HRT_SAMPLE_TAPER: what `auto` hands out -- blocks that start at taper_big samples and end on taper_min (0: uniform blocks of kSampleBlockAuto)
     bool taper_forced = false;                  // ... whatever the tile, like HRT_SAMPLE_BLOCK=N (tests)
     uint32_t last_schedule[4] = {0u, 0u, 0u, 0u};      // the last launch in sample blocks: largest block, smallest block, end of the halvings (0: uniform), passes

@@ -167,6 +167,9 @@ __device__ __forceinline__ V3 fold_chain_one(bool miss, const float *bg, uint32_
 // in two parts, with path_take and the primary rays between them: kPart 1, for every finished lane -- the seed, the record, and what ends a
 // path (a lane whose ray goes on to be shaded comes back with nothing to do) -- and kPart 2, the shading branch alone, for the lanes that
 // have a hit to shade: the finished ones and those whose record's test accepted.  kPart 0: all of it, one call, every other kernel.
+// kPart 1 takes in `restartable` whether the finished ray's walk began inside a seed's window, and reads the miss block's switch (HRT_MISS_BLOCK)
+// from PathArgs::trace_any, which a block render does not have (hrt_api.cpp: render_fused puts it there): a primary miss that had the launch's whole
+// interval takes the rest of the lane's hold on the pixel, below.
 typedef const __attribute__((address_space(1))) uint32_t *global_words;
 template <class V, class Lane, int kPart = 0>
 __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4], const TraverseArgs &a, V3 o, V3 d, float bt, float bu, float bv, uint32_t bprim, uint32_t binst,
@@ -221,6 +224,23 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
             } else {
                 // ... or the tapered schedule has a boundary there (device_types.h; no blocks, all three 0: never)
                 ends = ends || block_ends(a.path.sample_block, a.path.block_min, a.path.block_taper_end, P.px_sample);
+            }
+        }
+        if constexpr (V::kDirect) {
+            // The miss block (HRT_MISS_BLOCK; DESIGN.md section 2.1 "A primary miss takes the rest of its block"): the pixel's primary ray has
+            // walked the launch's whole interval from the root -- no seed bounded it, no window (`restartable`: path_finish's head) -- and left
+            // the scene.  Every further sample's primary ray is the same ray (no jitter), a miss at depth 1 draws no random number and folds
+            // to the same `r`, so the samples up to the end of the lane's hold are decided here: the same addends in the same order (n * r is
+            // another float), each one counted as the closest-hit ray it stands for, none of them launched.  Where the hold ends is the test
+            // above, as one function for the loop (device_types.h: hold_ends; hrt_sample_schedule holds both to the schedule's passes), and
+            // nothing is carried over it: the next block's first primary ray walks again.  (A ray that comes back a miss from inside a seed's
+            // window "cannot happen" and proves nothing: it goes on sample by sample.)
+            if (miss && P.px_depth == 1u && !restartable && a.seed_primary >= 2 && a.path.trace_any != 0u) {
+                while (!ends) {
+                    P.px_ax += r.x; P.px_ay += r.y; P.px_az += r.z;
+                    ++P.px_sample; ++P.px_rays_closest;
+                    ends = hold_ends(a.path.spp, a.path.sample_block, a.path.block_magic, a.path.block_min, a.path.block_taper_end, P.px_sample);
+                }
             }
         }
         if (ends) {

@@ -126,6 +126,18 @@ inline RenderPlan plan_fused_render(const RenderPlanInput &in) {
     return r;
 }
 
+// The regeneration threshold of one launch (TraverseArgs::refill_threshold: the lanes that are idle before a wave regenerates).  The render's
+// is the context's 20, or 12 on a two-level tree (hrt_api.cpp: fused_render_args); a launch of k_path_direct gets kDirectRefillThreshold
+// while nobody has set HRT_REFILL_THRESHOLD (`refill_auto`).  That kernel keeps the short rays out of the waiting pool -- a repeat primary
+// ray with a record never waits, a primary miss takes its block -- so what waits are bounces, and a regeneration is worth waiting longer
+// for: on C4 26 is 0.7 % above 20, every run of five alternating ones above 20's median plus twice its range, and C3 stays level; 32 is
+// another 0.4 % on C4 and 0.7 % under 20 on C3, whose paths are shorter (profiles/r33_primary_miss_block.txt section 6).  Every other
+// kernel keeps the render's value.
+constexpr int kDirectRefillThreshold = 26;
+inline int launch_refill_threshold(PathKernel kernel, int render_threshold, bool refill_auto) {
+    return refill_auto && kernel == PathKernel::Direct ? kDirectRefillThreshold : render_threshold;
+}
+
 // One launch of the render, after done_spp samples (the probe's included).
 struct LaunchPlan {
     uint32_t now, continue_sum;               // PathArgs::spp, continue_sum

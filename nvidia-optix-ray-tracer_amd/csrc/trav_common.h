@@ -578,8 +578,36 @@ struct LaneStats {
     // iterations those were alive and the iterations they waited for their regeneration, and the rays decided in the regeneration
     // (kDirect).  They take the drained phase's slots (HrtStats.tail), which such a build does not fill.
     unsigned long long quick = 0, prim_rays = 0, quick_rays = 0, quick_alive = 0, quick_wait = 0, direct_rays = 0;
+    // what a pixel's primary MISSES cost (k_path_direct's miss block; profiles/r33_primary_miss_block.txt section 0): `root` -- the lanes whose ray
+    // is a primary ray that walks from the root, root_alive / root_wait -- PER LANE, the iterations the lane's such ray has been alive and has
+    // waited; a ray that comes back a miss at depth 1 adds them to the wave's sums (miss_*).  ff_rays: the samples the miss block decided.
+    // miss_alive and miss_wait take the last two of the drained phase's slots; miss_rays and ff_rays share the word in front of debug[]
+    // (prim_tests - prim_tests_closest), 32 bits each: one launch of 2^32 rays at most between two resets.
+    unsigned long long root = 0, miss_rays = 0, miss_alive = 0, miss_wait = 0, ff_rays = 0;
+    uint32_t root_alive = 0, root_wait = 0;
 #endif
 #endif
+#if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
+    // the wave's sum of a per-lane count below 2^24, bit by bit (no cross-lane instruction that an instrumented loop would have to schedule)
+    static __device__ __forceinline__ unsigned long long wave_sum24(uint32_t v) {
+        unsigned long long sum = 0ull;
+        for (int b = 0; b < 24; ++b) sum += (unsigned long long)__popcll(__ballot((v >> b) & 1u)) << b;
+        return sum;
+    }
+#endif
+    // the regeneration looks at a finished ray: `primary_miss` -- the lane's is a primary ray (depth 1) that came back from the loop a miss
+    __device__ __forceinline__ void finished_primary([[maybe_unused]] bool primary_miss) {
+#if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
+        miss_rays += __popcll(__ballot(primary_miss));
+        miss_alive += wave_sum24(primary_miss ? root_alive : 0u); miss_wait += wave_sum24(primary_miss ? root_wait : 0u);
+#endif
+    }
+    // ... and the miss block has decided `n` further samples of the lane's pixel without a walk
+    __device__ __forceinline__ void fast_forwarded([[maybe_unused]] uint32_t n) {
+#if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
+        ff_rays += wave_sum24(n);
+#endif
+    }
     // the wave has found the tile used up (every regeneration from then on says so: the first one counts)
     __device__ __forceinline__ void drained([[maybe_unused]] bool exhausted) {
 #ifdef HRT_LANE_STATS
@@ -617,11 +645,15 @@ struct LaneStats {
         prim_rays += __popcll(__ballot(primary)); quick_rays += __popcll(q);
         const unsigned long long n = __popcll(__ballot(direct));
         direct_rays += n; prim += n;
+        const bool from_root = primary && !quick_lane;
+        root = (root & ~launched) | __ballot(from_root);
+        if (from_root) { root_alive = 0u; root_wait = 0u; }
 #endif
     }
     __device__ __forceinline__ void primary_slots([[maybe_unused]] uint64_t alive_m, [[maybe_unused]] uint64_t waiting_m) {
 #if defined(HRT_LANE_STATS) && defined(HRT_LANE_STATS_PRIMARY)
         quick_alive += __popcll(quick & alive_m); quick_wait += __popcll(quick & waiting_m);
+        root_alive += __builtin_amdgcn_inverse_ballot_w64(root & alive_m) ? 1u : 0u; root_wait += __builtin_amdgcn_inverse_ballot_w64(root & waiting_m & ~alive_m) ? 1u : 0u;
 #endif
     }
     // k_path_idle's loop copy with idle lanes off (trav_loop.h: kIdleOff) counts between two of these, where every lane is on: the counters
@@ -630,7 +662,7 @@ struct LaneStats {
 #ifdef HRT_LANE_STATS
         asm volatile("" : "+v"(iter), "+v"(alive), "+v"(node), "+v"(prim), "+v"(ppass));
 #ifdef HRT_LANE_STATS_PRIMARY
-        asm volatile("" : "+v"(quick), "+v"(quick_alive), "+v"(quick_wait));
+        asm volatile("" : "+v"(quick), "+v"(quick_alive), "+v"(quick_wait), "+v"(root), "+v"(root_alive), "+v"(root_wait));
 #endif
 #endif
     }
@@ -657,6 +689,7 @@ struct LaneStats {
 #ifdef HRT_LANE_STATS_PRIMARY
             (void)bias; (void)lane_iters; (void)exit_rel;
             atomicAdd(t + 0, prim_rays); atomicAdd(t + 1, quick_rays); atomicAdd(t + 3, quick_alive); atomicAdd(t + 4, quick_wait); atomicAdd(t + 5, direct_rays);
+            atomicAdd(t + 6, miss_alive); atomicAdd(t + 7, miss_wait); atomicAdd(d + 5, miss_rays | (ff_rays << 32));
 #else
             atomicAdd(t + 0, tail_iter); atomicAdd(t + 1, tail_alive);
             atomicMax(t + 3, ~(t_drained - base + bias)); atomicMax(t + 4, exit_rel); atomicAdd(t + 5, exit_rel);

@@ -32,9 +32,16 @@ if "primary" in sys.argv:
     # The counters take the drained phase's slots (HrtStats.tail); a record tested in the regeneration (k_path_direct) counts as a primitive test.
     t = s.tail
     prim_rays, quick, q_alive, q_wait, direct = t[0], t[1], t[3], t[4], t[5]
-    all_primary = prim_rays + direct
+    all_primary = prim_rays + direct + ((s.prim_tests - s.prim_tests_closest) >> 32)      # (walked, decided by their record, decided by the miss block: below)
     print("kernel", path_kernels.kernel_ran(s))
     print("primary rays", all_primary, "walked from the root", prim_rays - quick, "started at a node other than the root", quick, "decided in the regeneration", direct)
     print("h = share of primary rays with a record %.4f" % ((quick + direct) / max(all_primary, 1)))
     print("iterations the rays started at a node were alive", q_alive, "(%.2f each)  waited for their regeneration" % (q_alive / max(quick, 1)), q_wait, "(%.2f each)" % (q_wait / max(quick, 1)))
     print("their lane-slots %d of %d = %.2f %%" % (q_alive + q_wait, 64 * it, 100.0 * (q_alive + q_wait) / (64 * it)))
+    # primary rays that came back from the loop a miss (depth 1), the iterations they were alive and waited for their regeneration, and the samples
+    # k_path_direct's miss block decided without a walk (HRT_MISS_BLOCK): slots 6 and 7, and the two halves of prim_tests - prim_tests_closest
+    packed = s.prim_tests - s.prim_tests_closest
+    m_rays, ff, m_alive, m_wait = packed & 0xffffffff, packed >> 32, t[6], t[7]
+    print("primary rays that came back a miss", m_rays, "iterations alive", m_alive, "(%.2f each)  waited" % (m_alive / max(m_rays, 1)), m_wait, "(%.2f each)" % (m_wait / max(m_rays, 1)))
+    print("their lane-slots %d of %d = %.2f %%" % (m_alive + m_wait, 64 * it, 100.0 * (m_alive + m_wait) / (64 * it)))
+    print("samples decided by the miss block", ff)
