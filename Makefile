@@ -41,6 +41,11 @@ $(LIBDIR)/denoise.o: $(CSRC)/denoise.hip $(CSRC)/denoise_temporal_body.h $(CSRC)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the accumulated mode's kernel, in a unit of its own; rebuilt whenever the filter it feeds is (denoise.o's dependencies)
+$(LIBDIR)/denoise_accum.o: $(CSRC)/denoise_accum.hip $(CSRC)/denoise_temporal_body.h $(CSRC)/denoise_temporal_body.inc $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/bvh8_geom.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/denoise_link.o: $(CSRC)/denoise_link.hip $(CSRC)/denoise_temporal_body.h $(CSRC)/denoise_temporal_body.inc $(CSRC)/device_types.h $(CSRC)/trav_common.h $(CSRC)/bvh8_geom.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -79,7 +84,7 @@ $(LIBDIR)/bvh8_host_api.o: $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h include/hrt.
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o refit.o pose.o denoise.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
+OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o refit.o pose.o denoise.o denoise_accum.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
 $(LIBDIR)/libhrt.so: $(PATH_OBJS) $(OTHER_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 	@cat $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc $(CSRC)/*.hpp $(CSRC)/*.cpp include/*.h)) | sha256sum | cut -c1-16 > $(LIBDIR)/BUILD_ID

@@ -367,6 +367,7 @@ int  hrt_debug_denoise_temporal_state(HrtContext *ctx, HrtFloat4 *d_accum, float
 typedef struct HrtDenoiseVarianceParams {
     float    sigma_luminance;      /* luminance edge stop in standard deviations, > 0                                       (default 4.0)  */
     uint32_t history_min;          /* 1..65536: a hit pixel with L below it takes the 5x5 variance                          (default 4)    */
+                                   /* (accumulated mode: the samples a pixel needs before its own moments are believed, 2 at least)        */
     float    variance_floor;       /* added to sigma_luminance^2 var, > 0                                                   (default 1e-6) */
     uint32_t reserved;             /* must be 0 */
 } HrtDenoiseVarianceParams;
@@ -386,6 +387,32 @@ int  hrt_denoise_variance_launch(HrtContext *ctx, const HrtGlobalParams *h_param
  * NULL pointer skips its buffer.  hrt_debug_denoise_temporal_state gives its A, L and motion.  HRT_ERR_STATE before the first call.
  * Enqueued only. */
 int  hrt_debug_denoise_variance_state(HrtContext *ctx, float *d_moments, float *d_variance, void *stream);
+
+/* Accumulated mode: the variance-guided filter over a still frame that hrt_render_accumulate has sampled, its edge stop taken from the
+ * frame's own sums instead of a temporal history (DESIGN.md 3e "Accumulated mode"; tests/denoise_accumulated_ref.py restates it).
+ * Inputs: d_sum and d_taken as hrt_render_accumulate leaves them (width * height, frame order), and the frame's guides.  Per pixel with
+ * n = d_taken[p] samples: the linear mean m = sum.xyz / n (k_finalize_counts' arithmetic; (0, 0, 0) for n = 0; alpha 1); the guides
+ * with the depth of a pixel without a sample set to +inf, so that it is background to the filter -- never a tap, never filtered,
+ * black in the result: a frame of which only a tile has been accumulated is a valid input; and the variance of the mean's luminance:
+ * 0 on background, max(0, m2 - m1^2) / n with m1 = l(sum.xyz) / n, m2 = sum.w / n (hrt_sample_counts' estimator over n) on a hit with
+ * n >= max(history_min, 2), and on every other hit the variance of l(m) over the 5x5 block's hits.  These three go through
+ * hrt_denoise_filter_variance's passes, on LINEAR radiance (the other modes filter the encoded buffer: the moments are linear), and
+ * d_out receives colorToFloat4 of the result.  Parameters as for hrt_denoise_filter_variance (NULL: the defaults), with the same
+ * refusals.  HRT_ERR_INVALID also for a NULL d_sum, d_taken, d_guides or d_out, for d_out or d_linear_out equal to d_sum, and for
+ * d_linear_out equal to d_out; a refused call writes nothing.  The sums, the totals, the caller's guides and the RNG states are never
+ * written; neither is the temporal history read or forgotten: a still between two frames of a sequence leaves it alone.
+ * Enqueued only.
+ * ... over caller-given guides (no scene needed): the encoded result -> d_out, the filtered linear frame -> d_linear_out (may be
+ * NULL), the filtered variance -> d_var_out (may be NULL) */
+int  hrt_denoise_accumulated_filter(HrtContext *ctx, const HrtFloat4 *d_sum, const uint32_t *d_taken, const HrtDenoiseGuide *d_guides,
+                                    HrtFloat4 *d_out, HrtFloat4 *d_linear_out, float *d_var_out, uint32_t width, uint32_t height,
+                                    const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams, void *stream);
+/* ... over the guides of the frame h_raygen describes (traced, or the primary capture where it is the hits of exactly these rays, as
+ * in hrt_denoise_launch; HRT_ERR_STATE as there) into d_out, which may be h_raygen->colorBuffer: the colour buffer is not read, and
+ * not written unless it is d_out. */
+int  hrt_denoise_accumulated_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen,
+                                    const HrtFloat4 *d_sum, const uint32_t *d_taken, const HrtDenoiseParams *h_dparams,
+                                    const HrtDenoiseVarianceParams *h_vparams, HrtFloat4 *d_out, void *stream);
 
 /* ---- measurement (no reference counterpart: the reference has no timers) ------------- */
 enum { HRT_K_GENERATE = 0, HRT_K_TRAVERSE, HRT_K_TRAVERSE_ANY, HRT_K_BIN, HRT_K_SHADE,

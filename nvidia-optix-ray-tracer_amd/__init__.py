@@ -137,6 +137,7 @@ EXPORTS = [
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
     "hrt_denoise_temporal_rebind", "hrt_denoise_temporal_rebind_geometry",
     "hrt_denoise_variance_default_params", "hrt_denoise_filter_variance", "hrt_denoise_variance_launch", "hrt_debug_denoise_variance_state",
+    "hrt_denoise_accumulated_filter", "hrt_denoise_accumulated_launch",
     "hrt_render_accumulate", "hrt_sample_counts_default_params", "hrt_sample_counts",
 ]
 
@@ -222,6 +223,10 @@ def load_library():
     lib.hrt_denoise_variance_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.POINTER(DenoiseParams),
                                                 C.POINTER(DenoiseTemporalParams), C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p]
     lib.hrt_debug_denoise_variance_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hrt_denoise_accumulated_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceParams), C.c_void_p]
+    lib.hrt_denoise_accumulated_launch.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_void_p, C.c_void_p,
+                                                   C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceParams), C.c_void_p, C.c_void_p]
     lib.hrt_render_accumulate.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(RayGenParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(Tile), C.c_void_p]
     lib.hrt_sample_counts_default_params.argtypes = [C.POINTER(SampleCountParams)]

@@ -313,6 +313,15 @@ struct DenoiseVarianceArgs {
     uint32_t width, height;
     float history_min;                                       // L below it: the spatial estimate
 };
+// the accumulated mode (denoise_accum.hip; DESIGN.md 3e "Accumulated mode"): hrt_render_accumulate's sums and totals and the frame's
+// guides -> the linear mean, the variance of that mean and the guides the filter takes (a pixel without a sample: background)
+struct DenoiseAccumArgs {
+    const float4 *sum; const uint32_t *taken; const uint4 *guides;
+    float4 *mean; float *variance; uint4 *guides_out;        // (guides_out is not guides: a young pixel's taps read their neighbours' depths)
+    uint32_t width, height;
+    uint32_t believed;                                       // max(history_min, 2): a hit with fewer samples takes the 5x5 estimate
+};
+void launch_denoise_accumulated(const DenoiseAccumArgs &a, hipStream_t s);     // denoise_accum.hip
 void launch_denoise_variance(const DenoiseVarianceArgs &a, hipStream_t s);
 void launch_denoise_temporal(const DenoiseTemporalArgs &a, hipStream_t s);
 void launch_denoise_temporal_linked(const DenoiseTemporalLinkedArgs &a, hipStream_t s);      // denoise_link.hip

@@ -3,6 +3,7 @@
 // path kernel in the context's configuration, flattened and two-level trees alike), their hits turned into HrtDenoiseGuide records with
 // the material tables of the launch.  Filter: `iterations` a-trous passes, one launch each, ping-ponging between two frames the context
 // owns; the variance-guided filter is the same path (pass_constants, run_filter) with a variance frame ping-ponged next to the colour.
+// The accumulated mode (accumulated_filter) feeds that filter from hrt_render_accumulate's sums and encodes what it returns.
 // The temporal and the variance-guided mode share the reprojection step (run_temporal), the history and everything around their filter
 // (temporal_launch).  Every call only enqueues work (the material tables' upload after hrt_materials_set synchronises once, as in
 // hrt_render_launch).
@@ -117,8 +118,9 @@ int pass_constants(HrtContext *ctx, const HrtDenoiseParams *h_dparams, const Hrt
 }
 
 // variance == NULL: the plain filter.  Else a variance frame goes through the passes next to the colour, and into var_out if given.
+// out == NULL (with `last`): the result stays in the context's frame the last pass wrote, which *last receives.
 int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, const float *variance, float4 *out, float *var_out,
-               uint32_t width, uint32_t height, std::vector<DenoisePassArgs> &passes, hipStream_t s) {
+               uint32_t width, uint32_t height, std::vector<DenoisePassArgs> &passes, hipStream_t s, const float4 **last = nullptr) {
     int rc = ensure_work(ctx, width * height, variance ? kFilterVariance : kFilter);
     if (rc != HRT_OK) return rc;
     const float4 *src = color;
@@ -135,7 +137,8 @@ int run_filter(HrtContext *ctx, const float4 *color, const uint4 *guides, const 
         launch_denoise_pass(a, s);
         src = dst; vsrc = vdst;
     }
-    if (src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
+    if (last) *last = src;
+    if (out && src != out) HIP_TRY(ctx, hipMemcpyAsync(out, src, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
     if (var_out && vsrc != var_out) HIP_TRY(ctx, hipMemcpyAsync(var_out, vsrc, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToDevice, s));
     HIP_TRY(ctx, hipGetLastError());
     return HRT_OK;
@@ -176,6 +179,43 @@ int run_guides(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGen
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_tlas = h_params->handle;
     return HRT_OK;
+}
+
+// hrt_denoise_accumulated_filter, and hrt_denoise_accumulated_launch after its guide pass: sums, totals and guides -> mean, variance of
+// the mean and guides' (k_denoise_accumulated), the variance-guided filter over them, colorToFloat4 of its result.  The mean and its
+// variance go into the frames the first pass reads and the second writes (frame[1], var[1]), guides' into the context's guide buffer;
+// `guides` is the caller's, or the launch's in frame[0], which the first pass overwrites once the kernel has read it.
+int accumulated_filter(HrtContext *ctx, const float4 *sum, const uint32_t *taken, const uint4 *guides, float4 *out, float4 *linear_out,
+                       float *var_out, uint32_t width, uint32_t height, const HrtDenoiseVarianceParams &vp,
+                       std::vector<DenoisePassArgs> &passes, hipStream_t s) {
+    const uint32_t n = width * height;
+    int rc = ensure_work(ctx, n, kFilterVariance);
+    if (rc == HRT_OK) rc = ensure_work(ctx, n, kTrace);
+    if (rc != HRT_OK) return rc;
+    DenoiseWork &d = ctx->denoise;
+    DenoiseAccumArgs aa{};
+    aa.sum = sum; aa.taken = taken; aa.guides = guides;
+    aa.mean = d.frame[1]; aa.variance = d.var[1]; aa.guides_out = d.guides;
+    aa.width = width; aa.height = height; aa.believed = std::max(vp.history_min, 2u);
+    launch_denoise_accumulated(aa, s);
+    const float4 *filtered = nullptr;
+    rc = run_filter(ctx, d.frame[1], d.guides, d.var[1], linear_out, var_out, width, height, passes, s, &filtered);
+    if (rc != HRT_OK) return rc;
+    launch_color_to_float4(linear_out ? linear_out : filtered, out, n, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
+}
+
+// what both accumulated calls check before anything is enqueued (the context and the host pointers are the caller's to have checked)
+int accumulated_checks(HrtContext *ctx, const void *d_sum, const void *d_taken, const void *d_out, const void *d_linear_out,
+                       uint32_t width, uint32_t height, const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams &vp,
+                       std::vector<DenoisePassArgs> &passes) {
+    if (!d_sum || !d_taken || !d_out) return fail(ctx, HRT_ERR_INVALID, "accumulated denoise: d_sum, d_taken or d_out is NULL");
+    if (d_out == d_sum || d_linear_out == d_sum) return fail(ctx, HRT_ERR_INVALID, "accumulated denoise: the sums are not written: d_out and d_linear_out must not be d_sum");
+    if (d_linear_out && d_linear_out == d_out) return fail(ctx, HRT_ERR_INVALID, "accumulated denoise: d_linear_out is d_out");
+    int rc = check_frame(ctx, width, height);
+    if (rc == HRT_OK) rc = pass_constants(ctx, h_dparams, &vp, passes);
+    return rc;
 }
 
 // the temporal parameters (NULL: the defaults); HRT_ERR_INVALID when one is out of range
@@ -489,6 +529,41 @@ int hrt_denoise_variance_launch(HrtContext *ctx, const HrtGlobalParams *h_params
                                 void *stream) {
     const HrtDenoiseVarianceParams vp = variance_params(h_vparams);
     return temporal_launch(ctx, h_params, h_raygen, h_dparams, h_tparams, &vp, d_out, stream);
+}
+
+int hrt_denoise_accumulated_filter(HrtContext *ctx, const HrtFloat4 *d_sum, const uint32_t *d_taken, const HrtDenoiseGuide *d_guides,
+                                   HrtFloat4 *d_out, HrtFloat4 *d_linear_out, float *d_var_out, uint32_t width, uint32_t height,
+                                   const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    if (!d_guides) return fail(ctx, HRT_ERR_INVALID, "accumulated denoise: d_guides is NULL");
+    std::vector<DenoisePassArgs> passes;
+    const HrtDenoiseVarianceParams vp = variance_params(h_vparams);
+    int rc = accumulated_checks(ctx, d_sum, d_taken, d_out, d_linear_out, width, height, h_dparams, vp, passes);
+    if (rc != HRT_OK) return rc;
+    return accumulated_filter(ctx, reinterpret_cast<const float4 *>(d_sum), d_taken, reinterpret_cast<const uint4 *>(d_guides),
+                              reinterpret_cast<float4 *>(d_out), reinterpret_cast<float4 *>(d_linear_out), d_var_out, width, height, vp,
+                              passes, (hipStream_t)stream);
+}
+
+int hrt_denoise_accumulated_launch(HrtContext *ctx, const HrtGlobalParams *h_params, const HrtRayGenParams *h_raygen, const HrtFloat4 *d_sum,
+                                   const uint32_t *d_taken, const HrtDenoiseParams *h_dparams, const HrtDenoiseVarianceParams *h_vparams,
+                                   HrtFloat4 *d_out, void *stream) {
+    if (!ctx || !h_params || !h_raygen) return HRT_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    const uint32_t width = h_raygen->width, height = h_raygen->height;
+    std::vector<DenoisePassArgs> passes;
+    const HrtDenoiseVarianceParams vp = variance_params(h_vparams);
+    int rc = accumulated_checks(ctx, d_sum, d_taken, d_out, nullptr, width, height, h_dparams, vp, passes);
+    // the frames first: the guides of this frame go into one of them (accumulated_filter), which a larger frame would free again
+    if (rc == HRT_OK) rc = ensure_work(ctx, width * height, kFilterVariance);
+    if (rc != HRT_OK) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    uint4 *guides = reinterpret_cast<uint4 *>(ctx->denoise.frame[0]);
+    rc = run_guides(ctx, h_params, h_raygen, guides, s);
+    if (rc != HRT_OK) return rc;
+    return accumulated_filter(ctx, reinterpret_cast<const float4 *>(d_sum), d_taken, guides, reinterpret_cast<float4 *>(d_out), nullptr, nullptr,
+                              width, height, vp, passes, s);
 }
 
 int hrt_debug_denoise_variance_state(HrtContext *ctx, float *d_moments, float *d_variance, void *stream) {

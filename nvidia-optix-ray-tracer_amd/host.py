@@ -569,6 +569,48 @@ class Renderer:
         self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
         return moments, variance
 
+    def denoise_accumulated_filter(self, sum4, taken, guides, params=None, vparams=None, out=None, linear_out=None, var_out=None):
+        """The accumulated mode over given guides: ``sum4`` (H, W, 4) float32 and ``taken`` (H, W) int32 as accumulate() leaves them,
+        ``guides`` (H, W, 8) 16-bit -> (encoded colour, filtered linear frame, filtered variance): new tensors, or ``out``,
+        ``linear_out`` and ``var_out`` (False for either of the last two: not returned).  The filter runs on the linear mean sum / taken
+        with the variance of that mean as its edge stop; a pixel with taken == 0 is background.  params, vparams as for
+        denoise_filter_variance."""
+        torch = self._torch
+        h, w = int(sum4.shape[0]), int(sum4.shape[1])
+        assert sum4.is_contiguous() and tuple(sum4.shape) == (h, w, 4) and sum4.dtype == torch.float32
+        assert taken.is_contiguous() and tuple(taken.shape) == (h, w) and taken.dtype == torch.int32
+        assert guides.is_contiguous() and tuple(guides.shape) == (h, w, 8) and guides.element_size() == 2
+        out = torch.empty_like(sum4) if out is None else out
+        if linear_out is None:
+            linear_out = torch.empty_like(sum4)
+        if var_out is None:
+            var_out = torch.empty((h, w), dtype=torch.float32, device=sum4.device)
+        from . import DenoiseParams, DenoiseVarianceParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
+        vp = self._params(DenoiseVarianceParams, "hrt_denoise_variance_default_params", vparams)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_accumulated_filter(self.ctx, sum4.data_ptr(), taken.data_ptr(), guides.data_ptr(), out.data_ptr(),
+                                                            linear_out.data_ptr() if linear_out is not False else None,
+                                                            var_out.data_ptr() if var_out is not False else None, w, h, _ref(p), _ref(vp), st),
+                    "hrt_denoise_accumulated_filter")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return out, (linear_out if linear_out is not False else None), (var_out if var_out is not False else None)
+
+    def denoise_accumulated(self, params=None, vparams=None, out=None):
+        """The accumulated mode of denoiseOutput, for a still that accumulate() / render_adaptive() has sampled: the guides of the
+        current frame + the variance-guided filter of ``self.sum`` / ``self.taken`` on linear radiance, encoded -> a new (H, W, 4) float32
+        tensor, or ``out`` (which may be ``self.color``).  Needs no history and leaves denoise_temporal's and denoise_variance's alone."""
+        params_blk, rg = self._launch_blocks()
+        out = self._torch.empty_like(self.color) if out is None else out
+        from . import DenoiseParams, DenoiseVarianceParams
+        p = self._params(DenoiseParams, "hrt_denoise_default_params", params)
+        vp = self._params(DenoiseVarianceParams, "hrt_denoise_variance_default_params", vparams)
+        st = self._stream()
+        self._check(self.lib.hrt_denoise_accumulated_launch(self.ctx, C.byref(params_blk), C.byref(rg), self.sum.data_ptr(), self.taken.data_ptr(),
+                                                            _ref(p), _ref(vp), out.data_ptr(), st), "hrt_denoise_accumulated_launch")
+        self._check(self.lib.hrt_sync(self.ctx, st), "hrt_sync")
+        return out
+
     def to_rgba8_of(self, frame):
         """convertFloat4ToUchar4Kernel of any (H, W, 4) float32 device tensor (to_rgba8: of the colour buffer)."""
         torch = self._torch
