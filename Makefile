@@ -33,6 +33,10 @@ $(LIBDIR)/build_split.o: $(CSRC)/build_split.hip $(CSRC)/build.h $(CSRC)/build_d
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(LIBDIR)/build_reinsert.o: $(CSRC)/build_reinsert.hip $(CSRC)/build.h $(CSRC)/build_dev.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(LIBDIR)/refit.o: $(CSRC)/refit.hip $(CSRC)/device_types.h $(CSRC)/bvh8_geom.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -84,7 +88,7 @@ $(LIBDIR)/bvh8_host_api.o: $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h include/hrt.
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o refit.o pose.o denoise.o denoise_accum.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
+OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o build_reinsert.o refit.o pose.o denoise.o denoise_accum.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
 $(LIBDIR)/libhrt.so: $(PATH_OBJS) $(OTHER_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 	@cat $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc $(CSRC)/*.hpp $(CSRC)/*.cpp include/*.h)) | sha256sum | cut -c1-16 > $(LIBDIR)/BUILD_ID

@@ -101,6 +101,9 @@ struct GpuBuildInput {
     // gpu_build_max_refs(n_prims, split) entries
     SplitParams split;
     float *out_clip = nullptr;                           // 6 floats per record (split builds)
+    // fast-trace builds: rounds of the reinsertion pass over the finished BVH2 (build_reinsert.hip; 0: none), and the depth the path kernels
+    // take -- a tree the pass made deeper than that is built again without it
+    int reinsert_rounds = 0; uint32_t reinsert_max_depth = 0xffffffffu;
 };
 
 struct GpuBuildResult {
@@ -109,6 +112,8 @@ struct GpuBuildResult {
     uint32_t n_records = 0;                              // primitive records emitted (= n_prims without spatial splits)
     uint32_t split_levels = 0, n_cells = 0;
     bool fell_back = false;                              // the top-down phase gave up and PLOC alone built the tree
+    uint32_t reinsert_moved = 0;                         // moves the reinsertion pass made
+    bool reinsert_dropped = false;                       // the pass made the tree too deep: this is the tree without it
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     std::vector<uint32_t> level_begin;                   // nodes of level l: [level_begin[l], level_begin[l + 1])
 };
@@ -119,6 +124,8 @@ size_t gpu_split_table_bytes(uint32_t n_prims, const SplitParams &split);       
 uint32_t gpu_build_max_refs(uint32_t n_prims, const SplitParams *split);                    // most records / nodes a build can emit
 // build_split.hip: references of the valid primitives (pb_lo / pb_hi of `a`, scene bounds in a.counters) cut top-down into cells
 SplitPhaseResult gpu_split_phase(const GpuBuildArgs &a, uint32_t n_valid, const SplitParams &sp, BuildArena &arena, hipStream_t s);
+// build_reinsert.hip: rounds of the reinsertion pass over the finished BVH2 of `a` (nodes [0, n_nodes)); boxes, counts and cost tables are current afterwards
+hipError_t gpu_reinsert_bvh2(const GpuBuildArgs &a, uint32_t n_nodes, uint32_t root, int rounds, BuildArena &arena, hipStream_t s, bool verbose, uint32_t *moved, const char **where);
 constexpr size_t kBoundsScratchBytes = 512;           // ... of gpu_blas_bounds
 hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, float *lo, float *hi, void *d_scratch, hipStream_t s);
 // bounding sphere of a BLAS around `center` (radius < 0: none)

@@ -12,6 +12,8 @@
 //      merged surface area within +-2 positions) when the choice is mutual -- a BVH2 of near-SAH quality in ~40 rounds,
 //      every round a handful of O(n) launches; node numbers come from prefix sums, so the BVH2 is deterministic.  The last rounds
 //      (4096 clusters or fewer: all rounds of a small build) are one workgroup's, a barrier where the others have a launch;
+//   3a. fast-trace builds: the reinsertion pass over the finished BVH2 (build_reinsert.hip; HRT_REINSERT rounds), which recomputes the boxes,
+//      the reference counts and the cost tables of every inner node;
 //   4. the optimal SAH collapse to 8-wide nodes (Ylitie, Karras, Laine 2017, sec. 4.1: the same cost tables as the host
 //      builder bvh8_build.cpp): a node's table is computed where the node is made (its children are from earlier rounds);
 //   5. emission of the packed BVH8 breadth first, one launch per level (a small build: one workgroup for all levels), eight lanes
@@ -94,59 +96,7 @@ __global__ __launch_bounds__(256) void k_morton(GpuBuildArgs a) {
     a.keys[k] = key; a.vals[k] = k;
 }
 
-// ---- optimal collapse: cost tables (bvh8_build.cpp, same recurrences) ----
-// table of a node: c[1..7] as floats in t[1..7]; t[0] bits: leaf1 | use_dist[i] << i (i = 2..7) | split[j] << (8 + 3 (j - 2)) (j = 2..8)
-struct CostRow { float c[8]; };
-__device__ __forceinline__ uint32_t row_bits(const CostRow &r) { return __float_as_uint(r.c[0]); }
-__device__ __forceinline__ uint32_t row_split(uint32_t bits, int j) { return (bits >> (8 + 3 * (j - 2))) & 7u; }
-
-__device__ __forceinline__ float node_half_area(const float4 lo, const float4 hi) {
-    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-    return dx * dy + dy * dz + dz * dx;
-}
-
-__device__ void cost_of_node(const GpuBuildArgs &a, uint32_t nd, bool leaf, CostRow &out) {
-    const float kInf = INFINITY;
-    // (a box without area -- coinciding points, a line of them -- still costs a visit: with zero everywhere the tables tie and the tree comes out
-    // nearly binary, 15 levels for 5000 points; any positive area leaves everything else as it was)
-    const float area = fmaxf(node_half_area(a.node_lo[nd], a.node_hi[nd]), 1e-30f);
-    const uint32_t np = a.node_nprims[nd];
-    const float c_leaf = np <= a.max_leaf_prims ? area * a.c_prim * (float)np : kInf;
-    if (leaf) {
-        for (int i = 1; i <= 7; ++i) out.c[i] = c_leaf;
-        out.c[0] = __uint_as_float(1u);
-        return;
-    }
-    const uint32_t l = __float_as_uint(a.node_lo[nd].w), r = __float_as_uint(a.node_hi[nd].w);
-    CostRow cl, cr;
-    {   // the children's rows: written by an earlier launch
-        const float4 *pl = reinterpret_cast<const float4 *>(a.cost + 8 * (size_t)l), *pr = reinterpret_cast<const float4 *>(a.cost + 8 * (size_t)r);
-        const float4 l0 = pl[0], l1 = pl[1], r0 = pr[0], r1 = pr[1];
-        cl.c[0] = l0.x; cl.c[1] = l0.y; cl.c[2] = l0.z; cl.c[3] = l0.w; cl.c[4] = l1.x; cl.c[5] = l1.y; cl.c[6] = l1.z; cl.c[7] = l1.w;
-        cr.c[0] = r0.x; cr.c[1] = r0.y; cr.c[2] = r0.z; cr.c[3] = r0.w; cr.c[4] = r1.x; cr.c[5] = r1.y; cr.c[6] = r1.z; cr.c[7] = r1.w;
-    }
-    float dist[9]; uint32_t bits = 0u;
-    for (int j = 2; j <= 8; ++j) {
-        float best = kInf; int bk = 1;
-        for (int k = 1; k < j; ++k) {
-            const float v = cl.c[k < 7 ? k : 7] + cr.c[(j - k) < 7 ? (j - k) : 7];
-            if (v < best) { best = v; bk = k; }
-        }
-        dist[j] = best; bits |= (uint32_t)bk << (8 + 3 * (j - 2));
-    }
-    const float c_internal = dist[a.width] + area * a.c_node;      // (a.width children at most: 8, or fewer as an experiment -- HRT_BVH_WIDTH)
-    if (c_leaf <= c_internal) bits |= 1u;
-    out.c[1] = fminf(c_leaf, c_internal);
-    for (int i = 2; i <= 7; ++i) {
-        if (dist[i] < out.c[i - 1]) { out.c[i] = dist[i]; bits |= 1u << i; } else out.c[i] = out.c[i - 1];
-    }
-    out.c[0] = __uint_as_float(bits);
-}
-
-__device__ __forceinline__ void store_row(const GpuBuildArgs &a, uint32_t nd, const CostRow &r) {
-    float4 *p = reinterpret_cast<float4 *>(a.cost + 8 * (size_t)nd);
-    p[0] = make_float4(r.c[0], r.c[1], r.c[2], r.c[3]); p[1] = make_float4(r.c[4], r.c[5], r.c[6], r.c[7]);
-}
+// (the cost tables of the optimal collapse -- CostRow, cost_of_node, store_row -- are in build_dev.h: build_reinsert.hip recomputes them)
 
 // builds with spatial splits: the sort key of a reference is its cell, then the Morton code of its centroid within the cell's
 // centroid bounds (10 bits an axis: cells are small) -- the references of a cell stay together and PLOC works cell by cell
@@ -750,7 +700,7 @@ size_t gpu_build_scratch_bytes(uint32_t n_prims, const SplitParams *split) {
 
 // The build.  in: instance tables + output buffers sized for the worst case (one node and one record per leaf).  Synchronises `s`
 // a few dozen times for a counter each (split levels, PLOC rounds, levels); no geometry crosses the bus.
-GpuBuildResult gpu_build_bvh8(const GpuBuildInput &in, hipStream_t s) {
+static GpuBuildResult build_once(const GpuBuildInput &in, hipStream_t s) {
     GpuBuildResult res{};
     const uint32_t n = in.n_prims;
     GpuBuildArgs a{};
@@ -832,7 +782,7 @@ GpuBuildResult gpu_build_bvh8(const GpuBuildInput &in, hipStream_t s) {
     else hipLaunchKernelGGL(k_morton, dim3(blocks(n, 256)), dim3(256), 0, s, a);
     B_TRY(hipGetLastError());
     B_TRY(hipcub::DeviceRadixSort::SortPairs(temp, sort_bytes, a.keys, keys_out, a.vals, a.vals_sorted, (int)ns, 0, 64, s));
-    if (!split && n <= small_limit) {
+    if (!split && n <= small_limit && in.reinsert_rounds <= 0) {
         // ---- a small build (the reference's own scenes: a few thousand triangles): every PLOC round and every level of the emission in
         //      one workgroup each, and the host looks at the counters once, at the end ----
         hipLaunchKernelGGL(k_leaves, dim3(blocks(n, 256)), dim3(256), 0, s, a, kNone);
@@ -919,6 +869,13 @@ GpuBuildResult gpu_build_bvh8(const GpuBuildInput &in, hipStream_t s) {
             if (cnt) hipLaunchKernelGGL(k_cost_range, dim3(blocks(cnt, 256)), dim3(256), 0, s, a, node_base + b0, cnt, 0u);
         }
     B_TRY(hipGetLastError());
+    // ---- fast-trace builds: the reinsertion pass over the finished BVH2 (build_reinsert.hip), which leaves boxes, counts and tables current ----
+    // (not where the top-down phase gave up: that build is PLOC's tree, node for node)
+    if (in.reinsert_rounds > 0 && !res.fell_back) {
+        const uint32_t n2 = node_base + (split ? sp.n_top : 0u);
+        res.error = gpu_reinsert_bvh2(a, n2, root, in.reinsert_rounds, arena, s, in.split.verbose, &res.reinsert_moved, &res.where);
+        if (res.error != hipSuccess) goto done;
+    }
     // ---- emission, level by level ----
     {
         const uint2 first = make_uint2(root, 0u);
@@ -945,6 +902,23 @@ GpuBuildResult gpu_build_bvh8(const GpuBuildInput &in, hipStream_t s) {
     B_TRY(hipGetLastError());
     B_TRY(hipStreamSynchronize(s));
 done:
+    return res;
+}
+
+GpuBuildResult gpu_build_bvh8(const GpuBuildInput &in, hipStream_t s) {
+    GpuBuildResult res = build_once(in, s);
+    // A tree deeper than the path kernels take after the reinsertion pass: was it the pass?  The build without it says (the output buffers
+    // hold one tree at a time): where that tree is less deep it stays, otherwise the tree with the pass is built once more.
+    if (res.error == hipSuccess && in.reinsert_rounds > 0 && res.reinsert_moved != 0u && res.max_depth > in.reinsert_max_depth) {
+        GpuBuildInput plain = in; plain.reinsert_rounds = 0;
+        const uint32_t with_pass = res.max_depth;
+        res = build_once(plain, s);
+        if (res.error != hipSuccess) return res;
+        if (res.max_depth < with_pass) {
+            if (in.split.verbose) std::fprintf(stderr, "[hrt] device build: %u levels deep after the reinsertion pass, %u without (the path kernels take %u): the tree without it stays\n", with_pass, res.max_depth, in.reinsert_max_depth);
+            res.reinsert_dropped = true;
+        } else res = build_once(in, s);
+    }
     return res;
 }
 

@@ -53,6 +53,11 @@ struct alignas(16) PrimRecord {
 static_assert(sizeof(PrimRecord) == 48, "primitive record is 48 bytes");
 
 constexpr uint32_t kMaxLeafPrims = 3;      // unary count in 3 bits
+// fast-trace builds, both builders: rounds of the reinsertion pass over the finished BVH2 at most (HRT_REINSERT); the rounds end once one
+// moves fewer than 1 / kReinsertStopShare of the nodes (C4: the host's sequential pass after 4 rounds, the device's, which puts off the moves
+// that cross each other's paths, after 7)
+constexpr int kReinsertRounds = 8;
+constexpr uint32_t kReinsertStopShare = 256;
 constexpr uint32_t kPrimKindTriangle = 0, kPrimKindSphere = 1;
 constexpr uint32_t kPrimKindInstance = 2;      // builder input only: the "primitive" is an instance's BLAS box (the top level of a two-level tree)
 

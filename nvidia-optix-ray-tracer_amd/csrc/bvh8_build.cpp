@@ -5,6 +5,7 @@
 //   1. binned-SAH BVH2 over padded primitive bounds (16 bins x 3 axes) down to single primitives,
 //      big subtrees built on worker threads (topology does not depend on thread timing), optionally with
 //      spatial splits (SBVH: references cut by planes where that is cheaper, for static scenes);
+//   1a. fast-trace builds: an insertion-based optimisation of that BVH2 (Reinsert below; HRT_REINSERT rounds);
 //   2. optimal SAH collapse to 8-wide nodes by dynamic programming (Ylitie, Karras, Laine 2017,
 //      sec. 4.1): C(n, i) = cheapest way to represent subtree n as a forest of at most i roots,
 //      c_node = 1, c_prim = 0.45, leaves <= 3 primitives.  (A first greedy version -- always open
@@ -261,6 +262,85 @@ struct Builder {
     }
 };
 
+// Insertion-based optimisation of the finished BVH2 (Bittner, Hapala, Havran 2013): per round, every node but the root and its children, in
+// order of decreasing area, is taken out (its parent goes with it, the sibling moves up) and put back -- with the freed parent as the new
+// inner node -- beside the node where the summed area of the inner nodes grows least, found by a bounded descent from the root: a position is
+// worth looking at only while the growth of its ancestors plus the node's own area stays below the best found, and the best found starts at
+// what the removal saved, so only strict improvements move.  A reference's box is its own, so the cover of every primitive is unchanged.
+struct Reinsert {
+    std::vector<B2> &N; const uint32_t n;
+    std::vector<uint32_t> parent;
+    uint64_t moved = 0, searched = 0;
+    struct Item { uint32_t node; double ind; };
+    std::vector<Item> stack;
+
+    Reinsert(std::vector<B2> &nodes, uint32_t count) : N(nodes), n(count), parent(count, 0xffffffffu) {
+        for (uint32_t i = 0; i < n; ++i) if (N[i].count == 0) { parent[N[i].left] = i; parent[N[i].right] = i; }
+    }
+    static double area(const B2 &b) { return (double)half_area(b.lo, b.hi); }
+    static double area_with(const B2 &a, const B2 &b) {
+        float lo[3], hi[3];
+        for (int c = 0; c < 3; ++c) { lo[c] = std::min(a.lo[c], b.lo[c]); hi[c] = std::max(a.hi[c], b.hi[c]); }
+        return (double)half_area(lo, hi);
+    }
+    void refit(uint32_t a) {
+        B2 &x = N[a]; const B2 &l = N[x.left], &r = N[x.right];
+        for (int c = 0; c < 3; ++c) { x.lo[c] = std::min(l.lo[c], r.lo[c]); x.hi[c] = std::max(l.hi[c], r.hi[c]); }
+        x.nprims = l.nprims + r.nprims; x.first = l.first;
+    }
+    void refit_chain(uint32_t a) { for (;; a = parent[a]) { refit(a); if (a == 0) break; } }
+    void replace_child(uint32_t p, uint32_t from, uint32_t to) { if (N[p].left == from) N[p].left = to; else N[p].right = to; parent[to] = p; }
+    double inner_area() const { double s = 0.0; for (uint32_t i = 0; i < n; ++i) if (N[i].count == 0) s += area(N[i]); return s; }
+
+    bool try_move(uint32_t x) {
+        const uint32_t p = parent[x];
+        if (x == 0 || p == 0) return false;
+        const uint32_t g = parent[p], s = N[p].left == x ? N[p].right : N[p].left;
+        // take x and p out: s moves up; what that saves is the budget
+        replace_child(g, p, s);
+        double gain = area(N[p]);
+        for (uint32_t a = g;; a = parent[a]) { const double before = area(N[a]); refit(a); gain += before - area(N[a]); if (a == 0) break; }
+        const B2 &X = N[x];
+        const double ax = area(X);
+        double best = gain; uint32_t best_y = 0xffffffffu;
+        stack.clear(); stack.push_back({0u, 0.0});
+        while (!stack.empty()) {
+            const Item it = stack.back(); stack.pop_back();
+            if (!(it.ind + ax < best)) continue;
+            ++searched;
+            const B2 &Y = N[it.node];
+            const double direct = area_with(Y, X), total = it.ind + direct;
+            if (it.node != 0 && total < best) { best = total; best_y = it.node; }
+            if (Y.count > 0) continue;
+            const double child_ind = total - area(Y);
+            if (!(child_ind + ax < best)) continue;
+            // the nearer child (smaller union) is looked at first: pushed last
+            const double dl = area_with(N[Y.left], X), dr = area_with(N[Y.right], X);
+            if (dl <= dr) { stack.push_back({Y.right, child_ind}); stack.push_back({Y.left, child_ind}); }
+            else { stack.push_back({Y.left, child_ind}); stack.push_back({Y.right, child_ind}); }
+        }
+        if (best_y == 0xffffffffu || best_y == s) {      // nowhere better: back to where it was
+            replace_child(g, s, p); N[p].left = s; N[p].right = x; parent[s] = p; parent[x] = p;
+            refit_chain(p);
+            return false;
+        }
+        const uint32_t q = parent[best_y];
+        replace_child(q, best_y, p);
+        N[p].left = best_y; N[p].right = x; parent[best_y] = p; parent[x] = p;
+        refit_chain(p);
+        ++moved;
+        return true;
+    }
+
+    void round() {
+        std::vector<uint32_t> order; order.reserve(n);
+        std::vector<float> key(n);
+        for (uint32_t i = 0; i < n; ++i) { key[i] = half_area(N[i].lo, N[i].hi); if (i != 0 && parent[i] != 0) order.push_back(i); }
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] != key[b] ? key[a] > key[b] : a < b; });
+        for (uint32_t x : order) try_move(x);
+    }
+};
+
 inline uint8_t unary_count(uint32_t n) { return (uint8_t)((1u << n) - 1u); }
 
 // cost table of a BVH2 node for the optimal collapse: c[i] = cheapest representation of the subtree as a forest of at most i roots, i = 1..7;
@@ -269,7 +349,10 @@ struct Cost { float c[8]; uint8_t leaf1; uint8_t use_dist[8]; uint8_t split[9]; 
 
 }  // namespace
 
-void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, float scene_scale, uint32_t max_leaf_prims, bool spatial_splits) {
+// reinsert_rounds: rounds of the reinsertion pass over the BVH2; returns the moves it made
+static uint64_t build_bvh8_with(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, float scene_scale, uint32_t max_leaf_prims, bool spatial_splits, int reinsert_rounds) {
+    uint64_t reinsert_moved = 0;
+    const bool verbose = std::getenv("HRT_BUILD_VERBOSE") != nullptr;
     max_leaf_prims = std::min(std::max(max_leaf_prims, 1u), kMaxLeafPrims);
     out = Bvh8();
     const uint32_t n = (uint32_t)prims.size();
@@ -282,7 +365,7 @@ void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, flo
         out.nodes.push_back(root);
         out.level_begin = {0u, 1u};
         out.node_box.assign(6, 0.0f);
-        return;
+        return 0;
     }
 
     Builder B(prims);
@@ -325,6 +408,26 @@ void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, flo
     while ((1 << B.max_par_depth) < hw && B.max_par_depth < 10) B.max_par_depth++;      // (a fork per node down to this depth: at most hw subtree tasks alive)
     const auto t_begin = std::chrono::steady_clock::now();
     B.build(0, std::move(refs), 0, extra);
+    {
+        const int rounds = reinsert_rounds;
+        if (rounds > 0 && B.nodes[0].count == 0) {
+            Reinsert R(B.nodes, B.n_nodes.load());
+            double before = R.inner_area();
+            for (int r = 0; r < rounds; ++r) {
+                const auto t0 = std::chrono::steady_clock::now();
+                const uint64_t m0 = R.moved, s0 = R.searched;
+                R.round();
+                const double after = R.inner_area();
+                if (verbose)
+                    std::fprintf(stderr, "[hrt] host build: reinsertion round %d: %llu of %u nodes moved, %llu positions looked at, inner area %.9g -> %.9g (%.2f %%), %.2f s\n", r + 1,
+                                 (unsigned long long)(R.moved - m0), R.n, (unsigned long long)(R.searched - s0), before, after, 100.0 * (after / before - 1.0),
+                                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                before = after;
+                if (R.moved - m0 < R.n / kReinsertStopShare) break;
+            }
+            reinsert_moved = R.moved;
+        }
+    }
     const auto t_bvh2 = std::chrono::steady_clock::now();
 
     for (int a = 0; a < 3; ++a) { out.lo[a] = B.nodes[0].lo[a]; out.hi[a] = B.nodes[0].hi[a]; }
@@ -525,9 +628,9 @@ void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, flo
         if (!level.empty()) ++depth;
     }
     out.level_begin.push_back((uint32_t)out.nodes.size());
-    if (std::getenv("HRT_BUILD_VERBOSE")) {
+    if (verbose) {
         const auto t_end = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[hrt] host build: %u primitives -> %zu references, %zu nodes (%s): BVH2 %.3f s on up to %d threads, collapse + emission %.3f s\n", n, out.prims.size(), out.nodes.size(),
+        std::fprintf(stderr, "[hrt] host build: %u primitives -> %zu references, %zu nodes, depth %u (%s): BVH2 %.3f s on up to %d threads, collapse + emission %.3f s\n", n, out.prims.size(), out.nodes.size(), out.max_depth,
                      B.spatial ? "spatial splits" : "object splits only", std::chrono::duration<double>(t_bvh2 - t_begin).count(), hw, std::chrono::duration<double>(t_end - t_bvh2).count());
     }
 
@@ -552,6 +655,27 @@ void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, flo
         if (ar > 0.0f && std::isfinite(ar)) { total += below[i]; out.node_ref[2 * i + 1] = 1.0f / ar; } else below[i] = 0.0;
     }
     for (size_t i = 0; i < nn; ++i) out.node_ref[2 * i] = total > 0.0 ? (float)(below[i] / total) : 0.0f;
+    return reinsert_moved;
+}
+
+void build_bvh8(const std::vector<BuildPrim> &prims, Bvh8 &out, int threads, float scene_scale, uint32_t max_leaf_prims, bool spatial_splits) {
+    // fast-trace builds (the caller asked for spatial splits) get kReinsertRounds rounds of the reinsertion pass; HRT_REINSERT sets the
+    // number for every build of full leaves (0: none)
+    const bool full_leaves = std::min(std::max(max_leaf_prims, 1u), kMaxLeafPrims) == kMaxLeafPrims;
+    int rounds = spatial_splits && full_leaves ? kReinsertRounds : 0;
+    if (const char *e = std::getenv("HRT_REINSERT")) { const int v = std::atoi(e); if (v >= 0 && v <= 64 && full_leaves) rounds = v; }
+    const uint64_t moved = build_bvh8_with(prims, out, threads, scene_scale, max_leaf_prims, spatial_splits, rounds);
+    // the path kernels take trees of at most kHostFusedMaxDepth levels below the root: where the pass made the tree deeper than it would
+    // have been and deeper than that, the tree without the pass stays
+    constexpr uint32_t kHostFusedMaxDepth = 12;      // device_types.h: kFusedMaxDepth
+    if (moved != 0 && out.max_depth > kHostFusedMaxDepth) {
+        Bvh8 plain;
+        build_bvh8_with(prims, plain, threads, scene_scale, max_leaf_prims, spatial_splits, 0);
+        if (plain.max_depth < out.max_depth) {
+            if (std::getenv("HRT_BUILD_VERBOSE")) std::fprintf(stderr, "[hrt] host build: %u levels deep after the reinsertion pass, %u without: the tree without it stays\n", out.max_depth, plain.max_depth);
+            out = std::move(plain);
+        }
+    }
 }
 
 // ---- tree over instances -------------------------------------------------------------------------------------

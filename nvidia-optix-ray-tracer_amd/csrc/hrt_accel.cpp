@@ -544,13 +544,15 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     in.out_prims = device_split ? lay.at<unsigned char>(o_prims) : static_cast<unsigned char *>(d.d_prims); in.prim_stride = t.prim_stride;
     in.out_clip = device_split ? lay.at<float>(o_clip) : nullptr;
     in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
+    // a fast-trace build: the reinsertion pass over the finished BVH2 (not where the top-down phase gives up and PLOC alone builds the tree: build.hip)
+    if (device_split) { in.reinsert_rounds = ctx->reinsert_rounds; in.reinsert_max_depth = (uint32_t)ctx->fused_max_depth; }
     GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
     // A tree deeper than any kernel's stack (a chain of primitives over many orders of magnitude: nearest-neighbour clustering, like SAH, takes
     // one off the rest at every level): built again by position -- every cluster with its Morton neighbour, log2(n) levels, whatever the areas
     // (a split build too: the tree by position has no splits, its records are the primitives -- the staged buffers hold them all the same)
     if (r.error == hipSuccess && r.n_prims != 0u && too_deep(r.max_depth)) {
         if (ctx->build_verbose) std::fprintf(stderr, "[hrt] the tree is %u levels deep: built again by position\n", r.max_depth);
-        in.balanced = true; in.split.enabled = false;
+        in.balanced = true; in.split.enabled = false; in.reinsert_rounds = 0;
         r = gpu_build_bvh8(in, s);
     }
     if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build failed: %s (%s)", hipGetErrorString(r.error), r.where);
