@@ -25,15 +25,11 @@ $(PATH_OBJS): $(LIBDIR)/%.o: $(CSRC)/%.hip $(PATH_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/build.o: $(CSRC)/build.hip $(CSRC)/build.h $(CSRC)/build_dev.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/build_split.o: $(CSRC)/build_split.hip $(CSRC)/build.h $(CSRC)/build_dev.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/build_reinsert.o: $(CSRC)/build_reinsert.hip $(CSRC)/build.h $(CSRC)/build_dev.h $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h
+# the device builder: one translation unit per phase over the shared headers (bvh8_collapse.h: the collapse, shared with the host builder)
+BUILD_UNITS := build build_split build_reinsert
+BUILD_HDRS  := $(addprefix $(CSRC)/,build.h build_dev.h bvh8.h bvh8_geom.h bvh8_collapse.h)
+BUILD_OBJS  := $(BUILD_UNITS:%=$(LIBDIR)/%.o)
+$(BUILD_OBJS): $(LIBDIR)/%.o: $(CSRC)/%.hip $(BUILD_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -80,7 +76,7 @@ $(LIBDIR)/hrt_denoise.o: $(CSRC)/hrt_denoise.cpp $(API_DEPS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBDIR)/bvh8_build.o: $(CSRC)/bvh8_build.cpp $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h
+$(LIBDIR)/bvh8_build.o: $(CSRC)/bvh8_build.cpp $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h $(CSRC)/bvh8_collapse.h
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
@@ -88,7 +84,7 @@ $(LIBDIR)/bvh8_host_api.o: $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h include/hrt.
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-OTHER_OBJS := $(addprefix $(LIBDIR)/,build.o build_split.o build_reinsert.o refit.o pose.o denoise.o denoise_accum.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
+OTHER_OBJS := $(BUILD_OBJS) $(addprefix $(LIBDIR)/,refit.o pose.o denoise.o denoise_accum.o denoise_link.o denoise_link_prim.o hrt_api.o hrt_denoise.o hrt_accel.o hrt_mem.o bvh8_build.o bvh8_host_api.o)
 $(LIBDIR)/libhrt.so: $(PATH_OBJS) $(OTHER_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 	@cat $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc $(CSRC)/*.hpp $(CSRC)/*.cpp include/*.h)) | sha256sum | cut -c1-16 > $(LIBDIR)/BUILD_ID
@@ -148,7 +144,7 @@ asan: $(ASAN_DIR)/libhrt_io.so $(ASAN_DIR)/libhrt_host_bvh.so $(ASAN_DIR)/libora
 $(ASAN_DIR)/libhrt_io.so: $(CSRC)/host/scene_io.cpp $(CSRC)/host/json_min.hpp $(CSRC)/cr_trig.h $(CSRC)/srgb_pow.h include/hrt_io.h include/hrt_params.h
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) $(ASAN_FLAGS) -shared -o $@ $<
-$(ASAN_DIR)/libhrt_host_bvh.so: $(CSRC)/bvh8_build.cpp $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h include/hrt.h
+$(ASAN_DIR)/libhrt_host_bvh.so: $(CSRC)/bvh8_build.cpp $(CSRC)/bvh8_host_api.cpp $(CSRC)/bvh8.h $(CSRC)/bvh8_geom.h $(CSRC)/bvh8_collapse.h include/hrt.h
 	@mkdir -p $(ASAN_DIR)
 	$(CXX) $(ASAN_FLAGS) -DHRT_HOST_ONLY -shared -o $@ $(CSRC)/bvh8_build.cpp $(CSRC)/bvh8_host_api.cpp
 $(ASAN_DIR)/liboracle.so: oracle/oracle.c

@@ -14,11 +14,11 @@
 //      (4096 clusters or fewer: all rounds of a small build) are one workgroup's, a barrier where the others have a launch;
 //   3a. fast-trace builds: the reinsertion pass over the finished BVH2 (build_reinsert.hip; HRT_REINSERT rounds), which recomputes the boxes,
 //      the reference counts and the cost tables of every inner node;
-//   4. the optimal SAH collapse to 8-wide nodes (Ylitie, Karras, Laine 2017, sec. 4.1: the same cost tables as the host
-//      builder bvh8_build.cpp): a node's table is computed where the node is made (its children are from earlier rounds);
+//   4. the optimal SAH collapse to 8-wide nodes (bvh8_collapse.h: the code the host builder bvh8_build.cpp runs): a node's cost
+//      table is computed where the node is made (its children are from earlier rounds);
 //   5. emission of the packed BVH8 breadth first, one launch per level (a small build: one workgroup for all levels), eight lanes
-//      per node: forest roots from the tables, octant slot assignment, child / primitive blocks from atomic cursors -- topology
-//      and primitive ids only;
+//      per node: forest roots from the tables and octant slot assignment (bvh8_collapse.h again), child / primitive blocks from
+//      atomic cursors -- topology and primitive ids only;
 //   6. the refit kernels (refit.hip) then compute every world-space record, box, origin, exponent and quantised child box
 //      bottom-up, exactly as they do after an instance update: one arithmetic for build and refit.
 // The result does not depend on the tree: hits are defined by the canonical intersector over conservative boxes.
@@ -74,6 +74,20 @@ __device__ __forceinline__ uint64_t spread21(uint64_t x) {      // bit i -> bit 
     return x;
 }
 
+// Morton code of a box's centroid within the centroid bounds [cm, cx], `top` + 1 steps an axis (top = 2^bits - 1)
+__device__ __forceinline__ uint64_t morton_of_centroid(const float4 lo, const float4 hi, const float *cm, const float *cx, uint32_t top) {
+    const float ce[3] = {0.5f * (lo.x + hi.x), 0.5f * (lo.y + hi.y), 0.5f * (lo.z + hi.z)};
+    uint64_t q[3];
+    for (int d = 0; d < 3; ++d) {
+        const float ext = cx[d] - cm[d];
+        float t = ext > 0.0f ? (ce[d] - cm[d]) / ext : 0.0f;
+        t = fminf(fmaxf(t, 0.0f), 1.0f);
+        const uint32_t v = (uint32_t)(t * (float)top);
+        q[d] = v > top ? top : v;
+    }
+    return (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+}
+
 __global__ __launch_bounds__(256) void k_morton(GpuBuildArgs a) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= a.n) return;
@@ -82,21 +96,10 @@ __global__ __launch_bounds__(256) void k_morton(GpuBuildArgs a) {
     if (lo.w != 0.0f) {
         const float cm[3] = {ord2f(a.counters->cmin[0]), ord2f(a.counters->cmin[1]), ord2f(a.counters->cmin[2])};
         const float cx[3] = {ord2f(a.counters->cmax[0]), ord2f(a.counters->cmax[1]), ord2f(a.counters->cmax[2])};
-        const float ce[3] = {0.5f * (lo.x + hi.x), 0.5f * (lo.y + hi.y), 0.5f * (lo.z + hi.z)};
-        uint64_t q[3];
-        for (int d = 0; d < 3; ++d) {
-            const float ext = cx[d] - cm[d];
-            float t = ext > 0.0f ? (ce[d] - cm[d]) / ext : 0.0f;
-            t = fminf(fmaxf(t, 0.0f), 1.0f);
-            const uint32_t v = (uint32_t)(t * 2097151.0f);
-            q[d] = v > 2097151u ? 2097151u : v;
-        }
-        key = (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+        key = morton_of_centroid(lo, hi, cm, cx, 2097151u);      // 21 bits an axis
     }
     a.keys[k] = key; a.vals[k] = k;
 }
-
-// (the cost tables of the optimal collapse -- CostRow, cost_of_node, store_row -- are in build_dev.h: build_reinsert.hip recomputes them)
 
 // builds with spatial splits: the sort key of a reference is its cell, then the Morton code of its centroid within the cell's
 // centroid bounds (10 bits an axis: cells are small) -- the references of a cell stay together and PLOC works cell by cell
@@ -106,18 +109,18 @@ __global__ __launch_bounds__(256) void k_morton_refs(GpuBuildArgs a, uint32_t n_
     const float4 lo = a.ref_lo[i], hi = a.ref_hi[i];
     const uint32_t cell = __float_as_uint(hi.w);
     const SplitSeg &sg = segs[cell_seg[cell]];
-    const float ce[3] = {0.5f * (lo.x + hi.x), 0.5f * (lo.y + hi.y), 0.5f * (lo.z + hi.z)};
-    uint64_t q[3];
-    for (int d = 0; d < 3; ++d) {
-        const float cm = ord2f(sg.cb[d]), cx = -ord2f(sg.cb[3 + d]);
-        const float ext = cx - cm;
-        float t = ext > 0.0f ? (ce[d] - cm) / ext : 0.0f;
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
-        const uint32_t v = (uint32_t)(t * 1023.0f);
-        q[d] = v > 1023u ? 1023u : v;
-    }
-    a.keys[i] = ((uint64_t)cell << 30) | (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+    const float cm[3] = {ord2f(sg.cb[0]), ord2f(sg.cb[1]), ord2f(sg.cb[2])}, cx[3] = {-ord2f(sg.cb[3]), -ord2f(sg.cb[4]), -ord2f(sg.cb[5])};
+    a.keys[i] = ((uint64_t)cell << 30) | morton_of_centroid(lo, hi, cm, cx, 1023u);
     a.vals[i] = i;
+}
+
+// BVH2 node i: lo.xyz | left, hi.xyz | right.  Leaf: left = kNone, right = global primitive number (`prim`: its bits); cluster i of PLOC
+__device__ __forceinline__ void write_leaf(const GpuBuildArgs &a, uint32_t i, const float4 lo, const float4 hi, float prim) {
+    a.node_lo[i] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(kNone));
+    a.node_hi[i] = make_float4(hi.x, hi.y, hi.z, prim);
+    a.node_nprims[i] = 1u;
+    a.cl_a[i] = i;
+    CostRow row; cost_of_node(a, i, true, row); store_row(a, i, row);
 }
 
 __global__ __launch_bounds__(256) void k_leaves_refs(GpuBuildArgs a, uint32_t n_refs) {
@@ -125,12 +128,8 @@ __global__ __launch_bounds__(256) void k_leaves_refs(GpuBuildArgs a, uint32_t n_
     if (i >= n_refs) return;
     const uint32_t r = a.vals_sorted[i];
     const float4 lo = a.ref_lo[r], hi = a.ref_hi[r];
-    a.node_lo[i] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(kNone));
-    a.node_hi[i] = make_float4(hi.x, hi.y, hi.z, lo.w);
     a.node_cell[i] = __float_as_uint(hi.w);
-    a.node_nprims[i] = 1u;
-    a.cl_a[i] = i;
-    CostRow row; cost_of_node(a, i, true, row); store_row(a, i, row);
+    write_leaf(a, i, lo, hi, lo.w);
 }
 
 // the segments the top-down phase split are the top of the BVH2: node top_base + t for top node t, children = top nodes or the
@@ -151,7 +150,6 @@ __global__ __launch_bounds__(256) void k_top_link(GpuBuildArgs a, const SplitSeg
     a.node_nprims[id] = sg.count;
 }
 
-// BVH2 node i: lo.xyz | left, hi.xyz | right.  Leaf: left = kNone, right = global primitive number.
 // (nv = kNone: a small build, which does not stop for the host to learn the number of valid primitives -- taken from the counters, and
 // the PLOC counters are set here)
 __global__ __launch_bounds__(256) void k_leaves(GpuBuildArgs a, uint32_t nv_host) {
@@ -160,18 +158,42 @@ __global__ __launch_bounds__(256) void k_leaves(GpuBuildArgs a, uint32_t nv_host
     if (i == 0u && nv_host == kNone) { BuildCounters *c = a.counters; c->m_cur = nv; c->m_next = nv; c->node_base = nv; c->merges = 0u; }
     if (i >= nv) return;
     const uint32_t k = a.vals_sorted[i];
-    const float4 lo = a.pb_lo[k], hi = a.pb_hi[k];
-    a.node_lo[i] = make_float4(lo.x, lo.y, lo.z, __uint_as_float(kNone));
-    a.node_hi[i] = make_float4(hi.x, hi.y, hi.z, __uint_as_float(k));
-    a.node_nprims[i] = 1u;
-    a.cl_a[i] = i;
-    CostRow row; cost_of_node(a, i, true, row); store_row(a, i, row);
+    write_leaf(a, i, a.pb_lo[k], a.pb_hi[k], __uint_as_float(k));
 }
 
 __device__ __forceinline__ float merged_half_area(const float4 alo, const float4 ahi, const float4 blo, const float4 bhi) {
     const float ex = fmaxf(ahi.x, bhi.x) - fminf(alo.x, blo.x), ey = fmaxf(ahi.y, bhi.y) - fminf(alo.y, blo.y),
                 ez = fmaxf(ahi.z, bhi.z) - fminf(alo.z, blo.z);
     return ex * ey + ey * ez + ez * ex;
+}
+
+// ---- one PLOC round, step by step: the launch-per-round kernels and k_ploc_small below differ in how they move the data (LDS tiles and a
+//      device-wide scan; global memory and a block-wide scan), not in these ----
+// Is position j, at merged area ar, a better neighbour for position i than bj at `best`?  Strict <: the first (lowest) position wins ties --
+// except that position i ^ 1 beats any other of the same area: among thousands of coinciding primitives every cluster would otherwise choose
+// the lowest position in reach, one pair a round would be mutual and the tree a chain (6000 copies of a triangle: depth 860); with the
+// pairing rule they halve every round.  NaN areas still pick something
+__device__ __forceinline__ bool ploc_better(float ar, uint32_t j, float best, uint32_t bj, uint32_t i) {
+    return ar < best || bj == kNone || (ar == best && j == (i ^ 1u));
+}
+// the neighbour position i ends up with (balanced builds: by position, the clusters halve every round)
+__device__ __forceinline__ uint32_t ploc_neighbour(const GpuBuildArgs &a, uint32_t i, uint32_t m, uint32_t bj) {
+    return a.balanced ? ((i ^ 1u) < m ? (i ^ 1u) : kNone) : bj;
+}
+// per position: valid << 32 | starts-a-merge (a mutual pair: its lower position merges, its upper one goes); j = the neighbour i chose
+__device__ __forceinline__ uint64_t ploc_flag(const GpuBuildArgs &a, uint32_t i, uint32_t &j) {
+    j = a.nn[i];
+    const bool mutual = j != kNone && a.nn[j] == i;
+    return !mutual ? 1ull << 32 : i < j ? ((1ull << 32) | 1ull) : 0ull;
+}
+// clusters l and r become BVH2 node id (their tables: earlier rounds')
+__device__ __forceinline__ void ploc_merge(const GpuBuildArgs &a, uint32_t l, uint32_t r, uint32_t id) {
+    const float4 llo = a.node_lo[l], lhi = a.node_hi[l], rlo = a.node_lo[r], rhi = a.node_hi[r];
+    a.node_lo[id] = make_float4(fminf(llo.x, rlo.x), fminf(llo.y, rlo.y), fminf(llo.z, rlo.z), __uint_as_float(l));
+    a.node_hi[id] = make_float4(fmaxf(lhi.x, rhi.x), fmaxf(lhi.y, rhi.y), fmaxf(lhi.z, rhi.z), __uint_as_float(r));
+    a.node_nprims[id] = a.node_nprims[l] + a.node_nprims[r];
+    if (a.node_cell) a.node_cell[id] = a.node_cell[l];
+    CostRow row; cost_of_node(a, id, false, row); store_row(a, id, row);
 }
 
 // nearest neighbour of every cluster within +-ploc_radius positions (ties: the lower position)
@@ -199,25 +221,16 @@ __global__ __launch_bounds__(256) void k_ploc_nn(GpuBuildArgs a, const uint32_t 
         const int j = (int)i + d;
         if (d == 0 || j < 0 || j >= (int)m || s_cell[me + d] != my_cell) continue;
         const float ar = merged_half_area(mlo, mhi, s_lo[me + d], s_hi[me + d]);
-        // strict <: the first (lowest) position wins ties -- except that position i ^ 1 beats any other of the same area: among thousands of
-        // coinciding primitives every cluster would otherwise choose the lowest position in reach, one pair a round would be mutual and the
-        // tree a chain (6000 copies of a triangle: depth 860); with the pairing rule they halve every round.  NaN areas still pick something
-        if (ar < best || bj == kNone || (ar == best && (uint32_t)j == (i ^ 1u))) { best = ar; bj = (uint32_t)j; }
+        if (ploc_better(ar, (uint32_t)j, best, bj, i)) { best = ar; bj = (uint32_t)j; }
     }
-    if (a.balanced) bj = (i ^ 1u) < m ? (i ^ 1u) : kNone;      // by position: the clusters halve every round
-    a.nn[i] = bj;
+    a.nn[i] = ploc_neighbour(a, i, m, bj);
 }
 
-// per position: valid << 32 | starts-a-merge
 __global__ __launch_bounds__(256) void k_ploc_flags(GpuBuildArgs a, uint32_t m_bound) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const uint32_t m = a.counters->m_cur;
     if (i >= m) { if (i < m_bound) a.flags[i] = 0ull; return; }      // (the scan runs over the bound)
-    const uint32_t j = a.nn[i];
-    const bool mutual = j != kNone && a.nn[j] == i;
-    uint64_t f = 1ull << 32;
-    if (mutual) f = i < j ? ((1ull << 32) | 1ull) : 0ull;
-    a.flags[i] = f;
+    uint32_t j; a.flags[i] = ploc_flag(a, i, j);
 }
 
 __global__ __launch_bounds__(256) void k_ploc_apply(GpuBuildArgs a, const uint32_t *__restrict__ cl_in, uint32_t *__restrict__ cl_out) {
@@ -229,19 +242,14 @@ __global__ __launch_bounds__(256) void k_ploc_apply(GpuBuildArgs a, const uint32
     if ((f >> 32) == 0ull) return;
     const uint32_t pos = (uint32_t)(sc >> 32);
     if ((f & 1ull) == 0ull) { cl_out[pos] = cl_in[i]; return; }
-    const uint32_t l = cl_in[i], r = cl_in[a.nn[i]], id = node_base + (uint32_t)(sc & 0xffffffffu);
-    const float4 llo = a.node_lo[l], lhi = a.node_hi[l], rlo = a.node_lo[r], rhi = a.node_hi[r];
-    a.node_lo[id] = make_float4(fminf(llo.x, rlo.x), fminf(llo.y, rlo.y), fminf(llo.z, rlo.z), __uint_as_float(l));
-    a.node_hi[id] = make_float4(fmaxf(lhi.x, rhi.x), fmaxf(lhi.y, rhi.y), fmaxf(lhi.z, rhi.z), __uint_as_float(r));
-    a.node_nprims[id] = a.node_nprims[l] + a.node_nprims[r];
-    if (a.node_cell) a.node_cell[id] = a.node_cell[l];
+    const uint32_t id = node_base + (uint32_t)(sc & 0xffffffffu);
     cl_out[pos] = id;
-    CostRow row; cost_of_node(a, id, false, row); store_row(a, id, row);       // (the children's tables: earlier rounds')
+    ploc_merge(a, cl_in[i], cl_in[a.nn[i]], id);
 }
 
 // Few clusters (the whole of a small build, the last dozen rounds of a large one): ONE workgroup runs every remaining round, a barrier
-// where the large build has a launch -- a round of six launches costs 30 us of host time whatever its size.  Same arithmetic and the
-// same tie rules as k_ploc_nn / _flags / _apply, so a build is the same tree whichever kernels ran its rounds.
+// where the large build has a launch -- a round of six launches costs 30 us of host time whatever its size.  The round's steps are the
+// functions above, so a build is the same tree whichever kernels ran its rounds.
 constexpr uint32_t kSmallClusters = 16384u;                     // (what k_ploc_small can take; the host hands it 4096 at most)
 __global__ __launch_bounds__(1024) void k_ploc_small(GpuBuildArgs a, uint32_t *cl_a, uint32_t *cl_b, uint32_t n_cells) {
     typedef hipcub::BlockScan<uint64_t, 1024> Scan;
@@ -264,38 +272,26 @@ __global__ __launch_bounds__(1024) void k_ploc_small(GpuBuildArgs a, uint32_t *c
                 const uint32_t o = cin[j];
                 if (a.node_cell && a.node_cell[o] != my_cell) continue;
                 const float ar = merged_half_area(mlo, mhi, a.node_lo[o], a.node_hi[o]);
-                if (ar < best || bj == kNone || (ar == best && (uint32_t)j == (i ^ 1u))) { best = ar; bj = (uint32_t)j; }      // (k_ploc_nn's rule)
+                if (ploc_better(ar, (uint32_t)j, best, bj, i)) { best = ar; bj = (uint32_t)j; }
             }
-            if (a.balanced) bj = (i ^ 1u) < m ? (i ^ 1u) : kNone;
-            a.nn[i] = bj;
+            a.nn[i] = ploc_neighbour(a, i, m, bj);
         }
         __syncthreads();
         // flags, scan (tiles of 1024 clusters, the running totals carried from tile to tile), apply
         uint64_t run = 0ull;
         for (uint32_t base = 0; base < m; base += 1024u) {
             const uint32_t i = base + threadIdx.x;
-            uint64_t f = 0ull, e, total;
-            uint32_t j = kNone;
-            if (i < m) {
-                j = a.nn[i];
-                const bool mutual = j != kNone && a.nn[j] == i;
-                f = 1ull << 32;
-                if (mutual) f = i < j ? ((1ull << 32) | 1ull) : 0ull;
-            }
+            uint64_t e, total; uint32_t j = kNone;
+            const uint64_t f = i < m ? ploc_flag(a, i, j) : 0ull;
             Scan(tmp).ExclusiveSum(f, e, total);
             __syncthreads();
             e += run; run += total;
             if (i >= m || (f >> 32) == 0ull) continue;
             const uint32_t pos = (uint32_t)(e >> 32);
             if ((f & 1ull) == 0ull) { cout[pos] = cin[i]; continue; }
-            const uint32_t l = cin[i], r = cin[j], id = node_base + (uint32_t)(e & 0xffffffffu);
-            const float4 llo = a.node_lo[l], lhi = a.node_hi[l], rlo = a.node_lo[r], rhi = a.node_hi[r];
-            a.node_lo[id] = make_float4(fminf(llo.x, rlo.x), fminf(llo.y, rlo.y), fminf(llo.z, rlo.z), __uint_as_float(l));
-            a.node_hi[id] = make_float4(fmaxf(lhi.x, rhi.x), fmaxf(lhi.y, rhi.y), fmaxf(lhi.z, rhi.z), __uint_as_float(r));
-            a.node_nprims[id] = a.node_nprims[l] + a.node_nprims[r];
-            if (a.node_cell) a.node_cell[id] = a.node_cell[l];
+            const uint32_t id = node_base + (uint32_t)(e & 0xffffffffu);
             cout[pos] = id;
-            CostRow row; cost_of_node(a, id, false, row); store_row(a, id, row);
+            ploc_merge(a, cin[i], cin[j], id);
         }
         __threadfence_block();
         __syncthreads();
@@ -320,33 +316,17 @@ __global__ void k_ploc_advance(GpuBuildArgs a) {
 __global__ __launch_bounds__(256) void k_cost_range(GpuBuildArgs a, uint32_t first, uint32_t count, uint32_t leaf) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
-    CostRow row;
-    cost_of_node(a, first + i, leaf != 0u, row);
-    store_row(a, first + i, row);
+    CostRow row; cost_of_node(a, first + i, leaf != 0u, row); store_row(a, first + i, row);
 }
 
 // ---- emission of one BVH8 level ----
 struct Forest { uint32_t node[8]; int n; };
-__device__ void collect_forest(const GpuBuildArgs &a, uint32_t root, Forest &out) {
-    // Collector::distribute(root, 8) of bvh8_build.cpp, iteratively: (node, budget) pairs on a small stack; right pushed first
-    uint32_t st_node[16]; int st_budget[16]; bool st_open[16]; int sp = 0;
-    out.n = 0;
-    st_node[sp] = root; st_budget[sp] = (int)a.width; st_open[sp] = true; ++sp;
-    while (sp > 0) {
-        --sp;
-        const uint32_t x = st_node[sp]; int i = st_budget[sp]; const bool open = st_open[sp];
-        const uint32_t bits = __float_as_uint(a.cost[8 * (size_t)x]);
-        const bool leaf2 = __float_as_uint(a.node_lo[x].w) == kNone;
-        if (!open) {                                            // forest(x, i)
-            while (i > 1 && !((bits >> i) & 1u)) --i;
-            if (i == 1 || leaf2) { out.node[out.n++] = x; continue; }
-        }
-        const int k = (int)row_split(bits, i);                   // distribute(x, i)
-        const uint32_t l = __float_as_uint(a.node_lo[x].w), r = __float_as_uint(a.node_hi[x].w);
-        st_node[sp] = r; st_budget[sp] = (i - k) < 7 ? (i - k) : 7; st_open[sp] = false; ++sp;
-        st_node[sp] = l; st_budget[sp] = k < 7 ? k : 7; st_open[sp] = false; ++sp;
-    }
-}
+struct DeviceTree {                                              // the BVH2 and its tables, as collect_forest (bvh8_collapse.h) asks for them
+    const GpuBuildArgs &a;
+    __device__ uint32_t bits(uint32_t x) const { return __float_as_uint(a.cost[8 * (size_t)x]); }
+    __device__ bool leaf(uint32_t x) const { return __float_as_uint(a.node_lo[x].w) == kNone; }
+    __device__ void children(uint32_t x, uint32_t &l, uint32_t &r) const { l = __float_as_uint(a.node_lo[x].w); r = __float_as_uint(a.node_hi[x].w); }
+};
 
 // the <= 3 references of a leaf child: its little BVH2 subtree, in order
 __device__ __forceinline__ int leaf_refs(const GpuBuildArgs &a, uint32_t c, uint32_t *gk, uint32_t *leaf) {
@@ -388,7 +368,8 @@ __device__ void emit_item(const GpuBuildArgs &a, uint32_t b2, uint32_t self, uin
         if (node_is_leaf2 || (is_root_level && a.node_nprims[b2] <= a.max_leaf_prims)) {
             f.n = 1; f.node[0] = b2; ch_leaf[0] = true;              // the whole scene fits one leaf: wrap it
         } else {
-            collect_forest(a, b2, f);
+            const DeviceTree tree{a};
+            f.n = collect_forest(tree, b2, (int)a.width, f.node);
             // The children's boxes are stored on THIS node's 8-bit grid (step ~ extent / 255 per axis).  Where one child dwarfs the others --
             // an outlier far from the rest of the scene, a huge ground sphere beside small particles -- the small children's stored boxes are
             // blown up by the grid's step and every ray that enters the node visits most of them.  Such a node keeps its two BVH2 children
@@ -409,39 +390,16 @@ __device__ void emit_item(const GpuBuildArgs &a, uint32_t b2, uint32_t self, uin
                     f.n = 2; f.node[0] = __float_as_uint(nlo.w); f.node[1] = __float_as_uint(nhi.w);
                 }
             }
-            for (int k = 0; k < f.n; ++k) {
-                const uint32_t c = f.node[k];
-                ch_leaf[k] = __float_as_uint(a.node_lo[c].w) == kNone || (__float_as_uint(a.cost[8 * (size_t)c]) & 1u);
-            }
+            for (int k = 0; k < f.n; ++k) ch_leaf[k] = tree.leaf(f.node[k]) || row_leaf1(tree.bits(f.node[k]));
         }
-        // slot assignment: slot s is visited first by rays of octant s (bit2 = -x, bit1 = -y, bit0 = -z): greedy, as the host builder
-        float cost[8][8];
+        // the children's octant slots (bvh8_collapse.h), from their centres' offsets
+        float d[8][3];
         const float ncx[3] = {0.5f * (nlo.x + nhi.x), 0.5f * (nlo.y + nhi.y), 0.5f * (nlo.z + nhi.z)};
         for (int k = 0; k < f.n; ++k) {
             const float4 lo = a.node_lo[f.node[k]], hi = a.node_hi[f.node[k]];
-            const float d[3] = {0.5f * (lo.x + hi.x) - ncx[0], 0.5f * (lo.y + hi.y) - ncx[1], 0.5f * (lo.z + hi.z) - ncx[2]};
-            for (int q = 0; q < 8; ++q) {
-                const float sx = (q & 4) ? -1.0f : 1.0f, sy = (q & 2) ? -1.0f : 1.0f, sz = (q & 1) ? -1.0f : 1.0f;
-                cost[k][q] = d[0] * sx + d[1] * sy + d[2] * sz;
-            }
+            d[k][0] = 0.5f * (lo.x + hi.x) - ncx[0]; d[k][1] = 0.5f * (lo.y + hi.y) - ncx[1]; d[k][2] = 0.5f * (lo.z + hi.z) - ncx[2];
         }
-        bool child_done[8];
-        for (int q = 0; q < 8; ++q) child_done[q] = false;
-        for (int round = 0; round < f.n; ++round) {
-            int bk = -1, bs = -1; float bc = INFINITY;
-            for (int k = 0; k < f.n; ++k) {
-                if (child_done[k]) continue;
-                for (int q = 0; q < 8; ++q) {
-                    if (slot_child[q] >= 0) continue;
-                    if (cost[k][q] < bc) { bc = cost[k][q]; bk = k; bs = q; }
-                }
-            }
-            if (bk < 0) {   // NaN costs (degenerate boxes): first free pair
-                for (int k = 0; k < f.n && bk < 0; ++k) if (!child_done[k]) bk = k;
-                for (int q = 0; q < 8 && bs < 0; ++q) if (slot_child[q] < 0) bs = q;
-            }
-            slot_child[bs] = bk; child_done[bk] = true;
-        }
+        assign_octant_slots(f.n, d, slot_child);
     }
     // this lane's child
     int k = -1;
@@ -639,29 +597,35 @@ __global__ __launch_bounds__(256) void k_pack_spheres(const float *centers, cons
     out[4 * (size_t)p + 2] = centers[3 * (size_t)p + 2]; out[4 * (size_t)p + 3] = radii[p];
 }
 
-#define B_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { res.error = _e; res.where = #expr; goto done; } } while (0)
-
 }  // namespace
 
 void launch_pack_spheres(const float *centers, const float *radii, uint32_t n, float *out, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_pack_spheres, dim3(blocks(n, 256)), dim3(256), 0, s, centers, radii, n, out);
 }
 
-// object-space bounds of a BLAS's geometry into lo[3] / hi[3] (synchronises the stream for 24 bytes)
-hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, float *lo, float *hi, void *d_scratch, hipStream_t s) {
+// one reduction over a BLAS's geometry: the counters h go to the device (the caller's scratch, or memory of its own), launch(c) runs over
+// them, and h is what they hold afterwards (synchronises the stream)
+template <class Launch>
+static hipError_t blas_reduce(BuildCounters &h, void *d_scratch, hipStream_t s, Launch launch) {
     static_assert(sizeof(BuildCounters) <= kBoundsScratchBytes, "the counters are the only working memory");
-    for (int d = 0; d < 3; ++d) { lo[d] = INFINITY; hi[d] = -INFINITY; }
-    if (n_prims == 0) return hipSuccess;
     BuildCounters *c = reinterpret_cast<BuildCounters *>(d_scratch);
     hipError_t e = c ? hipSuccess : hipMalloc((void **)&c, sizeof(BuildCounters));
     if (e != hipSuccess) return e;
-    BuildCounters h{};
-    for (int d = 0; d < 3; ++d) { h.bmin[d] = h.cmin[d] = 0xffffffffu; h.bmax[d] = h.cmax[d] = 0u; }
     e = hipMemcpyAsync(c, &h, sizeof h, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_blas_bounds, dim3(blocks(n_prims, 1024)), dim3(1024), 0, s, d_src, n_prims, kind, c); e = hipGetLastError(); }
+    if (e == hipSuccess) { launch(c); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(&h, c, sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (!d_scratch) (void)hipFree(c);
+    return e;
+}
+
+// object-space bounds of a BLAS's geometry into lo[3] / hi[3] (synchronises the stream for 24 bytes)
+hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, float *lo, float *hi, void *d_scratch, hipStream_t s) {
+    for (int d = 0; d < 3; ++d) { lo[d] = INFINITY; hi[d] = -INFINITY; }
+    if (n_prims == 0) return hipSuccess;
+    BuildCounters h{};
+    for (int d = 0; d < 3; ++d) { h.bmin[d] = h.cmin[d] = 0xffffffffu; h.bmax[d] = h.cmax[d] = 0u; }
+    const hipError_t e = blas_reduce(h, d_scratch, s, [&](BuildCounters *c) { hipLaunchKernelGGL(k_blas_bounds, dim3(blocks(n_prims, 1024)), dim3(1024), 0, s, d_src, n_prims, kind, c); });
     if (e != hipSuccess) return e;
     if (h.bmin[0] <= h.bmax[0] && h.bmax[0] != 0u)
         for (int d = 0; d < 3; ++d) { lo[d] = ord2f(h.bmin[d]); hi[d] = ord2f(h.bmax[d]); }
@@ -671,15 +635,8 @@ hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, 
 hipError_t gpu_blas_radius(const float *d_src, uint32_t n_prims, uint32_t kind, const float *center, float *radius, void *d_scratch, hipStream_t s) {
     *radius = -1.0f;
     if (n_prims == 0) return hipSuccess;
-    BuildCounters *c = reinterpret_cast<BuildCounters *>(d_scratch);
-    hipError_t e = c ? hipSuccess : hipMalloc((void **)&c, sizeof(BuildCounters));
-    if (e != hipSuccess) return e;
     BuildCounters h{};
-    e = hipMemcpyAsync(c, &h, sizeof h, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_blas_radius, dim3(blocks(n_prims, 1024)), dim3(1024), 0, s, d_src, n_prims, kind, center[0], center[1], center[2], c); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, c, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (!d_scratch) (void)hipFree(c);
+    const hipError_t e = blas_reduce(h, d_scratch, s, [&](BuildCounters *c) { hipLaunchKernelGGL(k_blas_radius, dim3(blocks(n_prims, 1024)), dim3(1024), 0, s, d_src, n_prims, kind, center[0], center[1], center[2], c); });
     if (e != hipSuccess) return e;
     float r; memcpy(&r, &h.cmax[0], 4);
     // (the distances are rounded: a few ULPs of slack, and of the centre's coordinates)
@@ -698,139 +655,140 @@ size_t gpu_build_scratch_bytes(uint32_t n_prims, const SplitParams *split) {
     return (size_t)n_prims * 32u + cap * 32u + tables + std::max(phase, after) + (4u << 20);
 }
 
-// The build.  in: instance tables + output buffers sized for the worst case (one node and one record per leaf).  Synchronises `s`
-// a few dozen times for a counter each (split levels, PLOC rounds, levels); no geometry crosses the bus.
-static GpuBuildResult build_once(const GpuBuildInput &in, hipStream_t s) {
-    GpuBuildResult res{};
-    const uint32_t n = in.n_prims;
+namespace {
+
+// one workgroup per round beats six launches per round below a few thousand clusters (measured: 1024 .. 16384 all within 5 %; the
+// reference's 8 k-triangle sample is a little quicker through the launches and the tail: profiles/r03_device_split_build.txt)
+constexpr uint32_t kSmallLimit = 4096u;
+
+// One build: its state, and its phases in the order of the list at the top of this file.  A phase returns whether the build goes on: false
+// with res.error / res.where set, or false because the tree is finished (nothing valid to build over; the small build, which ends itself).
+struct Build {
+    const GpuBuildInput &in; hipStream_t s; GpuBuildResult &res; const uint32_t n;
     GpuBuildArgs a{};
-    void *temp = nullptr; size_t temp_bytes = 0, sort_bytes = 0, scan_bytes = 0;
-    uint64_t *keys_out = nullptr; uint32_t *cl_b = nullptr; uint2 *items_a = nullptr, *items_b = nullptr;
-    BuildCounters h{};
-    uint32_t nv = 0, nl = 0, ns = 0, m = 0, node_base = 0, root = 0, n_cells = 1;
-    bool split = false, small_tail = false;
-    // one workgroup per round beats six launches per round below a few thousand clusters (measured: 1024 .. 16384 all within 5 %; the
-    // reference's 8 k-triangle sample is a little quicker through the launches and the tail: profiles/r03_device_split_build.txt)
-    const uint32_t small_limit = 4096u;
-    SplitPhaseResult sp{};
     // working memory comes out of the caller's arena while it lasts (a small build otherwise spends more time in ~25 hipMalloc /
     // hipFree pairs, each of which synchronises the device, than in its kernels)
-    BuildArena arena; arena.base = in.scratch; arena.bytes = in.scratch_bytes;
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t { return arena.alloc(p, bytes); };
-
-    a.n = n; a.n_inst = in.n_inst; a.inst_first = in.d_inst_first; a.inst_kind = in.d_inst_kind; a.inst_src = in.d_inst_src;
-    a.inst_xf = in.d_inst_xf; a.inst_identity = in.d_inst_identity;
-    a.max_leaf_prims = in.max_leaf_prims; a.c_node = in.c_node; a.c_prim = in.c_prim; a.quant_guard = in.quant_guard;
-    a.instance_leaves = in.instance_leaves ? 1u : 0u;
-    a.balanced = in.balanced ? 1u : 0u;
-    a.width = in.width >= 2u && in.width <= 8u ? in.width : 8u;
-    a.ploc_radius = in.ploc_radius < 1 ? 1 : (in.ploc_radius > kPlocMaxRadius ? kPlocMaxRadius : in.ploc_radius);
-    a.out_nodes = in.out_nodes; a.node_stride = in.node_stride; a.out_prims = in.out_prims; a.prim_stride = in.prim_stride; a.out_node_ref = in.out_node_ref;
-
-    B_TRY(alloc((void **)&a.counters, sizeof(BuildCounters)));
-    B_TRY(alloc((void **)&a.pb_lo, sizeof(float4) * (size_t)n)); B_TRY(alloc((void **)&a.pb_hi, sizeof(float4) * (size_t)n));
-    for (int d = 0; d < 3; ++d) { h.bmin[d] = h.cmin[d] = 0xffffffffu; h.bmax[d] = h.cmax[d] = 0u; }
-    h.next_node = 1u;                                            // node 0 is the root
-    B_TRY(hipMemcpyAsync(a.counters, &h, sizeof h, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_prim_bounds, dim3(blocks(n, 1024)), dim3(1024), 0, s, a);
-    B_TRY(hipGetLastError());
-    // ---- spatial splits: the top-down phase turns the primitives into references grouped in cells ----
+    BuildArena arena;
+    BuildCounters h{};                                           // the host's copy of a.counters, as last read (read_counters)
+    uint32_t nv = 0, nl = 0, ns = 0, n_cells = 1;                // valid primitives, BVH2 leaves, sorted entries; cells PLOC works in
+    uint32_t node_base = 0, root = 0;                            // BVH2 nodes PLOC made (leaves included), the BVH2's root
+    bool split = false, small_tail = false; SplitPhaseResult sp{};
+    void *temp = nullptr; size_t sort_bytes = 0, scan_bytes = 0; uint64_t *keys_out = nullptr;
+    uint32_t *cl_b = nullptr, *cl_roots = nullptr; uint2 *items_a = nullptr, *items_b = nullptr;
+    Build(const GpuBuildInput &in_, hipStream_t s_, GpuBuildResult &res_) : in(in_), s(s_), res(res_), n(in_.n_prims) { arena.base = in.scratch; arena.bytes = in.scratch_bytes; }
+    bool ok(hipError_t e, const char *where) { if (e != hipSuccess) { res.error = e; res.where = where; } return e == hipSuccess; }
+    bool fail(const char *where) { return ok(hipErrorUnknown, where); }
+#define B_OK(expr) ok((expr), #expr)
+#define B_TRY(expr) do { if (!B_OK(expr)) return false; } while (0)
+    template <class T> hipError_t take(T *&p, size_t count) { return arena.alloc((void **)&p, sizeof(T) * count); }
+    bool read_counters() { return B_OK(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s)) && B_OK(hipStreamSynchronize(s)); }
+    // the counters say how many primitives are valid, and where: false when none is (nothing to hit: the caller emits the empty root)
+    bool valid_prims() {
+        res.n_prims = nv = n - h.n_invalid;
+        if (nv) for (int d = 0; d < 3; ++d) { res.lo[d] = ord2f(h.bmin[d]); res.hi[d] = ord2f(h.bmax[d]); }
+        return nv != 0;
+    }
+    // the emission is over and the counters read: what came out (with spatial splits, pieces of a primitive that met again in a leaf were emitted once)
+    bool finish(uint32_t depth) {
+        res.n_nodes = h.next_node; res.max_depth = depth; res.n_records = h.next_prim; res.level_begin.push_back(h.next_node);
+        return (split ? h.next_prim >= nv && h.next_prim <= nl : h.next_prim == nv) || fail("emitted primitive count differs from the valid count");
+    }
+    // 1. bounds of the primitives, of their centroids and of the scene
+    bool bounds() {
+        a.n = n; a.n_inst = in.n_inst; a.inst_first = in.d_inst_first; a.inst_kind = in.d_inst_kind; a.inst_src = in.d_inst_src;
+        a.inst_xf = in.d_inst_xf; a.inst_identity = in.d_inst_identity;
+        a.max_leaf_prims = in.max_leaf_prims; a.c_node = in.c_node; a.c_prim = in.c_prim; a.quant_guard = in.quant_guard;
+        a.instance_leaves = in.instance_leaves ? 1u : 0u; a.balanced = in.balanced ? 1u : 0u;
+        a.width = in.width >= 2u && in.width <= 8u ? in.width : 8u;
+        a.ploc_radius = in.ploc_radius < 1 ? 1 : (in.ploc_radius > kPlocMaxRadius ? kPlocMaxRadius : in.ploc_radius);
+        a.out_nodes = in.out_nodes; a.node_stride = in.node_stride; a.out_prims = in.out_prims; a.prim_stride = in.prim_stride; a.out_node_ref = in.out_node_ref;
+        B_TRY(take(a.counters, 1)); B_TRY(take(a.pb_lo, n)); B_TRY(take(a.pb_hi, n));
+        for (int d = 0; d < 3; ++d) { h.bmin[d] = h.cmin[d] = 0xffffffffu; h.bmax[d] = h.cmax[d] = 0u; }
+        h.next_node = 1u;                                            // node 0 is the root
+        B_TRY(hipMemcpyAsync(a.counters, &h, sizeof h, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_prim_bounds, dim3(blocks(n, 1024)), dim3(1024), 0, s, a);
+        return B_OK(hipGetLastError());
+    }
+    // 0. the top-down phase turns the primitives into references grouped in cells (spatial splits under HRT_CTX_FAST_TRACE)
     // (a few thousand primitives: the splits buy nothing a ray could notice, and the small build below is the quicker one)
-    split = in.split.enabled && (in.max_leaf_prims == kMaxLeafPrims || in.instance_leaves) && n >= std::max(in.split.cell_refs, 2u) && n > kSmallClusters / 4u;
-    if (split) {
-        B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-        B_TRY(hipStreamSynchronize(s));
-        nv = n - h.n_invalid;
-        if (nv < std::max(in.split.cell_refs, 2u)) split = false;
-    }
-    if (split) {
-        const size_t arena_mark = arena.used;
-        sp = gpu_split_phase(a, nv, in.split, arena, s);
-        if (sp.error != hipSuccess) {
-            // The top-down phase is an improvement, not a necessity: when it gives up (its tables outgrown twice, its ~120 bytes per
-            // reference of temporaries not to be had, counts that do not add up) and the stream is healthy, PLOC alone builds the tree --
-            // inside an update of a running animation that is a slower frame, not a failed one.
-            if (hipStreamSynchronize(s) != hipSuccess) { res.error = sp.error; res.where = sp.where; goto done; }
-            (void)hipGetLastError();
-            if (in.split.verbose) std::fprintf(stderr, "[hrt] device build: the top-down phase gave up (%s: %s); PLOC alone\n", sp.where, hipGetErrorString(sp.error));
-            arena.used = arena_mark;
-            split = false; sp = SplitPhaseResult{};
-            res.fell_back = true;
+    bool top_down() {
+        split = in.split.enabled && (in.max_leaf_prims == kMaxLeafPrims || in.instance_leaves) && n >= std::max(in.split.cell_refs, 2u) && n > kSmallClusters / 4u;
+        if (split) {
+            if (!read_counters()) return false;
+            nv = n - h.n_invalid;
+            if (nv < std::max(in.split.cell_refs, 2u)) split = false;
         }
+        if (split) {
+            const size_t arena_mark = arena.used;
+            sp = gpu_split_phase(a, nv, in.split, arena, s);
+            if (sp.error != hipSuccess) {
+                // The top-down phase is an improvement, not a necessity: when it gives up (its tables outgrown twice, its ~120 bytes per
+                // reference of temporaries not to be had, counts that do not add up) and the stream is healthy, PLOC alone builds the tree --
+                // inside an update of a running animation that is a slower frame, not a failed one.
+                if (hipStreamSynchronize(s) != hipSuccess) return ok(sp.error, sp.where);
+                (void)hipGetLastError();
+                if (in.split.verbose) std::fprintf(stderr, "[hrt] device build: the top-down phase gave up (%s: %s); PLOC alone\n", sp.where, hipGetErrorString(sp.error));
+                arena.used = arena_mark;
+                split = false; sp = SplitPhaseResult{};
+                res.fell_back = true;
+            } else {
+                a.ref_lo = sp.ref_lo; a.ref_hi = sp.ref_hi; a.out_clip = in.out_clip;
+                n_cells = sp.n_cells; res.split_levels = sp.levels; res.n_cells = sp.n_cells;
+            }
+        }
+        ns = split ? sp.n_refs : n;                                  // what is sorted: references, or all primitives (the invalid ones last)
+        return true;
     }
-    if (split) {
-        a.ref_lo = sp.ref_lo; a.ref_hi = sp.ref_hi; a.out_clip = in.out_clip;
-        n_cells = sp.n_cells; res.split_levels = sp.levels; res.n_cells = sp.n_cells;
+    // 2. the arrays of everything below, Morton codes, radix sort
+    bool arrays_and_sort() {
+        B_TRY(take(a.keys, ns)); B_TRY(take(keys_out, ns)); B_TRY(take(a.vals, ns)); B_TRY(take(a.vals_sorted, ns));
+        B_TRY(take(a.node_lo, 2 * (size_t)ns)); B_TRY(take(a.node_hi, 2 * (size_t)ns)); B_TRY(take(a.node_nprims, 2 * (size_t)ns));
+        if (split) B_TRY(take(a.node_cell, 2 * (size_t)ns));
+        B_TRY(take(a.cl_a, ns)); B_TRY(take(cl_b, ns)); B_TRY(take(a.nn, ns)); B_TRY(take(a.flags, ns)); B_TRY(take(a.scan, ns));
+        B_TRY(take(a.cost, 8 * 2 * (size_t)ns)); B_TRY(take(items_a, ns)); B_TRY(take(items_b, ns));
+        B_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.keys, keys_out, a.vals, a.vals_sorted, (int)ns, 0, 64, s));
+        B_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, a.scan, (int)ns, s));
+        B_TRY(arena.alloc(&temp, sort_bytes > scan_bytes ? sort_bytes : scan_bytes));
+        if (split) hipLaunchKernelGGL(k_morton_refs, dim3(blocks(ns, 256)), dim3(256), 0, s, a, ns, sp.segs, sp.cell_seg);
+        else hipLaunchKernelGGL(k_morton, dim3(blocks(n, 256)), dim3(256), 0, s, a);
+        B_TRY(hipGetLastError());
+        return B_OK(hipcub::DeviceRadixSort::SortPairs(temp, sort_bytes, a.keys, keys_out, a.vals, a.vals_sorted, (int)ns, 0, 64, s));
     }
-    ns = split ? sp.n_refs : n;                                  // what is sorted: references, or all primitives (the invalid ones last)
-    B_TRY(alloc((void **)&a.keys, sizeof(uint64_t) * (size_t)ns)); B_TRY(alloc((void **)&keys_out, sizeof(uint64_t) * (size_t)ns));
-    B_TRY(alloc((void **)&a.vals, sizeof(uint32_t) * (size_t)ns)); B_TRY(alloc((void **)&a.vals_sorted, sizeof(uint32_t) * (size_t)ns));
-    B_TRY(alloc((void **)&a.node_lo, sizeof(float4) * 2 * (size_t)ns)); B_TRY(alloc((void **)&a.node_hi, sizeof(float4) * 2 * (size_t)ns));
-    B_TRY(alloc((void **)&a.node_nprims, sizeof(uint32_t) * 2 * (size_t)ns));
-    if (split) B_TRY(alloc((void **)&a.node_cell, sizeof(uint32_t) * 2 * (size_t)ns));
-    B_TRY(alloc((void **)&a.cl_a, sizeof(uint32_t) * (size_t)ns)); B_TRY(alloc((void **)&cl_b, sizeof(uint32_t) * (size_t)ns));
-    B_TRY(alloc((void **)&a.nn, sizeof(uint32_t) * (size_t)ns));
-    B_TRY(alloc((void **)&a.flags, sizeof(uint64_t) * (size_t)ns)); B_TRY(alloc((void **)&a.scan, sizeof(uint64_t) * (size_t)ns));
-    B_TRY(alloc((void **)&a.cost, sizeof(float) * 8 * 2 * (size_t)ns));
-    B_TRY(alloc((void **)&items_a, sizeof(uint2) * (size_t)ns)); B_TRY(alloc((void **)&items_b, sizeof(uint2) * (size_t)ns));
-    B_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.keys, keys_out, a.vals, a.vals_sorted, (int)ns, 0, 64, s));
-    B_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, a.scan, (int)ns, s));
-    temp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-    B_TRY(alloc(&temp, temp_bytes));
-
-    if (split) hipLaunchKernelGGL(k_morton_refs, dim3(blocks(ns, 256)), dim3(256), 0, s, a, ns, sp.segs, sp.cell_seg);
-    else hipLaunchKernelGGL(k_morton, dim3(blocks(n, 256)), dim3(256), 0, s, a);
-    B_TRY(hipGetLastError());
-    B_TRY(hipcub::DeviceRadixSort::SortPairs(temp, sort_bytes, a.keys, keys_out, a.vals, a.vals_sorted, (int)ns, 0, 64, s));
-    if (!split && n <= small_limit && in.reinsert_rounds <= 0) {
-        // ---- a small build (the reference's own scenes: a few thousand triangles): every PLOC round and every level of the emission in
-        //      one workgroup each, and the host looks at the counters once, at the end ----
+    // 3. - 6. of a small build (the reference's own scenes: a few thousand triangles): every PLOC round and every level of the emission in one
+    // workgroup each, and the host looks at the counters once, at the end
+    bool is_small() const { return !split && n <= kSmallLimit && in.reinsert_rounds <= 0; }
+    bool small_build() {
         hipLaunchKernelGGL(k_leaves, dim3(blocks(n, 256)), dim3(256), 0, s, a, kNone);
         hipLaunchKernelGGL(k_ploc_small, dim3(1), dim3(1024), 0, s, a, a.cl_a, cl_b, 1u);
         hipLaunchKernelGGL(k_emit_small, dim3(1), dim3(1024), 0, s, a, items_a, items_b);
         hipLaunchKernelGGL(k_normalise_weights, dim3(blocks(in.instance_leaves ? 2u * n + 2u : n, 256)), dim3(256), 0, s, in.out_node_ref, kNone, a.counters);      // (a node per thread: at most n of them, with transform nodes 2 n + 1)
         B_TRY(hipGetLastError());
-        B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-        B_TRY(hipStreamSynchronize(s));
-        nv = n - h.n_invalid;
-        res.n_prims = nv;
-        if (nv == 0) goto done;
-        for (int d = 0; d < 3; ++d) { res.lo[d] = ord2f(h.bmin[d]); res.hi[d] = ord2f(h.bmax[d]); }
-        if (h.m_cur != 1u) { res.error = hipErrorUnknown; res.where = "PLOC made no progress"; goto done; }
-        if (h.n_levels == 0u || h.n_levels >= kMaxSmallLevels) { res.error = hipErrorUnknown; res.where = "small build: tree too deep"; goto done; }
-        res.ploc_rounds = h.small_rounds; res.n_nodes = h.next_node; res.max_depth = h.max_depth; res.n_records = h.next_prim;
+        if (!read_counters() || !valid_prims()) return false;
+        if (h.m_cur != 1u) return fail("PLOC made no progress");
+        if (h.n_levels == 0u || h.n_levels >= kMaxSmallLevels) return fail("small build: tree too deep");
+        res.ploc_rounds = h.small_rounds;
         for (uint32_t l = 0; l < h.n_levels; ++l) res.level_begin.push_back(h.level_begin[l]);
-        res.level_begin.push_back(h.next_node);
-        if (h.next_prim != nv) { res.error = hipErrorUnknown; res.where = "emitted primitive count differs from the valid count"; goto done; }
-        goto done;
+        return finish(h.max_depth);
     }
-    B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-    B_TRY(hipStreamSynchronize(s));
-    nv = n - h.n_invalid;
-    res.n_prims = nv;
-    if (nv == 0) goto done;                                      // nothing to hit: the caller emits the empty root
-    for (int d = 0; d < 3; ++d) { res.lo[d] = ord2f(h.bmin[d]); res.hi[d] = ord2f(h.bmax[d]); }
-    nl = split ? ns : nv;                                        // leaves of the BVH2
-
-    // ---- PLOC ----
-    if (split) hipLaunchKernelGGL(k_leaves_refs, dim3(blocks(nl, 256)), dim3(256), 0, s, a, nl);
-    else hipLaunchKernelGGL(k_leaves, dim3(blocks(nl, 256)), dim3(256), 0, s, a, nl);
-    m = nl; node_base = nl;
-    {
-        uint32_t *cl_in = a.cl_a, *cl_out = cl_b;
-        h.m_cur = m; h.node_base = node_base; h.m_next = m; h.merges = 0u;
+    // 3. PLOC: the leaves, then rounds until every cell is down to one cluster
+    bool ploc() {
+        if (!read_counters() || !valid_prims()) return false;
+        nl = split ? ns : nv;                                        // leaves of the BVH2
+        if (split) hipLaunchKernelGGL(k_leaves_refs, dim3(blocks(nl, 256)), dim3(256), 0, s, a, nl);
+        else hipLaunchKernelGGL(k_leaves, dim3(blocks(nl, 256)), dim3(256), 0, s, a, nl);
+        uint32_t m = nl, *cl_in = a.cl_a, *cl_out = cl_b;
+        h.m_cur = m; h.node_base = nl; h.m_next = m; h.merges = 0u;
         B_TRY(hipMemcpyAsync(a.counters, &h, sizeof h, hipMemcpyHostToDevice, s));
         // A round merges at least one pair, typically 40 % of the clusters.  The host launches kRoundsPerBatch rounds over the
         // cluster count it last read (a round past the end of the build copies the clusters left) and only then synchronises:
         // 6 read-backs for a million primitives instead of 44.  With cells the rounds end when every cell is down to one cluster.
         constexpr int kRoundsPerBatch = 8;
         while (m > n_cells) {
-            if (!split && m <= small_limit) {                    // the last rounds: one workgroup, one launch
+            if (!split && m <= kSmallLimit) {                        // the last rounds: one workgroup, one launch
                 hipLaunchKernelGGL(k_ploc_small, dim3(1), dim3(1024), 0, s, a, cl_in, cl_out, 1u);
                 B_TRY(hipGetLastError());
-                B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-                B_TRY(hipStreamSynchronize(s));
-                if (h.m_cur != 1u) { res.error = hipErrorUnknown; res.where = "PLOC made no progress"; goto done; }
+                if (!read_counters()) return false;
+                if (h.m_cur != 1u) return fail("PLOC made no progress");
                 res.ploc_rounds += h.small_rounds; m = 1u; root = h.root; small_tail = true;
                 break;
             }
@@ -844,64 +802,75 @@ static GpuBuildResult build_once(const GpuBuildInput &in, hipStream_t s) {
                 ++res.ploc_rounds;
             }
             B_TRY(hipGetLastError());
-            B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-            B_TRY(hipStreamSynchronize(s));
-            if (h.m_cur >= m) { res.error = hipErrorUnknown; res.where = "PLOC made no progress"; goto done; }
+            if (!read_counters()) return false;
+            if (h.m_cur >= m) return fail("PLOC made no progress");
             m = h.m_cur;
         }
-        if (m != n_cells) { res.error = hipErrorUnknown; res.where = "PLOC left fewer clusters than cells"; goto done; }
-        node_base = h.node_base;
+        if (m != n_cells) return fail("PLOC left fewer clusters than cells");
+        node_base = h.node_base; cl_roots = cl_in;
+        return true;
+    }
+    // the top of the tree: the split segments, numbered after PLOC's nodes (node_base + t; top node 0 is the root); then 4.'s cost tables of
+    // those nodes, level by level from the deepest up (the leaves' and PLOC's nodes' were computed where the nodes were made)
+    bool top_link_and_costs() {
         if (split && sp.n_top) {
-            // the top of the tree: the split segments, numbered after PLOC's nodes (node_base + t; top node 0 is the root)
-            if ((uint64_t)node_base + sp.n_top > 2ull * ns) { res.error = hipErrorUnknown; res.where = "BVH2 node count"; goto done; }
-            hipLaunchKernelGGL(k_top_link, dim3(blocks(sp.n_top, 256)), dim3(256), 0, s, a, sp.segs, sp.top_seg, cl_in, sp.n_top, node_base);
+            if ((uint64_t)node_base + sp.n_top > 2ull * ns) return fail("BVH2 node count");
+            hipLaunchKernelGGL(k_top_link, dim3(blocks(sp.n_top, 256)), dim3(256), 0, s, a, sp.segs, sp.top_seg, cl_roots, sp.n_top, node_base);
             B_TRY(hipGetLastError());
             root = node_base;
+            for (size_t l = sp.top_level_begin.size() - 1; l-- > 0;) {
+                const uint32_t b0 = sp.top_level_begin[l], cnt = sp.top_level_begin[l + 1] - b0;
+                if (cnt) hipLaunchKernelGGL(k_cost_range, dim3(blocks(cnt, 256)), dim3(256), 0, s, a, node_base + b0, cnt, 0u);
+            }
         } else if (!small_tail) {
-            B_TRY(hipMemcpyAsync(&root, cl_in, sizeof root, hipMemcpyDeviceToHost, s));
+            B_TRY(hipMemcpyAsync(&root, cl_roots, sizeof root, hipMemcpyDeviceToHost, s));
             B_TRY(hipStreamSynchronize(s));
         }
+        return B_OK(hipGetLastError());
     }
-    // ---- cost tables: the leaves' and PLOC's nodes' were computed where the nodes were made; the top-down phase's levels from the deepest up ----
-    if (split && sp.n_top)
-        for (size_t l = sp.top_level_begin.size() - 1; l-- > 0;) {
-            const uint32_t b0 = sp.top_level_begin[l], cnt = sp.top_level_begin[l + 1] - b0;
-            if (cnt) hipLaunchKernelGGL(k_cost_range, dim3(blocks(cnt, 256)), dim3(256), 0, s, a, node_base + b0, cnt, 0u);
-        }
-    B_TRY(hipGetLastError());
-    // ---- fast-trace builds: the reinsertion pass over the finished BVH2 (build_reinsert.hip), which leaves boxes, counts and tables current ----
+    // 3a. fast-trace builds: the reinsertion pass over the finished BVH2 (build_reinsert.hip), which leaves boxes, counts and tables current
     // (not where the top-down phase gave up: that build is PLOC's tree, node for node)
-    if (in.reinsert_rounds > 0 && !res.fell_back) {
+    bool reinsert() {
+        if (in.reinsert_rounds <= 0 || res.fell_back) return true;
         const uint32_t n2 = node_base + (split ? sp.n_top : 0u);
         res.error = gpu_reinsert_bvh2(a, n2, root, in.reinsert_rounds, arena, s, in.split.verbose, &res.reinsert_moved, &res.where);
-        if (res.error != hipSuccess) goto done;
+        return res.error == hipSuccess;
     }
-    // ---- emission, level by level ----
-    {
+    // 5. emission, level by level
+    bool emit() {
         const uint2 first = make_uint2(root, 0u);
         B_TRY(hipMemcpyAsync(items_a, &first, sizeof first, hipMemcpyHostToDevice, s));
         uint32_t level_begin = 0, level_count = 1, depth = 0;
         uint2 *it_in = items_a, *it_out = items_b;
-        res.level_begin.push_back(0u);
         while (level_count > 0u) {
             const uint32_t next_begin = level_begin + level_count;
             hipLaunchKernelGGL(k_emit_level, dim3(blocks(level_count, 16)), dim3(128), 0, s, a, it_in, level_count, it_out, next_begin, depth == 0 ? 1u : 0u);
             B_TRY(hipGetLastError());
-            B_TRY(hipMemcpyAsync(&h, a.counters, sizeof h, hipMemcpyDeviceToHost, s));
-            B_TRY(hipStreamSynchronize(s));
-            res.level_begin.push_back(next_begin);
+            if (!read_counters()) return false;
+            res.level_begin.push_back(level_begin);
             level_begin = next_begin; level_count = h.next_node - next_begin;
             std::swap(it_in, it_out);
             if (level_count) ++depth;
         }
-        res.n_nodes = h.next_node; res.max_depth = depth; res.n_records = h.next_prim;
-        // (with spatial splits, pieces of a primitive that met again in a leaf were emitted once)
-        if (split ? (h.next_prim < nv || h.next_prim > nl) : h.next_prim != nv) { res.error = hipErrorUnknown; res.where = "emitted primitive count differs from the valid count"; goto done; }
+        return finish(depth);
     }
-    hipLaunchKernelGGL(k_normalise_weights, dim3(blocks(res.n_nodes, 256)), dim3(256), 0, s, in.out_node_ref, res.n_nodes, a.counters);
-    B_TRY(hipGetLastError());
-    B_TRY(hipStreamSynchronize(s));
-done:
+    // the refit quality weights of the nodes, normalised
+    bool weights() {
+        hipLaunchKernelGGL(k_normalise_weights, dim3(blocks(res.n_nodes, 256)), dim3(256), 0, s, in.out_node_ref, res.n_nodes, a.counters);
+        return B_OK(hipGetLastError()) && B_OK(hipStreamSynchronize(s));
+    }
+};
+
+}  // namespace
+
+// The build.  in: instance tables + output buffers sized for the worst case (one node and one record per leaf).  Synchronises `s`
+// a few dozen times for a counter each (split levels, PLOC rounds, levels); no geometry crosses the bus.
+static GpuBuildResult build_once(const GpuBuildInput &in, hipStream_t s) {
+    GpuBuildResult res{};
+    Build b(in, s, res);
+    if (!(b.bounds() && b.top_down() && b.arrays_and_sort())) return res;
+    if (b.is_small()) { b.small_build(); return res; }
+    (void)(b.ploc() && b.top_link_and_costs() && b.reinsert() && b.emit() && b.weights());
     return res;
 }
 

@@ -1,5 +1,6 @@
-// build_dev.h -- device helpers shared by the two halves of the acceleration-structure build (build.hip: bounds, Morton order, PLOC,
-// collapse, emission; build_split.hip: the top-down phase with spatial splits).
+// build_dev.h -- device helpers shared by the units of the acceleration-structure build (build.hip: bounds, Morton order, PLOC, cost
+// tables, emission; build_split.hip: the top-down phase with spatial splits; build_reinsert.hip: the reinsertion pass): what needs
+// GpuBuildArgs.  The collapse itself -- the tables' recurrence, the forest, the octant slots -- is bvh8_collapse.h, shared with the host builder.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +8,7 @@
 #include "build.h"
 #include "bvh8.h"
 #include "bvh8_geom.h"
+#include "bvh8_collapse.h"
 
 namespace hrt {
 namespace {
@@ -66,58 +68,32 @@ __device__ __forceinline__ void block_minmax(float (&mn)[N], float (&mx)[N]) {
         }
 }
 
-// ---- optimal collapse: cost tables (bvh8_build.cpp, same recurrences) ----
-// table of a node: c[1..7] as floats in t[1..7]; t[0] bits: leaf1 | use_dist[i] << i (i = 2..7) | split[j] << (8 + 3 (j - 2)) (j = 2..8)
-struct CostRow { float c[8]; };
-__device__ __forceinline__ uint32_t row_bits(const CostRow &r) { return __float_as_uint(r.c[0]); }
-__device__ __forceinline__ uint32_t row_split(uint32_t bits, int j) { return (bits >> (8 + 3 * (j - 2))) & 7u; }
-
+// ---- optimal collapse (bvh8_collapse.h): a node's cost table from GpuBuildArgs -- its area floored, its children's rows loaded ----
 __device__ __forceinline__ float node_half_area(const float4 lo, const float4 hi) {
     const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
     return dx * dy + dy * dz + dz * dx;
 }
 
-__device__ void cost_of_node(const GpuBuildArgs &a, uint32_t nd, bool leaf, CostRow &out) {
-    const float kInf = INFINITY;
-    // (a box without area -- coinciding points, a line of them -- still costs a visit: with zero everywhere the tables tie and the tree comes out
-    // nearly binary, 15 levels for 5000 points; any positive area leaves everything else as it was)
-    const float area = fmaxf(node_half_area(a.node_lo[nd], a.node_hi[nd]), 1e-30f);
-    const uint32_t np = a.node_nprims[nd];
-    const float c_leaf = np <= a.max_leaf_prims ? area * a.c_prim * (float)np : kInf;
-    if (leaf) {
-        for (int i = 1; i <= 7; ++i) out.c[i] = c_leaf;
-        out.c[0] = __uint_as_float(1u);
-        return;
-    }
-    const uint32_t l = __float_as_uint(a.node_lo[nd].w), r = __float_as_uint(a.node_hi[nd].w);
-    CostRow cl, cr;
-    {   // the children's rows: written by an earlier launch
-        const float4 *pl = reinterpret_cast<const float4 *>(a.cost + 8 * (size_t)l), *pr = reinterpret_cast<const float4 *>(a.cost + 8 * (size_t)r);
-        const float4 l0 = pl[0], l1 = pl[1], r0 = pr[0], r1 = pr[1];
-        cl.c[0] = l0.x; cl.c[1] = l0.y; cl.c[2] = l0.z; cl.c[3] = l0.w; cl.c[4] = l1.x; cl.c[5] = l1.y; cl.c[6] = l1.z; cl.c[7] = l1.w;
-        cr.c[0] = r0.x; cr.c[1] = r0.y; cr.c[2] = r0.z; cr.c[3] = r0.w; cr.c[4] = r1.x; cr.c[5] = r1.y; cr.c[6] = r1.z; cr.c[7] = r1.w;
-    }
-    float dist[9]; uint32_t bits = 0u;
-    for (int j = 2; j <= 8; ++j) {
-        float best = kInf; int bk = 1;
-        for (int k = 1; k < j; ++k) {
-            const float v = cl.c[k < 7 ? k : 7] + cr.c[(j - k) < 7 ? (j - k) : 7];
-            if (v < best) { best = v; bk = k; }
-        }
-        dist[j] = best; bits |= (uint32_t)bk << (8 + 3 * (j - 2));
-    }
-    const float c_internal = dist[a.width] + area * a.c_node;      // (a.width children at most: 8, or fewer as an experiment -- HRT_BVH_WIDTH)
-    if (c_leaf <= c_internal) bits |= 1u;
-    out.c[1] = fminf(c_leaf, c_internal);
-    for (int i = 2; i <= 7; ++i) {
-        if (dist[i] < out.c[i - 1]) { out.c[i] = dist[i]; bits |= 1u << i; } else out.c[i] = out.c[i - 1];
-    }
-    out.c[0] = __uint_as_float(bits);
+__device__ __forceinline__ void load_row(const GpuBuildArgs &a, uint32_t nd, CostRow &r) {
+    const float4 *p = reinterpret_cast<const float4 *>(a.cost + 8 * (size_t)nd);
+    const float4 r0 = p[0], r1 = p[1];
+    r.c[0] = r0.x; r.c[1] = r0.y; r.c[2] = r0.z; r.c[3] = r0.w; r.c[4] = r1.x; r.c[5] = r1.y; r.c[6] = r1.z; r.c[7] = r1.w;
 }
 
 __device__ __forceinline__ void store_row(const GpuBuildArgs &a, uint32_t nd, const CostRow &r) {
     float4 *p = reinterpret_cast<float4 *>(a.cost + 8 * (size_t)nd);
     p[0] = make_float4(r.c[0], r.c[1], r.c[2], r.c[3]); p[1] = make_float4(r.c[4], r.c[5], r.c[6], r.c[7]);
+}
+
+__device__ void cost_of_node(const GpuBuildArgs &a, uint32_t nd, bool leaf, CostRow &out) {
+    // (a box without area -- coinciding points, a line of them -- still costs a visit: with zero everywhere the tables tie and the tree comes out
+    // nearly binary, 15 levels for 5000 points; any positive area leaves everything else as it was)
+    const float area = fmaxf(node_half_area(a.node_lo[nd], a.node_hi[nd]), 1e-30f);
+    const uint32_t np = a.node_nprims[nd];
+    if (leaf) { cost_row_leaf(area, np, a.max_leaf_prims, a.c_prim, out); return; }
+    CostRow cl, cr;                                                 // the children's rows: written by an earlier launch
+    load_row(a, __float_as_uint(a.node_lo[nd].w), cl); load_row(a, __float_as_uint(a.node_hi[nd].w), cr);
+    cost_row_inner(cl, cr, area, np, a.max_leaf_prims, a.c_node, a.c_prim, a.width, out);      // (a.width children at most: 8, or fewer as an experiment -- HRT_BVH_WIDTH)
 }
 
 inline uint32_t blocks(uint32_t n, uint32_t per) { return (n + per - 1u) / per; }

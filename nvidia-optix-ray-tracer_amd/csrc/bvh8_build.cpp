@@ -11,10 +11,11 @@
 //      c_node = 1, c_prim = 0.45, leaves <= 3 primitives.  (A first greedy version -- always open
 //      the largest inner child -- left 64 % of the nodes with only two children.)
 //   3. octant-ordered slot assignment so that (slot ^ (7 - ray_octant)) approximates
-//      front-to-back order during traversal;
+//      front-to-back order during traversal (2. and 3. are bvh8_collapse.h: the code the device builder runs);
 //   4. outward-rounded 8-bit quantisation of the child boxes against the node origin/exponent.
 #include "bvh8.h"
 #include "bvh8_geom.h"
+#include "bvh8_collapse.h"
 
 #include <algorithm>
 #include <atomic>
@@ -343,9 +344,13 @@ struct Reinsert {
 
 inline uint8_t unary_count(uint32_t n) { return (uint8_t)((1u << n) - 1u); }
 
-// cost table of a BVH2 node for the optimal collapse: c[i] = cheapest representation of the subtree as a forest of at most i roots, i = 1..7;
-// split[j], j = 2..8 = roots given to the left child when j roots are distributed over the two children
-struct Cost { float c[8]; uint8_t leaf1; uint8_t use_dist[8]; uint8_t split[9]; };
+// the BVH2 and its cost tables, as collect_forest (bvh8_collapse.h) asks for them
+struct HostTree {
+    const std::vector<B2> &nodes; const std::vector<CostRow> &cost;
+    uint32_t bits(uint32_t x) const { return row_bits(cost[x]); }
+    bool leaf(uint32_t x) const { return nodes[x].count > 0; }
+    void children(uint32_t x, uint32_t &l, uint32_t &r) const { l = nodes[x].left; r = nodes[x].right; }
+};
 
 }  // namespace
 
@@ -438,62 +443,25 @@ static uint64_t build_bvh8_with(const std::vector<BuildPrim> &prims, Bvh8 &out, 
     float kCNode = 1.0f, kCPrim = 0.45f;
     if (const char *e = std::getenv("HRT_BVH_CPRIM")) kCPrim = (float)std::atof(e);     // tuning experiments
     if (const char *e = std::getenv("HRT_BVH_CNODE")) kCNode = (float)std::atof(e);
-    std::vector<Cost> cost(nb2);
-    {   // post-order over the BVH2, the big subtrees on worker threads like the build itself (a table depends on its children's only)
+    std::vector<CostRow> cost(nb2);
+    {   // post-order over the BVH2, the big subtrees on worker threads like the build itself (a table depends on its children's only);
+        // the tables themselves: bvh8_collapse.h, over the half area as it is and nodes of up to 8 children
         struct Pass {
-            const Builder &B; std::vector<Cost> &cost; float c_node, c_prim; uint32_t max_leaf; int par_depth;
+            const Builder &B; std::vector<CostRow> &cost; float c_node, c_prim; uint32_t max_leaf; int par_depth;
             void run(uint32_t ni, int depth) {
-                const B2 &bn = B.nodes[ni];
-                Cost &cn = cost[ni];
-                std::memset(&cn, 0, sizeof cn);
-                const float kInf = std::numeric_limits<float>::infinity();
-                const float area = half_area(bn.lo, bn.hi);
-                const float c_leaf = bn.nprims <= max_leaf ? area * c_prim * (float)bn.nprims : kInf;
-                if (bn.count > 0) {                      // BVH2 leaf
-                    for (int i = 1; i <= 7; ++i) cn.c[i] = c_leaf;
-                    cn.leaf1 = 1;
-                    return;
-                }
+                const B2 &bn = B.nodes[ni]; const float area = half_area(bn.lo, bn.hi);
+                if (bn.count > 0) { cost_row_leaf(area, bn.nprims, max_leaf, c_prim, cost[ni]); return; }      // BVH2 leaf
                 if (depth < par_depth && bn.nprims > 8192) {
                     std::thread t([this, &bn, depth] { run(bn.left, depth + 1); });
                     run(bn.right, depth + 1);
                     t.join();
                 } else { run(bn.left, depth + 1); run(bn.right, depth + 1); }
-                const Cost &cl = cost[bn.left], &cr = cost[bn.right];
-                float dist[9];
-                for (int j = 2; j <= 8; ++j) {
-                    float best = kInf; int bk = 1;
-                    for (int k = 1; k < j; ++k) {
-                        const float v = cl.c[std::min(k, 7)] + cr.c[std::min(j - k, 7)];
-                        if (v < best) { best = v; bk = k; }
-                    }
-                    dist[j] = best; cn.split[j] = (uint8_t)bk;
-                }
-                const float c_internal = dist[8] + area * c_node;
-                cn.leaf1 = c_leaf <= c_internal ? 1 : 0;
-                cn.c[1] = std::min(c_leaf, c_internal);
-                for (int i = 2; i <= 7; ++i) {
-                    if (dist[i] < cn.c[i - 1]) { cn.c[i] = dist[i]; cn.use_dist[i] = 1; }
-                    else { cn.c[i] = cn.c[i - 1]; cn.use_dist[i] = 0; }
-                }
+                cost_row_inner(cost[bn.left], cost[bn.right], area, bn.nprims, max_leaf, c_node, c_prim, 8u, cost[ni]);
             }
         } pass{B, cost, kCNode, kCPrim, max_leaf_prims, B.max_par_depth};
         pass.run(0, 0);
     }
-    // roots of the forest that represents subtree n with a budget of j roots (as chosen by the tables)
-    struct Collector {
-        const Builder &B; const std::vector<Cost> &cost; uint32_t out[8]; int n = 0;
-        void forest(uint32_t x, int i) {            // at most i roots for subtree x
-            while (i > 1 && !cost[x].use_dist[i]) --i;
-            if (i == 1 || B.nodes[x].count > 0) { out[n++] = x; return; }
-            distribute(x, i);
-        }
-        void distribute(uint32_t x, int j) {        // subtree x opened: j roots over its two children
-            const int k = cost[x].split[j];
-            forest(B.nodes[x].left, std::min(k, 7));
-            forest(B.nodes[x].right, std::min(j - k, 7));
-        }
-    };
+    const HostTree tree{B.nodes, cost};
 
     // ---- emit 8-wide nodes breadth first so that inner children are contiguous: level by level, the nodes of a level in parallel
     //      (children, slots, quantised boxes, leaf records), a serial prefix in between for the child / primitive bases -- the
@@ -509,43 +477,17 @@ static uint64_t build_bvh8_with(const std::vector<BuildPrim> &prims, Bvh8 &out, 
         if (bn.count > 0 || (b2 == 0 && bn.nprims <= max_leaf_prims)) {
             ch[nch] = b2; ch_leaf[nch] = true; ++nch;         // the whole scene fits one leaf: wrap it
         } else {
-            Collector col{B, cost};
-            col.distribute(b2, 8);
-            for (int k = 0; k < col.n; ++k) {
-                ch[nch] = col.out[k];
-                ch_leaf[nch] = B.nodes[col.out[k]].count > 0 || cost[col.out[k]].leaf1;
-                ++nch;
-            }
+            nch = collect_forest(tree, b2, 8, ch);
+            for (int k = 0; k < nch; ++k) ch_leaf[k] = tree.leaf(ch[k]) || row_leaf1(tree.bits(ch[k]));
         }
-        // slot assignment: slot s is visited first by rays of octant s (bit2 = -x, bit1 = -y, bit0 = -z)
-        float ncx[3];
-        for (int a = 0; a < 3; ++a) ncx[a] = 0.5f * (bn.lo[a] + bn.hi[a]);
-        float scost[8][8];
+        // the children's octant slots (bvh8_collapse.h), from their centres' offsets
+        float d[8][3];
         for (int k = 0; k < nch; ++k) {
             const B2 &c = B.nodes[ch[k]];
-            const float d[3] = {0.5f * (c.lo[0] + c.hi[0]) - ncx[0], 0.5f * (c.lo[1] + c.hi[1]) - ncx[1], 0.5f * (c.lo[2] + c.hi[2]) - ncx[2]};
-            for (int s = 0; s < 8; ++s) {
-                const float sx = (s & 4) ? -1.0f : 1.0f, sy = (s & 2) ? -1.0f : 1.0f, sz = (s & 1) ? -1.0f : 1.0f;
-                scost[k][s] = d[0] * sx + d[1] * sy + d[2] * sz;
-            }
+            for (int a = 0; a < 3; ++a) d[k][a] = 0.5f * (c.lo[a] + c.hi[a]) - 0.5f * (bn.lo[a] + bn.hi[a]);
         }
-        int slot_child[8]; for (int s = 0; s < 8; ++s) slot_child[s] = -1;
-        bool child_done[8] = {false, false, false, false, false, false, false, false};
-        for (int round = 0; round < nch; ++round) {
-            int bk = -1, bs = -1; float bc = std::numeric_limits<float>::infinity();
-            for (int k = 0; k < nch; ++k) {
-                if (child_done[k]) continue;
-                for (int s = 0; s < 8; ++s) {
-                    if (slot_child[s] >= 0) continue;
-                    if (scost[k][s] < bc) { bc = scost[k][s]; bk = k; bs = s; }
-                }
-            }
-            if (bk < 0) {   // NaN costs (degenerate boxes): first free pair
-                for (int k = 0; k < nch && bk < 0; ++k) if (!child_done[k]) bk = k;
-                for (int s = 0; s < 8 && bs < 0; ++s) if (slot_child[s] < 0) bs = s;
-            }
-            slot_child[bs] = bk; child_done[bk] = true;
-        }
+        int slot_child[8];
+        assign_octant_slots(nch, d, slot_child);
         Bvh8Node &nd = L.nd; std::memset(&nd, 0, sizeof nd);
         for (int a = 0; a < 3; ++a) {
             nd.p[a] = bn.lo[a];
