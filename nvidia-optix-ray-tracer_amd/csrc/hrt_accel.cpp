@@ -112,9 +112,6 @@ float instance_tables(const std::vector<HrtInstance> &inst, const std::vector<st
     return *std::max_element(part.begin(), part.end());
 }
 
-void launch_refit_phases(RefitArgs ra, const std::vector<std::pair<uint32_t, uint32_t>> &phases, hipStream_t s);
-static RefitArgs refit_args(HrtContext *ctx, Tlas &t);
-
 // The host builder needs the geometry on the host: fetched from the BLAS's device copy the first time it is asked for
 // (HRT_BUILD=host only; the device build never brings geometry across the bus).
 int ensure_host_geometry(HrtContext *ctx, Blas &b, hipStream_t s) {
@@ -135,8 +132,9 @@ int ensure_host_geometry(HrtContext *ctx, Blas &b, hipStream_t s) {
     return HRT_OK;
 }
 
-// ---- what the device builds share (ensure_template, build_merged_on_device, build_two_level) ----
+// ---- what the device builds share (ensure_template, ensure_split_template, build_merged_on_device, build_two_level) ----
 static size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+static float refit_pad(float scene_scale) { return 4e-6f * std::max(1.0f, scene_scale); }
 
 // A build's arena holds its staged output and small tables in front of the build's own working memory.  take() lays them out, each
 // 256-aligned, before the arena exists (`used` is what they need in all); at() gives the pointers once it does.
@@ -145,13 +143,6 @@ struct ArenaLayout {
     unsigned char *base = nullptr;
     size_t take(size_t bytes) { const size_t at = used; used += align256(bytes); return at; }
     template <class T> T *at(size_t offset) const { return reinterpret_cast<T *>(base + offset); }
-};
-
-// Gives a build's arena back to the context when the build's scope ends, however it ends.  On an error path kernels may still be writing to
-// the arena: the stream is synchronised first, so that another loader thread is not handed it before they are done.
-struct ArenaRelease {
-    HrtContext *ctx; ScratchArena arena; hipStream_t s;
-    ~ArenaRelease() { (void)hipStreamSynchronize(s); scratch_release(ctx, arena); }
 };
 
 // The part of a device build's input that comes from the context's knobs; what differs between the builds is in the arguments (`topdown`: the
@@ -164,6 +155,69 @@ static GpuBuildInput build_input(const HrtContext *ctx, uint32_t max_leaf_prims,
     in.split.enabled = topdown; in.split.budget_frac = split_budget; in.split.alpha = ctx->split_alpha; in.split.bias = ctx->split_bias; in.split.cut_bias = ctx->split_cut_bias;
     in.split.cell_refs = (uint32_t)ctx->split_cell_refs; in.split.pad = pad; in.split.verbose = ctx->build_verbose;
     return in;
+}
+
+// One device build (build.hip) staged in ONE block of the context's working memory: the caller's own small tables in front (lay.take,
+// before stage()), then the build's worst-case output -- a node and two reference floats per entry (primitive, or reference of a spatial
+// split), the records where the caller has no block of its own for them, their clip boxes where the build splits -- then the build's own
+// arrays: a build allocates and frees nothing (eight hipMalloc / hipFree pairs used to cost more than a template's build).  `in`: build_input's,
+// with the counts, the instance tables and the strides filled in.
+enum class StagedRecords { None, Records, RecordsAndClip };
+struct StagedBuild {
+    HrtContext *ctx; hipStream_t s;
+    ArenaLayout lay; ScratchArena arena;
+    size_t want = 0;      // what stage() asked for (first)
+    // The arena goes back to the context when the build's scope ends, however it ends.  On an error path kernels may still be writing to
+    // it: the stream is synchronised first, so that another loader thread is not handed it before they are done.
+    ~StagedBuild() { if (arena.p) { (void)hipStreamSynchronize(s); scratch_release(ctx, arena); } }
+
+    // Lays the output out, acquires the arena and points in.out_* / in.scratch into it.  False when the working memory is not to be had --
+    // what then is the caller's business; or_without_topdown: then the build goes without the top-down phase's buffers, PLOC alone.
+    bool stage(GpuBuildInput &in, size_t max_entries, StagedRecords records, bool or_without_topdown) {
+        const size_t o_nodes = lay.take((size_t)in.node_stride * max_entries), o_ref = lay.take(sizeof(float) * 2 * max_entries);
+        const size_t o_prims = lay.take(records != StagedRecords::None ? (size_t)in.prim_stride * max_entries : 0u);
+        const size_t o_clip = lay.take(records == StagedRecords::RecordsAndClip ? sizeof(float) * 6 * max_entries : 0u);
+        want = lay.used + gpu_build_scratch_bytes(in.n_prims, &in.split);
+        arena = scratch_acquire(ctx, want);
+        if (!arena.p && or_without_topdown && in.split.enabled) {
+            in.split.enabled = false;
+            arena = scratch_acquire(ctx, lay.used + gpu_build_scratch_bytes(in.n_prims, &in.split));
+        }
+        if (!arena.p) return false;
+        lay.base = static_cast<unsigned char *>(arena.p);
+        in.out_nodes = lay.at<unsigned char>(o_nodes); in.out_node_ref = lay.at<float>(o_ref);
+        if (records != StagedRecords::None) in.out_prims = lay.at<unsigned char>(o_prims);
+        if (records == StagedRecords::RecordsAndClip) in.out_clip = lay.at<float>(o_clip);
+        in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
+        return true;
+    }
+    // The build itself (it synchronises the stream before it returns); `what`: the caller's name for it in the error text.
+    int build(const GpuBuildInput &in, const char *what, GpuBuildResult &r) {
+        r = gpu_build_bvh8(in, s);
+        if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "%s failed: %s (%s)", what, hipGetErrorString(r.error), r.where);
+        return HRT_OK;
+    }
+};
+
+// The build over ONE BLAS in its own space, a single identity instance (`in`: the knobs), into packed 80 / 48 byte records staged in `sb`.
+// The five small instance tables share the arena.  no_memory: nothing was built, the working memory is not to be had.
+static int build_blas_tree(const Blas &b, GpuBuildInput &in, StagedRecords records, const char *what, StagedBuild &sb, GpuBuildResult &r, bool &no_memory) {
+    HrtContext *ctx = sb.ctx; const hipStream_t s = sb.s;
+    const uint32_t h_first[2] = {0u, b.n_prims}, h_kind = b.kind, h_ident = 1u;
+    const float h_xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const void *h_src = b.d_verts;
+    ArenaLayout &lay = sb.lay;
+    const size_t o_first = lay.take(sizeof h_first), o_kind = lay.take(sizeof h_kind), o_src = lay.take(sizeof h_src), o_xf = lay.take(sizeof h_xf), o_ident = lay.take(sizeof h_ident);
+    in.n_prims = b.n_prims; in.n_inst = 1; in.node_stride = sizeof(Bvh8Node); in.prim_stride = sizeof(PrimRecord);
+    no_memory = !sb.stage(in, gpu_build_max_refs(b.n_prims, &in.split), records, false);
+    if (no_memory) return HRT_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
+    in.d_inst_first = lay.at<const uint32_t>(o_first); in.d_inst_kind = lay.at<const uint32_t>(o_kind);
+    in.d_inst_src = lay.at<const void *const>(o_src); in.d_inst_xf = lay.at<const float>(o_xf);
+    in.d_inst_identity = lay.at<const uint32_t>(o_ident);
+    return sb.build(in, what, r);
 }
 
 // Refit phases of a tree stored breadth first (nodes of level l: [level_begin[l], level_begin[l + 1])): a level each, children before parents.
@@ -190,28 +244,102 @@ static BuildPrim build_prim_of(const Blas &b, uint32_t p, const float *m, bool i
     return bp;
 }
 
+// the split build's working memory (~1.2 KB per primitive with the staged output) has to be there: otherwise the default build
+static bool split_build_fits(HrtContext *ctx, uint32_t n_prims) {
+    SplitParams probe; probe.enabled = true; probe.budget_frac = ctx->split_budget; probe.cell_refs = (uint32_t)ctx->split_cell_refs;
+    const size_t leaves = gpu_build_max_refs(n_prims, &probe);
+    const size_t want = gpu_build_scratch_bytes(n_prims, &probe) + leaves * (size_t)(128 + 8 + ctx->prim_stride + 24);
+    size_t free_b = 0, total_b = 0, kept = 0;      // (what the context keeps for later counts as free: an allocation that fails gives it back first)
+    { std::lock_guard<std::mutex> lk(ctx->scratch_mu); for (const ScratchArena &x : ctx->scratch_free) kept += x.bytes; }
+    { std::lock_guard<std::mutex> lk(ctx->pool_mu); kept += ctx->pool_bytes; }
+    return leaves <= (1u << 30) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want <= (free_b + kept) / 10 * 9;
+}
+
+// ---- refits: of an update (refit_tlas, hrt_tlas_update) and the one that completes a build ----
+// The phases of a refit, children before parents: wide phases get a launch each, the narrow ones at the end (the top
+// of the tree, or all of a small tree) run in one single-workgroup launch.
+void launch_refit_phases(RefitArgs ra, const std::vector<std::pair<uint32_t, uint32_t>> &phases, hipStream_t s) {
+    launch_refit_records(ra, s);                               // (small trees: ra.rec_box)
+    size_t tail = phases.size();
+    while (tail > 0 && phases.size() - tail < kRefitTopLevels && phases[tail - 1].second <= kRefitTopLevelNodes) --tail;
+    for (size_t i = 0; i < tail; ++i) { ra.first_node = phases[i].first; ra.n_nodes = phases[i].second; launch_refit_level(ra, s); }
+    RefitLevels top{};
+    for (size_t i = tail; i < phases.size(); ++i) { top.first[top.n_levels] = phases[i].first; top.count[top.n_levels] = phases[i].second; ++top.n_levels; }
+    launch_refit_top(ra, top, s);
+}
+
+// Small trees (the reference's own scenes) are refitted in one workgroup that walks the levels; the records' arithmetic -- most of the
+// work, and a chain of dependent loads -- runs before that, a thread per record, into 24 bytes per record (k_refit_records).
+constexpr uint32_t kRecBoxMaxRecords = 65536;
+static void attach_rec_box(HrtContext *ctx, Tlas &t, RefitArgs &ra, uint32_t n_records) {
+    if (n_records == 0u || n_records > kRecBoxMaxRecords) return;
+    if (!t.dev.d_rec_box && pool_alloc(ctx, (void **)&t.dev.d_rec_box, sizeof(float) * 6 * (size_t)n_records) != hipSuccess) { (void)hipGetLastError(); t.dev.d_rec_box = nullptr; return; }
+    ra.rec_box = t.dev.d_rec_box; ra.n_records = n_records;
+}
+
+// What every refit of a tree takes from it (its counts and two_level are set).  The caller adds what differs: the padding (`pad`, or `scale_bits`
+// when the scene scale is on the device), `area_sum` or `write_reference`, `clip`.
+static RefitArgs refit_args(HrtContext *ctx, Tlas &t) {
+    const TlasDevice &d = t.dev;
+    RefitArgs ra{};
+    ra.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); ra.node_stride = t.node_stride;
+    ra.prims = reinterpret_cast<unsigned char *>(d.d_prims); ra.prim_stride = t.prim_stride;
+    ra.node_box = d.d_node_box; ra.node_ref = d.d_node_ref; ra.inst_xf = d.d_inst_xf; ra.inst_identity = d.d_inst_identity; ra.inst_src = d.d_inst_src;
+    ra.order = d.d_order;
+    if (t.two_level) { ra.inst_inv = d.d_inst_inv; ra.inst_root = d.d_inst_root; }      // (the top level only: transform nodes and the boxes above them)
+    else attach_rec_box(ctx, t, ra, t.n_prims);
+    return ra;
+}
+
+// The refit that completes a build (t.phases are set; enqueued only): the device computes what the builder left blank -- world-space records,
+// boxes, origins, exponents, quantised children -- and the built areas the quality guard compares later refits with.  clip: RefitArgs::clip.
+static int reference_refit(HrtContext *ctx, Tlas &t, float pad, const float *clip, hipStream_t s) {
+    RefitArgs ra = refit_args(ctx, t);
+    ra.pad = pad; ra.write_reference = 1u; ra.clip = clip;
+    launch_refit_phases(ra, t.phases, s);
+    HIP_TRY(ctx, hipGetLastError());
+    return HRT_OK;
+}
+
+// ---- the object-space trees of a BLAS (BlasTree): the template and, under HRT_CTX_FAST_TRACE, the tree with spatial splits ----
 // Device memory a BLAS will own, while it is being filled: freed again unless everything arrived and the pointers were handed over -- a BLAS
 // never shows a tree of which only a part is there (several loader threads share the BLASes).
 struct PendingBlocks {
     void *p[3] = {nullptr, nullptr, nullptr};
     ~PendingBlocks() { for (void *q : p) if (q) (void)hipFree(q); }
-    template <class T> T *hand_over(int k) { T *q = static_cast<T *>(p[k]); p[k] = nullptr; return q; }
 };
+// A finished object-space tree -- `staged`: its counts and levels, with pointers into the host's copy or the build's arena (`kind` says
+// which) -- goes into blocks of its own, and `out` gets all of it once all of it is there.  oom_is_not_now: no room for the tree to stay is no
+// error, `out` stays empty (d_nodes == NULL) and a later TLAS may try again.
+static int keep_blas_tree(HrtContext *ctx, const BlasTree &staged, hipMemcpyKind kind, bool oom_is_not_now, hipStream_t s, BlasTree &out) {
+    PendingBlocks blk;
+    const void *src[3] = {staged.d_nodes, staged.d_prims, staged.d_clip};
+    const size_t bytes[3] = {sizeof(Bvh8Node) * (size_t)staged.n_nodes, sizeof(PrimRecord) * (size_t)staged.n_records, sizeof(float) * 6 * (size_t)staged.n_records};
+    const int n_blocks = staged.d_clip ? 3 : 2;
+    for (int k = 0; k < n_blocks; ++k) {
+        const hipError_t e = hipMalloc(&blk.p[k], std::max(bytes[k], k == 1 ? sizeof(PrimRecord) : (size_t)0));
+        if (e == hipErrorOutOfMemory && oom_is_not_now) { (void)hipGetLastError(); blk.p[k] = nullptr; return HRT_OK; }
+        HIP_TRY(ctx, e);
+    }
+    for (int k = 0; k < n_blocks; ++k) if (bytes[k]) HIP_TRY(ctx, hipMemcpyAsync(blk.p[k], src[k], bytes[k], kind, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    out = staged;
+    out.d_nodes = static_cast<unsigned char *>(blk.p[0]); out.d_prims = static_cast<unsigned char *>(blk.p[1]); out.d_clip = static_cast<float *>(blk.p[2]);
+    for (void *&q : blk.p) q = nullptr;      // (handed over)
+    return HRT_OK;
+}
 // Object-space BVH8 of one BLAS (built once): the subtree every instance of it gets in a tree over instances.  Built on the
 // device like everything else (one identity instance); only its topology -- nodes' child / primitive bases, masks, the
 // primitive ids -- comes back to the host, where assemble_instanced_bvh8 stitches instance subtrees under a top tree.
 static int template_to_device(HrtContext *ctx, Blas &b, hipStream_t s) {
-    if (b.d_tmpl_nodes || b.tmpl.nodes.empty()) return HRT_OK;
-    PendingBlocks blk;
-    HIP_TRY(ctx, hipMalloc(&blk.p[0], sizeof(Bvh8Node) * b.tmpl.nodes.size()));
-    HIP_TRY(ctx, hipMalloc(&blk.p[1], sizeof(PrimRecord) * std::max<size_t>(b.tmpl.prims.size(), 1)));
-    HIP_TRY(ctx, hipMemcpyAsync(blk.p[0], b.tmpl.nodes.data(), sizeof(Bvh8Node) * b.tmpl.nodes.size(), hipMemcpyHostToDevice, s));
-    if (!b.tmpl.prims.empty()) HIP_TRY(ctx, hipMemcpyAsync(blk.p[1], b.tmpl.prims.data(), sizeof(PrimRecord) * b.tmpl.prims.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    b.d_tmpl_prims = blk.hand_over<unsigned char>(1); b.d_tmpl_nodes = blk.hand_over<unsigned char>(0);
-    return HRT_OK;
+    if (b.tmpl_dev.d_nodes || b.tmpl.nodes.empty()) return HRT_OK;
+    BlasTree staged;
+    staged.d_nodes = reinterpret_cast<unsigned char *>(b.tmpl.nodes.data()); staged.d_prims = reinterpret_cast<unsigned char *>(b.tmpl.prims.data());
+    staged.n_nodes = (uint32_t)b.tmpl.nodes.size(); staged.n_records = (uint32_t)b.tmpl.prims.size();
+    staged.n_triangles = b.tmpl.n_triangles; staged.n_spheres = b.tmpl.n_spheres; staged.max_depth = b.tmpl.max_depth; staged.level_begin = b.tmpl.level_begin;
+    return keep_blas_tree(ctx, staged, hipMemcpyHostToDevice, false, s, b.tmpl_dev);
 }
-// keep_device: the topology also stays on the device (Blas::d_tmpl_*), for two-level TLASes to copy from
+// keep_device: the topology also stays on the device (Blas::tmpl_dev), for two-level TLASes to copy from
 int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = false) {
     if (!ctx->build_on_device) {
         const int rc = ensure_host_geometry(ctx, b, s);
@@ -233,30 +361,11 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
     b.tmpl = Bvh8();
     const uint32_t n = b.n_prims;
     if (n == 0) { build_bvh8({}, b.tmpl, 1); b.tmpl_built = true; return HRT_OK; }
-    // one block of the context's working memory holds the five small tables, the staged output and the build's own arrays: a template
-    // build allocates and frees nothing (eight hipMalloc / hipFree pairs used to cost more than the build)
-    const uint32_t h_first[2] = {0u, n}, h_kind = b.kind, h_ident = 1u;
-    const float h_xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    const void *h_src = b.d_verts;
-    ArenaLayout lay;
-    const size_t o_first = lay.take(sizeof h_first), o_kind = lay.take(sizeof h_kind), o_src = lay.take(sizeof h_src), o_xf = lay.take(sizeof h_xf), o_ident = lay.take(sizeof h_ident);
-    const size_t o_nodes = lay.take(sizeof(Bvh8Node) * (size_t)n), o_prims = lay.take(sizeof(PrimRecord) * (size_t)n), o_ref = lay.take(sizeof(float) * 2 * (size_t)n);
-    const ScratchArena arena = scratch_acquire(ctx, lay.used + gpu_build_scratch_bytes(n));
-    if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build of a BLAS template: no working memory");
-    ArenaRelease release{ctx, arena, s};
-    lay.base = static_cast<unsigned char *>(arena.p);
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
     GpuBuildInput in = build_input(ctx, kMaxLeafPrims, ctx->build_c_prim_bodies, false, false, 0.0f, 0.0f);      // (no top-down phase)
-    in.n_prims = n; in.n_inst = 1;
-    in.d_inst_first = lay.at<const uint32_t>(o_first); in.d_inst_kind = lay.at<const uint32_t>(o_kind);
-    in.d_inst_src = lay.at<const void *const>(o_src); in.d_inst_xf = lay.at<const float>(o_xf);
-    in.d_inst_identity = lay.at<const uint32_t>(o_ident);
-    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = sizeof(Bvh8Node); in.out_prims = lay.at<unsigned char>(o_prims); in.prim_stride = sizeof(PrimRecord); in.out_node_ref = lay.at<float>(o_ref);
-    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
-    const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
-    if (r.error != hipSuccess) return fail(ctx, HRT_ERR_HIP, "device build of a BLAS template failed: %s (%s)", hipGetErrorString(r.error), r.where);
+    StagedBuild sb{ctx, s}; GpuBuildResult r; bool no_memory;
+    const int rc = build_blas_tree(b, in, StagedRecords::Records, "device build of a BLAS template", sb, r, no_memory);
+    if (rc != HRT_OK) return rc;
+    if (no_memory) return fail(ctx, HRT_ERR_OOM, "device build of a BLAS template: no working memory");
     if (r.n_prims == 0) { build_bvh8({}, b.tmpl, 1); b.tmpl_built = true; return HRT_OK; }
     b.tmpl.nodes.resize(r.n_nodes); b.tmpl.prims.resize(r.n_prims);
     HIP_TRY(ctx, hipMemcpyAsync(b.tmpl.nodes.data(), in.out_nodes, sizeof(Bvh8Node) * (size_t)r.n_nodes, hipMemcpyDeviceToHost, s));
@@ -267,9 +376,6 @@ int ensure_template(HrtContext *ctx, Blas &b, hipStream_t s, bool keep_device = 
     b.tmpl_built = true;
     return keep_device ? template_to_device(ctx, b, s) : HRT_OK;
 }
-
-static bool split_build_fits(HrtContext *ctx, uint32_t n_prims);
-static float refit_pad(float scene_scale);
 
 // The split tree of a BLAS (Blas::split): the same build over one identity instance, with the top-down phase and the context's budget of
 // extra references -- as build_merged_on_device(.., device_split = true) builds the flattened scene.  Its record count is known afterwards:
@@ -284,55 +390,22 @@ static int ensure_split_template(HrtContext *ctx, Blas &b, hipStream_t s) {
     if (!split_build_fits(ctx, n)) return HRT_OK;      // (not for ever: a later TLAS may find the memory)
     float scale = 1.0f;
     for (int a = 0; a < 3; ++a) { if (std::isfinite(b.lo[a])) scale = std::max(scale, std::fabs(b.lo[a])); if (std::isfinite(b.hi[a])) scale = std::max(scale, std::fabs(b.hi[a])); }
-    const uint32_t h_first[2] = {0u, n}, h_kind = b.kind, h_ident = 1u;
-    const float h_xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    const void *h_src = b.d_verts;
     GpuBuildInput in = build_input(ctx, kMaxLeafPrims, ctx->build_c_prim_bodies, false, true, ctx->split_budget, refit_pad(scale));
-    in.n_prims = n; in.n_inst = 1;
-    const size_t max_leaves = gpu_build_max_refs(n, &in.split);
-    ArenaLayout lay;
-    const size_t o_first = lay.take(sizeof h_first), o_kind = lay.take(sizeof h_kind), o_src = lay.take(sizeof h_src), o_xf = lay.take(sizeof h_xf), o_ident = lay.take(sizeof h_ident);
-    const size_t o_nodes = lay.take(sizeof(Bvh8Node) * max_leaves), o_ref = lay.take(sizeof(float) * 2 * max_leaves);
-    const size_t o_prims = lay.take(sizeof(PrimRecord) * max_leaves), o_clip = lay.take(sizeof(float) * 6 * max_leaves);
-    const ScratchArena arena = scratch_acquire(ctx, lay.used + gpu_build_scratch_bytes(n, &in.split));
-    if (!arena.p) return HRT_OK;                        // (as above)
-    ArenaRelease release{ctx, arena, s};
-    lay.base = static_cast<unsigned char *>(arena.p);
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_first, h_first, sizeof h_first, hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_kind, &h_kind, 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_src, &h_src, sizeof(void *), hipMemcpyHostToDevice, s)); HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_xf, h_xf, sizeof h_xf, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.base + o_ident, &h_ident, 4, hipMemcpyHostToDevice, s));
-    in.d_inst_first = lay.at<const uint32_t>(o_first); in.d_inst_kind = lay.at<const uint32_t>(o_kind);
-    in.d_inst_src = lay.at<const void *const>(o_src); in.d_inst_xf = lay.at<const float>(o_xf);
-    in.d_inst_identity = lay.at<const uint32_t>(o_ident);
-    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = sizeof(Bvh8Node); in.out_prims = lay.at<unsigned char>(o_prims); in.prim_stride = sizeof(PrimRecord);
-    in.out_node_ref = lay.at<float>(o_ref); in.out_clip = lay.at<float>(o_clip);
-    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
-    const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
-    if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build of a BLAS's split tree failed: %s (%s)", hipGetErrorString(r.error), r.where);
+    StagedBuild sb{ctx, s}; GpuBuildResult r; bool no_memory;
+    int rc = build_blas_tree(b, in, StagedRecords::RecordsAndClip, "device build of a BLAS's split tree", sb, r, no_memory);
+    if (rc != HRT_OK || no_memory) return rc;                        // (no working memory: as above)
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] split tree of a BLAS: %u primitives -> %u records, %u nodes, depth %u, %u split levels, %u cells%s\n",
                      r.n_prims, r.n_records, r.n_nodes, r.max_depth, r.split_levels, r.n_cells, r.split_levels ? "" : " (not used: the unsplit template serves)");
     if (r.n_prims == 0u || r.split_levels == 0u || too_deep(r.max_depth)) { b.split_decided = true; return HRT_OK; }
-    PendingBlocks blk;
-    const size_t nb = sizeof(Bvh8Node) * (size_t)r.n_nodes, pb = sizeof(PrimRecord) * (size_t)r.n_records, cb = sizeof(float) * 6 * (size_t)r.n_records;
-    {   // no room for the tree to stay: like working memory that is not to be had -- the unsplit template serves, and a later TLAS may try again
-        const size_t bytes[3] = {nb, pb, cb};
-        for (int k = 0; k < 3; ++k) {
-            const hipError_t e = hipMalloc(&blk.p[k], bytes[k]);
-            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); blk.p[k] = nullptr; return HRT_OK; }
-            HIP_TRY(ctx, e);
-        }
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(blk.p[0], in.out_nodes, nb, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(blk.p[1], in.out_prims, pb, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(blk.p[2], in.out_clip, cb, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    Blas::SplitTree &t = b.split;
-    t.n_nodes = r.n_nodes; t.n_records = r.n_records; t.max_depth = r.max_depth; t.level_begin = r.level_begin;
-    t.n_triangles = b.kind == kPrimKindTriangle ? r.n_prims : 0u; t.n_spheres = b.kind == kPrimKindTriangle ? 0u : r.n_prims;
-    t.d_clip = blk.hand_over<float>(2); t.d_prims = blk.hand_over<unsigned char>(1); t.d_nodes = blk.hand_over<unsigned char>(0);
-    b.split_decided = true;
-    return HRT_OK;
+    BlasTree staged;
+    staged.d_nodes = in.out_nodes; staged.d_prims = in.out_prims; staged.d_clip = in.out_clip;
+    staged.n_nodes = r.n_nodes; staged.n_records = r.n_records; staged.max_depth = r.max_depth; staged.level_begin = r.level_begin;
+    staged.n_triangles = b.kind == kPrimKindTriangle ? r.n_prims : 0u; staged.n_spheres = b.kind == kPrimKindTriangle ? 0u : r.n_prims;
+    // (no room for the tree to stay: like working memory that is not to be had -- the unsplit template serves, and a later TLAS may try again)
+    rc = keep_blas_tree(ctx, staged, hipMemcpyDeviceToDevice, true, s, b.split);
+    if (rc == HRT_OK && b.split.d_nodes) b.split_decided = true;
+    return rc;
 }
 
 // Build a TLAS and upload it together with the tables the device refit needs (hrt_tlas_update).  What is built (TreeKind):
@@ -353,9 +426,6 @@ struct BuildPlan {
     uint32_t n_tri_in = 0;                                           // triangles among them
     std::vector<Blas *> uniq; std::vector<uint32_t> slot_of;        // TwoLevel: the BLASes that have instances in the tree; per instance, which of them
 };
-constexpr int kRetryFlattened = 1;      // build_tlas_fresh: the two-level tree asked for cannot be had (too deep for the path kernel's stack): build the flattened one
-
-static float refit_pad(float scene_scale) { return 4e-6f * std::max(1.0f, scene_scale); }
 
 // ---- the tables every structure needs: per instance the transform, its inverse, the identity flag and `src`, what the refit takes as the
 //      instance's geometry (the BLAS's vertices; the top level of a two-level tree: its bounds); the word the refit's area sum goes to; and
@@ -400,19 +470,30 @@ static int upload_instance_tables(HrtContext *ctx, Tlas &t, hipStream_t s) {
     return upload_instance_tables(ctx, t, src, s);
 }
 
+// ---- the pool blocks every tree has: nodes (n_nodes of them and node_tail bytes), a box and a reference area per node, records (one at
+//      least; the block the caller already made for them stays).  Leaves the tree's size on the device in t.alloc_bytes. ----
+static int alloc_tree_blocks(HrtContext *ctx, Tlas &t, size_t n_nodes, size_t node_tail, size_t n_records) {
+    TlasDevice &d = t.dev;
+    const size_t nb = (size_t)t.node_stride * n_nodes, rows = std::max<size_t>(n_nodes, 1), pb = (size_t)t.prim_stride * std::max<size_t>(n_records, 1);
+    HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, nb + node_tail));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * 6 * rows));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * 2 * rows));
+    if (!d.d_prims) HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, pb));
+    t.alloc_bytes = (uint64_t)nb + sizeof(float) * 8 * rows + pb;
+    return HRT_OK;
+}
+
 // ---- a host-built tree (t.bvh; `order`: the refit order of a tree over instances, empty otherwise) goes to the device ----
 static int upload_host_tree(HrtContext *ctx, Tlas &t, const std::vector<uint32_t> &order, hipStream_t s) {
     if (too_deep(t.bvh.max_depth)) return fail(ctx, HRT_ERR_INVALID, "BVH depth %u exceeds the traversal stack", t.bvh.max_depth);
-    const int rc = upload_instance_tables(ctx, t, s);
+    int rc = upload_instance_tables(ctx, t, s);
     if (rc != HRT_OK) return rc;
     TlasDevice &d = t.dev;
     const size_t n_nodes = t.bvh.nodes.size(), n_prims = t.bvh.prims.size();
     const size_t nb = (size_t)t.node_stride * n_nodes;
     const size_t pb = (size_t)t.prim_stride * std::max<size_t>(n_prims, 1);
-    HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, nb));
-    HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, pb));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * std::max<size_t>(6 * n_nodes, 6)));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * std::max<size_t>(2 * n_nodes, 2)));
+    rc = alloc_tree_blocks(ctx, t, n_nodes, 0, n_prims);
+    if (rc != HRT_OK) return rc;
     if (!order.empty()) HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_order, sizeof(uint32_t) * order.size()));
     if (t.node_stride == sizeof(Bvh8Node) && t.prim_stride == sizeof(PrimRecord)) {
         HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, t.bvh.nodes.data(), nb, hipMemcpyHostToDevice, s));
@@ -432,7 +513,6 @@ static int upload_host_tree(HrtContext *ctx, Tlas &t, const std::vector<uint32_t
         HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, t.bvh.node_ref.data(), sizeof(float) * t.bvh.node_ref.size(), hipMemcpyHostToDevice, s));
     if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync(d.d_order, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
     t.n_nodes = (uint32_t)n_nodes; t.n_prims = (uint32_t)n_prims;
-    t.alloc_bytes = (uint64_t)nb + sizeof(float) * 8 * std::max<size_t>(n_nodes, 1) + pb;
     t.n_triangles = t.bvh.n_triangles; t.n_spheres = t.bvh.n_spheres; t.max_depth = t.bvh.max_depth;
     for (int a = 0; a < 3; ++a) { t.lo[a] = t.bvh.lo[a]; t.hi[a] = t.bvh.hi[a]; }
     return HRT_OK;
@@ -490,16 +570,9 @@ static int build_over_instances(HrtContext *ctx, Tlas &t, const std::vector<HrtI
     t.bvh.node_ref.assign(2 * t.bvh.nodes.size(), 0.0f);
     for (size_t i = 0; i < it.weight.size(); ++i) t.bvh.node_ref[2 * i] = it.weight[i];
     for (size_t h = 0; h + 1 < it.phase_begin.size(); ++h) t.phases.emplace_back(it.phase_begin[h], it.phase_begin[h + 1] - it.phase_begin[h]);
-    const int rc = upload_host_tree(ctx, t, it.order, s);
+    int rc = upload_host_tree(ctx, t, it.order, s);
+    if (rc == HRT_OK && t.n_prims) rc = reference_refit(ctx, t, refit_pad(scene_scale), nullptr, s);      // (the host left all but the topology blank)
     if (rc != HRT_OK) return rc;
-    if (t.n_prims) {
-        // the device computes what the host left blank: world-space records, boxes, origins, exponents, quantised
-        // children, and the built areas the quality guard compares later refits with
-        RefitArgs ra = refit_args(ctx, t);
-        ra.pad = refit_pad(scene_scale); ra.write_reference = 1u;
-        launch_refit_phases(ra, t.phases, s);
-        HIP_TRY(ctx, hipGetLastError());
-    }
     HIP_TRY(ctx, hipStreamSynchronize(s));            // (it.order goes out of scope)
     return HRT_OK;
 }
@@ -511,10 +584,10 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     const uint32_t n = t.n_instances;
     const std::vector<uint32_t> &first = plan.first;
     TlasDevice &d = t.dev;
-    const int rc = upload_instance_tables(ctx, t, s);
+    int rc = upload_instance_tables(ctx, t, s);
     if (rc != HRT_OK) return rc;
-    const size_t pb = (size_t)t.prim_stride * std::max<size_t>(first[n], 1);
-    if (!device_split) HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, pb));      // (a split build knows its record count afterwards)
+    // (the records go where they stay; a split build knows its record count afterwards, and stages them)
+    if (!device_split) HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, (size_t)t.prim_stride * std::max<size_t>(first[n], 1)));
     HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_first, sizeof(uint32_t) * first.size()));
     HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_kind, sizeof(uint32_t) * std::max(n, 1u)));
     HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice, s));
@@ -524,56 +597,35 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     GpuBuildInput in = build_input(ctx, kMaxLeafPrims, t.scene_of_bodies ? ctx->build_c_prim_bodies : ctx->build_c_prim, false,
                                    device_split || ctx->build_topdown != 0, device_split ? ctx->split_budget : 0.0f, refit_pad(scene_scale));
     in.n_prims = first[n]; in.n_inst = n; in.d_inst_first = d.d_inst_first; in.d_inst_kind = d.d_inst_kind; in.d_inst_src = d.d_inst_src;
-    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity;
-    // worst-case node output (one node and two reference floats per leaf: primitive, or reference of a spatial split) at the front of the
-    // working memory; a split build's records and their clip boxes too (their number is known afterwards)
-    const size_t max_leaves = gpu_build_max_refs(in.n_prims, &in.split);
-    ArenaLayout lay;
-    const size_t o_nodes = lay.take((size_t)t.node_stride * max_leaves), o_ref = lay.take(sizeof(float) * 2 * max_leaves);
-    const size_t o_prims = lay.take(device_split ? (size_t)t.prim_stride * max_leaves : 0u), o_clip = lay.take(device_split ? sizeof(float) * 6 * max_leaves : 0u);
-    const size_t want = gpu_build_scratch_bytes(in.n_prims, &in.split) + lay.used;
-    ScratchArena arena = scratch_acquire(ctx, want);
-    if (!arena.p && in.split.enabled && !device_split) {      // no room for the top-down phase's buffers: PLOC alone
-        in.split.enabled = false;
-        arena = scratch_acquire(ctx, gpu_build_scratch_bytes(in.n_prims, nullptr) + lay.used);
-    }
-    if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", want);
-    ArenaRelease release{ctx, arena, s};
-    lay.base = static_cast<unsigned char *>(arena.p);
-    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = t.node_stride; in.out_node_ref = lay.at<float>(o_ref);
-    in.out_prims = device_split ? lay.at<unsigned char>(o_prims) : static_cast<unsigned char *>(d.d_prims); in.prim_stride = t.prim_stride;
-    in.out_clip = device_split ? lay.at<float>(o_clip) : nullptr;
-    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
+    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity; in.node_stride = t.node_stride; in.prim_stride = t.prim_stride;
+    in.out_prims = static_cast<unsigned char *>(d.d_prims);
     // a fast-trace build: the reinsertion pass over the finished BVH2 (not where the top-down phase gives up and PLOC alone builds the tree: build.hip)
     if (device_split) { in.reinsert_rounds = ctx->reinsert_rounds; in.reinsert_max_depth = (uint32_t)ctx->fused_max_depth; }
-    GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
+    StagedBuild sb{ctx, s};
+    if (!sb.stage(in, gpu_build_max_refs(in.n_prims, &in.split), device_split ? StagedRecords::RecordsAndClip : StagedRecords::None, !device_split))
+        return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", sb.want);
+    GpuBuildResult r;
+    rc = sb.build(in, "device build", r);
     // A tree deeper than any kernel's stack (a chain of primitives over many orders of magnitude: nearest-neighbour clustering, like SAH, takes
     // one off the rest at every level): built again by position -- every cluster with its Morton neighbour, log2(n) levels, whatever the areas
     // (a split build too: the tree by position has no splits, its records are the primitives -- the staged buffers hold them all the same)
-    if (r.error == hipSuccess && r.n_prims != 0u && too_deep(r.max_depth)) {
+    if (rc == HRT_OK && r.n_prims != 0u && too_deep(r.max_depth)) {
         if (ctx->build_verbose) std::fprintf(stderr, "[hrt] the tree is %u levels deep: built again by position\n", r.max_depth);
         in.balanced = true; in.split.enabled = false; in.reinsert_rounds = 0;
-        r = gpu_build_bvh8(in, s);
+        rc = sb.build(in, "device build", r);
     }
-    if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build failed: %s (%s)", hipGetErrorString(r.error), r.where);
+    if (rc != HRT_OK) return rc;
     {   // the tree's own buffers, as large as the build turned out to need (the build emitted its nodes into the working memory, sized for
         // the worst case: one node per primitive; typically a seventh is used)
         const size_t nn = std::max<size_t>(r.n_prims ? r.n_nodes : 1u, 1u);
-        HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, (size_t)t.node_stride * nn));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * 6 * nn));
-        HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * 2 * nn));
-        size_t rec_bytes = pb;
-        if (device_split) {
-            rec_bytes = (size_t)t.prim_stride * std::max<size_t>(r.n_records, 1);
-            HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, rec_bytes));
-            if (r.n_records) HIP_TRY(ctx, hipMemcpyAsync(d.d_prims, in.out_prims, (size_t)t.prim_stride * r.n_records, hipMemcpyDeviceToDevice, s));
-        }
+        rc = alloc_tree_blocks(ctx, t, nn, 0, device_split ? r.n_records : first[n]);
+        if (rc != HRT_OK) return rc;
+        if (device_split && r.n_records) HIP_TRY(ctx, hipMemcpyAsync(d.d_prims, in.out_prims, (size_t)t.prim_stride * r.n_records, hipMemcpyDeviceToDevice, s));
         if (r.n_prims) {
             HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, in.out_nodes, (size_t)t.node_stride * nn, hipMemcpyDeviceToDevice, s));
             HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, in.out_node_ref, sizeof(float) * 2 * nn, hipMemcpyDeviceToDevice, s));
             HIP_TRY(ctx, hipStreamSynchronize(s));         // the working memory goes back to the context when this scope ends
         }
-        t.alloc_bytes = (uint64_t)t.node_stride * nn + sizeof(float) * 8 * nn + rec_bytes;
     }
     t.bvh = Bvh8();
     if (r.n_prims == 0u) {
@@ -590,14 +642,12 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     t.n_triangles = plan.n_tri_in >= dropped ? plan.n_tri_in - dropped : 0u; t.n_spheres = r.n_prims - t.n_triangles;
     for (int a = 0; a < 3; ++a) { t.lo[a] = r.lo[a]; t.hi[a] = r.hi[a]; }
     t.phases = phases_from_levels(r.level_begin);
-    RefitArgs ra = refit_args(ctx, t);
-    ra.pad = in.split.pad; ra.write_reference = 1u;
     // (a split build: every record's box is the one its cell is responsible for, not the primitive's -- this once; a later
     // update would recompute the boxes from whole primitives, so the first update rebuilds instead: has_split_refs)
-    if (device_split && r.split_levels) { ra.clip = in.out_clip; t.has_split_refs = true; }
-    launch_refit_phases(ra, t.phases, s);
-    HIP_TRY(ctx, hipGetLastError());
-    if (device_split && r.split_levels) HIP_TRY(ctx, hipStreamSynchronize(s));      // (the clip boxes live in the working memory)
+    t.has_split_refs = device_split && r.split_levels;
+    rc = reference_refit(ctx, t, in.split.pad, t.has_split_refs ? in.out_clip : nullptr, s);
+    if (rc != HRT_OK) return rc;
+    if (t.has_split_refs) HIP_TRY(ctx, hipStreamSynchronize(s));      // (the clip boxes live in the working memory)
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] device build: %u primitives -> %u records, %u nodes, depth %u, %u PLOC rounds (radius %d), %u split levels, %u cells\n",
                      r.n_prims, r.n_records, r.n_nodes, r.max_depth, r.ploc_rounds, ctx->ploc_radius, r.split_levels, r.n_cells);
@@ -638,44 +688,30 @@ static int upload_blas_bounds(HrtContext *ctx, Tlas &t, std::vector<const void *
     return HRT_OK;
 }
 
-// The object-space tree a two-level TLAS copies in for one of its BLASes: the template (Blas::tmpl / d_tmpl_*), or under HRT_CTX_FAST_TRACE
-// the tree with spatial splits (Blas::split) where the BLAS has one.  (Both are written once, under Blas::tmpl_mu, and never change.)
-struct PackedTree {
-    const unsigned char *d_nodes = nullptr, *d_prims = nullptr; const float *d_clip = nullptr;
-    uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
-    const std::vector<uint32_t> *level_begin = nullptr;
-};
-static int packed_tree_of(HrtContext *ctx, Blas &b, bool fast_trace, hipStream_t s, PackedTree &out) {
+// The object-space tree a two-level TLAS copies in for one of its BLASes: the template (Blas::tmpl_dev), or under HRT_CTX_FAST_TRACE the tree
+// with spatial splits (Blas::split) where the BLAS has one.  (Both are written once, under Blas::tmpl_mu, and never change.)
+static int packed_tree_of(HrtContext *ctx, Blas &b, bool fast_trace, hipStream_t s, const BlasTree *&out) {
     if (fast_trace) {
         const int rc = ensure_split_template(ctx, b, s);
         if (rc != HRT_OK) return rc;
         bool have;
         { std::lock_guard<std::mutex> lk(b.tmpl_mu); have = b.split.d_nodes != nullptr; }
-        if (have) {
-            const Blas::SplitTree &t = b.split;
-            out.d_nodes = t.d_nodes; out.d_prims = t.d_prims; out.d_clip = t.d_clip; out.n_nodes = t.n_nodes; out.n_records = t.n_records;
-            out.n_triangles = t.n_triangles; out.n_spheres = t.n_spheres; out.max_depth = t.max_depth; out.level_begin = &t.level_begin;
-            return HRT_OK;
-        }
+        if (have) { out = &b.split; return HRT_OK; }
     }
-    const int rc = ensure_template(ctx, b, s, true);
-    if (rc != HRT_OK) return rc;
-    const Bvh8 &tp = b.tmpl;
-    out.d_nodes = b.d_tmpl_nodes; out.d_prims = b.d_tmpl_prims; out.n_nodes = (uint32_t)tp.nodes.size(); out.n_records = (uint32_t)tp.prims.size();
-    out.n_triangles = tp.n_triangles; out.n_spheres = tp.n_spheres; out.max_depth = tp.max_depth; out.level_begin = &tp.level_begin;
-    return HRT_OK;
+    out = &b.tmpl_dev;
+    return ensure_template(ctx, b, s, true);
 }
 
 // The refit of the packed BLAS trees, all BLASes at once: phase k = the k-th level from the bottom of every tree (a template is stored breadth
 // first, children one level below their parents), walked through an order array of node indices.
-static void pack_refit_order(const std::vector<PackedTree> &trees, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
+static void pack_refit_order(const std::vector<const BlasTree *> &trees, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
                              std::vector<uint32_t> &order, std::vector<std::pair<uint32_t, uint32_t>> &pack_phases) {
     const uint32_t nu = (uint32_t)trees.size();
     order.reserve(node_off[nu]);
     for (uint32_t k = 0; k <= blas_depth; ++k) {
         const uint32_t begin = (uint32_t)order.size();
         for (uint32_t j = 0; j < nu; ++j) {
-            const std::vector<uint32_t> &lb = *trees[j].level_begin;
+            const std::vector<uint32_t> &lb = trees[j]->level_begin;
             const uint32_t levels = lb.empty() ? 0u : (uint32_t)lb.size() - 1u;
             if (k >= levels) continue;
             const uint32_t l = levels - 1u - k;
@@ -702,24 +738,24 @@ static float object_space_reach(const Tlas &t, const std::vector<Blas *> &uniq, 
     return std::max(reach, obj_coord);
 }
 
-static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const BuildPlan &plan, bool fast_trace, float scene_scale, hipStream_t s) {
+// flatten_instead: the two-level tree asked for cannot be had (nothing valid to instance; too deep for the path kernel's stack, or too large
+// for it): nothing is wrong, and the caller builds the flattened one.
+static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, const BuildPlan &plan, bool fast_trace, float scene_scale, hipStream_t s, bool &flatten_instead) {
     const uint32_t n = t.n_instances;
     const std::vector<Blas *> &uniq = plan.uniq;
     const uint32_t nu = (uint32_t)uniq.size();
     TlasDevice &d = t.dev;
-    {
-        std::vector<const void *> src;
-        int rc = upload_blas_bounds(ctx, t, src, s);
-        if (rc == HRT_OK) rc = upload_instance_tables(ctx, t, src, s);
-        if (rc != HRT_OK) return rc;
-    }
+    std::vector<const void *> src;
+    int rc = upload_blas_bounds(ctx, t, src, s);
+    if (rc == HRT_OK) rc = upload_instance_tables(ctx, t, src, s);
+    if (rc != HRT_OK) return rc;
     std::vector<uint32_t> node_off(nu + 1, 0u), prim_off(nu + 1, 0u);
-    std::vector<PackedTree> trees(nu);
+    std::vector<const BlasTree *> trees(nu, nullptr);
     uint32_t blas_depth = 0, n_split = 0;
     for (uint32_t j = 0; j < nu; ++j) {
-        const int rc = packed_tree_of(ctx, *uniq[j], fast_trace, s, trees[j]);
+        rc = packed_tree_of(ctx, *uniq[j], fast_trace, s, trees[j]);
         if (rc != HRT_OK) return rc;
-        const PackedTree &tp = trees[j];
+        const BlasTree &tp = *trees[j];
         if ((uint64_t)node_off[j] + tp.n_nodes > 0x7fffffffull || (uint64_t)prim_off[j] + tp.n_records > 0x7fffffffull) return fail(ctx, HRT_ERR_INVALID, "two-level tree: more than 2^31 nodes or records");
         node_off[j + 1] = node_off[j] + tp.n_nodes; prim_off[j + 1] = prim_off[j] + tp.n_records;
         blas_depth = std::max(blas_depth, tp.max_depth);
@@ -737,35 +773,26 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     GpuBuildInput in = build_input(ctx, 1, ctx->build_c_prim, true, ctx->build_topdown != 0, 0.0f, refit_pad(scene_scale));
     in.width = 8;      // (HRT_BVH_WIDTH, the flattened trees' measuring knob, does not reach the top level)
     in.n_prims = n2; in.n_inst = n; in.d_inst_first = d.d_inst_first; in.d_inst_kind = d.d_inst_kind; in.d_inst_src = d.d_inst_src;
-    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity;
-    // worst case: a transform node per instance and fewer box nodes than instances
-    const size_t max_nodes = 2 * (size_t)n2 + 2;
-    ArenaLayout lay;
-    const size_t o_nodes = lay.take((size_t)t.node_stride * max_nodes), o_ref = lay.take(sizeof(float) * 2 * max_nodes);
+    in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity; in.node_stride = t.node_stride; in.prim_stride = t.prim_stride;
+    StagedBuild sb{ctx, s};
+    ArenaLayout &lay = sb.lay;
     // (the pack's refit tables and walk order share the block: nu small tables, one entry per BLAS node)
     const size_t o_pxf = lay.take(sizeof(float) * 12 * nu), o_pid = lay.take(sizeof(uint32_t) * nu), o_psrc = lay.take(sizeof(void *) * nu);
     const size_t o_porder = lay.take(sizeof(uint32_t) * (size_t)node_off[nu]);
     // (... and, where a BLAS tree has spatial splits, the box the pack's refit takes for every record of the TLAS: the BLASes keep their own copies)
     const size_t o_pclip = lay.take(n_split ? sizeof(float) * 6 * (size_t)prim_off[nu] : 0u);
-    const size_t want = gpu_build_scratch_bytes(n2, &in.split) + lay.used;
-    const ScratchArena arena = scratch_acquire(ctx, want);
-    if (!arena.p) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", want);
-    ArenaRelease release{ctx, arena, s};
-    lay.base = static_cast<unsigned char *>(arena.p);
-    in.out_nodes = lay.at<unsigned char>(o_nodes); in.node_stride = t.node_stride; in.out_node_ref = lay.at<float>(o_ref);
-    in.out_prims = in.out_nodes; in.prim_stride = t.prim_stride;        // (no record is written: the leaves are transform nodes)
-    in.scratch = lay.base + lay.used; in.scratch_bytes = arena.bytes - lay.used;
-    const GpuBuildResult r = gpu_build_bvh8(in, s);      // (synchronises the stream before it returns)
-    if (r.error != hipSuccess) return fail(ctx, r.error == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, "device build of the top level failed: %s (%s)", hipGetErrorString(r.error), r.where);
-    if (r.n_prims == 0u) return kRetryFlattened;                                 // nothing valid to instance: the flattened path emits the empty root
-    // the path kernel keeps one sibling group per level of BOTH trees on its node stack
-    if (r.max_depth + 1u + blas_depth > (uint32_t)ctx->fused_max_depth) return kRetryFlattened;
+    // worst case: a transform node per instance and fewer box nodes than instances
+    if (!sb.stage(in, 2 * (size_t)n2 + 2, StagedRecords::None, false)) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", sb.want);
+    in.out_prims = in.out_nodes;        // (no record is written: the leaves are transform nodes)
+    GpuBuildResult r;
+    rc = sb.build(in, "device build of the top level", r);
+    if (rc != HRT_OK) return rc;
+    // nothing valid to instance (the flattened path emits the empty root); the path kernel keeps one sibling group per level of BOTH trees on its node stack
+    if (r.n_prims == 0u || r.max_depth + 1u + blas_depth > (uint32_t)ctx->fused_max_depth) { flatten_instead = true; return HRT_OK; }
     const uint32_t n_top = r.n_nodes, n_all = n_top + node_off[nu], n_rec = prim_off[nu];
-    if ((uint64_t)n_all * t.node_stride >= ctx->fused_max_bytes || (uint64_t)std::max(n_rec, 1u) * t.prim_stride >= ctx->fused_max_bytes) return kRetryFlattened;
-    HIP_TRY(ctx, pool_alloc(ctx, &d.d_nodes, (size_t)t.node_stride * n_all + 16));       // (+16: the path kernel reads 80 bytes of the last node whatever its stride)
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_box, sizeof(float) * 6 * (size_t)n_all));
-    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_node_ref, sizeof(float) * 2 * (size_t)n_all));
-    HIP_TRY(ctx, pool_alloc(ctx, &d.d_prims, (size_t)t.prim_stride * std::max(n_rec, 1u)));
+    if ((uint64_t)n_all * t.node_stride >= ctx->fused_max_bytes || (uint64_t)std::max(n_rec, 1u) * t.prim_stride >= ctx->fused_max_bytes) { flatten_instead = true; return HRT_OK; }
+    rc = alloc_tree_blocks(ctx, t, n_all, 16, n_rec);       // (+16: the path kernel reads 80 bytes of the last node whatever its stride)
+    if (rc != HRT_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d.d_nodes, in.out_nodes, (size_t)t.node_stride * n_top, hipMemcpyDeviceToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d.d_node_ref, in.out_node_ref, sizeof(float) * 2 * (size_t)n_top, hipMemcpyDeviceToDevice, s));
     // (3) the BLAS trees behind the top level
@@ -774,10 +801,10 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_root, roots.data(), sizeof(uint32_t) * roots.size(), hipMemcpyHostToDevice, s));
     for (uint32_t j = 0; j < nu; ++j) {
         PackBlasArgs pa{};
-        pa.src_nodes = trees[j].d_nodes; pa.src_prims = trees[j].d_prims; pa.n_nodes = node_off[j + 1] - node_off[j]; pa.n_prims = prim_off[j + 1] - prim_off[j];
+        pa.src_nodes = trees[j]->d_nodes; pa.src_prims = trees[j]->d_prims; pa.n_nodes = node_off[j + 1] - node_off[j]; pa.n_prims = prim_off[j + 1] - prim_off[j];
         pa.dst_nodes = reinterpret_cast<unsigned char *>(d.d_nodes); pa.dst_prims = reinterpret_cast<unsigned char *>(d.d_prims); pa.node_stride = t.node_stride; pa.prim_stride = t.prim_stride;
         pa.node_off = n_top + node_off[j]; pa.prim_off = prim_off[j]; pa.slot = j;
-        if (n_split) { pa.dst_clip = lay.at<float>(o_pclip); pa.src_clip = trees[j].d_clip; pa.src_geom = uniq[j]->d_verts; }
+        if (n_split) { pa.dst_clip = lay.at<float>(o_pclip); pa.src_clip = trees[j]->d_clip; pa.src_geom = uniq[j]->d_verts; }
         launch_pack_blas(pa, s);
     }
     // their refit: per-BLAS tables with the identity transform
@@ -803,10 +830,8 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     // (4) the top level
     t.two_level = true; t.n_top_nodes = n_top; t.n_unique_blas = nu;
     t.phases = phases_from_levels(r.level_begin);
-    RefitArgs ra = refit_args(ctx, t);
-    ra.pad = in.split.pad; ra.write_reference = 1u;
-    launch_refit_phases(ra, t.phases, s);
-    HIP_TRY(ctx, hipGetLastError());
+    rc = reference_refit(ctx, t, in.split.pad, nullptr, s);
+    if (rc != HRT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s));
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] two-level build: %u instances over %u BLASes (%u with spatial splits) -> %u top nodes (depth %u, %u split levels), %u BLAS nodes (depth <= %u), %u records (flattened: %u)\n",
@@ -814,24 +839,12 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     t.bvh = Bvh8();
     t.n_nodes = n_all; t.n_prims = n_rec; t.max_depth = r.max_depth + 1u + blas_depth;
     t.n_triangles = t.n_spheres = 0;
-    for (uint32_t j = 0; j < nu; ++j) { t.n_triangles += trees[j].n_triangles; t.n_spheres += trees[j].n_spheres; }
-    t.alloc_bytes = (uint64_t)t.node_stride * n_all + sizeof(float) * 8 * (uint64_t)n_all + (uint64_t)t.prim_stride * std::max(n_rec, 1u);
+    for (uint32_t j = 0; j < nu; ++j) { t.n_triangles += trees[j]->n_triangles; t.n_spheres += trees[j]->n_spheres; }
     for (int a = 0; a < 3; ++a) { t.lo[a] = r.lo[a]; t.hi[a] = r.hi[a]; }
     return HRT_OK;
 }
 
 // ---- what to build, decided once ----
-
-// the split build's working memory (~1.2 KB per primitive with the staged output) has to be there: otherwise the default build
-static bool split_build_fits(HrtContext *ctx, uint32_t n_prims) {
-    SplitParams probe; probe.enabled = true; probe.budget_frac = ctx->split_budget; probe.cell_refs = (uint32_t)ctx->split_cell_refs;
-    const size_t leaves = gpu_build_max_refs(n_prims, &probe);
-    const size_t want = gpu_build_scratch_bytes(n_prims, &probe) + leaves * (size_t)(128 + 8 + ctx->prim_stride + 24);
-    size_t free_b = 0, total_b = 0, kept = 0;      // (what the context keeps for later counts as free: an allocation that fails gives it back first)
-    { std::lock_guard<std::mutex> lk(ctx->scratch_mu); for (const ScratchArena &x : ctx->scratch_free) kept += x.bytes; }
-    { std::lock_guard<std::mutex> lk(ctx->pool_mu); kept += ctx->pool_bytes; }
-    return leaves <= (1u << 30) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want <= (free_b + kept) / 10 * 9;
-}
 
 // Two levels or one?  Flattening costs memory, build and refit time in proportion to instances x primitives; a two-level tree
 // (transform nodes over one shared tree per BLAS) in proportion to instances + unique primitives, at the price of a ray
@@ -882,7 +895,10 @@ static int plan_build(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &
     return HRT_OK;
 }
 
-static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, hipStream_t s, bool instanced, bool fast_trace, int two_level_mode) {
+// flatten_instead: nothing was built, because the two-level tree that was asked for or chosen cannot be had (build_two_level) -- to be called
+// again with two_level_mode < 0
+static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, hipStream_t s, bool instanced, bool fast_trace, int two_level_mode, bool &flatten_instead) {
+    flatten_instead = false;
     const uint32_t n = (uint32_t)inst.size();
     std::vector<std::shared_ptr<Blas>> refs(n);
     {
@@ -916,9 +932,9 @@ static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInsta
     case TreeKind::OverInstances: rc = build_over_instances(ctx, t, inst, scene_scale, s); break;
     case TreeKind::DeviceMerged:  rc = build_merged_on_device(ctx, t, plan, false, scene_scale, s); break;
     case TreeKind::DeviceSplit:   rc = build_merged_on_device(ctx, t, plan, true, scene_scale, s); break;
-    case TreeKind::TwoLevel:      rc = build_two_level(ctx, t, inst, plan, fast_trace, scene_scale, s); break;
+    case TreeKind::TwoLevel:      rc = build_two_level(ctx, t, inst, plan, fast_trace, scene_scale, s, flatten_instead); break;
     }
-    if (rc != HRT_OK) return rc;
+    if (rc != HRT_OK || flatten_instead) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(s));
     t.instanced = plan.kind == TreeKind::OverInstances;
     t.fast_trace = fast_trace;
@@ -935,11 +951,12 @@ int build_tlas_into(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &in
     if (t.area_ready && t.area_pending) (void)hipEventSynchronize(t.area_ready);
     fresh.h_area = t.h_area; fresh.h_update_flags = t.h_update_flags; fresh.area_ready = t.area_ready;
     t.h_area = nullptr; t.h_update_flags = nullptr; t.area_ready = nullptr;
-    int rc = build_tlas_fresh(ctx, fresh, inst, s, instanced, fast_trace, two_level_mode);
-    if (rc == kRetryFlattened) {
+    bool flatten_instead;
+    int rc = build_tlas_fresh(ctx, fresh, inst, s, instanced, fast_trace, two_level_mode, flatten_instead);
+    if (rc == HRT_OK && flatten_instead) {
         free_tlas_device(ctx, fresh);
         fresh.two_level = false; fresh.phases.clear();
-        rc = build_tlas_fresh(ctx, fresh, inst, s, instanced, fast_trace, -1);
+        rc = build_tlas_fresh(ctx, fresh, inst, s, instanced, fast_trace, -1, flatten_instead);
     }
     if (rc != HRT_OK) {
         t.h_area = fresh.h_area; t.h_update_flags = fresh.h_update_flags; t.area_ready = fresh.area_ready;
@@ -981,40 +998,10 @@ int download_instances(HrtContext *ctx, const HrtInstance *d_instances, uint32_t
     return HRT_OK;
 }
 
-// The phases of a refit, children before parents: wide phases get a launch each, the narrow ones at the end (the top
-// of the tree, or all of a small tree) run in one single-workgroup launch.
-void launch_refit_phases(RefitArgs ra, const std::vector<std::pair<uint32_t, uint32_t>> &phases, hipStream_t s) {
-    launch_refit_records(ra, s);                               // (small trees: ra.rec_box)
-    size_t tail = phases.size();
-    while (tail > 0 && phases.size() - tail < kRefitTopLevels && phases[tail - 1].second <= kRefitTopLevelNodes) --tail;
-    for (size_t i = 0; i < tail; ++i) { ra.first_node = phases[i].first; ra.n_nodes = phases[i].second; launch_refit_level(ra, s); }
-    RefitLevels top{};
-    for (size_t i = tail; i < phases.size(); ++i) { top.first[top.n_levels] = phases[i].first; top.count[top.n_levels] = phases[i].second; ++top.n_levels; }
-    launch_refit_top(ra, top, s);
-}
+// ---- updates (hrt_tlas_update) ----
 
-// Small trees (the reference's own scenes) are refitted in one workgroup that walks the levels; the records' arithmetic -- most of the
-// work, and a chain of dependent loads -- runs before that, a thread per record, into 24 bytes per record (k_refit_records).
-constexpr uint32_t kRecBoxMaxRecords = 65536;
-static void attach_rec_box(HrtContext *ctx, Tlas &t, RefitArgs &ra, uint32_t n_records) {
-    if (n_records == 0u || n_records > kRecBoxMaxRecords) return;
-    if (!t.dev.d_rec_box && pool_alloc(ctx, (void **)&t.dev.d_rec_box, sizeof(float) * 6 * (size_t)n_records) != hipSuccess) { (void)hipGetLastError(); t.dev.d_rec_box = nullptr; return; }
-    ra.rec_box = t.dev.d_rec_box; ra.n_records = n_records;
-}
-
-// What every refit of a tree takes from it (its counts and two_level are set).  The caller adds what differs: the padding (`pad`, or `scale_bits`
-// when the scene scale is on the device), `area_sum` or `write_reference`, `clip`.
-static RefitArgs refit_args(HrtContext *ctx, Tlas &t) {
-    const TlasDevice &d = t.dev;
-    RefitArgs ra{};
-    ra.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); ra.node_stride = t.node_stride;
-    ra.prims = reinterpret_cast<unsigned char *>(d.d_prims); ra.prim_stride = t.prim_stride;
-    ra.node_box = d.d_node_box; ra.node_ref = d.d_node_ref; ra.inst_xf = d.d_inst_xf; ra.inst_identity = d.d_inst_identity; ra.inst_src = d.d_inst_src;
-    ra.order = d.d_order;
-    if (t.two_level) { ra.inst_inv = d.d_inst_inv; ra.inst_root = d.d_inst_root; }      // (the top level only: transform nodes and the boxes above them)
-    else attach_rec_box(ctx, t, ra, t.n_prims);
-    return ra;
-}
+// (an update's refit has been enqueued; its verdict is asked for later: take_refit_verdict)
+static void refit_enqueued(HrtContext *ctx, Tlas &t) { t.area_pending = true; t.refits++; t.refits_since_build++; ctx->tlas_refits++; }
 
 // Device refit of a built tree under new instance transforms: upload the per-instance tables, then one
 // k_refit_level launch per tree level, deepest first.  Asynchronous on s.
@@ -1032,8 +1019,54 @@ int refit_tlas(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, h
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(t.h_area, t.dev.d_area, sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipEventRecord(t.area_ready, s));
-    t.area_pending = true;
-    t.refits++; t.refits_since_build++; ctx->tlas_refits++;
+    refit_enqueued(ctx, t);
+    return HRT_OK;
+}
+
+// The verdict of the last refit (pending: t.area_pending), waited for: how much the boxes have grown since the build.  A refit keeps the
+// topology; `still_good`: not by so much yet that a fresh build pays for itself.
+static int take_refit_verdict(HrtContext *ctx, Tlas &t, bool &still_good) {
+    HIP_TRY(ctx, hipEventSynchronize(t.area_ready));
+    t.area_pending = false;
+    ctx->tlas_refit_ratio = (double)*t.h_area;
+    still_good = ctx->tlas_refit_ratio <= (double)ctx->refit_rebuild_ratio;
+    return HRT_OK;
+}
+
+// An asynchronous update (HRT_CTX_ASYNC_UPDATE): nothing is read back now.  First the verdict of the previous one (long complete), which
+// may say that this update has to take the synchronous path instead: to rebuild, or to re-read the sbtOffsets.
+enum class AsyncUpdate { Done, Rebuild, RereadSbt };
+static int update_async(HrtContext *ctx, Tlas *t, const HrtInstance *d_instances, uint32_t n, hipStream_t s, AsyncUpdate &outcome) {
+    if (t->area_pending) {
+        bool still_good;
+        const int rc = take_refit_verdict(ctx, *t, still_good);
+        if (rc != HRT_OK) return rc;
+        const uint32_t changed = t->h_update_flags[1];      // (bit 0: a handle or visibility bit; bit 1: an sbtOffset)
+        t->h_update_flags[1] = 0u;
+        if (!still_good || (changed & 1u) != 0u) { outcome = AsyncUpdate::Rebuild; return HRT_OK; }
+        if ((changed & 2u) != 0u) { outcome = AsyncUpdate::RereadSbt; return HRT_OK; }
+    }
+    // (the device words the tables kernel and the refit accumulate into -- scene scale, verdict bits, area sum -- are left in their
+    // initial state by the previous asynchronous update's epilogue; after a build or a synchronous update they are set here)
+    if (!t->async_words_ready) {
+        HIP_TRY(ctx, hipMemcpyAsync(t->dev.d_update_flags, t->h_update_flags + 2, sizeof(uint32_t) * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemsetAsync(t->dev.d_area, 0, sizeof(float), s));
+        t->async_words_ready = true;
+    }
+    InstanceTableArgs ia{};
+    ia.instances = d_instances; ia.n = n; ia.sig_handle = t->dev.d_sig_handle; ia.sig_visibility = t->dev.d_sig_visibility; ia.sig_sbt = t->dev.d_sig_sbt; ia.blas_box = t->dev.d_blas_box;
+    ia.inst_xf = t->dev.d_inst_xf; ia.inst_inv = t->dev.d_inst_inv; ia.inst_identity = t->dev.d_inst_identity; ia.flags = t->dev.d_update_flags;
+    launch_instance_tables(ia, s);
+    RefitArgs ra = refit_args(ctx, *t);
+    ra.scale_bits = t->dev.d_update_flags; ra.area_sum = t->dev.d_area;
+    { Timer tm(ctx, s, HRT_K_REFIT); launch_refit_phases(ra, t->phases, s); }
+    // one launch where there were two copies to the host, one from it and a fill: results to pinned memory, device words reset
+    UpdateEpilogueArgs ue{t->dev.d_area, t->dev.d_update_flags, t->h_area, t->h_update_flags, t->h_update_flags[2], t->h_update_flags[3]};
+    launch_update_epilogue(ue, s);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(t->area_ready, s));
+    refit_enqueued(ctx, *t);
+    outcome = AsyncUpdate::Done;
     return HRT_OK;
 }
 
@@ -1164,45 +1197,16 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     if (ctx->capture.tlas == tlas) ctx->capture.valid = false;      // (the primary hits of the tree as it was: a refit keeps the generation)
     if (n != t->n_instances) return fail(ctx, HRT_ERR_INVALID, "update must keep the instance count (%u != %u)", n, t->n_instances);
     if (n && !d_instances) return fail(ctx, HRT_ERR_INVALID, "d_instances is NULL");
-    bool force_rebuild = false, sbt_sync = false;
+    bool force_rebuild = false;
     // (the first update after a build takes the synchronous path below, which checks that refit on the spot: see there)
     if ((ctx->flags & HRT_CTX_ASYNC_UPDATE) != 0 && ctx->refit != 0 && t->n_prims != 0u && n != 0u && (t->refits_since_build != 0 || t->built_posed)) {
-        // ---- asynchronous update: nothing is read back now.  First the verdict of the previous one (long complete). ----
-        if (t->area_pending) {
-            HIP_TRY(ctx, hipEventSynchronize(t->area_ready));
-            t->area_pending = false;
-            ctx->tlas_refit_ratio = (double)*t->h_area;
-            if (!(ctx->tlas_refit_ratio <= (double)ctx->refit_rebuild_ratio) || (t->h_update_flags[1] & 1u) != 0u) force_rebuild = true;
-            else if ((t->h_update_flags[1] & 2u) != 0u) sbt_sync = true;      // an sbtOffset changed: the synchronous path below re-reads them
-            t->h_update_flags[1] = 0u;
-        }
-        if (!force_rebuild && !sbt_sync) {
-            // (the device words the tables kernel and the refit accumulate into -- scene scale, verdict bits, area sum -- are left in their
-            // initial state by the previous asynchronous update's epilogue; after a build or a synchronous update they are set here)
-            if (!t->async_words_ready) {
-                HIP_TRY(ctx, hipMemcpyAsync(t->dev.d_update_flags, t->h_update_flags + 2, sizeof(uint32_t) * 2, hipMemcpyHostToDevice, s));
-                HIP_TRY(ctx, hipMemsetAsync(t->dev.d_area, 0, sizeof(float), s));
-                t->async_words_ready = true;
-            }
-            InstanceTableArgs ia{};
-            ia.instances = d_instances; ia.n = n; ia.sig_handle = t->dev.d_sig_handle; ia.sig_visibility = t->dev.d_sig_visibility; ia.sig_sbt = t->dev.d_sig_sbt; ia.blas_box = t->dev.d_blas_box;
-            ia.inst_xf = t->dev.d_inst_xf; ia.inst_inv = t->dev.d_inst_inv; ia.inst_identity = t->dev.d_inst_identity; ia.flags = t->dev.d_update_flags;
-            launch_instance_tables(ia, s);
-            RefitArgs ra = refit_args(ctx, *t);
-            ra.scale_bits = t->dev.d_update_flags; ra.area_sum = t->dev.d_area;
-            { Timer tm(ctx, s, HRT_K_REFIT); launch_refit_phases(ra, t->phases, s); }
-            // one launch where there were two copies to the host, one from it and a fill: results to pinned memory, device words reset
-            UpdateEpilogueArgs ue{t->dev.d_area, t->dev.d_update_flags, t->h_area, t->h_update_flags, t->h_update_flags[2], t->h_update_flags[3]};
-            launch_update_epilogue(ue, s);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipEventRecord(t->area_ready, s));
-            t->area_pending = true;
-            t->refits++; t->refits_since_build++; ctx->tlas_refits++;
-            return HRT_OK;
-        }
+        AsyncUpdate outcome;
+        const int rc = update_async(ctx, t, d_instances, n, s, outcome);
+        if (rc != HRT_OK || outcome == AsyncUpdate::Done) return rc;
+        force_rebuild = outcome == AsyncUpdate::Rebuild;      // (RereadSbt: an sbtOffset changed, the synchronous path below re-reads them)
     }
     std::vector<HrtInstance> inst;
-    const int rc = download_instances(ctx, d_instances, n, s, inst);
+    int rc = download_instances(ctx, d_instances, n, s, inst);
     if (rc != HRT_OK) return rc;
     // (a tree with split references is a static-scene tree: refitted, its leaves would fall back to whole-primitive boxes around
     // duplicated records -- worse than no splits -- so the first update replaces it by a device-built tree)
@@ -1212,11 +1216,8 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     bool moved_far = false;
     if (same && t->refits_since_build == 0 && ctx->refit_moved_far_check && instances_moved_far(*t, inst)) { same = false; moved_far = true; }
     if (same && t->area_pending) {
-        HIP_TRY(ctx, hipEventSynchronize(t->area_ready));
-        t->area_pending = false;
-        // a refit keeps the topology: once the boxes have grown this much, a fresh build pays for itself
-        ctx->tlas_refit_ratio = (double)*t->h_area;
-        if (!(ctx->tlas_refit_ratio <= (double)ctx->refit_rebuild_ratio)) same = false;
+        rc = take_refit_verdict(ctx, *t, same);
+        if (rc != HRT_OK) return rc;
     }
     if (same) {
         bool sbt_changed = false;
@@ -1227,16 +1228,14 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
             HIP_TRY(ctx, hipStreamSynchronize(s));
         }
         const bool first_after_build = t->refits_since_build == 0;
-        const int rc = refit_tlas(ctx, *t, inst, s);
+        rc = refit_tlas(ctx, *t, inst, s);
         if (rc != HRT_OK || !first_after_build) return rc;
         // The first refit after a build is checked on the spot (one stream synchronisation per build): the reference builds
         // every file's IAS with identity transforms and poses it afterwards (RendererTime.cu:111-127), so this is the refit
         // that turns a tree built over coinciding particles into the real scene -- and the frame that follows would be
         // traced through boxes that span everything.  Later refits are checked asynchronously, at the next update.
-        HIP_TRY(ctx, hipEventSynchronize(t->area_ready));
-        t->area_pending = false;
-        ctx->tlas_refit_ratio = (double)*t->h_area;
-        if (ctx->tlas_refit_ratio <= (double)ctx->refit_rebuild_ratio) return HRT_OK;
+        rc = take_refit_verdict(ctx, *t, same);
+        if (rc != HRT_OK || same) return rc;
     }
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] update %llu of this tree rebuilds: %s (area ratio %.3f, %llu refits since the build)\n", (unsigned long long)(t->refits + t->rebuilds),

@@ -27,6 +27,16 @@
 
 namespace hrt {
 
+// An object-space tree of a BLAS on the device, as a two-level TLAS copies it in: topology in packed 80 / 48 byte records, stored breadth
+// first (nodes of level l: [level_begin[l], level_begin[l + 1])).  d_clip: a tree with spatial splits has the box of every record's part of
+// its primitive (6 floats per record: what the pack's refit takes instead of the primitive's own box); NULL otherwise.  Written once, under
+// Blas::tmpl_mu, and never changed; the BLAS owns the three blocks (hipMalloc).
+struct BlasTree {
+    unsigned char *d_nodes = nullptr, *d_prims = nullptr; float *d_clip = nullptr;
+    uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
+    std::vector<uint32_t> level_begin;
+};
+
 struct Blas {
     uint32_t kind = kPrimKindTriangle;
     uint32_t n_prims = 0;
@@ -41,20 +51,17 @@ struct Blas {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};   // object-space bounds
     // object-space BVH8 of this geometry alone: the per-instance subtree of the trees over instances (built on first use)
     std::mutex tmpl_mu; bool tmpl_built = false; Bvh8 tmpl;
-    // ... and its device copy (topology, packed 80 / 48 byte records): what a two-level TLAS copies in behind its top level
-    unsigned char *d_tmpl_nodes = nullptr, *d_tmpl_prims = nullptr;
+    BlasTree tmpl_dev;               // ... and its device copy: what a two-level TLAS copies in behind its top level
     float bsphere[4] = {0, 0, 0, -1.0f}; bool bsphere_ready = false;      // bounding sphere (centre of the box, largest vertex distance): the instances' tight bound
     // A SECOND object-space tree, with spatial splits: what the two-level trees of a HRT_CTX_FAST_TRACE context copy in instead of `tmpl` (the
-    // geometry never moves relative to these boxes, so the splits never expire).  Device only, packed like d_tmpl_*, plus the box of every
-    // record's part of its primitive (6 floats per record: what the pack's refit takes instead of the primitive's own box).  Built once
-    // (tmpl_mu) and shared by every TLAS that instances the BLAS; `tmpl` stays what it is.
-    struct SplitTree {
-        unsigned char *d_nodes = nullptr, *d_prims = nullptr; float *d_clip = nullptr;
-        uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
-        std::vector<uint32_t> level_begin;
-    } split;
+    // geometry never moves relative to these boxes, so the splits never expire).  Device only.  Built once (tmpl_mu) and shared by every TLAS
+    // that instances the BLAS; `tmpl` stays what it is.
+    BlasTree split;
     bool split_decided = false;      // `split` is there, or this BLAS is known to go without (4096 primitives or fewer; the top-down phase gave up)
-    ~Blas() { for (void *p : {(void *)d_verts, (void *)d_tmpl_nodes, (void *)d_tmpl_prims, (void *)split.d_nodes, (void *)split.d_prims, (void *)split.d_clip}) if (p) (void)hipFree(p); }
+    ~Blas() {
+        if (d_verts) (void)hipFree(d_verts);
+        for (BlasTree *t : {&tmpl_dev, &split}) for (void *p : {(void *)t->d_nodes, (void *)t->d_prims, (void *)t->d_clip}) if (p) (void)hipFree(p);
+    }
 };
 
 // The device memory of a TLAS: every member is a block from the context's pool (pool_alloc) and nothing else, so that free_tlas_device

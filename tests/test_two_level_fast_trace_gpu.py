@@ -291,7 +291,7 @@ def test_combinations_that_cannot_have_the_tree_fall_back(hrt, oracle, gpu_avail
     """Check 5.  A counting context, the host's fast-trace builder, HRT_TWO_LEVEL=-1 and two levels chosen by size leave
     HRT_CTX_FAST_TRACE what it was: the flattened split tree, node for node.  HRT_TWO_LEVEL=1 asks as the flag does.  A combined tree too
     deep for the path kernel's stack -- the split BLAS under a lowered HRT_FUSED_MAX_DEPTH, and a geometric chain whose BLAS no stack
-    could hold -- is built flattened instead (kRetryFlattened) and renders bit-exact against the oracle's FLATTENED mode."""
+    could hold -- is built flattened instead (build_two_level: flatten_instead) and renders bit-exact against the oracle's FLATTENED mode."""
     scene = _bodies_scene(hrt, n_bodies=5)
     both = hrt.CTX_FAST_TRACE | hrt.CTX_TWO_LEVEL
 
