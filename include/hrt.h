@@ -128,6 +128,29 @@ int  hrt_blas_build_triangles(HrtContext *ctx, const HrtFloat3 *d_vertices, uint
 int  hrt_blas_build_spheres(HrtContext *ctx, const HrtFloat3 *d_centers, const float *d_radii,
                             uint32_t n_spheres, void *stream, HrtTraversable *out_blas);
 int  hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas);
+/* OPTIX_BUILD_OPERATION_UPDATE for a triangle GAS: the same triangles at new object-space positions (a deforming mesh), without a new
+ * handle and without a rebuild.  `blas` is a live triangle BLAS of the context and n_vertices exactly what it was built with: triangle k
+ * stays triangle k.  HRT_ERR_INVALID for an unknown handle, a sphere BLAS, another count, or NULL d_vertices with a non-zero count; a
+ * refused call changes nothing.  A BLAS of zero primitives with n_vertices == 0: HRT_OK.
+ * The vertices are written into the BLAS's own copy on `stream` and the object-space bounds recomputed in the same pass
+ * (csrc/blas_update.hip; by the build's rule, so an updated BLAS has the bounds a BLAS built from these vertices has; non-finite
+ * vertices contribute nothing and their triangles are never hit).  Like the build, the call synchronises `stream` once for the bounds'
+ * read-back, and the caller may free d_vertices when it returns.  The BLAS's cached object-space trees (two-level TLASes, rebuilds
+ * during updates) are dropped and built again by the next build that wants them.
+ * Every TLAS that instances the BLAS is STALE until its next hrt_tlas_update, which picks the change up: a refit where the tree holds
+ * every primitive of the BLAS as a record of its own -- the default flattened build, trees over instances, two-level trees with
+ * unsplit BLAS trees (the BLAS's subtree is refitted in place, then the top level), synchronous and HRT_CTX_ASYNC_UPDATE alike,
+ * counted in HrtStats.tlas_refits, under the same quality verdict as moved instances (the two-level subtree's own degradation is
+ * not part of it) -- and a rebuild, counted in tlas_rebuilds, everywhere else: HRT_CTX_FAST_TRACE trees with split references,
+ * two-level trees in which the BLAS carries a split tree, trees built while a primitive of the BLAS was non-finite, HRT_REFIT=0.
+ * Tracing or rendering a stale TLAS is well defined: its records hold world-space (two-level: object-space) vertices of their own, so
+ * it sees the OLD geometry, bit for bit, until that update.  Shading normals are not the library's: they live in the caller's buffer
+ * (HrtSbtRecord.data.triangles.vertexNormals), which the caller rewrites, ordered on its stream against the launches that read it.
+ * The denoiser: a PENDING by-primitive link (hrt_denoise_temporal_rebind_geometry) that reads this BLAS as its old geometry is dropped,
+ * as hrt_tlas_destroy drops a link; an existing history is left alone -- it reprojects the instance as if rigid, the id and depth tests
+ * vet the taps: an approximation.  Not thread-safe against a concurrent build or update of a TLAS that instances the same BLAS;
+ * otherwise like the build calls.  Sphere BLASes have no update (rebuild them). */
+int  hrt_blas_update_triangles(HrtContext *ctx, HrtTraversable blas, const HrtFloat3 *d_vertices, uint32_t n_vertices, void *stream);
 
 /* replaces buildIAS / updateIAS, src/Global/RendererImpl.cu:174-242.  d_instances lives in
  * device memory (reference: cudaMemcpy H2D then build, src/Global/RendererMesh.cu:151-160).

@@ -128,6 +128,8 @@ SplitPhaseResult gpu_split_phase(const GpuBuildArgs &a, uint32_t n_valid, const 
 hipError_t gpu_reinsert_bvh2(const GpuBuildArgs &a, uint32_t n_nodes, uint32_t root, int rounds, BuildArena &arena, hipStream_t s, bool verbose, uint32_t *moved, const char **where);
 constexpr size_t kBoundsScratchBytes = 512;           // ... of gpu_blas_bounds
 hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, float *lo, float *hi, void *d_scratch, hipStream_t s);
+// blas_update.hip (hrt_blas_update_triangles): n_prims triangles from d_src into d_dst, and their bounds as gpu_blas_bounds gives them for d_dst afterwards
+hipError_t gpu_blas_update_triangles(const float *d_src, float *d_dst, uint32_t n_prims, float *lo, float *hi, void *d_scratch, hipStream_t s);
 // bounding sphere of a BLAS around `center` (radius < 0: none)
 hipError_t gpu_blas_radius(const float *d_src, uint32_t n_prims, uint32_t kind, const float *center, float *radius, void *d_scratch, hipStream_t s);
 void launch_pack_spheres(const float *centers, const float *radii, uint32_t n, float *out, hipStream_t s);

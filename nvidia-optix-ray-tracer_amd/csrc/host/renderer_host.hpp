@@ -54,6 +54,11 @@ inline GAS buildGASForTriangles(HrtContext *ctx, const RendererTriangle &t, hipS
     hrtCheckError(ctx, hrt_blas_build_triangles(ctx, t.dev_vertices, (uint32_t)(3 * t.count), stream, &h));
     return {h, nullptr};
 }
+// optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE on a triangle GAS (no call site in the reference, whose meshes are rigid): the same
+// triangles at new positions, triangle.count as at the build.  triangle.dev_normals is the caller's to rewrite; follow with updateIAS.
+inline void updateGASForTriangles(HrtContext *ctx, const GAS &gas, const RendererTriangle &t, hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_blas_update_triangles(ctx, gas.first, t.dev_vertices, (uint32_t)(3 * t.count), stream));
+}
 // buildIAS / updateIAS, src/Global/RendererImpl.cu:174-242
 inline IAS buildIAS(HrtContext *ctx, const HrtInstance *dev_instances, size_t instanceCount, hipStream_t stream = nullptr) {
     HrtTraversable h = 0;

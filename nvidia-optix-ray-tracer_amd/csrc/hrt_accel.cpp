@@ -659,27 +659,29 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
 //      in behind the top level and refitted in object space; (4) the top level's refit -- the only part an update repeats. ----
 
 // The top level's "geometry": per instance its BLAS's box and bounding sphere, on the device; `src` points the instances at them.
+// (one instance's ten floats; the bounding sphere is computed the first time a BLAS is asked for it, and again after hrt_blas_update_triangles)
+static int blas_bound_row(HrtContext *ctx, Blas &b, float *q, hipStream_t s) {
+    for (int a = 0; a < 3; ++a) { q[a] = b.lo[a]; q[3 + a] = b.hi[a]; }
+    q[6] = q[7] = q[8] = 0.0f; q[9] = -1.0f;
+    if (b.n_prims != 0u && b.lo[0] <= b.hi[0]) {
+        std::lock_guard<std::mutex> lk(b.tmpl_mu);
+        if (!b.bsphere_ready) {
+            for (int a = 0; a < 3; ++a) b.bsphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
+            const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
+            const hipError_t e = gpu_blas_radius(b.d_verts, b.n_prims, b.kind, b.bsphere, &b.bsphere[3], arena.p, s);
+            scratch_release(ctx, arena);
+            HIP_TRY(ctx, e);
+            b.bsphere_ready = true;
+        }
+        for (int a = 0; a < 4; ++a) q[6 + a] = b.bsphere[a];
+    }
+    return HRT_OK;
+}
 static int upload_blas_bounds(HrtContext *ctx, Tlas &t, std::vector<const void *> &src, hipStream_t s) {
     const uint32_t n = t.n_instances;
-    std::vector<float> bound(10 * (size_t)std::max(n, 1u), 0.0f);
-    for (uint32_t i = 0; i < n; ++i) {
-        Blas &b = *t.blas_refs[i];
-        float *q = &bound[10 * (size_t)i];
-        for (int a = 0; a < 3; ++a) { q[a] = b.lo[a]; q[3 + a] = b.hi[a]; }
-        q[9] = -1.0f;
-        if (b.n_prims != 0u && b.lo[0] <= b.hi[0]) {
-            std::lock_guard<std::mutex> lk(b.tmpl_mu);
-            if (!b.bsphere_ready) {
-                for (int a = 0; a < 3; ++a) b.bsphere[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
-                const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
-                const hipError_t e = gpu_blas_radius(b.d_verts, b.n_prims, b.kind, b.bsphere, &b.bsphere[3], arena.p, s);
-                scratch_release(ctx, arena);
-                HIP_TRY(ctx, e);
-                b.bsphere_ready = true;
-            }
-            for (int a = 0; a < 4; ++a) q[6 + a] = b.bsphere[a];
-        }
-    }
+    std::vector<float> &bound = t.h_blas_bound;      // (kept: pick_up_geometry renews the rows of BLASes whose geometry changes)
+    bound.assign(10 * (size_t)std::max(n, 1u), 0.0f);
+    for (uint32_t i = 0; i < n; ++i) RC_TRY(blas_bound_row(ctx, *t.blas_refs[i], &bound[10 * (size_t)i], s));
     HIP_TRY(ctx, pool_alloc(ctx, (void **)&t.dev.d_blas_bound, sizeof(float) * bound.size()));
     HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_blas_bound, bound.data(), sizeof(float) * bound.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -703,9 +705,10 @@ static int packed_tree_of(HrtContext *ctx, Blas &b, bool fast_trace, hipStream_t
 }
 
 // The refit of the packed BLAS trees, all BLASes at once: phase k = the k-th level from the bottom of every tree (a template is stored breadth
-// first, children one level below their parents), walked through an order array of node indices.
+// first, children one level below their parents), walked through an order array of node indices.  slices[j].phases: BLAS j's part of
+// every phase (contiguous in `order`), what the refit of that BLAS alone walks after hrt_blas_update_triangles.
 static void pack_refit_order(const std::vector<const BlasTree *> &trees, const std::vector<uint32_t> &node_off, uint32_t n_top, uint32_t blas_depth,
-                             std::vector<uint32_t> &order, std::vector<std::pair<uint32_t, uint32_t>> &pack_phases) {
+                             std::vector<uint32_t> &order, std::vector<std::pair<uint32_t, uint32_t>> &pack_phases, std::vector<PackSlice> &slices) {
     const uint32_t nu = (uint32_t)trees.size();
     order.reserve(node_off[nu]);
     for (uint32_t k = 0; k <= blas_depth; ++k) {
@@ -715,6 +718,7 @@ static void pack_refit_order(const std::vector<const BlasTree *> &trees, const s
             const uint32_t levels = lb.empty() ? 0u : (uint32_t)lb.size() - 1u;
             if (k >= levels) continue;
             const uint32_t l = levels - 1u - k;
+            if (lb[l + 1] > lb[l]) slices[j].phases.emplace_back((uint32_t)order.size(), lb[l + 1] - lb[l]);
             for (uint32_t x = lb[l]; x < lb[l + 1]; ++x) order.push_back(n_top + node_off[j] + x);
         }
         if (order.size() > begin) pack_phases.emplace_back(begin, (uint32_t)order.size() - begin);
@@ -736,6 +740,17 @@ static float object_space_reach(const Tlas &t, const std::vector<Blas *> &uniq, 
         if (std::isfinite(rown)) reach = std::max(reach, rown * scene_scale);
     }
     return std::max(reach, obj_coord);
+}
+
+// The refit of BLAS subtrees behind the top level of a two-level tree, in object space: the pack's own tables (not refit_args), the identity
+// transform, the BLASes' vertices, the padding the tree was built with.  The caller adds what differs: write_reference and clip at the build.
+static RefitArgs pack_refit_args(const Tlas &t) {
+    const TlasDevice &d = t.dev;
+    RefitArgs rp{};
+    rp.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); rp.node_stride = t.node_stride; rp.prims = reinterpret_cast<unsigned char *>(d.d_prims); rp.prim_stride = t.prim_stride;
+    rp.node_box = d.d_node_box; rp.node_ref = d.d_node_ref; rp.inst_xf = d.d_pack_xf; rp.inst_identity = d.d_pack_identity; rp.inst_src = d.d_pack_src; rp.order = d.d_pack_order;
+    rp.pad = 4e-6f * t.built_reach;
+    return rp;
 }
 
 // flatten_instead: the two-level tree asked for cannot be had (nothing valid to instance; too deep for the path kernel's stack, or too large
@@ -776,10 +791,13 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     in.d_inst_xf = d.d_inst_xf; in.d_inst_identity = d.d_inst_identity; in.node_stride = t.node_stride; in.prim_stride = t.prim_stride;
     StagedBuild sb{ctx, s};
     ArenaLayout &lay = sb.lay;
-    // (the pack's refit tables and walk order share the block: nu small tables, one entry per BLAS node)
-    const size_t o_pxf = lay.take(sizeof(float) * 12 * nu), o_pid = lay.take(sizeof(uint32_t) * nu), o_psrc = lay.take(sizeof(void *) * nu);
-    const size_t o_porder = lay.take(sizeof(uint32_t) * (size_t)node_off[nu]);
-    // (... and, where a BLAS tree has spatial splits, the box the pack's refit takes for every record of the TLAS: the BLASes keep their own copies)
+    // (the pack's refit tables and walk order stay with the tree -- nu small tables, one entry per BLAS node: the refit of one BLAS's subtree
+    // after hrt_blas_update_triangles walks them again)
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_pack_xf, sizeof(float) * 12 * nu));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_pack_identity, sizeof(uint32_t) * nu));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_pack_src, sizeof(void *) * nu));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_pack_order, sizeof(uint32_t) * std::max<size_t>(node_off[nu], 1)));
+    // (where a BLAS tree has spatial splits, the box the pack's refit takes for every record of the TLAS shares the build's block: the BLASes keep their own copies)
     const size_t o_pclip = lay.take(n_split ? sizeof(float) * 6 * (size_t)prim_off[nu] : 0u);
     // worst case: a transform node per instance and fewer box nodes than instances
     if (!sb.stage(in, 2 * (size_t)n2 + 2, StagedRecords::None, false)) return fail(ctx, HRT_ERR_OOM, "device build: no working memory (%zu bytes)", sb.want);
@@ -812,17 +830,17 @@ static int build_two_level(HrtContext *ctx, Tlas &t, const std::vector<HrtInstan
     for (uint32_t j = 0; j < nu; ++j) { pxf[12 * (size_t)j] = pxf[12 * (size_t)j + 5] = pxf[12 * (size_t)j + 10] = 1.0f; psrc[j] = uniq[j]->d_verts; }
     std::vector<uint32_t> order;
     std::vector<std::pair<uint32_t, uint32_t>> pack_phases;
-    pack_refit_order(trees, node_off, n_top, blas_depth, order, pack_phases);
+    t.pack.assign(nu, PackSlice());
+    for (uint32_t j = 0; j < nu; ++j) { t.pack[j].blas = uniq[j]; t.pack[j].n_records = trees[j]->n_records; t.pack[j].split = trees[j]->d_clip != nullptr; }
+    pack_refit_order(trees, node_off, n_top, blas_depth, order, pack_phases, t.pack);
     if (order.size() != node_off[nu]) return fail(ctx, HRT_ERR_HIP, "two-level tree: a BLAS template's levels do not cover its nodes");
-    HIP_TRY(ctx, hipMemcpyAsync(lay.at<float>(o_pxf), pxf.data(), sizeof(float) * pxf.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.at<uint32_t>(o_pid), pid.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.at<const void *>(o_psrc), psrc.data(), sizeof(void *) * nu, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(lay.at<uint32_t>(o_porder), order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_pack_xf, pxf.data(), sizeof(float) * pxf.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_pack_identity, pid.data(), sizeof(uint32_t) * nu, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync((void *)d.d_pack_src, psrc.data(), sizeof(void *) * nu, hipMemcpyHostToDevice, s));
+    if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync(d.d_pack_order, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, s));
     t.built_reach = object_space_reach(t, uniq, first2, scene_scale);
-    RefitArgs rp{};      // (the pack's own tables: not refit_args)
-    rp.nodes = reinterpret_cast<unsigned char *>(d.d_nodes); rp.node_stride = t.node_stride; rp.prims = reinterpret_cast<unsigned char *>(d.d_prims); rp.prim_stride = t.prim_stride;
-    rp.node_box = d.d_node_box; rp.node_ref = d.d_node_ref; rp.inst_xf = lay.at<float>(o_pxf); rp.inst_identity = lay.at<uint32_t>(o_pid); rp.inst_src = lay.at<const void *>(o_psrc); rp.order = lay.at<uint32_t>(o_porder);
-    rp.pad = 4e-6f * t.built_reach; rp.write_reference = 1u;
+    RefitArgs rp = pack_refit_args(t);
+    rp.write_reference = 1u;
     // (a record of a tree with spatial splits: the box of its part of the primitive, padded alike -- and for ever: an update refits the top level only)
     if (n_split) rp.clip = lay.at<float>(o_pclip);
     launch_refit_phases(rp, pack_phases, s);
@@ -926,6 +944,9 @@ static int build_tlas_fresh(HrtContext *ctx, Tlas &t, const std::vector<HrtInsta
     free_tlas_device(ctx, t);
     t.n_instances = n;
     t.blas_refs = std::move(refs);
+    t.blas_epoch.assign(n, 0);      // (the geometry every path below builds from)
+    for (uint32_t i = 0; i < n; ++i) t.blas_epoch[i] = t.blas_refs[i]->geometry_epoch;
+    t.pack.clear();
     // every path below uploads the tables all structures need (upload_instance_tables), makes the allocations of its own, and leaves the tree's counts in t
     switch (plan.kind) {
     case TreeKind::HostFlattened: rc = build_flattened_on_host(ctx, t, inst, plan.first[n], scene_scale, fast_trace, s); break;
@@ -1070,6 +1091,68 @@ static int update_async(HrtContext *ctx, Tlas *t, const HrtInstance *d_instances
     return HRT_OK;
 }
 
+// ---- geometry that changed under a tree (hrt_blas_update_triangles): every instance remembers the Blas::geometry_epoch its tree was last
+//      built or refitted for (Tlas::blas_epoch).  Host state only: an asynchronous update still reads nothing back. ----
+enum class GeometryChange { None, Refit, Rebuild };
+
+// Refit: the refit of the update brings the tree up to the new vertices (it reads them where they lie), once pick_up_geometry has renewed the
+// tables around it.  Rebuild: it cannot -- updates rebuild anyway (HRT_REFIT=0, a flattened tree with split references, an empty tree), or the
+// tree does not hold every primitive of a changed BLAS as a record of its own: the build left non-finite primitives out (and a BLAS that was
+// all of them has no subtree at all), or the BLAS's subtree in a two-level tree is its tree with spatial splits, whose clip boxes were the
+// old geometry's.
+static GeometryChange geometry_change(const HrtContext *ctx, const Tlas &t) {
+    const uint32_t n = t.n_instances;
+    bool changed = false;
+    for (uint32_t i = 0; i < n && !changed; ++i) changed = t.blas_refs[i]->geometry_epoch != t.blas_epoch[i];
+    if (!changed) return GeometryChange::None;
+    if (ctx->refit == 0 || t.has_split_refs || t.n_prims == 0u) return GeometryChange::Rebuild;
+    if (!t.two_level) {
+        uint64_t visible = 0;
+        for (uint32_t i = 0; i < n; ++i) visible += t.sig_visibility[i] ? t.blas_refs[i]->n_prims : 0u;
+        return (uint64_t)t.n_prims < visible ? GeometryChange::Rebuild : GeometryChange::Refit;
+    }
+    std::unordered_map<const Blas *, const PackSlice *> slice_of;
+    for (const PackSlice &ps : t.pack) slice_of[ps.blas] = &ps;
+    for (uint32_t i = 0; i < n; ++i) {
+        const Blas *b = t.blas_refs[i].get();
+        if (b->geometry_epoch == t.blas_epoch[i] || !t.sig_visibility[i] || b->n_prims == 0u) continue;
+        const auto it = slice_of.find(b);
+        if (it == slice_of.end() || it->second->split || it->second->n_records < b->n_prims) return GeometryChange::Rebuild;
+    }
+    return GeometryChange::Refit;
+}
+
+// Ahead of a refit that follows changed geometry, on its stream: the BLAS boxes the asynchronous tables kernel derives the scene scale from;
+// in a two-level tree the changed instances' "geometry" (their BLAS's box and bounding sphere: ten floats, the sphere computed anew --
+// the one read-back of this path, four bytes per changed BLAS) and the refit of the changed BLASes' subtrees -- the pack's refit of
+// build_two_level over their slices of its walk order: same topology, the new vertices.  (The flattened trees need no more: their refit
+// derives every record from the BLASes' vertices anyway.)  The subtrees' boxes do not enter the update's verdict.
+static int pick_up_geometry(HrtContext *ctx, Tlas &t, hipStream_t s) {
+    const uint32_t n = t.n_instances;
+    TlasDevice &d = t.dev;
+    t.h_blas_box.assign(6 * (size_t)std::max(n, 1u), 0.0f);
+    for (uint32_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { t.h_blas_box[6 * (size_t)i + a] = t.blas_refs[i]->lo[a]; t.h_blas_box[6 * (size_t)i + 3 + a] = t.blas_refs[i]->hi[a]; }
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_blas_box, t.h_blas_box.data(), sizeof(float) * t.h_blas_box.size(), hipMemcpyHostToDevice, s));
+    if (t.two_level) {
+        std::unordered_map<const Blas *, bool> moved;
+        uint32_t first = n, last = 0;                  // (one copy over the rows from the first changed instance to the last: a copy per row costs microseconds each)
+        for (uint32_t i = 0; i < n; ++i) {
+            Blas &b = *t.blas_refs[i];
+            if (b.geometry_epoch == t.blas_epoch[i]) continue;
+            moved[&b] = true;
+            RC_TRY(blas_bound_row(ctx, b, &t.h_blas_bound[10 * (size_t)i], s));
+            first = std::min(first, i); last = i;
+        }
+        if (first <= last) HIP_TRY(ctx, hipMemcpyAsync(d.d_blas_bound + 10 * (size_t)first, &t.h_blas_bound[10 * (size_t)first], sizeof(float) * 10 * (size_t)(last - first + 1), hipMemcpyHostToDevice, s));
+        const RefitArgs rp = pack_refit_args(t);
+        Timer tm(ctx, s, HRT_K_REFIT);
+        for (const PackSlice &ps : t.pack) if (moved.count(ps.blas)) launch_refit_phases(rp, ps.phases, s);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    for (uint32_t i = 0; i < n; ++i) t.blas_epoch[i] = t.blas_refs[i]->geometry_epoch;
+    return HRT_OK;
+}
+
 }  // namespace hrt
 
 // A rebuild in the middle of an animation.  Large scenes: the merged device build (3.1 ms for 2000 particles / 435 k triangles, 3.3 ms
@@ -1154,6 +1237,53 @@ int hrt_blas_build_spheres(HrtContext *ctx, const HrtFloat3 *d_centers, const fl
     return register_blas(ctx, std::move(b), out_blas);
 }
 
+// OPTIX_BUILD_OPERATION_UPDATE for a triangle GAS (include/hrt.h): new vertices into the BLAS's own copy and its bounds in one pass
+// (blas_update.hip); what was derived from the old ones goes -- the host copy, the bounding sphere, the cached object-space trees -- and the
+// epoch tells every TLAS over the BLAS, at its next hrt_tlas_update, that its tree is of the geometry as it was.
+int hrt_blas_update_triangles(HrtContext *ctx, HrtTraversable blas, const HrtFloat3 *d_vertices, uint32_t n_vertices, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    std::shared_ptr<Blas> b;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const auto it = ctx->blas.find(blas);
+        if (it == ctx->blas.end()) return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_triangles: unknown BLAS handle 0x%llx", (unsigned long long)blas);
+        b = it->second;
+    }
+    if (b->kind != kPrimKindTriangle) return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_triangles: 0x%llx is a sphere BLAS", (unsigned long long)blas);
+    if ((uint64_t)n_vertices != 3ull * b->n_prims)
+        return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_triangles: n_vertices (%u) is not what the BLAS was built with (%llu)", n_vertices, 3ull * b->n_prims);
+    if (n_vertices && !d_vertices) return fail(ctx, HRT_ERR_INVALID, "d_vertices is NULL");
+    if (reinterpret_cast<uintptr_t>(d_vertices) & 3u) return fail(ctx, HRT_ERR_INVALID, "d_vertices is not aligned for a float");
+    if (n_vertices == 0) return HRT_OK;
+    (void)hipSetDevice(ctx->device);
+    {   // a pending by-primitive link that reads this BLAS as its OLD geometry: what "previous" means is about to change under it
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DenoiseHistory &h = ctx->denoise_history;
+        if (h.link_pending && std::find(h.link_blas.begin(), h.link_blas.end(), b) != h.link_blas.end()) h.drop_link();
+    }
+    float lo[3], hi[3];
+    const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
+    const hipError_t e = gpu_blas_update_triangles(reinterpret_cast<const float *>(d_vertices), b->d_verts, b->n_prims, lo, hi, arena.p, (hipStream_t)stream);
+    scratch_release(ctx, arena);
+    HIP_TRY(ctx, e);
+    BlasTree old_tmpl, old_split;
+    {
+        std::lock_guard<std::mutex> lk(b->tmpl_mu);
+        for (int a = 0; a < 3; ++a) { b->lo[a] = lo[a]; b->hi[a] = hi[a]; }
+        b->bsphere_ready = false; b->bsphere[3] = -1.0f;
+        b->host_geometry = false; b->verts.clear();                       // (ensure_host_geometry fetches again)
+        b->tmpl = Bvh8(); b->tmpl_built = false; b->split_decided = false; // (rebuilt by the next build that wants them)
+        std::swap(old_tmpl, b->tmpl_dev); std::swap(old_split, b->split);
+        b->geometry_epoch++;
+    }
+    if (old_tmpl.d_nodes || old_split.d_nodes) {
+        // (a two-level build on another stream may still be copying from them)
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        for (BlasTree *tr : {&old_tmpl, &old_split}) for (void *p : {(void *)tr->d_nodes, (void *)tr->d_prims, (void *)tr->d_clip}) if (p) (void)hipFree(p);
+    }
+    return HRT_OK;
+}
+
 int hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas) {
     if (!ctx) return HRT_ERR_INVALID;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1197,9 +1327,12 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     if (ctx->capture.tlas == tlas) ctx->capture.valid = false;      // (the primary hits of the tree as it was: a refit keeps the generation)
     if (n != t->n_instances) return fail(ctx, HRT_ERR_INVALID, "update must keep the instance count (%u != %u)", n, t->n_instances);
     if (n && !d_instances) return fail(ctx, HRT_ERR_INVALID, "d_instances is NULL");
-    bool force_rebuild = false;
+    // (a BLAS of the tree has new vertices, hrt_blas_update_triangles: the refit picks them up where it can)
+    const GeometryChange geometry = geometry_change(ctx, *t);
+    bool force_rebuild = geometry == GeometryChange::Rebuild, pick_up = geometry == GeometryChange::Refit;
     // (the first update after a build takes the synchronous path below, which checks that refit on the spot: see there)
-    if ((ctx->flags & HRT_CTX_ASYNC_UPDATE) != 0 && ctx->refit != 0 && t->n_prims != 0u && n != 0u && (t->refits_since_build != 0 || t->built_posed)) {
+    if ((ctx->flags & HRT_CTX_ASYNC_UPDATE) != 0 && ctx->refit != 0 && t->n_prims != 0u && n != 0u && (t->refits_since_build != 0 || t->built_posed) && !force_rebuild) {
+        if (pick_up) { RC_TRY(pick_up_geometry(ctx, *t, s)); pick_up = false; }
         AsyncUpdate outcome;
         const int rc = update_async(ctx, t, d_instances, n, s, outcome);
         if (rc != HRT_OK || outcome == AsyncUpdate::Done) return rc;
@@ -1228,6 +1361,7 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
             HIP_TRY(ctx, hipStreamSynchronize(s));
         }
         const bool first_after_build = t->refits_since_build == 0;
+        if (pick_up) RC_TRY(pick_up_geometry(ctx, *t, s));
         rc = refit_tlas(ctx, *t, inst, s);
         if (rc != HRT_OK || !first_after_build) return rc;
         // The first refit after a build is checked on the spot (one stream synchronisation per build): the reference builds
@@ -1239,7 +1373,7 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     }
     if (ctx->build_verbose)
         std::fprintf(stderr, "[hrt] update %llu of this tree rebuilds: %s (area ratio %.3f, %llu refits since the build)\n", (unsigned long long)(t->refits + t->rebuilds),
-                     force_rebuild ? "verdict of the previous asynchronous refit" : moved_far ? "most instances are further from where the tree was built than they are wide" : "handles / visibility changed or the refit just done degraded the tree", ctx->tlas_refit_ratio.load(),
+                     geometry == GeometryChange::Rebuild ? "a BLAS has new vertices that a refit of this tree cannot follow" : force_rebuild ? "verdict of the previous asynchronous refit" : moved_far ? "most instances are further from where the tree was built than they are wide" : "handles / visibility changed or the refit just done degraded the tree", ctx->tlas_refit_ratio.load(),
                      (unsigned long long)t->refits_since_build);
     HIP_TRY(ctx, hipDeviceSynchronize());                 // launches on other streams may still read the old tree
     // a two-level tree stays one: its top level is rebuilt, the BLAS trees -- with their spatial splits, where it was built for trace speed -- are copied in again

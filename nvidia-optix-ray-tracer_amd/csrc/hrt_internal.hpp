@@ -30,7 +30,8 @@ namespace hrt {
 // An object-space tree of a BLAS on the device, as a two-level TLAS copies it in: topology in packed 80 / 48 byte records, stored breadth
 // first (nodes of level l: [level_begin[l], level_begin[l + 1])).  d_clip: a tree with spatial splits has the box of every record's part of
 // its primitive (6 floats per record: what the pack's refit takes instead of the primitive's own box); NULL otherwise.  Written once, under
-// Blas::tmpl_mu, and never changed; the BLAS owns the three blocks (hipMalloc).
+// Blas::tmpl_mu, and not changed afterwards -- hrt_blas_update_triangles drops it whole (the next build that wants it makes a new one); the
+// BLAS owns the three blocks (hipMalloc).
 struct BlasTree {
     unsigned char *d_nodes = nullptr, *d_prims = nullptr; float *d_clip = nullptr;
     uint32_t n_nodes = 0, n_records = 0, n_triangles = 0, n_spheres = 0, max_depth = 0;
@@ -49,13 +50,14 @@ struct Blas {
                                      // build and every refit derive the world-space records from it
                                      // (the caller may free its vertex buffer after the build, RendererMesh.cu:116)
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};   // object-space bounds
+    uint64_t geometry_epoch = 0;     // bumped by hrt_blas_update_triangles: a TLAS whose Tlas::blas_epoch differs still holds the geometry as it was
     // object-space BVH8 of this geometry alone: the per-instance subtree of the trees over instances (built on first use)
     std::mutex tmpl_mu; bool tmpl_built = false; Bvh8 tmpl;
     BlasTree tmpl_dev;               // ... and its device copy: what a two-level TLAS copies in behind its top level
     float bsphere[4] = {0, 0, 0, -1.0f}; bool bsphere_ready = false;      // bounding sphere (centre of the box, largest vertex distance): the instances' tight bound
     // A SECOND object-space tree, with spatial splits: what the two-level trees of a HRT_CTX_FAST_TRACE context copy in instead of `tmpl` (the
-    // geometry never moves relative to these boxes, so the splits never expire).  Device only.  Built once (tmpl_mu) and shared by every TLAS
-    // that instances the BLAS; `tmpl` stays what it is.
+    // geometry moves relative to these boxes only in hrt_blas_update_triangles, which drops the tree with its clip boxes).  Device only.
+    // Built once per geometry (tmpl_mu) and shared by every TLAS that instances the BLAS; `tmpl` stays what it is.
     BlasTree split;
     bool split_decided = false;      // `split` is there, or this BLAS is known to go without (4096 primitives or fewer; the top-down phase gave up)
     ~Blas() {
@@ -82,11 +84,21 @@ struct TlasDevice {
     unsigned long long *d_sig_handle = nullptr; uint32_t *d_sig_visibility = nullptr, *d_sig_sbt = nullptr; float *d_blas_box = nullptr;
     uint32_t *d_update_flags = nullptr;                  // [0] scene scale (float bits), [1] bit 0: handle / visibility changed, bit 1: an sbtOffset changed
     float *d_rec_box = nullptr;                          // small trees: 6 floats per record, the refit's per-record pass (refit.hip k_refit_records)
+    // two-level trees, for the refit of a BLAS's subtree after hrt_blas_update_triangles (the pack's refit of build_two_level): per unique
+    // BLAS the object -> "world" (identity), identity flag and geometry source; per BLAS node the walk order (Tlas::pack has the phases)
+    float *d_pack_xf = nullptr; uint32_t *d_pack_identity = nullptr; const void **d_pack_src = nullptr; uint32_t *d_pack_order = nullptr;
     uint32_t *d_leaf_parent = nullptr;                   // one-level trees of triangles: per record, the node whose leaf slot covers it (ensure_leaf_parent: made at the first launch that wants
                                                          // it; a refit keeps topology and record order, hence the table; a rebuild is a new Tlas and starts without one)
 };
 static_assert(std::is_standard_layout<TlasDevice>::value && std::is_trivially_copyable<TlasDevice>::value && sizeof(TlasDevice) % sizeof(void *) == 0,
               "TlasDevice holds pool blocks only: free_tlas_device walks it as an array of pointers");
+
+// One unique BLAS of a two-level tree: its subtree's records and, as ranges of TlasDevice::d_pack_order, its levels from the bottom up.
+struct PackSlice {
+    const Blas *blas = nullptr;             // (kept alive by Tlas::blas_refs)
+    uint32_t n_records = 0; bool split = false;      // split: the subtree is the BLAS's tree with spatial splits (its clip boxes are not kept: a changed geometry rebuilds)
+    std::vector<std::pair<uint32_t, uint32_t>> phases;
+};
 
 struct Tlas {
     uint32_t n_instances = 0;
@@ -103,6 +115,9 @@ struct Tlas {
     // refit (hrt_tlas_update): what must stay the same (the device tables the refit kernel reads: TlasDevice)
     std::vector<std::shared_ptr<Blas>> blas_refs;       // keeps the source geometry alive
     std::vector<uint64_t> sig_handle; std::vector<uint32_t> sig_visibility;
+    std::vector<uint64_t> blas_epoch;                   // per instance: Blas::geometry_epoch the tree was last built or refitted for
+    std::vector<float> h_blas_box, h_blas_bound;        // host copies of d_blas_box (made when a geometry has changed) / d_blas_bound (two-level trees: kept since the build)
+    std::vector<PackSlice> pack;                        // two-level trees: per unique BLAS
     std::vector<float> h_xf, h_inv; std::vector<uint32_t> h_ident;   // staging of the per-instance uploads
     // asynchronous updates (HRT_CTX_ASYNC_UPDATE)
     bool built_posed = false;                           // built by an update, for the poses of that frame (not the reference's identity-posed load-time build): asynchronous updates may follow at once

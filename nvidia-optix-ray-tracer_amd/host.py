@@ -102,6 +102,7 @@ class Renderer:
         self._n_inst = None
         self.tlas = None
         self._built_blas = {}       # BLAS handle -> its normals: the BLASes build_tlas(vertices=...) made
+        self._scene_blas = {}       # ... and load_scene's triangle BLASes (update_blas_vertices rewrites either in place)
         self._tlas_blas = {}        # TLAS handle -> those of them it was built over
         self._tlases = {}           # handle -> (host instance array, device instance array, count, SBT records): load_scene's and build_tlas's
         self.states = None
@@ -146,6 +147,7 @@ class Renderer:
                                 "hrt_blas_build_triangles")
                     del verts                              # the reference frees vertices after the build too
                     self._keep.append(normals)
+                    self._scene_blas[handle.value] = normals
                     if key is not None:
                         shared[key] = (handle.value, normals)
                 h_rec[i].data.ptr0 = normals.data_ptr()
@@ -262,6 +264,33 @@ class Renderer:
             raise self._err(f"destroy_tlas: 0x{tlas:x} is in use or not a TLAS of this renderer")
         self._check(self.lib.hrt_tlas_destroy(self.ctx, tlas), "hrt_tlas_destroy")
         del self._tlases[tlas]
+
+    def update_blas_vertices(self, handle_or_instance, vertices, normals=None):
+        """hrt_blas_update_triangles: the triangle BLAS gets new object-space ``vertices`` ((t, 3, 3) float32, as many triangles as it
+        was built with) in place, and the normals buffer the renderer keeps for it -- what its instances' records point at -- is
+        rewritten on the same stream with ``normals`` ((t, 3, 3); default scenes.face_normals of the vertices).  ``handle_or_instance``: the
+        handle of a BLAS load_scene or build_tlas(vertices=...) made, or (any other number) the index of an instance of the current TLAS,
+        whose BLAS is meant.  Does NOT update any TLAS: every TLAS over the BLAS shows the old geometry until its next update_instances."""
+        from . import scenes
+        handle = int(handle_or_instance)
+        if handle not in self._scene_blas and handle not in self._built_blas:
+            if self._n_inst is None or not 0 <= handle < self._n_inst:
+                raise self._err(f"update_blas_vertices: {handle} is neither a triangle BLAS of this renderer nor an instance of its TLAS")
+            handle = int(self._h_inst[handle].traversableHandle)
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3, 3)
+        nrm = scenes.face_normals(v) if normals is None else normals
+        nrm = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3, 3)
+        if nrm.shape != v.shape:
+            raise self._err(f"update_blas_vertices: {v.shape[0]} triangles and normals for {nrm.shape[0]}")
+        d_v = self._dev(v.reshape(-1, 3))
+        self._check(self.lib.hrt_blas_update_triangles(self.ctx, handle, d_v.data_ptr(), d_v.shape[0], self._stream()),
+                    "hrt_blas_update_triangles")
+        del d_v                                            # (the BLAS has its own copy, as after the build)
+        keep = self._scene_blas.get(handle, self._built_blas.get(handle))
+        if keep is not None:
+            if tuple(keep.shape) != (3 * v.shape[0], 3):
+                raise self._err(f"update_blas_vertices: the normals buffer of BLAS 0x{handle:x} holds {keep.shape[0] // 3} triangles")
+            keep.copy_(self._dev(nrm.reshape(-1, 3)))      # in place: the records keep their pointer
 
     def update_instances(self, transforms):
         """Per-frame instance update + updateIAS (src/Global/RendererMesh.cu:379-401)."""

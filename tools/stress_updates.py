@@ -2,7 +2,10 @@
 """Random animations: a random scene, then a sequence of hrt_tlas_update calls with random transforms -- small steps (refits), now and then a jump across
 the scene (the quality guard rebuilds), uneven scales and shears, an instance shrunk to nothing -- synchronous and asynchronous updates, flattened and
 two-level trees, other execution modes; after every update the frame is compared bit for bit with the oracle's render of the moved scene.
-    tools/stress_updates.py [n_scenes=20] [seed=1]"""
+--deform: between the instance updates a random triangle BLAS now and then gets new vertices in place (hrt_blas_update_triangles: a smooth
+2 % deformation, at times a scatter that no refit survives), picked up by the update that follows; the scenes and transforms are the same
+ones as without the option (the deformations draw from a generator of their own).
+    tools/stress_updates.py [n_scenes=20] [seed=1] [--deform]"""
 import importlib, os, sys, time, copy
 from pathlib import Path
 import numpy as np
@@ -12,9 +15,28 @@ import torch
 hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
 import oracle_py as oracle
 
-n_scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-bad = 0
+deform = "--deform" in sys.argv
+argv = [a for a in sys.argv if a != "--deform"]
+n_scenes = int(argv[1]) if len(argv) > 1 else 20
+rng = np.random.default_rng(int(argv[2]) if len(argv) > 2 else 1)
+drng = np.random.default_rng(1000 + (int(argv[2]) if len(argv) > 2 else 1))      # --deform's own
+bad = deformed = 0
+
+def deform_blas(r, scene, drng):
+    """new vertices for the BLAS of a random triangle instance, in the renderer and in every instance of the scene that shares it"""
+    tri = [i for i, it in enumerate(scene["instances"]) if it["geometry"] == "triangles"]
+    if not tri: return 0
+    i = int(drng.choice(tri)); it = scene["instances"][i]
+    p = it["vertices"].reshape(-1, 3).astype(np.float64)
+    ext = float((p.max(axis=0) - p.min(axis=0)).max()) or 1.0
+    if drng.random() < 0.1: q = p.mean(axis=0) + 20.0 * ext * drng.uniform(-1, 1, p.shape)
+    else: q = p + 0.02 * ext * np.sin(p @ drng.normal(0, 2.0 / ext, (3, 3)) + drng.uniform(0, 6.28, 3))
+    v = q.astype(np.float32).reshape(it["vertices"].shape)
+    r.update_blas_vertices(i, v)
+    for jt in scene["instances"]:
+        if jt is it or (jt["geometry"] == "triangles" and it.get("shape") is not None and jt.get("shape") == it.get("shape")):
+            jt["vertices"] = v; jt["normals"] = hrt.scenes.face_normals(v)
+    return 1
 
 def jitter(m, rng, big):
     m = m.reshape(3, 4).astype(np.float64).copy()
@@ -53,6 +75,7 @@ for k in range(n_scenes):
             big = rng.random() < 0.2
             tr = [jitter(it["transform"], rng, big) if rng.random() < 0.8 else it["transform"] for it in scene["instances"]]
             for it, m in zip(scene["instances"], tr): it["transform"] = m
+            if deform and drng.random() < 0.6: deformed += deform_blas(r, scene, drng)
             r.update_instances(tr)
             r.render(spp)
             got = r.linear.cpu().numpy().view(np.uint32)
@@ -67,5 +90,6 @@ for k in range(n_scenes):
     finally:
         r.close()
     print(time.strftime("%H:%M:%S"), k, scene["name"], (w, h, spp), "flags", flags, "mode", mode, "refits", int(st.tlas_refits) if st else "-", "rebuilds", int(st.tlas_rebuilds) if st else "-", "ok" if not bad else f"{bad} bad so far", flush=True)
+if deform: print("stress:", deformed, "BLAS updates")
 print("stress:", "all frames bit-exact" if not bad else f"{bad} FAILURES")
 sys.exit(1 if bad else 0)
