@@ -94,8 +94,10 @@ typedef struct HrtContext HrtContext;
                                     1.46 records per triangle, ~1.2 KB of working memory per triangle), or -- environment
                                     HRT_FAST_TRACE_BUILD=host -- by the host's binned-SAH builder from a host copy of the geometry (the same
                                     rules, ~1.3 s).  Such a tree is for static scenes: the first hrt_tlas_update replaces it by a
-                                    default-built one (a refit cannot keep the split references' boxes), and rebuilds inside hrt_tlas_update
-                                    are always default builds (the reference's IAS flags: ALLOW_UPDATE | PREFER_FAST_BUILD, RendererImpl.cu:180).
+                                    default-built one (a plain refit cannot keep the split references' boxes), and rebuilds inside hrt_tlas_update
+                                    are always default builds (the reference's IAS flags: ALLOW_UPDATE | PREFER_FAST_BUILD, RendererImpl.cu:180)
+                                    -- unless the context also has HRT_CTX_KEEP_SPLITS (below), under which the device-built tree is refitted
+                                    and keeps its splits.
                                     A split build whose tree comes out deeper than any kernel's stack (a geometric chain of primitives) is built
                                     again by position, without splits, like the default build; it used to fail with HRT_ERR_INVALID.
                                     TOGETHER WITH HRT_CTX_TWO_LEVEL (or HRT_TWO_LEVEL=1: two levels asked for, not chosen by size) -- the
@@ -110,6 +112,30 @@ typedef struct HrtContext HrtContext;
                                     two-level tree can be had -- HRT_CTX_COUNT, HRT_FUSED != 1, HRT_FAST_TRACE_BUILD=host, top + 1 + deepest
                                     BLAS levels beyond the path kernel's stack (split trees are deeper) -- the flattened split tree above is
                                     built, as with HRT_CTX_FAST_TRACE alone. */
+
+#define HRT_CTX_KEEP_SPLITS 0x80u /* together with HRT_CTX_FAST_TRACE: the FLATTENED tree the device builds with spatial splits keeps them through
+                                    hrt_tlas_update -- the reference's own configuration, PREFER_FAST_TRACE GASes under an IAS that updateIAS refits
+                                    every frame.  The tree is the one built without the flag, byte for byte; it also keeps, per record, the as-built
+                                    world clip box and the record's part of its triangle as ranges of the triangle's own barycentric coordinates
+                                    (48 B per record in all), and per instance the build's transform.  An update then REFITS it (tlas_refits), synchronous and
+                                    HRT_CTX_ASYNC_UPDATE alike: records of an instance whose transform is the build's bit for bit and whose BLAS has
+                                    had no hrt_blas_update_triangles since keep their as-built boxes (an update that moves nothing leaves the tree
+                                    byte-identical); a triangle record of any other instance takes the box of its barycentric hexagon under the new
+                                    vertices -- an affine map preserves barycentrics, so it holds under rotation, any scale, a singular matrix and
+                                    after hrt_blas_update_triangles, which such a tree follows by a refit too (unless the build left a non-finite
+                                    primitive out); a sphere record of a moved instance takes the sphere's whole box under every one of its
+                                    records (correct; the limitation).  The refit stands under the usual quality verdict
+                                    (HRT_REFIT_REBUILD_RATIO) and the first update's moved-far check; a rebuild inside an update -- a changed
+                                    handle or visibility bit, a verdict, moved far, HRT_REFIT=0 -- is a device split build again, not a default
+                                    build.  Read at hrt_ctx_create only (hrt_ctx_set_flags does not switch it); HRT_KEEP_SPLITS=1: every context.
+                                    No effect on HRT_FAST_TRACE_BUILD=host trees, two-level trees (which keep their splits anyway), trees built
+                                    again by position, and builds of 4096 primitives or fewer, which have no splits -- a rebuild under the flag
+                                    that comes out as one of these too (the visible primitives have fallen to 4096 or fewer, the tree is too
+                                    deep) leaves a tree without the tables, and from then on this TLAS is updated and rebuilt by the unflagged
+                                    rules: the flag acts on the tree a TLAS has, not on the context's intent.  Off by default, and not
+                                    for scenes that turn as a whole: measured with every instance moving, the kept splits trace 4-6 % slower
+                                    than the default tree after a rotation and level with it after a translation; what is saved is the
+                                    first update's rebuild. */
 
 /* replaces createContext / destroyContext, src/Global/RendererImpl.cu:6-27 */
 int  hrt_ctx_create(int device_id, uint32_t flags, HrtContext **out_ctx);
@@ -141,7 +167,8 @@ int  hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas);
  * every primitive of the BLAS as a record of its own -- the default flattened build, trees over instances, two-level trees with
  * unsplit BLAS trees (the BLAS's subtree is refitted in place, then the top level), synchronous and HRT_CTX_ASYNC_UPDATE alike,
  * counted in HrtStats.tlas_refits, under the same quality verdict as moved instances (the two-level subtree's own degradation is
- * not part of it) -- and a rebuild, counted in tlas_rebuilds, everywhere else: HRT_CTX_FAST_TRACE trees with split references,
+ * not part of it) -- and a rebuild, counted in tlas_rebuilds, everywhere else: HRT_CTX_FAST_TRACE trees with split references
+ * (but for the flattened tree built under HRT_CTX_KEEP_SPLITS, which refits: a triangle's barycentric ranges hold wherever it goes),
  * two-level trees in which the BLAS carries a split tree, trees built while a primitive of the BLAS was non-finite, HRT_REFIT=0.
  * Tracing or rendering a stale TLAS is well defined: its records hold world-space (two-level: object-space) vertices of their own, so
  * it sees the OLD geometry, bit for bit, until that update.  Shading normals are not the library's: they live in the caller's buffer
@@ -533,6 +560,10 @@ typedef struct HrtBvhBlob {
     float    bounds[6];
 } HrtBvhBlob;
 int  hrt_host_build_bvh8(const float *h_triangles, uint32_t n_triangles, HrtBvhBlob *out);
+/* Host only (tests): the part of the triangle tri9 (three vertices) inside the box box6 (lo, hi) as ranges of the triangle's own
+ * barycentric coordinates, out6 = {u0, u1, v0, v1, w0, w1} with p = v0 + u (v1 - v0) + v (v2 - v0), w = 1 - u - v: what a tree
+ * under HRT_CTX_KEEP_SPLITS keeps per record (csrc/bvh8_geom.h: clip_triangle_barycentric).  Full ranges [0, 1] where the part is empty. */
+int  hrt_host_clip_barycentric(const float tri9[9], const float box6[6], float out6[6]);
 /* Copy the flattened world-space BVH of a TLAS, as it is in device memory now (after any refit), back to
  * the host (same blob format). */
 int  hrt_tlas_download(HrtContext *ctx, HrtTraversable tlas, HrtBvhBlob *out);

@@ -122,6 +122,7 @@ assert C.sizeof(HitGroupParams) == 32 and C.sizeof(SbtRecord) == 64 and C.sizeof
 
 PROGRAM_SPHERE_ROUGH, PROGRAM_SPHERE_METAL, PROGRAM_TRIANGLE_ROUGH, PROGRAM_TRIANGLE_METAL = range(4)
 CTX_TIMING, CTX_COUNT, CTX_FAST_TRACE, CTX_ASYNC_UPDATE, CTX_TWO_LEVEL, CTX_REUSE_PRIMARY, CTX_CAPTURE_PRIMARY = 1, 2, 4, 8, 16, 32, 64
+CTX_KEEP_SPLITS = 128
 NO_INSTANCE = 0xFFFFFFFF        # HRT_NO_INSTANCE: hrt_denoise_temporal_rebind's "a body that was not there before"
 
 # every symbol include/hrt.h declares (checked by the CPU test-suite)
@@ -132,7 +133,7 @@ EXPORTS = [
     "hrt_sbt_record_pack_header", "hrt_materials_set", "hrt_miss_set",
     "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_primary_hits_get", "hrt_to_rgba8", "hrt_color_to_float4",
     "hrt_stats_reset", "hrt_stats_get", "hrt_sample_schedule", "hrt_trace_rays", "hrt_debug_set_linear_output",
-    "hrt_host_build_bvh8", "hrt_tlas_download", "hrt_host_leaf_parent", "hrt_tlas_leaf_parent", "hrt_host_free", "hrt_debug_trig",
+    "hrt_host_build_bvh8", "hrt_host_clip_barycentric", "hrt_tlas_download", "hrt_host_leaf_parent", "hrt_tlas_leaf_parent", "hrt_host_free", "hrt_debug_trig",
     "hrt_denoise_default_params", "hrt_denoise_guides", "hrt_denoise_filter", "hrt_denoise_launch",
     "hrt_denoise_temporal_default_params", "hrt_denoise_temporal_launch", "hrt_denoise_temporal_reset", "hrt_debug_denoise_temporal_state",
     "hrt_denoise_temporal_rebind", "hrt_denoise_temporal_rebind_geometry",
@@ -202,6 +203,7 @@ def load_library():
     lib.hrt_debug_set_linear_output.argtypes = [C.c_void_p, C.c_void_p]
     lib.hrt_debug_trig.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     lib.hrt_host_build_bvh8.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BvhBlob)]
+    lib.hrt_host_clip_barycentric.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.hrt_tlas_download.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(BvhBlob)]
     lib.hrt_host_leaf_parent.argtypes = [C.POINTER(BvhBlob), C.POINTER(C.c_uint32), C.c_uint64]
     lib.hrt_tlas_leaf_parent.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]

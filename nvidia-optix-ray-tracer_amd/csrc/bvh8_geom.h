@@ -137,6 +137,90 @@ HRT_HD void clip_triangle_to_box(const float *v0, const float *e1, const float *
     }
 }
 
+// The same part of the same triangle as ranges of the triangle's OWN barycentric coordinates (p = v0 + u e1 + v e2, w = 1 - u - v):
+// out6 = {u0, u1, v0, v1, w0, w1}.  An affine map keeps barycentrics, so the ranges bound the part under any later instance transform and
+// after hrt_blas_update_triangles has moved the vertices (HRT_CTX_KEEP_SPLITS: what the refit of a flattened split tree takes, bary_hexagon_box).
+// The same Sutherland-Hodgman in double, every polygon vertex carrying its (u, v): the corners' are exact, a cut interpolates them by
+// the parameter of the cut, so a degenerate triangle is no special case.  Each bound is rounded to float and moved outwards by
+// kBaryClipSlack, within [-kBaryClipSlack, 1 + kBaryClipSlack] (DESIGN.md section 3a has the budget; a bound clamped to [0, 1] proper would
+// lose its slack exactly where the part touches an edge of the triangle, which is where bary_hexagon_box needs it: the refit cuts the
+// result down to the primitive's own box anyway).  A polygon no plane has cut, a numerically empty one, a non-finite vertex or box:
+// the full ranges [0, 1] -- the whole primitive, always conservative.
+constexpr float kBaryClipSlack = 1.0e-6f;
+HRT_HD void clip_triangle_barycentric(const float *v0, const float *e1, const float *e2, const float *blo, const float *bhi, float *out6) {
+    for (int q = 0; q < 3; ++q) { out6[2 * q] = 0.0f; out6[2 * q + 1] = 1.0f; }
+    double poly[2][16][5]; int np = 3, cur = 0;
+    bool finite = true;
+    for (int c = 0; c < 3; ++c) {
+        poly[0][0][c] = v0[c];
+        poly[0][1][c] = (double)v0[c] + (double)e1[c];
+        poly[0][2][c] = (double)v0[c] + (double)e2[c];
+        finite = finite && fabsf(v0[c]) <= 3.0e38f && fabsf(e1[c]) <= 3.0e38f && fabsf(e2[c]) <= 3.0e38f;
+    }
+    if (!finite) return;
+    poly[0][0][3] = 0.0; poly[0][0][4] = 0.0; poly[0][1][3] = 1.0; poly[0][1][4] = 0.0; poly[0][2][3] = 0.0; poly[0][2][4] = 1.0;
+    for (int c = 0; c < 3 && np > 0; ++c)
+        for (int side = 0; side < 2 && np > 0; ++side) {
+            const double plane = side == 0 ? (double)blo[c] : (double)bhi[c];
+            const double sgn = side == 0 ? 1.0 : -1.0;
+            int nq = 0;
+            for (int i = 0; i < np; ++i) {
+                const double *u = poly[cur][i], *v = poly[cur][(i + 1) % np];
+                const double du = sgn * (u[c] - plane), dv = sgn * (v[c] - plane);
+                if (du >= 0.0) { for (int k = 0; k < 5; ++k) poly[cur ^ 1][nq][k] = u[k]; ++nq; }
+                if ((du > 0.0 && dv < 0.0) || (du < 0.0 && dv > 0.0)) {
+                    const double t = du / (du - dv);
+                    for (int k = 0; k < 5; ++k) poly[cur ^ 1][nq][k] = k == c ? plane : u[k] + t * (v[k] - u[k]);
+                    ++nq;
+                }
+            }
+            np = nq; cur ^= 1;
+        }
+    if (np == 0) return;
+    double l[3], h[3];
+    for (int i = 0; i < np; ++i) {
+        const double b[3] = {poly[cur][i][3], poly[cur][i][4], 1.0 - poly[cur][i][3] - poly[cur][i][4]};
+        for (int q = 0; q < 3; ++q) { l[q] = (i == 0 || b[q] < l[q]) ? b[q] : l[q]; h[q] = (i == 0 || b[q] > h[q]) ? b[q] : h[q]; }
+    }
+    bool whole = true;
+    for (int q = 0; q < 3; ++q) whole = whole && l[q] == 0.0 && h[q] == 1.0;      // (the corners' barycentrics are exact)
+    if (whole) return;
+    float g[6];
+    for (int q = 0; q < 3; ++q) {
+        const float fl = (float)l[q] - kBaryClipSlack, fh = (float)h[q] + kBaryClipSlack;
+        if (!(fl <= fh)) return;                                                   // (NaN: a box plane was)
+        g[2 * q] = fl > -kBaryClipSlack ? fl : -kBaryClipSlack; g[2 * q + 1] = fh < 1.0f + kBaryClipSlack ? fh : 1.0f + kBaryClipSlack;
+    }
+    for (int q = 0; q < 6; ++q) out6[q] = g[q];
+}
+
+// World box of the hexagon {u in [g0, g1], v in [g2, g3], u + v in [1 - g5, 1 - g4]} of a triangle in record form (g: the six ranges of
+// clip_triangle_barycentric): its vertices are all among eight points -- on u = g0 and u = g1 the two ends of v's interval there,
+// [max(g2, s0 - u), min(g3, s1 - u)], on v = g2 and v = g3 the two ends of u's, [max(g0, s0 - v), min(g1, s1 - v)], with s0 = 1 - g5,
+// s1 = 1 - g4 -- and every such point is one of the hexagon's.  Float, contraction off; the box is widened by the rounding of the
+// points: kBaryBoxRounding x (|v0| + |e1| + |e2|) per axis.  False when one of the four intervals comes out
+// empty: lo / hi then mean nothing and the caller keeps the whole primitive's box.
+constexpr float kBaryBoxRounding = 5.0e-7f;      // ~4.2 ULP
+HRT_HD bool bary_hexagon_box(const float *v0, const float *e1, const float *e2, const float *g, float *lo, float *hi) {
+    const float s0 = 1.0f - g[5], s1 = 1.0f - g[4];
+    float pu[8], pv[8];
+    bool ok = true;
+    for (int j = 0; j < 2; ++j) {
+        const float u = g[j], va = fmaxf(g[2], s0 - u), vb = fminf(g[3], s1 - u);
+        const float v = g[2 + j], ua = fmaxf(g[0], s0 - v), ub = fminf(g[1], s1 - v);
+        ok = ok && va <= vb && ua <= ub;
+        pu[4 * j] = u; pv[4 * j] = va; pu[4 * j + 1] = u; pv[4 * j + 1] = vb;
+        pu[4 * j + 2] = ua; pv[4 * j + 2] = v; pu[4 * j + 3] = ub; pv[4 * j + 3] = v;
+    }
+    for (int k = 0; k < 3; ++k) {
+        float l = INFINITY, h = -INFINITY;
+        for (int i = 0; i < 8; ++i) { const float p = (v0[k] + pu[i] * e1[k]) + pv[i] * e2[k]; l = fminf(l, p); h = fmaxf(h, p); }
+        const float w = kBaryBoxRounding * ((fabsf(v0[k]) + fabsf(e1[k])) + fabsf(e2[k]));
+        lo[k] = l - w; hi[k] = h + w;
+    }
+    return ok;
+}
+
 // Smallest exponent e (biased by 127, within [1, 254]) with 255 * 2^(e-127) >= ext, from the bits of ext.
 HRT_HD uint8_t node_exponent(float ext) {
     if (!(ext > 0.0f)) return 1;

@@ -3,6 +3,7 @@
 // HRT_HOST_ONLY), which runs the builder under AddressSanitizer / UBSan on the CPU.
 #include "../../include/hrt.h"
 #include "bvh8.h"
+#include "bvh8_geom.h"
 
 #include <algorithm>
 #include <cmath>
@@ -66,6 +67,15 @@ int hrt_host_build_bvh8(const float *h_triangles, uint32_t n_triangles, HrtBvhBl
     if (rc != HRT_OK) return rc;
     if (!b.nodes.empty()) std::memcpy(out->nodes, b.nodes.data(), sizeof(Bvh8Node) * b.nodes.size());
     if (!b.prims.empty()) std::memcpy(out->triangles, b.prims.data(), sizeof(PrimRecord) * b.prims.size());      // (memcpy from NULL is undefined even for 0 bytes: UBSan)
+    return HRT_OK;
+}
+
+// The arithmetic of a tree that keeps its splits (bvh8_geom.h), for the CPU suite: the triangle in record form, as the builders have it.
+int hrt_host_clip_barycentric(const float tri9[9], const float box6[6], float out6[6]) {
+    if (!tri9 || !box6 || !out6) return HRT_ERR_INVALID;
+    float e1[3], e2[3];
+    for (int a = 0; a < 3; ++a) { e1[a] = tri9[3 + a] - tri9[a]; e2[a] = tri9[6 + a] - tri9[a]; }
+    clip_triangle_barycentric(tri9, e1, e2, box6, box6 + 3, out6);
     return HRT_OK;
 }
 

@@ -211,6 +211,12 @@ struct RefitArgs {
                                    // are walked -- the records' arithmetic then runs one thread per record instead of inside the walk up the tree
     const float *clip;             // when set (the refit that completes a device build with spatial splits, flattened or of a two-level tree's BLASes): 6 floats per
                                    // record, the box of the part of the primitive this record stands for, taken instead of the primitive's own
+    // A flattened tree that keeps its spatial splits through updates (HRT_CTX_KEEP_SPLITS).  bary set: the launches take the kernels'
+    // <true> instantiations, `clip` is the tree's own copy of the as-built boxes and inst_changed is set.  A record of an instance whose
+    // word is 0 takes its as-built box; of any other, a triangle the box of its barycentric hexagon under the new vertices
+    // (bvh8_geom.h: bary_hexagon_box) within the primitive's own, a sphere the primitive's own.
+    const float *bary;             // 6 floats per record: {u0, u1, v0, v1, w0, w1} (clip_triangle_barycentric; spheres: unused)
+    const uint32_t *inst_changed;  // per instance: bit 0 the transform differs from the build's, bit 1 its BLAS has had new vertices since
 };
 constexpr uint32_t kRefitTopLevels = 16, kRefitTopLevelNodes = 128;      // (one pass of the 1024-thread workgroup per level; wider levels are quicker as launches of their own: 95 -> ~45 us for the reference's sample)
 struct RefitLevels { uint32_t n_levels; uint32_t first[kRefitTopLevels], count[kRefitTopLevels]; };   // phases in processing order, each at most kRefitTopLevelNodes wide
@@ -237,6 +243,7 @@ struct InstanceTableArgs {
     const float *blas_box;         // 6 floats per instance: object-space bounds of its BLAS (lo > hi: empty)
     float *inst_xf, *inst_inv; uint32_t *inst_identity;
     uint32_t *flags;               // [0]: scene scale (float bits, starts at 1.0f); [1]: bit 0 set when a handle or visibility bit differs (-> rebuild), bit 1 when an sbtOffset does (-> synchronous update)
+    const float *build_xf; uint32_t *inst_changed;      // trees that keep their splits (RefitArgs::inst_changed), else NULL: the transforms of the build; bit 0 is set here, bit 1 kept
 };
 void launch_instance_tables(const InstanceTableArgs &a, hipStream_t s);
 // the end of an asynchronous update, one launch instead of two copies to the host, one from it and a fill: the refit's area sum and the
@@ -244,6 +251,15 @@ void launch_instance_tables(const InstanceTableArgs &a, hipStream_t s);
 struct UpdateEpilogueArgs { float *d_area; uint32_t *d_flags; float *h_area; uint32_t *h_flags; uint32_t flags_init0, flags_init1; };
 void launch_update_epilogue(const UpdateEpilogueArgs &a, hipStream_t s);
 void launch_refit_top(const RefitArgs &a, const RefitLevels &lv, hipStream_t s);
+// after a flattened build with spatial splits under HRT_CTX_KEEP_SPLITS, one thread per record: a triangle record's part of its triangle -- the
+// world clip box the build gave it -- as ranges of the triangle's barycentrics (bvh8_geom.h: clip_triangle_barycentric), the triangle
+// taken through triangle_world from the source vertices and the build's transform, as the builder took it
+struct BaryClipArgs {
+    const unsigned char *prims; uint32_t prim_stride, n_records;
+    const float *inst_xf; const uint32_t *inst_identity; const void *const *inst_src;
+    const float *clip; float *bary;
+};
+void launch_bary_clip(const BaryClipArgs &a, hipStream_t s);
 
 // particle pose update (pose.hip)
 struct PoseArgs {

@@ -288,6 +288,7 @@ static RefitArgs refit_args(HrtContext *ctx, Tlas &t) {
     ra.order = d.d_order;
     if (t.two_level) { ra.inst_inv = d.d_inst_inv; ra.inst_root = d.d_inst_root; }      // (the top level only: transform nodes and the boxes above them)
     else attach_rec_box(ctx, t, ra, t.n_prims);
+    if (t.keeps_splits) { ra.clip = d.d_keep_clip; ra.bary = d.d_keep_bary; ra.inst_changed = d.d_inst_changed; }      // (every refit after the build's own)
     return ra;
 }
 
@@ -577,6 +578,29 @@ static int build_over_instances(HrtContext *ctx, Tlas &t, const std::vector<HrtI
     return HRT_OK;
 }
 
+// ---- HRT_CTX_KEEP_SPLITS: what a flattened split tree keeps so that later refits keep its split references' boxes --
+//      the as-built world clip boxes, out of the build's working memory; every triangle record's part of its triangle as barycentric ranges,
+//      which hold wherever the triangle goes; the build's transforms and the per-instance word "changed since the build".  The build's own
+//      refit has been enqueued and is not touched: the tree is byte for byte the one built without the flag. ----
+static int keep_split_tables(HrtContext *ctx, Tlas &t, const float *staged_clip, hipStream_t s) {
+    TlasDevice &d = t.dev;
+    const size_t n = std::max(t.n_instances, 1u), rec_bytes = sizeof(float) * 6 * (size_t)t.n_prims;
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_keep_clip, rec_bytes));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_keep_bary, rec_bytes));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_build_xf, sizeof(float) * 12 * n));
+    HIP_TRY(ctx, pool_alloc(ctx, (void **)&d.d_inst_changed, sizeof(uint32_t) * n));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_keep_clip, staged_clip, rec_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d.d_build_xf, d.d_inst_xf, sizeof(float) * 12 * n, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d.d_inst_changed, 0, sizeof(uint32_t) * n, s));
+    const BaryClipArgs ba{reinterpret_cast<const unsigned char *>(d.d_prims), t.prim_stride, t.n_prims, d.d_inst_xf, d.d_inst_identity, d.d_inst_src, d.d_keep_clip, d.d_keep_bary};
+    launch_bary_clip(ba, s);
+    HIP_TRY(ctx, hipGetLastError());
+    t.h_build_xf = t.h_xf; t.h_inst_changed.assign(n, 0u);
+    t.alloc_bytes += 2 * (uint64_t)rec_bytes + (sizeof(float) * 12 + sizeof(uint32_t)) * (uint64_t)n;
+    t.keeps_splits = true;
+    return HRT_OK;
+}
+
 // ---- the merged device build: every visible instance's primitives in ONE world-space tree -- topology and primitive ids from build.hip (the
 //      top-down SAH phase, with spatial splits when device_split, then PLOC in the cells, the optimal collapse, the emission); the refit
 //      computes every record, box and quantised child, exactly as after an instance update ----
@@ -646,6 +670,9 @@ static int build_merged_on_device(HrtContext *ctx, Tlas &t, const BuildPlan &pla
     // update would recompute the boxes from whole primitives, so the first update rebuilds instead: has_split_refs)
     t.has_split_refs = device_split && r.split_levels;
     rc = reference_refit(ctx, t, in.split.pad, t.has_split_refs ? in.out_clip : nullptr, s);
+    if (rc != HRT_OK) return rc;
+    t.build_dropped = dropped;
+    if (t.has_split_refs && ctx->keep_splits) rc = keep_split_tables(ctx, t, in.out_clip, s);
     if (rc != HRT_OK) return rc;
     if (t.has_split_refs) HIP_TRY(ctx, hipStreamSynchronize(s));      // (the clip boxes live in the working memory)
     if (ctx->build_verbose)
@@ -1032,6 +1059,11 @@ int refit_tlas(HrtContext *ctx, Tlas &t, const std::vector<HrtInstance> &inst, h
     HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_xf, t.h_xf.data(), sizeof(float) * t.h_xf.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_identity, t.h_ident.data(), sizeof(uint32_t) * t.h_ident.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(t.dev.d_area, 0, sizeof(float), s));
+    if (t.keeps_splits) {      // which instances are where the build had them, bit for bit (the asynchronous path: k_instance_tables)
+        for (uint32_t i = 0; i < t.n_instances; ++i)
+            t.h_inst_changed[i] = (t.h_inst_changed[i] & 2u) | (std::memcmp(&t.h_xf[12 * (size_t)i], &t.h_build_xf[12 * (size_t)i], 12 * sizeof(float)) != 0 ? 1u : 0u);
+        HIP_TRY(ctx, hipMemcpyAsync(t.dev.d_inst_changed, t.h_inst_changed.data(), sizeof(uint32_t) * t.h_inst_changed.size(), hipMemcpyHostToDevice, s));
+    }
     t.async_words_ready = false;
     RefitArgs ra = refit_args(ctx, t);
     ra.pad = refit_pad(scene_scale);
@@ -1077,6 +1109,7 @@ static int update_async(HrtContext *ctx, Tlas *t, const HrtInstance *d_instances
     InstanceTableArgs ia{};
     ia.instances = d_instances; ia.n = n; ia.sig_handle = t->dev.d_sig_handle; ia.sig_visibility = t->dev.d_sig_visibility; ia.sig_sbt = t->dev.d_sig_sbt; ia.blas_box = t->dev.d_blas_box;
     ia.inst_xf = t->dev.d_inst_xf; ia.inst_inv = t->dev.d_inst_inv; ia.inst_identity = t->dev.d_inst_identity; ia.flags = t->dev.d_update_flags;
+    if (t->keeps_splits) { ia.build_xf = t->dev.d_build_xf; ia.inst_changed = t->dev.d_inst_changed; }
     launch_instance_tables(ia, s);
     RefitArgs ra = refit_args(ctx, *t);
     ra.scale_bits = t->dev.d_update_flags; ra.area_sum = t->dev.d_area;
@@ -1105,7 +1138,12 @@ static GeometryChange geometry_change(const HrtContext *ctx, const Tlas &t) {
     bool changed = false;
     for (uint32_t i = 0; i < n && !changed; ++i) changed = t.blas_refs[i]->geometry_epoch != t.blas_epoch[i];
     if (!changed) return GeometryChange::None;
-    if (ctx->refit == 0 || t.has_split_refs || t.n_prims == 0u) return GeometryChange::Rebuild;
+    if (ctx->refit == 0 || (t.has_split_refs && !t.keeps_splits) || t.n_prims == 0u) return GeometryChange::Rebuild;
+    if (t.keeps_splits) {      // (its records outnumber the primitives: what the build left out is counted there.  Triangle k stays triangle k: so do its barycentric ranges)
+        for (uint32_t i = 0; i < n; ++i)
+            if (t.blas_refs[i]->geometry_epoch != t.blas_epoch[i] && t.blas_refs[i]->kind != kPrimKindTriangle) return GeometryChange::Rebuild;
+        return t.build_dropped != 0u ? GeometryChange::Rebuild : GeometryChange::Refit;
+    }
     if (!t.two_level) {
         uint64_t visible = 0;
         for (uint32_t i = 0; i < n; ++i) visible += t.sig_visibility[i] ? t.blas_refs[i]->n_prims : 0u;
@@ -1148,6 +1186,10 @@ static int pick_up_geometry(HrtContext *ctx, Tlas &t, hipStream_t s) {
         Timer tm(ctx, s, HRT_K_REFIT);
         for (const PackSlice &ps : t.pack) if (moved.count(ps.blas)) launch_refit_phases(rp, ps.phases, s);
         HIP_TRY(ctx, hipGetLastError());
+    }
+    if (t.keeps_splits) {      // the instances of the changed BLASes are "changed" for good: their as-built clip boxes are the old geometry's
+        for (uint32_t i = 0; i < n; ++i) if (t.blas_refs[i]->geometry_epoch != t.blas_epoch[i]) t.h_inst_changed[i] |= 2u;
+        HIP_TRY(ctx, hipMemcpyAsync(d.d_inst_changed, t.h_inst_changed.data(), sizeof(uint32_t) * t.h_inst_changed.size(), hipMemcpyHostToDevice, s));
     }
     for (uint32_t i = 0; i < n; ++i) t.blas_epoch[i] = t.blas_refs[i]->geometry_epoch;
     return HRT_OK;
@@ -1342,8 +1384,9 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     int rc = download_instances(ctx, d_instances, n, s, inst);
     if (rc != HRT_OK) return rc;
     // (a tree with split references is a static-scene tree: refitted, its leaves would fall back to whole-primitive boxes around
-    // duplicated records -- worse than no splits -- so the first update replaces it by a device-built tree)
-    bool same = ctx->refit != 0 && t->n_prims != 0u && !force_rebuild && !t->has_split_refs;
+    // duplicated records -- worse than no splits -- so the first update replaces it by a device-built tree; not the tree that was built
+    // under HRT_CTX_KEEP_SPLITS: its refit has every record's part of its primitive)
+    bool same = ctx->refit != 0 && t->n_prims != 0u && !force_rebuild && (!t->has_split_refs || t->keeps_splits);
     for (uint32_t i = 0; i < n && same; ++i)
         same = inst[i].traversableHandle == t->sig_handle[i] && (inst[i].visibilityMask & 1u) == t->sig_visibility[i];
     bool moved_far = false;
@@ -1377,7 +1420,9 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
                      (unsigned long long)t->refits_since_build);
     HIP_TRY(ctx, hipDeviceSynchronize());                 // launches on other streams may still read the old tree
     // a two-level tree stays one: its top level is rebuilt, the BLAS trees -- with their spatial splits, where it was built for trace speed -- are copied in again
-    const int rb = t->two_level ? build_tlas_into(ctx, *t, inst, s, false, t->fast_trace, 1) : build_tlas_into(ctx, *t, inst, s, rebuild_over_instances(ctx, *t));
+    // ... and a tree that keeps its splits is built with them again: the flag asks for trace speed through the animation
+    const int rb = t->two_level ? build_tlas_into(ctx, *t, inst, s, false, t->fast_trace, 1)
+                 : t->keeps_splits ? build_tlas_into(ctx, *t, inst, s, false, true, -1) : build_tlas_into(ctx, *t, inst, s, rebuild_over_instances(ctx, *t));
     if (rb == HRT_OK) t->built_posed = true;      // (built for the instances as they are now: the next update need not be checked on the spot)
     return rb;
 }

@@ -123,7 +123,7 @@ int hrt_ctx_create(int device_id, uint32_t flags, HrtContext **out_ctx) {
         return fail(nullptr, HRT_ERR_NO_DEVICE, "device %d is %s; libhrt carries gfx950 code only", device_id, prop.gcnArchName);
     if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, HRT_ERR_HIP, "hipSetDevice(%d) failed", device_id);
     std::unique_ptr<HrtContext> ctx(new HrtContext());
-    ctx->device = device_id; ctx->flags = flags; ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ctx->device = device_id; ctx->flags = flags; ctx->keep_splits = (flags & HRT_CTX_KEEP_SPLITS) != 0u; ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const std::vector<uint32_t> jump = make_jump_tables();
     if (hipMalloc((void **)&ctx->d_jump, jump.size() * sizeof(uint32_t)) != hipSuccess ||
         hipMemcpy(ctx->d_jump, jump.data(), jump.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||

@@ -89,6 +89,10 @@ struct TlasDevice {
     float *d_pack_xf = nullptr; uint32_t *d_pack_identity = nullptr; const void **d_pack_src = nullptr; uint32_t *d_pack_order = nullptr;
     uint32_t *d_leaf_parent = nullptr;                   // one-level trees of triangles: per record, the node whose leaf slot covers it (ensure_leaf_parent: made at the first launch that wants
                                                          // it; a refit keeps topology and record order, hence the table; a rebuild is a new Tlas and starts without one)
+    // a flattened tree that keeps its spatial splits through updates (HRT_CTX_KEEP_SPLITS; Tlas::keeps_splits): per record the as-built world
+    // clip box and the barycentric ranges of its part of its triangle (6 floats each), per instance the build's transform (12 floats) and the
+    // word "changed since the build" (RefitArgs::inst_changed)
+    float *d_keep_clip = nullptr, *d_keep_bary = nullptr, *d_build_xf = nullptr; uint32_t *d_inst_changed = nullptr;
 };
 static_assert(std::is_standard_layout<TlasDevice>::value && std::is_trivially_copyable<TlasDevice>::value && sizeof(TlasDevice) % sizeof(void *) == 0,
               "TlasDevice holds pool blocks only: free_tlas_device walks it as an array of pointers");
@@ -133,6 +137,10 @@ struct Tlas {
     float built_reach = 1.0f;                            // the largest object-space |coordinate| a ray origin was assumed to have when the BLAS trees were padded
     bool has_split_refs = false;                         // a FLATTENED tree built with spatial splits (HRT_CTX_FAST_TRACE): a refit would recompute the leaf boxes from whole primitives, so the first update rebuilds instead
                                                          // (never a two-level tree: its updates do not touch the BLAS trees, split or not)
+    bool keeps_splits = false;                           // ... built under HRT_CTX_KEEP_SPLITS: the tree has the tables (TlasDevice::d_keep_*) with which a refit keeps the split references' boxes, and is
+                                                         // refitted like any other; a rebuild inside an update is a split build again
+    uint32_t build_dropped = 0;                          // merged device builds: non-finite primitives the build left out
+    std::vector<float> h_build_xf; std::vector<uint32_t> h_inst_changed;      // keeps_splits: host copies of d_build_xf / d_inst_changed (synchronous updates fill bit 0 here)
     bool fast_trace = false;                             // what hrt_tlas_build was asked for: a rebuild inside hrt_tlas_update of a two-level tree asks for the same (the BLASes' split trees are reused)
     float *h_area = nullptr;                             // pinned: area sum of the last refit
     hipEvent_t area_ready = nullptr; bool area_pending = false;
@@ -349,6 +357,7 @@ struct HrtContext {
     // (profiles/r04_cprim_sweep.txt).  HRT_BVH_CPRIM sets both.
     float build_c_prim_bodies = 2.0f;
     bool build_verbose = false;                 // HRT_BUILD_VERBOSE: builds and updates report on stderr
+    bool keep_splits = false;                   // HRT_CTX_KEEP_SPLITS at hrt_ctx_create, or HRT_KEEP_SPLITS=1: flattened device split builds keep their splits through updates
     int refit = 1;                              // hrt_tlas_update: 1 = device refit when only transforms changed, 0 = always rebuild
     int refit_moved_far_check = 1;              // the first update after a build rebuilds without refitting first when most instances have moved further than their size (HRT_REFIT_MOVED_FAR=0: always refit first)
     float refit_rebuild_ratio = 1.5f;           // rebuild when the refitted tree's weighted mean node area has grown by this factor

@@ -21,7 +21,9 @@ namespace hrt {
 __device__ __forceinline__ float shfl_xor_f(float v, int m) { return __shfl_xor(v, m, 64); }
 
 // One primitive record: its world-space form from the object-space source and the instance's transform, and (a.rec_box) its padded box.
-// Returns the box in lo / hi (empty when the primitive is not finite).
+// Returns the box in lo / hi (empty when the primitive is not finite).  kKeep: a tree that keeps its spatial splits (RefitArgs::bary) -- the
+// other trees' instantiation is the code it was before there were two.
+template <bool kKeep>
 __device__ __forceinline__ void refit_record(const RefitArgs &a, size_t r, float pad, float *lo, float *hi) {
     unsigned char *rec = a.prims + r * a.prim_stride;
     float *rf = reinterpret_cast<float *>(rec);
@@ -30,11 +32,11 @@ __device__ __forceinline__ void refit_record(const RefitArgs &a, size_t r, float
     const float *m = a.inst_xf + 12 * (size_t)inst;
     const bool ident = a.inst_identity[inst] != 0u;
     float plo[3], phi[3];
+    float v0[3], e1[3], e2[3];
     if (kind == 0u) {
         const float *src = reinterpret_cast<const float *>(a.inst_src[inst]) + 9 * (size_t)prim;
         float s9[9];
         for (int q = 0; q < 9; ++q) s9[q] = src[q];
-        float v0[3], e1[3], e2[3];
         triangle_world(s9, m, ident, v0, e1, e2, plo, phi);
         rf[0] = v0[0]; rf[1] = v0[1]; rf[2] = v0[2];
         rf[4] = e1[0]; rf[5] = e1[1]; rf[6] = e1[2];
@@ -43,7 +45,18 @@ __device__ __forceinline__ void refit_record(const RefitArgs &a, size_t r, float
         const float c3[3] = {rf[0], rf[1], rf[2]};
         sphere_world_bounds(c3, rf[4], m, ident, plo, phi);
     }
-    if (a.clip) {                                      // a reference of a spatial split: the box its cell is responsible for
+    if (kKeep) {
+        if (a.inst_changed[inst] == 0u) {              // nothing of the instance has moved since the build: the box as built
+            const float *cb = a.clip + 6 * r;
+            for (int q = 0; q < 3; ++q) { plo[q] = cb[q]; phi[q] = cb[3 + q]; }
+        } else if (kind == 0u) {                       // the record's part of the triangle where the triangle is now, within the triangle's own box
+            const float *gb = a.bary + 6 * r;
+            float g[6], hlo[3], hhi[3];
+            for (int q = 0; q < 6; ++q) g[q] = gb[q];
+            const bool part = bary_hexagon_box(v0, e1, e2, g, hlo, hhi);
+            for (int q = 0; q < 3; ++q) { plo[q] = part ? fmaxf(plo[q], hlo[q]) : plo[q]; phi[q] = part ? fminf(phi[q], hhi[q]) : phi[q]; }
+        }                                              // (a sphere that has moved: its whole box, under every one of its records)
+    } else if (a.clip) {                               // a reference of a spatial split: the box its cell is responsible for
         const float *cb = a.clip + 6 * r;
         for (int q = 0; q < 3; ++q) { plo[q] = cb[q]; phi[q] = cb[3 + q]; }
     }
@@ -52,21 +65,25 @@ __device__ __forceinline__ void refit_record(const RefitArgs &a, size_t r, float
 }
 
 // small trees: every record by its own thread, before the levels are walked
+template <bool kKeep>
 __global__ __launch_bounds__(256) void k_refit_records(RefitArgs a) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= a.n_records) return;
     const float pad = a.scale_bits ? 4e-6f * fmaxf(1.0f, __uint_as_float(a.scale_bits[0])) : a.pad;
     float lo[3], hi[3];
-    refit_record(a, r, pad, lo, hi);
+    refit_record<kKeep>(a, r, pad, lo, hi);
     float *b = a.rec_box + 6 * (size_t)r;
     for (int q = 0; q < 3; ++q) { b[q] = lo[q]; b[3 + q] = hi[q]; }
 }
 void launch_refit_records(const RefitArgs &a, hipStream_t s) {
-    if (a.rec_box && a.n_records) hipLaunchKernelGGL(k_refit_records, dim3((a.n_records + 255u) / 256u), dim3(256), 0, s, a);
+    if (!a.rec_box || !a.n_records) return;
+    if (a.bary) hipLaunchKernelGGL(k_refit_records<true>, dim3((a.n_records + 255u) / 256u), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_refit_records<false>, dim3((a.n_records + 255u) / 256u), dim3(256), 0, s, a);
 }
 
 // One child slot of one node; the eight lanes of a node call this together (they exchange boxes by
 // shuffles), dead groups (live == false) go through the motions without touching memory.
+template <bool kKeep>
 __device__ __forceinline__ void refit_slot(const RefitArgs &a, uint32_t node, uint32_t slot, bool live) {
     unsigned char *nd = a.nodes + (size_t)node * a.node_stride;
     const uint32_t *ndw = reinterpret_cast<const uint32_t *>(nd);
@@ -102,7 +119,7 @@ __device__ __forceinline__ void refit_slot(const RefitArgs &a, uint32_t node, ui
                     if (a.rec_box) {                                   // (k_refit_records has been here)
                         const float *b = a.rec_box + 6 * (size_t)(prim_base + off + k);
                         for (int q = 0; q < 3; ++q) { plo[q] = b[q]; phi[q] = b[3 + q]; }
-                    } else refit_record(a, (size_t)(prim_base + off + k), pad, plo, phi);
+                    } else refit_record<kKeep>(a, (size_t)(prim_base + off + k), pad, plo, phi);
                     for (int q = 0; q < 3; ++q) { lo[q] = fminf(lo[q], plo[q]); hi[q] = fmaxf(hi[q], phi[q]); }
                 }
             }
@@ -185,15 +202,17 @@ __device__ __forceinline__ uint32_t phase_node(const RefitArgs &a, uint32_t firs
 }
 
 // a wide phase: one launch, eight lanes per node
+template <bool kKeep>
 __global__ __launch_bounds__(256) void k_refit_level(RefitArgs a) {
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
     const uint32_t local = tid >> 3;
     const bool live = local < a.n_nodes;                       // whole 8-lane groups are live or not
-    refit_slot(a, phase_node(a, a.first_node, live ? local : 0u), tid & 7u, live);
+    refit_slot<kKeep>(a, phase_node(a, a.first_node, live ? local : 0u), tid & 7u, live);
 }
 
 // the narrow phases at the top of the tree (and all of a small tree): one workgroup walks them in order
 // with a barrier in between, instead of one launch per phase
+template <bool kKeep>
 __global__ __launch_bounds__(1024) void k_refit_top(RefitArgs a, RefitLevels lv) {
     const uint32_t group = threadIdx.x >> 3, slot = threadIdx.x & 7u;
     for (uint32_t l = 0; l < lv.n_levels; ++l) {
@@ -201,7 +220,7 @@ __global__ __launch_bounds__(1024) void k_refit_top(RefitArgs a, RefitLevels lv)
         for (uint32_t base = 0; base < n; base += 128u) {
             const uint32_t local = base + group;
             const bool live = local < n;
-            refit_slot(a, phase_node(a, first, live ? local : 0u), slot, live);
+            refit_slot<kKeep>(a, phase_node(a, first, live ? local : 0u), slot, live);
         }
         __threadfence_block();
         __syncthreads();                                       // the next level reads this level's node boxes
@@ -221,6 +240,11 @@ __global__ __launch_bounds__(256) void k_instance_tables(InstanceTableArgs a) {
     if (u[13] != a.sig_sbt[i]) atomicOr(&a.flags[1], 2u);         // sbtOffset: the next update refreshes the material tables
     float t[12];
     for (int k = 0; k < 12; ++k) { t[k] = m[k]; a.inst_xf[12 * (size_t)i + k] = t[k]; }
+    if (a.inst_changed) {                                          // a tree that keeps its splits: is the instance where the build had it, bit for bit?
+        uint32_t diff = 0u;
+        for (int k = 0; k < 12; ++k) diff |= u[k] ^ __float_as_uint(a.build_xf[12 * (size_t)i + k]);
+        a.inst_changed[i] = (a.inst_changed[i] & 2u) | (diff != 0u ? 1u : 0u);
+    }
     const bool id = t[0] == 1.0f && t[1] == 0.0f && t[2] == 0.0f && t[3] == 0.0f && t[4] == 0.0f && t[5] == 1.0f && t[6] == 0.0f && t[7] == 0.0f &&
                     t[8] == 0.0f && t[9] == 0.0f && t[10] == 1.0f && t[11] == 0.0f &&
                     !(__float_as_uint(t[1]) | __float_as_uint(t[2]) | __float_as_uint(t[3]) | __float_as_uint(t[4]) | __float_as_uint(t[6]) | __float_as_uint(t[7]) |
@@ -307,6 +331,29 @@ void launch_pack_blas(const PackBlasArgs &a, hipStream_t s) {
     if (n) hipLaunchKernelGGL(k_pack_blas, dim3((n + 255u) / 256u), dim3(256), 0, s, a);
 }
 
+// ---- a tree that keeps its splits (device_types.h: BaryClipArgs): one thread per record, once per build ----
+__global__ __launch_bounds__(256) void k_bary_clip(BaryClipArgs a) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.n_records) return;
+    const uint32_t *ru = reinterpret_cast<const uint32_t *>(a.prims + (size_t)r * a.prim_stride);
+    const uint32_t prim = ru[3], inst = ru[7], kind = ru[11];
+    float *out = a.bary + 6 * (size_t)r;
+    float g[6] = {0.0f, 1.0f, 0.0f, 1.0f, 0.0f, 1.0f};
+    if (kind == 0u) {
+        const float *src = reinterpret_cast<const float *>(a.inst_src[inst]) + 9 * (size_t)prim;
+        float s9[9], v0[3], e1[3], e2[3], plo[3], phi[3];
+        for (int q = 0; q < 9; ++q) s9[q] = src[q];
+        triangle_world(s9, a.inst_xf + 12 * (size_t)inst, a.inst_identity[inst] != 0u, v0, e1, e2, plo, phi);
+        const float *cb = a.clip + 6 * (size_t)r;
+        const float blo[3] = {cb[0], cb[1], cb[2]}, bhi[3] = {cb[3], cb[4], cb[5]};
+        clip_triangle_barycentric(v0, e1, e2, blo, bhi, g);
+    }
+    for (int q = 0; q < 6; ++q) out[q] = g[q];
+}
+void launch_bary_clip(const BaryClipArgs &a, hipStream_t s) {
+    if (a.n_records) hipLaunchKernelGGL(k_bary_clip, dim3((a.n_records + 255u) / 256u), dim3(256), 0, s, a);
+}
+
 // ---- leaf_parent (device_types.h: LeafParentArgs): one thread per (node, slot) of a finished one-level tree.  A leaf slot names its records --
 // the node's primitive base + the meta byte's offset (bits 4..0), as many as the unary count (bits 7..5: 1, 3, 7) has bits -- and writes its
 // node's index for each; inner slots (meta bits 4 and 3 both set, bvh8.h) and empty ones (0) write nothing.  Every record has exactly one slot,
@@ -331,12 +378,14 @@ void launch_leaf_parent(const LeafParentArgs &a, hipStream_t s) {
 void launch_refit_level(const RefitArgs &a, hipStream_t s) {
     if (a.n_nodes == 0) return;
     const uint32_t threads = a.n_nodes * 8u;
-    hipLaunchKernelGGL(k_refit_level, dim3((threads + 255u) / 256u), dim3(256), 0, s, a);
+    if (a.bary) hipLaunchKernelGGL(k_refit_level<true>, dim3((threads + 255u) / 256u), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_refit_level<false>, dim3((threads + 255u) / 256u), dim3(256), 0, s, a);
 }
 
 void launch_refit_top(const RefitArgs &a, const RefitLevels &lv, hipStream_t s) {
     if (lv.n_levels == 0) return;
-    hipLaunchKernelGGL(k_refit_top, dim3(1), dim3(1024), 0, s, a, lv);
+    if (a.bary) hipLaunchKernelGGL(k_refit_top<true>, dim3(1), dim3(1024), 0, s, a, lv);
+    else hipLaunchKernelGGL(k_refit_top<false>, dim3(1), dim3(1024), 0, s, a, lv);
 }
 
 }  // namespace hrt

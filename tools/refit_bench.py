@@ -14,7 +14,7 @@ sys.path.insert(0, str(ROOT))
 hrt = importlib.import_module("nvidia-optix-ray-tracer_amd")
 
 
-def run(name, scene, poses_of, frames, mode):
+def run(name, scene, poses_of, frames, mode, asynchronous=False):
     """mode: "refit" (device refit), "rebuild" (HRT_REFIT=0: tree over instances, the default for rebuilds during updates)
     or "rebuild-merged" (HRT_TLAS_INSTANCED=-1: full SAH build over all primitives)."""
     refit = mode == "refit"
@@ -22,7 +22,7 @@ def run(name, scene, poses_of, frames, mode):
     os.environ["HRT_TLAS_INSTANCED"] = "-1" if mode == "rebuild-merged" else "0"
     import ctypes as C
     import torch
-    r = hrt.Renderer(0, hrt.CTX_TIMING)
+    r = hrt.Renderer(0, hrt.CTX_TIMING | (hrt.CTX_ASYNC_UPDATE if asynchronous else 0))
     r.load_scene(scene)
     r.set_frame(64, 64, 1, aov=False)
     r.render(1)
@@ -48,7 +48,7 @@ def run(name, scene, poses_of, frames, mode):
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     s = r.stats()
-    out = {"scene": name, "mode": mode, "instances": n,
+    out = {"scene": name, "mode": mode, "async_update": asynchronous, "instances": n,
            "bvh_nodes": int(n_nodes), "triangles": int(n_tris), "frames": frames,
            "update_call_ms": round((t1 - t0) * 1e3 / frames, 4), "update_done_ms": round((t2 - t0) * 1e3 / frames, 4),
            "tlas_refits": int(s.tlas_refits), "tlas_rebuilds": int(s.tlas_rebuilds), "refit_ratio": round(s.tlas_refit_ratio, 3)}
@@ -64,6 +64,7 @@ def run(name, scene, poses_of, frames, mode):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--async-update", action="store_true", help="HRT_CTX_ASYNC_UPDATE: the refits alone, with the per-instance tables derived on the device (k_instance_tables)")
     ap.add_argument("--only", default="", help="one case, e.g. particles-25:rebuild-merged (with --frames rebuilds: for API-level profiles)")
     a = ap.parse_args()
     if a.only:
@@ -83,7 +84,9 @@ def main():
         cached = lambda f, poses=poses, cache=cache: cache.setdefault(f, poses(f))               # noqa: E731
         for f in range(a.frames + 1):
             cached(f)
-        run("particles-%d" % n_p, sc, cached, a.frames, "refit")
+        run("particles-%d" % n_p, sc, cached, a.frames, "refit", a.async_update)
+        if a.async_update:
+            continue
         run("particles-%d" % n_p, sc, cached, min(a.frames, 5), "rebuild")
         run("particles-%d" % n_p, sc, cached, min(a.frames, 5), "rebuild-merged")
     # one big static instance that moves as a whole (C4 geometry)
@@ -92,8 +95,9 @@ def main():
     def poses(f, base=base):
         m = base.copy(); m[3] += 0.01 * f
         return [m]
-    run("soup-1m", sc, poses, a.frames, "refit")
-    run("soup-1m", sc, poses, 1, "rebuild")
+    run("soup-1m", sc, poses, a.frames, "refit", a.async_update)
+    if not a.async_update:
+        run("soup-1m", sc, poses, 1, "rebuild")
 
 
 if __name__ == "__main__":
