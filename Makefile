@@ -26,7 +26,7 @@ $(PATH_OBJS): $(LIBDIR)/%.o: $(CSRC)/%.hip $(PATH_HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the device builder: one translation unit per phase over the shared headers (bvh8_collapse.h: the collapse, shared with the host builder);
-# blas_update: hrt_blas_update_triangles' copy-and-bounds pass, which shares the builder's reduction
+# blas_update: hrt_blas_update_triangles' and hrt_blas_update_spheres' copy-and-bounds passes, which share the builder's reduction
 BUILD_UNITS := build build_split build_reinsert blas_update
 BUILD_HDRS  := $(addprefix $(CSRC)/,build.h build_dev.h bvh8.h bvh8_geom.h bvh8_collapse.h)
 BUILD_OBJS  := $(BUILD_UNITS:%=$(LIBDIR)/%.o)

@@ -123,7 +123,8 @@ typedef struct HrtContext HrtContext;
                                     byte-identical); a triangle record of any other instance takes the box of its barycentric hexagon under the new
                                     vertices -- an affine map preserves barycentrics, so it holds under rotation, any scale, a singular matrix and
                                     after hrt_blas_update_triangles, which such a tree follows by a refit too (unless the build left a non-finite
-                                    primitive out); a sphere record of a moved instance takes the sphere's whole box under every one of its
+                                    primitive out); a sphere record of a moved instance, or of a BLAS that has had hrt_blas_update_spheres (which
+                                    such a tree follows by a refit too), takes the sphere's whole box under every one of its
                                     records (correct; the limitation).  The refit stands under the usual quality verdict
                                     (HRT_REFIT_REBUILD_RATIO) and the first update's moved-far check; a rebuild inside an update -- a changed
                                     handle or visibility bit, a verdict, moved far, HRT_REFIT=0 -- is a device split build again, not a default
@@ -176,8 +177,35 @@ int  hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas);
  * The denoiser: a PENDING by-primitive link (hrt_denoise_temporal_rebind_geometry) that reads this BLAS as its old geometry is dropped,
  * as hrt_tlas_destroy drops a link; an existing history is left alone -- it reprojects the instance as if rigid, the id and depth tests
  * vet the taps: an approximation.  Not thread-safe against a concurrent build or update of a TLAS that instances the same BLAS;
- * otherwise like the build calls.  Sphere BLASes have no update (rebuild them). */
+ * otherwise like the build calls.  Sphere BLASes: hrt_blas_update_spheres, below. */
 int  hrt_blas_update_triangles(HrtContext *ctx, HrtTraversable blas, const HrtFloat3 *d_vertices, uint32_t n_vertices, void *stream);
+/* OPTIX_BUILD_OPERATION_UPDATE for a sphere GAS: the same spheres at new object-space centres and with new radii (a moving particle
+ * cloud), without a new handle and without a rebuild.  `blas` is a live sphere BLAS of the context and n_spheres exactly what it was
+ * built with: sphere k stays sphere k.  HRT_ERR_INVALID for a NULL context, an unknown handle, a triangle BLAS, another count, NULL
+ * d_centers or d_radii with a non-zero count, or a pointer that is not aligned for a float; a refused call changes nothing.  A BLAS of
+ * zero primitives with n_spheres == 0: HRT_OK.
+ * The centres and radii are written into the BLAS's own copy on `stream` (the radius verbatim, sign included, as the build stores it)
+ * and the object-space bounds recomputed in the same pass (csrc/blas_update.hip; by the build's rule, so an updated BLAS has the bounds
+ * a BLAS built from these arrays has; a sphere with a non-finite centre or radius contributes nothing and is never hit).  Like the
+ * build, the call synchronises `stream` once for the bounds' read-back, and the caller may free d_centers and d_radii when it returns.
+ * The BLAS's host copy, its bounding sphere and its cached object-space trees (two-level TLASes, rebuilds during updates) are dropped
+ * and made again by the next build that wants them, exactly as hrt_blas_update_triangles drops them.
+ * Every TLAS that instances the BLAS is STALE until its next hrt_tlas_update, which picks the change up: a refit where the tree holds
+ * every primitive of the BLAS as a record of its own -- the default flattened build, trees over instances, two-level trees with
+ * unsplit BLAS trees (the BLAS's subtree is refitted in place, then the top level), synchronous and HRT_CTX_ASYNC_UPDATE alike,
+ * counted in HrtStats.tlas_refits, under the same quality verdict as moved instances (the two-level subtree's own degradation is
+ * not part of it) -- and a rebuild, counted in tlas_rebuilds, everywhere else: HRT_CTX_FAST_TRACE trees with split references
+ * (but for the flattened tree built under HRT_CTX_KEEP_SPLITS, which refits: every record of a changed sphere takes the sphere's whole
+ * box at its new place, as under a moved instance), two-level trees in which the BLAS carries a split tree, trees built while a
+ * primitive of the BLAS was non-finite, HRT_REFIT=0.
+ * Tracing or rendering a stale TLAS is well defined: its records hold a centre and radius of their own, so it sees the OLD spheres,
+ * bit for bit, until that update.  Shading data is not the library's: HrtSbtRecord.data.sphere.centers / radii are the caller's
+ * buffers, which the caller rewrites, ordered on its stream against the launches that shade with them.
+ * The denoiser: sphere BLASes never link by primitive, so no pending link (hrt_denoise_temporal_rebind_geometry) can read one; an
+ * existing history is left alone -- it reprojects the instance as if rigid, the id and depth tests vet the taps: an approximation.
+ * Not thread-safe against a concurrent build or update of a TLAS that instances the same BLAS; otherwise like the build calls. */
+int  hrt_blas_update_spheres(HrtContext *ctx, HrtTraversable blas, const HrtFloat3 *d_centers, const float *d_radii,
+                             uint32_t n_spheres, void *stream);
 
 /* replaces buildIAS / updateIAS, src/Global/RendererImpl.cu:174-242.  d_instances lives in
  * device memory (reference: cudaMemcpy H2D then build, src/Global/RendererMesh.cu:151-160).

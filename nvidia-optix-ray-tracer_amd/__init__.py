@@ -128,7 +128,7 @@ NO_INSTANCE = 0xFFFFFFFF        # HRT_NO_INSTANCE: hrt_denoise_temporal_rebind's
 # every symbol include/hrt.h declares (checked by the CPU test-suite)
 EXPORTS = [
     "hrt_ctx_create", "hrt_ctx_destroy", "hrt_ctx_set_flags", "hrt_last_error", "hrt_version",
-    "hrt_blas_build_triangles", "hrt_blas_build_spheres", "hrt_blas_destroy", "hrt_blas_update_triangles",
+    "hrt_blas_build_triangles", "hrt_blas_build_spheres", "hrt_blas_destroy", "hrt_blas_update_triangles", "hrt_blas_update_spheres",
     "hrt_tlas_build", "hrt_tlas_update", "hrt_tlas_destroy", "hrt_pose_instances",
     "hrt_sbt_record_pack_header", "hrt_materials_set", "hrt_miss_set",
     "hrt_rng_init", "hrt_rng_free", "hrt_render_launch", "hrt_sync", "hrt_primary_hits_get", "hrt_to_rgba8", "hrt_color_to_float4",
@@ -180,6 +180,7 @@ def load_library():
     lib.hrt_blas_build_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.hrt_blas_destroy.argtypes = [C.c_void_p, C.c_uint64]
     lib.hrt_blas_update_triangles.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.hrt_blas_update_spheres.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.hrt_tlas_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.hrt_tlas_update.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.hrt_tlas_destroy.argtypes = [C.c_void_p, C.c_uint64]

@@ -130,6 +130,8 @@ constexpr size_t kBoundsScratchBytes = 512;           // ... of gpu_blas_bounds
 hipError_t gpu_blas_bounds(const float *d_src, uint32_t n_prims, uint32_t kind, float *lo, float *hi, void *d_scratch, hipStream_t s);
 // blas_update.hip (hrt_blas_update_triangles): n_prims triangles from d_src into d_dst, and their bounds as gpu_blas_bounds gives them for d_dst afterwards
 hipError_t gpu_blas_update_triangles(const float *d_src, float *d_dst, uint32_t n_prims, float *lo, float *hi, void *d_scratch, hipStream_t s);
+// ... (hrt_blas_update_spheres): n spheres from d_centers / d_radii into d_dst as {cx, cy, cz, r} (16-byte aligned), and their bounds likewise
+hipError_t gpu_blas_update_spheres(const float *d_centers, const float *d_radii, float *d_dst, uint32_t n, float *lo, float *hi, void *d_scratch, hipStream_t s);
 // bounding sphere of a BLAS around `center` (radius < 0: none)
 hipError_t gpu_blas_radius(const float *d_src, uint32_t n_prims, uint32_t kind, const float *center, float *radius, void *d_scratch, hipStream_t s);
 void launch_pack_spheres(const float *centers, const float *radii, uint32_t n, float *out, hipStream_t s);

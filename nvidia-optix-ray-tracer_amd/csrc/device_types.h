@@ -197,8 +197,9 @@ struct RefitArgs {
     const uint32_t *order;         // NULL: node index = position (trees stored breadth first)
     const float *inst_xf;          // 12 floats per instance: object -> world
     const uint32_t *inst_identity;
-    const void *const *inst_src;   // per instance: object-space triangle vertices (9 floats per triangle) of its BLAS; the top level of a
-                                   // two-level tree: the BLAS's object-space box (6 floats)
+    const void *const *inst_src;   // per instance: the object-space geometry of its BLAS where the BLAS keeps it (Blas::d_verts) -- 9 floats per
+                                   // triangle, {cx, cy, cz, r} per sphere (16-byte aligned) -- which every record is derived from anew; the
+                                   // top level of a two-level tree: the BLAS's object-space box and bounding sphere (10 floats)
     const float *inst_inv;         // two-level trees: 12 floats per instance, world -> object (written into the transform nodes)
     const uint32_t *inst_root;     // two-level trees: per instance, the node index of its BLAS's root
     float pad;

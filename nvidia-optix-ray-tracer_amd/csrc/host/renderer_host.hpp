@@ -59,6 +59,11 @@ inline GAS buildGASForTriangles(HrtContext *ctx, const RendererTriangle &t, hipS
 inline void updateGASForTriangles(HrtContext *ctx, const GAS &gas, const RendererTriangle &t, hipStream_t stream = nullptr) {
     hrtCheckError(ctx, hrt_blas_update_triangles(ctx, gas.first, t.dev_vertices, (uint32_t)(3 * t.count), stream));
 }
+// ... and on a sphere GAS (a moving particle cloud): the same spheres at new centres and with new radii, sphere.count as at the build.  The
+// record's centers / radii are the caller's buffers (sphere.dev_centers / dev_radii where they are the ones it shades with); follow with updateIAS.
+inline void updateGASForSpheres(HrtContext *ctx, const GAS &gas, const RendererSphere &s, hipStream_t stream = nullptr) {
+    hrtCheckError(ctx, hrt_blas_update_spheres(ctx, gas.first, s.dev_centers, s.dev_radii, (uint32_t)s.count, stream));
+}
 // buildIAS / updateIAS, src/Global/RendererImpl.cu:174-242
 inline IAS buildIAS(HrtContext *ctx, const HrtInstance *dev_instances, size_t instanceCount, hipStream_t stream = nullptr) {
     HrtTraversable h = 0;

@@ -1124,7 +1124,7 @@ static int update_async(HrtContext *ctx, Tlas *t, const HrtInstance *d_instances
     return HRT_OK;
 }
 
-// ---- geometry that changed under a tree (hrt_blas_update_triangles): every instance remembers the Blas::geometry_epoch its tree was last
+// ---- geometry that changed under a tree (hrt_blas_update_triangles / _spheres): every instance remembers the Blas::geometry_epoch its tree was last
 //      built or refitted for (Tlas::blas_epoch).  Host state only: an asynchronous update still reads nothing back. ----
 enum class GeometryChange { None, Refit, Rebuild };
 
@@ -1139,11 +1139,9 @@ static GeometryChange geometry_change(const HrtContext *ctx, const Tlas &t) {
     for (uint32_t i = 0; i < n && !changed; ++i) changed = t.blas_refs[i]->geometry_epoch != t.blas_epoch[i];
     if (!changed) return GeometryChange::None;
     if (ctx->refit == 0 || (t.has_split_refs && !t.keeps_splits) || t.n_prims == 0u) return GeometryChange::Rebuild;
-    if (t.keeps_splits) {      // (its records outnumber the primitives: what the build left out is counted there.  Triangle k stays triangle k: so do its barycentric ranges)
-        for (uint32_t i = 0; i < n; ++i)
-            if (t.blas_refs[i]->geometry_epoch != t.blas_epoch[i] && t.blas_refs[i]->kind != kPrimKindTriangle) return GeometryChange::Rebuild;
-        return t.build_dropped != 0u ? GeometryChange::Rebuild : GeometryChange::Refit;
-    }
+    // (its records outnumber the primitives: what the build left out is counted there.  Triangle k stays triangle k: so do its barycentric
+    // ranges; every record of a sphere takes the sphere's whole box at its new place, as under a moved instance)
+    if (t.keeps_splits) return t.build_dropped != 0u ? GeometryChange::Rebuild : GeometryChange::Refit;
     if (!t.two_level) {
         uint64_t visible = 0;
         for (uint32_t i = 0; i < n; ++i) visible += t.sig_visibility[i] ? t.blas_refs[i]->n_prims : 0u;
@@ -1237,6 +1235,28 @@ static int register_blas(HrtContext *ctx, std::shared_ptr<Blas> b, HrtTraversabl
     return HRT_OK;
 }
 
+// The BLAS's own copy holds new geometry (hrt_blas_update_triangles / _spheres) with these bounds: what was derived from the old goes -- the
+// host copy, the bounding sphere, the cached object-space trees, whose clip boxes are the old geometry's -- and the epoch tells every TLAS
+// over the BLAS, at its next hrt_tlas_update, that its tree is of the geometry as it was.
+static int geometry_replaced(HrtContext *ctx, Blas &b, const float *lo, const float *hi) {
+    BlasTree old_tmpl, old_split;
+    {
+        std::lock_guard<std::mutex> lk(b.tmpl_mu);
+        for (int a = 0; a < 3; ++a) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
+        b.bsphere_ready = false; b.bsphere[3] = -1.0f;
+        b.host_geometry = false; b.verts.clear(); b.centers.clear(); b.radii.clear();      // (ensure_host_geometry fetches again)
+        b.tmpl = Bvh8(); b.tmpl_built = false; b.split_decided = false;   // (rebuilt by the next build that wants them)
+        std::swap(old_tmpl, b.tmpl_dev); std::swap(old_split, b.split);
+        b.geometry_epoch++;
+    }
+    if (old_tmpl.d_nodes || old_split.d_nodes) {
+        // (a two-level build on another stream may still be copying from them)
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        for (BlasTree *tr : {&old_tmpl, &old_split}) for (void *p : {(void *)tr->d_nodes, (void *)tr->d_prims, (void *)tr->d_clip}) if (p) (void)hipFree(p);
+    }
+    return HRT_OK;
+}
+
 extern "C" {
 
 // ---- acceleration structures ---------------------------------------------------------
@@ -1308,22 +1328,33 @@ int hrt_blas_update_triangles(HrtContext *ctx, HrtTraversable blas, const HrtFlo
     const hipError_t e = gpu_blas_update_triangles(reinterpret_cast<const float *>(d_vertices), b->d_verts, b->n_prims, lo, hi, arena.p, (hipStream_t)stream);
     scratch_release(ctx, arena);
     HIP_TRY(ctx, e);
-    BlasTree old_tmpl, old_split;
+    return geometry_replaced(ctx, *b, lo, hi);
+}
+
+// ... and for a sphere GAS (include/hrt.h): new centres and radii into the BLAS's {cx, cy, cz, r} copy and its bounds in one pass.
+int hrt_blas_update_spheres(HrtContext *ctx, HrtTraversable blas, const HrtFloat3 *d_centers, const float *d_radii, uint32_t n_spheres, void *stream) {
+    if (!ctx) return HRT_ERR_INVALID;
+    std::shared_ptr<Blas> b;
     {
-        std::lock_guard<std::mutex> lk(b->tmpl_mu);
-        for (int a = 0; a < 3; ++a) { b->lo[a] = lo[a]; b->hi[a] = hi[a]; }
-        b->bsphere_ready = false; b->bsphere[3] = -1.0f;
-        b->host_geometry = false; b->verts.clear();                       // (ensure_host_geometry fetches again)
-        b->tmpl = Bvh8(); b->tmpl_built = false; b->split_decided = false; // (rebuilt by the next build that wants them)
-        std::swap(old_tmpl, b->tmpl_dev); std::swap(old_split, b->split);
-        b->geometry_epoch++;
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const auto it = ctx->blas.find(blas);
+        if (it == ctx->blas.end()) return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_spheres: unknown BLAS handle 0x%llx", (unsigned long long)blas);
+        b = it->second;
     }
-    if (old_tmpl.d_nodes || old_split.d_nodes) {
-        // (a two-level build on another stream may still be copying from them)
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        for (BlasTree *tr : {&old_tmpl, &old_split}) for (void *p : {(void *)tr->d_nodes, (void *)tr->d_prims, (void *)tr->d_clip}) if (p) (void)hipFree(p);
-    }
-    return HRT_OK;
+    if (b->kind != kPrimKindSphere) return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_spheres: 0x%llx is a triangle BLAS", (unsigned long long)blas);
+    if (n_spheres != b->n_prims)
+        return fail(ctx, HRT_ERR_INVALID, "hrt_blas_update_spheres: n_spheres (%u) is not what the BLAS was built with (%u)", n_spheres, b->n_prims);
+    if (n_spheres && (!d_centers || !d_radii)) return fail(ctx, HRT_ERR_INVALID, "sphere arrays are NULL");
+    if ((reinterpret_cast<uintptr_t>(d_centers) & 3u) || (reinterpret_cast<uintptr_t>(d_radii) & 3u)) return fail(ctx, HRT_ERR_INVALID, "sphere arrays are not aligned for a float");
+    if (n_spheres == 0) return HRT_OK;
+    (void)hipSetDevice(ctx->device);
+    // (no pending by-primitive link of the denoiser can read a sphere BLAS: they link triangle BLASes only)
+    float lo[3], hi[3];
+    const ScratchArena arena = scratch_acquire(ctx, kBoundsScratchBytes);
+    const hipError_t e = gpu_blas_update_spheres(reinterpret_cast<const float *>(d_centers), d_radii, b->d_verts, n_spheres, lo, hi, arena.p, (hipStream_t)stream);
+    scratch_release(ctx, arena);
+    HIP_TRY(ctx, e);
+    return geometry_replaced(ctx, *b, lo, hi);
 }
 
 int hrt_blas_destroy(HrtContext *ctx, HrtTraversable blas) {
@@ -1369,7 +1400,7 @@ int hrt_tlas_update(HrtContext *ctx, HrtTraversable tlas, const HrtInstance *d_i
     if (ctx->capture.tlas == tlas) ctx->capture.valid = false;      // (the primary hits of the tree as it was: a refit keeps the generation)
     if (n != t->n_instances) return fail(ctx, HRT_ERR_INVALID, "update must keep the instance count (%u != %u)", n, t->n_instances);
     if (n && !d_instances) return fail(ctx, HRT_ERR_INVALID, "d_instances is NULL");
-    // (a BLAS of the tree has new vertices, hrt_blas_update_triangles: the refit picks them up where it can)
+    // (a BLAS of the tree has new vertices or spheres, hrt_blas_update_triangles / _spheres: the refit picks them up where it can)
     const GeometryChange geometry = geometry_change(ctx, *t);
     bool force_rebuild = geometry == GeometryChange::Rebuild, pick_up = geometry == GeometryChange::Refit;
     // (the first update after a build takes the synchronous path below, which checks that refit on the spot: see there)

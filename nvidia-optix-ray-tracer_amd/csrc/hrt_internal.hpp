@@ -50,7 +50,7 @@ struct Blas {
                                      // build and every refit derive the world-space records from it
                                      // (the caller may free its vertex buffer after the build, RendererMesh.cu:116)
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};   // object-space bounds
-    uint64_t geometry_epoch = 0;     // bumped by hrt_blas_update_triangles: a TLAS whose Tlas::blas_epoch differs still holds the geometry as it was
+    uint64_t geometry_epoch = 0;     // bumped by hrt_blas_update_triangles / _spheres: a TLAS whose Tlas::blas_epoch differs still holds the geometry as it was
     // object-space BVH8 of this geometry alone: the per-instance subtree of the trees over instances (built on first use)
     std::mutex tmpl_mu; bool tmpl_built = false; Bvh8 tmpl;
     BlasTree tmpl_dev;               // ... and its device copy: what a two-level TLAS copies in behind its top level

@@ -286,6 +286,11 @@ __device__ __forceinline__ PathStep path_finish(Lane &P, uint32_t (&px_chain)[4]
         const uint32_t inst = binst;
         const HitGroup hg = a.path.hitgroups[inst];
         const uint32_t program = a.path.inst_program[inst];
+        // A primary hit on a SPHERE seeds nothing: the seed bounds the next walk at bt on the promise that the ray is inside the record's padded
+        // box at bt, which the triangle test's bt keeps and the sphere test's does not -- its discriminant cancels (b^2 - a cc, each term
+        // ~|o - c|^2 |d|^2), so a sphere of radius 0.008 seen from 6 units away is hit up to 2e-4 in front of its box, the bounded walk culls
+        // the box and the repeat ray, the same ray, comes back a miss.  The next primary ray walks the launch's whole interval, like a first one.
+        if constexpr (V::kSeed && V::kSpheres) { if (P.px_depth == 1u && program < (uint32_t)kProgramTriangleRough) *seed = a.tmax; }
         V3 hp, nd;
         scatter_programs<V::kSpheres>(program, hg, o, d, bt, bu, bv, bprim, P.px_rng, hp, nd);
         px_chain[P.px_depth - 1u] = inst;

@@ -41,9 +41,11 @@ __device__ __forceinline__ void refit_record(const RefitArgs &a, size_t r, float
         rf[0] = v0[0]; rf[1] = v0[1]; rf[2] = v0[2];
         rf[4] = e1[0]; rf[5] = e1[1]; rf[6] = e1[2];
         rf[8] = e2[0]; rf[9] = e2[1]; rf[10] = e2[2];
-    } else {
-        const float c3[3] = {rf[0], rf[1], rf[2]};
-        sphere_world_bounds(c3, rf[4], m, ident, plo, phi);
+    } else {                                           // {cx, cy, cz, r} where the BLAS keeps it (hrt_blas_update_spheres moves it), laid out as k_emit_level lays it out
+        const float4 s4 = *(reinterpret_cast<const float4 *>(a.inst_src[inst]) + prim);
+        const float c3[3] = {s4.x, s4.y, s4.z};
+        rf[0] = c3[0]; rf[1] = c3[1]; rf[2] = c3[2]; rf[4] = s4.w;
+        sphere_world_bounds(c3, s4.w, m, ident, plo, phi);
     }
     if (kKeep) {
         if (a.inst_changed[inst] == 0u) {              // nothing of the instance has moved since the build: the box as built

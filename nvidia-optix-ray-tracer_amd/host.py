@@ -103,6 +103,7 @@ class Renderer:
         self.tlas = None
         self._built_blas = {}       # BLAS handle -> its normals: the BLASes build_tlas(vertices=...) made
         self._scene_blas = {}       # ... and load_scene's triangle BLASes (update_blas_vertices rewrites either in place)
+        self._scene_spheres = {}    # load_scene's sphere BLASes: handle -> (centres, radii), the buffers their records shade with (update_blas_spheres rewrites them in place)
         self._tlas_blas = {}        # TLAS handle -> those of them it was built over
         self._tlases = {}           # handle -> (host instance array, device instance array, count, SBT records): load_scene's and build_tlas's
         self.states = None
@@ -153,11 +154,18 @@ class Renderer:
                 h_rec[i].data.ptr0 = normals.data_ptr()
                 prog = PROGRAM_TRIANGLE_ROUGH if it["material"] == "rough" else PROGRAM_TRIANGLE_METAL
             else:
-                centers = self._dev(it["centers"])
-                radii = self._dev(it["radii"])
-                self._check(lib.hrt_blas_build_spheres(self.ctx, centers.data_ptr(), radii.data_ptr(), radii.shape[0], st,
-                                                       C.byref(handle)), "hrt_blas_build_spheres")
-                self._keep += [centers, radii]
+                key = it.get("shape")
+                if key is not None and ("spheres", key) in shared:
+                    handle.value, (centers, radii) = shared[("spheres", key)]
+                else:
+                    centers = self._dev(it["centers"])
+                    radii = self._dev(it["radii"])
+                    self._check(lib.hrt_blas_build_spheres(self.ctx, centers.data_ptr(), radii.data_ptr(), radii.shape[0], st,
+                                                           C.byref(handle)), "hrt_blas_build_spheres")
+                    self._keep += [centers, radii]
+                    self._scene_spheres[handle.value] = (centers, radii)
+                    if key is not None:
+                        shared[("spheres", key)] = (handle.value, (centers, radii))
                 h_rec[i].data.ptr0 = centers.data_ptr()
                 h_rec[i].data.ptr1 = radii.data_ptr()
                 prog = PROGRAM_SPHERE_ROUGH if it["material"] == "rough" else PROGRAM_SPHERE_METAL
@@ -291,6 +299,30 @@ class Renderer:
             if tuple(keep.shape) != (3 * v.shape[0], 3):
                 raise self._err(f"update_blas_vertices: the normals buffer of BLAS 0x{handle:x} holds {keep.shape[0] // 3} triangles")
             keep.copy_(self._dev(nrm.reshape(-1, 3)))      # in place: the records keep their pointer
+
+    def update_blas_spheres(self, handle_or_instance, centers, radii):
+        """hrt_blas_update_spheres: the sphere BLAS gets new object-space ``centers`` ((n, 3) float32) and ``radii`` ((n,) float32, as many
+        spheres as it was built with) in place, and the centres and radii buffers the renderer keeps for it -- what its instances' records
+        shade with -- are rewritten on the same stream.  ``handle_or_instance``: the handle of a sphere BLAS load_scene made, or (any other
+        number) the index of an instance of the current TLAS, whose BLAS is meant.  Does NOT update any TLAS: every TLAS over the BLAS
+        shows the old spheres until its next update_instances."""
+        handle = int(handle_or_instance)
+        if handle not in self._scene_spheres:
+            if self._n_inst is None or not 0 <= handle < self._n_inst:
+                raise self._err(f"update_blas_spheres: {handle} is neither a sphere BLAS of this renderer nor an instance of its TLAS")
+            handle = int(self._h_inst[handle].traversableHandle)
+        if handle not in self._scene_spheres:
+            raise self._err(f"update_blas_spheres: BLAS 0x{handle:x} is not a sphere BLAS of this renderer")
+        c = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        keep_c, keep_r = self._scene_spheres[handle]
+        if c.shape[0] != r.shape[0] or tuple(keep_c.shape) != c.shape:
+            raise self._err(f"update_blas_spheres: {c.shape[0]} centres and {r.shape[0]} radii for a BLAS of {keep_r.shape[0]} spheres")
+        d_c, d_r = self._dev(c), self._dev(r)
+        self._check(self.lib.hrt_blas_update_spheres(self.ctx, handle, d_c.data_ptr(), d_r.data_ptr(), d_r.shape[0], self._stream()),
+                    "hrt_blas_update_spheres")
+        keep_c.copy_(d_c)                                  # in place: the records keep their pointers
+        keep_r.copy_(d_r)
 
     def update_instances(self, transforms):
         """Per-frame instance update + updateIAS (src/Global/RendererMesh.cu:379-401)."""

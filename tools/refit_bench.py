@@ -89,6 +89,19 @@ def main():
             continue
         run("particles-%d" % n_p, sc, cached, min(a.frames, 5), "rebuild")
         run("particles-%d" % n_p, sc, cached, min(a.frames, 5), "rebuild-merged")
+    # mixed_test_scene's kind of scene with 10^5 spheres (radii scaled down so that it stays a cloud): the refit of sphere records, which
+    # reads a sphere's 16 bytes from its BLAS
+    sc = hrt.scenes.mixed_test_scene(2000, 100000, width=1200, height=800, spp=1)
+    for it in sc["instances"]:
+        if it["geometry"] == "spheres":
+            it["radii"] = (it["radii"] * np.float32(0.02)).astype(np.float32)
+    base_xf = [it["transform"] for it in sc["instances"]]
+    def mixed_poses(f, base_xf=base_xf):
+        out = [m.copy() for m in base_xf]
+        for m in out:
+            m[3] += 0.01 * f
+        return out
+    run("mixed-1e5-spheres", sc, mixed_poses, a.frames, "refit", a.async_update)
     # one big static instance that moves as a whole (C4 geometry)
     sc = hrt.scenes.soup_1m(1920, 1080, 1)
     base = sc["instances"][0]["transform"]
